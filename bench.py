@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: group-128 uint4 RTN quantization of a 4096x11008 fp32 weight on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the `roofline` of those
+steps; every other object of the line is null.  `--full` adds everything listed below (the other layouts and entry
+points, the whole-model and file runs, the searches, GPTQ, the CPU baseline, the checks against the reference's digests);
+the `--no-*` switches trim a `--full` run.  `--dump-outputs DIR` writes what the last timed step returned (rank 0) as
+float32 .npy files: `scales.npy`, `zero_points.npy` in full and `q_sample.npy`, a fixed sample (seed 0) of 2^23 of the
+quantized bytes (the whole array would be 90 MB as float32).  The inputs depend on the rank alone, so two builds run
+with the same arguments can be compared file for file.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment bench.py launches the N ranks ITSELF (a
 `python -m torch.distributed.run` child, started before this process touches a GPU); under torch.distributed.run it is
@@ -85,6 +93,20 @@ def moved_bytes(layout: str) -> int:
 
 def sha16(a) -> str:
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
+
+
+DUMP_Q_SAMPLES = 1 << 23            # 32 MB of float32 out of the 22.5 M (nbits) / 45 M (kn) quantized bytes
+
+
+def dump_outputs(out_dir: str, q, s, z, qparams_only: bool) -> None:
+    """`--dump-outputs`: the arrays the timed call returned, as float32 .npy files (exact: bytes and fp32 scales)."""
+    os.makedirs(out_dir, exist_ok=True)
+    if not qparams_only:
+        qh = q.cpu().numpy()
+        idx = np.sort(np.random.default_rng(0).choice(qh.size, min(DUMP_Q_SAMPLES, qh.size), replace=False))
+        np.save(os.path.join(out_dir, "q_sample.npy"), qh[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "scales.npy"), s.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "zero_points.npy"), z.cpu().numpy().astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------------ launch plumbing
@@ -655,6 +677,11 @@ def main() -> None:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--batch-extra", type=int, default=4,
                     help="also time oq_rtn_quantize_batched_f32 with this many matrices per launch (0/1: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (the objects listed in the module docstring); "
+                         "off: set up, warm up, time --steps launches, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned (rank 0) to DIR/*.npy as float32")
     ap.add_argument("--no-extras", action="store_true", help="time only the headline configuration (used under rocprofv3)")
     ap.add_argument("--no-gptq", action="store_true", help="skip the `gptq` object (configs 4 / 5)")
     ap.add_argument("--no-seam", action="store_true", help="skip the `seam` object")
@@ -678,6 +705,9 @@ def main() -> None:
     ap.add_argument("--selftest-backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--no-rccl-selftest", action="store_true", help="skip the `rccl_selftest` object (a child process running --nccl-selftest)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
+    extras = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:          # before anything touches a GPU
         raise SystemExit(self_launch(os.path.abspath(__file__), args.gpus, sys.argv[1:]))
@@ -690,7 +720,7 @@ def main() -> None:
     # on cuda:0 and every kind of exchange the N-rank path issues.  Never the measured thing; a failure or a
     # hang of the child is reported inside the object and the headline still goes out.
     rccl_selftest = None
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_extras and not args.no_rccl_selftest and not args.qparams_only:
+    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and extras and not args.no_rccl_selftest and not args.qparams_only:
         rccl_selftest = run_selftest_child()
 
     import torch
@@ -760,12 +790,14 @@ def main() -> None:
     fence()
     wall = time.perf_counter() - t0
     dev_ms = ev0.elapsed_time(ev1)            # HIP events on the launch stream: device time of the K launches
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *outs[(args.steps - 1) % len(outs)], args.qparams_only)
 
     # the same launches with outputs that do not fit the Infinity Cache: `--rotate` output sets are 96 MB and
     # stay on chip from one step to the next, as the output of ONE quantized matrix does in real use; with `--rotate-out`
     # sets every output byte of a step is really written to HBM before its buffer comes round again
     streamed_us = None
-    if world == 1 and not args.no_extras and not args.qparams_only and args.rotate_out > len(outs):
+    if world == 1 and extras and not args.qparams_only and args.rotate_out > len(outs):
         more = [(torch.empty(q_elems, dtype=torch.uint8, device=dev), torch.empty(groups, dtype=torch.float32, device=dev),
                  torch.empty(groups, dtype=torch.uint8, device=dev)) for _ in range(args.rotate_out - len(outs))]
         sets = [(C.c_void_p(q.data_ptr()), C.c_void_p(sc.data_ptr()), C.c_void_p(z.data_ptr())) for (q, sc, z) in list(outs) + more]
@@ -790,7 +822,7 @@ def main() -> None:
 
     # per-launch distribution (median, p10 / p90): 100 more launches, one event pair each
     pct = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(100)]
         for i, (a, b) in enumerate(evs):
             a.record()
@@ -803,7 +835,7 @@ def main() -> None:
     # the same launches, many of them: the driver's 20 steps are 0.8 ms of device time, over before the GPU's clocks have
     # settled; 400 launches (16 ms) show what a caller that quantizes a model's worth of matrices one by one sees per launch
     sustained_us = None
-    if world == 1 and not args.no_extras and not args.qparams_only:
+    if world == 1 and extras and not args.qparams_only:
         for i in range(20):
             step(i)
         torch.cuda.synchronize()
@@ -818,7 +850,7 @@ def main() -> None:
     # the other output layout, shorter run, same buffers (reported next to the headline, never as `value`)
     other = "kn" if args.layout == "nbits" else "nbits"
     other_us = None
-    if world == 1 and not args.qparams_only and not args.no_extras:
+    if world == 1 and not args.qparams_only and extras:
         olayout = L.OQ_LAYOUT_KN if other == "kn" else L.OQ_LAYOUT_NBITS
         oq = torch.empty(K_DIM * N_DIM if other == "kn" else K_DIM * N_DIM // 2, dtype=torch.uint8, device=dev)
         oqp = C.c_void_p(oq.data_ptr())
@@ -859,7 +891,7 @@ def main() -> None:
     # the packed [K, N/2] layout of the int4 configurations (configs 4 / 5 are QInt4: not MatMulNBits-eligible, the reference
     # serialises their [K, N] integers two per byte, core/_pack.py:8-22): written by the fused kernel's epilogue
     packed_kn = None
-    if world == 1 and not args.qparams_only and not args.no_extras and not args.symmetric:
+    if world == 1 and not args.qparams_only and extras and not args.symmetric:
         pq = torch.empty(K_DIM * N_DIM // 2, dtype=torch.uint8, device=dev)
         pz = torch.empty(groups, dtype=torch.int8, device=dev)
         pqp, pzp = C.c_void_p(pq.data_ptr()), C.c_void_p(pz.data_ptr())
@@ -931,7 +963,7 @@ def main() -> None:
 
     # batched entry point: `--batch-extra` matrices per launch (stacked weights); reported separately
     batched = None
-    if world == 1 and not args.qparams_only and not args.no_extras and args.batch_extra > 1:
+    if world == 1 and not args.qparams_only and extras and args.batch_extra > 1:
         nb = args.batch_extra
         wb = torch.stack([w_src] * nb).contiguous()
         qb = torch.empty(nb * q_elems, dtype=torch.uint8, device=dev)
@@ -965,12 +997,12 @@ def main() -> None:
     # a whole model's weights in one call: Llama-2-7B's 224 MatMul weights resident in HBM (25.9 GB fp32), uint4 g128, through
     # oq_rtn_quantize_ptrs_f32 -- one launch per distinct shape (3), a device table of pointers instead of a per-node loop
     model_rtn = None
-    if world == 1 and not args.qparams_only and not args.no_extras and not args.no_model_rtn and not args.symmetric:
+    if world == 1 and not args.qparams_only and extras and not args.no_model_rtn and not args.symmetric:
         model_rtn = model_rtn_bench(dev, args.layout, outs[0], w_src)
 
     # the reference's DEFAULT strategies (QWeightArgs(): int8, group_size=None -> per tensor; and per channel) on the same matrix
     strategies = None
-    if world == 1 and not args.qparams_only and not args.no_extras and not args.symmetric:
+    if world == 1 and not args.qparams_only and extras and not args.symmetric:
         strategies = strategies_bench(dev, ws, rank)
 
     t = torch.tensor([wall, dev_ms], dtype=torch.float64, device=dev)
@@ -984,7 +1016,7 @@ def main() -> None:
 
     # ---- N > 1: every rank's last result to rank 0 through the RCCL gather north_star names
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         from onnx_quantize_amd.sharding import LayerSpec, gather_device_results
 
         specs = [LayerSpec(f"rank{r}.w", K_DIM, N_DIM) for r in range(world)]
@@ -1005,7 +1037,7 @@ def main() -> None:
     # ---- verify rank 0's last outputs against the reference digests (asymmetric / symmetric KAT2)
     verified = None
     digest = None
-    if rank == 0:
+    if rank == 0 and args.full:
         with open(os.path.join(ROOT, "tests", "golden", "digests.json")) as f:
             digests = json.load(f)
         digest = digests["config2_sym" if args.symmetric else "config2_asym"]
@@ -1025,28 +1057,28 @@ def main() -> None:
 
     # ---- the seam (host to host) on the same configuration, rank 0 at N = 1
     seam = None
-    if world == 1 and not args.no_seam and not args.no_extras and not args.symmetric:
+    if world == 1 and not args.no_seam and extras and not args.symmetric:
         seam = seam_bench(w_host, digests["config2_asym"])
 
     searches = None
-    if world == 1 and not args.no_awq and not args.no_extras and not args.symmetric:
+    if world == 1 and not args.no_awq and extras and not args.symmetric:
         searches = search_bench(dev, w_src)
     del ws, outs, calls, w_src
     torch.cuda.empty_cache()
     # ---- config 3 stand-in: min-max calibration of a gemma-3-270m-shaped activation population (rank 0 at N = 1)
     calibration = None
-    if world == 1 and not args.no_calibration and not args.no_extras:
+    if world == 1 and not args.no_calibration and extras:
         import bench_calib
 
         calibration = bench_calib.run(dev, cpu=not args.no_cpu_baseline)
         torch.cuda.empty_cache()
     awq = None
-    if world == 1 and not args.no_awq and not args.no_extras:
+    if world == 1 and not args.no_awq and extras:
         awq = awq_bench(dev)
         torch.cuda.empty_cache()
     # ---- the file path: an ONNX file of two Llama-2-7B-width decoder layers -> quantize_file -> an ONNX file
     model_file = None
-    if world == 1 and not args.no_model_file and not args.no_extras:
+    if world == 1 and not args.no_model_file and extras:
         import bench_model
 
         try:
@@ -1062,7 +1094,7 @@ def main() -> None:
     # `parity`, the default; and `corrected`), phases apart, one weight of each file verified against the per-layer device path.
     # PCIe- and file-inclusive: never `value`.
     model_file_7b = None
-    if world == 1 and not args.no_model_file and not args.no_model_file_7b and not args.no_extras:
+    if world == 1 and not args.no_model_file and not args.no_model_file_7b and extras:
         import bench_model
 
         try:
@@ -1079,7 +1111,7 @@ def main() -> None:
         torch.cuda.empty_cache()
     # ---- configs 4 / 5: GPTQ of a Llama-2-7B-shaped model from the same run (all ranks take part)
     gptq = None
-    if not args.no_gptq and not args.no_extras:
+    if not args.no_gptq and extras:
         import bench_gptq
 
         gargs = bench_gptq.build_parser().parse_args(["--gpus", str(world), "--layers", str(args.gptq_layers),
@@ -1166,7 +1198,7 @@ def main() -> None:
     }
     if os.environ.get("OQ_BENCH_REHEARSAL", "0") == "1":
         result["rehearsal"] = "ranks share one GPU, collectives on gloo: the multi-rank code path executed, NOT a scaling measurement"
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         base, (cq, cs, cz) = cpu_baseline(w_host)
         base["digest_ok"] = bool(sha16(cq) == digests["config2_asym"]["q_sha"] and sha16(cs) == digests["config2_asym"]["s_sha"])
         result["cpu_baseline"] = base

@@ -9,7 +9,7 @@ for setting in "$@"; do
     envs=""
     for kv in $setting; do envs="$envs OQ_RTN_$kv"; done
     log="$out/run_$i.json"
-    env $envs python bench.py --no-extras --no-cpu-baseline --steps 300 --warmup 30 > "$log" 2> "$out/run_$i.err" || { echo "FAILED: $setting"; tail -5 "$out/run_$i.err"; }
+    env $envs python bench.py --full --no-extras --no-cpu-baseline --steps 300 --warmup 30 > "$log" 2> "$out/run_$i.err" || { echo "FAILED: $setting"; tail -5 "$out/run_$i.err"; }
     python - "$log" "$setting" <<'PY'
 import json, sys
 try:

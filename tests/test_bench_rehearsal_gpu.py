@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_runs_the_multi_rank_path_on_one_gpu(ranks):
     env = dict(os.environ, OQ_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29650 + ranks))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
-                        "--gptq-layers", "3"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--gptq-layers", "3"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == ranks and "rehearsal" in line
@@ -37,7 +37,7 @@ def test_bench_gptq_padded_gather_switch_on_one_gpu():
     """`--gather padded`: the fallback of the streamed point-to-point gather -- one padded collective gather
     after the last kernel -- through the same two-rank run; what arrives on rank 0 equals what the senders hold."""
     env = dict(os.environ, OQ_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29661")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gptq-layers", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--gptq-layers", "2",
                         "--gptq-gather", "padded", "--gptq-extra-passes", "", "--no-model-rtn", "--no-awq", "--no-calibration", "--no-seam"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
