@@ -10,12 +10,9 @@
 // fp32 GEMMs of 137 GFLOP).
 #include "gemm_tn.hpp"
 #include "row_params.hpp"
+#include "rtn_internal.hpp"
 
 namespace oq {
-
-int32_t rtn_impl(const float* W, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size, int32_t symmetric,
-                 int32_t reduce_range, float clip_ratio, int32_t mse, void* q_out, float* scale_out, void* zp_out, int32_t layout, void* workspace,
-                 size_t workspace_bytes, void* stream, bool emit_q);
 
 constexpr int kAwqMaxGrid = 64;
 constexpr int kColChunks = 64;   // row chunks of the column reductions
@@ -648,8 +645,8 @@ static int32_t candidate_loss(const AwqWs& w, const float* W, int64_t ldw, const
             Wq = w.Ws;
             ldq = N;
         }
-        st = rtn_impl(Wq, K, N, ldq, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, 0, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN, w.rtn_ws,
-                      w.rtn_ws_bytes, s, true);
+        st = rtn_impl(RtnCall{Wq, K, N, ldq, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, 0, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN,
+                              w.rtn_ws, w.rtn_ws_bytes, s});
         if (st != OQ_OK) return st;
         ParamIndex pi;
         param_index(strategy, K, g, &pi);

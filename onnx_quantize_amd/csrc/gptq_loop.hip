@@ -12,6 +12,7 @@
 //   CORRECTED  U[i1+i][i1+j]  (row of the upper factor right of the diagonal: what GPTQ intends)
 // The batch update uses U[i2:, i1:i2] (PARITY: an all-zero block, the GEMM is skipped) or U[i1:i2, i2:]^T.
 #include "gemm_tn.hpp"
+#include "rtn_internal.hpp"
 
 #include <cstdlib>
 #include <utility>
@@ -693,10 +694,6 @@ __global__ __launch_bounds__(256) void gptq_parity_kernel(const LoopArgs a, int6
     }
 }
 
-int32_t rtn_impl(const float* W, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size,
-                 int32_t symmetric, int32_t reduce_range, float clip_ratio, int32_t mse, void* q_out, float* scale_out, void* zp_out,
-                 int32_t layout, void* workspace, size_t workspace_bytes, void* stream, bool emit_q);
-
 }  // namespace oq
 
 extern "C" {
@@ -854,8 +851,8 @@ int32_t oq_gptq_loop_f32(float* W, int64_t K, int64_t N, const float* U, int32_t
                 for (int64_t gi = first; gi * a.g < i1 + count; ++gi, ++slot) {
                     const int64_t r0 = gi * a.g;
                     const int64_t rows = (r0 + a.g <= K) ? a.g : K - r0;
-                    st = rtn_impl(W + r0 * N, rows, N, N, qtype, OQ_CHANNEL, -1, symmetric, reduce_range, clip_ratio, 1, nullptr,
-                                  pre_scale + slot * N, pre_zp + slot * N, OQ_LAYOUT_KN, mse_ws, mse_ws_bytes, stream, false);
+                    st = rtn_impl(RtnCall{W + r0 * N, rows, N, N, qtype, OQ_CHANNEL, -1, symmetric, reduce_range, clip_ratio, 1, nullptr,
+                                          pre_scale + slot * N, pre_zp + slot * N, OQ_LAYOUT_KN, mse_ws, mse_ws_bytes, stream, false});
                     if (st != OQ_OK) return st;
                 }
                 a.pre_scale = pre_scale; a.pre_zp = pre_zp; a.pre_first_group = first;

@@ -3,7 +3,7 @@
 // held in registers, reduced down the K axis per column (lane-local, then across waves through a
 // small LDS exchange), turned into (scale, zero point) in registers and quantized from the same
 // registers.  Nothing is reshaped into a GEMM and no transposed copy (utils.py:24) is ever made.
-#include "oq_common.hpp"
+#include "rtn_internal.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -172,10 +172,6 @@ __device__ __forceinline__ void tile_of_block(const RtnArgs& a, uint32_t bid, ui
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused one-pass kernel.  One block = GPB groups (stacked along K) x 256 columns; one group =
-// WPG waves x RPW rows.  Registers per lane: RPW x 4 fp32 of W.
-// ---------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------------
 // The [K/g, N] -> [N, K/g] transposition of the staged parameters INSIDE the fused launch (round 6; template mode TR, stateful entry
 // point only, packed nibbles of up to 32 k-groups: see the host's rule).  The separate transpose launch is 5 us of which the kernel
 // itself needs 1.5 (rocprofv3: 43.0 + 5.0 us against 43.2-44.5 us per call).
@@ -184,15 +180,16 @@ __device__ __forceinline__ void tile_of_block(const RtnArgs& a, uint32_t bid, ui
 // and a pair word never is, so every WORD says by itself whether it has been written.  `ncol_tiles` blocks are appended to the
 // grid; they are dispatched behind the last main block, into slots no main block is waiting for, and each takes one column tile:
 // poll ONE word of the tile's last k-group until it is there (the k-groups of a column tile finish roughly in order), read all of
-// the tile's words with `sc1` loads -- re-reading the few that are not written yet --, transpose them through the 16 KB of LDS the
-// fold uses, store whole 128-byte lines of the result, and put the zeros back (the state is what the next call finds).
+// the tile's words with `sc1` loads -- re-reading the few that are not written yet --, transpose them through 20 KB of LDS of their
+// own (`s_tr_f`, `s_tr_z`), store whole 128-byte lines of the result, and put the zeros back (the state is what the next call finds).
 // Also built: the transposition by the block of each column tile's LAST k-group after its own stores (no appended blocks) --
 // bit-exact, slower than the second launch (packed 44.5 -> 45.0 us, bytes 45.5 -> 48.9): the last round of blocks then carries
 // the read-back's round trips on top of its own work.
-// Forward progress: a main block never waits; an appended block waits only for main blocks of its own launch, and there are at
-// most `ncol_tiles` of them -- a few dozen of the device's workgroup slots -- so the blocks they wait for always find a slot whatever
-// the dispatch order.  (Launches of DIFFERENT streams could in principle fill the device with waiting blocks: the host orders them
-// through the ticket chain of rtn_resident.hip.)
+// Forward progress: a main block never waits; an appended block waits only for main blocks of its own launch.  The host takes this
+// path only when the ceil(N / 128) appended blocks fill at most 3/4 of the workgroup slots the device holds of this build (CUs x the
+// occupancy query; the rule of the ticketed kernels), so the blocks they wait for find a slot whatever the dispatch order; wider
+// calls stage the parameters for the transpose launch instead.  (Launches of DIFFERENT streams could in principle fill the device
+// with waiting blocks: the host orders them through the ticket chain of rtn_resident.hip.)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool lab_spin_over(uint32_t spins) {
 #ifdef OQ_SPIN_LIMIT      /* lab builds: give up instead of hanging the box (the result is garbage then) */
@@ -287,6 +284,8 @@ __device__ __forceinline__ void transposer_block(const RtnArgs& a, uint32_t part
     }
 }
 
+// Fused one-pass kernel.  One block = GPB groups (stacked along K) x 256 columns; one group = WPG waves x RPW rows.  Registers per
+// lane: RPW x 4 fp32 of W.
 template <int RPW, bool VEC4, bool EMIT_Q, bool NT = false, bool TR = false>      // TR: parameters staged in the caller's state and transposed inside the launch
 __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArgs a_in) {
     __shared__ float4 s_mn[kMaxWaves][kWave];
@@ -499,7 +498,6 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
     }
 #endif
 
-    do {      // the layout's stores; `break` instead of `return`: every wave reaches the tail below
     if (a.layout == OQ_LAYOUT_KN) {
         const uint32_t flip = bias ? 0x80808080u : 0u;
         if constexpr (VEC4) {
@@ -559,7 +557,7 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
                         else *reinterpret_cast<uint32_t*>(dst) = out;
                     }
                 }
-                break;
+                return;
             }
         }
         if (col_ok[0]) {
@@ -631,7 +629,7 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
                     }
                     if (col < a.N) *reinterpret_cast<uint4*>(a.q + (col * a.kgroups + kg0) * blob + part * 16) = t;
                 }
-                break;
+                return;
             }
         }
 #pragma unroll
@@ -671,7 +669,6 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
             }
         }
     }
-    } while (false);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1374,7 +1371,7 @@ __global__ __launch_bounds__(256) void transpose_qparams(const float* scale_t, c
     }
 }
 
-// Experiment knobs: speed only, every setting produces the same bytes (-1 = the tuned default).
+// Experiment knobs: speed only, every setting produces the same bytes (-1 = the tuned default).  Read once per process (rtn_impl).
 struct Tuning {
     int order = -1, gk = -1, nt = -1, stage = -1, stage_q = -1, wavek = -1, gpb = -1, wpb = -1, wps = -1, resident = -1, xg = -1;
     static int env_int(const char* name) { const char* v = getenv(name); return v ? atoi(v) : -1; }
@@ -1393,10 +1390,12 @@ struct Tuning {
         t.xg = env_int("OQ_RTN_XG");            // order 2: log2 of the neighbouring column tiles one XCD owns (speed only)
         return t;
     }
+    int nt_bits() const { return (nt >= 0 ? nt : 1) & kNtMask; }
 };
 
 // ------------------------------------------------------------------------------------ dispatch
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static int32_t zp_signed(int32_t qtype) { return (qtype == OQ_INT4 || qtype == OQ_INT8) ? 1 : 0; }
 
 // Rows per wave / waves per group for the fused kernel; false when the group is too tall.
 static bool fused_shape(int64_t g, int* rpw, int* wpg) {
@@ -1415,6 +1414,13 @@ static bool fused_shape(int64_t g, int* rpw, int* wpg) {
     return false;
 }
 
+// Shapes the in-launch transposition holds (the fused kernel's TR build: 16 rows per wave, eight waves per group, whole granules of
+// four k-groups and four columns).  oq_rtn_state_bytes sizes the state by it; the per-call conditions are the fused route's.
+static bool in_launch_shape(int64_t K, int64_t N, int64_t g) {
+    int rpw = 0, wpg = 0;
+    return fused_shape(g, &rpw, &wpg) && rpw == 16 && wpg == kMaxWaves && (K / g) % 4 == 0 && N % 4 == 0;
+}
+
 // Fills the id-division constants of the chosen block order; ids beyond the fast-division range use order 0.
 static void set_block_order(RtnArgs& a) {
     if (a.gk < 1) a.gk = 1;
@@ -1426,7 +1432,7 @@ static void set_block_order(RtnArgs& a) {
 }
 
 template <bool VEC4, bool EMIT_Q>
-static void launch_fused(int rpw, const RtnArgs& a, dim3 grid, dim3 block, hipStream_t s) {
+static void launch_fused_kernel(int rpw, const RtnArgs& a, dim3 grid, dim3 block, hipStream_t s) {
     switch (rpw) {
         case 1: hipLaunchKernelGGL((rtn_group_fused<1, VEC4, EMIT_Q>), grid, block, 0, s, a); break;
         case 2: hipLaunchKernelGGL((rtn_group_fused<2, VEC4, EMIT_Q>), grid, block, 0, s, a); break;
@@ -1446,6 +1452,9 @@ static void launch_fused(int rpw, const RtnArgs& a, dim3 grid, dim3 block, hipSt
         default: hipLaunchKernelGGL((rtn_group_fused<32, VEC4, EMIT_Q>), grid, block, 0, s, a); break;
     }
 }
+
+template <bool NT>
+static const void* tr_build() { return reinterpret_cast<const void*>(rtn_group_fused<16, true, true, NT, true>); }
 
 // the zeroed state of the in-launch transposition: [kgroups, N] fp32 scales + one 8-byte {four zero points, marker} granule per four columns
 static size_t fused_state_bytes(int64_t K, int64_t N, int64_t g) {
@@ -1476,28 +1485,6 @@ static int32_t resolve_group(int32_t strategy, int64_t K, int64_t group_size, in
     }
     return OQ_OK;
 }
-
-int32_t rtn_impl(const float* W, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
-                 int64_t group_size, int32_t symmetric, int32_t reduce_range, float clip_ratio, int32_t mse,
-                 void* q_out, float* scale_out, void* zp_out, int32_t layout, void* workspace,
-                 size_t workspace_bytes, void* stream, bool emit_q);
-
-}  // namespace oq
-
-// MSE search lives in rtn_mse.hip, the one-read channel / tensor kernels in rtn_resident.hip
-namespace oq {
-bool rtn_resident_eligible(int64_t K, int64_t N, int64_t ldw, const float* W, const void* q, int32_t strategy, int64_t g, int32_t layout,
-                           bool emit_q, size_t workspace_bytes);
-bool rtn_stream_is_capturing(hipStream_t s);
-int32_t ticket_chain_begin(hipStream_t s);
-void ticket_chain_end(hipStream_t s);
-int32_t rtn_resident_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g, uint8_t* q,
-                          float* scale, uint8_t* zp, int32_t layout, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state);
-size_t rtn_resident_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g);
-int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy,
-                     int64_t g, void* q_out, float* scale_out, void* zp_out, int32_t zp_signed, void* workspace,
-                     size_t workspace_bytes, hipStream_t s, bool emit_q);
-size_t rtn_mse_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g);
 
 // Pass 3 of the two-pass path (also the final pass of the MSE search): K1 with stored parameters.
 int32_t launch_quantize_kn(const float* W, int64_t K, int64_t N, int64_t ldw, int64_t g, int64_t kgroups, const float* scale,
@@ -1539,143 +1526,83 @@ static int64_t matrices_per_launch(int64_t K, int64_t N, int64_t count) {
     return m < count ? m : count;
 }
 
-// Strided batch of equally shaped matrices for the fused group kernel (set by oq_rtn_quantize_batched_f32 around
-// its call of rtn_impl; 1 matrix otherwise).
-struct BatchCtx { int64_t count = 1, w_stride = 0, q_stride = 0; const RtnPtrs* table = nullptr; };
-static thread_local BatchCtx g_batch;
-// oq_rtn_quantize_stateful_f32: the caller's zeroed, self-cleaning state for the one-read channel / tensor kernels
-struct StateCtx { void* state = nullptr; size_t bytes = 0; };
-static thread_local StateCtx g_state;
+// What the checks of a call derive from it, read by every route
+struct RtnShape {
+    QGrid grid;
+    int64_t g, kgroups;
+    bool vec4;           // 16-byte column loads of W (and 4-byte aligned q)
+    bool fused;          // a group the fused kernel holds: rpw rows per wave x wpg waves
+    int rpw = 0, wpg = 0;
+};
 
-int32_t rtn_impl(const float* W, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
-                 int64_t group_size, int32_t symmetric, int32_t reduce_range, float clip_ratio, int32_t mse,
-                 void* q_out, float* scale_out, void* zp_out, int32_t layout, void* workspace,
-                 size_t workspace_bytes, void* stream, bool emit_q) {
-    OQ_REQUIRE(W && scale_out && zp_out && (q_out || !emit_q), OQ_ERR_INVALID_ARGUMENT, "rtn: null pointer argument");
+// (a) Every argument check of a call, before any HIP call (tests/test_hostile_arguments.py runs them without a GPU).
+static int32_t check_call(const RtnCall& c, RtnShape& sh) {
+    const int64_t K = c.K, N = c.N, ldw = c.ldw;
+    OQ_REQUIRE(c.W && c.scale && c.zp && (c.q || !c.emit_q), OQ_ERR_INVALID_ARGUMENT, "rtn: null pointer argument");
     OQ_REQUIRE(K > 0 && N > 0 && ldw >= N, OQ_ERR_INVALID_ARGUMENT, "rtn: bad shape K=%lld N=%lld ldw=%lld",
                (long long)K, (long long)N, (long long)ldw);
     OQ_REQUIRE(matrix_ok(K, N, ldw), OQ_ERR_UNSUPPORTED, "rtn: matrix too large (K=%lld N=%lld ldw=%lld)", (long long)K, (long long)N, (long long)ldw);
-    OQ_REQUIRE(clip_ratio > 0.0f && clip_ratio <= 1.0f, OQ_ERR_INVALID_ARGUMENT,
-               "clip_ratio must be in (0.0, 1.0], got %g", clip_ratio);
-    OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS || layout == OQ_LAYOUT_KN_PACKED4, OQ_ERR_INVALID_ARGUMENT,
-               "rtn: bad layout %d", layout);
-    QGrid grid;
-    int32_t st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &grid);
+    OQ_REQUIRE(c.clip_ratio > 0.0f && c.clip_ratio <= 1.0f, OQ_ERR_INVALID_ARGUMENT,
+               "clip_ratio must be in (0.0, 1.0], got %g", c.clip_ratio);
+    OQ_REQUIRE(c.layout == OQ_LAYOUT_KN || c.layout == OQ_LAYOUT_NBITS || c.layout == OQ_LAYOUT_KN_PACKED4, OQ_ERR_INVALID_ARGUMENT,
+               "rtn: bad layout %d", c.layout);
+    int32_t st = make_grid(c.qtype, c.symmetric, c.reduce_range, c.clip_ratio, &sh.grid);
     if (st != OQ_OK) return st;
-    int64_t g;
-    st = resolve_group(strategy, K, group_size, &g);
+    st = resolve_group(c.strategy, K, c.group_size, &sh.g);
     if (st != OQ_OK) return st;
-    hipStream_t s = as_stream(stream);
-    const int32_t zp_signed = (qtype == OQ_INT4 || qtype == OQ_INT8) ? 1 : 0;
-    uint8_t* q8 = static_cast<uint8_t*>(q_out);
-    uint8_t* zp8 = static_cast<uint8_t*>(zp_out);
-
-    if (layout == OQ_LAYOUT_KN_PACKED4) {
+    const int64_t g = sh.g;
+    sh.kgroups = K / g;
+    sh.fused = c.strategy == OQ_GROUP && fused_shape(g, &sh.rpw, &sh.wpg);
+    sh.vec4 = (N % 4 == 0) && (ldw % 4 == 0) && aligned16(c.W) && (!c.emit_q || (reinterpret_cast<uintptr_t>(c.q) & 3u) == 0);
+    if (c.layout == OQ_LAYOUT_KN_PACKED4) {
         // two columns per byte, written by the fused group kernel's epilogue; everything else is refused loudly, never routed
         // through an unpacked result + a second launch
-        int rpw_p = 0, wpg_p = 0;
-        OQ_REQUIRE(emit_q && grid.bits == 4 && strategy == OQ_GROUP && K % g == 0 && fused_shape(g, &rpw_p, &wpg_p) && !mse, OQ_ERR_UNSUPPORTED,
+        OQ_REQUIRE(c.emit_q && sh.grid.bits == 4 && sh.fused && K % g == 0 && !c.mse, OQ_ERR_UNSUPPORTED,
                    "KN_PACKED4 layout needs a 4-bit type, the group strategy with K %% group_size == 0 and group_size <= 256, no mse");
-        OQ_REQUIRE(N % 4 == 0 && ldw % 4 == 0 && aligned16(W) && (reinterpret_cast<uintptr_t>(q_out) & 3u) == 0, OQ_ERR_UNSUPPORTED,
+        OQ_REQUIRE(N % 4 == 0 && ldw % 4 == 0 && aligned16(c.W) && (reinterpret_cast<uintptr_t>(c.q) & 3u) == 0, OQ_ERR_UNSUPPORTED,
                    "KN_PACKED4 layout needs N %% 4 == 0, ldw %% 4 == 0, a 16-byte aligned W and a 4-byte aligned output");
     }
-    if (strategy == OQ_GROUP && K % g != 0) {
+    if (c.strategy == OQ_GROUP && K % g != 0) {   // the flat straddling groups: nothing below applies
         OQ_REQUIRE((K * N) % g == 0, OQ_ERR_INVALID_ARGUMENT,
                    "cannot reshape array of size %lld into rows of %lld", (long long)(K * N), (long long)g);
-        OQ_REQUIRE(!mse, OQ_ERR_UNSUPPORTED, "mse with groups that straddle columns (K %% group_size != 0) is not supported");
-        OQ_REQUIRE(layout == OQ_LAYOUT_KN, OQ_ERR_UNSUPPORTED, "NBITS layout needs K %% group_size == 0");
-        const int64_t ngroups = K * N / g;
-        hipLaunchKernelGGL(rtn_flat_groups, dim3(static_cast<uint32_t>(ceil_div(ngroups, 4))), dim3(256), 0, s, W, K, N,
-                           ldw, g, ngroups, grid, emit_q ? q8 : nullptr, scale_out, zp8);
-        return check_launch("rtn_flat_groups");
+        OQ_REQUIRE(!c.mse, OQ_ERR_UNSUPPORTED, "mse with groups that straddle columns (K %% group_size != 0) is not supported");
+        OQ_REQUIRE(c.layout == OQ_LAYOUT_KN, OQ_ERR_UNSUPPORTED, "NBITS layout needs K %% group_size == 0");
+        return OQ_OK;
     }
-
-    if (mse) {
-        OQ_REQUIRE(layout == OQ_LAYOUT_KN, OQ_ERR_UNSUPPORTED, "NBITS layout with mse is not supported");
-        return rtn_mse_impl(W, K, N, ldw, grid, strategy, g, q_out, scale_out, zp_out, zp_signed, workspace,
-                            workspace_bytes, s, emit_q);
+    if (c.mse) {
+        OQ_REQUIRE(c.layout == OQ_LAYOUT_KN, OQ_ERR_UNSUPPORTED, "NBITS layout with mse is not supported");
+        return OQ_OK;
     }
-
-    const bool vec4 = (N % 4 == 0) && (ldw % 4 == 0) && aligned16(W) && (!emit_q || (reinterpret_cast<uintptr_t>(q_out) & 3u) == 0);
-    const int64_t kgroups = K / g;
-    int rpw = 0, wpg = 0;
-    const bool fused = strategy == OQ_GROUP && fused_shape(g, &rpw, &wpg);
-    if (layout == OQ_LAYOUT_NBITS) {
-        OQ_REQUIRE(strategy == OQ_GROUP && emit_q, OQ_ERR_UNSUPPORTED, "NBITS layout needs the group strategy");
-        OQ_REQUIRE(g % 16 == 0 && aligned16(q_out), OQ_ERR_UNSUPPORTED,
+    if (c.layout == OQ_LAYOUT_NBITS) {
+        OQ_REQUIRE(c.strategy == OQ_GROUP && c.emit_q, OQ_ERR_UNSUPPORTED, "NBITS layout needs the group strategy");
+        OQ_REQUIRE(g % 16 == 0 && aligned16(c.q), OQ_ERR_UNSUPPORTED,
                    "NBITS layout needs group_size %% 16 == 0 and a 16-byte aligned output");
     }
+    OQ_REQUIRE(c.batch == 1 || sh.fused, OQ_ERR_UNSUPPORTED, "batched call needs the fused group path");
+    return OQ_OK;
+}
 
+// (b) Which kernels take a call.  Speed only, except where a route does not hold the call.
+enum class Route { FlatGroups, Mse, Wave, Fused, Ticketed, ThreeLaunch };
+struct RtnPlan {
+    Route route;
+    bool staged = false;      // Fused: parameters staged [K/g, N] in the workspace, transposed by a second launch ...
+    bool in_launch = false;   // ... or staged in the caller's state and transposed inside the launch
+    bool use_state = false;   // Ticketed: the caller's zeroed state instead of the workspace
+};
+
+static bool in_launch_fits(int64_t N, bool nt);
+
+static RtnPlan plan_route(const RtnCall& c, const RtnShape& sh, const Tuning& tune, hipStream_t s) {
+    const int64_t K = c.K, N = c.N, g = sh.g, kgroups = sh.kgroups;
+    if (c.strategy == OQ_GROUP && K % g != 0) return {Route::FlatGroups};
+    if (c.mse) return {Route::Mse};
     // MatMulNBits blob with a group of 32 / 64 / 128 rows: wave-owns-group kernel (no LDS, no barrier)
-    {
-        static const Tuning tw = Tuning::from_env();
-        const bool wave_ok = strategy == OQ_GROUP && layout == OQ_LAYOUT_NBITS && vec4 && (g == 32 || g == 64 || g == 128) && tw.wavek != 0 &&
-                             ldw < (1 << 22);   // 32-bit lane offsets
-        if (wave_ok) {
-            OQ_REQUIRE(emit_q && aligned16(q_out), OQ_ERR_UNSUPPORTED, "NBITS layout needs a 16-byte aligned output");
-            RtnArgs a;
-            a.W = W; a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = kgroups;
-            a.q = q8; a.scale = scale_out; a.zp = zp8; a.grid = grid; a.layout = layout;
-            a.scale_t = nullptr; a.zp_t = nullptr; a.wpg = 1; a.stage_q = 0; a.pair_owner = 0;
-            a.tr_scale = nullptr; a.tr_zp = nullptr;
-            const int64_t batch = g_batch.count;
-            a.w_stride = g_batch.w_stride; a.q_stride = g_batch.q_stride; a.p_stride = N * kgroups; a.table = g_batch.table;
-            const int lpr = static_cast<int>(1024 / g);
-            int wpb = tw.wpb > 0 ? tw.wpb : 4;
-            if (wpb > kMaxWaves) wpb = kMaxWaves;
-            while (wpb & (wpb - 1)) wpb &= wpb - 1;   // power of two
-            int gpb = tw.gpb > 0 ? tw.gpb : 1;
-            while (gpb & (gpb - 1)) gpb &= gpb - 1;
-            while (gpb > 1 && (gpb > wpb || gpb > kgroups)) gpb >>= 1;
-            a.gpb = gpb;
-            a.spb_log2 = 0;
-            while ((1 << (a.spb_log2 + 1)) <= wpb / gpb) ++a.spb_log2;
-            const int64_t nstrips = ceil_div(N, 4 * lpr);
-            a.ncol_tiles = static_cast<uint32_t>(ceil_div(nstrips, wpb / gpb));
-            a.nrow_tiles = static_cast<uint32_t>(ceil_div(kgroups, gpb));
-            a.order = tw.order >= 0 ? tw.order : 2;
-            a.gk = tw.gk > 0 ? tw.gk : 4;
-            a.nt = (tw.nt >= 0 ? tw.nt : 1) & kNtMask;
-            // Column tiles (512 B of a row) that one XCD owns side by side inside a chunk of the L2-merging order.  One tile per XCD
-            // leaves an XCD a fixed 512-byte residue of every 4 KB of a row band; two neighbours (1 KB) measured 2-5 % faster on
-            // every Llama width but the multiples of 16384 (4096: 18.0 -> 17.2 us, 11008: 40.1 -> 38.8, 28672: 100.4 -> 96.3,
-            // 32000: 122.3 -> 116.4; 16384: 56.9 -> 57.7), eight (4 KB) on rows of 32 KB (8192: 32.3 -> 30.0, 8192 x 8192:
-            // 62.4 -> 56.6): scripts/lab_order_sweep.sh, docs/LAB_NOTES_r05.md.  Speed only.
-            // (g = 128; a tile of the g = 64 / 32 builds is 1 / 2 KB wide already: 4096 x 11008 g = 64 43.1 us with one tile, 44.6 with two)
-            {
-                const int want_log2 = N % 16384 == 0 ? 9 : (N % 8192 == 0 ? 12 : 10);      // bytes of a row one XCD owns side by side
-                int tile_log2 = 6;                                                          // 64 * lpr bytes: four strips of 4 * lpr columns
-                for (int l = lpr; l > 1; l >>= 1) ++tile_log2;
-                const int rule = want_log2 > tile_log2 ? want_log2 - tile_log2 : 0;
-                a.xg_log2 = tw.xg >= 0 ? static_cast<uint32_t>(tw.xg > 4 ? 4 : tw.xg) : static_cast<uint32_t>(rule);
-            }
-            set_block_order(a);
-            const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(batch)), block(static_cast<uint32_t>(wpb * kWave));
-            // the 5-waves-per-SIMD build addresses its outputs with 32-bit offsets and needs blocks of <= 4 waves
-            const bool small_idx = static_cast<uint64_t>(N) * static_cast<uint64_t>(K) * static_cast<uint64_t>(grid.bits) / 8u < (1ull << 32);
-            const int wps = tw.wps >= 0 ? tw.wps : kDefaultWps;
-            if (wps > 0 && small_idx && wpb <= 4 && lpr <= 16) {   // g = 32 (two lane sets) does not fit 96 registers: plain build
-                if (lpr == 8) hipLaunchKernelGGL((rtn_group_wave<8, true, 5>), grid_dim, block, 0, s, a);
-                else hipLaunchKernelGGL((rtn_group_wave<16, true, 5>), grid_dim, block, 0, s, a);
-                return check_launch("rtn_group_wave<5 waves per SIMD>");
-            }
-            switch (lpr) {
-                case 8: hipLaunchKernelGGL((rtn_group_wave<8, true>), grid_dim, block, 0, s, a); break;
-                case 16: hipLaunchKernelGGL((rtn_group_wave<16, true>), grid_dim, block, 0, s, a); break;
-                default: hipLaunchKernelGGL((rtn_group_wave<32, true>), grid_dim, block, 0, s, a); break;
-            }
-            return check_launch("rtn_group_wave");
-        }
-    }
-
-    if (fused) {
-        RtnArgs a;
-        a.W = W; a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = kgroups;
-        a.q = q8; a.scale = scale_out; a.zp = zp8; a.grid = grid; a.layout = layout;
-        a.scale_t = nullptr; a.zp_t = nullptr;
-        const int64_t batch = g_batch.count;
-        a.w_stride = g_batch.w_stride; a.q_stride = g_batch.q_stride; a.p_stride = N * kgroups; a.table = g_batch.table;
-        static const Tuning tune_s = Tuning::from_env();
+    if (c.strategy == OQ_GROUP && c.layout == OQ_LAYOUT_NBITS && sh.vec4 && (g == 32 || g == 64 || g == 128) && tune.wavek != 0 &&
+        c.ldw < (1 << 22))   // 32-bit lane offsets
+        return {Route::Wave};
+    if (sh.fused) {
+        RtnPlan p{Route::Fused};
         // [K,N] layouts: the n-major parameters either leave the kernel as they are (4-byte stores 128 bytes apart) or are
         // staged [K/g, N] and transposed by a second launch (~5 us of kernel + a boundary, whatever the size).  Rounds 1-4
         // staged always -- tuned on 4096 x 11008, the one Llama width where that is right: its 43 column tiles are odd, so
@@ -1687,124 +1614,214 @@ int32_t rtn_impl(const float* W, int64_t K, int64_t N, int64_t ldw, int32_t qtyp
         // cost of the second launch to dominate.  Speed only.
         const int64_t nct = ceil_div(N, kColsPerWave), nparams = kgroups * N;
         const bool direct = nct % 8 == 0 || nparams <= (256 << 10) || (nct % 2 == 0 && nparams <= (512 << 10));
-        const bool want_stage = tune_s.stage >= 0 ? tune_s.stage != 0 : (layout != OQ_LAYOUT_NBITS && !direct);
-        const bool staged = want_stage && vec4 && kgroups > 1 && workspace != nullptr &&
-                            workspace_bytes >= static_cast<size_t>(batch) * stage_ws(K, N, g) && (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0;
-        if (staged) {
-            a.scale_t = static_cast<float*>(workspace);
-            a.zp_t = static_cast<uint8_t*>(workspace) + (batch * kgroups * N * 4 + 255) / 256 * 256;
-        }
+        const bool want_stage = tune.stage >= 0 ? tune.stage != 0 : (c.layout != OQ_LAYOUT_NBITS && !direct);
+        p.staged = want_stage && sh.vec4 && kgroups > 1 && c.workspace != nullptr &&
+                   c.workspace_bytes >= static_cast<size_t>(c.batch) * stage_ws(K, N, g) && aligned16(c.workspace);
         // Round 6: with the caller's zeroed state (oq_rtn_quantize_stateful_f32) the staged parameters are transposed inside the
-        // launch, by blocks appended to the grid, instead of by a second launch (see transposer_block)
-        a.tr_scale = nullptr; a.tr_zp = nullptr;
+        // launch, by blocks appended to the grid, instead of by a second launch (see transposer_block).
         // Measured (scripts/lab_kn_inlaunch.py, same box, staged + launch -> in the launch, us; the shipped transposer: one block per 128
         // columns, two granules per thread in flight): packed nibbles 4096 x 11008 44.2-44.3 -> 41.3, 4096 x 11000 48.6 -> 45.3-45.4,
         // 8192 x 11008 (two passes of 32 k-groups) 74.5-75.1 -> 73.4-74.1, 4096 x 27648 91.2-93.1 -> 91.2-91.6, 4096 x 32000 108.0-108.2 ->
         // 106.7-107.5; [K,N] bytes int8 4096 x 11008 45.5-45.6 -> 43.2, 8192 x 11008 79.5-79.9 -> 78.8-79.0, 4096 x 27648 98.2-98.6 ->
         // 97.7-98.3, 4096 x 32000 112.8-113.1 -> 113.7 (the one loss).  More than two passes put their round trips on the tail of the
         // launch: up to 64 k-groups.  Speed only.
-        const bool in_launch = staged && tune_s.stage < 0 && emit_q && (layout == OQ_LAYOUT_KN_PACKED4 || layout == OQ_LAYOUT_KN) && kgroups <= 64 &&
-                               rpw == 16 && wpg == kMaxWaves && batch == 1 && g_batch.table == nullptr &&
-                               kgroups % 4 == 0 && N % 4 == 0 && g_state.state != nullptr && g_state.bytes >= fused_state_bytes(K, N, g) &&
-                               (reinterpret_cast<uintptr_t>(scale_out) & 15u) == 0 && (reinterpret_cast<uintptr_t>(zp8) & 3u) == 0 &&
-                               !rtn_stream_is_capturing(s);
-        if (in_launch) {
-            a.tr_scale = static_cast<float*>(g_state.state);
-            a.tr_zp = reinterpret_cast<uint2*>(static_cast<uint8_t*>(g_state.state) + (kgroups * N * 4 + 255) / 256 * 256);
-            a.scale_t = nullptr; a.zp_t = nullptr;
-        }
-        a.wpg = wpg;
-        a.pair_owner = 0;
-        for (uint32_t pr = 0; pr < 8; ++pr) a.pair_owner |= (pr % static_cast<uint32_t>(wpg)) << (3 * pr);
-        a.gpb = kMaxWaves / wpg > 0 ? kMaxWaves / wpg : 1;
-        if (a.gpb > kgroups) a.gpb = static_cast<int32_t>(kgroups);
-        a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, kColsPerWave));
-        a.nrow_tiles = static_cast<uint32_t>(ceil_div(kgroups, a.gpb));
-        // Tuned on 4096x11008 (profiles/r01_rtn_knob_sweep.txt).  [K,N] bytes: plain column-fastest ids, parameters
-        // staged [K/g, N] + transpose launch.  MatMulNBits blob: L2-merging id order (its 64-byte half lines and the
-        // 4-byte scales of neighbouring k-groups meet in one L2) + direct n-major parameter stores.  The OQ_RTN_*
-        // environment variables override these choices for experiments only.
-        static const Tuning tune = Tuning::from_env();
-        const bool blob = layout == OQ_LAYOUT_NBITS;
-        a.order = tune.order >= 0 ? tune.order : (blob ? 2 : 1);      // KN and KN_PACKED4 alike: plain column-fastest ids
-        a.gk = tune.gk > 0 ? tune.gk : 8;
-        // 16 column tiles (N = 4096): with column-fastest ids an XCD owns tiles x and x + 8 of EVERY row band; the L2-merging order
-        // with two neighbouring tiles per XCD measured 25.1 -> 22.3 us (4096 x 4096 [K,N] bytes), 50.7 -> 48.1 (11008 x 4096),
-        // 60.5 -> 57.6 (14336 x 4096); every other width of the sweep keeps the plain order (scripts/lab_order_sweep.sh)
-        const bool sixteen = !blob && a.ncol_tiles == 16 && tune.order < 0;
-        if (sixteen) a.order = 2;
-        a.nt = (tune.nt >= 0 ? tune.nt : 1) & kNtMask;
-        a.stage_q = ((tune.stage_q != 0) && blob && vec4 && rpw == 16 && a.wpg * a.gpb == kMaxWaves && kgroups % a.gpb == 0) ? 1 : 0;
-        a.spb_log2 = 0;
-        a.xg_log2 = tune.xg >= 0 ? static_cast<uint32_t>(tune.xg > 4 ? 4 : tune.xg) : (sixteen ? 1u : 0u);
-        set_block_order(a);
-        const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles + (in_launch ? static_cast<uint32_t>(ceil_div(N, 128)) : 0u), static_cast<uint32_t>(batch)),
-            block(static_cast<uint32_t>(a.wpg * a.gpb * kWave));
-        if (in_launch) {      // its appended blocks wait for its main blocks: ordered against every other waiting launch of the device
-            st = ticket_chain_begin(s);
-            if (st != OQ_OK) return st;
-        }
-        if (vec4) {
-            if (emit_q) launch_fused<true, true>(rpw, a, grid_dim, block, s);
-            else launch_fused<true, false>(rpw, a, grid_dim, block, s);
-        } else {
-            if (emit_q) launch_fused<false, true>(rpw, a, grid_dim, block, s);
-            else launch_fused<false, false>(rpw, a, grid_dim, block, s);
-        }
-        st = check_launch("rtn_group_fused");
-        if (in_launch) { ticket_chain_end(s); return st; }
-        if (st != OQ_OK || !staged) return st;
-        hipLaunchKernelGGL(transpose_qparams,
-                           dim3(static_cast<uint32_t>(ceil_div(N, 32)), static_cast<uint32_t>(ceil_div(kgroups, 32)), static_cast<uint32_t>(batch)),
-                           dim3(256), 0, s, a.scale_t, a.zp_t, kgroups, N, scale_out, zp8, a.table);
-        return check_launch("transpose_qparams");
+        p.in_launch = p.staged && tune.stage < 0 && c.emit_q && (c.layout == OQ_LAYOUT_KN_PACKED4 || c.layout == OQ_LAYOUT_KN) && kgroups <= 64 &&
+                      in_launch_shape(K, N, g) && c.batch == 1 && c.table == nullptr && c.state != nullptr &&
+                      c.state_bytes >= fused_state_bytes(K, N, g) && aligned16(c.scale) && (reinterpret_cast<uintptr_t>(c.zp) & 3u) == 0 &&
+                      !rtn_stream_is_capturing(s) && in_launch_fits(N, tune.nt_bits() != 0);
+        return p;
     }
-    OQ_REQUIRE(g_batch.count == 1, OQ_ERR_UNSUPPORTED, "batched call needs the fused group path");
-
     // channel, tensor, groups taller than the fused kernel holds: W read once, ranges completed across workgroups
     // (rtn_resident.hip); what it does not take (scalar-aligned operands, the blob layout, ranges without integers,
-    // columns taller than 16384 rows) runs on the three launches below
-    {
-        static const Tuning tr = Tuning::from_env();
-        // a stream under capture takes the three launches below: the ticketed kernels must never overlap one another, and a
-        // replayed graph is ordered against nothing the library sees
-        const bool ticketed_ok = tr.resident != 0 && !rtn_stream_is_capturing(s);
-        if (ticketed_ok && g_state.state != nullptr && rtn_resident_eligible(K, N, ldw, W, q_out, strategy, g, layout, emit_q, g_state.bytes))
-            return rtn_resident_impl(W, K, N, ldw, grid, strategy, g, q8, scale_out, zp8, layout, g_state.state, g_state.bytes, s, true);
-        if (ticketed_ok && rtn_resident_eligible(K, N, ldw, W, q_out, strategy, g, layout, emit_q, workspace ? workspace_bytes : 0))
-            return rtn_resident_impl(W, K, N, ldw, grid, strategy, g, q8, scale_out, zp8, layout, workspace, workspace_bytes, s, false);
+    // columns taller than 16384 rows) runs on the three launches.  A stream under capture takes the three launches too: the
+    // ticketed kernels must never overlap one another, and a replayed graph is ordered against nothing the library sees
+    if (tune.resident != 0 && !rtn_stream_is_capturing(s)) {
+        if (c.state != nullptr && rtn_resident_eligible(K, N, c.ldw, c.W, c.q, c.strategy, g, c.layout, c.emit_q, c.state_bytes))
+            return {Route::Ticketed, false, false, true};
+        if (rtn_resident_eligible(K, N, c.ldw, c.W, c.q, c.strategy, g, c.layout, c.emit_q, c.workspace ? c.workspace_bytes : 0))
+            return {Route::Ticketed};
     }
+    return {Route::ThreeLaunch};
+}
 
-    // two-pass
+// (c) One launcher per route.  The RtnArgs fields the wave and the fused kernel share:
+static RtnArgs group_args(const RtnCall& c, const RtnShape& sh, const Tuning& tune) {
+    RtnArgs a{};
+    a.W = c.W; a.K = c.K; a.N = c.N; a.ldw = c.ldw; a.g = sh.g; a.kgroups = sh.kgroups;
+    a.q = static_cast<uint8_t*>(c.q); a.scale = c.scale; a.zp = static_cast<uint8_t*>(c.zp); a.grid = sh.grid; a.layout = c.layout;
+    a.w_stride = c.w_stride; a.q_stride = c.q_stride; a.p_stride = c.N * sh.kgroups; a.table = c.table;
+    a.nt = tune.nt_bits();
+    return a;
+}
+
+static int32_t launch_flat_groups(const RtnCall& c, const RtnShape& sh, hipStream_t s) {
+    const int64_t ngroups = c.K * c.N / sh.g;
+    hipLaunchKernelGGL(rtn_flat_groups, dim3(static_cast<uint32_t>(ceil_div(ngroups, 4))), dim3(256), 0, s, c.W, c.K, c.N,
+                       c.ldw, sh.g, ngroups, sh.grid, c.emit_q ? static_cast<uint8_t*>(c.q) : nullptr, c.scale, static_cast<uint8_t*>(c.zp));
+    return check_launch("rtn_flat_groups");
+}
+
+static int32_t launch_wave(const RtnCall& c, const RtnShape& sh, const Tuning& tune, hipStream_t s) {
+    RtnArgs a = group_args(c, sh, tune);
+    a.wpg = 1;
+    const int lpr = static_cast<int>(1024 / sh.g);
+    int wpb = tune.wpb > 0 ? tune.wpb : 4;
+    if (wpb > kMaxWaves) wpb = kMaxWaves;
+    while (wpb & (wpb - 1)) wpb &= wpb - 1;   // power of two
+    int gpb = tune.gpb > 0 ? tune.gpb : 1;
+    while (gpb & (gpb - 1)) gpb &= gpb - 1;
+    while (gpb > 1 && (gpb > wpb || gpb > sh.kgroups)) gpb >>= 1;
+    a.gpb = gpb;
+    while ((1 << (a.spb_log2 + 1)) <= wpb / gpb) ++a.spb_log2;
+    const int64_t nstrips = ceil_div(c.N, 4 * lpr);
+    a.ncol_tiles = static_cast<uint32_t>(ceil_div(nstrips, wpb / gpb));
+    a.nrow_tiles = static_cast<uint32_t>(ceil_div(sh.kgroups, gpb));
+    a.order = tune.order >= 0 ? tune.order : 2;
+    a.gk = tune.gk > 0 ? tune.gk : 4;
+    // Column tiles (512 B of a row) that one XCD owns side by side inside a chunk of the L2-merging order.  One tile per XCD
+    // leaves an XCD a fixed 512-byte residue of every 4 KB of a row band; two neighbours (1 KB) measured 2-5 % faster on
+    // every Llama width but the multiples of 16384 (4096: 18.0 -> 17.2 us, 11008: 40.1 -> 38.8, 28672: 100.4 -> 96.3,
+    // 32000: 122.3 -> 116.4; 16384: 56.9 -> 57.7), eight (4 KB) on rows of 32 KB (8192: 32.3 -> 30.0, 8192 x 8192:
+    // 62.4 -> 56.6): scripts/lab_order_sweep.sh, docs/LAB_NOTES_r05.md.  Speed only.
+    // (g = 128; a tile of the g = 64 / 32 builds is 1 / 2 KB wide already: 4096 x 11008 g = 64 43.1 us with one tile, 44.6 with two)
+    const int want_log2 = c.N % 16384 == 0 ? 9 : (c.N % 8192 == 0 ? 12 : 10);      // bytes of a row one XCD owns side by side
+    int tile_log2 = 6;                                                              // 64 * lpr bytes: four strips of 4 * lpr columns
+    for (int l = lpr; l > 1; l >>= 1) ++tile_log2;
+    const int rule = want_log2 > tile_log2 ? want_log2 - tile_log2 : 0;
+    a.xg_log2 = tune.xg >= 0 ? static_cast<uint32_t>(tune.xg > 4 ? 4 : tune.xg) : static_cast<uint32_t>(rule);
+    set_block_order(a);
+    const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(c.batch)), block(static_cast<uint32_t>(wpb * kWave));
+    // the 5-waves-per-SIMD build addresses its outputs with 32-bit offsets and needs blocks of <= 4 waves
+    const bool small_idx = static_cast<uint64_t>(c.N) * static_cast<uint64_t>(c.K) * static_cast<uint64_t>(sh.grid.bits) / 8u < (1ull << 32);
+    const int wps = tune.wps >= 0 ? tune.wps : kDefaultWps;
+    if (wps > 0 && small_idx && wpb <= 4 && lpr <= 16) {   // g = 32 (two lane sets) does not fit 96 registers: plain build
+        if (lpr == 8) hipLaunchKernelGGL((rtn_group_wave<8, true, 5>), grid_dim, block, 0, s, a);
+        else hipLaunchKernelGGL((rtn_group_wave<16, true, 5>), grid_dim, block, 0, s, a);
+        return check_launch("rtn_group_wave<5 waves per SIMD>");
+    }
+    switch (lpr) {
+        case 8: hipLaunchKernelGGL((rtn_group_wave<8, true>), grid_dim, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((rtn_group_wave<16, true>), grid_dim, block, 0, s, a); break;
+        default: hipLaunchKernelGGL((rtn_group_wave<32, true>), grid_dim, block, 0, s, a); break;
+    }
+    return check_launch("rtn_group_wave");
+}
+
+static int32_t launch_fused(const RtnCall& c, const RtnShape& sh, const RtnPlan& p, const Tuning& tune, hipStream_t s) {
+    const int64_t N = c.N, kgroups = sh.kgroups;
+    RtnArgs a = group_args(c, sh, tune);
+    if (p.in_launch) {
+        a.tr_scale = static_cast<float*>(c.state);
+        a.tr_zp = reinterpret_cast<uint2*>(static_cast<uint8_t*>(c.state) + (kgroups * N * 4 + 255) / 256 * 256);
+    } else if (p.staged) {
+        a.scale_t = static_cast<float*>(c.workspace);
+        a.zp_t = static_cast<uint8_t*>(c.workspace) + (c.batch * kgroups * N * 4 + 255) / 256 * 256;
+    }
+    a.wpg = sh.wpg;
+    for (uint32_t pr = 0; pr < 8; ++pr) a.pair_owner |= (pr % static_cast<uint32_t>(sh.wpg)) << (3 * pr);
+    a.gpb = kMaxWaves / sh.wpg > 0 ? kMaxWaves / sh.wpg : 1;
+    if (a.gpb > kgroups) a.gpb = static_cast<int32_t>(kgroups);
+    a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, kColsPerWave));
+    a.nrow_tiles = static_cast<uint32_t>(ceil_div(kgroups, a.gpb));
+    // Tuned on 4096x11008 (profiles/r01_rtn_knob_sweep.txt).  [K,N] bytes: plain column-fastest ids, parameters
+    // staged [K/g, N] + transpose launch.  MatMulNBits blob: L2-merging id order (its 64-byte half lines and the
+    // 4-byte scales of neighbouring k-groups meet in one L2) + direct n-major parameter stores.  The OQ_RTN_*
+    // environment variables override these choices for experiments only.
+    const bool blob = c.layout == OQ_LAYOUT_NBITS;
+    a.order = tune.order >= 0 ? tune.order : (blob ? 2 : 1);      // KN and KN_PACKED4 alike: plain column-fastest ids
+    a.gk = tune.gk > 0 ? tune.gk : 8;
+    // 16 column tiles (N = 4096): with column-fastest ids an XCD owns tiles x and x + 8 of EVERY row band; the L2-merging order
+    // with two neighbouring tiles per XCD measured 25.1 -> 22.3 us (4096 x 4096 [K,N] bytes), 50.7 -> 48.1 (11008 x 4096),
+    // 60.5 -> 57.6 (14336 x 4096); every other width of the sweep keeps the plain order (scripts/lab_order_sweep.sh)
+    const bool sixteen = !blob && a.ncol_tiles == 16 && tune.order < 0;
+    if (sixteen) a.order = 2;
+    a.stage_q = ((tune.stage_q != 0) && blob && sh.vec4 && sh.rpw == 16 && a.wpg * a.gpb == kMaxWaves && kgroups % a.gpb == 0) ? 1 : 0;
+    a.xg_log2 = tune.xg >= 0 ? static_cast<uint32_t>(tune.xg > 4 ? 4 : tune.xg) : (sixteen ? 1u : 0u);
+    set_block_order(a);
+    const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles + (p.in_launch ? static_cast<uint32_t>(ceil_div(N, 128)) : 0u), static_cast<uint32_t>(c.batch)),
+        block(static_cast<uint32_t>(a.wpg * a.gpb * kWave));
+    if (p.in_launch) {      // its appended blocks wait for its main blocks: ordered against every other waiting launch of the device
+        const int32_t st = ticket_chain_begin(s);
+        if (st != OQ_OK) return st;
+    }
+    if (sh.vec4) (c.emit_q ? launch_fused_kernel<true, true> : launch_fused_kernel<true, false>)(sh.rpw, a, grid_dim, block, s);
+    else (c.emit_q ? launch_fused_kernel<false, true> : launch_fused_kernel<false, false>)(sh.rpw, a, grid_dim, block, s);
+    const int32_t st = check_launch("rtn_group_fused");
+    if (p.in_launch) ticket_chain_end(s);
+    if (st != OQ_OK || !p.staged || p.in_launch) return st;
+    hipLaunchKernelGGL(transpose_qparams,
+                       dim3(static_cast<uint32_t>(ceil_div(N, 32)), static_cast<uint32_t>(ceil_div(kgroups, 32)), static_cast<uint32_t>(c.batch)),
+                       dim3(256), 0, s, a.scale_t, a.zp_t, kgroups, N, c.scale, a.zp, a.table);
+    return check_launch("transpose_qparams");
+}
+
+// channel, tensor and tall groups in three launches: partial column ranges, their fold into parameters, K1 (W read twice)
+static int32_t launch_three(const RtnCall& c, const RtnShape& sh, hipStream_t s) {
+    const int64_t K = c.K, N = c.N, g = sh.g, kgroups = sh.kgroups;
     const size_t need = twopass_ws(K, N, g);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "rtn: workspace of %zu bytes needed, %zu given", need,
-               workspace_bytes);
+    OQ_REQUIRE(c.workspace && c.workspace_bytes >= need, OQ_ERR_WORKSPACE, "rtn: workspace of %zu bytes needed, %zu given", need,
+               c.workspace_bytes);
+    uint8_t* zp8 = static_cast<uint8_t*>(c.zp);
     RangeArgs r;
-    r.W = W; r.K = K; r.N = N; r.ldw = ldw; r.g = g; r.kgroups = kgroups;
+    r.W = c.W; r.K = K; r.N = N; r.ldw = c.ldw; r.g = g; r.kgroups = kgroups;
     r.chunks = ceil_div(g, kChunkRows);
-    r.pmin = static_cast<float*>(workspace);
+    r.pmin = static_cast<float*>(c.workspace);
     r.pmax = r.pmin + kgroups * r.chunks * N;
     r.ncol_tiles = static_cast<uint32_t>(ceil_div(N, kColsPerWave));
     r.nrow_tiles = static_cast<uint32_t>(kgroups * r.chunks);
-    const bool vec_in = (N % 4 == 0) && (ldw % 4 == 0) && aligned16(W);
+    const bool vec_in = (N % 4 == 0) && (c.ldw % 4 == 0) && aligned16(c.W);
     if (vec_in)
         hipLaunchKernelGGL(col_range_partial<true>, dim3(r.ncol_tiles * r.nrow_tiles), dim3(kMaxWaves * kWave), 0, s, r);
     else
         hipLaunchKernelGGL(col_range_partial<false>, dim3(r.ncol_tiles * r.nrow_tiles), dim3(kMaxWaves * kWave), 0, s, r);
-    st = check_launch("col_range_partial");
+    int32_t st = check_launch("col_range_partial");
     if (st != OQ_OK) return st;
-    if (strategy == OQ_TENSOR) {
+    if (c.strategy == OQ_TENSOR) {
         // fold the chunks per column in parallel (into the first row of the partial arrays), then one block folds N values
         hipLaunchKernelGGL(col_fold_kernel, dim3(static_cast<uint32_t>(ceil_div(N, 256))), dim3(256), 0, s, r.pmin, r.pmax, N,
                            kgroups * r.chunks);
-        hipLaunchKernelGGL(tensor_range_finalize, dim3(1), dim3(1024), 0, s, r.pmin, r.pmax, N, grid, scale_out, zp8);
+        hipLaunchKernelGGL(tensor_range_finalize, dim3(1), dim3(1024), 0, s, r.pmin, r.pmax, N, sh.grid, c.scale, zp8);
     } else {
         hipLaunchKernelGGL(col_range_finalize, dim3(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups)),
-                           dim3(256), 0, s, r.pmin, r.pmax, N, kgroups, r.chunks, grid, scale_out, zp8);
+                           dim3(256), 0, s, r.pmin, r.pmax, N, kgroups, r.chunks, sh.grid, c.scale, zp8);
     }
     st = check_launch("range_finalize");
-    if (st != OQ_OK || !emit_q) return st;
-    return launch_quantize_kn(W, K, N, ldw, g, kgroups, scale_out, zp8, q8, grid, zp_signed, strategy == OQ_TENSOR, s, layout);
+    if (st != OQ_OK || !c.emit_q) return st;
+    return launch_quantize_kn(c.W, K, N, c.ldw, g, kgroups, c.scale, zp8, static_cast<uint8_t*>(c.q), sh.grid, zp_signed(c.qtype),
+                              c.strategy == OQ_TENSOR, s, c.layout);
+}
+
+int32_t rtn_impl(const RtnCall& c) {
+    RtnShape sh;
+    const int32_t st = check_call(c, sh);
+    if (st != OQ_OK) return st;
+    static const Tuning tune = Tuning::from_env();
+    const hipStream_t s = as_stream(c.stream);
+    const RtnPlan p = plan_route(c, sh, tune, s);
+    switch (p.route) {
+        case Route::FlatGroups: return launch_flat_groups(c, sh, s);
+        case Route::Mse:
+            return rtn_mse_impl(c.W, c.K, c.N, c.ldw, sh.grid, c.strategy, sh.g, c.q, c.scale, c.zp, zp_signed(c.qtype), c.workspace,
+                                c.workspace_bytes, s, c.emit_q);
+        case Route::Wave: return launch_wave(c, sh, tune, s);
+        case Route::Fused: return launch_fused(c, sh, p, tune, s);
+        case Route::Ticketed:
+            return rtn_resident_impl(c.W, c.K, c.N, c.ldw, sh.grid, c.strategy, sh.g, static_cast<uint8_t*>(c.q), c.scale,
+                                     static_cast<uint8_t*>(c.zp), c.layout, p.use_state ? c.state : c.workspace,
+                                     p.use_state ? c.state_bytes : c.workspace_bytes, s, p.use_state);
+        case Route::ThreeLaunch: break;
+    }
+    return launch_three(c, sh, s);
+}
+
+// Forward progress of the in-launch transposition (see transposer_block): its ceil(N / 128) appended blocks take at most 3/4 of the
+// workgroup slots the device holds of the TR build that would run -- the rule of the ticketed kernels (rtn_resident_eligible).
+// Defined last and naming the kernels through tr_build only, so that the device code keeps its order of kernels (the launchers'):
+// host-only changes leave the assembly of this file unchanged, which is how they are checked.
+static bool in_launch_fits(int64_t N, bool nt) {
+    static std::atomic<int> cache[2][64];
+    const void* k = nt ? tr_build<true>() : tr_build<false>();
+    return 4 * ceil_div(N, 128) <= 3 * static_cast<int64_t>(resident_slots(cache[nt ? 1 : 0], k, kMaxWaves * kWave));
 }
 
 }  // namespace oq
@@ -1829,8 +1846,8 @@ int32_t oq_rtn_quantize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, i
                             int64_t group_size, int32_t symmetric, int32_t reduce_range, float clip_ratio,
                             int32_t mse, void* q_out, float* scale_out, void* zp_out, int32_t layout,
                             void* workspace, size_t workspace_bytes, void* stream) {
-    return oq::rtn_impl(W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, mse, q_out,
-                        scale_out, zp_out, layout, workspace, workspace_bytes, stream, true);
+    return oq::rtn_impl(oq::RtnCall{W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, mse, q_out, scale_out, zp_out,
+                                    layout, workspace, workspace_bytes, stream});
 }
 
 size_t oq_rtn_state_bytes(int64_t K, int64_t N, int32_t strategy, int64_t group_size) {
@@ -1839,7 +1856,7 @@ size_t oq_rtn_state_bytes(int64_t K, int64_t N, int32_t strategy, int64_t group_
     if (oq::resolve_group(strategy, K, group_size, &g) != OQ_OK || K % g != 0) return 0;
     int rpw = 0, wpg = 0;
     if (strategy == OQ_GROUP && oq::fused_shape(g, &rpw, &wpg))      // the fused group kernels: the staging of the in-launch parameter transposition
-        return (rpw == 16 && wpg == oq::kMaxWaves && (K / g) % 4 == 0 && N % 4 == 0 && K / g > 1) ? oq::fused_state_bytes(K, N, g) : 0;
+        return oq::in_launch_shape(K, N, g) ? oq::fused_state_bytes(K, N, g) : 0;
     return oq::rtn_resident_workspace(K, N, strategy, g);
 }
 
@@ -1849,20 +1866,19 @@ int32_t oq_rtn_quantize_stateful_f32(const float* W, int64_t K, int64_t N, int64
                                      void* workspace, size_t workspace_bytes, void* state, size_t state_bytes, void* stream) {
     OQ_REQUIRE(state == nullptr || (reinterpret_cast<uintptr_t>(state) & 15u) == 0, OQ_ERR_INVALID_ARGUMENT,
                "oq_rtn_quantize_stateful_f32: state must be 16-byte aligned");
-    oq::g_state.state = state;
-    oq::g_state.bytes = state ? state_bytes : 0;
-    const int32_t st = oq::rtn_impl(W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, mse, q_out, scale_out, zp_out,
-                                    layout, workspace, workspace_bytes, stream, true);
-    oq::g_state = oq::StateCtx();
-    return st;
+    oq::RtnCall c{W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, mse, q_out, scale_out, zp_out, layout,
+                  workspace, workspace_bytes, stream};
+    c.state = state;
+    c.state_bytes = state ? state_bytes : 0;
+    return oq::rtn_impl(c);
 }
 
 int32_t oq_rtn_qparams_f32(const float* W, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
                            int64_t group_size, int32_t symmetric, int32_t reduce_range, float clip_ratio,
                            int32_t mse, float* scale_out, void* zp_out, void* workspace, size_t workspace_bytes,
                            void* stream) {
-    return oq::rtn_impl(W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, mse, nullptr,
-                        scale_out, zp_out, OQ_LAYOUT_KN, workspace, workspace_bytes, stream, false);
+    return oq::rtn_impl(oq::RtnCall{W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, mse, nullptr, scale_out, zp_out,
+                                    OQ_LAYOUT_KN, workspace, workspace_bytes, stream, false});
 }
 
 size_t oq_rtn_batched_workspace_bytes(int64_t batch, int64_t K, int64_t N, int64_t group_size) {
@@ -1887,13 +1903,12 @@ int32_t oq_rtn_quantize_batched_f32(const float* W, int64_t batch, int64_t w_str
     int rpw = 0, wpg = 0;
     OQ_REQUIRE(oq::fused_shape(g, &rpw, &wpg), OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_batched_f32 needs a group the fused kernel holds (<= 256 rows)");
     const int64_t bits = (qtype == OQ_INT4 || qtype == OQ_UINT4) ? 4 : 8;
-    oq::g_batch.count = batch;
-    oq::g_batch.w_stride = w_stride;
-    oq::g_batch.q_stride = layout == OQ_LAYOUT_KN ? K * N : K * N * bits / 8;      // blob and KN_PACKED4 (4-bit only) alike
-    st = oq::rtn_impl(W, K, N, ldw, qtype, OQ_GROUP, group_size, symmetric, reduce_range, clip_ratio, 0, q_out, scale_out, zp_out, layout,
-                      workspace, workspace_bytes, stream, true);
-    oq::g_batch = oq::BatchCtx();
-    return st;
+    oq::RtnCall c{W, K, N, ldw, qtype, OQ_GROUP, group_size, symmetric, reduce_range, clip_ratio, 0, q_out, scale_out, zp_out, layout,
+                  workspace, workspace_bytes, stream};
+    c.batch = batch;
+    c.w_stride = w_stride;
+    c.q_stride = layout == OQ_LAYOUT_KN ? K * N : K * N * bits / 8;      // blob and KN_PACKED4 (4-bit only) alike
+    return oq::rtn_impl(c);
 }
 
 int32_t oq_rtn_quantize_ptrs_f32(const oq_rtn_ptrs* table_host, const oq_rtn_ptrs* table_device, int64_t count, int64_t K, int64_t N,
@@ -1922,12 +1937,12 @@ int32_t oq_rtn_quantize_ptrs_f32(const oq_rtn_ptrs* table_host, const oq_rtn_ptr
     }
     // How many matrices share a launch (blockIdx.y = entry): oq::matrices_per_launch.
     for (int64_t i = 0; i < count; i += per_launch) {
-        const int64_t m = count - i < per_launch ? count - i : per_launch;
-        oq::g_batch.count = m;
-        oq::g_batch.table = m > 1 ? reinterpret_cast<const oq::RtnPtrs*>(table_device) + i : nullptr;
-        st = oq::rtn_impl(table_host[i].W, K, N, ldw, qtype, OQ_GROUP, group_size, symmetric, reduce_range, clip_ratio, 0, table_host[i].q_out,
-                          table_host[i].scale_out, table_host[i].zp_out, layout, workspace, workspace_bytes, stream, true);
-        oq::g_batch = oq::BatchCtx();
+        const oq_rtn_ptrs& p = table_host[i];
+        oq::RtnCall c{p.W, K, N, ldw, qtype, OQ_GROUP, group_size, symmetric, reduce_range, clip_ratio, 0, p.q_out, p.scale_out, p.zp_out, layout,
+                      workspace, workspace_bytes, stream};
+        c.batch = count - i < per_launch ? count - i : per_launch;
+        c.table = c.batch > 1 ? reinterpret_cast<const oq::RtnPtrs*>(table_device) + i : nullptr;
+        st = oq::rtn_impl(c);
         if (st != OQ_OK) return st;
     }
     return OQ_OK;

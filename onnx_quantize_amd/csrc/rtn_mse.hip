@@ -17,7 +17,7 @@
 // Numerics: per-element arithmetic follows the reference (divide, rint, clamp, (q - zp) * s, subtract, abs,
 // |.|^2.4), but NumPy's pow kernel and its pairwise summation order cannot be reproduced bit for bit,
 // so two candidates whose errors differ in the last bits can swap; tests/test_mse_gpu.py is tolerance-aware.
-#include "oq_common.hpp"
+#include "rtn_internal.hpp"
 
 namespace oq {
 
@@ -257,11 +257,6 @@ size_t rtn_mse_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
     const int64_t rows = strategy == OQ_TENSOR ? 1 : N * (K / g);
     return static_cast<size_t>(rows) * sizeof(MseRow) + 1024 * kMseSteps * sizeof(float) + 512;
 }
-
-// quantize pass shared with the two-pass RTN path (rtn.hip)
-int32_t launch_quantize_kn(const float* W, int64_t K, int64_t N, int64_t ldw, int64_t g, int64_t kgroups, const float* scale,
-                           const uint8_t* zp, uint8_t* q, const QGrid& grid, int32_t zp_signed, bool tensor, hipStream_t s,
-                           int32_t layout);
 
 int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid_in, int32_t strategy, int64_t g,
                      void* q_out, float* scale_out, void* zp_out, int32_t zp_signed, void* workspace, size_t workspace_bytes,

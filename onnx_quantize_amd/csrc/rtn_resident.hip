@@ -32,7 +32,7 @@
 // quantized from registers / LDS; the rows of the other half tiles are dealt out statically and evenly over all waves (no
 // tickets, no barriers), re-read most-recent-first and software-pipelined over the two halves of the slot.  A matrix of up
 // to 1024 tiles is read exactly once and skips that phase altogether.
-#include "oq_common.hpp"
+#include "rtn_internal.hpp"
 
 #include <cstdlib>
 #include <mutex>
@@ -1052,12 +1052,20 @@ __global__ __launch_bounds__(256) void clear_words_kernel(uint4* p, uint32_t n16
 }
 
 // ------------------------------------------------------------------------------------ host side
-static int resident_blocks(const void* kernel, size_t dynamic_lds, int threads = kResWaves * kWave) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dynamic_lds) != hipSuccess) return 0;
-    return cus * per_cu;
+int resident_slots(std::atomic<int> (&cache)[64], const void* kernel, int threads, size_t dynamic_lds) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    int slots = cache[dev].load(std::memory_order_relaxed);
+    if (slots == 0) {   // benign race: every thread computes the same value
+        int cus = 0, per_cu = 0;
+        // the attribute belongs to this device's copy of the kernel and has to be set ahead of the query
+        if (dynamic_lds > 0 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(dynamic_lds)) != hipSuccess) return 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dynamic_lds) != hipSuccess) return 0;
+        slots = cus * per_cu;
+        cache[dev].store(slots, std::memory_order_relaxed);
+    }
+    return slots;
 }
 
 // Which kernel takes a channel / tall-group call (speed only, same bytes).  Measured, int8 per channel, same box
@@ -1095,31 +1103,17 @@ static int groups_tile_rows(int64_t g, int64_t ranges) {
 }
 static int64_t ranges_of(int64_t K, int64_t N, int64_t g) { return ceil_div(N, kResCols) * (K / g); }
 
-// workgroups of the channel / tall-group kernel chosen for `g` that the current device runs at once (cached per device)
+// workgroups of the channel / tall-group kernel chosen for `g` that the current device runs at once
 static int groups_resident(int64_t g, int64_t ranges) {
-    static int cache[3][64];
-    static bool filled[3][64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    const int which = groups_streamed(g, ranges) ? 0 : (groups_tile_rows(g, ranges) == 256 ? 1 : 2);
-    if (!filled[which][dev]) {   // benign race: every thread computes the same value
-        int cus = 0, per_cu = 0;
-        const void* k = which == 0 ? reinterpret_cast<const void*>(rtn_resident_stream)
-                      : which == 1 ? reinterpret_cast<const void*>(rtn_resident_groups<16, 16, 4>) : reinterpret_cast<const void*>(rtn_resident_groups<8, 16, 4>);
-        const int threads = which == 1 ? 16 * kWave : kResWaves * kWave;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, threads, 0) != hipSuccess) return 0;
-        cache[which][dev] = cus * per_cu;
-        filled[which][dev] = true;
-    }
-    return cache[which][dev];
+    static std::atomic<int> cache[3][64];
+    if (groups_streamed(g, ranges)) return resident_slots(cache[0], reinterpret_cast<const void*>(rtn_resident_stream), kResWaves * kWave);
+    if (groups_tile_rows(g, ranges) == 256) return resident_slots(cache[1], reinterpret_cast<const void*>(rtn_resident_groups<16, 16, 4>), 16 * kWave);
+    return resident_slots(cache[2], reinterpret_cast<const void*>(rtn_resident_groups<8, 16, 4>), kResWaves * kWave);
 }
 
 size_t rtn_resident_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
-    const int64_t kgroups = K / g, chunks = ceil_div(g, groups_tile_rows(g, ranges_of(K, N, g)));
-    const int64_t ncol_tiles = ceil_div(N, kResCols);
+    const int64_t kgroups = K / g, ncol_tiles = ceil_div(N, kResCols);
     if (strategy == OQ_TENSOR) return static_cast<size_t>(kResTensorHeader + (2 * ncol_tiles * ceil_div(K, kResTileRows) + 31) / 32 + 1) * 4 + 256;
-    (void)chunks;
     return static_cast<size_t>(2 * kgroups * ncol_tiles * kResCols + ncol_tiles * kgroups * kResCtrPad + kResHeader) * 4 + 256;
 }
 
@@ -1170,12 +1164,9 @@ bool rtn_stream_is_capturing(hipStream_t s) {
     return cap != hipStreamCaptureStatusNone;
 }
 
-static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g, uint8_t* q,
-                                   float* scale, uint8_t* zp, int32_t layout, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state);
-
-// The chain as two calls around a launch (also used by rtn.hip for the fused group launch whose appended blocks wait for its
-// main blocks).  `ticket_chain_begin` takes the device's mutex, makes `s` wait as described above and returns OQ_OK holding the
-// mutex; `ticket_chain_end` records the event (eager form) and releases it.  A failing begin holds nothing.
+// The chain as two calls around a launch (rtn.hip uses them for the fused launch whose appended blocks wait for its main blocks):
+// `ticket_chain_begin` takes the device's mutex and makes `s` wait as described above, `ticket_chain_end` records the event
+// (eager form) and releases the mutex.  A failing begin holds nothing.
 static thread_local TicketChain* t_chain_held = nullptr;
 int32_t ticket_chain_begin(hipStream_t s) {
     int dev = 0;
@@ -1223,15 +1214,6 @@ void ticket_chain_end(hipStream_t s) {
     c->m.unlock();
 }
 
-int32_t rtn_resident_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g, uint8_t* q,
-                          float* scale, uint8_t* zp, int32_t layout, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state) {
-    const int32_t pre = ticket_chain_begin(s);
-    if (pre != OQ_OK) return pre;
-    const int32_t st = rtn_resident_launch(W, K, N, ldw, grid, strategy, g, q, scale, zp, layout, workspace, workspace_bytes, s, zeroed_state);
-    ticket_chain_end(s);
-    return st;
-}
-
 static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g, uint8_t* q,
                                    float* scale, uint8_t* zp, int32_t layout, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state) {
     ResidentArgs a;
@@ -1257,18 +1239,8 @@ static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t
         a.key_max = base + 128;                  // one 16-byte slot {1, max key, complemented min key} per arrival (<= 512 workgroups)
         a.key_nmin = base + 128 + 64 * 32;       // 64 replicas x 32 words: {go, final max key, final complemented min key}
         a.held = base + kResTensorHeader;
-        // once per device: the attribute belongs to that device's copy of the kernel; the occupancy does not change either
-        // (two host calls of several microseconds each: a 256 x 512 call is host-bound)
-        static int resident_of[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail(OQ_ERR_LAUNCH, "rtn: no current device");
-        const void* kernel = reinterpret_cast<const void*>(rtn_tensor_onepass<kResWaves>);
-        if (resident_of[dev] == 0) {   // benign race: every thread computes the same value
-            if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kParkBytes) != hipSuccess)
-                return fail(OQ_ERR_LAUNCH, "rtn: %d bytes of LDS refused", kParkBytes);
-            resident_of[dev] = resident_blocks(kernel, kParkBytes);
-        }
-        const int resident = resident_of[dev];
+        static std::atomic<int> cache[64];
+        const int resident = resident_slots(cache, reinterpret_cast<const void*>(rtn_tensor_onepass<kResWaves>), kResWaves * kWave, kParkBytes);
         OQ_REQUIRE(resident > 0, OQ_ERR_LAUNCH, "rtn: occupancy query failed");
         uint32_t blocks = a.ntiles < static_cast<uint32_t>(resident) ? a.ntiles : static_cast<uint32_t>(resident);
         if (blocks > static_cast<uint32_t>(kResWaves * kWave)) blocks = kResWaves * kWave;   // the arrival slots: one per thread of the last finisher
@@ -1292,6 +1264,15 @@ static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t
         hipLaunchKernelGGL(rtn_resident_stream, dim3(blocks), dim3(kResWaves * kWave), 0, s, a);
     }
     return check_launch("rtn_resident_groups");
+}
+
+int32_t rtn_resident_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g, uint8_t* q,
+                          float* scale, uint8_t* zp, int32_t layout, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state) {
+    const int32_t pre = ticket_chain_begin(s);
+    if (pre != OQ_OK) return pre;
+    const int32_t st = rtn_resident_launch(W, K, N, ldw, grid, strategy, g, q, scale, zp, layout, workspace, workspace_bytes, s, zeroed_state);
+    ticket_chain_end(s);
+    return st;
 }
 
 }  // namespace oq
