@@ -188,28 +188,41 @@ def gen_rtn_small(out):
 
 def gen_rtn_mse(out):
     cases, arrays = [], {}
+    # (qtype, strategy, g, sym, kind, k, n, reduce_range, power of ten the weights are scaled by, seed or None = 700 + index)
     grid = [
-        ("uint4", "group", 32, False, "normal", 64, 24),
-        ("int4", "group", 16, True, "heavy", 64, 24),
-        ("int8", "channel", -1, False, "heavy", 48, 20),
-        ("uint8", "tensor", -1, False, "normal", 32, 16),
-        ("int8", "tensor", -1, True, "heavy", 32, 16),
-        ("uint4", "group", 128, False, "heavy", 256, 16),
+        ("uint4", "group", 32, False, "normal", 64, 24, False, 0, None),
+        ("int4", "group", 16, True, "heavy", 64, 24, False, 0, None),
+        ("int8", "channel", -1, False, "heavy", 48, 20, False, 0, None),
+        ("uint8", "tensor", -1, False, "normal", 32, 16, False, 0, None),
+        ("int8", "tensor", -1, True, "heavy", 32, 16, False, 0, None),
+        ("uint4", "group", 128, False, "heavy", 256, 16, False, 0, None),
+        # the judge of tests/test_mse_gpu.py pinned where its newer cases go
+        ("uint4", "group", 32, False, "normal", 64, 24, True, 0, None),       # reduce_range
+        ("int4", "group", 64, True, "heavy", 128, 24, True, 0, None),
+        ("uint4", "group", 32, True, "normal", 64, 24, False, 0, None),       # symmetric uint4
+        ("int4", "tensor", -1, False, "heavy", 64, 48, False, 0, None),       # a 4-bit tensor case
+        ("uint4", "group", 256, False, "normal", 512, 8, False, 0, None),
+        ("uint4", "channel", -1, False, "heavy", 33, 40, False, 0, None),     # odd K
+        ("uint4", "group", 128, False, "normal", 256, 16, False, -15, None),  # subnormal terms, normal sums
+        ("uint4", "group", 128, False, "normal", 256, 16, False, -17, None),  # subnormal sums
+        ("uint4", "group", 16, False, "normal", 128, 64, False, 0, 1),        # the stop falls inside the walk (iteration 12)
     ]
-    for idx, (qtype, strategy, g, sym, kind, k, n) in enumerate(grid):
-        seed = 700 + idx
+    for idx, (qtype, strategy, g, sym, kind, k, n, red, e10, seed) in enumerate(grid):
+        seed = 700 + idx if seed is None else seed
         w = weight(kind, seed, k, n)
-        q, s, z = rtn_call(w, qtype, strategy, g, sym, False, 1.0, True)
+        if e10:
+            w = (w * np.float32(10.0 ** e10)).astype(np.float32)
+        q, s, z = rtn_call(w, qtype, strategy, g, sym, red, 1.0, True)
         rows = R.utils._preprocess_array(w, ST[strategy], g)
         lo, hi = R.utils._compute_min_max_mse(
-            rows, QT[qtype], ST[strategy], g, sym, False, np.dtype(np.float32),
+            rows, QT[qtype], ST[strategy], g, sym, red, np.dtype(np.float32),
             QT[qtype].np_dtype)
         cid = f"m{idx:02d}"
         arrays.update({f"{cid}_w": w, f"{cid}_q": q, f"{cid}_s": s, f"{cid}_z": z,
                        f"{cid}_lo": np.asarray(lo), f"{cid}_hi": np.asarray(hi)})
         cases.append(dict(id=cid, qtype=qtype, strategy=strategy, group_size=g, symmetric=sym,
-                          reduce_range=False, clip_ratio=1.0, mse=True, kind=kind, seed=seed,
-                          k=k, n=n))
+                          reduce_range=red, clip_ratio=1.0, mse=True, kind=kind, seed=seed,
+                          k=k, n=n, scale_exp10=e10))
     np.savez_compressed(os.path.join(out, "rtn_mse.npz"), **arrays)
     with open(os.path.join(out, "rtn_mse.json"), "w") as f:
         json.dump(cases, f, indent=0)

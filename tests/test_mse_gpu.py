@@ -1,16 +1,24 @@
-"""M1 (utils.py:140-239, mse=True) on the GPU.  NumPy's float32 pow kernel and its pairwise summation order
-cannot be reproduced bit for bit, so this test is tolerance-aware, as SURVEY.md section 7 prescribes:
+"""M1 (utils.py:140-239, mse=True) on the GPU, judged row by row (tests/mse_verdict.py).
 
-* every row must end on one of the 20 candidate ranges of the reference's grid;
-* the candidate it ends on must be optimal for the ORACLE's own error table up to 1e-4 relative
-  (two candidates whose errors differ in the last bits may swap);
-* rows that end on the same candidate as the oracle (the vast majority) must match it bit for bit:
-  scale, zero point and every integer;
-* the global stop rule (no row improved five times) must cut the search at the same iteration.
+NumPy's float32 pow kernel and its pairwise summation order cannot be reproduced bit for bit, so two candidates of a row whose
+errors differ in the last bits may swap.  Which rows that can happen to is decided on the CPU from the reference's arithmetic alone:
+
+* a band tau per case (summation order + the two 1-ulp instructions + NumPy's own distance from float64; never above 1e-4);
+* a row whose best candidate leads by more than 2 tau in the float64 table is DECIDED and must equal the oracle bit for bit:
+  scale bits, zero point, every integer.  No percentage, no exceptions;
+* an UNDECIDED row must end on a candidate of the reference's grid, at or before the stop, within 2 tau of the best;
+* at most 1 % of a case's rows may be undecided.  That is a condition on the INPUTS (seeds and shapes were chosen on the CPU so that
+  the reference alone satisfies it) and is asserted before the GPU is asked, so that an input change cannot hide failures;
+* the global stop rule (no row improved five times) must cut the search at the oracle's iteration whenever that is decided.
+
+Every case reports rows, undecided rows and rows that differ from the oracle (`record_property`, and one printed line).
 """
+import os
+
 import numpy as np
 import pytest
 
+import mse_verdict as V
 import oq_oracle as O
 from conftest import load_json, load_npz
 
@@ -18,6 +26,7 @@ pytestmark = pytest.mark.gpu
 
 MSE_CASES = load_json("rtn_mse.json")
 MSE = load_npz("rtn_mse.npz")
+QTYPES = ["uint4", "int4", "uint8", "int8"]
 
 
 def dev(a):
@@ -25,45 +34,48 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def oracle_tables(w, qtype, strategy, g, sym, red):
-    rows = O.to_rows(w, strategy, g)
-    trace = []
-    lo, hi = O.min_max_mse(rows, qtype, strategy, sym, red, trace=trace)
-    errs = np.stack([np.asarray(e, dtype=np.float32).reshape(-1) for _, e in trace], axis=0)   # [iters, rows]
-    lo0, hi0 = O.min_max(rows, strategy, 1.0)
-    cands = []
-    for i in range(len(trace)):
-        p = 1 - i / 100.0
-        s, z = O.qparams(p * lo0, p * hi0, qtype, sym, red)
-        cands.append((np.asarray(s).reshape(-1), np.asarray(z).reshape(-1)))
-    return rows, errs, cands, (lo, hi)
+def strided(big, off, n):
+    """(device view, host view) of columns off .. off+n of `big`: leading dimension big.shape[1], base offset 4 * off bytes."""
+    return dev(big)[:, off:off + n], big[:, off:off + n]
 
 
-def check_case(ops, w, qtype, strategy, g, sym, red=False, max_swapped=0.02):
-    q, s, z = ops.rtn_quantize(dev(w), qtype, strategy, g, sym, red, 1.0, True)
+def reference(w, qtype, strategy, g, sym, red):
+    t = V.tables(w, qtype, strategy, g, sym, red)
+    stop = V.oracle_stop(w, qtype, strategy, g, sym, red, t)
+    j = V.judge(t)
+    assert j.stop == stop, "the tables' stop is not the oracle's"
+    return t, j, O.rtn_quantize(w, qtype, strategy, g, sym, red, 1.0, True)
+
+
+def run_case(ops, record_property, w, qtype, strategy, g, sym, red=False, wd=None, max_undecided=0.01, what=""):
+    """One case through the verdict.  `max_undecided`: the share of rows the reference alone may leave undecided, 1 % unless the
+    call states a measured reason for another ceiling (LONG_ROW_CEILING, MAGNITUDE_CEILING, GOLDEN_CEILING); it is asserted in
+    every case, before the GPU is asked."""
+    t, j, (eq, es, ez) = reference(w, qtype, strategy, g, sym, red)
+    rows = t.e32.shape[1]
+    undecided = int((~j.decided & ~t.nan_rows).sum())
+    allowed = rows // 100 if max_undecided == 0.01 else int(max_undecided * rows + 1e-9)
+    assert undecided <= allowed, f"{what}: {undecided} of {rows} rows undecided by the reference alone ({allowed} allowed): choose another input"
+    q, s, z = ops.rtn_quantize(dev(w) if wd is None else wd, qtype, strategy, g, sym, red, 1.0, True)
     q, s, z = q.cpu().numpy(), s.cpu().numpy(), z.cpu().numpy()
-    eq, es, ez = O.rtn_quantize(w, qtype, strategy, g, sym, red, 1.0, True)
-    assert q.shape == eq.shape and s.shape == es.shape and z.shape == ez.shape and q.dtype == eq.dtype
-    rows, errs, cands, _ = oracle_tables(w, qtype, strategy, g, sym, red)
-    nrows = errs.shape[1]
-    sg, zg = s.reshape(-1), z.reshape(-1)
-    so, zo = es.reshape(-1), ez.reshape(-1)
-    # which candidate did each GPU row end on?
-    idx = np.full(nrows, -1)
-    for i, (cs, cz) in enumerate(cands):
-        hit = (idx < 0) & (cs.view(np.uint32) == sg.view(np.uint32)) & (cz == zg)
-        idx[hit] = i
-    assert np.all(idx >= 0), "a row ended on a range outside the reference's candidate grid"
-    best = errs.min(axis=0)
-    chosen = errs[idx, np.arange(nrows)]
-    assert np.all(chosen <= best * (1 + 1e-4) + 1e-30)
-    same = (sg.view(np.uint32) == so.view(np.uint32)) & (zg == zo)
-    assert 1.0 - same.mean() <= max_swapped, f"{(~same).sum()} of {nrows} rows swapped candidates"
-    # bit-exact integers on every row that ended on the oracle's candidate
-    qr = O.to_rows(q, strategy, g).reshape(nrows, -1) if strategy != "tensor" else q.reshape(1, -1)
-    er = O.to_rows(eq, strategy, g).reshape(nrows, -1) if strategy != "tensor" else eq.reshape(1, -1)
-    np.testing.assert_array_equal(qr[same], er[same])
-    return same.mean(), errs.shape[0]
+    one_column = strategy == "channel" and w.shape[1] == 1      # NumPy's squeeze makes these 0-d, the library keeps [1]
+    assert q.shape == eq.shape and q.dtype == eq.dtype and z.dtype == ez.dtype
+    assert (s.shape == es.shape and z.shape == ez.shape) or (one_column and s.shape == (1,) and z.shape == (1,))
+    x_rows = V.rows_of(w, strategy, g)
+    v = V.verdict(t, j, s, z, es, ez, V.rows_of(q, strategy, g), V.rows_of(eq, strategy, g), what,
+                  requantize=lambda row, sc, zp: O.quantize(x_rows[row], sc, int(zp), qtype, sym, red))
+    # the GPU implies the oracle's stop: no row may sit on a candidate after it
+    if j.stop_decided:
+        on_grid_before = np.zeros(rows, bool)
+        sg, zg = s.reshape(-1), z.reshape(-1).astype(np.int64)
+        for i in range(j.stop + 1):
+            on_grid_before |= (t.scales[i].view(np.uint32) == sg.view(np.uint32)) & (t.zps[i] == zg)
+        assert np.all(on_grid_before | t.nan_rows), f"{what}: a row ended after the stop iteration {j.stop}"
+    for k, x in v.as_properties().items():
+        record_property(k, x)
+    print(f"[mse] {what or qtype}: rows {v.rows} undecided {v.undecided} differing {v.differing} stop {v.stop}"
+          f"{'' if v.stop_decided else '?'} tau {v.tau:.3g}")
+    return v, j
 
 
 @pytest.fixture(scope="module")
@@ -72,32 +84,39 @@ def ops():
     return _ops
 
 
+# The two goldens of tiny magnitude have 32 rows, of which the reference leaves one undecided (measured on the CPU, both); 1 % of 32
+# rows is no row at all, so their ceiling is that one row.  The goldens at unit magnitude have none and keep the 1 %.
+GOLDEN_CEILING = {-15: 1 / 32, -17: 1 / 32}
+
+
 @pytest.mark.parametrize("case", MSE_CASES, ids=[c["id"] for c in MSE_CASES])
-def test_mse_vs_reference_golden(ops, case):
+def test_mse_vs_reference_golden(ops, record_property, case):
     cid = case["id"]
     w = MSE[f"{cid}_w"]
-    frac, iters = check_case(ops, w, case["qtype"], case["strategy"], case["group_size"], case["symmetric"])
+    v, j = run_case(ops, record_property, w, case["qtype"], case["strategy"], case["group_size"], case["symmetric"],
+                    case["reduce_range"], max_undecided=GOLDEN_CEILING.get(case["scale_exp10"], 0.01), what=cid)
     # the oracle is itself pinned to the reference on these cases (tests/test_oracle_golden.py)
-    assert iters <= 20
+    assert j.stop <= 19
 
 
 @pytest.mark.parametrize("qtype,strategy,g,sym", [("uint4", "group", 128, False), ("int4", "group", 64, True),
                                                   ("int8", "channel", -1, False), ("uint8", "group", 32, False)])
-def test_mse_larger_matrices(ops, qtype, strategy, g, sym):
+def test_mse_larger_matrices(ops, record_property, qtype, strategy, g, sym):
     rng = np.random.default_rng(1000 + g + 7 * int(sym) + len(qtype))
     w = rng.standard_t(4, size=(512, 384)).astype(np.float32)
-    frac, iters = check_case(ops, w, qtype, strategy, g, sym)
-    assert 6 <= iters <= 20     # the global stop rule may or may not fire; check_case verified it fired identically
+    v, j = run_case(ops, record_property, w, qtype, strategy, g, sym, what=f"larger {qtype} {strategy} {g}")
+    assert 5 <= j.stop <= 19     # the global stop rule may or may not fire; run_case verified it fired identically
 
 
-def test_mse_early_stop_is_global(ops):
+def test_mse_early_stop_is_global(ops, record_property):
     """A single row (tensor strategy) whose error only gets worse when the range shrinks: the reference
     stops after iterations 0..5 (five stale ones).  The GPU must land on candidate 0 as well."""
     w = np.linspace(-1, 1, 256, dtype=np.float32).reshape(16, 16)
     trace = []
     O.min_max_mse(w, "int8", "tensor", False, False, trace=trace)
     assert len(trace) < 20
-    check_case(ops, w, "int8", "tensor", -1, False, max_swapped=0.0)
+    v, j = run_case(ops, record_property, w, "int8", "tensor", -1, False, what="early stop")
+    assert v.differing == 0 and v.undecided == 0 and j.stop_decided
 
 
 def test_mse_range_is_subset_of_minmax_range(ops):
@@ -122,3 +141,313 @@ def test_mse_full_size_smoke(ops):
     ratio = (s / s0).reshape(-1)
     grid = torch.tensor([1 - i / 100.0 for i in range(20)], device="cuda", dtype=torch.float32)
     assert bool(((ratio[:, None] - grid[None, :]).abs().amin(dim=1) < 1e-5).all())
+
+
+# ----------------------------------------------------------------------------------------------------------- the tensor strategy
+TENSOR_SHAPE = (1100, 1093)      # 1 202 300 elements: 4.6 passes of the 262 144 threads of mse_tensor_partial, N % 4 == 1
+
+
+@pytest.mark.parametrize("qtype,sym,seed", [("uint4", False, 12), ("int4", True, 11), ("uint8", False, 11), ("int8", True, 11)])
+def test_mse_tensor_strategy_beyond_one_pass(ops, record_property, qtype, sym, seed):
+    """More elements than `mse_tensor_partial` has threads, and not a multiple: its grid-stride loop, the loop of the single-block
+    `tensor_minmax_kernel` and all 1024 partials of `mse_tensor_mask` carry data.  Read through a view with a leading dimension of
+    N + 12 and a base offset of 16 bytes.  Seeds chosen on the CPU so that the one row is decided and, for the 4-bit types, its
+    winner is not candidate 0 (a kernel that always answers "candidate 0" fails here)."""
+    k, n = TENSOR_SHAPE
+    big = np.random.default_rng(seed).standard_normal((k, n + 12), dtype=np.float32)
+    wd, w = strided(big, 4, n)
+    v, j = run_case(ops, record_property, w, qtype, "tensor", -1, sym, wd=wd, what=f"tensor {qtype}")
+    assert j.decided[0] and j.stop_decided and v.differing == 0
+    if "4" in qtype:
+        assert j.winner[0] > 0
+
+
+# ----------------------------------------------------------------------------------------- reduce_range x symmetric, every kernel
+@pytest.mark.parametrize("g", [32, 64, 128, 16])
+@pytest.mark.parametrize("qtype", QTYPES)
+def test_mse_reduce_range_and_symmetric(ops, record_property, qtype, g):
+    """{symmetric, reduce_range} in {True, False}^2 on `mse_rows_reg_kernel<32 / 64 / 128>` and on the generic kernel (g = 16)."""
+    rng = np.random.default_rng(40 + g)
+    w = rng.standard_t(5, size=(256, 516)).astype(np.float32)
+    for sym in (False, True):
+        for red in (False, True):
+            run_case(ops, record_property, w, qtype, "group", g, sym, red, what=f"{qtype} g{g} sym{int(sym)} red{int(red)}")
+
+
+# ------------------------------------------------------------------------------------------------------- group sizes and widths
+# The band grows with the row length ((m - 1) 2^-24 for the sequential sum): from m = 256 on, 2 tau is 5e-5 to 8e-5, and on 4-bit
+# data that many rows have two candidates that close in the reference's OWN float64 table, on any seed.  Measured on the CPU on the
+# inputs below: g = 256 0 - 1.50 % (worst: 9 of 600), g = 512 0 - 2.92 % (15 of 514), K = 513 uint4 channels 2.67 % (8 of 300).
+# Those lengths get the ceiling below instead of 1 %; every shorter row, the whole column of K = 144 included, keeps the 1 %.
+LONG_ROW_CEILING = {256: 0.02, 512: 0.04, 513: 0.04}
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 300, 1028])
+@pytest.mark.parametrize("g,k", [(2, 64), (8, 64), (16, 128), (48, 96), (256, 512), (512, 1024), (-1, 144)])
+def test_mse_group_sizes_and_widths(ops, record_property, g, k, n):
+    """The generic `mse_rows_kernel` outside {32, 64, 128}, with N = 1 and N % 256 in {1, 255}; group -1 is the whole column."""
+    w = np.random.default_rng(7 * k + n + (g if g > 0 else 999)).standard_normal((k, n), dtype=np.float32)
+    ceiling = LONG_ROW_CEILING.get(g, 0.01)
+    run_case(ops, record_property, w, "uint4", "group", g, False, max_undecided=ceiling, what=f"g{g} {k}x{n}")
+    run_case(ops, record_property, w, "int4", "group", g, True, max_undecided=ceiling, what=f"g{g} {k}x{n} sym")
+
+
+@pytest.mark.parametrize("k", [33, 513])
+@pytest.mark.parametrize("qtype,sym", [("uint4", False), ("int8", True)])
+def test_mse_channel_with_odd_k(ops, record_property, k, qtype, sym):
+    w = np.random.default_rng(k).standard_t(4, size=(k, 300)).astype(np.float32)
+    run_case(ops, record_property, w, qtype, "channel", -1, sym, max_undecided=LONG_ROW_CEILING.get(k, 0.01),
+             what=f"channel K{k} {qtype}")
+
+
+@pytest.mark.parametrize("g", [128, 64, 32, 16, 48])
+@pytest.mark.parametrize("off", [4, 1])
+def test_mse_leading_dimension_and_misaligned_base(ops, record_property, g, off):
+    """Leading dimension N + 12 with a 16-byte (off = 4) and a 4-byte (off = 1) base offset, as
+    test_rtn_group_ragged_columns_vs_oracle does for RTN: `mse_rows_reg_kernel` builds its addresses from a 32-bit lane offset."""
+    k, n = (384 if g != 48 else 96 * 4), 300
+    big = np.random.default_rng(g * 10 + off).standard_normal((k, n + 12), dtype=np.float32)
+    wd, w = strided(big, off, n)
+    run_case(ops, record_property, w, "uint4", "group", g, False, wd=wd, what=f"ldw g{g} off{off}")
+
+
+# ---------------------------------------------------------------------------------------------------------------- entry points
+@pytest.mark.parametrize("strategy,g", [("group", 128), ("group", 16), ("channel", -1), ("tensor", -1)])
+def test_mse_parameters_only_and_clip_ratio(ops, strategy, g):
+    """`emit_q=False` (oq_rtn_qparams_f32) returns the parameters of the full call, and clip_ratio is ignored when mse is on
+    (utils.py:334-344: the searched range replaces the clipped one)."""
+    import torch
+    w = dev(np.random.default_rng(5).standard_t(4, size=(256, 260)).astype(np.float32))
+    for qtype, sym, red in (("uint4", False, False), ("int8", True, True)):
+        q, s, z = ops.rtn_quantize(w, qtype, strategy, g, sym, red, 1.0, True)
+        q2, s2, z2 = ops.rtn_quantize(w, qtype, strategy, g, sym, red, 1.0, True, emit_q=False)
+        assert q2 is None and torch.equal(s.view(torch.int32), s2.view(torch.int32)) and torch.equal(z, z2)
+        q3, s3, z3 = ops.rtn_quantize(w, qtype, strategy, g, sym, red, 0.8, True)
+        assert torch.equal(q, q3) and torch.equal(s.view(torch.int32), s3.view(torch.int32)) and torch.equal(z, z3)
+        _, s4, _ = ops.rtn_quantize(w, qtype, strategy, g, sym, red, 0.8, False)
+        assert not torch.equal(s4, s)
+
+
+def test_mse_refused_layouts_say_so(ops):
+    w = dev(np.random.default_rng(6).standard_normal((256, 64), dtype=np.float32))
+    with pytest.raises(Exception, match="NBITS layout with mse is not supported"):
+        ops.rtn_quantize(w, "uint4", "group", 128, mse=True, layout="nbits")
+    with pytest.raises(Exception, match="KN_PACKED4 layout needs .* no mse"):
+        ops.rtn_quantize(w, "uint4", "group", 128, mse=True, layout="kn_packed4")
+    with pytest.raises(Exception, match="mse with groups that straddle columns"):
+        ops.rtn_quantize(w[:96], "uint4", "group", 64, mse=True)           # 96 * 64 % 64 == 0 but K % g != 0
+
+
+# -------------------------------------------------------------------------------------------------------------- special values
+@pytest.mark.parametrize("g", [128, 16])
+def test_mse_zero_constant_positive_and_infinite_groups(ops, record_property, g):
+    k, n = 2 * g, 300
+    w = np.random.default_rng(60 + g).standard_normal((k, n), dtype=np.float32)
+    w[:g, 0:40] = 0.0                                  # all-zero groups: the tiny-scale guard, twenty identical candidates
+    w[g:, 40:80] = np.float32(0.37)                    # constant groups
+    w[:g, 80:120] = np.float32(-2.5)
+    w[:, 120:160] = np.abs(w[:, 120:160]) + 1          # strictly positive: lo0 = 0
+    w[:, 160:200] = -np.abs(w[:, 160:200]) - 1
+    w[3, 200:210] = np.inf                             # groups holding inf: every error is inf or NaN and loses against FLT_MAX
+    w[g + 5, 205:215] = -np.inf
+    for qtype, sym in (("uint4", False), ("int4", True), ("uint8", False)):
+        run_case(ops, record_property, w, qtype, "group", g, sym, what=f"special g{g} {qtype}")
+
+
+@pytest.mark.parametrize("strategy,g", [("group", 128), ("group", 16), ("channel", -1)])
+def test_mse_nan_weight_keeps_to_its_row(ops, record_property, strategy, g):
+    """A NaN weight: its row gets a NaN scale as in NumPy; every other row stays decided and exact, and the global stop is the one
+    of the same matrix without the NaN."""
+    w = np.random.default_rng(77).standard_normal((128, 260), dtype=np.float32)
+    _, j0, _ = reference(w, "uint4", strategy, g, False, False)
+    w2 = w.copy()
+    w2[70, 17] = np.nan
+    v, j = run_case(ops, record_property, w2, "uint4", strategy, g, False, what=f"nan {strategy} {g}")
+    assert v.nan_rows == 1 and j.stop == j0.stop and j.stop_decided
+
+
+# ---------------------------------------------------------------------------------------------------------------- the stop rule
+@pytest.mark.parametrize("k,n,seed,stop", [(256, 260, 0, 12), (64, 32, 36, 13), (32, 32, 22, 9)])
+def test_mse_stop_strictly_inside_the_walk(ops, record_property, k, n, seed, stop):
+    """uint4 g = 16 normal matrices whose oracle stops strictly between 5 and 19, at three different iterations (found on the CPU):
+    a kernel that cut the walk at another iteration moves the rows whose winner lies between the two cuts."""
+    w = np.random.default_rng(seed).standard_normal((k, n), dtype=np.float32)
+    v, j = run_case(ops, record_property, w, "uint4", "group", 16, False, what=f"stop {k}x{n}")
+    assert j.stop == stop and 5 < j.stop < 19 and j.stop_decided
+
+
+@pytest.mark.parametrize("kind,g,k,n,seed,stop,later,kept", [("normal", 16, 16, 4, 12, 7, 11, 1), ("normal", 32, 32, 4, 133, 8, 12, 3),
+                                                             ("t2", 32, 32, 8, 275, 11, 12, 5)])
+def test_mse_improvements_after_the_stop_are_ignored(ops, record_property, kind, g, k, n, seed, stop, later, kept):
+    """Small int4 symmetric matrices in which a DECIDED row's winner over the full walk (`later`) lies after the global stop, so the
+    row must keep an earlier candidate (`kept`): a kernel that walked on, or resolved rows without the stop, fails here.
+    Found by a bounded search on the CPU: seeds 0..299 of standard normal, Student t(2) and t(3) data, uint4 and symmetric int4,
+    g in {8, 16, 32}, shapes (g, 4), (g, 8), (2g, 8), (2g, 16); criterion: stop decided and strictly inside 5..19, no undecided row,
+    and a decided row whose full-walk minimum in the float64 table lies after the stop and beats the kept candidate by more than
+    2 tau.  13 of the 21 600 matrices qualify, all symmetric int4; the same search over uint4 g = 16 normal matrices of 32 x 32 to
+    128 x 64 (seeds 0..399) finds none.  g = 16 runs the generic kernel, g = 32 the register kernel."""
+    r = np.random.default_rng(seed)
+    w = (r.standard_normal((k, n)) if kind == "normal" else r.standard_t(2, size=(k, n))).astype(np.float32)
+    v, j = run_case(ops, record_property, w, "int4", "group", g, True, what=f"after the stop g{g} seed {seed}")
+    t = V.tables(w, "int4", "group", g, True, False)
+    cols = np.arange(v.rows)
+    full = np.argmin(t.e64, axis=0)
+    moved = (full > j.stop) & j.decided & (t.e64[full, cols] * (1 + 2 * t.tau) < t.e64[j.winner, cols])
+    assert j.stop == stop and j.stop_decided and v.undecided == 0 and v.differing == 0
+    assert moved.any() and int(full[moved][0]) == later and int(j.winner[moved][0]) == kept
+
+
+# ------------------------------------------------------------------------------------------------------------------ magnitudes
+MAGNITUDES = [-22, -20, -18, -17, -16, -15, -14, -12, -8, -4, 0, 4, 8, 12, 13, 14, 15, 16]
+# Share of rows the reference alone leaves undecided, measured on the CPU on the inputs below; 1 % wherever it is met.
+#   g = 16:  0 - 0.05 % (1 of 2080) at every exponent but two.  g = 128: 0 - 0.98 % for -22, -20, -16 and -4 .. 14.
+#   g = 128 at -15, -14, -12, -8, 15, 16: 1.04 - 1.30 % (20 of 1536).  Away from unit magnitude |log2 |d|| grows and tau_pow with it
+#            (3e-5 at 1e-15 against 9e-6 at 1), which puts that many rows inside 2 tau on any seed: ceiling 2 %.
+#   1e-17: the row sums are a few thousand subnormal ulps and the 4-ulp margin of the absolute rule ties 11.8 % of the rows at
+#            g = 128 (181 of 1536) and 43.1 % at g = 16 (896 of 2080): ceilings 15 % and 50 %.
+#   1e-18: the sums are about a dozen subnormal ulps; every candidate of every row lies within 4 ulps of the best in the reference's
+#            own table, so NO row and not the stop is decided (ceiling 100 %).  What is still asserted there: shapes and types;
+#            every row ends on a candidate of the reference's grid whose E32 is within 4 subnormal ulps of the row's best (and
+#            within the former 1e-4 rule); the integers of every row are exactly those of the candidate it ended on; rows on the
+#            oracle's candidate carry the oracle's integers.  Bit equality with the oracle is asserted for no row at 1e-18.
+MAGNITUDE_CEILING = {(128, -15): 0.02, (128, -14): 0.02, (128, -12): 0.02, (128, -8): 0.02, (128, 15): 0.02, (128, 16): 0.02,
+                     (128, -17): 0.15, (16, -17): 0.50, (128, -18): 1.0, (16, -18): 1.0}
+
+
+@pytest.mark.parametrize("e", MAGNITUDES)
+@pytest.mark.parametrize("g", [128, 16])
+def test_mse_magnitudes(ops, record_property, g, e):
+    """uint4 weights scaled by 10^e.  Below 1e-14 the terms |d|^2.4 are subnormal (the hardware log / exp units have no subnormals,
+    NumPy's power has); from 1e-16 down the row sums are subnormal too and the verdict's absolute rule applies; at 1e-22 everything
+    underflows and candidate 0 must stay.  At 1e16 some sums overflow to inf, which loses against FLT_MAX exactly as in NumPy."""
+    k, n = (512, 384) if g == 128 else (128, 260)
+    w = np.random.default_rng(5).standard_normal((k, n), dtype=np.float32)
+    w = (w * np.float32(10.0 ** e)).astype(np.float32)
+    run_case(ops, record_property, w, "uint4", "group", g, False, max_undecided=MAGNITUDE_CEILING.get((g, e), 0.01), what=f"1e{e} g{g}")
+
+
+@pytest.mark.parametrize("g,seed", [(128, 4), (16, 1)])
+def test_mse_tiny_and_ordinary_columns_in_one_wave(ops, record_property, g, seed):
+    """Odd columns at 1e-15, even columns at 1: every wave of the row kernels holds rows of both kinds, so the ordinary rows take the
+    shifted power path with a shift of 0 (and, at g = 128, the plain division in place of the reciprocal).  Their results must not
+    move: the case is judged like any other, and the even columns must equal the call on the even columns alone bit for bit
+    (seeds chosen on the CPU so that both matrices stop at the same iteration, 19 and 13: the stop is global)."""
+    import torch
+    w = np.random.default_rng(seed).standard_normal((2 * g, 320), dtype=np.float32)
+    w[:, 1::2] *= np.float32(1e-15)
+    run_case(ops, record_property, w, "uint4", "group", g, False, what=f"mixed wave g{g}")
+    q, s, z = ops.rtn_quantize(dev(w), "uint4", "group", g, mse=True)
+    q1, s1, z1 = ops.rtn_quantize(dev(w[:, 0::2]), "uint4", "group", g, mse=True)
+    kg = 2
+    assert reference(w, "uint4", "group", g, False, False)[1].stop == reference(w[:, 0::2], "uint4", "group", g, False, False)[1].stop
+    assert torch.equal(q[:, 0::2], q1)
+    assert torch.equal(s.reshape(-1, kg)[0::2].view(torch.int32), s1.reshape(-1, kg).view(torch.int32))
+    assert torch.equal(z.reshape(-1, kg)[0::2], z1.reshape(-1, kg))
+
+
+# --------------------------------------------------------------------------------------------------------------- property test
+def test_mse_random_configurations_against_the_oracle(ops, record_property):
+    """Property test in the style of test_random_configurations_against_the_oracle (hypothesis, fixed seed): qtype, strategy, g,
+    shape, symmetric, reduce_range, value kind and seed with mse=True, each example judged by the verdict.  The 1 % condition is
+    taken over the rows of the whole walk (tiny examples have few rows); `ties` and `zeros` are excluded from it by kind, because
+    half-integers make exact ties a property of the input."""
+    from hypothesis import HealthCheck, given, seed, settings, strategies as st
+    examples = int(os.environ.get("OQ_TEST_FUZZ_MSE_EXAMPLES", "150"))
+    totals = dict(rows=0, undecided=0, differing=0, cond_rows=0, cond_undecided=0)
+
+    @st.composite
+    def case(draw):
+        qtype = draw(st.sampled_from(QTYPES))
+        strategy = draw(st.sampled_from(["tensor", "channel", "group"]))
+        if strategy == "group":
+            g = draw(st.sampled_from([2, 8, 16, 24, 32, 64, 96, 128, 200, 256]))
+            k = g * draw(st.integers(1, 4))
+        else:
+            g, k = -1, draw(st.integers(1, 300))
+        n = draw(st.integers(1, 300))
+        sym, red = draw(st.booleans()), draw(st.booleans())
+        kind = draw(st.sampled_from(["normal", "wide", "tiny", "ties", "zeros", "positive"]))
+        return qtype, strategy, g, k, n, sym, red, kind, draw(st.integers(0, 2**31 - 1))
+
+    def make(kind, k, n, rs):
+        r = np.random.default_rng(rs)
+        w = r.standard_normal((k, n)).astype(np.float32)
+        if kind == "wide":
+            w *= np.float32(10.0) ** r.integers(-6, 7, size=(1, n)).astype(np.float32)
+        elif kind == "tiny":
+            w *= np.float32(1e-30)
+        elif kind == "ties":
+            w = (r.integers(-40, 41, size=(k, n)) * 0.5).astype(np.float32)
+        elif kind == "zeros":
+            w[r.random((k, n)) < 0.7] = 0
+            w[:, ::3] = 0
+        elif kind == "positive":
+            w = np.abs(w) + 1
+        return w
+
+    @seed(20240601 if examples == 150 else int(os.environ.get("OQ_TEST_FUZZ_SEED", "1")))
+    @settings(max_examples=examples, deadline=None, suppress_health_check=list(HealthCheck))
+    @given(case())
+    def run(c):
+        qtype, strategy, g, k, n, sym, red, kind, rs = c
+        w = make(kind, k, n, rs)
+        v, _ = run_case(ops, lambda *_: None, w, qtype, strategy, g, sym, red, max_undecided=1.0, what=str(c))
+        totals["rows"] += v.rows
+        totals["undecided"] += v.undecided
+        totals["differing"] += v.differing
+        if kind not in ("ties", "zeros"):
+            totals["cond_rows"] += v.rows
+            totals["cond_undecided"] += v.undecided
+
+    run()
+    for k, x in totals.items():
+        record_property(k, x)
+    print(f"[mse] property walk: {totals}")
+    assert totals["cond_undecided"] <= totals["cond_rows"] // 100, totals
+
+
+# --------------------------------------------------------------------------------------------------------------------- full size
+def test_mse_full_size_strips_vs_oracle(ops, record_property):
+    """4096 x 11008 uint4 g = 128 mse=True against the oracle on 64 strips of 32 columns, first and last included.  The search of
+    a strip alone equals the search of the full matrix up to the stop, which is global.  The full matrix's stop is derived twice:
+    the clearly improving iterations of the sampled strips, OR-ed, already leave fewer than five stale ones (more rows can only add
+    improvements), so it is 19; and the iterations on which sampled GPU rows end leave fewer than five unused as well.  Each strip
+    is then judged with that stop."""
+    import torch
+    k, n, g = 4096, 11008, 128
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    wd = torch.randn((k, n), generator=gen, device="cuda")
+    q, s, z = ops.rtn_quantize(wd, "uint4", "group", g, mse=True)
+    starts = sorted({0, n - 32} | {int(x) * 32 for x in np.random.default_rng(0).choice(n // 32, 62, replace=False)})
+    kg = k // g
+    s2, z2 = s.reshape(n, kg), z.reshape(n, kg)
+    strips = []
+    improving = np.zeros(O.MSE_STEPS, bool)
+    for c0 in starts:
+        w = wd[:, c0:c0 + 32].cpu().numpy()
+        t = V.tables(w, "uint4", "group", g, False, False)
+        improving |= np.array([x == 1 for x in V.judge(t).status])
+        strips.append((c0, w, t))
+    stop = V.stop_from_flags(improving)
+    assert stop == 19, "the sampled strips do not decide the stop of the full matrix"
+    rows = undecided = differing = 0
+    used = np.zeros(O.MSE_STEPS, bool)          # iterations on which some sampled GPU row ends: each of them improved that row
+    for c0, w, t in strips:
+        j = V.judge(t, stop=stop)
+        sg = s2[c0:c0 + 32].reshape(-1).cpu().numpy()
+        zg = z2[c0:c0 + 32].reshape(-1).cpu().numpy()
+        used |= ((t.scales.view(np.uint32) == sg.view(np.uint32)[None, :]) & (t.zps == zg[None, :])).any(axis=1)
+        # the oracle of the strip with the full matrix's stop: every row's first minimum of the reference's own table
+        first = np.argmin(t.e32[: stop + 1], axis=0)
+        es, ez = t.scales[first, np.arange(first.size)], t.zps[first, np.arange(first.size)]
+        eq = O.quantize(V.rows_of(w, "group", g), es.reshape(-1, 1), ez.reshape(-1, 1).astype(np.uint8), "uint4", False, False)
+        qs = q[:, c0:c0 + 32].cpu().numpy()
+        x_rows = V.rows_of(w, "group", g)
+        v = V.verdict(t, j, sg, zg, es, ez, V.rows_of(qs, "group", g), eq, f"strip {c0}",
+                      requantize=lambda row, sc, zp: O.quantize(x_rows[row], sc, int(zp), "uint4", False, False))
+        rows, undecided, differing = rows + v.rows, undecided + v.undecided, differing + v.differing
+    assert V.stop_from_flags(used) == 19, "the GPU rows leave five iterations unused: the kernel stopped early"
+    assert undecided <= rows // 100
+    for key, x in dict(rows=rows, undecided=undecided, differing=differing).items():
+        record_property(key, x)
+    print(f"[mse] full size strips: rows {rows} undecided {undecided} differing {differing}")

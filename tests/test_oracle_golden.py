@@ -107,11 +107,11 @@ def test_rtn_mse_bit_exact(case):
     cid = case["id"]
     w = MSE[f"{cid}_w"]
     rows = O.to_rows(w, case["strategy"], case["group_size"])
-    lo, hi = O.min_max_mse(rows, case["qtype"], case["strategy"], case["symmetric"], False)
+    lo, hi = O.min_max_mse(rows, case["qtype"], case["strategy"], case["symmetric"], case["reduce_range"])
     assert np.asarray(lo).tobytes() == MSE[f"{cid}_lo"].tobytes()
     assert np.asarray(hi).tobytes() == MSE[f"{cid}_hi"].tobytes()
     q, s, z = O.rtn_quantize(w, case["qtype"], case["strategy"], case["group_size"],
-                             case["symmetric"], False, 1.0, True)
+                             case["symmetric"], case["reduce_range"], 1.0, True)
     np.testing.assert_array_equal(q, MSE[f"{cid}_q"])
     assert s.tobytes() == MSE[f"{cid}_s"].tobytes()
     np.testing.assert_array_equal(z, MSE[f"{cid}_z"])
