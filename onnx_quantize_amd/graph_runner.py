@@ -1232,6 +1232,8 @@ class GraphRunner:
         if len(x) > 4 and x[4] is not None:
             raise UnsupportedOperator("GraphRunner: MatMulNBits with g_idx")
         w = ((q.to(torch.float32) - zpf[:, :, None]) * scales[:, :, None]).reshape(N, blocks * g)[:, :K]
+        if w.dtype != x[0].dtype:      # a half-precision A (its scales are stored in A's type): the product runs in A's type
+            w = w.to(x[0].dtype)
         out = x[0] @ w.t()
         if len(x) > 5 and x[5] is not None:
             out = out + x[5]

@@ -25,6 +25,10 @@ OQ_ERR_INVALID_ARGUMENT, OQ_ERR_UNSUPPORTED, OQ_ERR_WORKSPACE, OQ_ERR_LAUNCH, OQ
 QTYPE_CODE = {"int4": OQ_INT4, "uint4": OQ_UINT4, "int8": OQ_INT8, "uint8": OQ_UINT8,
               "int32": OQ_INT32, "uint32": OQ_UINT32}
 STRATEGY_CODE = {"tensor": OQ_TENSOR, "channel": OQ_CHANNEL, "group": OQ_GROUP}
+# include/oq_hip_half.h
+OQ_W_F16, OQ_W_BF16 = range(2)
+OQ_HALF_EXTENSION_VERSION = 1
+WTYPE_CODE = {"float16": OQ_W_F16, "bfloat16": OQ_W_BF16}
 
 
 class OqHipError(RuntimeError):
@@ -116,6 +120,13 @@ PROTOTYPES = {
     "oq_pack_nibbles": (_i32, [_p, _i64, _p, _p]),
 }
 
+# the half-precision extension: mirrors include/oq_hip_half.h one to one (tests/test_rtn_half_abi.py checks the set)
+HALF_PROTOTYPES = {
+    "oq_half_extension_version": (_i32, []),
+    "oq_rtn_half_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "oq_rtn_quantize_h16": (_i32, [_p, _i32, _i64, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _f32, _p, _p, _p, _i32, _p, _sz, _p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -142,7 +153,7 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:  # missing ROCm runtime etc.
             raise OqHipMissing(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in [*PROTOTYPES.items(), *HALF_PROTOTYPES.items()]:
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -151,6 +162,9 @@ def load() -> C.CDLL:
             fn.argtypes = args
         if lib.oq_abi_version() != OQ_ABI_VERSION:
             raise OqHipMissing(f"{LIB_PATH} has ABI {lib.oq_abi_version()}, expected {OQ_ABI_VERSION}")
+        if lib.oq_half_extension_version() != OQ_HALF_EXTENSION_VERSION:
+            raise OqHipMissing(f"{LIB_PATH} has half-precision extension {lib.oq_half_extension_version()}, "
+                               f"expected {OQ_HALF_EXTENSION_VERSION}")
         _lib = lib
     return _lib
 

@@ -139,17 +139,85 @@ def resolve_group(strategy: str, k: int, group_size) -> int:
     return k if g == -1 else g
 
 
+_HALF_WTYPE = {torch.float16: L.OQ_W_F16, torch.bfloat16: L.OQ_W_BF16}
+
+
+def _refuse_half(w, fn: str) -> None:
+    """The entry points that stay fp32-only say so by name instead of a bare dtype mismatch."""
+    if isinstance(w, torch.Tensor) and w.dtype in _HALF_WTYPE:
+        raise TypeError(f"{fn} takes fp32 weights only, got {w.dtype}: half-precision weights are served by rtn_quantize "
+                        f"(one matrix per call); convert with w.float() to use {fn}")
+
+
+def _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out):
+    """`rtn_quantize` on an fp16 / bf16 matrix through oq_rtn_quantize_h16 (csrc/rtn_half.hip): W is read as it is."""
+    if w.dim() != 2:
+        raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
+    _layout_code(layout)
+    if layout == "kn_packed4":
+        # no packed epilogue in the half kernels: the [K, N] route followed by the packer (the same bytes, core/_pack.py:8-22)
+        if out is not None:
+            raise ValueError("layout 'kn_packed4' of a half-precision matrix does not take `out`")
+        if not emit_q:
+            raise ValueError("layout 'kn_packed4' needs emit_q")
+        k, n = w.shape
+        g = resolve_group(strategy, k, group_size if group_size is not None else -1)
+        if BITS[qtype] != 4 or n % 2 or strategy != "group" or g > 256:
+            raise L.OqHipError(L.OQ_ERR_UNSUPPORTED, "KN_PACKED4 layout needs a 4-bit type, the group strategy with K % group_size == 0 "
+                                                     "and group_size <= 256, and an even number of columns")
+        q, scale, zp = _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, "kn", True, None)
+        return pack_nibbles(q).reshape(k, n // 2), scale, zp
+    w, ldw = _row_major(w)
+    k, n = w.shape
+    lib = L.load()
+    g = resolve_group(strategy, k, group_size if group_size is not None else -1)
+    if strategy == "group":
+        count, shape = (k * n) // g, ((k * n) // g, 1)
+    elif strategy == "channel":
+        count, shape = n, (n,)
+    else:
+        count, shape = 1, ()
+    dev = w.device
+    if out is not None:
+        q, scale, zp = out
+    else:
+        q = _q_buffer(layout, (), k, n, g, qtype, dev) if emit_q else None
+        scale = torch.empty(count, dtype=torch.float32, device=dev)
+        zp = torch.empty(count, dtype=container_dtype(qtype), device=dev)
+    gs = -1 if group_size is None else int(group_size)
+    ws = _workspace(lib.oq_rtn_half_workspace_bytes(k, n, L.STRATEGY_CODE[strategy], gs), dev)
+    L.check(lib.oq_rtn_quantize_h16(_ptr(w), _HALF_WTYPE[w.dtype], k, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
+                                    int(symmetric), int(reduce_range), float(clip_ratio), _ptr(q if emit_q else None), _ptr(scale),
+                                    _ptr(zp), _layout_code(layout), _ptr(ws), ws.numel(), _stream()))
+    return (q if emit_q else None), scale.reshape(shape), zp.reshape(shape)
+
+
 # ----------------------------------------------------------------------------- A1 / Q2
 def rtn_quantize(w: torch.Tensor, qtype: str, strategy: str, group_size=-1, symmetric=False,
                  reduce_range=False, clip_ratio=1.0, mse=False, layout: str = "kn", emit_q: bool = True,
                  out=None):
-    """rtn.py:54-109 on the GPU.  ``w`` [K, N] fp32 in HBM.
+    """rtn.py:54-109 on the GPU.  ``w`` [K, N] fp32, fp16 or bf16 in HBM.
 
     Returns (q, scale, zp) -- q [K, N] (layout "kn"), the MatMulNBits blob [N, K/g, g*bits/8] (layout "nbits") or
     [K, N/2] nibble pairs in core/_pack.py:8-22 order (layout "kn_packed4": 4-bit types, group strategy);
     scale/zp 0-d | [N] | [N*K/g, 1].  With ``emit_q=False`` q is None
     (utils.py:302-348 only).
+
+    A half-precision ``w`` gives, by definition, the result of this function on ``w.float()`` (both conversions are exact):
+    the same integers, zero points and fp32 scales, bit for bit.  Its routes:
+      - layouts "kn" / "nbits", any strategy, groups that divide K, no mse: oq_rtn_quantize_h16 reads the 2-byte matrix
+        as it is (one fused launch for groups of up to 256 rows, a range pass and a quantize pass otherwise);
+      - layout "kn_packed4": the "kn" route followed by `pack_nibbles`;
+      - ``mse=True`` and groups that straddle columns (K % group_size != 0) have no half kernel: ONE device cast,
+        ``w.float()``, then the fp32 path below.
     """
+    _require_device(w, "w")
+    if w.dtype in _HALF_WTYPE:
+        if w.dim() == 2:
+            g_h = resolve_group(strategy, w.shape[0], group_size if group_size is not None else -1)
+            if not mse and g_h > 0 and w.shape[0] % g_h == 0:
+                return _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out)
+        w = w.float()      # the documented cast route: mse, straddling groups
     _require_device(w, "w", torch.float32)
     if w.dim() != 2:
         raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
@@ -213,7 +281,11 @@ def hqq_quantize(w: torch.Tensor, group_size: int, reduce_range=False, clip_rati
                  kappa=1.01, iters=20, early_stop=True, emit_q: bool = True, layout: str = "kn", per_round_launches: bool = False):
     """hqq.py:147-213 on the GPU: uint4 / asymmetric / group with float zero points.  ``w`` [K, N] fp32 in HBM.
     Returns (q [K, N] uint8 | MatMulNBits blob [N, K/g, g/2] for layout="nbits" | None, scale [N*K/g, 1] fp32,
-    zero_point [N*K/g, 1] fp32, rounds int32[1] on device)."""
+    zero_point [N*K/g, 1] fp32, rounds int32[1] on device).  An fp16 / bf16 ``w`` takes one device cast, ``w.float()``
+    (exact): the arithmetic of HQQ stays fp32."""
+    _require_device(w, "w")
+    if w.dtype in _HALF_WTYPE:
+        w = w.float()
     _require_device(w, "w", torch.float32)
     if w.dim() != 2:
         raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
@@ -255,6 +327,7 @@ def rtn_quantize_tensor_many(ws, qtype: str, symmetric=False, reduce_range=False
         raise NotImplementedError("rtn_quantize_tensor_many: 4- and 8-bit types only")
     flats = []
     for w in ws:
+        _refuse_half(w, "rtn_quantize_tensor_many")
         _require_device(w, "w", torch.float32)
         flats.append(w if w.is_contiguous() else w.contiguous())
     dev = flats[0].device
@@ -282,6 +355,7 @@ def rtn_quantize_batched(w: torch.Tensor, qtype: str, group_size: int, symmetric
                          clip_ratio=1.0, layout: str = "kn", out=None):
     """rtn.py:54-109 for a stack of equally shaped weights ``w`` [B, K, N] in ONE launch (group strategy).
     Returns (q [B, K, N] | [B, N, K/g, g*bits/8], scale [B, N*K/g, 1], zp [B, N*K/g, 1])."""
+    _refuse_half(w, "rtn_quantize_batched")
     _require_device(w, "w", torch.float32)
     if w.dim() != 3 or not w.is_contiguous():
         raise ValueError("w must be a contiguous [B, K, N] tensor")
@@ -368,6 +442,7 @@ def rtn_quantize_many(ws, qtype: str, group_size: int, symmetric=False, reduce_r
         for i in idx:
             w = ws[i]
             if not (w.is_cuda and w.dtype is torch.float32 and w.device.index == cur_dev):
+                _refuse_half(w, "rtn_quantize_many")
                 _require_device(w, "w", torch.float32)      # raises with the full message
             if plain:                              # rows contiguous: the tensor as it is (the per-weight helper calls were a third of
                 w2, ldw = w, st0                   # this function's time on a 126-weight model)
@@ -1214,9 +1289,13 @@ def gptq_quantize(w: torch.Tensor, h: torch.Tensor, qtype: str, strategy: str, g
                   mode: str = "parity", shared=None, layout: str = "kn", method: str | None = None):
     """gptq.py:76-243 (`_gptq`) on device tensors: ``w`` [K, N] weights, ``h`` [K, K] accumulated Hessian.
     Neither input is modified.  Returns (q_int, scale, zp, info) with the reference's output shapes; ``layout``
-    "kn_packed4": q_int [K, N/2] as core/_pack.py:8-22 serialises the 4-bit result, written by the loop kernels."""
+    "kn_packed4": q_int [K, N/2] as core/_pack.py:8-22 serialises the 4-bit result, written by the loop kernels.
+    An fp16 / bf16 ``w`` takes one device cast, ``w.float()`` (exact): the arithmetic of GPTQ stays fp32."""
     if mode not in _LOOP_MODES:
         raise ValueError("mode must be 'parity' or 'corrected'")
+    _require_device(w, "W")
+    if w.dtype in _HALF_WTYPE:
+        w = w.float()
     _require_device(w, "W", torch.float32)
     _require_device(h, "H", torch.float32)
     k, n = w.shape

@@ -418,10 +418,11 @@ def _standardize_gemm(G: _Graph) -> None:
         n.attribute = [make_attribute("transB", 0)]
 
 
-def _target_nodes(G: _Graph, qconfig: QConfig) -> list:
+def _target_nodes(G: _Graph, qconfig: QConfig, half_native: bool = False) -> list:
     """calibrate.py:48-89 + the `check` methods of the rules (matmul_to_qmatmul.py:31-41, gemm_to_qgemm.py:13-44): op type
     selected, name not ignored, constant weight (and bias), Gemm with `transB = 0`.  Weights that are not matrices are left
-    alone (the numeric path is defined on [K, N])."""
+    alone (the numeric path is defined on [K, N]).  `half_native`: FLOAT16 matrices are targets too (`half_weights="native"`)."""
+    element_types = (DataType.FLOAT, DataType.FLOAT16) if half_native else (DataType.FLOAT,)
     ignores = [re.compile(p) for p in qconfig.ignore]
     out = []
     for n in G.g.node:
@@ -437,8 +438,11 @@ def _target_nodes(G: _Graph, qconfig: QConfig) -> list:
             continue
         if n.op_type == "Gemm" and _attr(n, "transB") != 0:
             continue
-        if len(G.inits[n.input[1]].dims) != 2 or G.inits[n.input[1]].data_type != DataType.FLOAT:
-            logger.warning("node '%s': weight '%s' is not a float32 matrix (the numeric path is defined on fp32 [K, N]); left as it is", n.name, n.input[1])
+        if len(G.inits[n.input[1]].dims) != 2 or G.inits[n.input[1]].data_type not in element_types:
+            if half_native:
+                logger.warning("node '%s': weight '%s' is not a float32 or float16 matrix; left as it is", n.name, n.input[1])
+            else:
+                logger.warning("node '%s': weight '%s' is not a float32 matrix (the numeric path is defined on fp32 [K, N]); left as it is", n.name, n.input[1])
             continue
         out.append(n)
     return out
@@ -793,12 +797,47 @@ class Prepared:
     """A model after the pre-passes: the graph view, the nodes to quantize, their calibration results and the per-node
     configurations a preprocessor changed (AWQ's clip ratio)."""
 
-    def __init__(self, model, graph, targets, meta, per_node):
+    def __init__(self, model, graph, targets, meta, per_node, half_targets=()):
         self.model, self.graph, self.targets, self.meta, self.per_node = model, graph, targets, meta, per_node
+        self.half_targets = set(half_targets)      # id(node) of the targets whose weight is a FLOAT16 matrix (`half_weights="native"`)
+
+
+HALF_WEIGHTS = ("error", "native")
+
+
+def _half_candidates(G: _Graph, qconfig: QConfig, element_types) -> list:
+    return [n.input[1] for n in G.g.node if not n.domain and n.op_type in qconfig.target_op_types and len(n.input) > 1 and n.input[1] in G.inits
+            and len(G.inits[n.input[1]].dims) == 2 and G.inits[n.input[1]].data_type in element_types]
+
+
+def _check_half_native(G: _Graph, qconfig: QConfig, targets) -> set:
+    """`half_weights="native"`: FLOAT16 [K, N] weights are quantized as they are by the MatMulNBits rule of a weight-only
+    configuration; everything else says what is unsupported."""
+    bf16 = _half_candidates(G, qconfig, (DataType.BFLOAT16,))
+    if bf16:
+        raise NotImplementedError(f"half_weights='native': '{bf16[0]}' is a BFLOAT16 initializer, which this package's ONNX codec has no NumPy "
+                                  "type for; FLOAT16 weights are supported (ops.rtn_quantize takes bf16 tensors on the device)")
+    half = [n for n in targets if G.inits[n.input[1]].data_type == DataType.FLOAT16]
+    if not half:
+        return set()
+    name = half[0].input[1]
+    if qconfig.input_activations is not None or qconfig.output_activations is not None:
+        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): activation quantization (the QDQ / QLinear rules with "
+                                  "activation arguments) is unsupported on half-precision models; only weight-only MatMulNBits is")
+    if qconfig.preprocessors:
+        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): preprocessors (AWQ / SmoothQuant) are unsupported on half-precision models")
+    if _needs_calibration(qconfig) or qconfig.calibration_data is not None:
+        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): calibrated configurations (calibration data, GPTQ) are "
+                                  "unsupported on half-precision models; only weight-only RTN through MatMulNBits is")
+    algorithm = getattr(qconfig.weights.algorithm, "algorithm_type", None)
+    if algorithm != "rtn":
+        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): the {algorithm} algorithm is unsupported on half-precision "
+                                  "models (HQQ keeps float zero points next to the scales); only weight-only RTN through MatMulNBits is")
+    return {id(n) for n in half}
 
 
 def apply_pre_passes(model, qconfig: QConfig, *, device="cuda", calibrate=None, searches=None, post_calibration="if_read",
-                     _defer_host_copies: bool = False) -> Prepared:
+                     _defer_host_copies: bool = False, half_weights: str = "error") -> Prepared:
     """quantize.py:50-59 + pre_passes/__init__.py:47-98: opset, names, duplicated initializers, MatMul + Add -> Gemm, Gemm with
     `transB = 0`, calibration, the preprocessors' passes and the calibration after them.  `post_calibration`: "if_read" skips
     the second calibration walk when nothing downstream reads its results (weight-only RTN behind AWQ / SmoothQuant: no static
@@ -806,8 +845,11 @@ def apply_pre_passes(model, qconfig: QConfig, *, device="cuda", calibrate=None, 
     model = as_model(model)
     if model.graph is None:
         raise ValueError("the model has no graph")
+    if half_weights not in HALF_WEIGHTS:
+        raise ValueError(f"half_weights must be one of {HALF_WEIGHTS}, got {half_weights!r}")
     G = _structural_passes(model)
-    targets = _target_nodes(G, qconfig)
+    targets = _target_nodes(G, qconfig, half_native=half_weights == "native")
+    half_targets = _check_half_native(G, qconfig, targets) if half_weights == "native" else set()
     if not targets:
         # an fp16 / bf16 export (the usual half-precision form) has constant MatMul / Gemm weights and not one fp32
         # matrix among them; returning it untouched with a success status would look like a quantized model
@@ -836,7 +878,7 @@ def apply_pre_passes(model, qconfig: QConfig, *, device="cuda", calibrate=None, 
     qconfig.calibration_data = None                         # pre_passes/__init__.py:90: the caller's configuration lets go of the data
     if not _defer_host_copies:
         G.materialize()
-    return Prepared(model, G, targets, meta, per_node)
+    return Prepared(model, G, targets, meta, per_node, half_targets)
 
 
 def _on(device):
@@ -853,19 +895,27 @@ def _on(device):
 
 
 def quantize_model(model, qconfig: QConfig, *, device="cuda", weight_arrays=None, quantize_bias=None, calibrate=None,
-                   searches=None) -> Message:
+                   searches=None, half_weights: str = "error") -> Message:
     """quantize.py:28-80 on a parsed ModelProto / ONNX bytes / a path.  Returns a new parsed ModelProto (`onnx_proto.serialize`
     gives the file).  `weight_arrays` / `quantize_bias` / `calibrate` / `searches`: the numeric providers (default: the
     device-resident seam, the HIP bias kernel, the on-device calibration walk `_calibrate` and `DeviceSearches`; tests inject
     the oracle).  `calibrate(model, graph view, target nodes, qconfig, device, keep_inputs=False)` returns {id(node): meta}
-    like `_calibrate`."""
+    like `_calibrate`.
+
+    `half_weights`: "error" (default) refuses a model whose constant MatMul / Gemm weights are half precision by name;
+    "native" quantizes FLOAT16 [K, N] weights as they are (the 2-byte matrix goes to the device and the RTN kernel reads it)
+    where the configuration is weight-only and the rule is the MatMulNBits one (QUInt4 / QUInt8 group-wise).  The emitted
+    node carries the blob and zero points of the fp32 copy of the weight and the scales as FLOAT16 -- `np.float16(scale32)`,
+    round to nearest even, of the fp32 scale the integers were made with.  Everything else on a
+    half-precision weight raises NotImplementedError and says what is unsupported."""
     if not isinstance(qconfig, QConfig):
         raise TypeError(f"qconfig must be a QConfig, got {type(qconfig)}")
     if qconfig.weights is None and qconfig.input_activations is None and qconfig.output_activations is None:
         logger.info("No quantization parameters specified in qconfig. Returning original model.")
         return as_model(model)
     with _on(device):
-        prepared = apply_pre_passes(model, qconfig, device=device, calibrate=calibrate, searches=searches, _defer_host_copies=weight_arrays is None)
+        prepared = apply_pre_passes(model, qconfig, device=device, calibrate=calibrate, searches=searches, _defer_host_copies=weight_arrays is None,
+                                    half_weights=half_weights)
         return _emit(prepared, qconfig, weight_arrays if weight_arrays is not None else _PackedSeam(), quantize_bias)
 
 
@@ -920,7 +970,17 @@ def _emit(prepared: Prepared, qconfig: QConfig, weight_arrays, quantize_bias) ->
         in_channels = int(G.inits[w_name].dims[0])
         plan = _plan(prepared, node, qconfig, weight_arrays, quantize_bias, on_device=isinstance(weight_arrays, _PackedSeam) or getattr(weight_arrays, "on_device", False))
         packed = getattr(weight_arrays, "packed", {})
+        is_half = id(node) in prepared.half_targets
+        if is_half and plan.call["name"] != "MatMulNBits":
+            raise NotImplementedError(f"half_weights='native': node '{node.name}' (weight '{w_name}', FLOAT16) would be rewritten by the "
+                                      f"{plan.call['name']} rule; on half-precision weights only the MatMulNBits rule (QUInt4 / QUInt8, "
+                                      "group-wise, a power-of-two group of at least 16) is supported, the QDQ / QLinear rules are not")
         for name, array in plan.initializers:
+            if is_half and name == f"{w_name}/scale":
+                # MatMulNBits takes its scales in the activation's type: the fp32 scale the integers were made with, rounded to
+                # nearest even (a scale below the fp16 normal range loses bits or becomes zero: DESIGN.md 4.14)
+                with np.errstate(over="ignore"):
+                    array = np.asarray(array, dtype=np.float32).astype(np.float16)
             if name != w_name and name in G.inits and (readers.get(name, 0) > 1 or name in G.graph_outputs):
                 raise ValueError(f"node '{node.name}': the initializer '{name}' it rewrites is a graph output or is read elsewhere and could "
                                  "not be duplicated; remove it from the graph's inputs / outputs or ignore this node")
@@ -1045,7 +1105,8 @@ def _quantize_sharded(model, qconfig, group, device, weight_arrays, quantize_bia
 def quantize_file(src, dst, qconfig: QConfig, external_data="auto", **kw) -> Message:
     """Read `src` (tensors in side files are memory-mapped, not read), quantize, write `dst`.  `external_data`: a file name
     next to `dst` for the tensors, None for one file with everything inline, "auto" (default): `<dst name>.data` when the
-    source kept its tensors outside or the result would pass 1 GiB, inline otherwise.  Returns the quantized model."""
+    source kept its tensors outside or the result would pass 1 GiB, inline otherwise.  Every other keyword goes to
+    `quantize_model` -- `half_weights="native"` among them, for a file whose weights are FLOAT16.  Returns the quantized model."""
     from .onnx_proto import resolve_external_data
     src_model = load_model(src, load_external_data=False)
     had_external = resolve_external_data(src_model, os.path.dirname(os.path.abspath(os.fspath(src)))) > 0

@@ -25,9 +25,10 @@ __all__ = ["quantize"]
 logger = logging.getLogger("onnx_quantize")
 
 
-def quantize(model, qconfig: QConfig):
+def quantize(model, qconfig: QConfig, *, half_weights: str = "error"):
     """Same signature and error behaviour as the reference: TypeError for anything that is not a model; the model is
-    returned unchanged when ``qconfig`` selects nothing to quantize."""
+    returned unchanged when ``qconfig`` selects nothing to quantize.  ``half_weights="native"`` (this package's own writer
+    only): FLOAT16 weights are quantized as they are by the weight-only MatMulNBits rule (`model_quantize.quantize_model`)."""
     from .onnx_proto import Message, serialize
 
     own_input = isinstance(model, (bytes, bytearray, memoryview, str, os.PathLike)) or \
@@ -39,9 +40,12 @@ def quantize(model, qconfig: QConfig):
         if nothing and not isinstance(model, (str, os.PathLike)):
             logger.info("Nothing to quantize: returning the model unchanged.")
             return model
-        out = quantize_model(model, qconfig)
+        out = quantize_model(model, qconfig, half_weights=half_weights)
         return serialize(out) if isinstance(model, (bytes, bytearray, memoryview)) else out
 
+    if half_weights != "error":
+        raise NotImplementedError("half_weights is an option of this package's own writer: pass ONNX bytes, a path or a model parsed by "
+                                  "onnx_quantize_amd.onnx_proto.parse_model")
     try:
         import onnx
     except ImportError as e:

@@ -157,7 +157,8 @@ def _strategy(s) -> str:
 def _upload(name, array):
     from .staging import upload
 
-    return upload(array)
+    # an fp16 weight goes up as it is: RTN reads the 2-byte matrix (ops.rtn_quantize), GPTQ / HQQ cast it once on the device
+    return upload(array, keep_half=True)
 
 
 def _host(t, dtype=None):
@@ -226,11 +227,12 @@ def weight_arrays(w, qconfig, out=None, is_matmul_nbits_compatible: bool = False
     res = None
     if w_np.ndim == 2 and getattr(a.algorithm, "algorithm_type", None) in ("rtn", "hqq", "gptq"):
         resident = getattr(w, "device_value", None)      # a caller that already holds this weight in HBM (the file path's
-        if resident is not None and (tuple(resident.shape) != tuple(w_np.shape) or str(resident.dtype) != "torch.float32"   # calibration walk)
+        if resident is not None and (tuple(resident.shape) != tuple(w_np.shape)                                           # calibration walk)
+                                     or str(resident.dtype) not in ("torch.float32", "torch.float16", "torch.bfloat16")
                                      or not resident.is_cuda or not resident.is_contiguous()):
             resident = None
         if resident is None and getattr(w, "placeholder", False):      # the host array of such a value is zeros that carry the shape
-            raise RuntimeError(f"'{w.name}': the weight lives in HBM only and its device copy cannot be used ({'missing' if getattr(w, 'device_value', None) is None else 'not contiguous fp32 of the declared shape'})")
+            raise RuntimeError(f"'{w.name}': the weight lives in HBM only and its device copy cannot be used ({'missing' if getattr(w, 'device_value', None) is None else 'not a contiguous fp32 / fp16 / bf16 tensor of the declared shape'})")
         res = _device_algorithm(resident if resident is not None else _upload(w.name, w_np), w.name, qconfig, out, is_matmul_nbits_compatible,
                                 want_packed4=packed4 and not is_matmul_nbits_compatible)
     if res is None:        # an algorithm plugin without kernels here: its own NumPy route, then the wire format on the GPU

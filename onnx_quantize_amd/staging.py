@@ -114,14 +114,15 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def upload(a: np.ndarray):
+def upload(a: np.ndarray, keep_half: bool = False):
     """fp32 C-contiguous copy of ``a`` in HBM, ordered on the current stream.  The copy is blocking (pageable source):
-    when this returns the bytes have left ``a`` (and any temporary made of it)."""
+    when this returns the bytes have left ``a`` (and any temporary made of it).  ``keep_half``: an fp16 array travels as
+    its 2-byte elements (half the bytes over the host link) for the kernels that read them directly."""
     import torch
 
     import warnings
 
-    src = np.ascontiguousarray(a, dtype=np.float32)
+    src = np.ascontiguousarray(a, dtype=np.float16 if keep_half and a.dtype == np.float16 else np.float32)
     with warnings.catch_warnings():
         # a read-only source (a view into the bytes of a model file, model_quantize.py) is only read here
         warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
