@@ -72,6 +72,7 @@ class HessianAccumulator:
         self.n = 0
 
     def add(self, x) -> None:
+        """``x`` [samples, ..., K] fp32, fp16 or bf16 in HBM; a half tensor is read as it is (no upcast, `ops.hessian_accumulate`)."""
         from .hip import ops
         self.n = ops.hessian_accumulate(x, self.h, self.n)
 
@@ -108,8 +109,9 @@ class ActivationStream:
         self._held_bytes = 0
         self._search_inputs: dict = {}
         self.hessians: dict[str, HessianAccumulator] = {}
-        # 0 (default): the Hessian updates of a batch in one grouped launch chain (per-tensor calls on 4 side streams when a
-        # Hessian method the grouped chain does not run is selected); n > 0: per-tensor calls on n side streams
+        # 0 (default): the Hessian updates of a batch in one grouped launch chain (per-tensor calls on 4 side streams for fp16 /
+        # bf16 activations and when a Hessian method the grouped chain does not run is selected); n > 0: per-tensor calls on n
+        # side streams
         self.hessian_streams = max(0, int(hessian_streams))
         self._side = None
         self.absmax: dict = {}
@@ -141,40 +143,45 @@ class ActivationStream:
             else:
                 self.calibrator.collect_many(activations)
         wanted = sorted(self.hessian_names & activations.keys())
+        # fp16 / bf16 activations go to the Hessian as they are (ops.hessian_accumulate reads the 2-byte tensor: one exact
+        # matrix-core product, no fp32 copy); there is no grouped half chain, so they take the per-tensor side-stream route
+        half = [name for name in wanted if activations[name].dtype in (torch.float16, torch.bfloat16)]
+        full = [name for name in wanted if name not in half]
         streams = self.hessian_streams
-        if wanted and streams == 0 and ops.hessian_method() not in ("auto", "f16x3"):
+        if full and streams == 0 and ops.hessian_method() not in ("auto", "f16x3"):
             streams = 4      # the grouped chain runs the fp16-piece kernels only: other methods would become serial per-tensor
                              # calls on one stream, so they take the side-stream route below
-        if wanted and streams == 0:
+        grouped, per_tensor = (full, half) if streams == 0 else ([], wanted)
+        if grouped:
             # one launch chain for all tapped inputs of the batch (ops.hessian_accumulate_many): a batch of a small model is
             # 72 tensors of 6 to 36 product tiles each, launch-bound and never filling the chip one at a time
             xs = []
-            for name in wanted:
+            for name in grouped:
                 x = activations[name]
                 x32 = x if x.dtype == torch.float32 else x.to(torch.float32)
                 if name not in self.hessians:
                     self.hessians[name] = HessianAccumulator(x32.shape[-1], x32.device)
                 xs.append(x32)
-            accs = [self.hessians[name] for name in wanted]
+            accs = [self.hessians[name] for name in grouped]
             for acc, n in zip(accs, ops.hessian_accumulate_many(xs, [a.h for a in accs], [a.n for a in accs])):
                 acc.n = n
-        elif wanted:
-            # per-tensor calls spread over a few side streams (fork / join by events): the route for the Hessian methods
-            # the grouped call does not run (hessian_streams > 0 selects it)
+        if per_tensor:
+            # per-tensor calls spread over a few side streams (fork / join by events): the route for half-precision activations
+            # and for the Hessian methods the grouped call does not run (hessian_streams > 0 selects it for everything)
             cur = torch.cuda.current_stream()
             if self._side is None:
-                self._side = [torch.cuda.Stream(device=activations[wanted[0]].device) for _ in range(streams)]
+                self._side = [torch.cuda.Stream(device=activations[per_tensor[0]].device) for _ in range(streams or 4)]
             fork = cur.record_event()
-            for i, name in enumerate(wanted):
+            for i, name in enumerate(per_tensor):
                 x = activations[name]
                 side = self._side[i % len(self._side)] if self._side else cur
                 side.wait_event(fork)
                 with torch.cuda.stream(side):
-                    x32 = x if x.dtype == torch.float32 else x.to(torch.float32)
+                    xh = x if x.dtype in (torch.float32, torch.float16, torch.bfloat16) else x.to(torch.float32)
                     acc = self.hessians.get(name)
                     if acc is None:
-                        acc = self.hessians[name] = HessianAccumulator(x32.shape[-1], x32.device)
-                    acc.add(x32)
+                        acc = self.hessians[name] = HessianAccumulator(xh.shape[-1], xh.device)
+                    acc.add(xh)
                 x.record_stream(side)
             for side in self._side:
                 cur.wait_stream(side)

@@ -1,6 +1,8 @@
 // fp32 TN GEMM on v_mfma_f32_32x32x2_f32 (see gemm_tn.hpp) and G1, the GPTQ Hessian accumulate.
 #include "gemm_tn.hpp"
 
+#include "../../include/oq_hip_half.h"
+
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -404,6 +406,34 @@ int32_t oq_hessian_accumulate_f32(const float* X, int64_t T, int64_t K, int64_t 
     // gptq.py:257  inp = math.sqrt(2 / num_samples) * inp  (double evaluated, weak scalar -> fp32 multiply)
     const float sx = static_cast<float>(std::sqrt(2.0 / static_cast<double>(n_total)));
     return launch_syrk_tn(X, T, K, ldx, sx, 1.0f, beta, H, workspace, workspace_bytes, as_stream(stream));
+}
+
+// G1 on activations that are fp16 / bf16 (include/oq_hip_half.h): the same update on the exact fp32 values of X, X read as it is.
+size_t oq_hessian_half_workspace_bytes(int64_t T, int64_t K) {
+    if (!matrix_ok(T, K, K) || K > kMaxHessianWidth) {
+        set_error("oq_hessian_half_workspace_bytes: bad shape T=%lld K=%lld", (long long)T, (long long)K);
+        return 0;
+    }
+    return syrk_h16_pieces_bytes(T, K) + hessian_slab_budget(K) + 512;
+}
+
+int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype, int64_t T, int64_t K, int64_t ldx, int64_t n_seen, int64_t n_add, float* H,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    // every check before any arithmetic on an extent and before any HIP call
+    OQ_REQUIRE(xtype == OQ_W_F16 || xtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: unknown xtype %d", xtype);
+    OQ_REQUIRE(X != nullptr && H != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: null X / H");
+    OQ_REQUIRE((reinterpret_cast<uintptr_t>(X) & 1u) == 0 && (reinterpret_cast<uintptr_t>(H) & 3u) == 0, OQ_ERR_INVALID_ARGUMENT,
+               "oq_hessian_accumulate_h16: X must be 2-byte aligned and H 4-byte aligned");
+    OQ_REQUIRE(T > 0 && K > 0 && ldx >= K, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: bad shape T=%lld K=%lld ldx=%lld", (long long)T,
+               (long long)K, (long long)ldx);
+    OQ_REQUIRE(matrix_ok(T, K, ldx) && K <= kMaxHessianWidth, OQ_ERR_UNSUPPORTED, "oq_hessian_accumulate_h16: operand too large (T=%lld K=%lld ldx=%lld)",
+               (long long)T, (long long)K, (long long)ldx);
+    OQ_REQUIRE(n_seen >= 0 && n_add > 0 && n_seen <= kMaxSamples && n_add <= kMaxSamples, OQ_ERR_INVALID_ARGUMENT,
+               "oq_hessian_accumulate_h16: bad sample counts %lld + %lld", (long long)n_seen, (long long)n_add);
+    const int64_t n_total = n_seen + n_add;
+    const float beta = n_seen == 0 ? 0.0f : static_cast<float>(static_cast<double>(n_seen) / static_cast<double>(n_total));   // gptq.py:254
+    const float alpha = static_cast<float>(2.0 / static_cast<double>(n_total));   // 2 / n on the sum, as the piece methods of oq_hessian_accumulate_f32
+    return launch_syrk_h16(X, xtype == OQ_W_BF16, T, K, ldx, alpha, beta, H, workspace, workspace_bytes, as_stream(stream));
 }
 
 // G1 for the tensors of one calibration batch (calibrate.py:292-305 hands `_accumulate_hessian` one input per node): one

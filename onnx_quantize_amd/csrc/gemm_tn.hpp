@@ -89,6 +89,13 @@ int32_t launch_syrk_bf16x3(const float* X, int64_t T, int64_t K, int64_t ldx, fl
 int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, unsigned char* base, float* slab,
                            size_t slab_bytes, int terms, int phases, hipStream_t s);   // phases: 1 = X -> pieces, 2 = pieces -> C, 3 = both
 
+// The same update for an X that IS fp16 / bf16 (syrk_bf16x3.hip, section 4): X is packed as it is (2 bytes per element) and every
+// pair of elements meets in ONE matrix-core product with fp32 accumulation.  workspace = the packed operand
+// (syrk_h16_pieces_bytes) + 256, followed by optional T-slice slabs of K x K floats.
+size_t syrk_h16_pieces_bytes(int64_t T, int64_t K);
+int32_t launch_syrk_h16(const void* X, bool bf16, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, void* workspace,
+                        size_t workspace_bytes, hipStream_t s);
+
 // Many Hessian updates in one launch chain (syrk_bf16x3.hip, section 2c).  items: int64 {X, H, T, K, ldx, n_seen, n_add, 0} each.
 size_t syrk_f16x3_many_workspace_bytes(const int64_t* items_host, int64_t count);
 int32_t launch_syrk_f16x3_many(const int64_t* items_host, const int64_t* items_device, int64_t count, void* workspace, size_t workspace_bytes,

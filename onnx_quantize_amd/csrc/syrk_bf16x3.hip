@@ -551,6 +551,11 @@ constexpr int kHiStage = 2 * kHiPlane;        // A | B
 constexpr int kHiRing = 4;
 static_assert(kHiRing * kHiStage <= StageGeom<3>::LDS, "the hi-only ring fits the LDS reserved for the generic loop");
 
+// FRAG: f16x8 (the first fp16 pieces) or bf16x8 (section 4: bf16 activations as they are); the same 16x16x32 operand layout.
+__device__ __forceinline__ void mfma_m16(const f16x8& x, const f16x8& y, f32x4v& c) { c = __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); }
+__device__ __forceinline__ void mfma_m16(const bf16x8& x, const bf16x8& y, f32x4v& c) { c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, y, c, 0, 0, 0); }
+
+template <typename FRAG = f16x8>
 __device__ __forceinline__ void f16_hi_mainloop(const char* const (&gsrc)[4], const int64_t (&stage_bytes)[4], const int64_t nstages,
                                                 unsigned char* lds, f32x4v (&acc)[4][8]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -582,17 +587,17 @@ __device__ __forceinline__ void f16_hi_mainloop(const char* const (&gsrc)[4], co
     const uint32_t rd_a = static_cast<uint32_t>((kc * kST + wm * 64 + cl) * 16);
     const uint32_t rd_b = static_cast<uint32_t>(kHiPlane + (kc * kST + wn * 128 + cl) * 16);
     int cur = 0;
-    f16x8 a[4], b[2];
+    FRAG a[4], b[2];
     {   // the first operands of stage 0
-        a[0] = *reinterpret_cast<const f16x8*>(lds + rd_a);
-        b[0] = *reinterpret_cast<const f16x8*>(lds + rd_b);
+        a[0] = *reinterpret_cast<const FRAG*>(lds + rd_a);
+        b[0] = *reinterpret_cast<const FRAG*>(lds + rd_b);
     }
     for (int64_t s = 0; s < nstages; ++s) {
         int wr = cur + kHiRing - 1;
         wr = wr >= kHiRing ? wr - kHiRing : wr;
         const unsigned char* base = lds + cur * kHiStage;
 #pragma unroll
-        for (int i = 1; i < 4; ++i) a[i] = *reinterpret_cast<const f16x8*>(base + rd_a + i * 16 * 16);
+        for (int i = 1; i < 4; ++i) a[i] = *reinterpret_cast<const FRAG*>(base + rd_a + i * 16 * 16);
         stage_dma(s + kHiRing - 1, wr);                  // slot `wr` was multiplied in stage s - 1: everybody has passed its barrier
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -600,10 +605,10 @@ __device__ __forceinline__ void f16_hi_mainloop(const char* const (&gsrc)[4], co
             for (int i = 0; i < 4; ++i) {
                 if (i == 1 && j < 7) {
                     __builtin_amdgcn_sched_barrier(0);
-                    b[(j + 1) & 1] = *reinterpret_cast<const f16x8*>(base + rd_b + (j + 1) * 16 * 16);
+                    b[(j + 1) & 1] = *reinterpret_cast<const FRAG*>(base + rd_b + (j + 1) * 16 * 16);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], b[j & 1], acc[i][j], 0, 0, 0);
+                mfma_m16(a[i], b[j & 1], acc[i][j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -611,8 +616,8 @@ __device__ __forceinline__ void f16_hi_mainloop(const char* const (&gsrc)[4], co
         __builtin_amdgcn_s_barrier();
         cur = cur + 1 == kHiRing ? 0 : cur + 1;
         // the next stage's first operands right behind the barrier (the last stage re-reads a slot that holds a copy of it)
-        a[0] = *reinterpret_cast<const f16x8*>(lds + cur * kHiStage + rd_a);
-        b[0] = *reinterpret_cast<const f16x8*>(lds + cur * kHiStage + rd_b);
+        a[0] = *reinterpret_cast<const FRAG*>(lds + cur * kHiStage + rd_a);
+        b[0] = *reinterpret_cast<const FRAG*>(lds + cur * kHiStage + rd_b);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the re-reads past the end: the epilogue reuses the ring
     __builtin_amdgcn_s_barrier();
@@ -664,38 +669,12 @@ __device__ __forceinline__ void staged_tile_epilogue(const f32x4v (&acc)[4][8], 
     }
 }
 
-// `tile`: the block's (XCD-remapped) index among the upper-triangle tiles of this matrix; `slice`: its T-slice
-__device__ __forceinline__ void syrk_f16_m16_body(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all,
-                                                  const float alpha_in, const float beta, float* __restrict__ C,
-                                                  float* __restrict__ slab, const int64_t stages_per_slice, const int ntiles,
-                                                  const float* __restrict__ post_scale, const int tile, const int64_t slice, unsigned char* lds,
-                                                  const int64_t ldc,    // leading dimension of C (slabs are always K x K)
-                                                  const bool mirror_all = true) {   // false: only diagonal tiles write their lower half
-    using G = StageGeom<3>;
-    constexpr int PIECES = 2, CH = 4, NDMA = G::NDMA;
-    const float alpha = post_scale ? alpha_in * post_scale[1] : alpha_in;
-    int tile_m, tile_n;
-    upper_tile_of(tile, ntiles, tile_m, tile_n);
+// A symmetric product's 256 x 256 accumulator tile -> C (alpha, beta, both triangles) or, with T-slices, -> the slice's slab as it is
+// (the reduction applies alpha / beta and the symmetry).  Shared by the fp16-piece SYRK and the half-precision SYRK of section 4.
+__device__ __forceinline__ void syrk_tile_store(const f32x4v (&acc)[4][8], unsigned char* lds, const int tile_m, const int tile_n, const int64_t K,
+                                                const float alpha, const float beta, float* __restrict__ C, float* __restrict__ slab,
+                                                const int64_t slice, const int64_t ldc, const bool mirror_all) {
     const int64_t m0 = static_cast<int64_t>(tile_m) * kST, n0 = static_cast<int64_t>(tile_n) * kST;
-    const int64_t s_begin = slice * stages_per_slice;
-    const int64_t s_end = s_begin + stages_per_slice < nstages_all ? s_begin + stages_per_slice : nstages_all;
-    const int64_t nstages = s_end - s_begin;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-
-    const char* gsrc[8];
-    int64_t stage_bytes[8];
-#pragma unroll
-    for (int i = 0; i < NDMA; ++i) {
-        const int q = wave * NDMA + i;
-        const int quarter = q & 3, cc = (q >> 2) % CH, pc = (q / (4 * CH)) % PIECES, op = q / (4 * CH * PIECES);
-        const int64_t colq = (op ? n0 : m0) + quarter * 64 + lane;
-        gsrc[i] = reinterpret_cast<const char*>(P + ((s_begin * CH + cc) * PIECES + pc) * Kp + colq);
-        stage_bytes[i] = static_cast<int64_t>(CH) * PIECES * Kp * 16;
-    }
-    f32x4v acc[4][8];
-    f16_m16_mainloop<NDMA>(gsrc, stage_bytes, nstages, lds, acc);
-
     float* out = slab ? slab + slice * K * K : C;
     const bool direct = slab == nullptr;
     const int64_t ld = direct ? ldc : K;
@@ -740,6 +719,41 @@ __device__ __forceinline__ void syrk_f16_m16_body(const u32x4* __restrict__ P, c
     };
     if (direct && (diag || mirror_all)) staged_tile_epilogue<true>(acc, lds, rows, cols);
     else staged_tile_epilogue<false>(acc, lds, rows, cols);
+}
+
+// `tile`: the block's (XCD-remapped) index among the upper-triangle tiles of this matrix; `slice`: its T-slice
+__device__ __forceinline__ void syrk_f16_m16_body(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all,
+                                                  const float alpha_in, const float beta, float* __restrict__ C,
+                                                  float* __restrict__ slab, const int64_t stages_per_slice, const int ntiles,
+                                                  const float* __restrict__ post_scale, const int tile, const int64_t slice, unsigned char* lds,
+                                                  const int64_t ldc,    // leading dimension of C (slabs are always K x K)
+                                                  const bool mirror_all = true) {   // false: only diagonal tiles write their lower half
+    using G = StageGeom<3>;
+    constexpr int PIECES = 2, CH = 4, NDMA = G::NDMA;
+    const float alpha = post_scale ? alpha_in * post_scale[1] : alpha_in;
+    int tile_m, tile_n;
+    upper_tile_of(tile, ntiles, tile_m, tile_n);
+    const int64_t m0 = static_cast<int64_t>(tile_m) * kST, n0 = static_cast<int64_t>(tile_n) * kST;
+    const int64_t s_begin = slice * stages_per_slice;
+    const int64_t s_end = s_begin + stages_per_slice < nstages_all ? s_begin + stages_per_slice : nstages_all;
+    const int64_t nstages = s_end - s_begin;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+    const char* gsrc[8];
+    int64_t stage_bytes[8];
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
+        const int q = wave * NDMA + i;
+        const int quarter = q & 3, cc = (q >> 2) % CH, pc = (q / (4 * CH)) % PIECES, op = q / (4 * CH * PIECES);
+        const int64_t colq = (op ? n0 : m0) + quarter * 64 + lane;
+        gsrc[i] = reinterpret_cast<const char*>(P + ((s_begin * CH + cc) * PIECES + pc) * Kp + colq);
+        stage_bytes[i] = static_cast<int64_t>(CH) * PIECES * Kp * 16;
+    }
+    f32x4v acc[4][8];
+    f16_m16_mainloop<NDMA>(gsrc, stage_bytes, nstages, lds, acc);
+
+    syrk_tile_store(acc, lds, tile_m, tile_n, K, alpha, beta, C, slab, slice, ldc, mirror_all);
 }
 
 __global__ __launch_bounds__(kSThreads) void syrk_f16_m16_kernel(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all,
@@ -1206,6 +1220,23 @@ int32_t launch_syrk_bf16x3(const float* X, int64_t T, int64_t K, int64_t ldx, fl
     return syrk_pieces_phases(X, T, K, ldx, alpha, beta, C, base, reinterpret_cast<float*>(base + pieces), workspace_bytes - pieces - 256, terms, 3, s);
 }
 
+// T-slices of a symmetric product on 256 x 256 tiles (one block per CU, 256 CUs): the slice count (<= 16, slices of >= 512 rows,
+// slab permitting) whose block count fills whole rounds of 256 best; ties go to fewer slices.
+static int choose_t_slices(int64_t nstages, int stage_rows, int64_t tiles, int64_t K, size_t slab_bytes) {
+    int splits = 1;
+    const int64_t min_stages = 512 / stage_rows;                 // slices of >= 512 rows
+    const int64_t by_rows = nstages / min_stages > 0 ? nstages / min_stages : 1;
+    int64_t cap = by_rows < 16 ? by_rows : 16;
+    while (cap > 1 && static_cast<size_t>(cap) * K * K * sizeof(float) > slab_bytes) --cap;
+    double best = -1.0;
+    for (int c = 1; c <= cap; ++c) {
+        const int64_t blocks = tiles * c;
+        const double fill = static_cast<double>(blocks) / static_cast<double>(ceil_div(blocks, 256) * 256);
+        if (fill > best + 0.02) { best = fill; splits = c; }      // more slices only for a real gain (each costs a K x K pass)
+    }
+    return splits;
+}
+
 int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, unsigned char* base, float* slab,
                            size_t slab_bytes, int terms, int phases, hipStream_t s) {
     const bool f16 = terms == 3;
@@ -1253,19 +1284,7 @@ int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, fl
     // is flat (1 slice 17.04, 4: 17.02).  A cost model that prefers fewer slices (5 and 1 for these shapes) was tried and
     // measured equal in time, but every slice is also a shorter fp32 accumulation chain: with one slice instead of four the
     // error against float64 of an 8192-row K = 11008 call rose from 8e-7 to 4e-6 of max |H| (bound: 1e-5).  More slices stay.
-    int splits = 1;
-    {
-        const int64_t min_stages = 512 / stage_rows;                 // slices of >= 512 rows
-        const int64_t by_rows = nstages / min_stages > 0 ? nstages / min_stages : 1;
-        int64_t cap = by_rows < 16 ? by_rows : 16;
-        while (cap > 1 && static_cast<size_t>(cap) * K * K * sizeof(float) > slab_bytes) --cap;
-        double best = -1.0;
-        for (int c = 1; c <= cap; ++c) {
-            const int64_t blocks = tiles * c;
-            const double fill = static_cast<double>(blocks) / static_cast<double>(ceil_div(blocks, 256) * 256);
-            if (fill > best + 0.02) { best = fill; splits = c; }      // more slices only for a real gain (each costs a K x K pass)
-        }
-    }
+    int splits = choose_t_slices(nstages, stage_rows, tiles, K, slab_bytes);
 #ifdef OQ_SYRK_LAB
     if (const char* v = getenv("OQ_SYRK_SPLITS")) {      // lab builds only (scripts/lab_syrk_splits.sh): force the slice count
         const int c = atoi(v);
@@ -1513,5 +1532,121 @@ int32_t launch_gemm_f16x3(const void* pieces_a, const void* pieces_b, int64_t M,
 }
 
 int64_t gemm_f16x3_tiles(int64_t M, int64_t N) { return (padded_k(M) / kST) * (padded_k(N) / kST); }
+
+// ---- 4. Activations that ARE fp16 / bf16 (oq_hessian_accumulate_h16, include/oq_hip_half.h).  An fp16 x fp16 or bf16 x bf16
+// product is exact in fp32, so X needs no pieces, no absmax pass and no power-of-two scale: ONE matrix-core product with fp32
+// accumulation (v_mfma_f32_16x16x32_f16 / _bf16) instead of the three of section 2b, and no product rounding at all -- only the
+// order of the fp32 sums separates the result from float64.  X is never expanded to fp32 in memory.
+//   pack_h16_kernel   X [T, K] (2 B read) -> P[chunk of 8 rows][column padded to 256] x 16 B (2 B written): the layout of the
+//                     first-piece plane of section 2b without the second plane, zero rows behind T and zero columns behind K.
+//                     A thread takes two neighbouring columns x 8 rows: dword loads where the rows are 4-byte aligned (VEC),
+//                     2-byte loads otherwise and for the last column of an odd K -- the same bits either way.
+//   syrk_h16_kernel   the stage loop of the first pieces alone (f16_hi_mainloop: 32-row stages, ring of four, LDS-DMA staging)
+//                     on the compact plane, the tile epilogue and the T-slices of section 2b.
+template <bool VEC>
+__global__ __launch_bounds__(256) void pack_h16_kernel(const uint16_t* __restrict__ X, const int64_t T, const int64_t K, const int64_t ldx,
+                                                       const int64_t Kp, const int64_t nchunks, u32x4* __restrict__ P) {
+    const int64_t col = (static_cast<int64_t>(blockIdx.y) * 256 + threadIdx.x) * 2;
+    if (col >= Kp) return;
+    const bool ok0 = col < K, ok1 = col + 1 < K;
+    const int64_t c_end = (static_cast<int64_t>(blockIdx.x) + 1) * 4 < nchunks ? (static_cast<int64_t>(blockIdx.x) + 1) * 4 : nchunks;
+#pragma unroll 1
+    for (int64_t c = static_cast<int64_t>(blockIdx.x) * 4; c < c_end; ++c) {
+        uint32_t v[8];      // row r of the chunk: column `col` in the low half, `col + 1` in the high half
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int64_t t = c * 8 + r;
+            uint32_t x = 0;
+            if (t < T && ok0) {
+                const uint16_t* src = X + t * ldx + col;
+                if (VEC && ok1) x = *reinterpret_cast<const uint32_t*>(src);
+                else x = static_cast<uint32_t>(src[0]) | (ok1 ? static_cast<uint32_t>(src[1]) << 16 : 0u);
+            }
+            v[r] = x;
+        }
+        u32x4 p0, p1;
+#pragma unroll
+        for (int rp = 0; rp < 4; ++rp) {
+            p0[rp] = (v[2 * rp] & 0xffffu) | (v[2 * rp + 1] << 16);
+            p1[rp] = (v[2 * rp] >> 16) | (v[2 * rp + 1] & 0xffff0000u);
+        }
+        u32x4* o = P + c * Kp + col;        // col + 1 < Kp: Kp is even
+        __builtin_nontemporal_store(p0, o);
+        __builtin_nontemporal_store(p1, o + 1);
+    }
+}
+
+template <typename FRAG>
+__global__ __launch_bounds__(kSThreads) void syrk_h16_kernel(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all,
+                                                             const float alpha, const float beta, float* __restrict__ C, float* __restrict__ slab,
+                                                             const int64_t stages_per_slice, const int ntiles) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    int tile_m, tile_n;
+    upper_tile_of(static_cast<int>(xcd_remap(blockIdx.x, gridDim.x)), ntiles, tile_m, tile_n);
+    const int64_t m0 = static_cast<int64_t>(tile_m) * kST, n0 = static_cast<int64_t>(tile_n) * kST;
+    const int64_t slice = blockIdx.y, s_begin = slice * stages_per_slice;
+    const int64_t s_end = s_begin + stages_per_slice < nstages_all ? s_begin + stages_per_slice : nstages_all;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const char* gsrc[4];
+    int64_t stage_bytes[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int q = wave * 4 + i;                     // 32 pieces of 1 KB: operand q / 16, chunk (q / 4) % 4, quarter q % 4
+        const int quarter = q & 3, cc = (q >> 2) & 3, op = q >> 4;
+        stage_bytes[i] = 4 * Kp * 16;
+        gsrc[i] = reinterpret_cast<const char*>(P + (s_begin * 4 + cc) * Kp + (op ? n0 : m0) + quarter * 64 + lane);
+    }
+    f32x4v acc[4][8];
+    f16_hi_mainloop<FRAG>(gsrc, stage_bytes, s_end - s_begin, lds, acc);
+    syrk_tile_store(acc, lds, tile_m, tile_n, K, alpha, beta, C, slab, slice, K, true);
+}
+
+constexpr int kH16StageRows = 32;      // four 8-row chunks: one k-step of the 16x16x32 instructions
+static size_t syrk_h16_plane_bytes(int64_t T, int64_t K) { return static_cast<size_t>(stages_of(T, kH16StageRows)) * 4 * static_cast<size_t>(padded_k(K)) * 16; }
+
+size_t syrk_h16_pieces_bytes(int64_t T, int64_t K) { return (T <= 0 || K <= 0) ? 0 : syrk_h16_plane_bytes(T, K); }
+
+template <typename FRAG>
+static int32_t launch_syrk_h16_typed(const u32x4* P, int64_t K, int64_t Kp, int64_t nstages, float alpha, float beta, float* C, float* slab,
+                                     size_t slab_bytes, hipStream_t s) {
+    const int lds_bytes = kHiRing * kHiStage;
+    OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_h16_kernel<FRAG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess,
+               OQ_ERR_LAUNCH, "syrk_h16: cannot reserve %d bytes of LDS", lds_bytes);
+    const int tn = static_cast<int>(Kp / kST);
+    const int64_t tiles = static_cast<int64_t>(tn) * (tn + 1) / 2;
+    int splits = choose_t_slices(nstages, kH16StageRows, tiles, K, slab ? slab_bytes : 0);
+    const int64_t per = ceil_div(nstages, splits);
+    splits = static_cast<int>(ceil_div(nstages, per));
+    float* slab_f = splits > 1 ? slab : nullptr;
+    hipLaunchKernelGGL(syrk_h16_kernel<FRAG>, dim3(static_cast<uint32_t>(tiles), static_cast<uint32_t>(splits)), dim3(kSThreads), lds_bytes, s, P, K, Kp,
+                       nstages, alpha, beta, C, slab_f, per, tn);
+    const int32_t st = check_launch("syrk_h16_kernel");
+    if (st != OQ_OK || splits == 1) return st;
+    return launch_syrk_reduce(slab_f, splits, K, alpha, beta, C, kST, s);
+}
+
+int32_t launch_syrk_h16(const void* X, bool bf16, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, void* workspace,
+                        size_t workspace_bytes, hipStream_t s) {
+    OQ_REQUIRE(X != nullptr && C != nullptr && T > 0 && K >= 1 && ldx >= K, OQ_ERR_INVALID_ARGUMENT, "syrk_h16: bad argument");
+    const size_t plane = syrk_h16_plane_bytes(T, K);
+    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= plane + 256, OQ_ERR_WORKSPACE, "syrk_h16: workspace of %zu bytes needed for the packed operand, %zu given",
+               plane + 256, workspace ? workspace_bytes : static_cast<size_t>(0));
+    unsigned char* base = static_cast<unsigned char*>(workspace);
+    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
+    u32x4* P = reinterpret_cast<u32x4*>(base);
+    const int64_t Kp = padded_k(K), nstages = stages_of(T, kH16StageRows), nchunks = nstages * 4;
+    const dim3 grid(static_cast<uint32_t>(ceil_div(nchunks, 4)), static_cast<uint32_t>(ceil_div(Kp, 512)));     // x <= 2^26 (T < 2^31), y <= 256
+    const uint16_t* X16 = static_cast<const uint16_t*>(X);
+    if ((reinterpret_cast<uintptr_t>(X) & 3u) == 0 && (ldx & 1) == 0)
+        hipLaunchKernelGGL(pack_h16_kernel<true>, grid, dim3(256), 0, s, X16, T, K, ldx, Kp, nchunks, P);
+    else
+        hipLaunchKernelGGL(pack_h16_kernel<false>, grid, dim3(256), 0, s, X16, T, K, ldx, Kp, nchunks, P);
+    const int32_t st = check_launch("pack_h16_kernel");
+    if (st != OQ_OK) return st;
+    float* slab = reinterpret_cast<float*>(base + plane);
+    const size_t slab_bytes = workspace_bytes - plane - 256;
+    return bf16 ? launch_syrk_h16_typed<bf16x8>(P, K, Kp, nstages, alpha, beta, C, slab, slab_bytes, s)
+                : launch_syrk_h16_typed<f16x8>(P, K, Kp, nstages, alpha, beta, C, slab, slab_bytes, s);
+}
 
 }  // namespace oq

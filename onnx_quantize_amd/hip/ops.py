@@ -994,9 +994,18 @@ def matmul_pieces(x: torch.Tensor, w: MatmulOperand | torch.Tensor) -> torch.Ten
 
 # ----------------------------------------------------------------------------- G1 - G4
 def hessian_accumulate(x: torch.Tensor, h: torch.Tensor, n_seen: int, method: str | None = None) -> int:
-    """gptq.py:246-260, in place on ``h`` [K, K]; ``x`` [n_add, ..., K] fp32.  Returns the new sample
+    """gptq.py:246-260, in place on ``h`` [K, K]; ``x`` [n_add, ..., K] fp32, fp16 or bf16.  Returns the new sample
     count.  The activations are streamed through the MFMA TN GEMM; nothing is concatenated.  ``method``: the X^T X kernel
-    of this call (None: the calling thread's default, `hessian_set_method`)."""
+    of this call (None: the calling thread's default, `hessian_set_method`).
+
+    An fp16 / bf16 ``x`` is read as it is (`oq_hessian_accumulate_h16`, csrc/syrk_bf16x3.hip section 4) and defines the result
+    as gptq.py:257 does, on its exact fp32 values.  ``method`` and the thread default are IGNORED for it: half x half
+    products are exact in fp32, so the one matrix-core product that route runs carries no operand split and no product
+    rounding -- it is at least as exact as each of the fp32 methods, "f32" included, and there is nothing to choose."""
+    _require_device(x, "x")
+    if x.dtype in _HALF_WTYPE:
+        _method_code(method)                       # an unknown name is still an error
+        return _hessian_accumulate_half(x, h, n_seen)
     _require_device(x, "x", torch.float32)
     _require_device(h, "H", torch.float32)
     n_add = int(x.shape[0])
@@ -1012,13 +1021,26 @@ def hessian_accumulate(x: torch.Tensor, h: torch.Tensor, n_seen: int, method: st
     return int(n_seen) + n_add
 
 
+def _hessian_accumulate_half(x: torch.Tensor, h: torch.Tensor, n_seen: int) -> int:
+    _require_device(h, "H", torch.float32)
+    n_add = int(x.shape[0])
+    x2, ldx = _row_major(x.reshape(-1, x.shape[-1]))
+    t, k = x2.shape
+    if h.shape != (k, k) or not h.is_contiguous():
+        raise ValueError(f"H must be a contiguous [{k}, {k}] tensor")
+    lib = L.load()
+    ws = _workspace(lib.oq_hessian_half_workspace_bytes(t, k), x.device)
+    L.check(lib.oq_hessian_accumulate_h16(_ptr(x2), _HALF_WTYPE[x.dtype], t, k, ldx, int(n_seen), n_add, _ptr(h), _ptr(ws), ws.numel(), _stream()))
+    return int(n_seen) + n_add
+
+
 _MANY_MIN_K, _MANY_MIN_ROWS, _MANY_MAX_ROWS = 512, 512, 32768
 
 
 def hessian_accumulate_many(xs, hs, n_seen) -> list[int]:
     """gptq.py:246-260 for a list of (input, Hessian) pairs -- the tensors one calibration batch taps -- in ONE launch chain
     (`oq_hessian_accumulate_many_f32`).  ``xs[i]`` [n_add, ..., K_i] fp32, ``hs[i]`` [K_i, K_i] updated in place, ``n_seen[i]``
-    the samples already in it; returns the new sample counts.  Items narrower than 512 columns or shorter than 512 rows
+    the samples already in it; returns the new sample counts.  fp16 / bf16 items, items narrower than 512 columns or shorter than 512 rows
     (their padding to 256-wide tiles would cost more than the launches save), items longer than 32 768 rows (the grouped
     product sums an item's rows in ONE fp32 chain; the per-tensor call slices long inputs, which also keeps the rounding error
     at 1e-6 of max |H|), and every item when another Hessian method than the fp16 pieces is selected, go through
@@ -1030,6 +1052,9 @@ def hessian_accumulate_many(xs, hs, n_seen) -> list[int]:
     rows, keep = [], []
     grouped = hessian_method() in ("auto", "f16x3")
     for i, (x, h) in enumerate(zip(xs, hs)):
+        if isinstance(x, torch.Tensor) and x.dtype in _HALF_WTYPE:       # no grouped half chain: the half kernel, item by item
+            out[i] = hessian_accumulate(x, h, n_seen[i])
+            continue
         _require_device(x, "x", torch.float32)
         _require_device(h, "H", torch.float32)
         x2, ldx = _row_major(x.reshape(-1, x.shape[-1]))

@@ -421,7 +421,7 @@ def _standardize_gemm(G: _Graph) -> None:
 def _target_nodes(G: _Graph, qconfig: QConfig, half_native: bool = False) -> list:
     """calibrate.py:48-89 + the `check` methods of the rules (matmul_to_qmatmul.py:31-41, gemm_to_qgemm.py:13-44): op type
     selected, name not ignored, constant weight (and bias), Gemm with `transB = 0`.  Weights that are not matrices are left
-    alone (the numeric path is defined on [K, N]).  `half_native`: FLOAT16 matrices are targets too (`half_weights="native"`)."""
+    alone (the numeric path is defined on [K, N]).  `half_native`: FLOAT16 matrices are targets too (`half_weights` other than "error")."""
     element_types = (DataType.FLOAT, DataType.FLOAT16) if half_native else (DataType.FLOAT,)
     ignores = [re.compile(p) for p in qconfig.ignore]
     out = []
@@ -799,10 +799,10 @@ class Prepared:
 
     def __init__(self, model, graph, targets, meta, per_node, half_targets=()):
         self.model, self.graph, self.targets, self.meta, self.per_node = model, graph, targets, meta, per_node
-        self.half_targets = set(half_targets)      # id(node) of the targets whose weight is a FLOAT16 matrix (`half_weights="native"`)
+        self.half_targets = set(half_targets)      # id(node) of the targets whose weight is a FLOAT16 matrix (`half_weights` other than "error")
 
 
-HALF_WEIGHTS = ("error", "native")
+HALF_WEIGHTS = ("error", "native", "native_calibrated")
 
 
 def _half_candidates(G: _Graph, qconfig: QConfig, element_types) -> list:
@@ -810,28 +810,36 @@ def _half_candidates(G: _Graph, qconfig: QConfig, element_types) -> list:
             and len(G.inits[n.input[1]].dims) == 2 and G.inits[n.input[1]].data_type in element_types]
 
 
-def _check_half_native(G: _Graph, qconfig: QConfig, targets) -> set:
+def _check_half_native(G: _Graph, qconfig: QConfig, targets, half_weights: str = "native") -> set:
     """`half_weights="native"`: FLOAT16 [K, N] weights are quantized as they are by the MatMulNBits rule of a weight-only
-    configuration; everything else says what is unsupported."""
+    RTN configuration.  `half_weights="native_calibrated"`: the same, and weight-only GPTQ as well -- the calibration walk
+    runs the FLOAT16 graph as it is and its fp16 activations go to the Hessian without an fp32 copy
+    (`oq_hessian_accumulate_h16`).  Everything else says what is unsupported."""
+    opt = f"half_weights='{half_weights}'"
     bf16 = _half_candidates(G, qconfig, (DataType.BFLOAT16,))
     if bf16:
-        raise NotImplementedError(f"half_weights='native': '{bf16[0]}' is a BFLOAT16 initializer, which this package's ONNX codec has no NumPy "
+        raise NotImplementedError(f"{opt}: '{bf16[0]}' is a BFLOAT16 initializer, which this package's ONNX codec has no NumPy "
                                   "type for; FLOAT16 weights are supported (ops.rtn_quantize takes bf16 tensors on the device)")
     half = [n for n in targets if G.inits[n.input[1]].data_type == DataType.FLOAT16]
     if not half:
         return set()
     name = half[0].input[1]
     if qconfig.input_activations is not None or qconfig.output_activations is not None:
-        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): activation quantization (the QDQ / QLinear rules with "
+        raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): activation quantization (the QDQ / QLinear rules with "
                                   "activation arguments) is unsupported on half-precision models; only weight-only MatMulNBits is")
     if qconfig.preprocessors:
-        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): preprocessors (AWQ / SmoothQuant) are unsupported on half-precision models")
-    if _needs_calibration(qconfig) or qconfig.calibration_data is not None:
-        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): calibrated configurations (calibration data, GPTQ) are "
-                                  "unsupported on half-precision models; only weight-only RTN through MatMulNBits is")
+        raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): preprocessors (AWQ / SmoothQuant) are unsupported on half-precision models")
     algorithm = getattr(qconfig.weights.algorithm, "algorithm_type", None)
+    if half_weights == "native_calibrated":
+        if algorithm not in ("rtn", "gptq"):
+            raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): the {algorithm} algorithm is unsupported on half-precision models (HQQ "
+                                      "keeps float zero points next to the scales); only weight-only RTN and GPTQ through MatMulNBits are")
+        return {id(n) for n in half}
+    if _needs_calibration(qconfig) or qconfig.calibration_data is not None:
+        raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): calibrated configurations (calibration data, GPTQ) are unsupported with this "
+                                  "value, only weight-only RTN through MatMulNBits is; half_weights='native_calibrated' takes weight-only GPTQ")
     if algorithm != "rtn":
-        raise NotImplementedError(f"half_weights='native' ('{name}' is FLOAT16): the {algorithm} algorithm is unsupported on half-precision "
+        raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): the {algorithm} algorithm is unsupported on half-precision "
                                   "models (HQQ keeps float zero points next to the scales); only weight-only RTN through MatMulNBits is")
     return {id(n) for n in half}
 
@@ -848,8 +856,8 @@ def apply_pre_passes(model, qconfig: QConfig, *, device="cuda", calibrate=None, 
     if half_weights not in HALF_WEIGHTS:
         raise ValueError(f"half_weights must be one of {HALF_WEIGHTS}, got {half_weights!r}")
     G = _structural_passes(model)
-    targets = _target_nodes(G, qconfig, half_native=half_weights == "native")
-    half_targets = _check_half_native(G, qconfig, targets) if half_weights == "native" else set()
+    targets = _target_nodes(G, qconfig, half_native=half_weights != "error")
+    half_targets = _check_half_native(G, qconfig, targets, half_weights) if half_weights != "error" else set()
     if not targets:
         # an fp16 / bf16 export (the usual half-precision form) has constant MatMul / Gemm weights and not one fp32
         # matrix among them; returning it untouched with a success status would look like a quantized model
@@ -907,7 +915,11 @@ def quantize_model(model, qconfig: QConfig, *, device="cuda", weight_arrays=None
     where the configuration is weight-only and the rule is the MatMulNBits one (QUInt4 / QUInt8 group-wise).  The emitted
     node carries the blob and zero points of the fp32 copy of the weight and the scales as FLOAT16 -- `np.float16(scale32)`,
     round to nearest even, of the fp32 scale the integers were made with.  Everything else on a
-    half-precision weight raises NotImplementedError and says what is unsupported."""
+    half-precision weight raises NotImplementedError and says what is unsupported, calibrated configurations included.
+    "native_calibrated" is "native" plus weight-only GPTQ: the calibration walk runs the FLOAT16 graph as it is (random
+    calibration data takes the input's own type), the tapped fp16 activations go to the Hessian without an fp32 copy
+    (`ops.hessian_accumulate` on half tensors), the weight is upcast exactly for the loop, and the scales are stored as FLOAT16 by
+    the same rule.  Activation arguments, preprocessors, HQQ and BFLOAT16 initializers stay refused by name."""
     if not isinstance(qconfig, QConfig):
         raise TypeError(f"qconfig must be a QConfig, got {type(qconfig)}")
     if qconfig.weights is None and qconfig.input_activations is None and qconfig.output_activations is None:
@@ -972,7 +984,7 @@ def _emit(prepared: Prepared, qconfig: QConfig, weight_arrays, quantize_bias) ->
         packed = getattr(weight_arrays, "packed", {})
         is_half = id(node) in prepared.half_targets
         if is_half and plan.call["name"] != "MatMulNBits":
-            raise NotImplementedError(f"half_weights='native': node '{node.name}' (weight '{w_name}', FLOAT16) would be rewritten by the "
+            raise NotImplementedError(f"half_weights: node '{node.name}' (weight '{w_name}', FLOAT16) would be rewritten by the "
                                       f"{plan.call['name']} rule; on half-precision weights only the MatMulNBits rule (QUInt4 / QUInt8, "
                                       "group-wise, a power-of-two group of at least 16) is supported, the QDQ / QLinear rules are not")
         for name, array in plan.initializers:
@@ -1106,7 +1118,8 @@ def quantize_file(src, dst, qconfig: QConfig, external_data="auto", **kw) -> Mes
     """Read `src` (tensors in side files are memory-mapped, not read), quantize, write `dst`.  `external_data`: a file name
     next to `dst` for the tensors, None for one file with everything inline, "auto" (default): `<dst name>.data` when the
     source kept its tensors outside or the result would pass 1 GiB, inline otherwise.  Every other keyword goes to
-    `quantize_model` -- `half_weights="native"` among them, for a file whose weights are FLOAT16.  Returns the quantized model."""
+    `quantize_model` -- `half_weights="native"` / `"native_calibrated"` among them, for a file whose weights are FLOAT16.  Returns the
+    quantized model."""
     from .onnx_proto import resolve_external_data
     src_model = load_model(src, load_external_data=False)
     had_external = resolve_external_data(src_model, os.path.dirname(os.path.abspath(os.fspath(src)))) > 0
