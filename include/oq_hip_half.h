@@ -1,6 +1,6 @@
 /*
- * oq_hip_half.h -- half-precision extension of the C ABI of oq_hip.h: RTN on fp16 / bf16 weights and the GPTQ Hessian of
- * fp16 / bf16 activations, both read as they are.
+ * oq_hip_half.h -- half-precision extension of the C ABI of oq_hip.h: RTN on fp16 / bf16 weights, the GPTQ Hessian and the
+ * calibration statistics (running min / max, absmax) of fp16 / bf16 activations, all read as they are.
  *
  * oq_hip.h stays what it is (OQ_ABI_VERSION 2); the entry points below live in the same library and follow the same
  * conventions (device pointers, asynchronous on `stream`, no allocation, 0 or a negative oq_status, oq_last_error()).
@@ -73,6 +73,44 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
 size_t oq_hessian_half_workspace_bytes(int64_t T, int64_t K);
 int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype /* oq_wtype */, int64_t T, int64_t K, int64_t ldx, int64_t n_seen,
                                   int64_t n_add, float* H, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * C1  core/_calibration/minmax.py:40-64  MinMaxCalibrator.collect on x.astype(np.float32), without the fp32 copy: replaces
+ *     the cast followed by oq_minmax_collect_f32.  Min and max of fp16 / bf16 values are exact, so `state` comes out as
+ *     oq_minmax_collect_f32 leaves it on the upcast tensor, bit for bit (NaN anywhere -> both extrema NaN, -0 < +0,
+ *     subnormals are values).
+ *
+ *   x          `count` elements of 2 bytes of type `xtype` (an oq_wtype), 2-byte aligned: the elements in front of the first
+ *              16-byte boundary and behind the last one are read singly, the rest eight at a time.
+ *   state      fp32 {min, max, seen, -} in device memory, as in oq_minmax_collect_f32 (zero-filled before its first use).
+ *   momentum   in [0, 1): 0 keeps the running min / max, > 0 the EMA of minmax.py:53-60.
+ *   workspace  oq_minmax_half_workspace_bytes (4-byte aligned).  The query returns 0 for a count outside 1 .. 2^40.
+ * ------------------------------------------------------------------------------------------- */
+size_t oq_minmax_half_workspace_bytes(int64_t count);
+int32_t oq_minmax_collect_h16(const void* x, int32_t xtype /* oq_wtype */, int64_t count, float* state, double momentum,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* C1 for a whole calibration batch of 2-byte tensors of ONE element type: replaces a cast and an oq_minmax_collect_f32 per
+ *     tensor (calibrate.py:264-266) by one launch pair, as oq_minmax_collect_many_f32 does for fp32 tensors.  `desc` is a
+ *     DEVICE array (8-byte aligned) of n oq_minmax_desc {x, count, state} whose `x` points at 2-byte elements of type
+ *     `xtype`; every count > 0; each state fp32 as above.  1 <= n <= 65535; the query returns 0 outside. */
+size_t oq_minmax_many_half_workspace_bytes(int64_t n);
+int32_t oq_minmax_collect_many_h16(const void* desc, int64_t n, int32_t xtype /* oq_wtype */, double momentum, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * S1  pre_passes/smooth_quant.py:62-74  the per-channel max |x| on x.astype(np.float32), without the fp32 copy: replaces the cast followed by oq_absmax_f32.  |x| of an fp16 / bf16 value is exact: `out` equals
+ *     oq_absmax_f32's on the upcast matrix bit for bit (starting from 0; a NaN poisons exactly its column / row).
+ *
+ *   x          [R, C], 2 bytes per element of type `xtype` (an oq_wtype), leading dimension ldx >= C (elements).  Rows that
+ *              are not 16-byte aligned (C or ldx no multiple of 8, an unaligned base) take 2-byte loads and give the same.
+ *   transposed 0: out[c] = max_r |x[r, c]| (C floats).  Non-zero: out[r] = max_c |x[r, c]| (R floats), no workspace used.
+ *   workspace  oq_absmax_half_workspace_bytes (4-byte aligned): the per-128-row partial maxima.  The query returns 0 for a
+ *              shape outside the bounds of oq_hip.h.
+ * ------------------------------------------------------------------------------------------- */
+size_t oq_absmax_half_workspace_bytes(int64_t R, int64_t C, int32_t transposed);
+int32_t oq_absmax_h16(const void* x, int32_t xtype /* oq_wtype */, int64_t R, int64_t C, int64_t ldx, int32_t transposed, float* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 """Calibration parameters and the GPU min-max calibrator (reference: core/_calibration/{base,minmax,
 factory}.py).  The calibrator keeps the running (min, max) of every tensor name in device memory and
-updates it with one HBM-bound reduction per batch (oq_minmax_collect_f32/f64); nothing is copied back
-until ``data[name]`` or ``compute_range`` is read.
+updates it with one HBM-bound reduction per batch (oq_minmax_collect_f32/f64; oq_minmax_collect_h16 for
+fp16 / bf16 tensors in HBM, read as they are); nothing is copied back until ``data[name]`` or
+``compute_range`` is read.
 """
 from __future__ import annotations
 
@@ -122,7 +123,8 @@ class Calibrator(abc.ABC):
 
 class MinMaxCalibrator(Calibrator):
     """minmax.py:11-87 on the GPU.  ``collect`` accepts a NumPy array (copied to HBM) or a torch tensor
-    already in HBM (no copy: the on-device calibration driver of SURVEY.md 8f-N1 feeds those)."""
+    already in HBM (no copy: the on-device calibration driver of SURVEY.md 8f-N1 feeds those).  An fp16 / bf16
+    tensor in HBM is reduced as it is into an fp32 state: the statistics of its upcast, without the upcast."""
 
     def __init__(self, momentum: float = 0.0):
         super().__init__()
@@ -135,6 +137,7 @@ class MinMaxCalibrator(Calibrator):
 
         from .hip import ops
 
+        half = (torch.float16, torch.bfloat16)
         if isinstance(array, np.ndarray):
             if array.dtype not in (np.float32, np.float64):
                 if array.dtype == np.float16:
@@ -143,39 +146,43 @@ class MinMaxCalibrator(Calibrator):
                     raise TypeError(f"MinMaxCalibrator (HIP) supports float32/float64 activations, got {array.dtype}")
             x = torch.from_numpy(np.ascontiguousarray(array)).cuda()
         elif isinstance(array, torch.Tensor):
-            x = array if array.dtype in (torch.float32, torch.float64) else array.to(torch.float32)
+            x = array if array.dtype in (torch.float32, torch.float64, *half) else array.to(torch.float32)
             if not x.is_cuda:
                 x = x.cuda()
         else:
             raise TypeError("collect() expects a numpy array or a torch tensor")
         if name not in self.data:
+            state_dtype = torch.float64 if x.dtype == torch.float64 else torch.float32     # fp16 / bf16: an fp32 state
             np_dtype = np.dtype(np.float64 if x.dtype == torch.float64 else np.float32)
-            self.data[name] = CalibrationData(ops.minmax_state(x.device, x.dtype), np_dtype)
+            self.data[name] = CalibrationData(ops.minmax_state(x.device, state_dtype), np_dtype)
         entry = self.data[name]
-        if entry._state.dtype != x.dtype:
+        if entry._state.dtype != x.dtype and not (x.dtype in half and entry._state.dtype == torch.float32):
             x = x.to(entry._state.dtype)
         ops.minmax_collect(x, entry._state, self.momentum)
 
     def collect_many(self, arrays) -> None:
-        """``collect`` for a whole calibration batch ({name: fp32 torch tensor in HBM}) in one launch pair -- what an
-        on-device calibration driver calls once per batch instead of calibrate.py:264-266's per-tensor loop.  Same
-        statistics as calling ``collect`` for every item (first sight / EMA / running min-max per name)."""
+        """``collect`` for a whole calibration batch ({name: torch tensor in HBM}) -- what an on-device calibration driver
+        calls once per batch instead of calibrate.py:264-266's per-tensor loop.  The batch is partitioned by dtype: its fp32,
+        its fp16 and its bf16 tensors get one launch pair each (the half ones are read as they are), anything else takes
+        ``collect``.  Same statistics as calling ``collect`` for every item (first sight / EMA / running min-max per name)."""
         import torch
 
         from .hip import ops
 
-        names, xs = [], []
+        by_dtype: dict = {torch.float32: ([], []), torch.float16: ([], []), torch.bfloat16: ([], [])}
         for name, t in arrays.items():
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32) or (
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in by_dtype) or (
                     name in self.data and self.data[name]._state.dtype != torch.float32):
                 self.collect(name, t)            # anything else takes the per-tensor path
                 continue
             if name not in self.data:
                 self.data[name] = CalibrationData(ops.minmax_state(t.device, torch.float32), np.dtype(np.float32))
+            names, xs = by_dtype[t.dtype]
             names.append(name)
             xs.append(t)
-        if xs:
-            ops.minmax_collect_many(xs, [self.data[n]._state for n in names], self.momentum)
+        for names, xs in by_dtype.values():
+            if xs:
+                ops.minmax_collect_many(xs, [self.data[n]._state for n in names], self.momentum)
 
     def compute_range(self, name: str) -> tuple[np.ndarray, np.ndarray]:
         if name not in self.data:

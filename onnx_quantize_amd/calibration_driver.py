@@ -5,11 +5,12 @@ array in a list (`core/_calibration/calibrate.py:204-251`), and only then walks 
 through the calibrator (`_set_qparams`, :254-285) and once to concatenate the GPTQ inputs (`_set_qparams_gptq`,
 :288-307).  Here the activations never leave HBM and are consumed batch by batch as the model produces them:
 
-* range statistics  -> `MinMaxCalibrator.collect_many` (one launch pair per batch, `oq_minmax_collect_many_f32`);
+* range statistics  -> `MinMaxCalibrator.collect_many` (one launch pair per batch and dtype: `oq_minmax_collect_many_f32`,
+                       `oq_minmax_collect_many_h16` for fp16 / bf16 activations, which are read as they are);
 * GPTQ inputs       -> one `HessianAccumulator` per distinct value name, fed through `oq_hessian_accumulate_f32`
                        (the running form of gptq.py:246-260: the same H as the reference's single call on the
                        concatenation, see `HessianAccumulator`);
-* SmoothQuant stats -> running per-channel absmax (`oq_absmax_f32`, smooth_quant.py:62-69);
+* SmoothQuant stats -> running per-channel absmax (`oq_absmax_f32` / `oq_absmax_h16`, smooth_quant.py:62-69);
 * AWQ needs the activations themselves: `keep_names` holds those (and only those) in HBM.
 
 What produces the activations is a *runner*: any callable ``runner(feed) -> {value name: tensor in HBM}``.
@@ -88,7 +89,10 @@ class ActivationStream:
     calibrator (calibrate.py:355-373), every tapped name each time; input parameters are read after the first walk,
     output parameters after the second.  For running min / max that changes nothing; with ``momentum > 0`` the
     output ranges are an EMA over the batch sequence seen twice.  The stream reproduces that from the per-batch
-    extrema (two floats per name and batch, kept on the device) instead of from the activations."""
+    extrema (two fp32 values per name and batch, kept on the device) instead of from the activations.
+
+    Activations may be fp32, fp16 or bf16: ranges, absmax and Hessians read a half tensor as it is and keep fp32 results
+    (those of the upcast tensor); no fp32 copy of an activation is made for them."""
 
     def __init__(self, *, calibrator=None, input_names: Iterable[str] = (), output_names: Iterable[str] = (),
                  hessian_names: Iterable[str] = (), absmax_names: Iterable[str] = (), keep_names: Iterable[str] = (),
@@ -187,7 +191,8 @@ class ActivationStream:
                 cur.wait_stream(side)
         for name in self.absmax_names & activations.keys():
             x = activations[name]
-            cur = ops.absmax(x if x.dtype == torch.float32 else x.to(torch.float32))
+            # fp16 / bf16 as they are (oq_absmax_h16: fp32 out, the values of the upcast without the upcast)
+            cur = ops.absmax(x if x.dtype in (torch.float32, torch.float16, torch.bfloat16) else x.to(torch.float32))
             self.absmax[name] = cur if name not in self.absmax else torch.maximum(self.absmax[name], cur)
         names = sorted(self.statistics_names & activations.keys())
         if names and not self.statistics and self._held_bytes <= self.statistics_after_bytes:

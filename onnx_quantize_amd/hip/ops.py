@@ -672,10 +672,17 @@ _MINMAX_WS: dict = {}   # (device index, stream) -> workspace reused by every co
 
 def minmax_collect(x: torch.Tensor, state: torch.Tensor, momentum: float = 0.0) -> None:
     """minmax.py:40-64: fold one activation batch into `state`, entirely on the device.  This sits in the
-    calibration loop (thousands of tensors per run), so the host side is kept to one ctypes call."""
-    if not x.is_cuda or x.dtype not in (torch.float32, torch.float64):
+    calibration loop (thousands of tensors per run), so the host side is kept to one ctypes call.
+
+    An fp16 / bf16 ``x`` is read as it is (`oq_minmax_collect_h16`, csrc/reduce_half.hip) into an fp32 state: the state of
+    the fp32 call on ``x.float()``, bit for bit, without that copy."""
+    half = x.dtype in _HALF_WTYPE
+    if not x.is_cuda or not (half or x.dtype in (torch.float32, torch.float64)):
         raise TypeError("activations must be fp32/fp64 tensors in GPU memory")
-    if state.dtype != x.dtype:
+    if half:
+        if state.dtype != torch.float32:
+            raise TypeError(f"the state of an {x.dtype} activation must be fp32, got {state.dtype}")
+    elif state.dtype != x.dtype:
         raise TypeError("state dtype must match the activation dtype")
     flat = x if x.is_contiguous() else x.contiguous()
     n = flat.numel()
@@ -685,22 +692,30 @@ def minmax_collect(x: torch.Tensor, state: torch.Tensor, momentum: float = 0.0) 
     stream = torch.cuda.current_stream(x.device).cuda_stream
     key = (x.device.index, stream)
     ws = _MINMAX_WS.get(key)
-    if ws is None:
-        ws = _MINMAX_WS[key] = _workspace(lib.oq_minmax_workspace_bytes(n), x.device)
-    fn = lib.oq_minmax_collect_f32 if x.dtype == torch.float32 else lib.oq_minmax_collect_f64
-    st = fn(flat.data_ptr(), n, state.data_ptr(), float(momentum), ws.data_ptr(), ws.numel(), stream)
+    if ws is None:    # one workspace serves both entry points (neither size depends on the count)
+        ws = _MINMAX_WS[key] = _workspace(max(lib.oq_minmax_workspace_bytes(n), lib.oq_minmax_half_workspace_bytes(n)), x.device)
+    if half:
+        st = lib.oq_minmax_collect_h16(flat.data_ptr(), _HALF_WTYPE[x.dtype], n, state.data_ptr(), float(momentum), ws.data_ptr(),
+                                       ws.numel(), stream)
+    else:
+        fn = lib.oq_minmax_collect_f32 if x.dtype == torch.float32 else lib.oq_minmax_collect_f64
+        st = fn(flat.data_ptr(), n, state.data_ptr(), float(momentum), ws.data_ptr(), ws.numel(), stream)
     if st:
         L.check(st)
 
 
 def minmax_collect_many(xs, states, momentum: float = 0.0) -> None:
-    """minmax.py:40-64 for a list of fp32 tensors in ONE launch pair (oq_minmax_collect_many_f32): ``xs[i]`` is folded
-    into ``states[i]``.  The 24-byte descriptors travel in one small host-to-device copy per call."""
+    """minmax.py:40-64 for a list of tensors of ONE dtype -- fp32 (oq_minmax_collect_many_f32), fp16 or bf16
+    (oq_minmax_collect_many_h16, read as they are) -- in ONE launch pair: ``xs[i]`` is folded into the fp32 ``states[i]``.
+    The 24-byte descriptors travel in one small host-to-device copy per call."""
     if len(xs) != len(states) or not xs:
         raise ValueError("minmax_collect_many needs equally long, non-empty lists")
+    dtype = xs[0].dtype if xs[0].dtype in _HALF_WTYPE else torch.float32
     flats = []
     for x, st in zip(xs, states):
-        if not x.is_cuda or x.dtype != torch.float32 or st.dtype != torch.float32:
+        if not x.is_cuda or x.dtype != dtype or st.dtype != torch.float32:
+            if dtype != torch.float32 and x.is_cuda and x.dtype in (torch.float32, *_HALF_WTYPE) and st.dtype == torch.float32:
+                raise TypeError(f"minmax_collect_many takes tensors of one dtype per call, got {dtype} and {x.dtype}")
             raise TypeError("minmax_collect_many takes fp32 tensors in GPU memory (use minmax_collect for fp64)")
         f = x if x.is_contiguous() else x.contiguous()
         if f.numel() == 0:
@@ -710,19 +725,29 @@ def minmax_collect_many(xs, states, momentum: float = 0.0) -> None:
     table = torch.tensor([[f.data_ptr(), f.numel(), st.data_ptr()] for f, st in zip(flats, states)], dtype=torch.int64)
     desc = table.to(dev, non_blocking=False)
     lib = L.load()
-    ws = _workspace(lib.oq_minmax_many_workspace_bytes(len(flats)), dev)
-    L.check(lib.oq_minmax_collect_many_f32(_ptr(desc), len(flats), float(momentum), _ptr(ws), ws.numel(), _stream()))
+    if dtype == torch.float32:
+        ws = _workspace(lib.oq_minmax_many_workspace_bytes(len(flats)), dev)
+        L.check(lib.oq_minmax_collect_many_f32(_ptr(desc), len(flats), float(momentum), _ptr(ws), ws.numel(), _stream()))
+    else:
+        ws = _workspace(lib.oq_minmax_many_half_workspace_bytes(len(flats)), dev)
+        L.check(lib.oq_minmax_collect_many_h16(_ptr(desc), len(flats), _HALF_WTYPE[dtype], float(momentum), _ptr(ws), ws.numel(), _stream()))
 
 
 def absmax(x: torch.Tensor, per_row: bool = False) -> torch.Tensor:
     """smooth_quant.py:62-74: max |x| per last-axis channel ([..., C] -> [C]); per_row=True gives the
-    per-row absmax of a 2-D matrix (weights [K, N] -> [K])."""
-    _require_device(x, "x", torch.float32)
+    per-row absmax of a 2-D matrix (weights [K, N] -> [K]).  fp32 out.  An fp16 / bf16 ``x`` is read as it is
+    (`oq_absmax_h16`) and gives what ``absmax(x.float())`` gives, bit for bit."""
+    half = isinstance(x, torch.Tensor) and x.dtype in _HALF_WTYPE
+    _require_device(x, "x", None if half else torch.float32)
     x2 = x.reshape(-1, x.shape[-1])
     x2, ldx = _row_major(x2)
     r, c = x2.shape
     lib = L.load()
     out = torch.empty(r if per_row else c, dtype=torch.float32, device=x.device)
+    if half:
+        ws = _workspace(lib.oq_absmax_half_workspace_bytes(r, c, int(per_row)), x.device)
+        L.check(lib.oq_absmax_h16(_ptr(x2), _HALF_WTYPE[x.dtype], r, c, ldx, int(per_row), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+        return out
     ws = _workspace(lib.oq_absmax_workspace_bytes(r, c, int(per_row)), x.device)
     L.check(lib.oq_absmax_f32(_ptr(x2), r, c, ldx, int(per_row), _ptr(out), _ptr(ws), ws.numel(), _stream()))
     return out
