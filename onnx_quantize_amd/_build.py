@@ -71,9 +71,7 @@ def _compile(src: str, force: bool, extra: tuple = ()) -> str:
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags: tuple = ()) -> str:
-    """``extra_flags`` is for lab builds only (``--attribution`` below adds -DOQ_RTN_ATTRIBUTION, the store-dropping
-    variants of the RTN kernel that scripts/sweep_rtn*.sh time on a GPU box's scratch copy); `__graft_entry__.build()`
-    and the tests never pass any."""
+    """``extra_flags`` is for lab builds only (``--define`` below); `__graft_entry__.build()` and the tests never pass any."""
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIB_DIR, exist_ok=True)
     srcs = sources()
@@ -92,9 +90,7 @@ def build(force: bool = False, verbose: bool = True, extra_flags: tuple = ()) ->
 
 
 if __name__ == "__main__":
-    if "--attribution" in sys.argv:          # never the shipped library: forces a full rebuild with the lab switches compiled in
-        build(force=True, extra_flags=("-DOQ_RTN_ATTRIBUTION",))
-    elif "--define" in sys.argv:             # lab builds on a GPU box's scratch copy: --define NAME [--define NAME ...]
+    if "--define" in sys.argv:               # lab builds on a GPU box's scratch copy: --define NAME [--define NAME ...]
         build(force=True, extra_flags=tuple("-D" + sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == "--define"))
     else:
         build(force="--force" in sys.argv)

@@ -5,23 +5,9 @@
 // registers.  Nothing is reshaped into a GEMM and no transposed copy (utils.py:24) is ever made.
 #include "rtn_internal.hpp"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace oq {
-
-// Attribution switches (bits 3-6 of OQ_RTN_NT: drop the parameter stores, drop the blob stores, write a wave-contiguous
-// -- WRONG -- layout, 8-byte instead of 16-byte blob stores) exist only in builds made with -DOQ_RTN_ATTRIBUTION
-// (scripts/sweep_rtn*.sh).  The shipped library compiles them out and masks the environment value to the two
-// layout-neutral bits (0: non-temporal W loads / [K,N] stores, 1: non-temporal blob stores), so no environment variable
-// can make liboq_hip.so return anything but the reference's bytes (tests/test_library_abi.py).
-#ifdef OQ_RTN_ATTRIBUTION
-#define OQ_ATTR(nt, bit) (((nt) & (bit)) != 0)
-constexpr int kNtMask = 127;
-#else
-#define OQ_ATTR(nt, bit) false
-constexpr int kNtMask = 3;
-#endif
 
 // Division of a block id by a launch constant without the ~30-instruction integer-divide expansion: the quotient
 // estimate float(n) * fl(1/d) is within 1 of n / d for n < 2^22 and is corrected with the exact remainder.
@@ -56,7 +42,7 @@ struct RtnArgs {
     uint8_t* zp;
     float* scale_t;   // optional staging [kgroups, N] (coalesced); transposed to `scale` by transpose_qparams
     uint8_t* zp_t;
-    // Round 6 (template mode TR): staging in the caller's zeroed STATE, transposed inside this launch by `ncol_tiles` blocks appended to
+    // Template mode TR: staging in the caller's zeroed STATE, transposed inside this launch by `ncol_tiles` blocks appended to
     // the grid (see transposer_block).  tr_zp: 8 bytes per four columns, each zero point in 16 bits with bit 8 set.
     float* tr_scale;
     uint2* tr_zp;
@@ -65,13 +51,11 @@ struct RtnArgs {
     int32_t wpg;      // waves per group
     int32_t gpb;      // groups per block
     uint32_t ncol_tiles, nrow_tiles;
-    int32_t order;    // 0: K-direction fastest + XCD strips, 1: column tiles fastest (row-sequential DRAM stream)
-    int32_t nt;       // non-temporal loads of W
+    int32_t order;    // 0: K-direction fastest + XCD strips, 1: column tiles fastest (row-sequential DRAM stream), 2: L2-merging chunks
     int32_t stage_q;  // NBITS: transpose the block's packed output through LDS (64/128-byte chunks per column)
     int32_t gk;       // order 2: row tiles per id chunk (see the block order in rtn_group_fused)
     uint32_t xg_log2; // order 2: log2 of the neighbouring column tiles one XCD owns inside a chunk (0 = one)
     FastDiv fd_ncol, fd_band, fd_chunk;  // ncol_tiles, ncol_tiles * gk, 8 * gk (block ids < 2^22, checked by the host)
-    int32_t spb_log2;  // wave kernel: log2(strips per block)
     uint32_t pair_owner;  // fused kernel, direct parameter stores: wave (inside its group) that stores pair p, 3 bits each
     // strided batch (oq_rtn_quantize_batched_f32): matrix b lives at base + b * stride (elements / bytes as noted)
     int64_t w_stride, q_stride, p_stride;  // fp32 elements of W; bytes of q; entries of scale / zp (also of the staging)
@@ -88,25 +72,16 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // comes back as slower stores; what stays (same box, alternating, 4096 x 11008): bytes 42.1-42.4 -> 41.5-41.7 us, packed nibbles
 // 40.1-40.3 -> 39.25, 11008 x 4096 45.0 -> 44.5 and 43.7 -> 43.05.  Every store instruction there writes whole 128-byte lines.  The
 // MatMulNBits blob does NOT: its 16-byte pieces meet their neighbours (other k-groups: other waves) in the L2, written through they
-// are a fabric write each (38.3-38.4 -> 38.5-38.7 us): bit 0 stays off.  OQ_RTN_SC1 (lab builds): bit 0 the 4-bit blob of the
-// wave kernel, bit 1 the [K,N] bytes, bit 2 the packed [K,N/2] dwords.
-#ifndef OQ_RTN_SC1
-#define OQ_RTN_SC1 6
-#endif
-// K1's fast path is proven row group by row group: OQ_WAVE_GROUP / OQ_FUSED_GROUP rows share ONE decision (a running
-// v_maximum3_f32 of the residuals against the narrowest band, then one ballot) where rounds 1-5 spent a compare and a scalar OR
-// per element and a ballot + branch per row.  Same box, alternating, 4096 x 11008: blob 38.8-39.0 -> 38.1 us (4096 x 4096 17.35 ->
-// 16.2), [K,N] bytes 41.7 -> 40.4, packed nibbles 39.3 -> 37.85.  Four rows per decision cost the wave kernel its fifth wave per
-// SIMD in effect (50.3 us) and the fused kernel its fourth (129 registers): two it is.
-#ifndef OQ_WAVE_GROUP
-#define OQ_WAVE_GROUP 2
-#endif
-#ifndef OQ_FUSED_GROUP
-#define OQ_FUSED_GROUP 2
-#endif
+// are a fabric write each (38.3-38.4 -> 38.5-38.7 us): the blob keeps plain stores.
 __device__ __forceinline__ void store_sc1(uint32_t w, uint32_t* p) { asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(w) : "memory"); }
 
-constexpr int kDefaultWps = 5;     // wave kernel build used when OQ_RTN_WPS is unset (see Tuning)
+// K1's fast path is proven row group by row group: kDecisionRows rows share ONE decision (a running v_maximum3_f32 of the
+// residuals against the narrowest band, then one ballot) instead of a compare and a scalar OR per element and a ballot + branch
+// per row.  Same box, alternating, 4096 x 11008: blob 38.8-39.0 -> 38.1 us (4096 x 4096 17.35 -> 16.2), [K,N] bytes 41.7 -> 40.4,
+// packed nibbles 39.3 -> 37.85.  Four rows per decision cost the wave kernel its fifth wave per SIMD in effect (50.3 us) and the
+// fused kernel its fourth (129 registers): two it is.
+constexpr int kDecisionRows = 2;
+constexpr int kWaveStrips = 4;     // wave kernel: strips (= waves) per block, one k-group each
 constexpr int kColsPerWave = 256;  // 64 lanes x 4 columns: 1 KiB of one fp32 row per wave-instruction
 constexpr int kMaxWaves = 8;
 
@@ -157,7 +132,7 @@ __device__ __forceinline__ void tile_of_block(const RtnArgs& a, uint32_t bid, ui
             cc = r / ((8u << a.xg_log2) * gk_eff);
             r -= cc * (8u << a.xg_log2) * gk_eff;
         }
-        // xg_log2 > 0 (lab): an XCD owns 2^xg_log2 NEIGHBOURING column tiles of a chunk instead of one
+        // xg_log2 > 0: an XCD owns 2^xg_log2 NEIGHBOURING column tiles of a chunk instead of one (the launchers' width rules)
         const uint32_t cw = 8u << a.xg_log2;
         const uint32_t w = min(cw, a.ncol_tiles - cc * cw);
         if (w == cw) {
@@ -172,7 +147,7 @@ __device__ __forceinline__ void tile_of_block(const RtnArgs& a, uint32_t bid, ui
 }
 
 // ---------------------------------------------------------------------------------------------
-// The [K/g, N] -> [N, K/g] transposition of the staged parameters INSIDE the fused launch (round 6; template mode TR, stateful entry
+// The [K/g, N] -> [N, K/g] transposition of the staged parameters INSIDE the fused launch (template mode TR, stateful entry
 // point only, packed nibbles of up to 32 k-groups: see the host's rule).  The separate transpose launch is 5 us of which the kernel
 // itself needs 1.5 (rocprofv3: 43.0 + 5.0 us against 43.2-44.5 us per call).
 // Every main block stores its parameters into the caller's zeroed state with agent-scope (`sc1`) word stores -- four scales and two
@@ -286,8 +261,9 @@ __device__ __forceinline__ void transposer_block(const RtnArgs& a, uint32_t part
 
 // Fused one-pass kernel.  One block = GPB groups (stacked along K) x 256 columns; one group = WPG waves x RPW rows.  Registers per
 // lane: RPW x 4 fp32 of W.
-template <int RPW, bool VEC4, bool EMIT_Q, bool NT = false, bool TR = false>      // TR: parameters staged in the caller's state and transposed inside the launch
+template <int RPW, bool VEC4, bool EMIT_Q, bool TR = false>      // TR: parameters staged in the caller's state and transposed inside the launch
 __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArgs a_in) {
+    constexpr bool NT = RPW == 16;   // the 16-row builds (the Llama-sized groups) load W non-temporally
     __shared__ float4 s_mn[kMaxWaves][kWave];
     __shared__ float4 s_mx[kMaxWaves][kWave];
 
@@ -451,11 +427,10 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
 
     // K1 from registers: v[r][i] <- clamped, biased level (an exact small float).
     const float lo_b = static_cast<float>(qmin + bias), hi_b = static_cast<float>(qmax + bias);
-#if OQ_FUSED_GROUP > 1
-    // one decision per OQ_FUSED_GROUP rows on a running NaN-propagating maximum of |t - k| (v_maximum3_f32 with |.| modifiers) against
+    // one decision per kDecisionRows rows on a running NaN-propagating maximum of |t - k| (v_maximum3_f32 with |.| modifiers) against
     // the narrowest band of the lane's four columns, instead of a compare + scalar OR per element and a ballot + branch per row
     {
-        constexpr int GROUP = RPW % OQ_FUSED_GROUP == 0 ? OQ_FUSED_GROUP : 1;
+        constexpr int GROUP = RPW % kDecisionRows == 0 ? kDecisionRows : 1;
         const float thr_min = nmin(nmin(cq[0].thr, cq[1].thr), nmin(cq[2].thr, cq[3].thr));
 #pragma unroll
         for (int rg = 0; rg < RPW; rg += GROUP) {
@@ -482,21 +457,6 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
                 for (int i = 0; i < 4; ++i) v[rg + r][i] = f[r][i];
         }
     }
-#else
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-        float f[4];
-        bool unsafe = false;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) f[i] = quantize_fast_biased(v[r][i], cq[i], lo_b, hi_b, unsafe);
-        if (__builtin_amdgcn_ballot_w64(unsafe) != 0) {  // wave-uniform, rare: redo this row with the IEEE divide
-#pragma unroll
-            for (int i = 0; i < 4; ++i) f[i] = quantize_exact_biased(v[r][i], cq[i], qmin, qmax, bias);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[r][i] = f[i];
-    }
-#endif
 
     if (a.layout == OQ_LAYOUT_KN) {
         const uint32_t flip = bias ? 0x80808080u : 0u;
@@ -509,9 +469,7 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
                     w = __builtin_amdgcn_cvt_pk_u8_f32(v[r][1], 1, w);
                     w = __builtin_amdgcn_cvt_pk_u8_f32(v[r][2], 2, w);
                     w = __builtin_amdgcn_cvt_pk_u8_f32(v[r][3], 3, w);
-                    if constexpr ((OQ_RTN_SC1 & 2) != 0) store_sc1(w ^ flip, reinterpret_cast<uint32_t*>(o + r * a.N));
-                    else if constexpr (NT) __builtin_nontemporal_store(w ^ flip, reinterpret_cast<uint32_t*>(o + r * a.N));
-                    else *reinterpret_cast<uint32_t*>(o + r * a.N) = w ^ flip;
+                    store_sc1(w ^ flip, reinterpret_cast<uint32_t*>(o + r * a.N));
                 }
             }
         } else {
@@ -552,10 +510,7 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
                     const uint32_t theirs = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(mine), 0xb1 /* quad_perm:[1,0,3,2] */, 0xf, 0xf, false));
                     const uint32_t out = odd ? ((theirs >> 16) | (mine & 0xffff0000u)) : ((mine & 0xffffu) | (theirs << 16));
                     uint8_t* dst = a.q + ((row0 + j + (odd ? 8 : 0)) * a.N + tile_col0 + (lane & ~1) * 4) / 2;
-                    if (pair_ok) {
-                        if constexpr ((OQ_RTN_SC1 & 4) != 0) store_sc1(out, reinterpret_cast<uint32_t*>(dst));
-                        else *reinterpret_cast<uint32_t*>(dst) = out;
-                    }
+                    if (pair_ok) store_sc1(out, reinterpret_cast<uint32_t*>(dst));
                 }
                 return;
             }
@@ -708,10 +663,10 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
     uint32_t col_tile, row_tile;
     tile_of_block(a, bid, nblk, row_tile, col_tile);
 
-    // block = gpb k-groups x spb strips of 4 * LPR columns; neighbouring strips on neighbouring waves
-    const int spb = 1 << a.spb_log2;
-    const int64_t kg = static_cast<int64_t>(row_tile) * a.gpb + (wave >> a.spb_log2);
-    const int64_t strip0 = (static_cast<int64_t>(col_tile) * spb + (wave & (spb - 1))) * (4 * LPR);
+    // block = one k-group x kWaveStrips strips of 4 * LPR columns; neighbouring strips on neighbouring waves
+    // (the tile ids come out of a float division: readfirstlane keeps what follows from them in scalar registers)
+    const int64_t kg = __builtin_amdgcn_readfirstlane(row_tile);
+    const int64_t strip0 = (static_cast<int64_t>(__builtin_amdgcn_readfirstlane(col_tile)) * kWaveStrips + wave) * (4 * LPR);
     if (kg >= a.kgroups || strip0 >= a.N) return;  // wave-uniform; nothing below synchronises
     // WPS > 0: 32-bit output indices (the host checks N * K/g * G/2 < 2^32): scalar base + 32-bit lane offset addressing
     // instead of 64-bit address pairs held across the kernel
@@ -778,9 +733,8 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
         const ColQ c = make_colq(qparam_from_minmax(mnj, mxj, a.grid), mnj, mxj, bias);
         own_scale = c.scale;
         if (h < 4) s_scale[wave][j * LPR + cl] = c.scale;      // for the fallback: slot i of strip column cl at [i * LPR + cl]
-        if (h < 4 && col_ok && !OQ_ATTR(a.nt, 8)) {   // rtn.py:98-109 result layout (entry n * K/g + kg); lane set j stores column slot j
-            idx_t o = (c0 + j) * kgroups_i + kg_i;
-            if (OQ_ATTR(a.nt, 32)) o = static_cast<idx_t>((kg * (a.N / (4 * LPR)) + strip0 / (4 * LPR)) * (4 * LPR) + lane);   // attribution builds only
+        if (h < 4 && col_ok) {   // rtn.py:98-109 result layout (entry n * K/g + kg); lane set j stores column slot j
+            const idx_t o = (c0 + j) * kgroups_i + kg_i;
             a.scale[o] = c.scale;
             a.zp[o] = static_cast<uint8_t>(static_cast<int32_t>(c.zpb) - bias);
         }
@@ -849,15 +803,14 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
         const f32x2 rv[2] = {{rinv[0], rinv[1]}, {rinv[2], rinv[3]}};
         const f32x2 zm[2] = {{zpb[0] + kMagic, zpb[1] + kMagic}, {zpb[2] + kMagic, zpb[3] + kMagic}};
         const float lo_m = lo_b + kMagic, hi_m = hi_b + kMagic;
-#if OQ_WAVE_GROUP > 1
-        // one decision per OQ_WAVE_GROUP rows: the residuals fold into a running NaN-propagating maximum (one v_maximum3_f32 with |.|
+        // one decision per kDecisionRows rows: the residuals fold into a running NaN-propagating maximum (one v_maximum3_f32 with |.|
         // modifiers per pair) instead of two compares and two scalar ORs per pair and a ballot + branch per row
 #pragma unroll
-        for (int rg = 0; rg < 16; rg += OQ_WAVE_GROUP) {
-            float f[OQ_WAVE_GROUP][4];
+        for (int rg = 0; rg < 16; rg += kDecisionRows) {
+            float f[kDecisionRows][4];
             float far = 0.0f;
 #pragma unroll
-            for (int r = 0; r < OQ_WAVE_GROUP; ++r)
+            for (int r = 0; r < kDecisionRows; ++r)
 #pragma unroll
                 for (int p2 = 0; p2 < 2; ++p2) {
                     const f32x2 x = {v[rg + r][2 * p2], v[rg + r][2 * p2 + 1]};
@@ -871,48 +824,23 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
                 float se[4];
                 fallback_scales(se);
 #pragma unroll
-                for (int r = 0; r < OQ_WAVE_GROUP; ++r)
+                for (int r = 0; r < kDecisionRows; ++r)
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         f[r][i] = __uint_as_float(0x4B400000u + static_cast<uint32_t>(quantize_one(v[rg + r][i], se[i], static_cast<int32_t>(zpb[i]) - bias, qmin, qmax) + bias));
             }
 #pragma unroll
-            for (int r = 0; r < OQ_WAVE_GROUP; ++r)
+            for (int r = 0; r < kDecisionRows; ++r)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[rg + r][i] = f[r][i];
         }
-#else
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float f[4];
-            bool unsafe = false;
-#pragma unroll
-            for (int p2 = 0; p2 < 2; ++p2) {
-                const f32x2 x = {v[r][2 * p2], v[r][2 * p2 + 1]};
-                const f32x2 u = __builtin_elementwise_fma(x, rv[p2], zm[p2]);
-                const f32x2 res = __builtin_elementwise_fma(x, rv[p2], zm[p2] - u);
-                unsafe = unsafe || !(fabsf(res.x) < thr) || !(fabsf(res.y) < thr);
-                f[2 * p2] = __builtin_amdgcn_fmed3f(u.x, lo_m, hi_m);
-                f[2 * p2 + 1] = __builtin_amdgcn_fmed3f(u.y, lo_m, hi_m);
-            }
-            if (__builtin_amdgcn_ballot_w64(unsafe) != 0) {  // wave-uniform, rare: redo this row with the IEEE divide
-                float se[4];
-                fallback_scales(se);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    f[i] = __uint_as_float(0x4B400000u + static_cast<uint32_t>(quantize_one(v[r][i], se[i], static_cast<int32_t>(zpb[i]) - bias, qmin, qmax) + bias));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[r][i] = f[i];
-        }
-#endif
-        if (!col_ok || OQ_ATTR(a.nt, 16)) return;
+        if (!col_ok) return;
         // qrules/_common.py:72-87: out-channel n, k-group kg -> G * bits / 8 bytes, k ascending, even k in the low nibble.
         // v[r][i] holds M + level: the level is byte 0 of its bits (the other three bytes are those of M).
         auto low_bytes = [](uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3) {   // [b0.0, b1.0, b2.0, b3.0]
             return __builtin_amdgcn_perm(b1, b0, 0x0c0c0400u) | __builtin_amdgcn_perm(b3, b2, 0x04000c0cu);
         };
-        if (a.grid.bits == 4 && LPR == 8 && !OQ_ATTR(a.nt, 64)) {
+        if (a.grid.bits == 4 && LPR == 8) {
             // 16-byte stores: the lane sets 2m and 2m + 1 of a 16-lane DPP row hold neighbouring 8-byte pieces of every
             // column slot.  The even set takes its partner's pieces of slots 0 and 1, the odd set its partner's pieces of
             // slots 2 and 3 (one row_ror:8 per dword), and every lane issues TWO 16-byte stores instead of four 8-byte ones.
@@ -939,9 +867,7 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
                 const u32x4 val = odd ? u32x4{r0, r1, m0, m1} : u32x4{m0, m1, r0, r1};
                 const idx_t col = c0 + (odd ? 2 + t : t);
                 u32x4* o = reinterpret_cast<u32x4*>(a.q + ((col * kgroups_i + kg_i) * (G / 2) + (h & ~1) * 8));
-                if constexpr ((OQ_RTN_SC1 & 1) != 0) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(o), "v"(val) : "memory");
-                else if (a.nt & 2) __builtin_nontemporal_store(val, o);
-                else *o = val;
+                *o = val;
             }
         } else if (a.grid.bits == 4) {
             const uint32_t flip = bias ? 0x88888888u : 0u;
@@ -957,11 +883,7 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
                     words[wd] = low_bytes(pr[0], pr[1], pr[2], pr[3]) ^ flip;
                 }
                 u32x2* o = reinterpret_cast<u32x2*>(a.q + (((c0 + i) * kgroups_i + kg_i) * (G / 2) + h * 8));
-                if (OQ_ATTR(a.nt, 32))   // attribution builds only: every store instruction writes 512 contiguous bytes
-                    o = reinterpret_cast<u32x2*>(a.q + ((kg * (a.N / (4 * LPR)) + strip0 / (4 * LPR)) * (2 * G * LPR) + i * 512 + lane * 8));
-                const u32x2 t = {words[0], words[1]};
-                if (a.nt & 2) __builtin_nontemporal_store(t, o);
-                else *o = t;
+                *o = u32x2{words[0], words[1]};
             }
         } else {
             const uint32_t flip = bias ? 0x80808080u : 0u;
@@ -973,9 +895,7 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
                     words[wd] = low_bytes(__float_as_uint(v[wd * 4][i]), __float_as_uint(v[wd * 4 + 1][i]), __float_as_uint(v[wd * 4 + 2][i]),
                                           __float_as_uint(v[wd * 4 + 3][i])) ^ flip;
                 u32x4* o = reinterpret_cast<u32x4*>(a.q + (((c0 + i) * kgroups_i + kg_i) * G + h * 16));
-                const u32x4 t = {words[0], words[1], words[2], words[3]};
-                if (a.nt & 2) __builtin_nontemporal_store(t, o);
-                else *o = t;
+                *o = u32x4{words[0], words[1], words[2], words[3]};
             }
         }
         return;
@@ -1021,9 +941,7 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
                 words[wd] = (ev | (od << 4)) ^ flip;
             }
             u32x2* o = reinterpret_cast<u32x2*>(a.q + (((c0 + i) * kgroups_i + kg_i) * (G / 2) + h * 8));
-            const u32x2 t = {words[0], words[1]};
-            if (a.nt & 2) __builtin_nontemporal_store(t, o);
-            else *o = t;
+            *o = u32x2{words[0], words[1]};
         }
     } else {
         const uint32_t flip = bias ? 0x80808080u : 0u;
@@ -1038,9 +956,7 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
                 words[wd] = acc ^ flip;
             }
             u32x4* o = reinterpret_cast<u32x4*>(a.q + (((c0 + i) * kgroups_i + kg_i) * G + h * 16));
-            const u32x4 t = {words[0], words[1], words[2], words[3]};
-            if (a.nt & 2) __builtin_nontemporal_store(t, o);
-            else *o = t;
+            *o = u32x4{words[0], words[1], words[2], words[3]};
         }
     }
 }
@@ -1371,28 +1287,6 @@ __global__ __launch_bounds__(256) void transpose_qparams(const float* scale_t, c
     }
 }
 
-// Experiment knobs: speed only, every setting produces the same bytes (-1 = the tuned default).  Read once per process (rtn_impl).
-struct Tuning {
-    int order = -1, gk = -1, nt = -1, stage = -1, stage_q = -1, wavek = -1, gpb = -1, wpb = -1, wps = -1, resident = -1, xg = -1;
-    static int env_int(const char* name) { const char* v = getenv(name); return v ? atoi(v) : -1; }
-    static Tuning from_env() {
-        Tuning t;
-        t.order = env_int("OQ_RTN_ORDER");      // 0 K-fastest + XCD strips, 1 column tiles fastest, 2 L2-merging blocks
-        t.gk = env_int("OQ_RTN_GK");            // row tiles per id block of order 2
-        t.nt = env_int("OQ_RTN_NT");            // bit 0 non-temporal W loads and [K,N] stores, bit 1 non-temporal blob stores (masked with kNtMask)
-        t.stage = env_int("OQ_RTN_STAGE");      // stage (scale, zp) as [K/g, N] + transpose launch
-        t.stage_q = env_int("OQ_RTN_STAGE_Q");  // assemble blob chunks in LDS
-        t.wavek = env_int("OQ_RTN_WAVEK");      // blob layout: wave-owns-group kernel (1) or the block kernel (0)
-        t.gpb = env_int("OQ_RTN_GPB");          // wave kernel: k-groups per block
-        t.wpb = env_int("OQ_RTN_WPB");          // wave kernel: waves per block
-        t.wps = env_int("OQ_RTN_WPS");          // wave kernel: 0 = the 4-waves-per-SIMD build, 5 = the 92-register build (5 per SIMD)
-        t.resident = env_int("OQ_RTN_RESIDENT"); // channel / tensor / tall groups: 0 = the three-launch path that reads W twice
-        t.xg = env_int("OQ_RTN_XG");            // order 2: log2 of the neighbouring column tiles one XCD owns (speed only)
-        return t;
-    }
-    int nt_bits() const { return (nt >= 0 ? nt : 1) & kNtMask; }
-};
-
 // ------------------------------------------------------------------------------------ dispatch
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static int32_t zp_signed(int32_t qtype) { return (qtype == OQ_INT4 || qtype == OQ_INT8) ? 1 : 0; }
@@ -1423,7 +1317,6 @@ static bool in_launch_shape(int64_t K, int64_t N, int64_t g) {
 
 // Fills the id-division constants of the chosen block order; ids beyond the fast-division range use order 0.
 static void set_block_order(RtnArgs& a) {
-    if (a.gk < 1) a.gk = 1;
     const uint64_t nblk = static_cast<uint64_t>(a.ncol_tiles) * a.nrow_tiles;
     if (nblk >= (1u << 22)) a.order = 0;
     a.fd_ncol = make_fastdiv(a.ncol_tiles);
@@ -1441,20 +1334,17 @@ static void launch_fused_kernel(int rpw, const RtnArgs& a, dim3 grid, dim3 block
         case 16:
             if constexpr (VEC4 && EMIT_Q) {
                 if (a.tr_scale != nullptr) {      // the host sets it only with rpw == 16, eight waves per group, vec4, emit_q
-                    if (a.nt) hipLaunchKernelGGL((rtn_group_fused<16, true, true, true, true>), grid, block, 0, s, a);
-                    else hipLaunchKernelGGL((rtn_group_fused<16, true, true, false, true>), grid, block, 0, s, a);
+                    hipLaunchKernelGGL((rtn_group_fused<16, true, true, true>), grid, block, 0, s, a);
                     break;
                 }
             }
-            if (a.nt) hipLaunchKernelGGL((rtn_group_fused<16, VEC4, EMIT_Q, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((rtn_group_fused<16, VEC4, EMIT_Q, false>), grid, block, 0, s, a);
+            hipLaunchKernelGGL((rtn_group_fused<16, VEC4, EMIT_Q>), grid, block, 0, s, a);
             break;
         default: hipLaunchKernelGGL((rtn_group_fused<32, VEC4, EMIT_Q>), grid, block, 0, s, a); break;
     }
 }
 
-template <bool NT>
-static const void* tr_build() { return reinterpret_cast<const void*>(rtn_group_fused<16, true, true, NT, true>); }
+static const void* tr_build() { return reinterpret_cast<const void*>(rtn_group_fused<16, true, true, true>); }
 
 // the zeroed state of the in-launch transposition: [kgroups, N] fp32 scales + one 8-byte {four zero points, marker} granule per four columns
 static size_t fused_state_bytes(int64_t K, int64_t N, int64_t g) {
@@ -1515,11 +1405,7 @@ int32_t launch_quantize_kn(const float* W, int64_t K, int64_t N, int64_t ldw, in
 // of large matrices lose a little again (dirty output lines evicted between another matrix' reads instead of written back
 // in a burst at a kernel's end).  ~1.6e8 parameters per launch sits at or next to the best point of every row.
 static int64_t matrices_per_launch(int64_t K, int64_t N, int64_t count) {
-    static const int64_t per_launch = [] {      // OQ_RTN_MPL: parameters per launch in millions (lab; speed only)
-        const char* v = getenv("OQ_RTN_MPL");
-        const long x = v ? atol(v) : 0;
-        return x > 0 ? static_cast<int64_t>(x) * 1000000 : static_cast<int64_t>(160000000);
-    }();
+    constexpr int64_t per_launch = 160000000;
     int64_t m = per_launch / (K * N);
     if (m > 65535) m = 65535;   // blockIdx.y
     if (m < 1) m = 1;
@@ -1591,33 +1477,32 @@ struct RtnPlan {
     bool use_state = false;   // Ticketed: the caller's zeroed state instead of the workspace
 };
 
-static bool in_launch_fits(int64_t N, bool nt);
+static bool in_launch_fits(int64_t N);
 
-static RtnPlan plan_route(const RtnCall& c, const RtnShape& sh, const Tuning& tune, hipStream_t s) {
+static RtnPlan plan_route(const RtnCall& c, const RtnShape& sh, hipStream_t s) {
     const int64_t K = c.K, N = c.N, g = sh.g, kgroups = sh.kgroups;
     if (c.strategy == OQ_GROUP && K % g != 0) return {Route::FlatGroups};
     if (c.mse) return {Route::Mse};
     // MatMulNBits blob with a group of 32 / 64 / 128 rows: wave-owns-group kernel (no LDS, no barrier)
-    if (c.strategy == OQ_GROUP && c.layout == OQ_LAYOUT_NBITS && sh.vec4 && (g == 32 || g == 64 || g == 128) && tune.wavek != 0 &&
+    if (c.strategy == OQ_GROUP && c.layout == OQ_LAYOUT_NBITS && sh.vec4 && (g == 32 || g == 64 || g == 128) &&
         c.ldw < (1 << 22))   // 32-bit lane offsets
         return {Route::Wave};
     if (sh.fused) {
         RtnPlan p{Route::Fused};
         // [K,N] layouts: the n-major parameters either leave the kernel as they are (4-byte stores 128 bytes apart) or are
-        // staged [K/g, N] and transposed by a second launch (~5 us of kernel + a boundary, whatever the size).  Rounds 1-4
-        // staged always -- tuned on 4096 x 11008, the one Llama width where that is right: its 43 column tiles are odd, so
-        // with column-fastest ids the k-groups of a column run on eight different XCDs and their 4-byte pieces of a line
-        // never meet in one L2.  Round 5 (scripts/lab_knob_sweep.sh, STAGE=0, [K,N] bytes, K = 4096): N = 256 11.6 -> 8.5 us,
+        // staged [K/g, N] and transposed by a second launch (~5 us of kernel + a boundary, whatever the size).  Staging is
+        // right on 4096 x 11008: its 43 column tiles are odd, so with column-fastest ids the k-groups of a column run on
+        // eight different XCDs and their 4-byte pieces of a line never meet in one L2.  Staged -> direct, [K,N] bytes,
+        // K = 4096 (docs/LAB_NOTES_r05.md): N = 256 11.6 -> 8.5 us,
         // 2048 15.0 -> 11.6, 4096 22.4 -> 19.3, 5120 25.7 -> 23.7, 8192 35.0 -> 32.2, 11264 45.4 -> 43.6, 14336 54.4 -> 51.9,
         // 28672 101.6 -> 99.5; 11008 44.8 -> 46.6, 27648 98.1 -> 100.1, 32000 112.4 -> 124.3.  Direct when the column tiles
         // are a multiple of eight (every k-group of a column on one XCD), or the parameters are few enough for the fixed
         // cost of the second launch to dominate.  Speed only.
         const int64_t nct = ceil_div(N, kColsPerWave), nparams = kgroups * N;
         const bool direct = nct % 8 == 0 || nparams <= (256 << 10) || (nct % 2 == 0 && nparams <= (512 << 10));
-        const bool want_stage = tune.stage >= 0 ? tune.stage != 0 : (c.layout != OQ_LAYOUT_NBITS && !direct);
-        p.staged = want_stage && sh.vec4 && kgroups > 1 && c.workspace != nullptr &&
+        p.staged = c.layout != OQ_LAYOUT_NBITS && !direct && sh.vec4 && kgroups > 1 && c.workspace != nullptr &&
                    c.workspace_bytes >= static_cast<size_t>(c.batch) * stage_ws(K, N, g) && aligned16(c.workspace);
-        // Round 6: with the caller's zeroed state (oq_rtn_quantize_stateful_f32) the staged parameters are transposed inside the
+        // With the caller's zeroed state (oq_rtn_quantize_stateful_f32) the staged parameters are transposed inside the
         // launch, by blocks appended to the grid, instead of by a second launch (see transposer_block).
         // Measured (scripts/lab_kn_inlaunch.py, same box, staged + launch -> in the launch, us; the shipped transposer: one block per 128
         // columns, two granules per thread in flight): packed nibbles 4096 x 11008 44.2-44.3 -> 41.3, 4096 x 11000 48.6 -> 45.3-45.4,
@@ -1625,17 +1510,17 @@ static RtnPlan plan_route(const RtnCall& c, const RtnShape& sh, const Tuning& tu
         // 106.7-107.5; [K,N] bytes int8 4096 x 11008 45.5-45.6 -> 43.2, 8192 x 11008 79.5-79.9 -> 78.8-79.0, 4096 x 27648 98.2-98.6 ->
         // 97.7-98.3, 4096 x 32000 112.8-113.1 -> 113.7 (the one loss).  More than two passes put their round trips on the tail of the
         // launch: up to 64 k-groups.  Speed only.
-        p.in_launch = p.staged && tune.stage < 0 && c.emit_q && (c.layout == OQ_LAYOUT_KN_PACKED4 || c.layout == OQ_LAYOUT_KN) && kgroups <= 64 &&
+        p.in_launch = p.staged && c.emit_q && (c.layout == OQ_LAYOUT_KN_PACKED4 || c.layout == OQ_LAYOUT_KN) && kgroups <= 64 &&
                       in_launch_shape(K, N, g) && c.batch == 1 && c.table == nullptr && c.state != nullptr &&
                       c.state_bytes >= fused_state_bytes(K, N, g) && aligned16(c.scale) && (reinterpret_cast<uintptr_t>(c.zp) & 3u) == 0 &&
-                      !rtn_stream_is_capturing(s) && in_launch_fits(N, tune.nt_bits() != 0);
+                      !rtn_stream_is_capturing(s) && in_launch_fits(N);
         return p;
     }
     // channel, tensor, groups taller than the fused kernel holds: W read once, ranges completed across workgroups
     // (rtn_resident.hip); what it does not take (scalar-aligned operands, the blob layout, ranges without integers,
     // columns taller than 16384 rows) runs on the three launches.  A stream under capture takes the three launches too: the
     // ticketed kernels must never overlap one another, and a replayed graph is ordered against nothing the library sees
-    if (tune.resident != 0 && !rtn_stream_is_capturing(s)) {
+    if (!rtn_stream_is_capturing(s)) {
         if (c.state != nullptr && rtn_resident_eligible(K, N, c.ldw, c.W, c.q, c.strategy, g, c.layout, c.emit_q, c.state_bytes))
             return {Route::Ticketed, false, false, true};
         if (rtn_resident_eligible(K, N, c.ldw, c.W, c.q, c.strategy, g, c.layout, c.emit_q, c.workspace ? c.workspace_bytes : 0))
@@ -1645,12 +1530,11 @@ static RtnPlan plan_route(const RtnCall& c, const RtnShape& sh, const Tuning& tu
 }
 
 // (c) One launcher per route.  The RtnArgs fields the wave and the fused kernel share:
-static RtnArgs group_args(const RtnCall& c, const RtnShape& sh, const Tuning& tune) {
+static RtnArgs group_args(const RtnCall& c, const RtnShape& sh) {
     RtnArgs a{};
     a.W = c.W; a.K = c.K; a.N = c.N; a.ldw = c.ldw; a.g = sh.g; a.kgroups = sh.kgroups;
     a.q = static_cast<uint8_t*>(c.q); a.scale = c.scale; a.zp = static_cast<uint8_t*>(c.zp); a.grid = sh.grid; a.layout = c.layout;
     a.w_stride = c.w_stride; a.q_stride = c.q_stride; a.p_stride = c.N * sh.kgroups; a.table = c.table;
-    a.nt = tune.nt_bits();
     return a;
 }
 
@@ -1661,40 +1545,32 @@ static int32_t launch_flat_groups(const RtnCall& c, const RtnShape& sh, hipStrea
     return check_launch("rtn_flat_groups");
 }
 
-static int32_t launch_wave(const RtnCall& c, const RtnShape& sh, const Tuning& tune, hipStream_t s) {
-    RtnArgs a = group_args(c, sh, tune);
+static int32_t launch_wave(const RtnCall& c, const RtnShape& sh, hipStream_t s) {
+    RtnArgs a = group_args(c, sh);
     a.wpg = 1;
     const int lpr = static_cast<int>(1024 / sh.g);
-    int wpb = tune.wpb > 0 ? tune.wpb : 4;
-    if (wpb > kMaxWaves) wpb = kMaxWaves;
-    while (wpb & (wpb - 1)) wpb &= wpb - 1;   // power of two
-    int gpb = tune.gpb > 0 ? tune.gpb : 1;
-    while (gpb & (gpb - 1)) gpb &= gpb - 1;
-    while (gpb > 1 && (gpb > wpb || gpb > sh.kgroups)) gpb >>= 1;
-    a.gpb = gpb;
-    while ((1 << (a.spb_log2 + 1)) <= wpb / gpb) ++a.spb_log2;
+    // block = kWaveStrips waves: one k-group x four neighbouring strips of 4 * lpr columns
     const int64_t nstrips = ceil_div(c.N, 4 * lpr);
-    a.ncol_tiles = static_cast<uint32_t>(ceil_div(nstrips, wpb / gpb));
-    a.nrow_tiles = static_cast<uint32_t>(ceil_div(sh.kgroups, gpb));
-    a.order = tune.order >= 0 ? tune.order : 2;
-    a.gk = tune.gk > 0 ? tune.gk : 4;
+    a.ncol_tiles = static_cast<uint32_t>(ceil_div(nstrips, kWaveStrips));
+    a.nrow_tiles = static_cast<uint32_t>(sh.kgroups);
+    a.order = 2;
+    a.gk = 4;
     // Column tiles (512 B of a row) that one XCD owns side by side inside a chunk of the L2-merging order.  One tile per XCD
     // leaves an XCD a fixed 512-byte residue of every 4 KB of a row band; two neighbours (1 KB) measured 2-5 % faster on
     // every Llama width but the multiples of 16384 (4096: 18.0 -> 17.2 us, 11008: 40.1 -> 38.8, 28672: 100.4 -> 96.3,
     // 32000: 122.3 -> 116.4; 16384: 56.9 -> 57.7), eight (4 KB) on rows of 32 KB (8192: 32.3 -> 30.0, 8192 x 8192:
-    // 62.4 -> 56.6): scripts/lab_order_sweep.sh, docs/LAB_NOTES_r05.md.  Speed only.
+    // 62.4 -> 56.6): docs/LAB_NOTES_r05.md.  Speed only.
     // (g = 128; a tile of the g = 64 / 32 builds is 1 / 2 KB wide already: 4096 x 11008 g = 64 43.1 us with one tile, 44.6 with two)
     const int want_log2 = c.N % 16384 == 0 ? 9 : (c.N % 8192 == 0 ? 12 : 10);      // bytes of a row one XCD owns side by side
     int tile_log2 = 6;                                                              // 64 * lpr bytes: four strips of 4 * lpr columns
     for (int l = lpr; l > 1; l >>= 1) ++tile_log2;
-    const int rule = want_log2 > tile_log2 ? want_log2 - tile_log2 : 0;
-    a.xg_log2 = tune.xg >= 0 ? static_cast<uint32_t>(tune.xg > 4 ? 4 : tune.xg) : static_cast<uint32_t>(rule);
+    a.xg_log2 = static_cast<uint32_t>(want_log2 > tile_log2 ? want_log2 - tile_log2 : 0);
     set_block_order(a);
-    const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(c.batch)), block(static_cast<uint32_t>(wpb * kWave));
-    // the 5-waves-per-SIMD build addresses its outputs with 32-bit offsets and needs blocks of <= 4 waves
+    const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(c.batch)), block(kWaveStrips * kWave);
+    // the 5-waves-per-SIMD build addresses its outputs with 32-bit offsets; g = 32 (two lane sets) does not fit its 96
+    // registers.  Everything else runs the plain build.
     const bool small_idx = static_cast<uint64_t>(c.N) * static_cast<uint64_t>(c.K) * static_cast<uint64_t>(sh.grid.bits) / 8u < (1ull << 32);
-    const int wps = tune.wps >= 0 ? tune.wps : kDefaultWps;
-    if (wps > 0 && small_idx && wpb <= 4 && lpr <= 16) {   // g = 32 (two lane sets) does not fit 96 registers: plain build
+    if (small_idx && lpr <= 16) {
         if (lpr == 8) hipLaunchKernelGGL((rtn_group_wave<8, true, 5>), grid_dim, block, 0, s, a);
         else hipLaunchKernelGGL((rtn_group_wave<16, true, 5>), grid_dim, block, 0, s, a);
         return check_launch("rtn_group_wave<5 waves per SIMD>");
@@ -1707,9 +1583,9 @@ static int32_t launch_wave(const RtnCall& c, const RtnShape& sh, const Tuning& t
     return check_launch("rtn_group_wave");
 }
 
-static int32_t launch_fused(const RtnCall& c, const RtnShape& sh, const RtnPlan& p, const Tuning& tune, hipStream_t s) {
+static int32_t launch_fused(const RtnCall& c, const RtnShape& sh, const RtnPlan& p, hipStream_t s) {
     const int64_t N = c.N, kgroups = sh.kgroups;
-    RtnArgs a = group_args(c, sh, tune);
+    RtnArgs a = group_args(c, sh);
     if (p.in_launch) {
         a.tr_scale = static_cast<float*>(c.state);
         a.tr_zp = reinterpret_cast<uint2*>(static_cast<uint8_t*>(c.state) + (kgroups * N * 4 + 255) / 256 * 256);
@@ -1723,20 +1599,19 @@ static int32_t launch_fused(const RtnCall& c, const RtnShape& sh, const RtnPlan&
     if (a.gpb > kgroups) a.gpb = static_cast<int32_t>(kgroups);
     a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, kColsPerWave));
     a.nrow_tiles = static_cast<uint32_t>(ceil_div(kgroups, a.gpb));
-    // Tuned on 4096x11008 (profiles/r01_rtn_knob_sweep.txt).  [K,N] bytes: plain column-fastest ids, parameters
-    // staged [K/g, N] + transpose launch.  MatMulNBits blob: L2-merging id order (its 64-byte half lines and the
-    // 4-byte scales of neighbouring k-groups meet in one L2) + direct n-major parameter stores.  The OQ_RTN_*
-    // environment variables override these choices for experiments only.
-    const bool blob = c.layout == OQ_LAYOUT_NBITS;
-    a.order = tune.order >= 0 ? tune.order : (blob ? 2 : 1);      // KN and KN_PACKED4 alike: plain column-fastest ids
-    a.gk = tune.gk > 0 ? tune.gk : 8;
+    // Tuned on 4096x11008 (profiles/r01_rtn_knob_sweep.txt).  [K,N] bytes and packed nibbles: plain column-fastest ids.
+    // MatMulNBits blob: L2-merging id order (its 64-byte half lines and the 4-byte scales of neighbouring k-groups meet
+    // in one L2) + direct n-major parameter stores.
     // 16 column tiles (N = 4096): with column-fastest ids an XCD owns tiles x and x + 8 of EVERY row band; the L2-merging order
     // with two neighbouring tiles per XCD measured 25.1 -> 22.3 us (4096 x 4096 [K,N] bytes), 50.7 -> 48.1 (11008 x 4096),
-    // 60.5 -> 57.6 (14336 x 4096); every other width of the sweep keeps the plain order (scripts/lab_order_sweep.sh)
-    const bool sixteen = !blob && a.ncol_tiles == 16 && tune.order < 0;
-    if (sixteen) a.order = 2;
-    a.stage_q = ((tune.stage_q != 0) && blob && sh.vec4 && sh.rpw == 16 && a.wpg * a.gpb == kMaxWaves && kgroups % a.gpb == 0) ? 1 : 0;
-    a.xg_log2 = tune.xg >= 0 ? static_cast<uint32_t>(tune.xg > 4 ? 4 : tune.xg) : (sixteen ? 1u : 0u);
+    // 60.5 -> 57.6 (14336 x 4096); every other width of the sweep keeps the plain order (docs/LAB_NOTES_r05.md)
+    const bool blob = c.layout == OQ_LAYOUT_NBITS;
+    const bool sixteen = !blob && a.ncol_tiles == 16;
+    a.order = (blob || sixteen) ? 2 : 1;
+    a.gk = 8;
+    a.xg_log2 = sixteen ? 1u : 0u;
+    // the blob chunks of a block are assembled in LDS when its eight waves hold whole chunks of every column
+    a.stage_q = (blob && sh.vec4 && sh.rpw == 16 && a.wpg * a.gpb == kMaxWaves && kgroups % a.gpb == 0) ? 1 : 0;
     set_block_order(a);
     const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles + (p.in_launch ? static_cast<uint32_t>(ceil_div(N, 128)) : 0u), static_cast<uint32_t>(c.batch)),
         block(static_cast<uint32_t>(a.wpg * a.gpb * kWave));
@@ -1795,16 +1670,15 @@ int32_t rtn_impl(const RtnCall& c) {
     RtnShape sh;
     const int32_t st = check_call(c, sh);
     if (st != OQ_OK) return st;
-    static const Tuning tune = Tuning::from_env();
     const hipStream_t s = as_stream(c.stream);
-    const RtnPlan p = plan_route(c, sh, tune, s);
+    const RtnPlan p = plan_route(c, sh, s);
     switch (p.route) {
         case Route::FlatGroups: return launch_flat_groups(c, sh, s);
         case Route::Mse:
             return rtn_mse_impl(c.W, c.K, c.N, c.ldw, sh.grid, c.strategy, sh.g, c.q, c.scale, c.zp, zp_signed(c.qtype), c.workspace,
                                 c.workspace_bytes, s, c.emit_q);
-        case Route::Wave: return launch_wave(c, sh, tune, s);
-        case Route::Fused: return launch_fused(c, sh, p, tune, s);
+        case Route::Wave: return launch_wave(c, sh, s);
+        case Route::Fused: return launch_fused(c, sh, p, s);
         case Route::Ticketed:
             return rtn_resident_impl(c.W, c.K, c.N, c.ldw, sh.grid, c.strategy, sh.g, static_cast<uint8_t*>(c.q), c.scale,
                                      static_cast<uint8_t*>(c.zp), c.layout, p.use_state ? c.state : c.workspace,
@@ -1815,13 +1689,12 @@ int32_t rtn_impl(const RtnCall& c) {
 }
 
 // Forward progress of the in-launch transposition (see transposer_block): its ceil(N / 128) appended blocks take at most 3/4 of the
-// workgroup slots the device holds of the TR build that would run -- the rule of the ticketed kernels (rtn_resident_eligible).
-// Defined last and naming the kernels through tr_build only, so that the device code keeps its order of kernels (the launchers'):
+// workgroup slots the device holds of the TR build -- the rule of the ticketed kernels (rtn_resident_eligible).
+// Defined last and naming the kernel through tr_build only, so that the device code keeps its order of kernels (the launchers'):
 // host-only changes leave the assembly of this file unchanged, which is how they are checked.
-static bool in_launch_fits(int64_t N, bool nt) {
-    static std::atomic<int> cache[2][64];
-    const void* k = nt ? tr_build<true>() : tr_build<false>();
-    return 4 * ceil_div(N, 128) <= 3 * static_cast<int64_t>(resident_slots(cache[nt ? 1 : 0], k, kMaxWaves * kWave));
+static bool in_launch_fits(int64_t N) {
+    static std::atomic<int> cache[64];
+    return 4 * ceil_div(N, 128) <= 3 * static_cast<int64_t>(resident_slots(cache, tr_build(), kMaxWaves * kWave));
 }
 
 }  // namespace oq

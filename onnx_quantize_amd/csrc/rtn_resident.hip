@@ -34,7 +34,6 @@
 // to 1024 tiles is read exactly once and skips that phase altogether.
 #include "rtn_internal.hpp"
 
-#include <cstdlib>
 #include <mutex>
 
 namespace oq {
@@ -1069,7 +1068,7 @@ int resident_slots(std::atomic<int> (&cache)[64], const void* kernel, int thread
 }
 
 // Which kernel takes a channel / tall-group call (speed only, same bytes).  Measured, int8 per channel, same box
-// (scripts/quick_strategies.py --lib, round 4):
+// (scripts/quick_strategies.py --lib, docs/LAB_NOTES_r04.md):
 //                                   4096x11008  4096x4096  8192x8192  11008x4096  16384x4096
 //   rtn_resident_groups, 256 rows      65.0        27.7      100        83.7        125.9 us
 //   rtn_resident_groups, 128 rows      70          30          -        84            -
@@ -1077,25 +1076,14 @@ int resident_slots(std::atomic<int> (&cache)[64], const void* kernel, int thread
 // The streamed kernel wins wherever a workgroup refills its slots a few times: taller ranges than 4096 rows, or at least
 // four 128-row tiles per workgroup of a 256-CU device (4096 x 11008: 5.4).  With two tiles per workgroup (4096 x 4096) they
 // are all it ever loads, one after the other, and the one-tile-per-workgroup kernel keeps the call.
-// 64- and 32-row tiles (4 / 7 workgroups per CU) took 92 / 154 us on the first.  OQ_RTN_RES_TILE = 256 | 128 forces
-// rtn_resident_groups with that tile height, OQ_RTN_RES_TILE = 1 the streamed kernel (lab switch).
+// 64- and 32-row tiles (4 / 7 workgroups per CU) took 92 / 154 us on the first.
 constexpr int64_t kResStreamAbove = 4096;
 constexpr int64_t kResStreamTiles = 1024;
-static int forced_tile_rows() {
-    static const int forced = [] {
-        const char* v = getenv("OQ_RTN_RES_TILE");
-        const int r = v ? atoi(v) : 0;
-        return (r == 256 || r == 128 || r == 1) ? r : 0;
-    }();
-    return forced;
-}
 // `ranges`: column tiles x k-groups of the call
 static bool groups_streamed(int64_t g, int64_t ranges) {
-    if (forced_tile_rows()) return forced_tile_rows() == 1;
     return g > kResStreamAbove || ranges * ceil_div(g, kResGroupTileRows) >= kResStreamTiles;
 }
 static int groups_tile_rows(int64_t g, int64_t ranges) {
-    if (forced_tile_rows() > 1) return forced_tile_rows();
     if (groups_streamed(g, ranges)) return kResGroupTileRows;
     // a call of fewer 256-row tiles than the device has CUs leaves CUs idle: 128-row tiles then (4096 x 2048 int8 per channel:
     // 128 tiles 20.1 us, 256 tiles of 128 rows 17.0; at 256 tiles -- 4096 x 4096, 2048 x 8192 -- the taller tiles win: 27.3 / 24.9 against 30 / 28.0)

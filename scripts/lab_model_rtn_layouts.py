@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Lab: the model-scale RTN call (Llama-2-7B's 224 weights) in the output layouts; OQ_RTN_* knobs apply (speed only)."""
+"""Lab: the model-scale RTN call (Llama-2-7B's 224 weights) in the output layouts."""
 import os
 import sys
 

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Group RTN on several shapes under ONE setting of the OQ_RTN_* knobs (they are read once per process): time per launch
-through the C ABI (HIP events on the launch stream, inputs rotating over > 256 MiB), fraction of the 8 TB/s roofline in
-algorithmic bytes, digest of the outputs (settings must agree on it).
+"""Group RTN on several shapes: time per launch through the C ABI (HIP events on the launch stream, inputs rotating over
+> 256 MiB), fraction of the 8 TB/s roofline in algorithmic bytes, digest of the outputs (builds compared with --lib must
+agree on it).
 
-    OQ_RTN_XG=2 python scripts/lab_rtn_shapes.py --shapes 4096x4096,11008x4096 --layout nbits
+    python scripts/lab_rtn_shapes.py --shapes 4096x4096,11008x4096 --layout nbits [--lib build/lab/x.so]
 """
 import argparse
 import ctypes as C
@@ -42,7 +42,6 @@ def main():
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     layout = {"nbits": L.OQ_LAYOUT_NBITS, "kn": L.OQ_LAYOUT_KN, "kn_packed4": L.OQ_LAYOUT_KN_PACKED4}[args.layout]
     bits = 4 if "4" in args.qtype else 8
-    knobs = {k: v for k, v in os.environ.items() if k.startswith("OQ_RTN_")}
     for shp in args.shapes.split(","):
         k, n = (int(v) for v in shp.split("x"))
         rot = max(3, min(12, (900 << 20) // (k * n * 4)))
@@ -85,7 +84,7 @@ def main():
             torch.cuda.synchronize()
             times.append(round(e0.elapsed_time(e1) * 1e3 / args.reps, 2))
         alg = k * n * 4 + k * n * bits // 8 + groups * 5
-        print(json.dumps(dict(shape=shp, layout=args.layout, knobs=knobs, us=times, frac=round(alg / min(times) / 1e6 / 8.0, 4), digest=dig)), flush=True)
+        print(json.dumps(dict(shape=shp, layout=args.layout, us=times, frac=round(alg / min(times) / 1e6 / 8.0, 4), digest=dig)), flush=True)
         del ws, outs, wsbuf
         torch.cuda.empty_cache()
 

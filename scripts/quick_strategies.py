@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-tensor / per-channel / tall-group RTN on the Llama shapes: time per call (HIP events on the launch stream, rotating
-inputs so that reads come from HBM), fraction of the 8 TB/s roofline in algorithmic bytes, digest of the outputs.
-OQ_RTN_RESIDENT=0 selects the three-launch path that reads W twice (rounds 1-3); the digests of the two must agree.
+inputs so that reads come from HBM), fraction of the 8 TB/s roofline in algorithmic bytes, digest of the outputs.  `--lib` runs another build of the library (the previous commit's, say) for a same-box
+comparison; the digests of the two must agree.
 
     python scripts/quick_strategies.py [--reps 200] [--json out.json]
 """
@@ -33,7 +33,7 @@ def main():
     ap.add_argument("--only", default=None, help="one strategy only: channel | tensor | group")
     args = ap.parse_args()
     torch.cuda.set_device(0)
-    out = {"resident": os.environ.get("OQ_RTN_RESIDENT", "1"), "rows": []}
+    out = {"rows": []}
     for shp in args.shapes.split(","):
         k, n = (int(v) for v in shp.split("x"))
         rot = max(2, min(6, (800 << 20) // (k * n * 4)))

@@ -169,15 +169,18 @@ def test_c_program_quantizes_on_the_gpu(tmp_path):
 
 
 def test_shipped_library_has_no_attribution_switches():
-    """The store-dropping / wrong-layout variants of the RTN kernel (OQ_RTN_NT bits 3-6) exist only behind
-    -DOQ_RTN_ATTRIBUTION; the build used by `__graft_entry__.build()` and the tests never defines it."""
+    """The shipped library has no experiment switches at all: its sources read no environment variable (the only `getenv`
+    calls sit behind `#ifdef OQ_SYRK_LAB`, which no shipped flag defines), the store-dropping RTN variants and the `nt`
+    argument that selected them are gone, and the build used by `__graft_entry__.build()` and the tests defines no lab macro."""
     from onnx_quantize_amd import _build
-    assert not any("OQ_RTN_ATTRIBUTION" in f for f in _build.CXXFLAGS)
-    src = open(os.path.join(_build.SRC, "rtn.hip")).read()
-    assert "#ifdef OQ_RTN_ATTRIBUTION" in src and "constexpr int kNtMask = 3;" in src
-    # every use of the upper bits goes through the macro that the shipped build defines as `false`
-    import re
-    assert not re.search(r"a\.nt\s*&\s*(8|16|32|64)\b", src)
+    for name in sorted(os.listdir(_build.SRC)):
+        text = open(os.path.join(_build.SRC, name)).read()
+        shipped = re.sub(r"^#ifdef OQ_SYRK_LAB\b.*?^#endif", "", text, flags=re.S | re.M)
+        assert "getenv" not in shipped, name
+        assert "OQ_RTN_ATTRIBUTION" not in text and "OQ_ATTR(" not in text, name
+        assert not re.search(r"\ba\.nt\b", text), name       # the field itself (`a.ntiles` of the ticketed kernels is another thing)
+    for flag in _build.CXXFLAGS + [f for fl in _build.PER_FILE_FLAGS.values() for f in fl]:
+        assert not re.match(r"-D\s*\w*_LAB\b", flag) and "OQ_RTN_ATTRIBUTION" not in flag, flag
 
 
 @pytest.mark.gpu

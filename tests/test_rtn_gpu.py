@@ -238,6 +238,31 @@ def test_nbits_layout_signed_symmetric_clipped(ops, qtype, g, sym, rr, clip):
     np.testing.assert_array_equal(z.cpu().numpy().reshape(-1), ez.reshape(-1))
 
 
+ROUTE_EDGES = (
+    # wave kernel: K = 3 g -- a last band shorter than its four row tiles --, N = 132 -- a ragged last strip with N % 4 == 0
+    [(3 * g, 132, g, qtype, "nbits") for g in (32, 64, 128) for qtype in ("uint4", "int4", "uint8")]
+    + [(128, 4, 128, "uint4", "nbits"),                                      # wave kernel: one group, one wave, a grid of one block
+       (128 * 9, 4096, 128, "int8", "kn"),                                   # fused kernel, 16 column tiles: the chunked order, 9 row tiles against bands of 8
+       (32, 260, 16, "uint4", "nbits"), (32, 260, 16, "int8", "nbits"),      # fused blob, 2 k-groups per block: chunks stored from registers
+       (128, 260, 16, "uint4", "nbits"), (128, 260, 16, "int8", "nbits")])   # fused blob, 8 k-groups per block: chunks assembled in LDS
+
+
+@pytest.mark.parametrize("k,n,g,qtype,layout", ROUTE_EDGES, ids=["-".join(str(v) for v in c) for c in ROUTE_EDGES])
+def test_group_routes_at_their_band_and_strip_edges_vs_oracle(ops, k, n, g, qtype, layout):
+    """Every rule the group launchers take (wave kernel; fused kernel in the chunked order of 16 column tiles; fused blob
+    with and without the LDS assembly of its chunks) at the shapes where its id map or its stores have an edge: bit-exact."""
+    w = np.random.default_rng(k * 31 + n + g).standard_normal((k, n), dtype=np.float32)
+    eq, es, ez = O.rtn_quantize(w, qtype, "group", g)
+    q, s, z = ops.rtn_quantize(dev(w), qtype, "group", g, layout=layout)
+    if layout == "nbits":
+        bits = O.BITWIDTH[qtype]
+        u = (eq.astype(np.int16) & (0xF if bits == 4 else 0xFF)).astype(np.uint8)   # two's-complement nibbles / bytes
+        eq = O.matmul_nbits_layout(u, es, ez, g, bits)[0]
+    np.testing.assert_array_equal(q.cpu().numpy(), eq)
+    assert s.cpu().numpy().tobytes() == es.tobytes()
+    np.testing.assert_array_equal(z.cpu().numpy().reshape(-1), ez.reshape(-1))
+
+
 def test_roundtrip_property_full_size(ops):
     """Size-independent property at BASELINE size: |dequant(q) - w| <= scale/2 (+1 ulp slack)
     wherever the value was not clipped, and every group hits both ends of the integer range."""
