@@ -74,6 +74,32 @@ size_t oq_hessian_half_workspace_bytes(int64_t T, int64_t K);
 int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype /* oq_wtype */, int64_t T, int64_t K, int64_t ldx, int64_t n_seen,
                                   int64_t n_add, float* H, void* workspace, size_t workspace_bytes, void* stream);
 
+/* G1 for a LIST of 2-byte inputs of ONE element type in one launch chain: what oq_hessian_accumulate_many_f32 (oq_hip.h) is
+ *     for fp32 inputs -- the tensors one calibration batch taps, each far too small to fill the device alone.  Every item is one
+ *     oq_hessian_accumulate_h16 call; the chain is three launches for the whole table (plan, re-layout, product) whose blocks
+ *     never wait for one another.
+ *
+ *   items      `count` oq_hessian_item (oq_hip.h, unchanged) in host memory and the same bytes in device memory: the host copy
+ *              is checked and sizes the launches, the kernels read the device copy.  `X` points at 2-byte elements of type
+ *              `xtype` (2-byte aligned, ldx >= K in elements); every other field as in oq_hip.h.  Items whose rows are only
+ *              2-byte aligned (odd ldx, an unaligned base) take narrower loads, item by item, and give the same result.
+ *              1 <= count <= 65535.
+ *   H          of every item: fp32 [K, K], contiguous, comes out full and exactly symmetric; read only when n_seen > 0.
+ *   result     every item runs ONE T-slice: an item of up to 992 rows (where oq_hessian_accumulate_h16 runs one slice too)
+ *              gets the bits of that call.  A longer item is summed in one fp32 chain where the per-tensor call slices T
+ *              from 993 rows: the same tolerance against float64, not the same bits.
+ *   checks     the bounds of oq_hessian_accumulate_h16 for every item (OQ_ERR_INVALID_ARGUMENT / OQ_ERR_UNSUPPORTED, the
+ *              message names the item), an unknown xtype OQ_ERR_INVALID_ARGUMENT, a missing or short workspace
+ *              OQ_ERR_WORKSPACE -- all on the host copy before anything is launched: on any refusal no H is touched.
+ *   workspace  oq_hessian_many_half_workspace_bytes(items_host, count) =
+ *                  count * 128 (the device table) rounded up to 256
+ *                + the packed operand of every item: T padded to 32 x K padded to 256 x 2 bytes
+ *                + 512.
+ *              The query returns 0 for a table outside the bounds (null, count, T, K of an item). */
+size_t oq_hessian_many_half_workspace_bytes(const oq_hessian_item* items_host, int64_t count);
+int32_t oq_hessian_accumulate_many_h16(const oq_hessian_item* items_host, const oq_hessian_item* items_device, int64_t count,
+                                       int32_t xtype /* oq_wtype */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * C1  core/_calibration/minmax.py:40-64  MinMaxCalibrator.collect on x.astype(np.float32), without the fp32 copy: replaces
  *     the cast followed by oq_minmax_collect_f32.  Min and max of fp16 / bf16 values are exact, so `state` comes out as

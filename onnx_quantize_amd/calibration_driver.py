@@ -113,9 +113,9 @@ class ActivationStream:
         self._held_bytes = 0
         self._search_inputs: dict = {}
         self.hessians: dict[str, HessianAccumulator] = {}
-        # 0 (default): the Hessian updates of a batch in one grouped launch chain (per-tensor calls on 4 side streams for fp16 /
-        # bf16 activations and when a Hessian method the grouped chain does not run is selected); n > 0: per-tensor calls on n
-        # side streams
+        # 0 (default): the Hessian updates of a batch in one grouped launch chain per element type (fp32 activations take
+        # per-tensor calls on 4 side streams when a Hessian method the grouped fp32 chain does not run is selected); n > 0:
+        # per-tensor calls on n side streams for everything
         self.hessian_streams = max(0, int(hessian_streams))
         self._side = None
         self.absmax: dict = {}
@@ -147,31 +147,35 @@ class ActivationStream:
             else:
                 self.calibrator.collect_many(activations)
         wanted = sorted(self.hessian_names & activations.keys())
-        # fp16 / bf16 activations go to the Hessian as they are (ops.hessian_accumulate reads the 2-byte tensor: one exact
-        # matrix-core product, no fp32 copy); there is no grouped half chain, so they take the per-tensor side-stream route
+        # fp16 / bf16 activations go to the Hessian as they are (one exact matrix-core product, no fp32 copy) and are grouped like
+        # the fp32 ones: ops.hessian_accumulate_many runs one launch chain per element type (oq_hessian_accumulate_many_h16)
         half = [name for name in wanted if activations[name].dtype in (torch.float16, torch.bfloat16)]
         full = [name for name in wanted if name not in half]
-        streams = self.hessian_streams
-        if full and streams == 0 and ops.hessian_method() not in ("auto", "f16x3"):
-            streams = 4      # the grouped chain runs the fp16-piece kernels only: other methods would become serial per-tensor
-                             # calls on one stream, so they take the side-stream route below
-        grouped, per_tensor = (full, half) if streams == 0 else ([], wanted)
+        if self.hessian_streams > 0:
+            grouped, per_tensor, streams = [], wanted, self.hessian_streams
+        elif full and ops.hessian_method() not in ("auto", "f16x3"):
+            # the grouped fp32 chain runs the fp16-piece kernels only: other methods would become serial per-tensor calls on one
+            # stream, so the fp32 items take the side-stream route below; the method does not concern half items
+            grouped, per_tensor, streams = half, full, 4
+        else:
+            grouped, per_tensor, streams = wanted, [], 0
         if grouped:
-            # one launch chain for all tapped inputs of the batch (ops.hessian_accumulate_many): a batch of a small model is
-            # 72 tensors of 6 to 36 product tiles each, launch-bound and never filling the chip one at a time
+            # one launch chain per element type for all tapped inputs of the batch (ops.hessian_accumulate_many): a batch of a
+            # small model is 72 tensors of 6 to 36 product tiles each, launch-bound and never filling the chip one at a time
             xs = []
             for name in grouped:
                 x = activations[name]
-                x32 = x if x.dtype == torch.float32 else x.to(torch.float32)
+                if name not in half and x.dtype != torch.float32:
+                    x = x.to(torch.float32)
                 if name not in self.hessians:
-                    self.hessians[name] = HessianAccumulator(x32.shape[-1], x32.device)
-                xs.append(x32)
+                    self.hessians[name] = HessianAccumulator(x.shape[-1], x.device)
+                xs.append(x)
             accs = [self.hessians[name] for name in grouped]
             for acc, n in zip(accs, ops.hessian_accumulate_many(xs, [a.h for a in accs], [a.n for a in accs])):
                 acc.n = n
         if per_tensor:
-            # per-tensor calls spread over a few side streams (fork / join by events): the route for half-precision activations
-            # and for the Hessian methods the grouped call does not run (hessian_streams > 0 selects it for everything)
+            # per-tensor calls spread over a few side streams (fork / join by events): the route for fp32 activations under a Hessian
+            # method the grouped call does not run (hessian_streams > 0 selects it for everything, half activations included)
             cur = torch.cuda.current_stream()
             if self._side is None:
                 self._side = [torch.cuda.Stream(device=activations[per_tensor[0]].device) for _ in range(streams or 4)]

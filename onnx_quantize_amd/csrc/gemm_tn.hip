@@ -436,6 +436,21 @@ int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype, int64_t T, int64
     return launch_syrk_h16(X, xtype == OQ_W_BF16, T, K, ldx, alpha, beta, H, workspace, workspace_bytes, as_stream(stream));
 }
 
+// G1 for the fp16 / bf16 tensors of one calibration batch in one launch chain (syrk_bf16x3.hip, section 4b)
+size_t oq_hessian_many_half_workspace_bytes(const oq_hessian_item* items_host, int64_t count) {
+    const size_t need = syrk_h16_many_workspace_bytes(reinterpret_cast<const int64_t*>(items_host), count);
+    if (need == 0) set_error("oq_hessian_many_half_workspace_bytes: bad table (count=%lld)", (long long)count);
+    return need;
+}
+
+int32_t oq_hessian_accumulate_many_h16(const oq_hessian_item* items_host, const oq_hessian_item* items_device, int64_t count, int32_t xtype,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(sizeof(oq_hessian_item) == 64, "eight 8-byte fields");
+    OQ_REQUIRE(xtype == OQ_W_F16 || xtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_many_h16: unknown xtype %d", xtype);
+    return launch_syrk_h16_many(reinterpret_cast<const int64_t*>(items_host), reinterpret_cast<const int64_t*>(items_device), count, xtype == OQ_W_BF16,
+                                workspace, workspace_bytes, as_stream(stream));
+}
+
 // G1 for the tensors of one calibration batch (calibrate.py:292-305 hands `_accumulate_hessian` one input per node): one
 // launch chain for all of them, fp16-piece method.
 size_t oq_hessian_many_workspace_bytes(const oq_hessian_item* items_host, int64_t count) {

@@ -96,6 +96,12 @@ size_t syrk_h16_pieces_bytes(int64_t T, int64_t K);
 int32_t launch_syrk_h16(const void* X, bool bf16, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, void* workspace,
                         size_t workspace_bytes, hipStream_t s);
 
+// Many half-precision Hessian updates in one launch chain (syrk_bf16x3.hip, section 4b): the same items with X at 2-byte elements of
+// one type.  The workspace query returns 0 for a table outside the bounds.
+size_t syrk_h16_many_workspace_bytes(const int64_t* items_host, int64_t count);
+int32_t launch_syrk_h16_many(const int64_t* items_host, const int64_t* items_device, int64_t count, bool bf16, void* workspace, size_t workspace_bytes,
+                             hipStream_t s);
+
 // Many Hessian updates in one launch chain (syrk_bf16x3.hip, section 2c).  items: int64 {X, H, T, K, ldx, n_seen, n_add, 0} each.
 size_t syrk_f16x3_many_workspace_bytes(const int64_t* items_host, int64_t count);
 int32_t launch_syrk_f16x3_many(const int64_t* items_host, const int64_t* items_device, int64_t count, void* workspace, size_t workspace_bytes,

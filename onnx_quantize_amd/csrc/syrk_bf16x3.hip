@@ -848,8 +848,8 @@ __global__ void syrk_factor_plan_kernel(const float* __restrict__ Lt, float* __r
 }
 
 // the item whose block range holds `id`: FIRST(items[m]) <= id < FIRST(items[m + 1])
-template <typename First>
-__device__ __forceinline__ int item_of_block(const SyrkItem* __restrict__ items, const int count, const int64_t id, First first) {
+template <typename Item, typename First>
+__device__ __forceinline__ int item_of_block(const Item* __restrict__ items, const int count, const int64_t id, First first) {
     int lo = 0, hi = count - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -1543,15 +1543,16 @@ int64_t gemm_f16x3_tiles(int64_t M, int64_t N) { return (padded_k(M) / kST) * (p
 //                     2-byte loads otherwise and for the last column of an odd K -- the same bits either way.
 //   syrk_h16_kernel   the stage loop of the first pieces alone (f16_hi_mainloop: 32-row stages, ring of four, LDS-DMA staging)
 //                     on the compact plane, the tile epilogue and the T-slices of section 2b.
+// Both bodies are shared with the grouped kernels of section 4b.  (bx, by): the block's four chunks and its 512 columns.
 template <bool VEC>
-__global__ __launch_bounds__(256) void pack_h16_kernel(const uint16_t* __restrict__ X, const int64_t T, const int64_t K, const int64_t ldx,
-                                                       const int64_t Kp, const int64_t nchunks, u32x4* __restrict__ P) {
-    const int64_t col = (static_cast<int64_t>(blockIdx.y) * 256 + threadIdx.x) * 2;
+__device__ __forceinline__ void pack_h16_body(const uint16_t* __restrict__ X, const int64_t T, const int64_t K, const int64_t ldx, const int64_t Kp,
+                                              const int64_t nchunks, u32x4* __restrict__ P, const int64_t bx, const int64_t by) {
+    const int64_t col = (by * 256 + threadIdx.x) * 2;
     if (col >= Kp) return;
     const bool ok0 = col < K, ok1 = col + 1 < K;
-    const int64_t c_end = (static_cast<int64_t>(blockIdx.x) + 1) * 4 < nchunks ? (static_cast<int64_t>(blockIdx.x) + 1) * 4 : nchunks;
+    const int64_t c_end = (bx + 1) * 4 < nchunks ? (bx + 1) * 4 : nchunks;
 #pragma unroll 1
-    for (int64_t c = static_cast<int64_t>(blockIdx.x) * 4; c < c_end; ++c) {
+    for (int64_t c = bx * 4; c < c_end; ++c) {
         uint32_t v[8];      // row r of the chunk: column `col` in the low half, `col + 1` in the high half
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
@@ -1576,15 +1577,21 @@ __global__ __launch_bounds__(256) void pack_h16_kernel(const uint16_t* __restric
     }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(256) void pack_h16_kernel(const uint16_t* __restrict__ X, const int64_t T, const int64_t K, const int64_t ldx,
+                                                       const int64_t Kp, const int64_t nchunks, u32x4* __restrict__ P) {
+    pack_h16_body<VEC>(X, T, K, ldx, Kp, nchunks, P, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(blockIdx.y));
+}
+
+// `tile`: the block's (XCD-remapped) index among the upper-triangle tiles of this matrix; `slice`: its T-slice
 template <typename FRAG>
-__global__ __launch_bounds__(kSThreads) void syrk_h16_kernel(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all,
-                                                             const float alpha, const float beta, float* __restrict__ C, float* __restrict__ slab,
-                                                             const int64_t stages_per_slice, const int ntiles) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+__device__ __forceinline__ void syrk_h16_body(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all, const float alpha,
+                                              const float beta, float* __restrict__ C, float* __restrict__ slab, const int64_t stages_per_slice,
+                                              const int ntiles, const int tile, const int64_t slice, unsigned char* lds) {
     int tile_m, tile_n;
-    upper_tile_of(static_cast<int>(xcd_remap(blockIdx.x, gridDim.x)), ntiles, tile_m, tile_n);
+    upper_tile_of(tile, ntiles, tile_m, tile_n);
     const int64_t m0 = static_cast<int64_t>(tile_m) * kST, n0 = static_cast<int64_t>(tile_n) * kST;
-    const int64_t slice = blockIdx.y, s_begin = slice * stages_per_slice;
+    const int64_t s_begin = slice * stages_per_slice;
     const int64_t s_end = s_begin + stages_per_slice < nstages_all ? s_begin + stages_per_slice : nstages_all;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const char* gsrc[4];
@@ -1599,6 +1606,15 @@ __global__ __launch_bounds__(kSThreads) void syrk_h16_kernel(const u32x4* __rest
     f32x4v acc[4][8];
     f16_hi_mainloop<FRAG>(gsrc, stage_bytes, s_end - s_begin, lds, acc);
     syrk_tile_store(acc, lds, tile_m, tile_n, K, alpha, beta, C, slab, slice, K, true);
+}
+
+template <typename FRAG>
+__global__ __launch_bounds__(kSThreads) void syrk_h16_kernel(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all,
+                                                             const float alpha, const float beta, float* __restrict__ C, float* __restrict__ slab,
+                                                             const int64_t stages_per_slice, const int ntiles) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    syrk_h16_body<FRAG>(P, K, Kp, nstages_all, alpha, beta, C, slab, stages_per_slice, ntiles, static_cast<int>(xcd_remap(blockIdx.x, gridDim.x)),
+                        static_cast<int64_t>(blockIdx.y), lds);
 }
 
 constexpr int kH16StageRows = 32;      // four 8-row chunks: one k-step of the 16x16x32 instructions
@@ -1647,6 +1663,135 @@ int32_t launch_syrk_h16(const void* X, bool bf16, int64_t T, int64_t K, int64_t 
     const size_t slab_bytes = workspace_bytes - plane - 256;
     return bf16 ? launch_syrk_h16_typed<bf16x8>(P, K, Kp, nstages, alpha, beta, C, slab, slab_bytes, s)
                 : launch_syrk_h16_typed<f16x8>(P, K, Kp, nstages, alpha, beta, C, slab, slab_bytes, s);
+}
+
+// ---- 4b. Many half-precision Hessian updates in one launch chain (oq_hessian_accumulate_many_h16): section 2c for the tensors
+// of a calibration batch that ARE fp16 / bf16.  Three launches for the whole table -- plan, pack, product -- and every block
+// independent of every other.  Each item runs ONE T-slice and writes H directly (alpha / beta in the epilogue, both triangles),
+// through the bodies of section 4: an item of up to 992 rows (where oq_hessian_accumulate_h16 takes one slice too) gets the
+// bits of that call.  Half the operand bytes of 2c, no absmax / scale passes, one matrix-core product instead of three.
+struct H16Item {
+    const uint16_t* X;
+    float* C;
+    u32x4* P;                // the item's packed plane: [nchunks][Kp] x 16 B
+    int64_t T, K, ldx, Kp, nchunks, nstages;
+    int64_t pack0;           // first block of this item in the pack launch; its pack grid is nstages x ceil(Kp / 512)
+    int64_t tile0;           // first block of this item in the product launch
+    float alpha, beta;
+    int32_t tn;
+    int32_t vec;             // 1: base 4-byte aligned and ldx even -- dword loads in the pack (pack_h16_body<true>)
+    int64_t pad_[3];
+};
+static_assert(sizeof(H16Item) == 128, "the workspace formula of oq_hip_half.h: 128 bytes of table per item");
+
+// public items (oq_hip.h: int64 {X, H, T, K, ldx, n_seen, n_add, 0}, X at 2-byte elements) -> H16Item table; one thread
+__global__ void syrk_h16_many_plan_kernel(const int64_t* __restrict__ pub, const int count, unsigned char* __restrict__ planes_base,
+                                          H16Item* __restrict__ items) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int64_t pack0 = 0, tile0 = 0;
+    size_t off = 0;
+    for (int m = 0; m < count; ++m) {
+        const int64_t* it = pub + static_cast<int64_t>(m) * 8;
+        H16Item o;
+        o.X = reinterpret_cast<const uint16_t*>(it[0]);
+        o.C = reinterpret_cast<float*>(it[1]);
+        o.T = it[2]; o.K = it[3]; o.ldx = it[4];
+        const int64_t n_seen = it[5], n_total = it[5] + it[6];
+        o.Kp = (o.K + kST - 1) / kST * kST;
+        o.nstages = (o.T + kH16StageRows - 1) / kH16StageRows;
+        o.nchunks = o.nstages * 4;
+        o.P = reinterpret_cast<u32x4*>(planes_base + off);
+        off += static_cast<size_t>(o.nchunks) * static_cast<size_t>(o.Kp) * 16;
+        o.pack0 = pack0;
+        pack0 += o.nstages * ((o.Kp + 511) / 512);
+        o.tn = static_cast<int32_t>(o.Kp / kST);
+        o.tile0 = tile0;
+        tile0 += static_cast<int64_t>(o.tn) * (o.tn + 1) / 2;
+        o.alpha = static_cast<float>(2.0 / static_cast<double>(n_total));                                               // as oq_hessian_accumulate_h16
+        o.beta = n_seen == 0 ? 0.0f : static_cast<float>(static_cast<double>(n_seen) / static_cast<double>(n_total));   // gptq.py:254
+        o.vec = ((static_cast<uint64_t>(it[0]) & 3u) == 0 && (o.ldx & 1) == 0) ? 1 : 0;
+        o.pad_[0] = o.pad_[1] = o.pad_[2] = 0;
+        items[m] = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void pack_h16_many_kernel(const H16Item* __restrict__ items, const int count) {
+    const int64_t id = blockIdx.x;
+    const int m = item_of_block(items, count, id, [](const H16Item& i) { return i.pack0; });
+    const H16Item& it = items[m];
+    const int64_t local = id - it.pack0, nbx = it.nstages;       // four chunks per block: ceil(nchunks / 4) = nstages
+    // the host's choice of pack_h16_kernel<VEC>, per item: uniform over the block
+    if (it.vec) pack_h16_body<true>(it.X, it.T, it.K, it.ldx, it.Kp, it.nchunks, it.P, local % nbx, local / nbx);
+    else pack_h16_body<false>(it.X, it.T, it.K, it.ldx, it.Kp, it.nchunks, it.P, local % nbx, local / nbx);
+}
+
+template <typename FRAG>
+__global__ __launch_bounds__(kSThreads) void syrk_h16_many_kernel(const H16Item* __restrict__ items, const int count) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int64_t id = xcd_remap(blockIdx.x, gridDim.x);
+    const int m = item_of_block(items, count, id, [](const H16Item& i) { return i.tile0; });
+    const H16Item& it = items[m];
+    syrk_h16_body<FRAG>(it.P, it.K, it.Kp, it.nstages, it.alpha, it.beta, it.C, nullptr, it.nstages, it.tn, static_cast<int>(id - it.tile0), 0, lds);
+}
+
+static size_t syrk_h16_many_table_bytes(int64_t count) { return (static_cast<size_t>(count) * sizeof(H16Item) + 255) / 256 * 256; }
+
+size_t syrk_h16_many_workspace_bytes(const int64_t* items_host, int64_t count) {
+    if (items_host == nullptr || count <= 0 || count > 65535) return 0;
+    size_t total = syrk_h16_many_table_bytes(count) + 512;
+    for (int64_t m = 0; m < count; ++m) {
+        const int64_t T = items_host[m * 8 + 2], K = items_host[m * 8 + 3];
+        if (!matrix_ok(T, K, K) || K > kMaxHessianWidth) return 0;
+        total += syrk_h16_plane_bytes(T, K);
+    }
+    return total;
+}
+
+template <typename FRAG>
+static int32_t launch_syrk_h16_many_product(const H16Item* table, int n, int64_t tiles, hipStream_t s) {
+    const int lds_bytes = kHiRing * kHiStage;
+    OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_h16_many_kernel<FRAG>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess,
+               OQ_ERR_LAUNCH, "hessian_many_h16: cannot reserve %d bytes of LDS", lds_bytes);
+    hipLaunchKernelGGL(syrk_h16_many_kernel<FRAG>, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), lds_bytes, s, table, n);
+    return check_launch("syrk_h16_many_kernel");
+}
+
+int32_t launch_syrk_h16_many(const int64_t* items_host, const int64_t* items_device, int64_t count, bool bf16, void* workspace, size_t workspace_bytes,
+                             hipStream_t s) {
+    // every check on the host copy, before any arithmetic on an extent and before any HIP call
+    OQ_REQUIRE(count > 0 && count <= 65535, OQ_ERR_INVALID_ARGUMENT, "hessian_many_h16: count=%lld, 1 to 65535 items expected", (long long)count);
+    OQ_REQUIRE(items_host != nullptr && items_device != nullptr, OQ_ERR_INVALID_ARGUMENT, "hessian_many_h16: null item table (host and device copies are needed)");
+    int64_t pack_blocks = 0, tiles = 0;
+    for (int64_t m = 0; m < count; ++m) {
+        const int64_t* it = items_host + m * 8;
+        const int64_t T = it[2], K = it[3], ldx = it[4], n_seen = it[5], n_add = it[6];
+        OQ_REQUIRE(it[0] != 0 && it[1] != 0, OQ_ERR_INVALID_ARGUMENT, "hessian_many_h16: item %lld: null X / H", (long long)m);
+        OQ_REQUIRE((static_cast<uint64_t>(it[0]) & 1u) == 0 && (static_cast<uint64_t>(it[1]) & 3u) == 0, OQ_ERR_INVALID_ARGUMENT,
+                   "hessian_many_h16: item %lld: X must be 2-byte aligned and H 4-byte aligned", (long long)m);
+        OQ_REQUIRE(T > 0 && K > 0 && ldx >= K, OQ_ERR_INVALID_ARGUMENT, "hessian_many_h16: item %lld: bad shape T=%lld K=%lld ldx=%lld", (long long)m,
+                   (long long)T, (long long)K, (long long)ldx);
+        OQ_REQUIRE(matrix_ok(T, K, ldx) && K <= kMaxHessianWidth, OQ_ERR_UNSUPPORTED,
+                   "hessian_many_h16: item %lld: operand too large (T=%lld K=%lld ldx=%lld)", (long long)m, (long long)T, (long long)K, (long long)ldx);
+        OQ_REQUIRE(n_seen >= 0 && n_add > 0 && n_seen <= kMaxSamples && n_add <= kMaxSamples, OQ_ERR_INVALID_ARGUMENT,
+                   "hessian_many_h16: item %lld: bad sample counts %lld + %lld", (long long)m, (long long)n_seen, (long long)n_add);
+        const int64_t Kp = padded_k(K), tn = Kp / kST;
+        pack_blocks += stages_of(T, kH16StageRows) * ceil_div(Kp, 512);      // < 2^26 * 2^8 per item
+        tiles += tn * (tn + 1) / 2;
+    }
+    OQ_REQUIRE(pack_blocks < (1ll << 31) && tiles < (1ll << 31), OQ_ERR_UNSUPPORTED, "hessian_many_h16: too many blocks for one launch");
+    const size_t need = syrk_h16_many_workspace_bytes(items_host, count);
+    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "hessian_many_h16: workspace of %zu bytes needed, %zu given", need,
+               workspace ? workspace_bytes : static_cast<size_t>(0));
+    unsigned char* base = static_cast<unsigned char*>(workspace);
+    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
+    H16Item* table = reinterpret_cast<H16Item*>(base);
+    unsigned char* planes = base + syrk_h16_many_table_bytes(count);
+    const int n = static_cast<int>(count);
+    hipLaunchKernelGGL(syrk_h16_many_plan_kernel, dim3(1), dim3(64), 0, s, items_device, n, planes, table);
+    hipLaunchKernelGGL(pack_h16_many_kernel, dim3(static_cast<uint32_t>(pack_blocks)), dim3(256), 0, s, table, n);
+    const int32_t st = check_launch("pack_h16_many_kernel");
+    if (st != OQ_OK) return st;
+    return bf16 ? launch_syrk_h16_many_product<bf16x8>(table, n, tiles, s) : launch_syrk_h16_many_product<f16x8>(table, n, tiles, s);
 }
 
 }  // namespace oq

@@ -1063,33 +1063,41 @@ _MANY_MIN_K, _MANY_MIN_ROWS, _MANY_MAX_ROWS = 512, 512, 32768
 
 
 def hessian_accumulate_many(xs, hs, n_seen) -> list[int]:
-    """gptq.py:246-260 for a list of (input, Hessian) pairs -- the tensors one calibration batch taps -- in ONE launch chain
-    (`oq_hessian_accumulate_many_f32`).  ``xs[i]`` [n_add, ..., K_i] fp32, ``hs[i]`` [K_i, K_i] updated in place, ``n_seen[i]``
-    the samples already in it; returns the new sample counts.  fp16 / bf16 items, items narrower than 512 columns or shorter than 512 rows
-    (their padding to 256-wide tiles would cost more than the launches save), items longer than 32 768 rows (the grouped
-    product sums an item's rows in ONE fp32 chain; the per-tensor call slices long inputs, which also keeps the rounding error
-    at 1e-6 of max |H|), and every item when another Hessian method than the fp16 pieces is selected, go through
-    `hessian_accumulate` one by one."""
+    """gptq.py:246-260 for a list of (input, Hessian) pairs -- the tensors one calibration batch taps -- in one launch chain per
+    element type: `oq_hessian_accumulate_many_f32` for the fp32 items, `oq_hessian_accumulate_many_h16` for the fp16 items and
+    again for the bf16 items, which are read as they are (no fp32 copy).  ``xs[i]`` [n_add, ..., K_i] fp32, fp16 or bf16,
+    ``hs[i]`` [K_i, K_i] fp32 updated in place, ``n_seen[i]`` the samples already in it; returns the new sample counts.
+
+    Items narrower than 512 columns or shorter than 512 rows (their padding to 256-wide tiles would cost more than the launches
+    save) and items longer than 32 768 rows (a grouped product sums an item's rows in ONE fp32 chain; the per-tensor call slices
+    long inputs, which also keeps the rounding error at 1e-6 of max |H|) go through `hessian_accumulate` one by one, whatever
+    their type.  So does every fp32 item when another Hessian method than the fp16 pieces is selected; the method is irrelevant
+    for half items (`hessian_accumulate`), which stay grouped.  A half type with a single eligible item takes the per-tensor call
+    too: a chain of one saves no launch.  Grouped half items of up to 992 rows get the bits of `hessian_accumulate`, longer ones
+    the same tolerance."""
     xs, hs, n_seen = list(xs), list(hs), [int(n) for n in n_seen]
     if not (len(xs) == len(hs) == len(n_seen)):
         raise ValueError("hessian_accumulate_many: xs, hs and n_seen must have one entry per item")
     out = [0] * len(xs)
     rows, keep = [], []
+    half: dict = {}                   # element type -> [(index, table row, the tensor the row points into)]
     grouped = hessian_method() in ("auto", "f16x3")
     for i, (x, h) in enumerate(zip(xs, hs)):
-        if isinstance(x, torch.Tensor) and x.dtype in _HALF_WTYPE:       # no grouped half chain: the half kernel, item by item
-            out[i] = hessian_accumulate(x, h, n_seen[i])
-            continue
-        _require_device(x, "x", torch.float32)
+        is_half = isinstance(x, torch.Tensor) and x.dtype in _HALF_WTYPE
+        _require_device(x, "x", None if is_half else torch.float32)
         _require_device(h, "H", torch.float32)
         x2, ldx = _row_major(x.reshape(-1, x.shape[-1]))
         t, k = x2.shape
         if h.shape != (k, k) or not h.is_contiguous():
             raise ValueError(f"H[{i}] must be a contiguous [{k}, {k}] tensor")
-        if not grouped or k < _MANY_MIN_K or t < _MANY_MIN_ROWS or t > _MANY_MAX_ROWS:
+        if not (grouped or is_half) or k < _MANY_MIN_K or t < _MANY_MIN_ROWS or t > _MANY_MAX_ROWS:
             out[i] = hessian_accumulate(x, h, n_seen[i])
             continue
-        rows.append((x2.data_ptr(), h.data_ptr(), t, k, ldx, n_seen[i], int(x.shape[0]), 0))
+        row = (x2.data_ptr(), h.data_ptr(), t, k, ldx, n_seen[i], int(x.shape[0]), 0)
+        if is_half:
+            half.setdefault(x.dtype, []).append((i, row, x2))
+            continue
+        rows.append(row)
         keep.append(x2)
         out[i] = n_seen[i] + int(x.shape[0])
     if rows:
@@ -1101,6 +1109,21 @@ def hessian_accumulate_many(xs, hs, n_seen) -> list[int]:
         hp = C.c_void_p(host.ctypes.data)
         ws = _workspace(lib.oq_hessian_many_workspace_bytes(hp, len(rows)), keep[0].device)
         L.check(lib.oq_hessian_accumulate_many_f32(hp, _ptr(dev), len(rows), _ptr(ws), ws.numel(), _stream()))
+    for dtype, items in half.items():
+        if len(items) == 1:
+            i = items[0][0]
+            out[i] = hessian_accumulate(xs[i], hs[i], n_seen[i])
+            continue
+        import numpy as np
+
+        lib = L.load()
+        host = np.asarray([row for _, row, _ in items], dtype=np.int64)
+        dev = torch.from_numpy(host).to(items[0][2].device)
+        hp = C.c_void_p(host.ctypes.data)
+        ws = _workspace(lib.oq_hessian_many_half_workspace_bytes(hp, len(items)), items[0][2].device)
+        L.check(lib.oq_hessian_accumulate_many_h16(hp, _ptr(dev), len(items), _HALF_WTYPE[dtype], _ptr(ws), ws.numel(), _stream()))
+        for i, row, _ in items:
+            out[i] = row[5] + row[6]
     return out
 
 
