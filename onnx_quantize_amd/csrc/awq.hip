@@ -517,24 +517,14 @@ struct AwqWs {   // carving of the caller's workspace
 // fp16 pieces (22 bits: rounding G to 11 bits would move every column's loss the same way, nothing averages out), D with
 // its first (its rounding errors are independent per column): two products.
 // Break-even: two products of 2 K^2 N against one of 2 T K N, plus the Gram matrix over ~20 candidates.
-#ifndef OQ_AWQ_GRAM_RATIO
-#define OQ_AWQ_GRAM_RATIO 3   /* measured on 4096^2 (scripts/lab_awq_routes.py): T = 2 K direct 6.8 / 3.3 ms vs Gram 7.1 / 3.8; T = 3 K 9.0 / 4.4 vs 7.3 / 3.9 */
-#endif
-constexpr int64_t kAwqGramRatio = OQ_AWQ_GRAM_RATIO;
+// Measured on 4096^2, scale search / clip search in ms: T = 2 K direct 6.8 / 3.3 vs Gram 7.1 / 3.8; T = 3 K 9.0 / 4.4 vs 7.3 / 3.9.
+constexpr int64_t kAwqGramRatio = 3;
 static bool awq_use_gram(int64_t T, int64_t K) { return T >= kAwqGramRatio * K; }
 static int64_t loss_tiles(int64_t T, int64_t K, int64_t N) { return gemm_f16x3_tiles(awq_use_gram(T, K) ? K : T, N); }
 static int64_t loss_stride(int64_t T, int64_t K, int64_t N) { return (loss_tiles(T, K, N) + 63) / 64 * 64; }
 // all candidates' partial sums -> their losses, one launch
 static int32_t finish_losses(const float* gemm_part, int n_cand, int64_t T, int64_t K, int64_t N, float* losses_out, hipStream_t s);
 
-#ifndef OQ_AWQ_HI_ONLY
-#define OQ_AWQ_HI_ONLY 1   /* lab: 0 = the three-product (22-bit) loss of round 3 */
-#endif
-constexpr bool kAwqHiPiecesOnly = OQ_AWQ_HI_ONLY != 0;
-#ifndef OQ_AWQ_FUSED_PIECES
-#define OQ_AWQ_FUSED_PIECES 1   /* lab: 0 = D in fp32 + the split launch of round 4 */
-#endif
-constexpr bool kAwqFusedPieces = OQ_AWQ_FUSED_PIECES != 0;
 static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 // Smallest group the searches take (the reference's own AWQ tests use 8, test/pre_passes/test_awq.py:68); the parameter
@@ -590,13 +580,13 @@ static int32_t param_index(int32_t strategy, int64_t K, int64_t g, ParamIndex* p
     return OQ_OK;
 }
 
-// the fused route of candidate_loss: direct product (the Gram route reads D itself in its epilogue), first pieces only, and a
-// contraction length that fills its last stage (no zero chunks to write behind the rows)
+// the fused route of candidate_loss: direct product (the Gram route reads D itself in its epilogue) and a contraction length
+// that fills its last stage (no zero chunks to write behind the rows); otherwise D goes through fp32 and a split launch
 static bool group_fused(int32_t strategy, int64_t g, int64_t K, int64_t N, int64_t ldw, const float* W) {      // the fused quantize-residual kernel takes the candidate
     return N % 4 == 0 && ldw % 4 == 0 && (reinterpret_cast<uintptr_t>(W) & 15u) == 0 && strategy == OQ_GROUP && (g == 16 || g == 32 || g == 64 || g == 128) && K % g == 0;
 }
 static bool pieces_route(const AwqWs& w, int64_t K) {
-    return kAwqFusedPieces && kAwqHiPiecesOnly && !w.gram && gemm_f16x3_chunks(K) * 8 == K;
+    return !w.gram && gemm_f16x3_chunks(K) * 8 == K;
 }
 
 // once per search, fused route: row maxima of W, the bounds and the pieces' scales of all candidates (three launches)
@@ -631,7 +621,7 @@ static int32_t candidate_loss(const AwqWs& w, const float* W, int64_t ldw, const
             st = check_launch("awq_group_diff_kernel (pieces)");
             if (st != OQ_OK) return st;
             float* part = w.gemm_part + static_cast<int64_t>(candidate) * loss_stride(T, K, N);
-            return launch_gemm_f16x3(w.pieces_x, w.pieces_d, T, N, K, 1.0f, 0.0f, nullptr, 0, part, s, kAwqHiPiecesOnly);
+            return launch_gemm_f16x3(w.pieces_x, w.pieces_d, T, N, K, 1.0f, 0.0f, nullptr, 0, part, s);
         }
         hipLaunchKernelGGL(awq_group_diff_kernel<false>, dgrid, dim3(512), 0, s, W, K, N, ldw, g, grid, wpg, row_scale, w.D, w.diff_part,
                            static_cast<const float*>(nullptr), static_cast<float*>(nullptr), static_cast<u32x4a*>(nullptr), static_cast<int64_t>(0));
@@ -664,15 +654,15 @@ static int32_t candidate_loss(const AwqWs& w, const float* W, int64_t ldw, const
     st = check_launch("awq_diff_kernel");
     if (st != OQ_OK) return st;
     // the pieces of D with the scale from awq_diff_kernel's partial maxima (instead of a second pass over D)
-    st = make_f16x2_pieces_from_partials(w.D, K, N, N, w.diff_part, nparts, w.pieces_d, s, kAwqHiPiecesOnly);   // both routes read D's first pieces only
+    st = make_f16x2_pieces_from_partials(w.D, K, N, N, w.diff_part, nparts, w.pieces_d, s);   // both routes read D's first pieces only
     if (st != OQ_OK) return st;
     // first pieces only: every term of the product carries a relative rounding error <= 2^-10, the loss is a sum of T N
     // squared K-term dot products -- its error (~1e-7 relative, measured against the three-product form) is four orders of
     // magnitude below what separates neighbouring grid points; a third of the matrix work (264 -> ~100 us per candidate)
     float* part = w.gemm_part + static_cast<int64_t>(candidate) * loss_stride(T, K, N);
     if (w.gram)   // <D, G D>, see finish_losses
-        return launch_gemm_f16x3(w.pieces_g, w.pieces_d, K, N, K, 1.0f, 0.0f, w.D, N, part, s, false, true, kAwqHiPiecesOnly);   // G 22 bits, D 11
-    return launch_gemm_f16x3(w.pieces_x, w.pieces_d, T, N, K, 1.0f, 0.0f, nullptr, 0, part, s, kAwqHiPiecesOnly);
+        return launch_gemm_f16x3(w.pieces_g, w.pieces_d, K, N, K, 1.0f, 0.0f, w.D, N, part, s, true);   // G 22 bits, D 11
+    return launch_gemm_f16x3(w.pieces_x, w.pieces_d, T, N, K, 1.0f, 0.0f, nullptr, 0, part, s);
 }
 
 static int32_t finish_losses(const float* gemm_part, int n_cand, int64_t T, int64_t K, int64_t N, float* losses_out, hipStream_t s) {

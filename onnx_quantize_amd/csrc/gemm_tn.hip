@@ -528,7 +528,7 @@ int32_t oq_matmul_pieces_f32(const void* pieces_a, const void* pieces_b, int64_t
                oq_matmul_pieces_bytes(Kd, N) != 0 && (reinterpret_cast<uintptr_t>(pieces_a) & 255u) == 0 &&
                (reinterpret_cast<uintptr_t>(pieces_b) & 255u) == 0, OQ_ERR_INVALID_ARGUMENT, "oq_matmul_pieces_f32: bad argument");
     const float* unscale = a_per_row_scales ? matmul_row_scales(const_cast<void*>(pieces_a), Kd, M) + M : nullptr;
-    return launch_gemm_f16x3(pieces_a, pieces_b, M, N, Kd, alpha, beta, C, ldc, nullptr, as_stream(stream), false, false, false, unscale);
+    return launch_gemm_f16x3(pieces_a, pieces_b, M, N, Kd, alpha, beta, C, ldc, nullptr, as_stream(stream), false, unscale);
 }
 
 }  // extern "C"

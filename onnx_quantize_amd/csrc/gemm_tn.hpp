@@ -78,10 +78,11 @@ __device__ __forceinline__ void upper_tile_of(int rem, int ntiles, int& tile_m, 
 int32_t launch_syrk_reduce(const float* slab, int splits, int64_t K, float alpha, float beta, float* C, int tile, hipStream_t s,
                            const float* post_scale = nullptr);
 
-// The same update on the bf16 matrix cores with fp32-exact operands (syrk_bf16x3.hip): every fp32 element is split
-// into three bf16 pieces whose sum is the element exactly; `terms` = 6 (piece products down to 2^-16, the dropped
-// ones are below fp32 rounding of a product), 9 (all of them) or 3 (two fp16 pieces of the scaled element, three products).  workspace = the pieces (syrk_bf16x3_pieces_bytes)
-// followed by optional T-slice slabs of K x K floats.
+// The same update on the half-precision matrix cores from operand pieces (syrk_bf16x3.hip, sections 1 to 2b).  `terms` = 6 or 9:
+// every fp32 element is split into three bf16 pieces whose sum is the element exactly, and 6 (piece products down to 2^-16,
+// the dropped ones are below fp32 rounding of a product) or all 9 products run on syrk_pieces_kernel<terms>.  `terms` = 3: two
+// fp16 pieces of the power-of-two scaled element and three products, on syrk_f16_m16_kernel.
+// workspace = the pieces (syrk_bf16x3_pieces_bytes) followed by optional T-slice slabs of K x K floats.
 size_t syrk_bf16x3_pieces_bytes(int64_t T, int64_t K);
 int32_t launch_syrk_bf16x3(const float* X, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C,
                            void* workspace, size_t workspace_bytes, int terms, hipStream_t s);
@@ -125,19 +126,19 @@ int32_t launch_inverse_level_f16x3(const float* Lt, float* X, float* Y, float* S
 //   make_f16x2_pieces      absmax -> power-of-two scale -> two fp16 pieces of every element, zero-padded to 32 contraction rows
 //                          and 256 columns; `pieces` (256-byte aligned, gemm_f16x3_pieces_bytes(Kd, cols)) holds the scale
 //                          header and the pieces.  contraction_is_fast_axis: the source is [cols, Kd] row-major (A = X^T).
-//   launch_gemm_f16x3      exactly one of C (store: alpha / beta like launch_gemm_tn) and loss_partial (one float per block
-//                          = gemm_f16x3_tiles(M, N): the sum of squares of that block's part of A^T B, nothing else written).
-//                          hi_pieces_only (loss form only): the product of the first pieces alone -- 11-bit operands, a third of
-//                          the matrix work; what the AWQ / clip searches' losses need (awq.hip).
+//   launch_gemm_f16x3      exactly one of C (store: alpha / beta like launch_gemm_tn, all three products) and loss_partial (one
+//                          float per block = gemm_f16x3_tiles(M, N): the sum of squares of that block's part of A^T B, nothing
+//                          else written; the product of the FIRST pieces alone -- 11-bit operands, a third of the matrix work;
+//                          what the AWQ / clip searches' losses need, awq.hip).
 //                          dot_with_c: C [M, N] is READ and loss_partial gets, per block, the sum of (A^T B) o C over its part
-//                          (the quadratic form <D, G D> of the searches' Gram route); with b_first_piece_only two products
-//                          instead of three: A with both pieces against B's first.
+//                          (the quadratic form <D, G D> of the searches' Gram route); two products: A with both pieces
+//                          against B's first.
 size_t gemm_f16x3_pieces_bytes(int64_t Kd, int64_t cols);
 int32_t make_f16x2_pieces(const float* X, int64_t Kd, int64_t cols, int64_t ldx, bool contraction_is_fast_axis, void* pieces, hipStream_t s,
                           bool wide_range = false,    // wide_range: a scale over the whole fp32 exponent range (plain GEMM operands; 1 / s^2 unset)
                           float* row_scales = nullptr);   // [2 cols] (fast-axis sources only): one power-of-two scale per source row instead of one per operand
 // For a producer that writes the FIRST (hi) fp16 pieces of a row-major [Kd, cols] operand itself instead of handing a
-// fp32 matrix to make_f16x2_pieces* (awq.hip: the quantize-residual kernel, round 5).  The eight fp16 of rows 8c .. 8c + 7 of
+// fp32 matrix to make_f16x2_pieces* (awq.hip: the quantize-residual kernel).  The eight fp16 of rows 8c .. 8c + 7 of
 // column n (k ascending, each fl16(x * s), round to nearest even) are the 16-byte vector
 //     P[(2 c) * gemm_f16x3_padded_cols(cols) + n],   P = pieces + gemm_f16x3_header_bytes();
 // columns from `cols` to the padded width and chunks from ceil(Kd / 8) to gemm_f16x3_chunks(Kd) must hold zeros.  The
@@ -146,11 +147,13 @@ int32_t make_f16x2_pieces(const float* X, int64_t Kd, int64_t cols, int64_t ldx,
 size_t gemm_f16x3_header_bytes();
 int64_t gemm_f16x3_padded_cols(int64_t cols);
 int64_t gemm_f16x3_chunks(int64_t Kd);
+// The FIRST pieces (the lo plane is left untouched) of a [Kd, cols] row-major source whose max |x| is already folded into
+// `npart` device partials: for consumers that read first pieces only (the loss and dot forms' B operand).
 int32_t make_f16x2_pieces_from_partials(const float* X, int64_t Kd, int64_t cols, int64_t ldx, const float* absmax_partials, int npart, void* pieces,
-                                        hipStream_t s, bool first_pieces_only = false);   // true: the lo plane is left untouched (consumers that read first pieces only)   // [Kd, cols] row-major source whose max |x| is already folded into `npart` device partials
+                                        hipStream_t s);
 int32_t launch_gemm_f16x3(const void* pieces_a, const void* pieces_b, int64_t M, int64_t N, int64_t Kd, float alpha, float beta, float* C,
-                          int64_t ldc, float* loss_partial, hipStream_t s, bool hi_pieces_only = false, bool dot_with_c = false,
-                          bool b_first_piece_only = false, const float* row_unscale_a = nullptr);   // row_unscale_a [M]: A was split with per-row scales
+                          int64_t ldc, float* loss_partial, hipStream_t s, bool dot_with_c = false,
+                          const float* row_unscale_a = nullptr);   // row_unscale_a [M]: A was split with per-row scales
 int64_t gemm_f16x3_tiles(int64_t M, int64_t N);
 
 }  // namespace oq

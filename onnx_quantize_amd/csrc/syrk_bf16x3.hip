@@ -1,50 +1,57 @@
-// G1 on the bf16 matrix cores with fp32-exact operands:  C = beta C + alpha X^T X  for tall X [T, K]  (gptq.py:246-260).
+// Symmetric and two-operand products on the gfx950 matrix cores from fp32 operands cut into half-precision PIECES: the GPTQ
+// Hessian  C = beta C + alpha X^T X  for tall X [T, K]  (gptq.py:246-260), the factor's trailing update and inverse, the lazy
+// batch update of the GPTQ loop and the loss products of the AWQ / clip searches.
 //
-// v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate (157 vs 2 500 TFLOP/s dense), and the Hessian is 90 % of a GPTQ
-// run.  An fp32 number is the exact sum of three bf16 numbers: hi = bf16(x), mid = bf16(x - hi), lo = x - hi - mid (8 + 8
-// + 8 significand bits; the subtractions are exact).  So x y = sum over the nine piece products, each of which is EXACT
-// in fp32 (8 x 8 bits), accumulated in fp32 by v_mfma_f32_32x32x16_bf16.  Relative to x y the products weigh
-//   hi.hi 1 | hi.mid, mid.hi 2^-8 | mid.mid, hi.lo, lo.hi 2^-16 | mid.lo, lo.mid 2^-24 | lo.lo 2^-32.
-// terms = 6 keeps everything down to 2^-16 (what is dropped is <= 2^-23 |x y|, the size of ONE fp32 rounding of the
-// product, and of either sign because the pieces are rounded to nearest); terms = 9 keeps all and is then MORE exact
-// than an fp32 fma chain (no product rounding at all).  6 MFMAs at 16 x the fp32 rate = 2.7 x the fp32 peak.
-// (bf16 has fp32's exponent range, so the split needs no scaling; inf / NaN inputs give NaN where fp32 gives inf / NaN.)
+// Why pieces.  v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate (157 vs 2 500 TFLOP/s dense), and the Hessian is 90 % of a
+// GPTQ run.  Three kinds of arithmetic, all accumulated in fp32 by the matrix cores:
 //
-// Two kernels.
-//  1. split_bf16x3_kernel: X -> pieces P, once (HBM-bound: 4 B read + 6 B written per element).  The MFMA wants, per
-//     lane, 8 consecutive k (= rows t of X) of ONE column, so a thread takes one column x 8 rows (coalesced dword loads
-//     across the wave), splits them in registers and writes three 16-byte vectors {t0..t7}:
-//         P[chunk = t / 8][piece][column (padded to 256)] x 16 B,   zero rows / columns behind T / K.
-//     Splitting inside the GEMM was measured first: every block re-splits its two panels (K / 256 times each element),
-//     and ~100 dependent VALU instructions per wave and stage do not hide under 48 MFMAs -- 212 against 336 TFLOP/s
-//     (fp32-equivalent) with the split compiled out.
-//  2. syrk_pieces_kernel: 256 x 256 tile of C per block, 8 waves (4 x 2), each 64 x 128 = 2 x 4 MFMA tiles (128
-//     accumulator registers).  A stage = 16 rows = [operand A|B][piece][chunk 0|1][256 columns] x 16 B = 48 KB of LDS, in
-//     exactly the order P holds them, so staging is 48 global_load_lds_dwordx4 (1 KB each, 6 per wave): no staging
-//     registers, no ds_write, no VALU.  LDS is a ring of three stages (144 KB, one block per CU).
+//  bf16x3 (`terms` = 6, 9).  An fp32 number is the exact sum of three bf16 numbers: hi = bf16(x), mid = bf16(x - hi),
+//     lo = x - hi - mid (8 + 8 + 8 significand bits; the subtractions are exact).  So x y = sum over the nine piece products,
+//     each of which is EXACT in fp32 (8 x 8 bits).  Relative to x y the products weigh
+//       hi.hi 1 | hi.mid, mid.hi 2^-8 | mid.mid, hi.lo, lo.hi 2^-16 | mid.lo, lo.mid 2^-24 | lo.lo 2^-32.
+//     terms = 6 keeps everything down to 2^-16 (what is dropped is <= 2^-23 |x y|, the size of ONE fp32 rounding of the
+//     product, and of either sign because the pieces are rounded to nearest); terms = 9 keeps all and is then MORE exact
+//     than an fp32 fma chain (no product rounding at all).  6 MFMAs at 16 x the fp32 rate = 2.7 x the fp32 peak.
+//     (bf16 has fp32's exponent range, so the split needs no scaling; inf / NaN inputs give NaN where fp32 gives inf / NaN.)
+//  f16x2 (`terms` = 3, "f16x3": three products).  TWO fp16 pieces per element, hi = f16(x s), lo = f16(x s - hi): 11 + 11
+//     significand bits, i.e. operands rounded to 22 bits (relative 2^-23), and the three products hi.hi, hi.lo, lo.hi (what is
+//     dropped -- lo.lo and the operand roundings -- is <= 3 * 2^-23 |x y|, the size of the product roundings of an fp32 fma
+//     chain and of either sign).  HALF the matrix-core work of terms = 6.  fp16 has five exponent bits, so the batch is scaled
+//     by a power of two s that puts max |x| into [2^14, 2^15) (one extra read of X for the absmax: 3 % of the call) and
+//     1 / s^2 -- exact -- goes onto alpha on the device.  Elements below 2^-29 max |x| lose low-order bits of their lo piece to
+//     fp16's subnormal spacing: an ABSOLUTE error below 2^-39 max |x|.  Consumers that can live with 11-bit operands run the
+//     first pieces alone (one product).
+//  native half.  Activations that ARE fp16 / bf16 need no pieces and no scale: their products are exact in fp32.
 //
-// Round 2, `terms` = 3 ("f16x3"): the same machinery on the fp16 matrix instructions (syrk_f16_m16_kernel, 16x16x32, by
-// default; syrk_pieces_kernel<3>, 32x32x16, with OQ_SYRK_F16_M16=0) with TWO fp16 pieces per element,
-// hi = f16(x s), lo = f16(x s - hi): 11 + 11 significand bits, i.e. operands rounded to 22 bits (relative 2^-23), and the
-// three products hi.hi, hi.lo, lo.hi (what is dropped -- lo.lo and the operand roundings -- is <= 3 * 2^-23 |x y|, the
-// size of the product roundings of an fp32 fma chain and of either sign).  HALF the matrix-core work of terms = 6.
-// fp16 has five exponent bits, so the batch is scaled by a power of two s that puts max |x| into [2^14, 2^15) (one extra
-// read of X for the absmax: 3 % of the call) and 1 / s^2 -- exact -- goes onto alpha on the device.  Elements below
-// 2^-29 max |x| lose low-order bits of their lo piece to fp16's subnormal spacing: an ABSOLUTE error below 2^-39 max |x|.
+// Pieces live in memory as P[chunk = t / 8][piece][column (padded to 256)] x 16 B -- the eight consecutive k (= rows t of X)
+// of one column that a lane hands to an MFMA -- with zero rows / columns behind T / K, so a stage of the product is copied to
+// LDS by global_load_lds_dwordx4 alone: no staging registers, no ds_write, no VALU.  Every product kernel computes a
+// 256 x 256 tile of C per block with 8 waves (4 x 2), 64 x 128 per wave (128 accumulator registers), one block per CU.
+//
+// Sections (entry points of gemm_tn.hpp -> kernels launched):
+//  1.  X -> bf16 pieces.  syrk_pieces_phases / launch_syrk_bf16x3, terms 6 and 9 -> split_bf16x3_kernel.
+//  1b. X -> fp16 pieces.  The same with terms 3, make_f16x2_pieces, make_f16x2_pieces_from_partials -> absmax_partial_kernel,
+//      absmax_scale_kernel / absmax_scale_wide_kernel, split_f16x2_kernel; for a source with the contraction on its fast
+//      axis row_pow2_scales_kernel and split_f16x2_fast_axis_kernel (they sit behind section 3b).
+//  2.  C += pieces^T pieces on bf16 pieces (v_mfma_f32_32x32x16_bf16).  syrk_pieces_phases, terms 6 and 9 ->
+//      syrk_pieces_kernel<6>, <9>, then launch_syrk_reduce when T is sliced.
+//  2b. The same on fp16 pieces (v_mfma_f32_16x16x32_f16): the stage loops and tile epilogues that sections 2c to 4b share.
+//      syrk_pieces_phases, terms 3 -> syrk_f16_m16_kernel, then launch_syrk_reduce when T is sliced.
+//  2c. Many Hessian updates, and the factor's trailing update, in one launch chain.  launch_syrk_f16x3_many,
+//      launch_syrk_f16x3_factor_update -> syrk_many_plan_kernel / syrk_factor_plan_kernel, absmax_partial_many_kernel,
+//      absmax_scale_many_kernel, split_f16x2_many_kernel, syrk_f16_m16_many_kernel.
+//  3.  Two-operand GEMM on fp16 pieces.  launch_gemm_f16x3 -> gemm_f16x3_kernel<0> (store, three products), <1, 1> (sum of
+//      squares, first pieces), <2, 2> (dot with C, two products).
+//  3b. One level of the factor's recursive-doubling inverse.  launch_inverse_level_f16x3 -> inverse_level_plan_kernel, the
+//      grouped preparation kernels of 2c, gemm_f16x3_many_kernel.
+//  4.  Hessian of fp16 / bf16 activations.  launch_syrk_h16 -> pack_h16_kernel<VEC>, syrk_h16_kernel<f16x8 | bf16x8>, then
+//      launch_syrk_reduce when T is sliced.
+//  4b. Many of those in one launch chain.  launch_syrk_h16_many -> syrk_h16_many_plan_kernel, pack_h16_many_kernel,
+//      syrk_h16_many_kernel<f16x8 | bf16x8>.
+// The host side of sections 1 to 3b sits between 3b and 4.
 #include "gemm_tn.hpp"
 
 #include <type_traits>
-
-#ifndef OQ_SYRK_F16_STRIDE
-#define OQ_SYRK_F16_STRIDE 3   /* measured on K = 11008: stride 5 21.7, 4 21.4, 3 21.1, 2 21.1, 1 21.3 ms per 65 536 rows */
-#endif
-#define OQ_SYRK_F16_STRIDE_EXPR (F16 ? OQ_SYRK_F16_STRIDE : 4)
-#ifndef OQ_SYRK_M16_STRIDE
-#define OQ_SYRK_M16_STRIDE 4   /* K = 11008, ms per 65 536 rows: stride 2 19.0-19.2, 4 18.83, 6 18.9, 8 18.9-19.0, 10 19.2-19.3 */
-#endif
-#ifndef OQ_SYRK_F16_DEEP
-#define OQ_SYRK_F16_DEEP 1
-#endif
 
 namespace oq {
 
@@ -55,21 +62,21 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kST = 256;                          // block tile edge
 constexpr int kSThreads = 512;
-// Geometry of a stage by piece kind.  bf16: three pieces, 16 rows (two 8-row chunks = the k of one MFMA) per stage, ring of
-// three stages = 144 KB.  fp16: two pieces and half the MFMAs per row, so a stage holds 32 rows (four chunks, two MFMA
-// k-steps) to keep 48 MFMAs per wave between two barriers, and the ring has two stages = 128 KB.
-template <int TERMS> struct StageGeom {
-    static constexpr bool F16 = TERMS == 3;
-    static constexpr int PIECES = F16 ? 2 : 3;
-    static constexpr int CH = (F16 && OQ_SYRK_F16_DEEP) ? 4 : 2;                     // 8-row chunks per stage
-    static constexpr int RING = (F16 && OQ_SYRK_F16_DEEP) ? 2 : 3;
+// Geometry of a stage: PIECES planes per operand, CH chunks of 8 rows, a ring of RING stages in LDS.
+template <int PIECES_, int CH_, int RING_> struct StageGeom {
+    static constexpr int PIECES = PIECES_, CH = CH_, RING = RING_;
     static constexpr int ROWS = 8 * CH;
     static constexpr int PLANE = CH * kST * 16;                // one piece of one operand: [chunk][256 columns] x 16 B
     static constexpr int OPERAND = PIECES * PLANE;
     static constexpr int STAGE = 2 * OPERAND;                  // A | B
     static constexpr int LDS = RING * STAGE;
-    static constexpr int NDMA = STAGE / 1024 / 8;              // 1 KB pieces of a stage per wave: 6 (bf16) / 8 (fp16)
+    static constexpr int NDMA = STAGE / 1024 / 8;              // 1 KB pieces of a stage per wave
 };
+// bf16: three pieces, 16 rows (two chunks = the k of one 32x32x16 MFMA) per stage = 48 KB, ring of three = 144 KB, 6 DMAs per wave.
+using Bf16Stage = StageGeom<3, 2, 3>;
+// fp16: two pieces and half the MFMAs per row, so a stage holds 32 rows (four chunks = the k of one 16x16x32 MFMA) = 64 KB to
+// keep 48 MFMA-equivalents per wave between two barriers; ring of two = 128 KB, 8 DMAs per wave.
+using F16Stage = StageGeom<2, 4, 2>;
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -87,7 +94,10 @@ __device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& hi, uin
     lo = pk_bf16(s0, s1);
 }
 
-// ---- 1. X -> pieces
+// ---- 1. X -> bf16 pieces, once (HBM-bound: 4 B read + 6 B written per element).  A thread takes one column x 8 rows (coalesced
+// dword loads across the wave), splits them in registers and writes three 16-byte vectors {t0..t7}.  Splitting inside the GEMM
+// was measured first: every block re-splits its two panels (K / 256 times each element), and ~100 dependent VALU instructions
+// per wave and stage do not hide under 48 MFMAs -- 212 against 336 TFLOP/s (fp32-equivalent) with the split compiled out.
 __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float* __restrict__ X, const int64_t T, const int64_t K, const int64_t ldx,
                                                            const int64_t Kp, const int64_t nchunks, u32x4* __restrict__ P) {
     const int64_t k = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -117,18 +127,13 @@ __global__ __launch_bounds__(256) void split_bf16x3_kernel(const float* __restri
 }
 
 // ---- 1b. fp16 pieces: scale, then hi = f16(x s), lo = f16(x s - hi)
-#ifdef OQ_PREP_NT
-#define OQ_PREP_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define OQ_PREP_LOAD(p) (*(p))
-#endif
 __device__ __forceinline__ void absmax_partial_body(const float* __restrict__ X, const int64_t T, const int64_t K, const int64_t ldx,
                                                     float* __restrict__ partial, const int64_t nblocks, const int64_t block) {
     float m = 0.f;
     const int64_t rows_per = (T + nblocks - 1) / nblocks;
     const int64_t t0 = block * rows_per, t1 = t0 + rows_per < T ? t0 + rows_per : T;
     for (int64_t t = t0; t < t1; ++t)
-        for (int64_t k = threadIdx.x; k < K; k += 256) m = nmax(m, fabsf(OQ_PREP_LOAD(X + t * ldx + k)));
+        for (int64_t k = threadIdx.x; k < K; k += 256) m = nmax(m, fabsf(X[t * ldx + k]));
     m = wave_max(m);
     __shared__ float sm[4];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
@@ -199,7 +204,7 @@ __device__ __forceinline__ void split_f16x2_body(const float* __restrict__ X, co
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int64_t t = c * 8 + r;
-            const float x = OQ_PREP_LOAD(src + (t < T ? t : T - 1) * ldx);
+            const float x = src[(t < T ? t : T - 1) * ldx];
             v[r] = (t < T && col_ok) ? x * sc : 0.f;                       // a power of two: exact
             // a sample whose square the fp32 path still sees (H[k][k] > 0: the channel is NOT dead, gptq.py:284-286) must not
             // vanish below fp16's last subnormal (|x| < 2^-40 max|x|): it keeps one unit there
@@ -227,18 +232,15 @@ __global__ __launch_bounds__(256) void split_f16x2_kernel(const float* __restric
     split_f16x2_body(X, T, K, ldx, Kp, nchunks, scale, alpha, P, static_cast<int64_t>(blockIdx.x), static_cast<int64_t>(blockIdx.y));
 }
 
-// one matrix-core instruction on a piece pair, chosen by the piece type
-__device__ __forceinline__ void mfma_pieces(const bf16x8& x, const bf16x8& y, f32x16& c) { c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0); }
-__device__ __forceinline__ void mfma_pieces(const f16x8& x, const f16x8& y, f32x16& c) { c = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, c, 0, 0, 0); }
-
 // The piece products of one output tile, small terms first, and the slot in front of which the B operand of the next
-// tile column is fetched.  bf16: 0 = hi, 1 = mid, 2 = lo; fp16: 0 = hi, 1 = lo.
+// tile column is fetched.  0 = hi, 1 = mid, 2 = lo.
 template <int TERMS> struct TermSeq;
-template <> struct TermSeq<3> { static constexpr int A[3] = {1, 0, 0}, B[3] = {0, 1, 0}, PF = 1; };
 template <> struct TermSeq<6> { static constexpr int A[6] = {2, 0, 1, 1, 0, 0}, B[6] = {0, 2, 1, 0, 1, 0}, PF = 3; };
 template <> struct TermSeq<9> { static constexpr int A[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0}, B[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0}, PF = 6; };
 
-// ---- 2. C += pieces^T pieces
+// ---- 2. C += pieces^T pieces on bf16 pieces, TERMS = 6 or 9 products per tile and k-step
+// A stage = 16 rows = [operand A|B][piece][chunk 0|1][256 columns] x 16 B = 48 KB of LDS, in exactly the order P holds them, so
+// staging is 48 global_load_lds_dwordx4 (1 KB each, 6 per wave).  LDS is a ring of three stages (144 KB, one block per CU).
 // Stream of one stage (sched_barrier(0) pins it; what sits BETWEEN two MFMAs issues while the first one runs):
 //   slots 0-23  this wave's six global_load_lds of stage s + 2 into ring slot (s + 2) % 3 (free since the last barrier),
 //               one every fourth slot
@@ -248,15 +250,12 @@ template <> struct TermSeq<9> { static constexpr int A[9] = {2, 2, 1, 2, 0, 1, 1
 //   end         vmcnt(0) (the DMAs were issued ~40 MFMAs ago), lgkmcnt(0), s_barrier.
 template <int TERMS>
 __global__ __launch_bounds__(kSThreads) void syrk_pieces_kernel(const u32x4* __restrict__ P, const int64_t K, const int64_t Kp, const int64_t nstages_all,
-                                                                const float alpha_in, const float beta, float* __restrict__ C,
-                                                                float* __restrict__ slab, const int64_t stages_per_slice, const int ntiles,
-                                                                const float* __restrict__ post_scale) {
-    using G = StageGeom<TERMS>;
-    constexpr bool F16 = G::F16;
+                                                                const float alpha, const float beta, float* __restrict__ C,
+                                                                float* __restrict__ slab, const int64_t stages_per_slice, const int ntiles) {
+    using G = Bf16Stage;
     constexpr int PIECES = G::PIECES, CH = G::CH, RING = G::RING, NDMA = G::NDMA;
+    static_assert(CH == 2 && RING == 3, "one 16-deep k-step per stage; stage s + 1 has landed while stage s is multiplied");
     constexpr int kPlaneBytes = G::PLANE, kOperandBytes = G::OPERAND, kStageBytes = G::STAGE;
-    using frag = std::conditional_t<F16, f16x8, bf16x8>;
-    const float alpha = post_scale ? alpha_in * post_scale[1] : alpha_in;      // fp16 pieces: 1 / s^2, a power of two
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     int tile_m, tile_n;
     upper_tile_of(static_cast<int>(xcd_remap(blockIdx.x, gridDim.x)), ntiles, tile_m, tile_n);
@@ -271,10 +270,8 @@ __global__ __launch_bounds__(kSThreads) void syrk_pieces_kernel(const u32x4* __r
 
     // ---- loader role: pieces q = NDMA wave .. NDMA wave + NDMA - 1 of the stage; piece q = 1 KB =
     // (operand, piece, chunk, quarter of 64 columns) in LDS order [operand][piece][chunk][256 columns]
-    // bounds are the maxima over both piece kinds, not NDMA / PIECES: a dependent-size array captured by a lambda silently
-    // invalidates the host side of this kernel (clang 22, HIP: no stub is emitted and the library does not load)
-    const char* gsrc[8];
-    uint32_t ldst[8];
+    const char* gsrc[NDMA];
+    uint32_t ldst[NDMA];
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) {
         const int q = wave * NDMA + i;
@@ -289,7 +286,7 @@ __global__ __launch_bounds__(kSThreads) void syrk_pieces_kernel(const u32x4* __r
                                          (__attribute__((address_space(3))) void*)(lds + slot3 * kStageBytes + ldst[i]), 16, 0, 0);
     };
 
-    // prologue: the first RING - 1 stages (clamped to the last stage of the slice when the slice is shorter: harmless re-reads)
+    // prologue: the first two stages (clamped to the last stage of the slice when the slice is shorter: harmless re-reads)
 #pragma unroll
     for (int st = 0; st < RING - 1; ++st)
 #pragma unroll
@@ -305,83 +302,68 @@ __global__ __launch_bounds__(kSThreads) void syrk_pieces_kernel(const u32x4* __r
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-    constexpr int kSlots = 8 * TERMS * (CH / 2);
-    static_assert(kSlots >= 2 + (NDMA - 1) * (OQ_SYRK_F16_STRIDE_EXPR) + 1, "the DMAs must fit into the stream");
+    constexpr int kSlots = 8 * TERMS;                   // MFMAs of a wave per stage
+    constexpr int STRIDE = 4;                           // one DMA every fourth MFMA
+    static_assert(kSlots >= 2 + (NDMA - 1) * STRIDE + 1, "the DMAs must fit into the stream");
     const uint32_t rd_a = static_cast<uint32_t>((kc * kST + wm * 64 + cl) * 16);
     const uint32_t rd_b = static_cast<uint32_t>(kOperandBytes + (kc * kST + wn * 128 + cl) * 16);
-    constexpr int kStepBytes = 2 * kST * 16;            // the two chunks of one MFMA k-step
-    frag a[2][3], b[2][3];
-    auto read_a = [&](int slot3, int h, int i) {
+    bf16x8 a[2][PIECES], b[2][PIECES];
+    auto read_a = [&](int slot3, int i) {
 #pragma unroll
         for (int p = PIECES - 1; p >= 0; --p)
-            a[i][p] = *reinterpret_cast<const frag*>(lds + slot3 * kStageBytes + rd_a + p * kPlaneBytes + h * kStepBytes + i * 32 * 16);
+            a[i][p] = *reinterpret_cast<const bf16x8*>(lds + slot3 * kStageBytes + rd_a + p * kPlaneBytes + i * 32 * 16);
     };
-    auto read_b = [&](int slot3, int h, int j, int which) {
+    auto read_b = [&](int slot3, int j, int which) {
 #pragma unroll
         for (int p = 0; p < PIECES; ++p)
-            b[which][p] = *reinterpret_cast<const frag*>(lds + slot3 * kStageBytes + rd_b + p * kPlaneBytes + h * kStepBytes + j * 32 * 16);
+            b[which][p] = *reinterpret_cast<const bf16x8*>(lds + slot3 * kStageBytes + rd_b + p * kPlaneBytes + j * 32 * 16);
     };
     auto stage_body = [&](auto phase_tag, int64_t s, int cur3, int nxt3, int wr3) {
-        constexpr int STRIDE = OQ_SYRK_F16_STRIDE_EXPR;                  // one DMA every fourth MFMA
         constexpr int DMA0 = decltype(phase_tag)::value ? 2 : 0;         // first slot of this wave's DMAs
         const int64_t s_dma = s + RING - 1 < nstages ? s + RING - 1 : nstages - 1;   // behind the slice: re-read its last stage into a slot nobody reads
         int slot = 0;
-        auto mm = [&](const frag& x, const frag& y, f32x16& c) {
+        auto mm = [&](const bf16x8& x, const bf16x8& y, f32x16& c) {
             __builtin_amdgcn_sched_barrier(0);
-            mfma_pieces(x, y, c);
+            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (slot >= DMA0 && slot < DMA0 + NDMA * STRIDE && (slot - DMA0) % STRIDE == 0) stage_dma(s_dma, wr3, (slot - DMA0) / STRIDE);
             ++slot;
         };
         using seq = TermSeq<TERMS>;
+        read_a(cur3, 1);                                  // a[0], b[0] came with the previous stage
 #pragma unroll
-        for (int h = 0; h < CH / 2; ++h) {
-            constexpr bool kLookAhead = RING >= 3;        // stage s + 1 landed before the last barrier only with a ring of three
-            const bool last_step = h == CH / 2 - 1;
-            read_a(cur3, h, 1);                           // a[0], b[0] came with the previous k-step
+        for (int j = 0; j < 4; ++j) {
+            const int cur = j & 1;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int cur = j & 1;
+            for (int i = 0; i < 2; ++i) {
+                f32x16 c = acc[i][j];
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    f32x16 c = acc[i][j];
-#pragma unroll
-                    for (int t = 0; t < TERMS; ++t) {
-                        if (t == seq::PF && i == 0) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (j < 3) read_b(cur3, h, j + 1, cur ^ 1);
-                            else if (!last_step) read_b(cur3, h + 1, 0, 0);
-                            else if (kLookAhead) read_b(nxt3, 0, 0, 0);
-                        }
-                        mm(a[i][seq::A[t]], b[cur][seq::B[t]], c);
-                    }
-                    acc[i][j] = c;
-                    if (i == 0 && j == 3) {
+                for (int t = 0; t < TERMS; ++t) {
+                    if (t == seq::PF && i == 0) {
                         __builtin_amdgcn_sched_barrier(0);
-                        if (!last_step) read_a(cur3, h + 1, 0);
-                        else if (kLookAhead) read_a(nxt3, 0, 0);
+                        if (j < 3) read_b(cur3, j + 1, cur ^ 1);
+                        else read_b(nxt3, 0, 0);
                     }
+                    mm(a[i][seq::A[t]], b[cur][seq::B[t]], c);
+                }
+                acc[i][j] = c;
+                if (i == 0 && j == 3) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    read_a(nxt3, 0);
                 }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
     };
-    read_b(0, 0, 0, 0);
-    read_a(0, 0, 0);
-    int cur3 = 0, nxt3 = RING >= 3 ? 1 : 1, wr3 = RING - 1;
+    read_b(0, 0, 0);
+    read_a(0, 0);
+    int cur3 = 0, nxt3 = 1, wr3 = 2;
     // Neighbouring waves (the two of a SIMD, and neighbouring SIMDs) run the same stream with their DMAs two slots apart,
     // so that they do not all pay the issue cost of a global_load_lds -- M0, address, ~100 cycles on a busy CU -- in the
     // same MFMA gap (measured: all in slots 0-5 199, half a stage apart 213-219, one every fourth slot and two slots
     // apart 225 TFLOP/s fp32-equivalent, K = 11008).  Two copies of the loop: a branch inside it would cost the
     // accumulators their registers.
-    auto rotate = [&]() {
-        if (RING >= 3) { const int t3 = cur3; cur3 = nxt3; nxt3 = wr3; wr3 = t3; }
-        else {           // ring of two: the stage just filled becomes current, and its first operands are fetched now
-            const int t3 = cur3; cur3 = wr3; nxt3 = t3; wr3 = t3;
-            read_b(cur3, 0, 0, 0);
-            read_a(cur3, 0, 0);
-        }
-    };
+    auto rotate = [&]() { const int t3 = cur3; cur3 = nxt3; nxt3 = wr3; wr3 = t3; };
     const int phase = __builtin_amdgcn_readfirstlane((wave >> 2) ^ (wave & 1));
     if (phase) {
         for (int64_t s = 0; s < nstages; ++s) {
@@ -427,11 +409,14 @@ __global__ __launch_bounds__(kSThreads) void syrk_pieces_kernel(const u32x4* __r
         }
 }
 
-// ---- 2b. The fp16-piece GEMM on v_mfma_f32_16x16x32_f16 (experiment: OQ_SYRK_F16_M16=1).  Same block tile, stage geometry
-// (32 rows = four 8-row chunks = ONE k-step of this instruction), ring of two and LDS-DMA staging as syrk_pieces_kernel<3>;
+// ---- 2b. The fp16-piece products on v_mfma_f32_16x16x32_f16.  Same block tile and LDS-DMA staging as section 2 with the
+// fp16 stage (F16Stage: 32 rows = four 8-row chunks = ONE k-step of this instruction, ring of two);
 // a wave's 64 x 128 tile is 4 x 8 tiles of 16 x 16.  Lane l supplies rows / columns i = l & 15 and the eight k-values of
 // chunk l >> 4 -- the same 16-byte vector P holds.  C/D map: col = l & 15, row = 4 (l >> 4) + e, e = 0..3.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
+// Slots between two DMAs of the three-product stream.  K = 11008, ms per 65 536 rows: stride 2 19.0-19.2, 4 18.83, 6 18.9,
+// 8 18.9-19.0, 10 19.2-19.3
+constexpr int kM16DmaStride = 4;
 
 // The stage loop of the 16x16x32 kernels, shared by the SYRK (A = B = one piece array) and the two-operand GEMM
 // (gemm_f16x3_kernel).  gsrc[i]: where this wave's i-th 1 KB piece of stage 0 comes from; a stage further is
@@ -443,8 +428,9 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 template <int NDMA, int PRODUCTS = 3>
 __device__ __forceinline__ void f16_m16_mainloop(const char* const (&gsrc)[8], const int64_t (&stage_bytes)[8], const int64_t nstages,
                                                  unsigned char* lds, f32x4v (&acc)[4][8]) {
-    using G = StageGeom<3>;
+    using G = F16Stage;
     static_assert(G::CH == 4 && G::RING == 2, "one 32-deep k-step per stage");
+    static_assert(PRODUCTS == 2 || PRODUCTS == 3, "the first pieces alone run in f16_hi_mainloop");
     constexpr int PIECES = 2;
     constexpr int kPlaneBytes = G::PLANE, kOperandBytes = G::OPERAND, kStageBytes = G::STAGE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -454,8 +440,8 @@ __device__ __forceinline__ void f16_m16_mainloop(const char* const (&gsrc)[8], c
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) ldst[i] = static_cast<uint32_t>(wave * NDMA + i) * 1024u;
     static_assert(PRODUCTS == 3 || NDMA == 8, "operand of a wave's DMA pieces: wave / 4, piece (wave / 2) % 2, with eight per wave");
-    // uniform: PRODUCTS = 1 fetches hi planes only, PRODUCTS = 2 everything but B's lo plane (waves 6 and 7)
-    const bool dma_on = PRODUCTS == 3 || (PRODUCTS == 1 ? ((wave >> 1) & 1) == 0 : wave < 6);
+    // uniform: PRODUCTS = 2 fetches everything but B's lo plane (waves 6 and 7)
+    const bool dma_on = PRODUCTS == 3 || wave < 6;
     auto stage_dma = [&](int64_t s_rel, int slot, int i) {
         if (dma_on)
             __builtin_amdgcn_global_load_lds(gsrc[i] + s_rel * stage_bytes[i],
@@ -478,14 +464,14 @@ __device__ __forceinline__ void f16_m16_mainloop(const char* const (&gsrc)[8], c
     f16x8 a[4][2], b[2][2];
     auto read_a = [&](int slot, int i) {
 #pragma unroll
-        for (int p = (PRODUCTS >= 2 ? PIECES : 1) - 1; p >= 0; --p) a[i][p] = *reinterpret_cast<const f16x8*>(lds + slot * kStageBytes + rd_a + p * kPlaneBytes + i * 16 * 16);
+        for (int p = PIECES - 1; p >= 0; --p) a[i][p] = *reinterpret_cast<const f16x8*>(lds + slot * kStageBytes + rd_a + p * kPlaneBytes + i * 16 * 16);
     };
     auto read_b = [&](int slot, int j, int which) {
 #pragma unroll
         for (int p = 0; p < (PRODUCTS == 3 ? PIECES : 1); ++p) b[which][p] = *reinterpret_cast<const f16x8*>(lds + slot * kStageBytes + rd_b + p * kPlaneBytes + j * 16 * 16);   // B's first piece only unless all three products run
     };
     auto stage_body = [&](auto phase_tag, int64_t s, int cur, int wr) {
-        constexpr int STRIDE = PRODUCTS == 3 ? OQ_SYRK_M16_STRIDE : PRODUCTS == 2 ? 3 : 2;   // in 16-cycle MFMA slots (32 per product and stage)
+        constexpr int STRIDE = PRODUCTS == 3 ? kM16DmaStride : 3;   // in 16-cycle MFMA slots (32 per product and stage)
         constexpr int DMA0 = decltype(phase_tag)::value ? (PRODUCTS == 3 ? 4 : 2) : 0;
         const int64_t s_dma = s + 1 < nstages ? s + 1 : nstages - 1;
         int slot = 0;
@@ -507,7 +493,7 @@ __device__ __forceinline__ void f16_m16_mainloop(const char* const (&gsrc)[8], c
                     __builtin_amdgcn_sched_barrier(0);
                     read_b(cur, j + 1, cb ^ 1);
                 }
-                if constexpr (PRODUCTS >= 2) mm(a[i][1], b[cb][0], c);     // lo . hi
+                mm(a[i][1], b[cb][0], c);     // lo . hi
                 if constexpr (PRODUCTS == 3) mm(a[i][0], b[cb][1], c);     // hi . lo
                 mm(a[i][0], b[cb][0], c);     // hi . hi
                 acc[i][j] = c;
@@ -549,7 +535,7 @@ __device__ __forceinline__ void f16_m16_mainloop(const char* const (&gsrc)[8], c
 constexpr int kHiPlane = 4 * kST * 16;        // [4 chunks][256 columns] x 16 B
 constexpr int kHiStage = 2 * kHiPlane;        // A | B
 constexpr int kHiRing = 4;
-static_assert(kHiRing * kHiStage <= StageGeom<3>::LDS, "the hi-only ring fits the LDS reserved for the generic loop");
+static_assert(kHiRing * kHiStage <= F16Stage::LDS, "the hi-only ring fits the LDS reserved for the generic loop");
 
 // FRAG: f16x8 (the first fp16 pieces) or bf16x8 (section 4: bf16 activations as they are); the same 16x16x32 operand layout.
 __device__ __forceinline__ void mfma_m16(const f16x8& x, const f16x8& y, f32x4v& c) { c = __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); }
@@ -634,7 +620,7 @@ __device__ __forceinline__ void f16_hi_mainloop(const char* const (&gsrc)[4], co
 constexpr int kEpiLd = 260;   // floats per staged row: 4 kc * 260 = 16 kc (mod 64 banks), the 16 cl lanes consecutive: no conflicts
 template <bool TRANSPOSED, typename Rows, typename Cols>
 __device__ __forceinline__ void staged_tile_epilogue(const f32x4v (&acc)[4][8], unsigned char* lds, Rows&& rows, Cols&& cols) {
-    static_assert(64 * kEpiLd * 4 <= StageGeom<3>::LDS, "a 64-row pass fits the stage ring");
+    static_assert(64 * kEpiLd * 4 <= F16Stage::LDS, "a 64-row pass fits the stage ring");
     float* t = reinterpret_cast<float*>(lds);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -728,7 +714,7 @@ __device__ __forceinline__ void syrk_f16_m16_body(const u32x4* __restrict__ P, c
                                                   const float* __restrict__ post_scale, const int tile, const int64_t slice, unsigned char* lds,
                                                   const int64_t ldc,    // leading dimension of C (slabs are always K x K)
                                                   const bool mirror_all = true) {   // false: only diagonal tiles write their lower half
-    using G = StageGeom<3>;
+    using G = F16Stage;
     constexpr int PIECES = 2, CH = 4, NDMA = G::NDMA;
     const float alpha = post_scale ? alpha_in * post_scale[1] : alpha_in;
     int tile_m, tile_n;
@@ -800,8 +786,8 @@ __global__ void syrk_many_plan_kernel(const int64_t* __restrict__ pub, const int
         o.T = it[2]; o.K = it[3]; o.ldx = it[4]; o.ldc = it[3];
         const int64_t n_seen = it[5], n_total = it[5] + it[6];
         o.Kp = (o.K + kST - 1) / kST * kST;
-        o.nstages = (o.T + StageGeom<3>::ROWS - 1) / StageGeom<3>::ROWS;
-        o.nchunks = o.nstages * StageGeom<3>::CH;
+        o.nstages = (o.T + F16Stage::ROWS - 1) / F16Stage::ROWS;
+        o.nchunks = o.nstages * F16Stage::CH;
         o.scale = reinterpret_cast<float*>(pieces_base + off);
         o.P = reinterpret_cast<u32x4*>(pieces_base + off + 16384);
         off += 16384 + static_cast<size_t>(o.nchunks) * 2 * static_cast<size_t>(o.Kp) * 16;
@@ -830,8 +816,8 @@ __global__ void syrk_factor_plan_kernel(const float* __restrict__ Lt, float* __r
     o.C = P + m * ms + pend * K + pend;
     o.T = pend - O; o.K = K - pend; o.ldx = K; o.ldc = K;
     o.Kp = (o.K + kST - 1) / kST * kST;
-    o.nstages = (o.T + StageGeom<3>::ROWS - 1) / StageGeom<3>::ROWS;
-    o.nchunks = o.nstages * StageGeom<3>::CH;
+    o.nstages = (o.T + F16Stage::ROWS - 1) / F16Stage::ROWS;
+    o.nchunks = o.nstages * F16Stage::CH;
     const size_t item_bytes = 16384 + static_cast<size_t>(o.nchunks) * 2 * static_cast<size_t>(o.Kp) * 16;
     o.scale = reinterpret_cast<float*>(pieces_base + m * item_bytes);
     o.P = reinterpret_cast<u32x4*>(pieces_base + m * item_bytes + 16384);
@@ -910,7 +896,7 @@ struct PieceGemm {
 
 template <int EPI, int PRODUCTS = 3>
 __device__ __forceinline__ void gemm_f16x3_body(const PieceGemm& g, const int tile, unsigned char* lds) {
-    using G = StageGeom<3>;
+    using G = F16Stage;
     constexpr int PIECES = 2, CH = 4, NDMA = G::NDMA;
     const int tiles_n = static_cast<int>(g.Np / kST);
     const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
@@ -1072,16 +1058,16 @@ struct InverseLevel {
 };
 
 __device__ __forceinline__ size_t piece_bytes_dev(int64_t T, int64_t cols) {
-    const int64_t st = (T + StageGeom<3>::ROWS - 1) / StageGeom<3>::ROWS, cp = (cols + kST - 1) / kST * kST;
-    return 16384 + static_cast<size_t>(st) * StageGeom<3>::CH * 2 * static_cast<size_t>(cp) * 16;
+    const int64_t st = (T + F16Stage::ROWS - 1) / F16Stage::ROWS, cp = (cols + kST - 1) / kST * kST;
+    return 16384 + static_cast<size_t>(st) * F16Stage::CH * 2 * static_cast<size_t>(cp) * 16;
 }
 
 __device__ __forceinline__ SyrkItem prep_item(const float* X, int64_t T, int64_t cols, int64_t ldx, unsigned char* where, int64_t split0) {
     SyrkItem o;
     o.X = X; o.C = nullptr; o.T = T; o.K = cols; o.ldx = ldx; o.ldc = 0;
     o.Kp = (cols + kST - 1) / kST * kST;
-    o.nstages = (T + StageGeom<3>::ROWS - 1) / StageGeom<3>::ROWS;
-    o.nchunks = o.nstages * StageGeom<3>::CH;
+    o.nstages = (T + F16Stage::ROWS - 1) / F16Stage::ROWS;
+    o.nchunks = o.nstages * F16Stage::CH;
     o.scale = reinterpret_cast<float*>(where);
     o.P = reinterpret_cast<u32x4*>(where + 16384);
     o.split0 = split0; o.tile0 = 0; o.tn = 0;
@@ -1092,8 +1078,8 @@ __device__ __forceinline__ SyrkItem prep_item(const float* X, int64_t T, int64_t
 }
 
 __device__ __forceinline__ int64_t split_blocks_of(int64_t T, int64_t cols) {
-    const int64_t st = (T + StageGeom<3>::ROWS - 1) / StageGeom<3>::ROWS, cp = (cols + kST - 1) / kST * kST;
-    return (cp / 256) * ((st * StageGeom<3>::CH + 3) / 4);
+    const int64_t st = (T + F16Stage::ROWS - 1) / F16Stage::ROWS, cp = (cols + kST - 1) / kST * kST;
+    return (cp / 256) * ((st * F16Stage::CH + 3) / 4);
 }
 
 __global__ void inverse_level_plan_kernel(const InverseLevel lv, unsigned char* __restrict__ pieces_base, SyrkItem* __restrict__ prep,
@@ -1196,8 +1182,8 @@ static int64_t stages_of(int64_t T, int rows) { return ceil_div(T, rows); }
 size_t syrk_bf16x3_pieces_bytes(int64_t T, int64_t K) {
     if (T <= 0 || K <= 0) return 0;
     // room for either kind: three bf16 pieces of 16-row stages, or the scale header + two fp16 pieces of 32-row stages
-    const size_t b16 = static_cast<size_t>(stages_of(T, StageGeom<6>::ROWS)) * StageGeom<6>::CH * StageGeom<6>::PIECES;
-    const size_t f16 = static_cast<size_t>(stages_of(T, StageGeom<3>::ROWS)) * StageGeom<3>::CH * StageGeom<3>::PIECES;
+    const size_t b16 = static_cast<size_t>(stages_of(T, Bf16Stage::ROWS)) * Bf16Stage::CH * Bf16Stage::PIECES;
+    const size_t f16 = static_cast<size_t>(stages_of(T, F16Stage::ROWS)) * F16Stage::CH * F16Stage::PIECES;
     return (b16 > f16 ? b16 : f16) * padded_k(K) * 16 + kScaleHeaderBytes;
 }
 
@@ -1245,16 +1231,10 @@ int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, fl
     u32x4* P = reinterpret_cast<u32x4*>(base + (f16 ? kScaleHeaderBytes : 0));
     if (slab == nullptr) slab_bytes = 0;
     // per launch, not once: the attribute belongs to the current device's copy of the kernel
-#ifdef OQ_SYRK_LAB
-    static const bool f16_m16_env = [] { const char* v = getenv("OQ_SYRK_F16_M16"); return !v || atoi(v) != 0; }();   // lab builds only; 0: the 32x32x16 form
-    const bool f16_m16 = f16 && f16_m16_env;
-#else
-    const bool f16_m16 = f16;      // the shipped library reads no environment here
-#endif
-    const void* kfn = f16_m16 ? reinterpret_cast<const void*>(&syrk_f16_m16_kernel) : terms == 9 ? reinterpret_cast<const void*>(&syrk_pieces_kernel<9>)
-                                 : (terms == 6 ? reinterpret_cast<const void*>(&syrk_pieces_kernel<6>) : reinterpret_cast<const void*>(&syrk_pieces_kernel<3>));
-    const int lds_bytes = f16 ? StageGeom<3>::LDS : StageGeom<6>::LDS;
-    const int stage_rows = f16 ? StageGeom<3>::ROWS : StageGeom<6>::ROWS, stage_chunks = stage_rows / 8;
+    const void* kfn = f16 ? reinterpret_cast<const void*>(&syrk_f16_m16_kernel)
+                          : (terms == 9 ? reinterpret_cast<const void*>(&syrk_pieces_kernel<9>) : reinterpret_cast<const void*>(&syrk_pieces_kernel<6>));
+    const int lds_bytes = f16 ? F16Stage::LDS : Bf16Stage::LDS;
+    const int stage_rows = f16 ? F16Stage::ROWS : Bf16Stage::ROWS, stage_chunks = stage_rows / 8;
     hipError_t e1 = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     OQ_REQUIRE(e1 == hipSuccess, OQ_ERR_LAUNCH, "syrk_bf16x3: cannot reserve %d bytes of LDS", lds_bytes);
     const int64_t Kp = padded_k(K), nstages = stages_of(T, stage_rows), nchunks = nstages * stage_chunks;
@@ -1280,31 +1260,21 @@ int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, fl
     const int64_t tiles = static_cast<int64_t>(tn) * (tn + 1) / 2;
     // T-slices: one block per CU (128-144 KB of LDS), 256 CUs.  Choose the slice count (<= 16, slices of >= 512 rows, slab
     // permitting) whose block count fills whole rounds of 256 best; ties go to fewer slices.  Measured on K = 4096, 65 536
-    // rows (scripts/lab_syrk_splits.py, ms per product): 1 slice 3.26, 3: 2.72, 5: 2.57, 7: 2.54, 9: 2.53, 15: 2.61; K = 11008
+    // rows (ms per product, slice count forced): 1 slice 3.26, 3: 2.72, 5: 2.57, 7: 2.54, 9: 2.53, 15: 2.61; K = 11008
     // is flat (1 slice 17.04, 4: 17.02).  A cost model that prefers fewer slices (5 and 1 for these shapes) was tried and
     // measured equal in time, but every slice is also a shorter fp32 accumulation chain: with one slice instead of four the
     // error against float64 of an 8192-row K = 11008 call rose from 8e-7 to 4e-6 of max |H| (bound: 1e-5).  More slices stay.
     int splits = choose_t_slices(nstages, stage_rows, tiles, K, slab_bytes);
-#ifdef OQ_SYRK_LAB
-    if (const char* v = getenv("OQ_SYRK_SPLITS")) {      // lab builds only (scripts/lab_syrk_splits.sh): force the slice count
-        const int c = atoi(v);
-        if (c >= 1 && (c == 1 || static_cast<size_t>(c) * K * K * sizeof(float) <= slab_bytes)) splits = c;
-    }
-#endif
     int64_t per = ceil_div(nstages, splits);
     splits = static_cast<int>(ceil_div(nstages, per));
     float* slab_f = splits > 1 ? slab : nullptr;
     const dim3 grid(static_cast<uint32_t>(tiles), static_cast<uint32_t>(splits));
-    const float* no_scale = nullptr;
     if (terms == 9)
-        hipLaunchKernelGGL(syrk_pieces_kernel<9>, grid, dim3(kSThreads), lds_bytes, s, P, K, Kp, nstages, alpha, beta, C, slab_f, per, tn, no_scale);
+        hipLaunchKernelGGL(syrk_pieces_kernel<9>, grid, dim3(kSThreads), lds_bytes, s, P, K, Kp, nstages, alpha, beta, C, slab_f, per, tn);
     else if (terms == 6)
-        hipLaunchKernelGGL(syrk_pieces_kernel<6>, grid, dim3(kSThreads), lds_bytes, s, P, K, Kp, nstages, alpha, beta, C, slab_f, per, tn, no_scale);
-    else if (f16_m16)
-        hipLaunchKernelGGL(syrk_f16_m16_kernel, grid, dim3(kSThreads), lds_bytes, s, P, K, Kp, nstages, alpha, beta, C, slab_f, per, tn,
-                           static_cast<const float*>(scale));
+        hipLaunchKernelGGL(syrk_pieces_kernel<6>, grid, dim3(kSThreads), lds_bytes, s, P, K, Kp, nstages, alpha, beta, C, slab_f, per, tn);
     else
-        hipLaunchKernelGGL(syrk_pieces_kernel<3>, grid, dim3(kSThreads), lds_bytes, s, P, K, Kp, nstages, alpha, beta, C, slab_f, per, tn,
+        hipLaunchKernelGGL(syrk_f16_m16_kernel, grid, dim3(kSThreads), lds_bytes, s, P, K, Kp, nstages, alpha, beta, C, slab_f, per, tn,
                            static_cast<const float*>(scale));
     st = check_launch("syrk_pieces_kernel");
     if (st != OQ_OK || splits == 1) return st;
@@ -1314,7 +1284,7 @@ int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, fl
 
 // ---- many Hessian updates, one launch chain (section 2c)
 static size_t syrk_many_item_bytes(int64_t T, int64_t K) {
-    return kScaleHeaderBytes + static_cast<size_t>(stages_of(T, StageGeom<3>::ROWS)) * StageGeom<3>::CH * 2 * static_cast<size_t>(padded_k(K)) * 16;
+    return kScaleHeaderBytes + static_cast<size_t>(stages_of(T, F16Stage::ROWS)) * F16Stage::CH * 2 * static_cast<size_t>(padded_k(K)) * 16;
 }
 static size_t syrk_many_table_bytes(int64_t count) { return (static_cast<size_t>(count) * sizeof(SyrkItem) + 255) / 256 * 256; }
 
@@ -1339,7 +1309,7 @@ int32_t launch_syrk_f16x3_many(const int64_t* items_host, const int64_t* items_d
                    "hessian_many: item %lld: X, H, T > 0, K > 0, ldx >= K, n_seen >= 0, n_add > 0 expected", (long long)m);
         OQ_REQUIRE(matrix_ok(it[2], it[3], it[4]) && it[3] <= kMaxHessianWidth && it[5] <= kMaxSamples && it[6] <= kMaxSamples, OQ_ERR_UNSUPPORTED,
                    "hessian_many: item %lld is too large", (long long)m);
-        const int64_t Kp = padded_k(it[3]), nchunks = stages_of(it[2], StageGeom<3>::ROWS) * StageGeom<3>::CH, tn = Kp / kST;
+        const int64_t Kp = padded_k(it[3]), nchunks = stages_of(it[2], F16Stage::ROWS) * F16Stage::CH, tn = Kp / kST;
         split_blocks += (Kp / 256) * ceil_div(nchunks, 4);
         tiles += tn * (tn + 1) / 2;
     }
@@ -1351,15 +1321,15 @@ int32_t launch_syrk_f16x3_many(const int64_t* items_host, const int64_t* items_d
     SyrkItem* table = reinterpret_cast<SyrkItem*>(base);
     unsigned char* pieces = base + syrk_many_table_bytes(count);
     const int n = static_cast<int>(count);
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_f16_m16_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, StageGeom<3>::LDS);
-    OQ_REQUIRE(e1 == hipSuccess, OQ_ERR_LAUNCH, "hessian_many: cannot reserve %d bytes of LDS", StageGeom<3>::LDS);
+    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_f16_m16_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F16Stage::LDS);
+    OQ_REQUIRE(e1 == hipSuccess, OQ_ERR_LAUNCH, "hessian_many: cannot reserve %d bytes of LDS", F16Stage::LDS);
     hipLaunchKernelGGL(syrk_many_plan_kernel, dim3(1), dim3(64), 0, s, items_device, n, pieces, table);
     hipLaunchKernelGGL(absmax_partial_many_kernel, dim3(kManyAbsmaxBlocks, static_cast<uint32_t>(n)), dim3(256), 0, s, table);
     hipLaunchKernelGGL(absmax_scale_many_kernel, dim3(static_cast<uint32_t>(n)), dim3(256), 0, s, table);
     hipLaunchKernelGGL(split_f16x2_many_kernel, dim3(static_cast<uint32_t>(split_blocks)), dim3(256), 0, s, table, n);
     int32_t st = check_launch("split_f16x2_many_kernel");
     if (st != OQ_OK) return st;
-    hipLaunchKernelGGL(syrk_f16_m16_many_kernel, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), StageGeom<3>::LDS, s, table, n);
+    hipLaunchKernelGGL(syrk_f16_m16_many_kernel, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), F16Stage::LDS, s, table, n);
     return check_launch("syrk_f16_m16_many_kernel");
 }
 
@@ -1379,23 +1349,23 @@ int32_t launch_syrk_f16x3_factor_update(const float* Lt, float* P, int64_t ms, i
     SyrkItem* table = reinterpret_cast<SyrkItem*>(base);
     unsigned char* pieces = base + syrk_many_table_bytes(count);
     const int n = static_cast<int>(count);
-    const int64_t Kp = padded_k(rest), nchunks = stages_of(kd, StageGeom<3>::ROWS) * StageGeom<3>::CH, tn = Kp / kST;
+    const int64_t Kp = padded_k(rest), nchunks = stages_of(kd, F16Stage::ROWS) * F16Stage::CH, tn = Kp / kST;
     const int64_t split_blocks = count * (Kp / 256) * ceil_div(nchunks, 4), tiles = count * (tn * (tn + 1) / 2);
     OQ_REQUIRE(split_blocks < (1ll << 31) && tiles < (1ll << 31), OQ_ERR_UNSUPPORTED, "factor update: too many blocks for one launch");
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_f16_m16_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, StageGeom<3>::LDS);
-    OQ_REQUIRE(e1 == hipSuccess, OQ_ERR_LAUNCH, "factor update: cannot reserve %d bytes of LDS", StageGeom<3>::LDS);
+    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_f16_m16_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F16Stage::LDS);
+    OQ_REQUIRE(e1 == hipSuccess, OQ_ERR_LAUNCH, "factor update: cannot reserve %d bytes of LDS", F16Stage::LDS);
     hipLaunchKernelGGL(syrk_factor_plan_kernel, dim3(static_cast<uint32_t>(ceil_div(count, 64))), dim3(64), 0, s, Lt, P, ms, n, K, O, pend, pieces, table);
     hipLaunchKernelGGL(absmax_partial_many_kernel, dim3(kManyAbsmaxBlocks, static_cast<uint32_t>(n)), dim3(256), 0, s, table);
     hipLaunchKernelGGL(absmax_scale_many_kernel, dim3(static_cast<uint32_t>(n)), dim3(256), 0, s, table);
     hipLaunchKernelGGL(split_f16x2_many_kernel, dim3(static_cast<uint32_t>(split_blocks)), dim3(256), 0, s, table, n);
-    hipLaunchKernelGGL(syrk_f16_m16_many_kernel, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), StageGeom<3>::LDS, s, table, n);
+    hipLaunchKernelGGL(syrk_f16_m16_many_kernel, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), F16Stage::LDS, s, table, n);
     return check_launch("syrk_f16_m16_many_kernel (factor update)");
 }
 
 static size_t piece_bytes_host(int64_t T, int64_t cols) {
-    return kScaleHeaderBytes + static_cast<size_t>(stages_of(T, StageGeom<3>::ROWS)) * StageGeom<3>::CH * 2 * static_cast<size_t>(padded_k(cols)) * 16;
+    return kScaleHeaderBytes + static_cast<size_t>(stages_of(T, F16Stage::ROWS)) * F16Stage::CH * 2 * static_cast<size_t>(padded_k(cols)) * 16;
 }
-static int64_t split_blocks_host(int64_t T, int64_t cols) { return (padded_k(cols) / 256) * ceil_div(stages_of(T, StageGeom<3>::ROWS) * StageGeom<3>::CH, 4); }
+static int64_t split_blocks_host(int64_t T, int64_t cols) { return (padded_k(cols) / 256) * ceil_div(stages_of(T, F16Stage::ROWS) * F16Stage::CH, 4); }
 
 size_t inverse_level_f16x3_bytes(int64_t b, int64_t b2, int64_t problems) {
     if (b <= 0 || b2 <= 0 || problems <= 0) return 0;
@@ -1417,8 +1387,8 @@ int32_t launch_inverse_level_f16x3(const float* Lt, float* X, float* Y, float* S
     const int64_t split1 = n * (split_blocks_host(b, b2) + split_blocks_host(b, b) + split_blocks_host(b2, b2)), split2 = n * split_blocks_host(b2, b);
     const int64_t tiles = (padded_k(b2) / kST) * (padded_k(b) / kST);
     OQ_REQUIRE(split1 < (1ll << 31) && split2 < (1ll << 31) && tiles < (1ll << 31), OQ_ERR_UNSUPPORTED, "inverse level: too many blocks for one launch");
-    OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, StageGeom<3>::LDS) == hipSuccess,
-               OQ_ERR_LAUNCH, "inverse level: cannot reserve %d bytes of LDS", StageGeom<3>::LDS);
+    OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F16Stage::LDS) == hipSuccess,
+               OQ_ERR_LAUNCH, "inverse level: cannot reserve %d bytes of LDS", F16Stage::LDS);
     InverseLevel lv;
     lv.Lt = Lt; lv.X = X; lv.Y = Y; lv.S = S; lv.ms = ms; lv.K = K; lv.b = b; lv.b2 = b2; lv.first = first; lv.pairs = pairs;
     lv.count = static_cast<int32_t>(count);
@@ -1427,18 +1397,18 @@ int32_t launch_inverse_level_f16x3(const float* Lt, float* X, float* Y, float* S
     hipLaunchKernelGGL(absmax_partial_many_kernel, dim3(kManyAbsmaxBlocks, n3), dim3(256), 0, s, prep);
     hipLaunchKernelGGL(absmax_scale_many_kernel, dim3(n3), dim3(256), 0, s, prep);
     hipLaunchKernelGGL(split_f16x2_many_kernel, dim3(static_cast<uint32_t>(split1)), dim3(256), 0, s, prep, static_cast<int>(n3));
-    hipLaunchKernelGGL(gemm_f16x3_many_kernel, dim3(static_cast<uint32_t>(tiles), n1), dim3(kSThreads), StageGeom<3>::LDS, s, gemms);
+    hipLaunchKernelGGL(gemm_f16x3_many_kernel, dim3(static_cast<uint32_t>(tiles), n1), dim3(kSThreads), F16Stage::LDS, s, gemms);
     hipLaunchKernelGGL(absmax_partial_many_kernel, dim3(kManyAbsmaxBlocks, n1), dim3(256), 0, s, prep + 3 * n);
     hipLaunchKernelGGL(absmax_scale_many_kernel, dim3(n1), dim3(256), 0, s, prep + 3 * n);
     hipLaunchKernelGGL(split_f16x2_many_kernel, dim3(static_cast<uint32_t>(split2)), dim3(256), 0, s, prep + 3 * n, static_cast<int>(n1));
-    hipLaunchKernelGGL(gemm_f16x3_many_kernel, dim3(static_cast<uint32_t>(tiles), n1), dim3(kSThreads), StageGeom<3>::LDS, s, gemms + n);
+    hipLaunchKernelGGL(gemm_f16x3_many_kernel, dim3(static_cast<uint32_t>(tiles), n1), dim3(kSThreads), F16Stage::LDS, s, gemms + n);
     return check_launch("inverse level (fp16 pieces)");
 }
 
 // ---- host side of the two-operand GEMM (gemm_tn.hpp)
 size_t gemm_f16x3_pieces_bytes(int64_t Kd, int64_t cols) {
     if (Kd <= 0 || cols <= 0) return 0;
-    return static_cast<size_t>(stages_of(Kd, StageGeom<3>::ROWS)) * StageGeom<3>::CH * 2 * padded_k(cols) * 16 + kScaleHeaderBytes;
+    return static_cast<size_t>(stages_of(Kd, F16Stage::ROWS)) * F16Stage::CH * 2 * padded_k(cols) * 16 + kScaleHeaderBytes;
 }
 
 int32_t make_f16x2_pieces(const float* X, int64_t Kd, int64_t cols, int64_t ldx, bool contraction_is_fast_axis, void* pieces, hipStream_t s,
@@ -1446,7 +1416,7 @@ int32_t make_f16x2_pieces(const float* X, int64_t Kd, int64_t cols, int64_t ldx,
     OQ_REQUIRE(X && pieces && Kd > 0 && cols > 0 && (reinterpret_cast<uintptr_t>(pieces) & 255u) == 0, OQ_ERR_INVALID_ARGUMENT, "make_f16x2_pieces: bad argument");
     float* scale = static_cast<float*>(pieces);
     u32x4* P = reinterpret_cast<u32x4*>(static_cast<unsigned char*>(pieces) + kScaleHeaderBytes);
-    const int64_t Cp = padded_k(cols), nstages = stages_of(Kd, StageGeom<3>::ROWS), nchunks = nstages * StageGeom<3>::CH;
+    const int64_t Cp = padded_k(cols), nstages = stages_of(Kd, F16Stage::ROWS), nchunks = nstages * F16Stage::CH;
     OQ_REQUIRE(ceil_div(nchunks, 4) <= 65535, OQ_ERR_UNSUPPORTED, "make_f16x2_pieces: contraction too long (%lld)", (long long)Kd);
     // absmax over the whole operand: rows x row length as stored
     const int64_t rows = contraction_is_fast_axis ? cols : Kd, rowlen = contraction_is_fast_axis ? Kd : cols;
@@ -1468,62 +1438,52 @@ int32_t make_f16x2_pieces(const float* X, int64_t Kd, int64_t cols, int64_t ldx,
     return check_launch("split_f16x2 (gemm pieces)");
 }
 
-// The same for a row-major [Kd, cols] source whose maximum |x| the caller already has as `npart` partial maxima on the
-// device (a producer kernel that folded them while writing X): no second pass over X for the scale.
+// The FIRST pieces of a row-major [Kd, cols] source whose maximum |x| the caller already has as `npart` partial maxima on the
+// device (a producer kernel that folded them while writing X): no second pass over X for the scale, and the lo plane is left
+// untouched (the consumers, the AWQ / clip searches' loss products, read first pieces only).
 int32_t make_f16x2_pieces_from_partials(const float* X, int64_t Kd, int64_t cols, int64_t ldx, const float* absmax_partials, int npart, void* pieces,
-                                        hipStream_t s, bool first_pieces_only) {
+                                        hipStream_t s) {
     OQ_REQUIRE(X && pieces && absmax_partials && npart > 0 && Kd > 0 && cols > 0 && (reinterpret_cast<uintptr_t>(pieces) & 255u) == 0, OQ_ERR_INVALID_ARGUMENT,
                "make_f16x2_pieces_from_partials: bad argument");
     float* scale = static_cast<float*>(pieces);
     u32x4* P = reinterpret_cast<u32x4*>(static_cast<unsigned char*>(pieces) + kScaleHeaderBytes);
-    const int64_t Cp = padded_k(cols), nstages = stages_of(Kd, StageGeom<3>::ROWS), nchunks = nstages * StageGeom<3>::CH;
+    const int64_t Cp = padded_k(cols), nstages = stages_of(Kd, F16Stage::ROWS), nchunks = nstages * F16Stage::CH;
     OQ_REQUIRE(ceil_div(nchunks, 4) <= 65535, OQ_ERR_UNSUPPORTED, "make_f16x2_pieces_from_partials: contraction too long (%lld)", (long long)Kd);
     hipLaunchKernelGGL(absmax_scale_kernel, dim3(1), dim3(256), 0, s, absmax_partials, npart, scale);
     hipLaunchKernelGGL(split_f16x2_kernel, dim3(static_cast<uint32_t>(Cp / 256), static_cast<uint32_t>(ceil_div(nchunks, 4))), dim3(256), 0, s, X, Kd, cols, ldx,
-                       Cp, nchunks, scale, first_pieces_only ? kSplitHiOnly : 0.0f, P);
+                       Cp, nchunks, scale, kSplitHiOnly, P);
     return check_launch("split_f16x2 (gemm pieces, given maxima)");
 }
 
 size_t gemm_f16x3_header_bytes() { return kScaleHeaderBytes; }
 int64_t gemm_f16x3_padded_cols(int64_t cols) { return padded_k(cols); }
-int64_t gemm_f16x3_chunks(int64_t Kd) { return stages_of(Kd, StageGeom<3>::ROWS) * StageGeom<3>::CH; }
+int64_t gemm_f16x3_chunks(int64_t Kd) { return stages_of(Kd, F16Stage::ROWS) * F16Stage::CH; }
 int32_t launch_gemm_f16x3(const void* pieces_a, const void* pieces_b, int64_t M, int64_t N, int64_t Kd, float alpha, float beta, float* C,
-                          int64_t ldc, float* loss_partial, hipStream_t s, bool hi_pieces_only, bool dot_with_c, bool b_first_piece_only,
-                          const float* row_unscale_a) {
+                          int64_t ldc, float* loss_partial, hipStream_t s, bool dot_with_c, const float* row_unscale_a) {
     OQ_REQUIRE(pieces_a && pieces_b && M > 0 && N > 0 && Kd > 0 && ((C != nullptr) != (loss_partial != nullptr) || dot_with_c), OQ_ERR_INVALID_ARGUMENT,
                "gemm_f16x3: bad argument");
-    OQ_REQUIRE(!hi_pieces_only || (loss_partial && !dot_with_c), OQ_ERR_INVALID_ARGUMENT, "gemm_f16x3: the one-product form exists for the sum-of-squares epilogue only");
     OQ_REQUIRE(!dot_with_c || (C && loss_partial && ldc >= N), OQ_ERR_INVALID_ARGUMENT, "gemm_f16x3: the dot epilogue reads C [M, N] and writes one partial per block");
     PieceGemm g;
     g.scale_a = static_cast<const float*>(pieces_a);
     g.scale_b = static_cast<const float*>(pieces_b);
     g.PA = reinterpret_cast<const u32x4*>(static_cast<const unsigned char*>(pieces_a) + kScaleHeaderBytes);
     g.PB = reinterpret_cast<const u32x4*>(static_cast<const unsigned char*>(pieces_b) + kScaleHeaderBytes);
-    g.M = M; g.N = N; g.Mp = padded_k(M); g.Np = padded_k(N); g.nstages = stages_of(Kd, StageGeom<3>::ROWS);
+    g.M = M; g.N = N; g.Mp = padded_k(M); g.Np = padded_k(N); g.nstages = stages_of(Kd, F16Stage::ROWS);
     g.alpha = alpha; g.beta = beta; g.C = C; g.ldc = ldc; g.partial = loss_partial;
     OQ_REQUIRE(row_unscale_a == nullptr || (C != nullptr && loss_partial == nullptr), OQ_ERR_INVALID_ARGUMENT, "gemm_f16x3: per-row scales exist for the store form only");
     g.row_unscale_a = row_unscale_a;
     const int64_t tiles = (g.Mp / kST) * (g.Np / kST);
     OQ_REQUIRE(tiles < (1 << 30), OQ_ERR_UNSUPPORTED, "gemm_f16x3: too many tiles");
-    const int lds_bytes = StageGeom<3>::LDS;
-    OQ_REQUIRE(!b_first_piece_only || dot_with_c, OQ_ERR_INVALID_ARGUMENT, "gemm_f16x3: the two-product form exists for the dot epilogue only");
-    if (dot_with_c && b_first_piece_only) {
+    const int lds_bytes = F16Stage::LDS;
+    if (dot_with_c) {          // two products: A with both pieces against B's first
         OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_kernel<2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess,
                    OQ_ERR_LAUNCH, "gemm_f16x3: cannot reserve %d bytes of LDS", lds_bytes);
         hipLaunchKernelGGL((gemm_f16x3_kernel<2, 2>), dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), lds_bytes, s, g);
-    } else if (dot_with_c) {
-        OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess,
-                   OQ_ERR_LAUNCH, "gemm_f16x3: cannot reserve %d bytes of LDS", lds_bytes);
-        hipLaunchKernelGGL(gemm_f16x3_kernel<2>, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), lds_bytes, s, g);
-    } else if (loss_partial && hi_pieces_only) {
+    } else if (loss_partial) {   // one product: the first pieces alone
         OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_kernel<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess,
                    OQ_ERR_LAUNCH, "gemm_f16x3: cannot reserve %d bytes of LDS", lds_bytes);
         hipLaunchKernelGGL((gemm_f16x3_kernel<1, 1>), dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), lds_bytes, s, g);
-    } else if (loss_partial) {
-        OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess,
-                   OQ_ERR_LAUNCH, "gemm_f16x3: cannot reserve %d bytes of LDS", lds_bytes);
-        hipLaunchKernelGGL(gemm_f16x3_kernel<1>, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), lds_bytes, s, g);
-    } else {
+    } else {                     // the store form: three products
         OQ_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x3_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess,
                    OQ_ERR_LAUNCH, "gemm_f16x3: cannot reserve %d bytes of LDS", lds_bytes);
         hipLaunchKernelGGL(gemm_f16x3_kernel<0>, dim3(static_cast<uint32_t>(tiles)), dim3(kSThreads), lds_bytes, s, g);

@@ -169,14 +169,18 @@ def test_c_program_quantizes_on_the_gpu(tmp_path):
 
 
 def test_shipped_library_has_no_attribution_switches():
-    """The shipped library has no experiment switches at all: its sources read no environment variable (the only `getenv`
-    calls sit behind `#ifdef OQ_SYRK_LAB`, which no shipped flag defines), the store-dropping RTN variants and the `nt`
-    argument that selected them are gone, and the build used by `__graft_entry__.build()` and the tests defines no lab macro."""
+    """The shipped library has no experiment switches at all: no file of its sources so much as mentions `getenv` (not even
+    behind an `#ifdef` or in a comment), the lab macros that once selected or tuned variants of the Hessian / piece-GEMM and AWQ
+    kernels are gone with the variants, the store-dropping RTN variants and the `nt` argument that selected them are gone, and
+    the build used by `__graft_entry__.build()` and the tests defines no lab macro."""
     from onnx_quantize_amd import _build
+    removed_macros = ("OQ_SYRK_LAB", "OQ_SYRK_F16_M16", "OQ_SYRK_SPLITS", "OQ_SYRK_F16_STRIDE", "OQ_SYRK_F16_STRIDE_EXPR", "OQ_SYRK_F16_DEEP",
+                      "OQ_SYRK_M16_STRIDE", "OQ_PREP_NT", "OQ_PREP_LOAD", "OQ_AWQ_HI_ONLY", "OQ_AWQ_FUSED_PIECES", "OQ_AWQ_GRAM_RATIO")
     for name in sorted(os.listdir(_build.SRC)):
         text = open(os.path.join(_build.SRC, name)).read()
-        shipped = re.sub(r"^#ifdef OQ_SYRK_LAB\b.*?^#endif", "", text, flags=re.S | re.M)
-        assert "getenv" not in shipped, name
+        assert "getenv" not in text, name
+        for macro in removed_macros:
+            assert macro not in text, (name, macro)
         assert "OQ_RTN_ATTRIBUTION" not in text and "OQ_ATTR(" not in text, name
         assert not re.search(r"\ba\.nt\b", text), name       # the field itself (`a.ntiles` of the ticketed kernels is another thing)
     for flag in _build.CXXFLAGS + [f for fl in _build.PER_FILE_FLAGS.values() for f in fl]:
