@@ -408,16 +408,8 @@ __global__ __launch_bounds__(160) void gptq_coef_image_kernel(const float* __res
     }
 }
 
-#ifdef OQ_LOOP_STAMPS   // lab builds only (python -m onnx_quantize_amd._build --define OQ_LOOP_STAMPS): s_memtime per phase
-__device__ unsigned long long g_loop_stamps[16];
-#define OQ_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_loop_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define OQ_STAMP(i) do {} while (0)
-#endif
-
 __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
     __shared__ float P[kCoefFloats];   // 64 KB
-    OQ_STAMP(0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r16 = lane & 15, c4 = lane >> 4;
     const int64_t c = (static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + wave) * 4 + c4;
@@ -440,7 +432,6 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
         const float x = a.Wt[(a.i1 - a.wt_row0 + (row < count ? row : count - 1)) * a.N + cc];
         if (k & 1) w2[k >> 1].y = x; else w2[k >> 1].x = x;
     }
-    OQ_STAMP(14);
     float scale;
     int32_t zp;
     if (a.i1 == 0) {  // gptq.py:104-116
@@ -469,7 +460,6 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
             for (int u = 0; u < kBatch; ++u) dst[idx[u]] = v[u];
         }
     }
-    OQ_STAMP(13);
     SlabIn in;
     in.cs = make_colstate(scale, zp);
     in.lo_m = static_cast<float>(a.grid.qmin) + kMagicF;
@@ -477,11 +467,8 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
     in.r16 = r16;
     int64_t grp = a.g > 0 ? a.i1 / a.g : 0;
     int64_t rem = a.g > 0 ? a.i1 - grp * a.g : 1;   // position of the slab's first row inside its group
-    OQ_STAMP(1);
     __builtin_amdgcn_s_waitcnt(0);   // vmcnt(0): this wave's LDS-DMAs have landed
-    OQ_STAMP(2);
     __syncthreads();
-    OQ_STAMP(3);
 
     for (int k0 = 0; k0 < nslabs; ++k0) {
         const int64_t row0 = a.i1 + 16 * k0;
@@ -550,7 +537,6 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
             a.err[(a.err_row0 + 16 * k0 + r16) * a.N + c] = save_e;
             a.q_deq[row * a.N + c] = (save_cl - in.cs.zm) * in.cs.scale;
         }
-        OQ_STAMP(4 + k0);
         // the next slab becomes slot 0
         w2[0] = f32x2{w2[0].y, w2[1].x};
         w2[1] = f32x2{w2[1].y, w2[2].x};
@@ -565,7 +551,6 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
         a.carry_scale[c] = scale;
         a.carry_zp[c] = zp;
     }
-    OQ_STAMP(12);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -908,9 +893,5 @@ int32_t oq_gptq_loop_f32(float* W, int64_t K, int64_t N, const float* U, int32_t
     }
     return OQ_OK;
 }
-
-#ifdef OQ_LOOP_STAMPS
-void oq_lab_loop_stamps(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(oq::g_loop_stamps), sizeof(unsigned long long) * 16); }
-#endif
 
 }  // extern "C"

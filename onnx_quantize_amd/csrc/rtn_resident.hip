@@ -18,20 +18,20 @@
 //   * the integers come out of the same registers with the exact-reciprocal fast path of the group kernels
 //     (oq_common.hpp), so they are the reference's bits by construction.
 //
-// `rtn_resident_groups`: channel and tall groups of up to 4096 rows.  The tiles of one range (one column tile x one
-// k-group) have consecutive tickets, are loaded at about the same time by different workgroups, and every one of them waits
-// for its siblings' partial ranges before it quantizes: one read of W, no second pass.
-// `rtn_resident_stream`: the same for taller ranges with persistent workgroups and two tile slots: a tile is published
-// into one slot before the workgroup waits for the range of the tile in the other one, and that tile's rows are stored
-// while the next tile's rows are loaded into their place.
-// `rtn_tensor_onepass`: per-tensor.  ONE 8-wave workgroup per CU.  Phase A streams all tiles once (running min / max in
-// registers, no barrier per tile beyond the ticket exchange) through one register slot; a workgroup KEEPS the last FOUR tiles
-// it loaded -- the slot, two tiles parked in its ACCUMULATION registers, one in 128 KB of LDS: 128 MB of the matrix stay on
-// the chip.  One returning add per workgroup counts the tiles and hands out an arrival slot for its partial range and the ids
-// of the tiles it keeps; the workgroup that completes the count folds the slots and broadcasts {go, keys}; kept tiles are
-// quantized from registers / LDS; the rows of the other half tiles are dealt out statically and evenly over all waves (no
-// tickets, no barriers), re-read most-recent-first and software-pipelined over the two halves of the slot.  A matrix of up
-// to 1024 tiles is read exactly once and skips that phase altogether.
+// In this file (entry point -> kernel -> helpers; each kernel's forward-progress argument stands in front of it):
+//   rtn_resident_eligible / rtn_resident_workspace   does this path take the call, and with how many bytes of state
+//   rtn_resident_impl -> ticket_chain_begin, rtn_resident_launch, ticket_chain_end   (the launches of one device form a chain)
+//   rtn_resident_launch -> groups_streamed / groups_tile_rows pick the kernel:
+//     rtn_resident_groups<8 | 16>   channel and tall groups of up to 4096 rows: one workgroup = one ticket = one tile of 128 or
+//                                   256 rows, which waits for its siblings' partial ranges before it quantizes
+//     rtn_resident_stream           taller ranges, or >= 1024 tiles: persistent workgroups with two tile slots
+//                                   -> stream_step -> stream_tile, stream_fold_local, stream_publish_wave, stream_keys,
+//                                      stream_params, stream_rows
+//     rtn_tensor_onepass            per-tensor: one workgroup per CU keeps the last four tiles it loaded on the chip
+//                                   -> acc_put_half / acc_get_half (the parks), tile4_origin
+//     clear_words_kernel            zeroes the state of a call that brought none
+//   shared by the kernels: the ordered keys and agent-scope atomics, spin_until, clean_state, load_tile, store_q_word,
+//   quantize_store_tile (K1 from registers)
 #include "rtn_internal.hpp"
 
 #include <mutex>
@@ -50,12 +50,8 @@ constexpr int kResMaxTensorTiles = 32768;         // bitmap of kept half tiles +
 constexpr int kResTensorHeader = 128 + 64 * 32 + 64 * 32;   // tickets / counter, 512 arrival slots of 16 bytes, 64 result replicas (a 128-byte line each)
 constexpr int kResGroupTileRows = 128;            // tile height of rtn_resident_stream and of rtn_resident_groups<8> (see groups_tile_rows)
 constexpr int kResCtrPad = 32;                   // uint32 words per range counter: a 128-byte line each (hundreds of workgroups poll them)
-#ifndef OQ_RES_A_NT
-#define OQ_RES_A_NT false   /* default-policy loads in phase A keep the lines in the Infinity Cache for phase B: 75 us against 78 with nt */
-#endif
-#ifndef OQ_RES_SLEEP
-#define OQ_RES_SLEEP 8   /* s_sleep between two polls of a counter */
-#endif
+constexpr bool kResPhaseANt = false;             // default-policy loads in phase A keep the lines in the Infinity Cache for phase B: 75 us against 78 with nt
+constexpr int kResSleep = 8;                      // s_sleep between two polls of a counter
 
 struct ResidentArgs {
     const float* W;
@@ -65,13 +61,11 @@ struct ResidentArgs {
     float* scale;
     uint8_t* zp;
     QGrid grid;
-    int32_t layout;
     uint32_t ncol_tiles, ntiles;
     uint32_t* key_max;    // groups: [slots] ordered key of the running maximum; tensor: the arrival slots (16 bytes per workgroup)
     uint32_t* key_nmin;   // groups: [slots] complement of the ordered key of the running minimum (kept as a maximum); tensor: the replica lines
     uint32_t* counters;   // groups: one per (column tile, k-group); tensor: [0] = tiles counted + arrivals
     uint32_t* tickets;    // [0]
-    uint32_t* held;       // unused since the kept tiles travel in the arrival slots (kept for the layout of the workspace)
     // Self-cleaning (oq_rtn_quantize_stateful_f32: the caller's `state` is zero when the call starts and zero again when it
     // ends, so no clear launch runs in front of the kernel): every workgroup counts itself out at `done`; the cleaner --
     // the one that holds the last ticket / ticket 0 -- waits for all the others and zeroes [clean_base, +clean_words).
@@ -114,12 +108,12 @@ __device__ uint32_t g_spin_timeouts;
 __device__ __forceinline__ void spin_until(const uint32_t* p, uint32_t target) {
     for (uint32_t i = 0; agent_load(p) < target; ++i) {
         if (i >= static_cast<uint32_t>(OQ_SPIN_LIMIT)) { atomicAdd(&g_spin_timeouts, 1u); return; }
-        __builtin_amdgcn_s_sleep(OQ_RES_SLEEP);
+        __builtin_amdgcn_s_sleep(kResSleep);
     }
 }
 #else
 __device__ __forceinline__ void spin_until(const uint32_t* p, uint32_t target) {
-    while (agent_load(p) < target) __builtin_amdgcn_s_sleep(OQ_RES_SLEEP);
+    while (agent_load(p) < target) __builtin_amdgcn_s_sleep(kResSleep);
 }
 #endif
 
@@ -151,96 +145,60 @@ __device__ __forceinline__ void load_tile(const ResidentArgs& a, int64_t row0, i
     }
 }
 
-// One dword of quantized bytes to HBM.  OQ_RES_STORE (lab): 0 = `nt` (streaming, but write-BACK: the lines stay dirty in the XCD's L2
-// until they are evicted or the kernel ends), 1 = default policy, 2 = `sc1` (agent scope: written through), 3 = `sc0 sc1`, 4 = `sc1 nt`,
-// 5 = `sc0 sc1 nt`.
-#ifndef OQ_RES_STORE
-#define OQ_RES_STORE 0
-#endif
-__device__ __forceinline__ void store_q_word(uint32_t w, uint32_t* p) {
-#if OQ_RES_STORE == 0
-    __builtin_nontemporal_store(w, p);
-#elif OQ_RES_STORE == 1
-    *p = w;
-#elif OQ_RES_STORE == 2
-    asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(w) : "memory");
-#elif OQ_RES_STORE == 3
-    asm volatile("global_store_dword %0, %1, off sc0 sc1" : : "v"(p), "v"(w) : "memory");
-#elif OQ_RES_STORE == 4
-    asm volatile("global_store_dword %0, %1, off sc1 nt" : : "v"(p), "v"(w) : "memory");
-#else
-    asm volatile("global_store_dword %0, %1, off sc0 sc1 nt" : : "v"(p), "v"(w) : "memory");
-#endif
-}
+// One dword of quantized bytes to HBM: `nt` (streaming, but write-BACK: the lines stay dirty in the XCD's L2 until they are
+// evicted or the kernel ends).  The five other store forms that were tried are in docs/LAB_NOTES_r13.md.
+__device__ __forceinline__ void store_q_word(uint32_t w, uint32_t* p) { __builtin_nontemporal_store(w, p); }
 
-// K1 from registers + [K, N] byte stores (one dword = a lane's four columns of a row).
-// GROUP > 1 (the kernels that run one or two waves per SIMD and so have nobody to fill the bubbles): the fast path of GROUP rows
-// as independent chains with ONE decision behind them -- |t - k| of every element folded into a running NaN-propagating maximum
-// on the vector ALU (v_maximum3_f32 with |.| modifiers: half an instruction per element) and compared once with the narrowest
-// band of the lane's four columns, instead of a compare + scalar OR per element and a ballot + branch per row.  (The packed
-// "magic number" form of rtn.hip's wave kernel was tried here: 65.1 -> 70.3 us per call, packed fp32 runs at half rate.)
-template <int ROWS = kResRows, int GROUP = 1>
+// K1 from registers + [K, N] byte stores (one dword = a lane's four columns of a row).  These kernels run one or two waves per
+// SIMD and so have nobody to fill the bubbles: the fast path takes GROUP rows as independent chains with ONE decision behind
+// them -- |t - k| of every element folded into a running NaN-propagating maximum on the vector ALU (v_maximum3_f32 with |.|
+// modifiers: half an instruction per element) and compared once with the narrowest band of the lane's four columns, instead of
+// a compare + scalar OR per element and a ballot + branch per row.  (The packed "magic number" form of rtn.hip's wave kernel
+// was tried here: 65.1 -> 70.3 us per call, packed fp32 runs at half rate.)
+//
+// In the "magic number" domain of rtn.hip's wave kernel: with M = 1.5 * 2^23 the fp32 grid around M + k has spacing 1, so
+// u = fma(x, rinv, zp + bias + M) IS M + rint(x * rinv + zp + bias) -- product, zero point and rounding in one correctly
+// rounded operation -- and res = fma(x, rinv, (zp + bias + M) - u) is the distance of x * rinv + zp from that integer,
+// exact but for one rounding of <= 2^-25: |res| inside the band proves the integer the reference's, everything else (ties,
+// NaN, inf, sums beyond the grid) is redone with the IEEE division.  The level is byte 0 of the clamped float's bits.
+// fma, sub, fma, half a v_maximum3, med3 and 3/4 of a byte permute per element: 5.25 instructions against 6.5.
+template <int ROWS, int GROUP>
 __device__ __forceinline__ void quantize_store_tile(const ResidentArgs& a, const ColQ (&cq)[4], float (&v)[ROWS][4], int64_t row0,
                                                     int64_t row_end, int64_t tile_col0, int lane) {
+    static_assert(GROUP > 1 && ROWS % GROUP == 0, "whole groups of at least two rows");
+    constexpr float kMagic = 12582912.0f;          // 1.5 * 2^23, bits 0x4B400000
     const int32_t qmin = a.grid.qmin, qmax = a.grid.qmax;
     const int32_t bias = qmin < 0 ? 128 : 0;
     const float lo_b = static_cast<float>(qmin + bias), hi_b = static_cast<float>(qmax + bias);
     const uint32_t flip = bias ? 0x80808080u : 0u;
     const bool col_ok = tile_col0 + lane * 4 < a.N;
     uint8_t* o = a.q + row0 * a.N + tile_col0 + lane * 4;
-    if constexpr (GROUP == 1) {
+    const float thr_min = nmin(nmin(cq[0].thr, cq[1].thr), nmin(cq[2].thr, cq[3].thr));   // the narrowest band of the four columns: never less careful
+    const float zm[4] = {cq[0].zpb + kMagic, cq[1].zpb + kMagic, cq[2].zpb + kMagic, cq[3].zpb + kMagic};
+    const float lo_m = lo_b + kMagic, hi_m = hi_b + kMagic;
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            float f[4];
-            bool unsafe = false;
+    for (int rg = 0; rg < ROWS; rg += GROUP) {
+        uint32_t f[GROUP][4];
+        float far = 0.0f;          // the largest |res| of the group, NaN if any
 #pragma unroll
-            for (int i = 0; i < 4; ++i) f[i] = quantize_fast_biased(v[r][i], cq[i], lo_b, hi_b, unsafe);
-            if (__builtin_amdgcn_ballot_w64(unsafe) != 0) {   // wave-uniform, rare: redo this row with the IEEE divide
+        for (int r = 0; r < GROUP; ++r)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) f[i] = quantize_exact_biased(v[r][i], cq[i], qmin, qmax, bias);
+            for (int i = 0; i < 4; ++i) {
+                const float u = __builtin_fmaf(v[rg + r][i], cq[i].rinv, zm[i]);
+                const float res = __builtin_fmaf(v[rg + r][i], cq[i].rinv, zm[i] - u);
+                far = nmax(far, fabsf(res));
+                f[r][i] = __float_as_uint(__builtin_amdgcn_fmed3f(u, lo_m, hi_m));
             }
-            uint32_t w = __builtin_amdgcn_cvt_pk_u8_f32(f[0], 0, 0);
-            w = __builtin_amdgcn_cvt_pk_u8_f32(f[1], 1, w);
-            w = __builtin_amdgcn_cvt_pk_u8_f32(f[2], 2, w);
-            w = __builtin_amdgcn_cvt_pk_u8_f32(f[3], 3, w);
-            if (col_ok && row0 + r < row_end) store_q_word(w ^ flip, reinterpret_cast<uint32_t*>(o + r * a.N));
-        }
-    } else {
-        // In the "magic number" domain of rtn.hip's wave kernel: with M = 1.5 * 2^23 the fp32 grid around M + k has spacing 1, so
-        // u = fma(x, rinv, zp + bias + M) IS M + rint(x * rinv + zp + bias) -- product, zero point and rounding in one correctly
-        // rounded operation -- and res = fma(x, rinv, (zp + bias + M) - u) is the distance of x * rinv + zp from that integer,
-        // exact but for one rounding of <= 2^-25: |res| inside the band proves the integer the reference's, everything else (ties,
-        // NaN, inf, sums beyond the grid) is redone with the IEEE division.  The level is byte 0 of the clamped float's bits.
-        // fma, sub, fma, half a v_maximum3, med3 and 3/4 of a byte permute per element: 5.25 instructions against 6.5.
-        static_assert(ROWS % GROUP == 0, "whole groups");
-        constexpr float kMagic = 12582912.0f;          // 1.5 * 2^23, bits 0x4B400000
-        const float thr_min = nmin(nmin(cq[0].thr, cq[1].thr), nmin(cq[2].thr, cq[3].thr));   // the narrowest band of the four columns: never less careful
-        const float zm[4] = {cq[0].zpb + kMagic, cq[1].zpb + kMagic, cq[2].zpb + kMagic, cq[3].zpb + kMagic};
-        const float lo_m = lo_b + kMagic, hi_m = hi_b + kMagic;
-#pragma unroll
-        for (int rg = 0; rg < ROWS; rg += GROUP) {
-            uint32_t f[GROUP][4];
-            float far = 0.0f;          // the largest |res| of the group, NaN if any
+        if (__builtin_amdgcn_ballot_w64(!(far < thr_min)) != 0) {   // wave-uniform, rare: redo these rows with the IEEE divide
 #pragma unroll
             for (int r = 0; r < GROUP; ++r)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float u = __builtin_fmaf(v[rg + r][i], cq[i].rinv, zm[i]);
-                    const float res = __builtin_fmaf(v[rg + r][i], cq[i].rinv, zm[i] - u);
-                    far = nmax(far, fabsf(res));
-                    f[r][i] = __float_as_uint(__builtin_amdgcn_fmed3f(u, lo_m, hi_m));
-                }
-            if (__builtin_amdgcn_ballot_w64(!(far < thr_min)) != 0) {   // wave-uniform, rare: redo these rows with the IEEE divide
+                for (int i = 0; i < 4; ++i) f[r][i] = static_cast<uint32_t>(quantize_one(v[rg + r][i], cq[i].scale, cq[i].zp, qmin, qmax) + bias);
+        }
 #pragma unroll
-                for (int r = 0; r < GROUP; ++r)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) f[r][i] = static_cast<uint32_t>(quantize_one(v[rg + r][i], cq[i].scale, cq[i].zp, qmin, qmax) + bias);
-            }
-#pragma unroll
-            for (int r = 0; r < GROUP; ++r) {
-                const uint32_t w = __builtin_amdgcn_perm(f[r][1], f[r][0], 0x0c0c0400u) | __builtin_amdgcn_perm(f[r][3], f[r][2], 0x04000c0cu);   // byte 0 of each
-                if (col_ok && row0 + rg + r < row_end) store_q_word(w ^ flip, reinterpret_cast<uint32_t*>(o + (rg + r) * a.N));
-            }
+        for (int r = 0; r < GROUP; ++r) {
+            const uint32_t w = __builtin_amdgcn_perm(f[r][1], f[r][0], 0x0c0c0400u) | __builtin_amdgcn_perm(f[r][3], f[r][2], 0x04000c0cu);   // byte 0 of each
+            if (col_ok && row0 + rg + r < row_end) store_q_word(w ^ flip, reinterpret_cast<uint32_t*>(o + (rg + r) * a.N));
         }
     }
 }
@@ -256,11 +214,10 @@ __device__ __forceinline__ void quantize_store_tile(const ResidentArgs& a, const
 // chunks <= 128 against 256 CUs) the missing tickets are always taken, loaded and published without waiting, and R
 // completes.  Workgroups that are not resident yet hold no ticket and nobody waits for them.
 // ---------------------------------------------------------------------------------------------
-#ifndef OQ_GROUPS_GROUP
-#define OQ_GROUPS_GROUP 2   /* rows per decision of K1 (quantize_store_tile): 4096 x 4096 int8 per channel 27.7 us with 1, 26.6 with 2, 26.9-27.9 with 4 (<= 128 registers) */
-#endif
-template <int WAVES, int ROWS, int WPS>
-__global__ __launch_bounds__(WAVES* kWave, WPS) void rtn_resident_groups(const ResidentArgs a) {
+constexpr int kGroupsGroup = 2;   // rows per decision of K1 (quantize_store_tile): 4096 x 4096 int8 per channel 27.7 us with 1, 26.6 with 2, 26.9-27.9 with 4 (<= 128 registers)
+template <int WAVES>
+__global__ __launch_bounds__(WAVES* kWave, 4) void rtn_resident_groups(const ResidentArgs a) {
+    constexpr int ROWS = kResRows;
     constexpr int kTileRows = WAVES * ROWS;
     __shared__ float4 s_mn[WAVES][kWave];
     __shared__ float4 s_mx[WAVES][kWave];
@@ -354,7 +311,7 @@ __global__ __launch_bounds__(WAVES* kWave, WPS) void rtn_resident_groups(const R
             }
         }
     }
-    quantize_store_tile<ROWS, OQ_GROUPS_GROUP>(a, cq, v, row0, row_end, tile_col0, lane);
+    quantize_store_tile<ROWS, kGroupsGroup>(a, cq, v, row0, row_end, tile_col0, lane);
     if (a.done != nullptr) {   // uniform
         // every state access of this workgroup is complete (its key loads returned, its counter add was seen by its own poll)
         if (t + 1u == a.ntiles) clean_state(a, a.ntiles - 1u, WAVES * kWave);
@@ -380,16 +337,6 @@ __global__ __launch_bounds__(WAVES* kWave, WPS) void rtn_resident_groups(const R
 // chunks against 3/4 of the workgroups the device holds) R completes.  Workgroups that are not resident yet hold no ticket
 // and nobody waits for them.
 // ---------------------------------------------------------------------------------------------
-#ifdef OQ_TENSOR_STAMPS   // lab build only (scripts/lab_tensor_stamps.py): 100 MHz wall-clock stamps of every workgroup's phases
-__device__ uint64_t g_tensor_stamps[512 * 8];
-#define OQ_STAMP(i) do { if (threadIdx.x == 0) g_tensor_stamps[blockIdx.x * 8 + (i)] = wall_clock64(); } while (0)
-// accumulate the time since *T0 into counter i and restart the clock (stream kernel: per-phase sums over a workgroup's tiles)
-#define OQ_LAP(i, T0) do { if (threadIdx.x == 0) { const uint64_t now_ = wall_clock64(); g_tensor_stamps[blockIdx.x * 8 + (i)] += now_ - (T0); (T0) = now_; } } while (0)
-#else
-#define OQ_STAMP(i) do { } while (0)
-#define OQ_LAP(i, T0) do { } while (0)
-#endif
-
 struct StreamTile {          // everything uniform over the workgroup except slot0 / col_ok
     uint32_t range, c, kg;
     int64_t row0, row_end, tile_col0, slot0;
@@ -493,16 +440,15 @@ __device__ __forceinline__ void stream_params(const ResidentArgs& a, const Strea
     }
 }
 
-// Quantize and store the tile in `v` in groups of OQ_STREAM_GROUP rows, each group's registers refilled at once with the same rows
-// of tile `n` (when `refill`): the CU's loads run beside its stores instead of after them.  K1 as in quantize_store_tile's grouped
-// form: the magic-number domain, one decision per group on a running v_maximum3 of the residuals (per row with a compare and a
-// scalar OR per element until round 6: 62.1-64.5 -> 60.9-61.9 us per call on 4096 x 11008).
-#ifndef OQ_STREAM_GROUP
-#define OQ_STREAM_GROUP 4
-#endif
+// Quantize and store the tile in `v` in groups of kStreamGroup rows, each group's registers refilled at once with the same rows
+// of tile `n` (when `refill`): the CU's loads run beside its stores instead of after them.  K1 as in quantize_store_tile,
+// with which it shares everything but the refill (left duplicated: docs/LAB_NOTES_r13.md): the magic-number domain, one decision
+// per group on a running v_maximum3 of the residuals (per row with a compare and a scalar OR per element until round 6:
+// 62.1-64.5 -> 60.9-61.9 us per call on 4096 x 11008).
+constexpr int kStreamGroup = 4;
 __device__ __forceinline__ void stream_rows(const ResidentArgs& a, const StreamTile& s, const ColQ (&cq)[4], bool refill, const StreamTile& n,
                                             int lane, float (&v)[kResRows][4]) {
-    constexpr int GROUP = OQ_STREAM_GROUP;
+    constexpr int GROUP = kStreamGroup;
     static_assert(kResRows % GROUP == 0, "whole groups");
     constexpr float kMagic = 12582912.0f;          // 1.5 * 2^23
     const int32_t qmin = a.grid.qmin, qmax = a.grid.qmax;
@@ -560,7 +506,7 @@ __device__ __forceinline__ void stream_rows(const ResidentArgs& a, const StreamT
 // flight and unpublished: the roles swap.  Returns X's new ticket (>= ntiles: the slot is empty).
 __device__ __forceinline__ uint32_t stream_step(const ResidentArgs& a, uint32_t tx, float (&vx)[kResRows][4], bool y_valid, uint32_t ty,
                                                 float (&vy)[kResRows][4], int lane, int wave, float4 (&s_mn)[kResWaves][kWave],
-                                                float4 (&s_mx)[kResWaves][kWave], uint32_t& s_ticket, uint32_t& s_flag, uint64_t& lap0) {
+                                                float4 (&s_mx)[kResWaves][kWave], uint32_t& s_ticket, uint32_t& s_flag) {
     const StreamTile sx = stream_tile(a, tx, lane, wave);
     const StreamTile sy = stream_tile(a, y_valid ? ty : tx, lane, wave);
     const uint32_t chunks = static_cast<uint32_t>(a.chunks);
@@ -578,7 +524,6 @@ __device__ __forceinline__ uint32_t stream_step(const ResidentArgs& a, uint32_t 
         if (threadIdx.x == kWave) spin_until(a.counters + sx.range * kResCtrPad, chunks);
         __syncthreads();
     }
-    OQ_LAP(1, lap0);
     uint32_t pending = 0;
     if (threadIdx.x == 0) pending = agent_add(a.tickets, 1u);     // behind every wait of this step; its tile is published before the next one
     uint32_t kmx[4], kmn[4];
@@ -588,20 +533,14 @@ __device__ __forceinline__ uint32_t stream_step(const ResidentArgs& a, uint32_t 
         __syncthreads();
         if (wave == 0) stream_publish_wave(a, sy, lane, s_mn, s_mx);
     }
-    OQ_LAP(4, lap0);
     ColQ cq[4];
     stream_params(a, sx, lane, wave, kmx, kmn, cq);
     if (threadIdx.x == 0) s_ticket = pending;
     __syncthreads();
     const uint32_t tn = s_ticket;     // the next write of s_ticket lies behind the first barrier of the next step
-    OQ_LAP(2, lap0);
     const bool refill = tn < a.ntiles;                         // uniform
     const StreamTile n = stream_tile(a, refill ? tn : tx, lane, wave);
     stream_rows(a, sx, cq, refill, n, lane, vx);
-    OQ_LAP(3, lap0);
-#ifdef OQ_TENSOR_STAMPS
-    if (threadIdx.x == 0) g_tensor_stamps[blockIdx.x * 8 + 6] += 1;
-#endif
     return tn;
 }
 
@@ -613,13 +552,6 @@ __global__ __launch_bounds__(kResWaves* kWave, 2) void rtn_resident_stream(const
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const uint32_t ntiles = a.ntiles;
     float v0[kResRows][4], v1[kResRows][4];
-    uint64_t lap0 = 0;
-#ifdef OQ_TENSOR_STAMPS
-    if (threadIdx.x < 8) g_tensor_stamps[blockIdx.x * 8 + threadIdx.x] = 0;
-    __syncthreads();
-    lap0 = wall_clock64();
-    const uint64_t kernel_t0 = lap0;
-#endif
     if (threadIdx.x == 0) s_ticket = agent_add(a.tickets, 1u);
     __syncthreads();
     uint32_t ta = s_ticket, tb = ntiles;
@@ -642,15 +574,11 @@ __global__ __launch_bounds__(kResWaves* kWave, 2) void rtn_resident_stream(const
             const StreamTile s = stream_tile(a, tb, lane, wave);
             load_tile<true>(a, s.row0 < s.row_end ? s.row0 : s.row_end - 1, s.row_end, s.tile_col0, lane, v1);
         }
-        OQ_LAP(0, lap0);
-        while (ta < ntiles || tb < ntiles) {
-            if (ta < ntiles) ta = stream_step(a, ta, v0, tb < ntiles, tb, v1, lane, wave, s_mn, s_mx, s_ticket, s_flag, lap0);
-            if (tb < ntiles) tb = stream_step(a, tb, v1, ta < ntiles, ta, v0, lane, wave, s_mn, s_mx, s_ticket, s_flag, lap0);
+            while (ta < ntiles || tb < ntiles) {
+            if (ta < ntiles) ta = stream_step(a, ta, v0, tb < ntiles, tb, v1, lane, wave, s_mn, s_mx, s_ticket, s_flag);
+            if (tb < ntiles) tb = stream_step(a, tb, v1, ta < ntiles, ta, v0, lane, wave, s_mn, s_mx, s_ticket, s_flag);
         }
     }
-#ifdef OQ_TENSOR_STAMPS
-    if (threadIdx.x == 0) g_tensor_stamps[blockIdx.x * 8 + 5] = wall_clock64() - kernel_t0;
-#endif
     if (a.done != nullptr) {   // uniform; `first` = the workgroup that took ticket 0 (it always exists)
         if (first) clean_state(a, gridDim.x - 1u, kResWaves * kWave);
         else if (threadIdx.x == 0) agent_add(a.done, 1u);
@@ -667,10 +595,8 @@ __global__ __launch_bounds__(kResWaves* kWave, 2) void rtn_resident_stream(const
 // taken by a running workgroup that reaches its add without waiting for anybody, so the wait ends whatever the number of
 // resident workgroups is; a workgroup that starts late finds no ticket, adds nothing and waits like the others.  Phase B
 // never waits either.
-// ---------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------------
-// rtn_tensor_onepass: per-tensor, W read once where the chip can hold it and 1.26 times on 4096 x 11008.
 //
+// W is read once where the chip can hold it and 1.26 times on 4096 x 11008.
 // ONE 8-wave workgroup per CU (two waves per SIMD: 256 registers per lane each, which a kernel that names accumulation registers
 // gets as 128 architectural + 128 accumulation registers).  A tile is 128 x 256 = 16 rows per wave = 64 registers per lane.
 // Phase A streams all tiles once (tickets; running min / max in registers) through ONE register slot V; in front of every load
@@ -686,20 +612,16 @@ __global__ __launch_bounds__(kResWaves* kWave, 2) void rtn_resident_stream(const
 // registers / LDS; the rows of the other half tiles are dealt out statically and evenly over all waves (no tickets, no
 // barriers), re-read most-recent-first and software-pipelined over the two halves of V.
 //
-// The same with ONE wave per SIMD (4-wave workgroups, 32 rows per wave, 256 + 256 registers) streams phase A just as fast but
-// needs 6.8 us instead of 2.3 to quantize and store a tile -- a single wave per SIMD has nobody to fill its bubbles --: 80.4-87.5 us.
-// The template parameter is kept for that measurement; only <8> is instantiated.
+// The same with ONE wave per SIMD (4-wave workgroups, 32 rows per wave, 256 + 256 registers) streamed phase A just as fast but
+// needed 6.8 us instead of 2.3 to quantize and store a tile -- a single wave per SIMD has nobody to fill its bubbles --: 80.4-87.5 us.
 // ---------------------------------------------------------------------------------------------
 constexpr int kHalfRows = kResTileRows / 2;                      // phase-B unit: half a tile, 64 rows x 256 columns
 constexpr int kParkBytes = kResWaves * kResRows * kWave * 16;    // one tile: 128 KB
 constexpr uint32_t kNoTile = 0xFFFFFFFFu;
-#ifndef OQ_T4_GROUP
-#define OQ_T4_GROUP 4   /* rows per decision of the quantize + store code (quantize_store_tile) */
-#endif
+constexpr int kTensorGroup = 4;                       // rows per decision of the quantize + store code (quantize_store_tile)
 constexpr uint32_t kT4MaxTiles = 32766;               // the fourth kept tile travels as tile + 1 in 15 bits of its arrival slot
 
-// The parks are PHYSICAL accumulation registers named in the assembly text: a[0..63] and a[64..127] (a[0..127] and a[128..255] in
-// the one-wave-per-SIMD form).  As operands of the `a` register class they went through the register allocator, which copied them
+// The parks are PHYSICAL accumulation registers named in the assembly text: a[0..63] and a[64..127].  As operands of the `a` register class they went through the register allocator, which copied them
 // at every join of the control flow: 738 v_accvgpr_mov and 1.2 KB of scratch per lane.  Named like this the compiler does not
 // know that they hold anything -- and it does place values of its own in a0, a1, ... once a kernel that names accumulation
 // registers runs out of architectural ones (128 here).  So the kernel is written to stay below that: V is loaded at ONE place of
@@ -727,20 +649,18 @@ __device__ __forceinline__ void acc_get_half(float (&v)[HR][4]) {
     }
 }
 
-template <int ROWS>
 __device__ __forceinline__ void tile4_origin(uint32_t tile, uint32_t ncol, int wave, int64_t& row0, int64_t& col0) {
     const uint32_t row_tile = tile / ncol, col_tile = tile - row_tile * ncol;
-    row0 = static_cast<int64_t>(row_tile) * kResTileRows + wave * ROWS;
+    row0 = static_cast<int64_t>(row_tile) * kResTileRows + wave * kResRows;
     col0 = static_cast<int64_t>(col_tile) * kResCols;
 }
 
-template <int WAVES>
-__global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(const ResidentArgs a) {
-    constexpr int ROWS = kResTileRows / WAVES;        // rows per wave: 32 (one wave per SIMD) or 16 (two)
+__global__ __launch_bounds__(kResWaves* kWave, 2) void rtn_tensor_onepass(const ResidentArgs a) {
+    constexpr int WAVES = kResWaves, ROWS = kResRows;
     constexpr int HR = ROWS / 2;                      // V is two halves
     constexpr int THREADS = WAVES * kWave;
     constexpr int A0 = 0, A1 = ROWS * 4;              // first accumulation register of the two parks
-    constexpr int GROUP = OQ_T4_GROUP;
+    constexpr int GROUP = kTensorGroup;
     extern __shared__ __attribute__((aligned(16))) unsigned char park_lds[];   // kParkBytes: [wave][row of the wave][lane 64] x 16 B
     __shared__ float s_mn[WAVES], s_mx[WAVES];
     __shared__ uint32_t s_ticket, s_keys[3], s_wsum[WAVES];
@@ -750,15 +670,10 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
     const uint32_t ntiles = a.ntiles, ncol = a.ncol_tiles, nunits = 2u * ntiles;
     float4* park = reinterpret_cast<float4*>(park_lds) + (wave * ROWS) * kWave + lane;   // this lane's slot of row 0
 
-    float v[2][HR][4];                          // V: two halves of 16 rows
-    if constexpr (WAVES == 4) asm volatile("" : : : "a0", "a255");   // the descriptor reserves the two parks (see acc_put_half): a[0..255]
-    else asm volatile("" : : : "a0", "a127");                        // a[0..127]
+    float v[2][HR][4];                          // V: two halves of 8 rows
+    asm volatile("" : : : "a0", "a127");        // the descriptor reserves the two parks (see acc_put_half): a[0..127]
     float rmn = INFINITY, rmx = -INFINITY;
     uint32_t processed = 0, idV = kNoTile, idA0 = kNoTile, idA1 = kNoTile, idL = kNoTile;
-#ifdef OQ_TENSOR_STAMPS
-    if (threadIdx.x == 0) g_tensor_stamps[blockIdx.x * 8 + 7] = g_tensor_stamps[blockIdx.x * 8 + 5];   // the end of the previous call
-#endif
-    OQ_STAMP(0);
     if (threadIdx.x == 0) s_ticket = agent_add(a.tickets, 1u);
     __syncthreads();
     uint32_t t = s_ticket;
@@ -771,10 +686,10 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
         if (threadIdx.x == 0) s_ticket = agent_add(a.tickets, 1u);
         idV = t;
         int64_t row0, col0;
-        tile4_origin<ROWS>(t, ncol, wave, row0, col0);
+        tile4_origin(t, ncol, wave, row0, col0);
         const int64_t r_hi = row0 + HR;
-        load_tile<OQ_RES_A_NT, HR>(a, row0 < a.K ? row0 : a.K - 1, a.K, col0, lane, v[0]);
-        load_tile<OQ_RES_A_NT, HR>(a, r_hi < a.K ? r_hi : a.K - 1, a.K, col0, lane, v[1]);
+        load_tile<kResPhaseANt, HR>(a, row0 < a.K ? row0 : a.K - 1, a.K, col0, lane, v[0]);
+        load_tile<kResPhaseANt, HR>(a, r_hi < a.K ? r_hi : a.K - 1, a.K, col0, lane, v[1]);
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -815,13 +730,9 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
         }
         load_fold();
     }
-    // Publish: as rtn_tensor_onepass (one returning add per workgroup, one 16-byte arrival slot, the last finisher folds the
-    // slots and broadcasts {go, keys} to 64 replica lines).  The slot names up to four kept tiles.
+    // Publish: one returning add per workgroup, one 16-byte arrival slot; the last finisher folds the slots and broadcasts
+    // {go, keys} to 64 replica lines.  The slot names up to four kept tiles.
     uint32_t* replica = a.key_nmin + (blockIdx.x & 63u) * 32u;
-    OQ_STAMP(1);
-#ifdef OQ_TENSOR_STAMPS
-    if (threadIdx.x == 0) g_tensor_stamps[blockIdx.x * 8 + 6] = processed;
-#endif
     if (processed) {
         rmn = wave_min(rmn);
         rmx = wave_max(rmx);
@@ -873,14 +784,13 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
         u32x4r line;
         do {
             asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(line) : "v"(replica) : "memory");
-            if (line[0] == 0u) __builtin_amdgcn_s_sleep(OQ_RES_SLEEP);
+            if (line[0] == 0u) __builtin_amdgcn_s_sleep(kResSleep);
         } while (line[0] == 0u);
         s_keys[0] = line[1];
         s_keys[1] = line[2];
         s_keys[2] = line[3];
     }
     __syncthreads();
-    OQ_STAMP(2);
     const bool any_dropped = (s_keys[2] & 0x80000000u) != 0u;      // uniform over the grid
     u32x4r my_slot = {0u, 0u, 0u, 0u};
     if (any_dropped && threadIdx.x < (s_keys[2] & 0x7fffffffu))
@@ -912,14 +822,12 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
     }
     if (idV != kNoTile) {   // uniform
         int64_t row0, col0;
-        tile4_origin<ROWS>(idV, ncol, wave, row0, col0);
+        tile4_origin(idV, ncol, wave, row0, col0);
         quantize_store_tile<HR, GROUP>(a, cq, v[0], row0, a.K, col0, lane);
         quantize_store_tile<HR, GROUP>(a, cq, v[1], row0 + HR, a.K, col0, lane);
     }
-    OQ_STAMP(3);
-    // Phase B: as rtn_tensor_onepass (the rows of the unheld halves, most recently read first, dealt out statically and evenly
-    // over all waves of the grid), pipelined over the two halves of V; the first step's loads are issued before the parked
-    // tiles are stored.
+    // Phase B: the rows of the unheld halves, most recently read first, dealt out statically and evenly over all waves of the
+    // grid, pipelined over the two halves of V; the first step's loads are issued before the parked tiles are stored.
     // Once every wave has its slot this workgroup has read the state for the last time: it counts itself out HERE, not at its
     // end, so that the cleaner finds the count complete when it gets there and the zeroing hides behind the others' phase B.
     if (any_dropped) {
@@ -966,7 +874,6 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
     } else if (a.done != nullptr && !first && threadIdx.x == 0) {
         agent_add(a.done, 1u);                             // the replica line was this workgroup's last read of the state
     }
-    OQ_STAMP(4);
     int64_t a_row0 = 0, a_end = 0, a_col0 = 0, b_row0 = 0, b_end = 0, b_col0 = 0;
     auto next_step = [&](int64_t& row0, int64_t& row_end, int64_t& col0) -> bool {
         while (pos < stop) {
@@ -998,7 +905,7 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
     if (a_live) load_tile<true, HR>(a, a_row0, a_end, a_col0, lane, v[0]);         // in flight while the parked tiles are stored
     if (idA0 != kNoTile) {   // uniform
         int64_t row0, col0;
-        tile4_origin<ROWS>(idA0, ncol, wave, row0, col0);
+        tile4_origin(idA0, ncol, wave, row0, col0);
         acc_get_half<A0, 0>(v[1]);
         quantize_store_tile<HR, GROUP>(a, cq, v[1], row0, a.K, col0, lane);
         acc_get_half<A0, 1>(v[1]);
@@ -1006,7 +913,7 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
     }
     if (idA1 != kNoTile) {   // uniform
         int64_t row0, col0;
-        tile4_origin<ROWS>(idA1, ncol, wave, row0, col0);
+        tile4_origin(idA1, ncol, wave, row0, col0);
         acc_get_half<A1, 0>(v[1]);
         quantize_store_tile<HR, GROUP>(a, cq, v[1], row0, a.K, col0, lane);
         acc_get_half<A1, 1>(v[1]);
@@ -1014,7 +921,7 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
     }
     if (idL != kNoTile) {   // uniform: back from LDS into the same lanes' registers
         int64_t row0, col0;
-        tile4_origin<ROWS>(idL, ncol, wave, row0, col0);
+        tile4_origin(idL, ncol, wave, row0, col0);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -1039,7 +946,6 @@ __global__ __launch_bounds__(WAVES* kWave, WAVES / 4) void rtn_tensor_onepass(co
             if (b_live) load_tile<true, HR>(a, b_row0, b_end, b_col0, lane, v[1]);
         }
     }
-    OQ_STAMP(5);
     if (a.done != nullptr && first) clean_state(a, gridDim.x - 1u, THREADS);   // uniform; `first` = the workgroup that took ticket 0 (it always exists)
 }
 
@@ -1095,12 +1001,14 @@ static int64_t ranges_of(int64_t K, int64_t N, int64_t g) { return ceil_div(N, k
 static int groups_resident(int64_t g, int64_t ranges) {
     static std::atomic<int> cache[3][64];
     if (groups_streamed(g, ranges)) return resident_slots(cache[0], reinterpret_cast<const void*>(rtn_resident_stream), kResWaves * kWave);
-    if (groups_tile_rows(g, ranges) == 256) return resident_slots(cache[1], reinterpret_cast<const void*>(rtn_resident_groups<16, 16, 4>), 16 * kWave);
-    return resident_slots(cache[2], reinterpret_cast<const void*>(rtn_resident_groups<8, 16, 4>), kResWaves * kWave);
+    if (groups_tile_rows(g, ranges) == 256) return resident_slots(cache[1], reinterpret_cast<const void*>(rtn_resident_groups<16>), 16 * kWave);
+    return resident_slots(cache[2], reinterpret_cast<const void*>(rtn_resident_groups<8>), kResWaves * kWave);
 }
 
 size_t rtn_resident_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
     const int64_t kgroups = K / g, ncol_tiles = ceil_div(N, kResCols);
+    // per-tensor: the words behind the header are slack (a bitmap of kept tiles lived there until the kept tiles moved into the
+    // arrival slots); the size is part of what oq_rtn_workspace_bytes / oq_rtn_state_bytes promise and stays
     if (strategy == OQ_TENSOR) return static_cast<size_t>(kResTensorHeader + (2 * ncol_tiles * ceil_div(K, kResTileRows) + 31) / 32 + 1) * 4 + 256;
     return static_cast<size_t>(2 * kgroups * ncol_tiles * kResCols + ncol_tiles * kgroups * kResCtrPad + kResHeader) * 4 + 256;
 }
@@ -1159,9 +1067,6 @@ static thread_local TicketChain* t_chain_held = nullptr;
 int32_t ticket_chain_begin(hipStream_t s) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail(OQ_ERR_LAUNCH, "rtn: no current device");
-#ifdef OQ_NO_TICKET_CHAIN      /* lab: what the chain costs a single stream */
-    return OQ_OK;
-#endif
     OQ_REQUIRE(!rtn_stream_is_capturing(s), OQ_ERR_UNSUPPORTED, "rtn: a ticketed kernel cannot be captured into a graph (its replays would be ordered against nothing)");
     const uintptr_t id = reinterpret_cast<uintptr_t>(s);      // an opaque key from here on
     TicketChain& c = g_chain[dev];
@@ -1186,7 +1091,7 @@ int32_t ticket_chain_begin(hipStream_t s) {
 }
 void ticket_chain_end(hipStream_t s) {
     TicketChain* c = t_chain_held;
-    if (c == nullptr) return;                                  // OQ_NO_TICKET_CHAIN
+    if (c == nullptr) return;      // a failing begin holds nothing: an end behind it must not unlock a mutex this thread does not own
     t_chain_held = nullptr;
     if (c->eager) {      // also after a launch that failed half way (its clear launch may be in the stream)
         if (hipEventRecord(c->ev, s) != hipSuccess) {
@@ -1203,11 +1108,11 @@ void ticket_chain_end(hipStream_t s) {
 }
 
 static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g, uint8_t* q,
-                                   float* scale, uint8_t* zp, int32_t layout, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state) {
+                                   float* scale, uint8_t* zp, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state) {
     ResidentArgs a;
     const int tile_rows = strategy == OQ_TENSOR ? kResTileRows : groups_tile_rows(g, ranges_of(K, N, g));
     a.W = W; a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = K / g; a.chunks = ceil_div(g, strategy == OQ_TENSOR ? kResTileRows : tile_rows);
-    a.q = q; a.scale = scale; a.zp = zp; a.grid = grid; a.layout = layout;
+    a.q = q; a.scale = scale; a.zp = zp; a.grid = grid;
     a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, kResCols));
     const size_t need = rtn_resident_workspace(K, N, strategy, g);
     OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "rtn: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
@@ -1219,30 +1124,28 @@ static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t
         const uint32_t n16 = static_cast<uint32_t>((need - 256 + 15) / 16);   // `need` counts whole words past the aligned base; the +256 slack covers the round-up
         hipLaunchKernelGGL(clear_words_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, reinterpret_cast<uint4*>(base), n16);
     }
-    a.tickets = base;                 // [0] phase A; phase B's at [32] (see the kernels: tickets + 32)
+    a.tickets = base;                 // [0]: the one ticket counter of every kernel
     a.counters = base + kResHeader;   // groups: one per range
     if (strategy == OQ_TENSOR) {
         a.ntiles = a.ncol_tiles * static_cast<uint32_t>(ceil_div(K, kResTileRows));
         a.counters = base + 64;                  // tiles counted
         a.key_max = base + 128;                  // one 16-byte slot {1, max key, complemented min key} per arrival (<= 512 workgroups)
         a.key_nmin = base + 128 + 64 * 32;       // 64 replicas x 32 words: {go, final max key, final complemented min key}
-        a.held = base + kResTensorHeader;
         static std::atomic<int> cache[64];
-        const int resident = resident_slots(cache, reinterpret_cast<const void*>(rtn_tensor_onepass<kResWaves>), kResWaves * kWave, kParkBytes);
+        const int resident = resident_slots(cache, reinterpret_cast<const void*>(rtn_tensor_onepass), kResWaves * kWave, kParkBytes);
         OQ_REQUIRE(resident > 0, OQ_ERR_LAUNCH, "rtn: occupancy query failed");
         uint32_t blocks = a.ntiles < static_cast<uint32_t>(resident) ? a.ntiles : static_cast<uint32_t>(resident);
         if (blocks > static_cast<uint32_t>(kResWaves * kWave)) blocks = kResWaves * kWave;   // the arrival slots: one per thread of the last finisher
-        hipLaunchKernelGGL(rtn_tensor_onepass<kResWaves>, dim3(blocks), dim3(kResWaves * kWave), kParkBytes, s, a);
+        hipLaunchKernelGGL(rtn_tensor_onepass, dim3(blocks), dim3(kResWaves * kWave), kParkBytes, s, a);
         return check_launch("rtn_tensor_onepass");
     }
     const int64_t ranges = static_cast<int64_t>(a.ncol_tiles) * a.kgroups;
     a.ntiles = static_cast<uint32_t>(ranges * a.chunks);
-    a.held = nullptr;
     a.key_max = a.counters + ranges * kResCtrPad;
     a.key_nmin = a.key_max + a.kgroups * static_cast<int64_t>(a.ncol_tiles) * kResCols;
     if (!groups_streamed(g, ranges)) {
-        if (tile_rows == 256) hipLaunchKernelGGL((rtn_resident_groups<16, 16, 4>), dim3(a.ntiles), dim3(16 * kWave), 0, s, a);
-        else hipLaunchKernelGGL((rtn_resident_groups<8, 16, 4>), dim3(a.ntiles), dim3(8 * kWave), 0, s, a);
+        if (tile_rows == 256) hipLaunchKernelGGL((rtn_resident_groups<16>), dim3(a.ntiles), dim3(16 * kWave), 0, s, a);
+        else hipLaunchKernelGGL((rtn_resident_groups<8>), dim3(a.ntiles), dim3(8 * kWave), 0, s, a);
     } else {
         const int resident = groups_resident(g, ranges);
         // forward progress needs at least `chunks` running workgroups (see the kernel): rtn_resident_eligible has checked it
@@ -1258,7 +1161,7 @@ int32_t rtn_resident_impl(const float* W, int64_t K, int64_t N, int64_t ldw, con
                           float* scale, uint8_t* zp, int32_t layout, void* workspace, size_t workspace_bytes, hipStream_t s, bool zeroed_state) {
     const int32_t pre = ticket_chain_begin(s);
     if (pre != OQ_OK) return pre;
-    const int32_t st = rtn_resident_launch(W, K, N, ldw, grid, strategy, g, q, scale, zp, layout, workspace, workspace_bytes, s, zeroed_state);
+    const int32_t st = rtn_resident_launch(W, K, N, ldw, grid, strategy, g, q, scale, zp, workspace, workspace_bytes, s, zeroed_state);
     ticket_chain_end(s);
     return st;
 }
@@ -1271,11 +1174,5 @@ extern "C" int32_t oq_lab_spin_timeouts(uint32_t* host_out, int32_t reset) {
     const uint32_t zero = 0;
     if (reset && hipMemcpyToSymbol(HIP_SYMBOL(oq::g_spin_timeouts), &zero, sizeof(uint32_t)) != hipSuccess) return -1;
     return 0;
-}
-#endif
-
-#ifdef OQ_TENSOR_STAMPS
-extern "C" int32_t oq_lab_tensor_stamps(uint64_t* host_out /* [512 * 8] */) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(oq::g_tensor_stamps), sizeof(uint64_t) * 512 * 8) == hipSuccess ? 0 : -1;
 }
 #endif

@@ -81,7 +81,8 @@ def test_gptq_loop_kernels_do_not_spill(tmp_path):
 def test_resident_rtn_kernels_keep_their_tiles_in_registers(tmp_path):
     """`rtn_resident_groups` (channel, tall groups: W read once) holds a 128 x 256 tile in 64 registers per lane while the range
     completes elsewhere; two 8-wave workgroups per CU (<= 128 registers, no scratch) are what keeps loads in flight while one of
-    them waits.  `rtn_tensor_onepass` runs ONE 8-wave workgroup per CU that keeps a tile in 64 architectural registers, two in
+    them waits.  `rtn_resident_stream` holds two such tiles per workgroup, one 8-wave workgroup per CU (<= 256 registers, no
+    scratch, two waves per SIMD).  `rtn_tensor_onepass` runs ONE 8-wave workgroup per CU that keeps a tile in 64 architectural registers, two in
     its 128 accumulation registers -- named as PHYSICAL registers a[0..127] in the assembly text, so the register allocator
     must not have placed anything of its own there -- and one in LDS; a spill would turn its kept tiles into scratch traffic."""
     from onnx_quantize_amd import _build
@@ -92,7 +93,7 @@ def test_resident_rtn_kernels_keep_their_tiles_in_registers(tmp_path):
     seen = {}
     for m in re.finditer(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)", r.stderr, re.S):
         seen[m.group(1)] = tuple(int(m.group(i)) for i in (2, 3, 4))
-    for key, max_vgprs, min_occ in (("rtn_resident_groups", 128, 4), ("rtn_tensor_onepass", 256, 2)):
+    for key, max_vgprs, min_occ in (("rtn_resident_groups", 128, 4), ("rtn_resident_stream", 256, 2), ("rtn_tensor_onepass", 256, 2)):
         hits = [v for k, v in seen.items() if key in k]
         assert hits, (key, list(seen))
         for vgprs, scratch, occ in hits:
@@ -101,7 +102,7 @@ def test_resident_rtn_kernels_keep_their_tiles_in_registers(tmp_path):
     # of 64 registers, each written at one place and read back at one place) and no other use of an `a` register: the compiler
     # turns to them only once the architectural registers run out (<= 128 here), and then it would take a[0], a[1], ... -- the parks
     text = (tmp_path / "res.s").read_text()
-    m = re.search(r"^_ZN2oq18rtn_tensor_onepassILi8EEEvNS_12ResidentArgsE:.*?s_endpgm", text, re.S | re.M)
+    m = re.search(r"^_ZN2oq18rtn_tensor_onepassENS_12ResidentArgsE:.*?s_endpgm", text, re.S | re.M)
     assert m, "kernel body not found"
     body = m.group(0)
     writes = re.findall(r"v_accvgpr_write_b32 (\S+),", body)
@@ -111,7 +112,7 @@ def test_resident_rtn_kernels_keep_their_tiles_in_registers(tmp_path):
     assert "v_accvgpr_mov" not in body
     others = [ln for ln in body.splitlines() if "accvgpr" not in ln and re.search(r"[ ,]a(\[|\d)", ln.split(";")[0])]
     assert not others, others[:5]
-    meta = [c for c in text.split("- .agpr_count:")[1:] if "_ZN2oq18rtn_tensor_onepassILi8EEEvNS_12ResidentArgsE\n" in c.split(".vgpr_count:")[0]]
+    meta = [c for c in text.split("- .agpr_count:")[1:] if "_ZN2oq18rtn_tensor_onepassENS_12ResidentArgsE\n" in c.split(".vgpr_count:")[0]]
     assert len(meta) == 1
     agpr = int(meta[0].split()[0])
     total = int(re.search(r"\.vgpr_count:\s+(\d+)", meta[0]).group(1))

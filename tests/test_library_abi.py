@@ -171,11 +171,15 @@ def test_c_program_quantizes_on_the_gpu(tmp_path):
 def test_shipped_library_has_no_attribution_switches():
     """The shipped library has no experiment switches at all: no file of its sources so much as mentions `getenv` (not even
     behind an `#ifdef` or in a comment), the lab macros that once selected or tuned variants of the Hessian / piece-GEMM and AWQ
-    kernels are gone with the variants, the store-dropping RTN variants and the `nt` argument that selected them are gone, and
-    the build used by `__graft_entry__.build()` and the tests defines no lab macro."""
+    kernels are gone with the variants, the store-dropping RTN variants and the `nt` argument that selected them are gone, the
+    switches and phase stamps of the ticketed RTN kernels and of the GPTQ loop are gone (the only preprocessor conditional on an
+    `OQ_` macro left is `OQ_SPIN_LIMIT`), and the build used by `__graft_entry__.build()` and the tests defines no lab macro."""
     from onnx_quantize_amd import _build
     removed_macros = ("OQ_SYRK_LAB", "OQ_SYRK_F16_M16", "OQ_SYRK_SPLITS", "OQ_SYRK_F16_STRIDE", "OQ_SYRK_F16_STRIDE_EXPR", "OQ_SYRK_F16_DEEP",
-                      "OQ_SYRK_M16_STRIDE", "OQ_PREP_NT", "OQ_PREP_LOAD", "OQ_AWQ_HI_ONLY", "OQ_AWQ_FUSED_PIECES", "OQ_AWQ_GRAM_RATIO")
+                      "OQ_SYRK_M16_STRIDE", "OQ_PREP_NT", "OQ_PREP_LOAD", "OQ_AWQ_HI_ONLY", "OQ_AWQ_FUSED_PIECES", "OQ_AWQ_GRAM_RATIO",
+                      "OQ_RES_A_NT", "OQ_RES_SLEEP", "OQ_RES_STORE", "OQ_GROUPS_GROUP", "OQ_STREAM_GROUP", "OQ_T4_GROUP", "OQ_TENSOR_STAMPS",
+                      "OQ_NO_TICKET_CHAIN", "OQ_LOOP_STAMPS")
+    conditionals = []
     for name in sorted(os.listdir(_build.SRC)):
         text = open(os.path.join(_build.SRC, name)).read()
         assert "getenv" not in text, name
@@ -183,6 +187,10 @@ def test_shipped_library_has_no_attribution_switches():
             assert macro not in text, (name, macro)
         assert "OQ_RTN_ATTRIBUTION" not in text and "OQ_ATTR(" not in text, name
         assert not re.search(r"\ba\.nt\b", text), name       # the field itself (`a.ntiles` of the ticketed kernels is another thing)
+        assert not re.search(r"\bOQ_(STAMP|LAP)\b", text), name     # the phase stamps of the ticketed kernels and of the GPTQ loop
+        conditionals += re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b[^\n]*?\b(OQ_\w+)", text, re.M)
+    # the one switch left: spins that give up instead of hanging a shared box, for the first runs of a changed hand-off
+    assert conditionals and set(conditionals) == {"OQ_SPIN_LIMIT"}, conditionals
     for flag in _build.CXXFLAGS + [f for fl in _build.PER_FILE_FLAGS.values() for f in fl]:
         assert not re.match(r"-D\s*\w*_LAB\b", flag) and "OQ_RTN_ATTRIBUTION" not in flag, flag
 
