@@ -47,6 +47,40 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
                             float clip_ratio, void* q_out /* NULL: parameters only */, float* scale_out,
                             void* zp_out, int32_t layout, void* workspace, size_t workspace_bytes, void* stream);
 
+/* A1 over a LIST of equally shaped 2-byte matrices of ONE element type that live anywhere in device memory (the MatMul weights of
+ *     a resident fp16 / bf16 model): what oq_rtn_quantize_ptrs_f32 (oq_hip.h) is for fp32 weights.  Entry i of the table holds the
+ *     four device pointers of matrix i; all matrices of a call share K, N, ldw, the group size and the quantization grid.
+ *
+ *   scope      the group strategy with K % group_size == 0 and group_size <= 256 (after the clamp to K; -1 = K): exactly what
+ *              oq_rtn_quantize_h16 runs as one fused launch.  Everything else OQ_ERR_UNSUPPORTED -- call oq_rtn_quantize_h16 per
+ *              matrix.  No workspace, no state: no workgroup waits for another, nothing is accumulated.
+ *   result     per matrix that of oq_rtn_quantize_h16, bit for bit (and so that of oq_rtn_quantize_f32 on the upcast matrix).
+ *   tables     `table_host` and `table_device` are the same `count` entries in host and device memory: the host copy is checked
+ *              and sizes the launches, the kernels read the device copy, which may be NULL when count == 1.  1 <= count <= 65535.
+ *              About 1.6e8 parameters share a launch (blockIdx.y = entry, at most 65535), the rule of oq_rtn_quantize_ptrs_f32;
+ *              later launches read table_device + i.
+ *   W          [K, N] of type `wtype`, leading dimension ldw >= N (elements), 2-byte aligned.
+ *   q_out      OQ_LAYOUT_KN: K*N bytes.  OQ_LAYOUT_NBITS: the blob, group_size % 16 == 0 and every q_out 16-byte aligned.
+ *              OQ_LAYOUT_KN_PACKED4: K*N/2 bytes, two columns per byte in core/_pack.py:8-22 order -- the bytes oq_pack_nibbles
+ *              makes of the [K, N] result, without the [K, N] store, the packer's read and its launch; 4-bit types, even N and a
+ *              group_size of 16 / 32 / 64 / 128 / 256 (OQ_ERR_UNSUPPORTED otherwise).  Never NULL.
+ *   scale_out  fp32, 4-byte aligned; zp_out 1 byte each: entry n*(K/g)+kg, as in oq_rtn_quantize_h16.
+ *   widths     16-byte loads of W need N % 8 == 0, ldw % 8 == 0 and EVERY W 16-byte aligned; whole 8-byte ([K, N]) or 4-byte
+ *              ([K, N/2]) stores need N % 8 == 0 and EVERY q_out aligned to them.  One entry short of that puts the whole call on
+ *              the narrow build, which gives the same bytes: group entries by alignment where that matters.
+ *   checks     an unknown wtype, null tables, count, the shape bounds, clip_ratio, the layout rules and, entry by entry, null
+ *              pointers and alignment (the message names the entry) -- all on the host copy before anything is launched: on any
+ *              refusal no output is touched. */
+typedef struct {
+    const void* W;
+    void* q_out;
+    float* scale_out;
+    void* zp_out;
+} oq_rtn_ptrs_h16;   /* the layout of oq_rtn_ptrs */
+int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn_ptrs_h16* table_device, int64_t count,
+                                 int32_t wtype, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int64_t group_size,
+                                 int32_t symmetric, int32_t reduce_range, float clip_ratio, int32_t layout, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * G1  core/_algorithms/gptq.py:246-260  _accumulate_hessian on inp.astype(np.float32) (:257), without the fp32 copy:
  *     replaces the cast followed by oq_hessian_accumulate_f32.

@@ -1404,7 +1404,7 @@ int32_t launch_quantize_kn(const float* W, int64_t K, int64_t N, int64_t ldw, in
 // A lone small matrix cannot fill the chip (4096 waves on 5120 slots all start and end together); very long merged launches
 // of large matrices lose a little again (dirty output lines evicted between another matrix' reads instead of written back
 // in a burst at a kernel's end).  ~1.6e8 parameters per launch sits at or next to the best point of every row.
-static int64_t matrices_per_launch(int64_t K, int64_t N, int64_t count) {
+int64_t matrices_per_launch(int64_t K, int64_t N, int64_t count) {
     constexpr int64_t per_launch = 160000000;
     int64_t m = per_launch / (K * N);
     if (m > 65535) m = 65535;   // blockIdx.y

@@ -5,6 +5,8 @@
 //   group strategy, K % g == 0, g <= 256        one fused launch, W read once
 //     g = 16 / 32 / 64 / 128 / 256              rtn_half_wave: a wave holds 128 (256) rows x 64 columns as PACKED halves in registers
 //     every other g                             rtn_half_column: a thread per (group, column); the second read of its rows hits the L2
+//     a LIST of matrices of one shape           the same two kernels with blockIdx.y = entry of a device table of pointers
+//                                               (rtn_half_wave_many / rtn_half_column_many, oq_rtn_quantize_ptrs_h16)
 //   channel, tensor, g > 256                    two launches over W (half_range + a fold, half_quantize): reading 2-byte W twice
 //                                               costs what the fp32 kernels pay to read it once; nothing waits for another workgroup
 #include "rtn_internal.hpp"
@@ -54,6 +56,15 @@ struct HalfArgs {
     float* pmax;
 };
 
+// The four pointers of one matrix: the fields of HalfArgs for a single matrix, an entry of the device table for a list
+// (the layout of oq_rtn_ptrs_h16).
+struct HalfPtrs {
+    const uint16_t* W;
+    uint8_t* q;       // null: parameters only
+    float* scale;
+    uint8_t* zp;
+};
+
 // Signed levels are biased by 128 so that every level is a byte v_cvt_pk_u8_f32 can place: the low nibble of level + 128 is the
 // two's-complement nibble already, the byte needs bit 7 flipped back.
 __device__ __forceinline__ int32_t level_bias(const QGrid& g) { return g.qmin < 0 ? 128 : 0; }
@@ -80,8 +91,12 @@ __device__ __forceinline__ uint32_t nibble_word(uint32_t a, uint32_t b) {   // b
 // Three waves per SIMD for the 16-row build with vector loads (the hot path): 164 registers for fp16; bf16 would take 172 and
 // fall to two waves, capped at 168 it parks two registers in scratch (docs/LAB_NOTES_r07.md: measured 40.6 / 55.9 us on
 // 4096 x 11008 as built; the choice comes from the occupancy arithmetic, not from an A/B).
-template <typename E, int R, bool VEC>
-__global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(const HalfArgs a) {
+//
+// The tile work is one __device__ body that takes the matrix' pointers: rtn_half_wave passes those of HalfArgs, rtn_half_wave_many
+// those of entry blockIdx.y of a table.  PACKED adds the [K, N/2] epilogue (OQ_LAYOUT_KN_PACKED4) the list entry point offers: a
+// lane's eight neighbouring columns of a row are two words of level bytes, its four packed bytes one nibble_word.
+template <typename E, int R, bool VEC, bool PACKED>
+__device__ __forceinline__ void half_wave_tile(const HalfArgs& a, const HalfPtrs m) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 3, cl = lane & 7;
@@ -116,7 +131,7 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
         const int64_t lrow = rows_ok ? row0 : tile_row0;
         if constexpr (VEC) {   // N % 8 == 0: a lane's eight columns are in or out together
             const int64_t lc = col0 < a.N ? col0 : a.N - 8;
-            const uint16_t* p = a.W + lrow * a.ldw + lc;
+            const uint16_t* p = m.W + lrow * a.ldw + lc;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const hu32x4 u = __builtin_nontemporal_load(reinterpret_cast<const hu32x4*>(p + r * a.ldw));
@@ -128,7 +143,7 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
             for (int j = 0; j < 8; ++j) c[j] = col0 + j < a.N ? col0 + j : a.N - 1;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const uint16_t* p = a.W + (lrow + r) * a.ldw;
+                const uint16_t* p = m.W + (lrow + r) * a.ldw;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[r][j] = static_cast<uint32_t>(p[c[2 * j]]) | (static_cast<uint32_t>(p[c[2 * j + 1]]) << 16);
             }
@@ -181,11 +196,11 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
         sc[j] = c.scale; rinv[j] = c.rinv; zpb[j] = c.zpb;
         thr = nmin(thr, c.thr);
         if (cv[j] && (j & (a.spg - 1)) == hs) {   // rtn.py:98-109 result layout: entry n * K/g + kg
-            a.scale[(col0 + j) * a.kgroups + kg] = p.scale;
-            a.zp[(col0 + j) * a.kgroups + kg] = static_cast<uint8_t>(p.zp);
+            m.scale[(col0 + j) * a.kgroups + kg] = p.scale;
+            m.zp[(col0 + j) * a.kgroups + kg] = static_cast<uint8_t>(p.zp);
         }
     }
-    if (a.q == nullptr) return;
+    if (m.q == nullptr) return;
 
     const float lo_b = static_cast<float>(qmin + bias), hi_b = static_cast<float>(qmax + bias);
     // level (biased, an exact small float) of row r, column slot j
@@ -200,7 +215,8 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
         return __builtin_amdgcn_fmed3f(k + zpb[j], lo_b, hi_b);
     };
 
-    if (a.layout == OQ_LAYOUT_KN) {
+    const bool packed = PACKED && a.layout == OQ_LAYOUT_KN_PACKED4;
+    if (a.layout == OQ_LAYOUT_KN || packed) {
         const uint32_t flip = bias ? 0x80808080u : 0u;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -217,7 +233,21 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
                 return unsafe;
             };
             if (__builtin_amdgcn_ballot_w64(row_words(false)) != 0) row_words(true);   // wave-uniform, rare: the IEEE divide
-            uint8_t* o = a.q + (row0 + r) * a.N + col0;
+            if constexpr (PACKED) {
+                if (packed) {   // even N (host): a pair of columns is in or out together; qvec: N % 8 == 0 and 4-byte aligned rows
+                    const uint32_t pw = nibble_word(w[0], w[1]);
+                    uint8_t* o = m.q + (row0 + r) * (a.N >> 1) + (col0 >> 1);
+                    if (a.qvec) {
+                        if (cv[0]) __builtin_nontemporal_store(pw, reinterpret_cast<uint32_t*>(o));
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (cv[2 * i]) o[i] = static_cast<uint8_t>(pw >> (8 * i));
+                    }
+                    continue;
+                }
+            }
+            uint8_t* o = m.q + (row0 + r) * a.N + col0;
             if (a.qvec) {
                 if (cv[0]) __builtin_nontemporal_store(hu32x2{w[0], w[1]}, reinterpret_cast<hu32x2*>(o));
             } else {
@@ -249,7 +279,7 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
         };
         if (__builtin_amdgcn_ballot_w64(col_words(false)) != 0) col_words(true);   // wave-uniform, rare: the IEEE divide
         if (!cv[j]) continue;
-        uint8_t* o = a.q + ((col0 + j) * a.kgroups + kg) * blob;
+        uint8_t* o = m.q + ((col0 + j) * a.kgroups + kg) * blob;
         if (four) {
             o += hs * (R / 2);
             if constexpr (R == 16) {
@@ -266,20 +296,32 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
     }
 }
 
+template <typename E, int R, bool VEC>
+__global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(const HalfArgs a) {
+    half_wave_tile<E, R, VEC, false>(a, HalfPtrs{a.W, a.q, a.scale, a.zp});
+}
+
+// A list of matrices of one shape: blockIdx.y is the entry (wave-uniform: its four pointers come by scalar loads), blockIdx.x the tile in the single
+// matrix' order, so every matrix keeps its bands.  A null table is a list of one, whose pointers are in HalfArgs.
+template <typename E, int R, bool VEC>
+__global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave_many(const HalfArgs a, const HalfPtrs* __restrict__ table) {
+    half_wave_tile<E, R, VEC, true>(a, table != nullptr ? table[blockIdx.y] : HalfPtrs{a.W, a.q, a.scale, a.zp});
+}
+
 // ------------------------------------------------------------------------------------ plain kernels (a thread per column)
 // K1 with stored parameters on rows [r0, r1) of column `col`; the IEEE division (oq::quantize_one).  [K,N] bytes, or -- whole slabs
 // of 16 rows of one group -- 8 / 16 bytes of the blob.
 template <typename E>
-__device__ __forceinline__ void quantize_rows(const HalfArgs& a, int64_t col, int64_t r0, int64_t r1, int64_t kg, float scale, int32_t zp) {
+__device__ __forceinline__ void quantize_rows(const HalfArgs& a, const HalfPtrs& m, int64_t col, int64_t r0, int64_t r1, int64_t kg, float scale, int32_t zp) {
     const int32_t qmin = a.grid.qmin, qmax = a.grid.qmax;
-    const uint16_t* w = a.W + col;
+    const uint16_t* w = m.W + col;
     if (a.layout == OQ_LAYOUT_KN) {
-        for (int64_t r = r0; r < r1; ++r) a.q[r * a.N + col] = static_cast<uint8_t>(quantize_one(E::one(w[r * a.ldw]), scale, zp, qmin, qmax));
+        for (int64_t r = r0; r < r1; ++r) m.q[r * a.N + col] = static_cast<uint8_t>(quantize_one(E::one(w[r * a.ldw]), scale, zp, qmin, qmax));
         return;
     }
     // g % 16 == 0 (host): [r0, r1) is a whole number of 16-row slabs of group kg
     const int64_t blob = a.g * a.grid.bits / 8;
-    uint8_t* o = a.q + (col * a.kgroups + kg) * blob;
+    uint8_t* o = m.q + (col * a.kgroups + kg) * blob;
     for (int64_t r = r0; r < r1; r += 16) {
         uint32_t lw[4];
 #pragma unroll
@@ -298,21 +340,30 @@ __device__ __forceinline__ void quantize_rows(const HalfArgs& a, int64_t col, in
 
 // Fused, any g <= 256 with K % g == 0: a thread per (group, column), neighbouring threads on neighbouring columns.
 template <typename E>
-__global__ __launch_bounds__(256) void rtn_half_column(const HalfArgs a) {
+__device__ __forceinline__ void half_column_groups(const HalfArgs& a, const HalfPtrs m) {
     const int64_t kg = blockIdx.x / a.ncol_tiles;
     const int64_t col = static_cast<int64_t>(blockIdx.x % a.ncol_tiles) * 256 + threadIdx.x;
     if (col >= a.N) return;
     const int64_t r0 = kg * a.g, r1 = r0 + a.g;
     float mn = INFINITY, mx = -INFINITY;
     for (int64_t r = r0; r < r1; ++r) {
-        const float x = E::one(a.W[r * a.ldw + col]);
+        const float x = E::one(m.W[r * a.ldw + col]);
         mn = nmin(mn, x);
         mx = nmax(mx, x);
     }
     const QParam p = qparam_from_minmax(mn, mx, a.grid);
-    a.scale[col * a.kgroups + kg] = p.scale;
-    a.zp[col * a.kgroups + kg] = static_cast<uint8_t>(p.zp);
-    if (a.q != nullptr) quantize_rows<E>(a, col, r0, r1, kg, p.scale, p.zp);
+    m.scale[col * a.kgroups + kg] = p.scale;
+    m.zp[col * a.kgroups + kg] = static_cast<uint8_t>(p.zp);
+    if (m.q != nullptr) quantize_rows<E>(a, m, col, r0, r1, kg, p.scale, p.zp);
+}
+template <typename E>
+__global__ __launch_bounds__(256) void rtn_half_column(const HalfArgs a) {
+    half_column_groups<E>(a, HalfPtrs{a.W, a.q, a.scale, a.zp});
+}
+// ... of entry blockIdx.y of a table (null: a list of one, in HalfArgs), as rtn_half_wave_many
+template <typename E>
+__global__ __launch_bounds__(256) void rtn_half_column_many(const HalfArgs a, const HalfPtrs* __restrict__ table) {
+    half_column_groups<E>(a, table != nullptr ? table[blockIdx.y] : HalfPtrs{a.W, a.q, a.scale, a.zp});
 }
 
 // Two-launch route, launch 1: ranges of chunks of up to 64 rows of a group, [kgroups * chunks, N].
@@ -380,7 +431,7 @@ __global__ __launch_bounds__(256) void half_quantize(const HalfArgs a) {
     const int64_t r0 = kg * a.g + s * 16, r1 = min(r0 + 16, kg * a.g + a.g);
     const int64_t pi = a.tensor ? 0 : col * a.kgroups + kg;
     const int32_t zp = a.grid.qmin < 0 ? static_cast<int32_t>(static_cast<int8_t>(a.zp[pi])) : static_cast<int32_t>(a.zp[pi]);
-    quantize_rows<E>(a, col, r0, r1, kg, a.scale[pi], zp);
+    quantize_rows<E>(a, HalfPtrs{a.W, a.q, a.scale, a.zp}, col, r0, r1, kg, a.scale[pi], zp);
 }
 
 // ------------------------------------------------------------------------------------ host
@@ -447,6 +498,31 @@ static int32_t half_launch(HalfArgs& a, int32_t strategy, hipStream_t s) {
     const int64_t slabs = a.kgroups * ceil_div(g, 16);
     hipLaunchKernelGGL(half_quantize<E>, dim3(a.ncol_tiles * static_cast<uint32_t>(slabs)), dim3(256), 0, s, a);
     return check_launch("half_quantize");
+}
+
+// oq_rtn_quantize_ptrs_h16: one launch of `batch` matrices of one shape, entry b at table[b] (device memory; null: batch == 1,
+// the pointers are in `a`).  The tile work, tile shape and block order of half_launch's fused arm with the entry as grid y.
+template <typename E>
+static int32_t half_launch_many(HalfArgs& a, const HalfPtrs* table, int64_t batch, hipStream_t s) {
+    const int64_t g = a.g;
+    const dim3 block(256);
+    if (g == 16 || g == 32 || g == 64 || g == 128 || g == 256) {
+        const int rows = g == 256 ? 32 : 16;
+        a.spg = static_cast<int32_t>(g / rows);
+        a.nrow_tiles = static_cast<uint32_t>(ceil_div(a.K, 8 * rows));
+        a.gk = 4;
+        const dim3 grid(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(batch));
+        if (rows == 16) {
+            if (a.vec) hipLaunchKernelGGL((rtn_half_wave_many<E, 16, true>), grid, block, 0, s, a, table);
+            else hipLaunchKernelGGL((rtn_half_wave_many<E, 16, false>), grid, block, 0, s, a, table);
+        } else {
+            if (a.vec) hipLaunchKernelGGL((rtn_half_wave_many<E, 32, true>), grid, block, 0, s, a, table);
+            else hipLaunchKernelGGL((rtn_half_wave_many<E, 32, false>), grid, block, 0, s, a, table);
+        }
+        return check_launch("rtn_half_wave_many");
+    }
+    hipLaunchKernelGGL(rtn_half_column_many<E>, dim3(a.ncol_tiles * static_cast<uint32_t>(a.kgroups), static_cast<uint32_t>(batch)), block, 0, s, a, table);
+    return check_launch("rtn_half_column_many");
 }
 
 }  // namespace oq
@@ -519,6 +595,81 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
     }
     const hipStream_t s = as_stream(stream);
     return wtype == OQ_W_F16 ? half_launch<ElemF16>(a, strategy, s) : half_launch<ElemBF16>(a, strategy, s);
+}
+
+int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn_ptrs_h16* table_device, int64_t count, int32_t wtype,
+                                 int64_t K, int64_t N, int64_t ldw, int32_t qtype, int64_t group_size, int32_t symmetric,
+                                 int32_t reduce_range, float clip_ratio, int32_t layout, void* stream) {
+    using namespace oq;
+    static_assert(sizeof(HalfPtrs) == sizeof(oq_rtn_ptrs_h16) && sizeof(oq_rtn_ptrs_h16) == sizeof(oq_rtn_ptrs), "device view of oq_rtn_ptrs_h16");
+    // every check on the host copy, before any arithmetic on an extent and before any HIP call
+    OQ_REQUIRE(wtype == OQ_W_F16 || wtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: unknown wtype %d", wtype);
+    OQ_REQUIRE(table_host != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: null table_host");
+    OQ_REQUIRE(count >= 1 && count <= 65535, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: count %lld outside 1 .. 65535", (long long)count);
+    OQ_REQUIRE(table_device != nullptr || count == 1, OQ_ERR_INVALID_ARGUMENT,
+               "oq_rtn_quantize_ptrs_h16: null table_device with count %lld (it may be null for count 1 only)", (long long)count);
+    OQ_REQUIRE(K > 0 && N > 0 && ldw >= N, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: bad shape K=%lld N=%lld ldw=%lld", (long long)K,
+               (long long)N, (long long)ldw);
+    OQ_REQUIRE(matrix_ok(K, N, ldw), OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: matrix too large (K=%lld N=%lld ldw=%lld)", (long long)K,
+               (long long)N, (long long)ldw);
+    OQ_REQUIRE(clip_ratio > 0.0f && clip_ratio <= 1.0f, OQ_ERR_INVALID_ARGUMENT, "clip_ratio must be in (0.0, 1.0], got %g", clip_ratio);
+    OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS || layout == OQ_LAYOUT_KN_PACKED4, OQ_ERR_INVALID_ARGUMENT,
+               "oq_rtn_quantize_ptrs_h16: bad layout %d", layout);
+    HalfArgs a{};
+    int32_t st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &a.grid);
+    if (st != OQ_OK) return st;
+    int64_t g;
+    st = half_group(OQ_GROUP, K, group_size, &g);
+    if (st != OQ_OK) return st;
+    OQ_REQUIRE(K % g == 0, OQ_ERR_UNSUPPORTED,
+               "oq_rtn_quantize_ptrs_h16: group_size %lld does not divide K=%lld (groups that straddle columns have no half-precision kernel)",
+               (long long)g, (long long)K);
+    OQ_REQUIRE(half_fused(OQ_GROUP, g), OQ_ERR_UNSUPPORTED,
+               "oq_rtn_quantize_ptrs_h16: group_size %lld is taller than the fused kernels hold (256 rows); call oq_rtn_quantize_h16 per matrix",
+               (long long)g);
+    const bool wave = g == 16 || g == 32 || g == 64 || g == 128 || g == 256;
+    if (layout == OQ_LAYOUT_NBITS)
+        OQ_REQUIRE(g % 16 == 0, OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: NBITS layout needs group_size %% 16 == 0, got %lld", (long long)g);
+    if (layout == OQ_LAYOUT_KN_PACKED4) {
+        OQ_REQUIRE(a.grid.bits == 4, OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: KN_PACKED4 layout needs a 4-bit type");
+        OQ_REQUIRE(N % 2 == 0, OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: KN_PACKED4 layout needs an even number of columns, got N=%lld", (long long)N);
+        OQ_REQUIRE(wave, OQ_ERR_UNSUPPORTED,
+                   "oq_rtn_quantize_ptrs_h16: KN_PACKED4 layout needs a group_size of 16, 32, 64, 128 or 256 (the wave kernel), got %lld", (long long)g);
+    }
+    // the load and store widths are chosen for the call: every entry has to meet what they promise, or the call runs the narrow build
+    bool vec = N % 8 == 0 && ldw % 8 == 0, qvec = N % 8 == 0;
+    const uintptr_t q_store = layout == OQ_LAYOUT_KN_PACKED4 ? 4 : 8;
+    for (int64_t i = 0; i < count; ++i) {
+        const oq_rtn_ptrs_h16& p = table_host[i];
+        OQ_REQUIRE(p.W && p.q_out && p.scale_out && p.zp_out, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: null pointer in entry %lld", (long long)i);
+        OQ_REQUIRE(half_aligned(p.W, 2) && half_aligned(p.scale_out, 4), OQ_ERR_INVALID_ARGUMENT,
+                   "oq_rtn_quantize_ptrs_h16: entry %lld: W must be 2-byte aligned and scale_out 4-byte aligned", (long long)i);
+        OQ_REQUIRE(layout != OQ_LAYOUT_NBITS || half_aligned(p.q_out, 16), OQ_ERR_UNSUPPORTED,
+                   "oq_rtn_quantize_ptrs_h16: entry %lld: NBITS layout needs a 16-byte aligned q_out", (long long)i);
+        vec = vec && half_aligned(p.W, 16);
+        qvec = qvec && half_aligned(p.q_out, q_store);
+    }
+    a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = K / g;
+    a.layout = layout;
+    a.vec = vec ? 1 : 0;
+    a.qvec = qvec ? 1 : 0;
+    a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, 256));
+    OQ_REQUIRE(static_cast<int64_t>(a.ncol_tiles) * a.kgroups * ceil_div(g, 16) <= kMaxExtent, OQ_ERR_UNSUPPORTED,
+               "oq_rtn_quantize_ptrs_h16: matrix too large for one launch (K=%lld N=%lld)", (long long)K, (long long)N);
+
+    // How many matrices share a launch (blockIdx.y = entry): the rule of the fp32 entry point, oq::matrices_per_launch.
+    const int64_t per_launch = matrices_per_launch(K, N, count);
+    const hipStream_t s = as_stream(stream);
+    for (int64_t i = 0; i < count; i += per_launch) {
+        const int64_t batch = count - i < per_launch ? count - i : per_launch;
+        const HalfPtrs* table = table_device != nullptr ? reinterpret_cast<const HalfPtrs*>(table_device) + i : nullptr;
+        const oq_rtn_ptrs_h16& p = table_host[i];   // read by the kernel only where there is no device table (count == 1)
+        a.W = static_cast<const uint16_t*>(p.W);
+        a.q = static_cast<uint8_t*>(p.q_out); a.scale = p.scale_out; a.zp = static_cast<uint8_t*>(p.zp_out);
+        st = wtype == OQ_W_F16 ? half_launch_many<ElemF16>(a, table, batch, s) : half_launch_many<ElemBF16>(a, table, batch, s);
+        if (st != OQ_OK) return st;
+    }
+    return OQ_OK;
 }
 
 }  // extern "C"

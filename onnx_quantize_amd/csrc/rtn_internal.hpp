@@ -1,4 +1,4 @@
-// Host-side declarations shared by the RTN sources (rtn.hip, rtn_resident.hip, rtn_mse.hip) and their callers inside the
+// Host-side declarations shared by the RTN sources (rtn.hip, rtn_resident.hip, rtn_mse.hip, rtn_half.hip) and their callers inside the
 // library (awq.hip, gptq_loop.hip).  Not part of the C ABI.
 #pragma once
 
@@ -39,6 +39,9 @@ struct RtnCall {
 
 // rtn.hip
 int32_t rtn_impl(const RtnCall& c);
+// matrices of one shape that share a launch of a pointer-table entry point (oq_rtn_quantize_ptrs_f32 / _h16): a parameter budget
+// per launch, capped by blockIdx.y
+int64_t matrices_per_launch(int64_t K, int64_t N, int64_t count);
 // pass 3 of the three-launch path, also the final pass of the MSE search: K1 with stored parameters
 int32_t launch_quantize_kn(const float* W, int64_t K, int64_t N, int64_t ldw, int64_t g, int64_t kgroups, const float* scale,
                            const uint8_t* zp, uint8_t* q, const QGrid& grid, int32_t zp_signed, bool tensor, hipStream_t s,

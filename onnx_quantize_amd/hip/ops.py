@@ -146,7 +146,7 @@ def _refuse_half(w, fn: str) -> None:
     """The entry points that stay fp32-only say so by name instead of a bare dtype mismatch."""
     if isinstance(w, torch.Tensor) and w.dtype in _HALF_WTYPE:
         raise TypeError(f"{fn} takes fp32 weights only, got {w.dtype}: half-precision weights are served by rtn_quantize "
-                        f"(one matrix per call); convert with w.float() to use {fn}")
+                        f"(one matrix per call) and rtn_quantize_model (a list of matrices); convert with w.float() to use {fn}")
 
 
 def _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out):
@@ -210,6 +210,7 @@ def rtn_quantize(w: torch.Tensor, qtype: str, strategy: str, group_size=-1, symm
       - layout "kn_packed4": the "kn" route followed by `pack_nibbles`;
       - ``mse=True`` and groups that straddle columns (K % group_size != 0) have no half kernel: ONE device cast,
         ``w.float()``, then the fp32 path below.
+    A LIST of half matrices (a resident model) goes through `rtn_quantize_model`: one launch for the matrices of a shape.
     """
     _require_device(w, "w")
     if w.dtype in _HALF_WTYPE:
@@ -542,6 +543,114 @@ def rtn_quantize_many(ws, qtype: str, group_size: int, symmetric=False, reduce_r
     for idx, q, sc, zp, _mats in made:
         for j, i in enumerate(idx):
             out[i] = (q[j], sc[j], zp[j])
+    return out
+
+
+_HALF_WAVE_GROUPS = (16, 32, 64, 128, 256)     # csrc/rtn_half.hip: the group sizes rtn_half_wave has a build for
+
+
+def _half_list_route(w, g: int, qtype: str, layout: str) -> bool:
+    """Whether oq_rtn_quantize_ptrs_h16 takes this half matrix as it is (rows contiguous, a group the fused kernels hold, a
+    layout the kernel of that group writes, per-matrix outputs that stay aligned inside a shared buffer)."""
+    k, n = w.shape
+    if g > 256 or w.stride(1) != 1 or (k > 1 and w.stride(0) < n):
+        return False
+    if layout == "kn_packed4":
+        return g in _HALF_WAVE_GROUPS and BITS[qtype] == 4 and n % 2 == 0
+    if layout == "nbits":
+        return g % 16 == 0 and (n * k * BITS[qtype] // 8) % 16 == 0
+    return True
+
+
+def rtn_quantize_model(ws, qtype: str, group_size: int, symmetric=False, reduce_range=False, clip_ratio=1.0, layout: str = "kn"):
+    """rtn.py:54-109 (group strategy) for the MatMul weights of a model resident in HBM: a LIST of [K, N] device weights of any
+    mix of fp32 / fp16 / bf16 and of any shapes.  Returns [(q, scale, zp)] in input order with the shapes and dtypes of
+    `rtn_quantize_many`; per matrix the bits are those of `rtn_quantize` on that tensor (for a half tensor: on its upcast).
+
+      - fp32 items go to `rtn_quantize_many`, unchanged;
+      - half items are grouped by (dtype, shape, strides, 16-byte alignment of the base) and every group is ONE
+        oq_rtn_quantize_ptrs_h16 call (csrc/rtn_half.hip: the fused half kernels with blockIdx.y = entry of a device table of
+        pointers; no fp32 copy, no workspace): a tensor viewed from an odd offset never puts the aligned ones on the narrow loads.
+        Layout "kn_packed4" comes straight out of that launch (no [K, N] intermediate, no packer);
+      - half items that entry point does not take -- groups taller than 256 rows, the packed layout on a group size without a
+        wave build, rows that are not contiguous -- go one by one through `rtn_quantize`.
+
+    The outputs of one C call are views of three shared buffers.  All table rows go through the page-locked staging rows and
+    the side stream of `rtn_quantize_many`'s small-model path: everything is prepared first, the table goes up in one copy and
+    the C calls follow back to back."""
+    if not ws:
+        return []
+    lay = _layout_code(layout)
+    out = [None] * len(ws)
+    here = torch.device("cuda", torch.cuda.current_device())
+    f32, singles = [], []
+    groups: dict = {}       # (dtype, shape, strides, base 16-byte aligned) -> [takes the list route, indices, W pointers]
+    for i, w in enumerate(ws):              # a handful of attribute reads per weight: a small model is bound by this function
+        dt = getattr(w, "dtype", None)
+        if dt not in _HALF_WTYPE:
+            f32.append(i)                   # rtn_quantize_many checks (and names) what is not an fp32 device tensor
+            continue
+        if w.device != here:
+            _require_device(w, "w")         # raises with the full message
+        ptr = w.data_ptr()
+        key = (dt, w.shape, w.stride(), (ptr & 15) == 0)
+        slot = groups.get(key)
+        if slot is None:                    # the first of its key: the checks every member shares
+            if w.dim() != 2:
+                raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
+            k, n = w.shape
+            if k == 0 or n == 0:
+                raise ValueError(f"rtn_quantize_model: weight {i} is empty ({k} x {n})")
+            g = resolve_group("group", k, group_size)
+            if g <= 0 or k % g:
+                raise ValueError("rtn_quantize_model needs K % group_size == 0 for every weight")
+            slot = groups[key] = [_half_list_route(w, g, qtype, layout), [], []]
+        slot[1].append(i)
+        slot[2].append(ptr)
+    for key in [key for key, slot in groups.items() if not slot[0]]:
+        singles.extend(groups.pop(key)[1])
+    if f32:
+        for i, r in zip(f32, rtn_quantize_many([ws[i] for i in f32], qtype, group_size, symmetric, reduce_range, clip_ratio, layout)):
+            out[i] = r
+    if groups:
+        lib = L.load()
+        cdt = container_dtype(qtype)
+        total = sum(len(slot[1]) for slot in groups.values())
+        pin, side = _table_stage(here, total)
+        table_dev = torch.empty((total, 4), dtype=torch.int64, device=here)
+        table_dev.record_stream(side)
+        pin_np = pin.numpy()
+        calls, made, row = [], [], 0
+        for (dtype, (k, n), strides, _aligned), (_ok, idx, ptrs) in groups.items():     # host side only: outputs and table rows of every call
+            g = resolve_group("group", k, group_size)
+            cnt = len(idx)
+            q = _q_buffer(layout, (cnt,), k, n, g, qtype, here)
+            sc = torch.empty((cnt, n * k // g, 1), dtype=torch.float32, device=here)
+            zp = torch.empty((cnt, n * k // g, 1), dtype=cdt, device=here)
+            rows = pin_np[row:row + cnt]
+            steps = np.arange(cnt, dtype=np.int64)
+            rows[:, 0] = ptrs
+            rows[:, 1] = q.data_ptr() + steps * (q[0].numel() * q.element_size())
+            rows[:, 2] = sc.data_ptr() + steps * (sc[0].numel() * 4)
+            rows[:, 3] = zp.data_ptr() + steps * (zp[0].numel() * zp.element_size())
+            calls.append((_HALF_WTYPE[dtype], k, n, strides[0] if k > 1 else max(n, strides[0]), cnt, row))
+            made.append((idx, q, sc, zp))
+            row += cnt
+        if any(c[4] > 1 for c in calls):           # one copy on the side stream; the launch stream waits for it
+            cur = torch.cuda.current_stream()
+            with torch.cuda.stream(side):
+                table_dev.copy_(pin[:total], non_blocking=True)
+                ready = side.record_event()
+            cur.wait_event(ready)
+        host0, dev0, stream = pin.data_ptr(), table_dev.data_ptr(), _stream()
+        for wtype, k, n, ldw, cnt, row in calls:
+            L.check(lib.oq_rtn_quantize_ptrs_h16(C.c_void_p(host0 + 32 * row), C.c_void_p(dev0 + 32 * row if cnt > 1 else 0), cnt, wtype, k, n, ldw,
+                                                 L.QTYPE_CODE[qtype], int(group_size), int(symmetric), int(reduce_range), float(clip_ratio), lay, stream))
+        for idx, q, sc, zp in made:                # the per-matrix views, one unbind per buffer
+            for i, r in zip(idx, zip(q.unbind(0), sc.unbind(0), zp.unbind(0))):
+                out[i] = r
+    for i in singles:
+        out[i] = rtn_quantize(ws[i], qtype, "group", group_size, symmetric, reduce_range, clip_ratio, layout=layout)
     return out
 
 
