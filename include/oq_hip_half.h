@@ -1,6 +1,7 @@
 /*
  * oq_hip_half.h -- half-precision extension of the C ABI of oq_hip.h: RTN on fp16 / bf16 weights, the GPTQ Hessian and the
- * calibration statistics (running min / max, absmax) of fp16 / bf16 activations, all read as they are.
+ * calibration statistics (running min / max, absmax, the |x| column statistics of the AWQ / SmoothQuant searches) of fp16 / bf16
+ * activations, all read as they are.
  *
  * oq_hip.h stays what it is (OQ_ABI_VERSION 2); the entry points below live in the same library and follow the same
  * conventions (device pointers, asynchronous on `stream`, no allocation, 0 or a negative oq_status, oq_last_error()).
@@ -171,6 +172,44 @@ int32_t oq_minmax_collect_many_h16(const void* desc, int64_t n, int32_t xtype /*
 size_t oq_absmax_half_workspace_bytes(int64_t R, int64_t C, int32_t transposed);
 int32_t oq_absmax_h16(const void* x, int32_t xtype /* oq_wtype */, int64_t R, int64_t C, int64_t ldx, int32_t transposed, float* out,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N2s pre_passes/awq.py:47-50 (sum_t |x[t, k]|) and pre_passes/smooth_quant.py:62-69 (max_t |x[t, k]|) as RUNNING statistics
+ *     over calibration batches, for a LIST of 2-byte inputs of ONE element type, without an fp32 copy: replaces, per tensor, the
+ *     cast, oq_abs_sum_cols_f32(accumulate = 1), oq_absmax_f32 and the maximum with the running value.  Each input is read
+ *     once for both statistics; the whole table takes two launches (partials, fold) whose blocks never wait for one another;
+ *     no atomics.
+ *
+ *   items      `count` oq_abs_stats_item in host memory and the same bytes in device memory (8-byte aligned): the host copy is
+ *              checked and sizes the launches, the kernels read the device copy, which may be NULL when count == 1.
+ *              1 <= count <= 65535.
+ *   X          [T, K], 2 bytes per element of type `xtype`, leading dimension ldx >= K (elements), 2-byte aligned.  Items whose
+ *              rows are not 16-byte aligned (K or ldx no multiple of 8, an unaligned base) take narrower loads, item by item,
+ *              and give the same bits.
+ *   abs_sum    fp32 [K], 4-byte aligned:  abs_sum[k] <- abs_sum[k] + S_k, S_k the sum over the rows of |x[t, k]| on the exact
+ *              fp32 values in the order of oq_abs_sum_cols_f32 (min(T, 64) row chunks of ceil(T / chunks) rows; inside a chunk
+ *              fours as (a + b) + (c + d), then single rows; the chunks added from 0): the bits of
+ *              oq_abs_sum_cols_f32(..., accumulate = 1) on the upcast matrix.
+ *   absmax     fp32 [K], 4-byte aligned:  absmax[k] <- max(absmax[k], max_t |x[t, k]|), NaN-propagating (a NaN in the running
+ *              value or in the column gives NaN): the maximum of the running value and oq_absmax_f32 on the upcast matrix.
+ *   checks     an unknown xtype, null tables, count and, item by item, null pointers, alignment and the extent rules of oq_hip.h
+ *              (T, K >= 1, ldx >= K, all < 2^31, T * ldx <= 2^40) OQ_ERR_INVALID_ARGUMENT (the message names the item); a missing
+ *              or short workspace OQ_ERR_WORKSPACE -- all on the host copy before anything is launched: on any refusal no
+ *              output is touched.
+ *   workspace  oq_abs_stats_many_half_workspace_bytes(items_host, count) =
+ *                  count * max over the items of (min(T, 64) * K) * 8   (the partial sums and maxima, one slot per item)
+ *                + 256.
+ *              The query returns 0 for a table outside the bounds (null, count, T, K, ldx of an item).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* X;
+    int64_t T, K, ldx;
+    float* abs_sum;
+    float* absmax;
+} oq_abs_stats_item;
+size_t oq_abs_stats_many_half_workspace_bytes(const oq_abs_stats_item* items_host, int64_t count);
+int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq_abs_stats_item* items_device, int64_t count,
+                                   int32_t xtype /* oq_wtype */, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

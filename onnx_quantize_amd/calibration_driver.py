@@ -11,6 +11,8 @@ through the calibrator (`_set_qparams`, :254-285) and once to concatenate the GP
                        (the running form of gptq.py:246-260: the same H as the reference's single call on the
                        concatenation, see `HessianAccumulator`);
 * SmoothQuant stats -> running per-channel absmax (`oq_absmax_f32` / `oq_absmax_h16`, smooth_quant.py:62-69);
+* search statistics -> `ops.SearchStatistics` per name in `statistics_names` (Gram matrix, |x| sums and maxima; fp16 / bf16
+                       activations through `oq_abs_stats_cols_many_h16` and the half Hessian kernels, read as they are);
 * AWQ needs the activations themselves: `keep_names` holds those (and only those) in HBM.
 
 What produces the activations is a *runner*: any callable ``runner(feed) -> {value name: tensor in HBM}``.
@@ -91,8 +93,9 @@ class ActivationStream:
     output ranges are an EMA over the batch sequence seen twice.  The stream reproduces that from the per-batch
     extrema (two fp32 values per name and batch, kept on the device) instead of from the activations.
 
-    Activations may be fp32, fp16 or bf16: ranges, absmax and Hessians read a half tensor as it is and keep fp32 results
-    (those of the upcast tensor); no fp32 copy of an activation is made for them."""
+    Activations may be fp32, fp16 or bf16: ranges, absmax, Hessians and the search statistics (`statistics_names`) read a half
+    tensor as it is and keep fp32 results (those of the upcast tensor); no fp32 copy of an activation is made for them.  A half
+    value named in `statistics_names` is always folded into its `ops.SearchStatistics`, never held."""
 
     def __init__(self, *, calibrator=None, input_names: Iterable[str] = (), output_names: Iterable[str] = (),
                  hessian_names: Iterable[str] = (), absmax_names: Iterable[str] = (), keep_names: Iterable[str] = (),
@@ -107,10 +110,12 @@ class ActivationStream:
         self.statistics: dict = {}
         # ... but only once it matters: up to `statistics_after_bytes` of them the batches are simply held (a small model's
         # walk costs nothing that way and the searches see the reference's arrays); past it, what is held is folded into the
-        # statistics and every later batch goes straight there
+        # statistics and every later batch goes straight there.  That is the rule for fp32 values; fp16 / bf16 values are folded
+        # from their first batch on and do not count towards the bytes held
         self.statistics_after_bytes = int(statistics_after_bytes)
         self._held_for_search: dict[str, list] = {}
         self._held_bytes = 0
+        self._folding = False             # the fp32 names have gone past `statistics_after_bytes`
         self._search_inputs: dict = {}
         self.hessians: dict[str, HessianAccumulator] = {}
         # 0 (default): the Hessian updates of a batch in one grouped launch chain per element type (fp32 activations take
@@ -199,23 +204,31 @@ class ActivationStream:
             cur = ops.absmax(x if x.dtype in (torch.float32, torch.float16, torch.bfloat16) else x.to(torch.float32))
             self.absmax[name] = cur if name not in self.absmax else torch.maximum(self.absmax[name], cur)
         names = sorted(self.statistics_names & activations.keys())
-        if names and not self.statistics and self._held_bytes <= self.statistics_after_bytes:
-            for name in names:
+        # fp16 / bf16 values go straight into their statistics as they arrive (ops.SearchStatistics reads them as they are, no fp32
+        # copy) and are never held, whatever `statistics_after_bytes` says: the array searches have no half route.  What happens
+        # to the fp32 names does not depend on them.
+        fold = [name for name in names if activations[name].dtype in (torch.float16, torch.bfloat16)]
+        full = [name for name in names if name not in fold]
+        if full and not self._folding and self._held_bytes <= self.statistics_after_bytes:
+            for name in full:
                 self._held_for_search.setdefault(name, []).append(activations[name])
                 self._held_bytes += activations[name].numel() * activations[name].element_size()
             if self._held_bytes > self.statistics_after_bytes:         # too much to hold: fold what is there, stream from now on
+                self._folding = True
                 held, self._held_for_search = self._held_for_search, {}
                 for name, batches in held.items():
                     self.statistics[name] = ops.SearchStatistics(batches[0].shape[-1], batches[0].device)
                 for i in range(max(len(b) for b in held.values())):
                     part = [n for n in held if i < len(held[n])]
                     ops.SearchStatistics.add_many([self.statistics[n] for n in part], [held[n][i] for n in part])
-        elif names:
-            for name in names:
+        elif full:
+            fold = sorted(fold + full)
+        if fold:
+            for name in fold:
                 if name not in self.statistics:
                     x = activations[name]
                     self.statistics[name] = ops.SearchStatistics(x.shape[-1], x.device)
-            ops.SearchStatistics.add_many([self.statistics[n] for n in names], [activations[n] for n in names])
+            ops.SearchStatistics.add_many([self.statistics[n] for n in fold], [activations[n] for n in fold])
         for name in self.keep_names & activations.keys():
             self._kept.setdefault(name, []).append(activations[name])
         self.batches += 1
@@ -251,8 +264,8 @@ class ActivationStream:
 
     def search_input(self, name: str):
         """What the AWQ / SmoothQuant searches get for the value `name` (`statistics_names`): its batches concatenated along axis
-        0 while the walk could hold them (calibrate.py:301-302), its `ops.SearchStatistics` once it could not.  One object per
-        name, whoever asks."""
+        0 while the walk could hold them (calibrate.py:301-302), its `ops.SearchStatistics` once it could not -- and always for an
+        fp16 / bf16 value.  One object per name, whoever asks."""
         if name not in self._search_inputs:
             import torch
             if name in self.statistics:

@@ -136,6 +136,8 @@ HALF_PROTOTYPES = {
     "oq_minmax_collect_many_h16": (_i32, [_p, _i64, _i32, _f64, _p, _sz, _p]),
     "oq_absmax_half_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "oq_absmax_h16": (_i32, [_p, _i32, _i64, _i64, _i64, _i32, _p, _p, _sz, _p]),
+    "oq_abs_stats_many_half_workspace_bytes": (_sz, [_p, _i64]),
+    "oq_abs_stats_cols_many_h16": (_i32, [_p, _p, _i64, _i32, _p, _sz, _p]),
 }
 
 _lock = threading.Lock()

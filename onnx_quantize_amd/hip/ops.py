@@ -862,6 +862,42 @@ def absmax(x: torch.Tensor, per_row: bool = False) -> torch.Tensor:
     return out
 
 
+def abs_stats_accumulate_many(xs, abs_sums, absmaxes) -> None:
+    """awq.py:47-50 / smooth_quant.py:62-69 as running statistics for a list of fp16 / bf16 tensors of ONE dtype, in ONE C call
+    (`oq_abs_stats_cols_many_h16`, csrc/abs_stats_half.hip: two launches for the whole list): ``xs[i]`` [..., K_i] is read as it
+    is, once, and folded into the fp32 ``abs_sums[i]`` [K_i] (+= sum over rows of |x|) and ``absmaxes[i]`` [K_i] (NaN-propagating
+    maximum with max over rows of |x|), both updated in place.  The results are, bit for bit, those of the fp32 route on
+    ``xs[i].float()``: `oq_abs_sum_cols_f32` accumulating, and ``torch.maximum(running, absmax(x.float()))``.
+    The 48-byte items travel in one small host-to-device copy per call (none for a list of one)."""
+    xs, abs_sums, absmaxes = list(xs), list(abs_sums), list(absmaxes)
+    if not xs or not (len(xs) == len(abs_sums) == len(absmaxes)):
+        raise ValueError("abs_stats_accumulate_many needs equally long, non-empty lists")
+    dtype = xs[0].dtype if isinstance(xs[0], torch.Tensor) else None
+    rows, keep = [], []
+    for i, (x, sm, mx) in enumerate(zip(xs, abs_sums, absmaxes)):
+        _require_device(x, "x")
+        if x.dtype not in _HALF_WTYPE or dtype not in _HALF_WTYPE:
+            raise TypeError(f"abs_stats_accumulate_many takes fp16 / bf16 tensors, got {x.dtype if dtype in _HALF_WTYPE else dtype}")
+        if x.dtype != dtype:
+            raise TypeError(f"abs_stats_accumulate_many takes tensors of one dtype per call, got {dtype} and {x.dtype}")
+        if x.dim() < 1 or x.numel() == 0:
+            raise ValueError(f"abs_stats_accumulate_many: x[{i}] is empty ({tuple(x.shape)})")
+        x2, ldx = _row_major(x.reshape(-1, x.shape[-1]))
+        t, k = x2.shape
+        for name, out in (("abs_sums", sm), ("absmaxes", mx)):
+            _require_device(out, f"{name}[{i}]", torch.float32)
+            if out.shape != (k,) or not out.is_contiguous():
+                raise ValueError(f"{name}[{i}] must be a contiguous [{k}] tensor")
+        rows.append((x2.data_ptr(), t, k, ldx, sm.data_ptr(), mx.data_ptr()))
+        keep.append(x2)
+    lib = L.load()
+    host = np.asarray(rows, dtype=np.int64)
+    dev = torch.from_numpy(host).to(keep[0].device) if len(rows) > 1 else None          # 48 bytes per item, one blocking copy
+    hp = C.c_void_p(host.ctypes.data)
+    ws = _workspace(lib.oq_abs_stats_many_half_workspace_bytes(hp, len(rows)), keep[0].device)
+    L.check(lib.oq_abs_stats_cols_many_h16(hp, _ptr(dev), len(rows), _HALF_WTYPE[dtype], _ptr(ws), ws.numel(), _stream()))
+
+
 # ----------------------------------------------------------------------------- N2: AWQ / SmoothQuant searches
 def _flat_inputs(x: torch.Tensor) -> torch.Tensor:
     _require_device(x, "inputs", torch.float32)
@@ -926,7 +962,10 @@ class SearchStatistics:
     held): `gram` = (2 / rows) X^T X (the Hessian update rule of gptq.py:246-260 with n counting ROWS), `abs_sum[k]` = sum_t |x[t, k]|
     (awq.py:47-50 divides by the rows), `absmax[k]` = max_t |x[t, k]| (smooth_quant.py:62-69), `rows`.  `divide(scale)` is the
     reference's in-place rescale of the stored input (`node.meta["input"] /= scale`, awq.py:191 / smooth_quant.py:121) in these
-    terms: the next consumer of the same value searches on what the previous one left."""
+    terms: the next consumer of the same value searches on what the previous one left.
+
+    Batches may be fp32, fp16 or bf16: a half batch is read as it is (`abs_stats_accumulate_many`, `hessian_accumulate`) into the
+    same fp32 statistics -- `abs_sum` and `absmax` with the bits the upcast batch gives, `gram` within the Hessian tolerance."""
 
     def __init__(self, k: int, device):
         self.gram = torch.zeros((k, k), dtype=torch.float32, device=device)
@@ -935,6 +974,13 @@ class SearchStatistics:
         self.rows = 0
 
     def add(self, x: torch.Tensor) -> None:
+        """Fold one batch ``x`` [samples, ..., K] in.  An fp16 / bf16 ``x`` is read as it is: one `abs_stats_accumulate_many` call
+        of one item (both |x| statistics in one pass, the bits of the fp32 route on ``x.float()``) and `hessian_accumulate` on the
+        half tensor; no fp32 copy is made."""
+        if isinstance(x, torch.Tensor) and x.dtype in _HALF_WTYPE:
+            abs_stats_accumulate_many([x], [self.abs_sum], [self.absmax])
+            self.rows = hessian_accumulate(x.reshape(-1, x.shape[-1]), self.gram, self.rows)
+            return
         x2 = _flat_inputs(x if x.dtype == torch.float32 else x.to(torch.float32))
         x2, ldx = _row_major(x2)
         t, k = x2.shape
@@ -946,19 +992,31 @@ class SearchStatistics:
 
     @staticmethod
     def add_many(stats: "list[SearchStatistics]", xs) -> None:
-        """`add` for several values of one batch: the Gram updates in ONE grouped launch chain (`hessian_accumulate_many`: a batch of
-        a small model is dozens of small products, launch-bound one at a time)."""
+        """`add` for several values of one batch: the Gram updates in ONE grouped launch chain per element type
+        (`hessian_accumulate_many`: a batch of a small model is dozens of small products, launch-bound one at a time), and the |x|
+        statistics of the fp16 / bf16 values in one `abs_stats_accumulate_many` call per element type -- those are read as they
+        are, no fp32 copy is made.  fp32 values take the per-tensor |x| kernels."""
         flat = []
         for x in xs:
+            if isinstance(x, torch.Tensor) and x.dtype in _HALF_WTYPE:
+                _require_device(x, "inputs")
+                flat.append(_row_major(x.reshape(-1, x.shape[-1]))[0])
+                continue
             x2 = _flat_inputs(x if x.dtype == torch.float32 else x.to(torch.float32))
             flat.append(_row_major(x2)[0])
         lib = L.load()
-        for st, x2 in zip(stats, flat):
+        half: dict = {}                   # element type -> positions
+        for i, (st, x2) in enumerate(zip(stats, flat)):
+            if x2.dtype in _HALF_WTYPE:
+                half.setdefault(x2.dtype, []).append(i)
+                continue
             t, k = x2.shape
             ws = _workspace(lib.oq_abs_sum_cols_workspace_bytes(k), x2.device)
             L.check(lib.oq_abs_sum_cols_f32(_ptr(x2), t, k, x2.stride(0), _ptr(st.abs_sum), 1, _ptr(ws), ws.numel(), _stream()))
             st.absmax = torch.maximum(st.absmax, absmax(x2))
-        if hessian_method() in ("auto", "f16x3"):
+        for idx in half.values():
+            abs_stats_accumulate_many([flat[i] for i in idx], [stats[i].abs_sum for i in idx], [stats[i].absmax for i in idx])
+        if half or hessian_method() in ("auto", "f16x3"):                 # the method does not concern half items
             for st, n in zip(stats, hessian_accumulate_many(flat, [st.gram for st in stats], [st.rows for st in stats])):
                 st.rows = n
         else:
@@ -973,7 +1031,16 @@ class SearchStatistics:
         self.gram /= s.reshape(1, -1)
 
 
+def _search_weight(w):
+    """The searches run in fp32: an fp16 / bf16 ``w`` takes ONE device cast, `w.float()`, as `gptq_quantize` does (exact, so the
+    result is that of the fp32 weight with the same values)."""
+    if isinstance(w, torch.Tensor) and w.is_cuda and w.dtype in _HALF_WTYPE:
+        return w.float()
+    return w
+
+
 def _stats_args(stats: "SearchStatistics", w, qtype, group_size):
+    w = _search_weight(w)
     _require_device(w, "w", torch.float32)
     k = stats.gram.shape[0]
     if w.dim() != 2 or w.shape[0] != k:
@@ -988,7 +1055,8 @@ def _stats_args(stats: "SearchStatistics", w, qtype, group_size):
 
 def awq_scale_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
                            reduce_range=False, n_grid: int = 20):
-    """`awq_scale_search` from running statistics (oq_awq_scale_search_stats_f32): (best_scale [K] on device, losses[n_grid])."""
+    """`awq_scale_search` from running statistics (oq_awq_scale_search_stats_f32): (best_scale [K] on device, losses[n_grid]).
+    An fp16 / bf16 ``w`` is cast once (`w.float()`); the arithmetic of the search is fp32."""
     w2, ldw, k, n, gs = _stats_args(stats, w, qtype, group_size)
     lib = L.load()
     dev = w2.device
@@ -1005,7 +1073,8 @@ def awq_scale_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: st
 
 def awq_clip_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
                           reduce_range=False):
-    """`awq_clip_search` from running statistics (oq_awq_clip_search_stats_f32): (best clip_ratio, losses[10])."""
+    """`awq_clip_search` from running statistics (oq_awq_clip_search_stats_f32): (best clip_ratio, losses[10]).
+    An fp16 / bf16 ``w`` is cast once (`w.float()`)."""
     w2, ldw, k, n, gs = _stats_args(stats, w, qtype, group_size)
     lib = L.load()
     dev = w2.device
@@ -1020,13 +1089,16 @@ def awq_clip_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str
 
 
 def smooth_quant_scale_stats(stats: "SearchStatistics", w: torch.Tensor, alpha: float) -> torch.Tensor:
-    """`smooth_quant_scale` from the running per-channel absmax: the kernel's column absmax of a one-row matrix is that row."""
+    """`smooth_quant_scale` from the running per-channel absmax: the kernel's column absmax of a one-row matrix is that row.
+    An fp16 / bf16 ``w`` is cast once (`w.float()`)."""
     return smooth_quant_scale(stats.absmax.reshape(1, -1), w, alpha)
 
 
 def smooth_quant_scale(x: torch.Tensor, w: torch.Tensor, alpha: float) -> torch.Tensor:
-    """pre_passes/smooth_quant.py:62-74, :111-113 (oq_smooth_quant_scale_f32): the smoothing scale [K] on the device."""
+    """pre_passes/smooth_quant.py:62-74, :111-113 (oq_smooth_quant_scale_f32): the smoothing scale [K] on the device.  ``x`` is
+    fp32; an fp16 / bf16 ``w`` is cast once (`w.float()`)."""
     x2, ldx = _row_major(_flat_inputs(x))
+    w = _search_weight(w)
     _require_device(w, "w", torch.float32)
     t, k = x2.shape
     if w.dim() != 2 or w.shape[0] != k:           # the kernel reads K rows of W: a shorter W would be read out of bounds
