@@ -1,5 +1,5 @@
 /*
- * oq_hip_half.h -- half-precision extension of the C ABI of oq_hip.h: RTN on fp16 / bf16 weights, the GPTQ Hessian and the
+ * oq_hip_half.h -- half-precision extension of the C ABI of oq_hip.h: RTN and HQQ on fp16 / bf16 weights, the GPTQ Hessian and the
  * calibration statistics (running min / max, absmax, the |x| column statistics of the AWQ / SmoothQuant searches) of fp16 / bf16
  * activations, all read as they are.
  *
@@ -81,6 +81,29 @@ typedef struct {
 int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn_ptrs_h16* table_device, int64_t count,
                                  int32_t wtype, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int64_t group_size,
                                  int32_t symmetric, int32_t reduce_range, float clip_ratio, int32_t layout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N2  core/_algorithms/hqq.py:106-213  optimize_weights + the final quantization on W.astype(np.float32), without the fp32
+ *     copy: replaces the cast followed by oq_hqq_optimize_f32 (oq_hip.h).  Both conversions to fp32 are exact and the
+ *     arithmetic of HQQ stays fp32, so the result is DEFINED as that of oq_hqq_optimize_f32 on the upcast matrix: the integers
+ *     (both layouts), the float zero points and `rounds` match it bit for bit on every route.  The kernels keep the fp32
+ *     kernels' work split (one thread per (column, k-group), 256 columns per block), so the float64 partial sums of
+ *     |w - w_r|, their fold and with them every `best` / early-stop decision are the same.
+ *
+ *   W          [K, N], 2 bytes per element of type `wtype`, leading dimension ldw >= N (elements), 2-byte aligned; no other
+ *              alignment is needed (every lane reads its own column, 2 bytes a row).
+ *   routes     group_size 16 / 32 / 64 / 128 and 1 <= iters <= 32: all rounds in one pass over W, a group's values held in
+ *              registers as fp32 (three launches), as for fp32.  group_size 256: the same one pass, the group held as
+ *              PACKED 2-byte elements (128 registers) -- oq_hqq_optimize_f32 has no such route and re-reads W every round.
+ *              Everything else, and per_round_launches != 0: one launch pair per round (2 * iters + 1 launches).
+ *   arguments  every other argument, the workspace (oq_hqq_workspace_bytes, 8-byte aligned), the statuses and the messages
+ *              are those of oq_hqq_optimize_f32; in addition an unknown wtype and a W that is not 2-byte aligned are
+ *              OQ_ERR_INVALID_ARGUMENT.  Everything is refused on the host before any launch: no output is touched.
+ * ------------------------------------------------------------------------------------------- */
+int32_t oq_hqq_optimize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw /* elements */, int64_t group_size,
+                            int32_t reduce_range, const float* scale, const float* zero_point_in, double lp_norm, double beta,
+                            double kappa, int32_t iters, int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout,
+                            float* zero_point_out, int32_t* rounds_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * G1  core/_algorithms/gptq.py:246-260  _accumulate_hessian on inp.astype(np.float32) (:257), without the fp32 copy:

@@ -61,7 +61,8 @@ class HqqConfig(AlgorithmConfig):
 def _hqq_quantize(w_f: np.ndarray, quant_type: QuantType, group_size: int, reduce_range: bool = False, clip_ratio: float = 1.0,
                   mse: bool = False, scale_dtype: np.dtype = np.float32, zp_dtype: np.dtype = np.float32, lp_norm: float = 0.7,
                   beta: float = 1e1, kappa: float = 1.01, iters: int = 20, early_stop: bool = True):
-    """hqq.py:147-213 through oq_hqq_optimize_f32: (q [K, N], scale [N*K/g, 1], zero_point [N*K/g, 1] float)."""
+    """hqq.py:147-213 through oq_hqq_optimize_f32 / _h16: (q [K, N], scale [N*K/g, 1], zero_point [N*K/g, 1] float).  An
+    np.float16 array travels and is read as its 2-byte elements: the result of the fp32 array it upcasts to, bit for bit."""
     import torch
 
     from ..hip import ops
@@ -72,7 +73,7 @@ def _hqq_quantize(w_f: np.ndarray, quant_type: QuantType, group_size: int, reduc
     w = np.asarray(w_f)
     from ..staging import upload
 
-    wd = upload(w)
+    wd = upload(w, keep_half=True)
     q, s, z, _ = ops.hqq_quantize(wd, -1 if group_size is None else group_size, bool(reduce_range), float(clip_ratio), bool(mse),
                                   float(lp_norm), float(beta), float(kappa), int(iters), bool(early_stop))
     from ..staging import download

@@ -15,9 +15,30 @@
 // agree to a few ulp and an integer may move where w / s + z lands within that distance of a tie; the row means
 // use NumPy's summation tree (8 strided partial sums per <= 128 elements, halves above) to stay as close as
 // possible.  tests/test_hqq_gpu.py states the tolerances.
+//
+// Element types: W is fp32, fp16 or bf16 (oq_hqq_optimize_h16, oq_hip_half.h); the 2-byte types are read as they are and
+// converted exactly at the load, the arithmetic is the fp32 one in every instantiation.  The work split (one thread = one
+// (column, k-group) row, 256 columns per block, grid (ceil(N / 256), K / g)) is the same for all three, so the float64 partials
+// of sum |w - w_r|, their fold and every decision are those of the fp32 kernels on the upcast matrix: the same bits.
 #include "oq_common.hpp"
 
+#include "../../include/oq_hip_half.h"
+
 namespace oq {
+
+// ------------------------------------------------------------------------------------ element types
+struct HqqF32 {
+    typedef float raw;
+    static __device__ __forceinline__ float one(float b) { return b; }
+};
+struct HqqF16 {
+    typedef uint16_t raw;
+    static __device__ __forceinline__ float one(uint16_t b) { return static_cast<float>(__builtin_bit_cast(_Float16, b)); }
+};
+struct HqqBF16 {   // the upper half of an fp32
+    typedef uint16_t raw;
+    static __device__ __forceinline__ float one(uint16_t b) { return __uint_as_float(static_cast<uint32_t>(b) << 16); }
+};
 
 struct HqqCtrl {
     double best_err;
@@ -28,7 +49,7 @@ struct HqqCtrl {
 };
 
 struct HqqArgs {
-    const float* W;
+    const void* W;        // [K, N] of the kernel's element type, leading dimension ldw (elements)
     int64_t K, N, ldw, g, kgroups;
     const float* scale;   // [N * kgroups], entry n * kgroups + kg (rtn.py:98-109 layout)
     float* zp_cur;        // zero points of the round being evaluated
@@ -105,6 +126,7 @@ __device__ __forceinline__ float hqq_shrink(float d, float inv_beta, float expo)
     return __builtin_copysignf(m, d);
 }
 
+template <typename E>
 __global__ __launch_bounds__(256) void hqq_round_kernel(const HqqArgs a) {
     __shared__ double s_part[4];
     const int64_t col = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -123,9 +145,9 @@ __global__ __launch_bounds__(256) void hqq_round_kernel(const HqqArgs a) {
         const float z = a.zp_cur[r];
         const float inv = 1.0f / a.scale[r];                               // hqq.py:120
         const float ninv = -inv, rr = refined_rcp(inv);                    // the row's divisor of :125, see div_refined
-        const float* w = a.W + kg * a.g * a.ldw + col;
+        const typename E::raw* w = static_cast<const typename E::raw*>(a.W) + kg * a.g * a.ldw + col;
         const float zmean = pairwise_row(a.g, [&](int64_t t) {
-            const float x = w[t * a.ldw];
+            const float x = E::one(w[t * a.ldw]);
             const float wq = nmin(nmax(rintf(x * inv + z), a.qmin), a.qmax);   // :124
             const float wr = div_refined(wq - z, ninv, rr);                    // :125 (wq - z) / inv
             const float d = x - wr;
@@ -158,9 +180,15 @@ constexpr int kHqqFusedMaxIters = 32;
 
 struct HqqBetas { float inv_beta[kHqqFusedMaxIters]; };
 
-template <int G>
+// The tile: G fp32 registers, the 2-byte types converted once at the load (no cost per round).  G = 256 exists for the 2-byte
+// types only and keeps the tile PACKED, elements 2 i and 2 i + 1 of the group in one register (128 registers; as fp32 the tile
+// alone would be the whole budget of two waves per SIMD): an element is unpacked where a round uses it.
+template <typename E, int G>
 __global__ __launch_bounds__(256, 2) void hqq_rounds_reg_kernel(const HqqArgs a, const float* zero_point_in, float* traj /* [iters + 1][rows] */,
                                                                double* partial /* [iters][parts] */, const HqqBetas betas, int32_t iters) {
+    typedef typename E::raw raw;
+    constexpr bool kPacked = G > 128;
+    static_assert(G % 8 == 0 && G <= 256 && (!kPacked || sizeof(raw) == 2), "register tile");
     __shared__ double s_part[4];
     const int64_t col = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     const int64_t kg = blockIdx.y;
@@ -172,12 +200,28 @@ __global__ __launch_bounds__(256, 2) void hqq_rounds_reg_kernel(const HqqArgs a,
     const int64_t part = static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x;
     // wave-uniform row base + one 32-bit lane offset for all G loads (64-bit per-lane addresses for 128 rows would need 256
     // registers before the first value has landed)
-    const char* base = reinterpret_cast<const char*>(a.W + kg * G * a.ldw);
-    const uint32_t lane_off = static_cast<uint32_t>(cc) * 4u;
-    const int64_t row_bytes = a.ldw * 4;
-    float x[G];
+    const char* base = reinterpret_cast<const char*>(static_cast<const raw*>(a.W) + kg * G * a.ldw);
+    const uint32_t lane_off = static_cast<uint32_t>(cc) * static_cast<uint32_t>(sizeof(raw));
+    const int64_t row_bytes = a.ldw * static_cast<int64_t>(sizeof(raw));
+    float x[kPacked ? 1 : G];
+    uint32_t xp[kPacked ? G / 2 : 1];
+    (void)x; (void)xp;
+    if constexpr (kPacked) {
+        // 16 loads in flight, then their 8 packed registers, pinned HERE: left alone all 256 loads are issued first, each into a
+        // register of its own, the packing sinks in front of the first round and the tile spills on the way
 #pragma unroll
-    for (int t = 0; t < G; ++t) x[t] = *reinterpret_cast<const float*>(base + t * row_bytes + lane_off);
+        for (int tb = 0; tb < G; tb += 16) {
+#pragma unroll
+            for (int u = 0; u < 16; u += 2)
+                xp[(tb + u) / 2] = static_cast<uint32_t>(*reinterpret_cast<const raw*>(base + (tb + u) * row_bytes + lane_off)) |
+                                   (static_cast<uint32_t>(*reinterpret_cast<const raw*>(base + (tb + u + 1) * row_bytes + lane_off)) << 16);
+            asm volatile("" : "+v"(xp[tb / 2]), "+v"(xp[tb / 2 + 1]), "+v"(xp[tb / 2 + 2]), "+v"(xp[tb / 2 + 3]), "+v"(xp[tb / 2 + 4]),
+                              "+v"(xp[tb / 2 + 5]), "+v"(xp[tb / 2 + 6]), "+v"(xp[tb / 2 + 7]));
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < G; ++t) x[t] = E::one(*reinterpret_cast<const raw*>(base + t * row_bytes + lane_off));
+    }
     float z = zero_point_in[r];
     const float inv = 1.0f / a.scale[r];                                       // hqq.py:120
     const float ninv = -inv, rr = refined_rcp(inv);                            // the row's divisor of :125, see div_refined
@@ -195,26 +239,38 @@ __global__ __launch_bounds__(256, 2) void hqq_rounds_reg_kernel(const HqqArgs a,
         // One 8-element group at a time: every group reads the zero point and 1 / scale through its own opaque copy, so its
         // work cannot be hoisted in front of the previous group's (left alone, all G / 8 independent groups are interleaved and
         // G = 128 spills 600+ bytes per lane).
+        // G = 256: two such leaves of 128 elements, left + right (pairwise_row for n = 256).
         float acc[8];
+        float leaves = 0.f;
+        (void)leaves;
 #pragma unroll
         for (int t0 = 0; t0 < G; t0 += 8) {
             float zg = z, ig = inv_r, ng = ninv, rg = rr;
             if (t0 == 0) asm volatile("" : "+v"(zg), "+v"(ig), "+v"(ng), "+v"(rg));
             else asm volatile("" : "+v"(zg), "+v"(ig), "+v"(ng), "+v"(rg) : "v"(acc[0]), "v"(acc[3]), "v"(acc[7]));   // ... and AFTER the previous group is folded
+            // the packed tile: the unpacked values do not change from round to round either, and kept they are the fp32 tile
+            if constexpr (kPacked) asm volatile("" : "+v"(xp[t0 / 2]), "+v"(xp[t0 / 2 + 1]), "+v"(xp[t0 / 2 + 2]), "+v"(xp[t0 / 2 + 3]));
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float xv = x[t0 + j];
+                float xv;
+                if constexpr (kPacked) xv = E::one(static_cast<raw>(xp[(t0 + j) / 2] >> (16 * (j & 1))));
+                else xv = x[t0 + j];
                 const float wq = nmin(nmax(rintf(xv * ig + zg), a.qmin), a.qmax);   // :124
                 const float wr = div_refined(wq - zg, ng, rg);                        // :125 (wq - zg) / inv
                 const float d = xv - wr;
                 abs_sum += static_cast<double>(fabsf(d));                             // :131
                 const float we = hqq_shrink(d, inv_beta, a.expo);                     // :126
                 const float v = wq - (xv - we) * ig;                                  // :140
-                acc[j] = t0 == 0 ? v : acc[j] + v;     // NumPy's pairwise sum of a row of <= 128 elements: 8 strided partial sums
+                acc[j] = t0 % 128 == 0 ? v : acc[j] + v;     // NumPy's pairwise sum of a row of <= 128 elements: 8 strided partial sums
+            }
+            if constexpr (kPacked) {
+                if (t0 == 120) leaves = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));   // the left leaf
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        float zmean = (((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]))) / static_cast<float>(G);
+        float zmean = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+        if constexpr (kPacked) zmean = leaves + zmean;
+        zmean = zmean / static_cast<float>(G);
         // the row mean is complete HERE: left alone the optimiser sinks the shrink / mean half of every element below the
         // error reduction and its barrier and keeps d and w_q of all G elements alive across it (2 G registers: spills at 128)
         asm volatile("" : "+v"(zmean) : : "memory");
@@ -309,6 +365,7 @@ __global__ void hqq_init_kernel(HqqCtrl* ctrl) {
 
 // After the last round: settle `best` and quantize with it (hqq.py:163-171: round(w / s + z), float zero point
 // inside the rounding, no int32 cast).  q is the [K, N] one-value-per-byte array `_post_process_array` returns.
+template <typename E>
 __global__ __launch_bounds__(256) void hqq_finish_kernel(const HqqArgs a, uint8_t* q, float* zp_out, int32_t layout) {
     const int64_t col = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     const int64_t kg = blockIdx.y;
@@ -320,7 +377,7 @@ __global__ __launch_bounds__(256) void hqq_finish_kernel(const HqqArgs a, uint8_
     zp_out[r] = z;
     if (q == nullptr) return;
     const float s = a.scale[r];
-    const float* w = a.W + kg * a.g * a.ldw + col;
+    const typename E::raw* w = static_cast<const typename E::raw*>(a.W) + kg * a.g * a.ldw + col;
     if (layout == OQ_LAYOUT_NBITS) {
         // qrules/_common.py:72-87: the (column, k-group) chunk is g / 2 consecutive bytes, even k in the low nibble
         uint8_t* o = q + r * (a.g / 2);
@@ -328,7 +385,7 @@ __global__ __launch_bounds__(256) void hqq_finish_kernel(const HqqArgs a, uint8_
             uint32_t word = 0;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float v = nmin(nmax(rintf(w[(t + j) * a.ldw] / s + z), a.qmin), a.qmax);
+                const float v = nmin(nmax(rintf(E::one(w[(t + j) * a.ldw]) / s + z), a.qmin), a.qmax);
                 word |= (static_cast<uint32_t>(v) & 0xfu) << (4 * j);
             }
             *reinterpret_cast<uint32_t*>(o + t / 2) = word;
@@ -336,50 +393,60 @@ __global__ __launch_bounds__(256) void hqq_finish_kernel(const HqqArgs a, uint8_
         return;
     }
     for (int64_t t = 0; t < a.g; ++t) {
-        const float v = nmin(nmax(rintf(w[t * a.ldw] / s + z), a.qmin), a.qmax);
+        const float v = nmin(nmax(rintf(E::one(w[t * a.ldw]) / s + z), a.qmin), a.qmax);
         q[(kg * a.g + t) * a.N + col] = static_cast<uint8_t>(v);
     }
 }
 
-}  // namespace oq
-
-extern "C" {
-
-using namespace oq;
-
-size_t oq_hqq_workspace_bytes(int64_t K, int64_t N, int64_t group_size) {
-    if (!oq::matrix_ok(K, N, N)) return 0;
-    int64_t g = group_size > K ? K : group_size;
-    if (g == -1) g = K;
-    if (g <= 0 || K % g != 0) return 0;
-    const int64_t rows = N * (K / g);
-    const int64_t parts = ceil_div(N, 256) * (K / g);
-    // per-round route: three zero-point arrays + one partial per workgroup; one-pass route (g = 16 .. 128, <= 32 rounds): the
-    // zero points of every round + the partials of every round
-    const size_t per_round = static_cast<size_t>(rows) * 4 * 3 + static_cast<size_t>(parts) * 8;
-    const size_t one_pass = static_cast<size_t>(rows) * 4 * (kHqqFusedMaxIters + 1) + static_cast<size_t>(parts) * 8 * kHqqFusedMaxIters;
-    return (per_round > one_pass ? per_round : one_pass) + 1024;
+template <typename E>
+static void hqq_launch_rounds(int64_t g, dim3 grid, hipStream_t s, const HqqArgs& a, const float* zero_point_in, float* traj, const HqqBetas& betas,
+                              int32_t iters) {
+    switch (g) {
+        case 16: hipLaunchKernelGGL((hqq_rounds_reg_kernel<E, 16>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
+        case 32: hipLaunchKernelGGL((hqq_rounds_reg_kernel<E, 32>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
+        case 64: hipLaunchKernelGGL((hqq_rounds_reg_kernel<E, 64>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
+        case 128: hipLaunchKernelGGL((hqq_rounds_reg_kernel<E, 128>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
+        default:   // 256: the packed tile of the 2-byte types (hqq_optimize sends fp32 there never)
+            if constexpr (sizeof(typename E::raw) == 2)
+                hipLaunchKernelGGL((hqq_rounds_reg_kernel<E, 256>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters);
+            break;
+    }
 }
 
-int32_t oq_hqq_optimize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, int64_t group_size, int32_t reduce_range,
+// oq_hqq_optimize_f32 and oq_hqq_optimize_h16: one implementation, `fn` is the entry point's name in the messages.  Every check
+// stands in front of the first device call: a refused call touches no output.
+template <typename E>
+static int32_t hqq_optimize(const char* fn, const void* W, int64_t K, int64_t N, int64_t ldw, int64_t group_size, int32_t reduce_range,
                             const float* scale, const float* zero_point_in, double lp_norm, double beta, double kappa, int32_t iters,
-                            int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout, float* zero_point_out, int32_t* rounds_out,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-    OQ_REQUIRE(W && scale && zero_point_in && zero_point_out && matrix_ok(K, N, ldw), OQ_ERR_INVALID_ARGUMENT,
-               "oq_hqq_optimize_f32: bad argument");
-    OQ_REQUIRE(iters >= 0 && beta > 0.0, OQ_ERR_INVALID_ARGUMENT, "oq_hqq_optimize_f32: iters >= 0 and beta > 0 needed");
-    OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS, OQ_ERR_INVALID_ARGUMENT, "oq_hqq_optimize_f32: bad layout %d", layout);
+                            int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout, float* zero_point_out,
+                            int32_t* rounds_out, void* workspace, size_t workspace_bytes, void* stream) {
+    OQ_REQUIRE(W != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null W", fn);
+    OQ_REQUIRE(scale != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null scale", fn);
+    OQ_REQUIRE(zero_point_in != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null zero_point_in", fn);
+    OQ_REQUIRE(zero_point_out != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null zero_point_out", fn);
+    OQ_REQUIRE(matrix_ok(K, N, ldw), OQ_ERR_INVALID_ARGUMENT, "%s: bad shape K=%lld N=%lld ldw=%lld", fn, (long long)K, (long long)N,
+               (long long)ldw);
+    OQ_REQUIRE(iters >= 0 && beta > 0.0, OQ_ERR_INVALID_ARGUMENT, "%s: iters >= 0 and beta > 0 needed (iters=%d beta=%g)", fn, iters, beta);
+    OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS, OQ_ERR_INVALID_ARGUMENT, "%s: bad layout %d", fn, layout);
     int64_t g = group_size > K ? K : group_size;   // utils.py:19-22
     if (g == -1) g = K;
-    OQ_REQUIRE(g > 0, OQ_ERR_INVALID_ARGUMENT, "oq_hqq_optimize_f32: bad group_size %lld", (long long)group_size);
-    OQ_REQUIRE(K % g == 0, OQ_ERR_UNSUPPORTED, "oq_hqq_optimize_f32: groups that straddle columns (K %% group_size != 0) are not supported");
+    OQ_REQUIRE(g > 0, OQ_ERR_INVALID_ARGUMENT, "%s: bad group_size %lld", fn, (long long)group_size);
+    OQ_REQUIRE(K % g == 0, OQ_ERR_UNSUPPORTED, "%s: groups that straddle columns (K %% group_size != 0) are not supported (K=%lld group_size %lld)",
+               fn, (long long)K, (long long)g);
     const int64_t kgroups = K / g;
-    OQ_REQUIRE(kgroups <= 65535, OQ_ERR_UNSUPPORTED, "oq_hqq_optimize_f32: more than 65535 groups per column");
+    OQ_REQUIRE(kgroups <= 65535, OQ_ERR_UNSUPPORTED, "%s: more than 65535 groups per column", fn);
     const size_t need = oq_hqq_workspace_bytes(K, N, group_size);
     OQ_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, OQ_ERR_WORKSPACE,
-               "oq_hqq_optimize_f32: 8-byte aligned workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+               "%s: 8-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace ? workspace_bytes : static_cast<size_t>(0));
     int64_t qmin, qmax;
-    OQ_REQUIRE(qrange_host(OQ_UINT4, 0, reduce_range, &qmin, &qmax), OQ_ERR_INVALID_ARGUMENT, "oq_hqq_optimize_f32: qrange");
+    OQ_REQUIRE(qrange_host(OQ_UINT4, 0, reduce_range, &qmin, &qmax), OQ_ERR_INVALID_ARGUMENT, "%s: qrange", fn);
+    // One pass over W for all rounds where the group fits the register tile (the reference's only HQQ configurations: group
+    // sizes that are powers of two >= 16, hqq.py:66-70; 256 as packed 2-byte elements only) and the trajectory fits the
+    // workspace; same bits as the per-round loop.  iters == 0 takes the loop (no round: the given zero points).
+    const bool tile = g == 16 || g == 32 || g == 64 || g == 128 || (g == 256 && sizeof(typename E::raw) == 2);
+    const bool one_pass = tile && iters >= 1 && iters <= kHqqFusedMaxIters && !per_round_launches;
+    OQ_REQUIRE(layout == OQ_LAYOUT_KN || q_out == nullptr || ((one_pass || g % 8 == 0) && (reinterpret_cast<uintptr_t>(q_out) & 3u) == 0),
+               OQ_ERR_UNSUPPORTED, "%s: NBITS layout needs group_size %% 8 == 0 and a 4-byte aligned output", fn);
     hipStream_t s = as_stream(stream);
     const int64_t rows = N * kgroups;
     const dim3 grid(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups));
@@ -397,10 +464,7 @@ int32_t oq_hqq_optimize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, i
     a.expo = static_cast<float>(lp_norm - 1.0);
     a.round = 0; a.inv_beta = 0.f;
 
-    // One pass over W for all rounds where the group fits the register tile (the reference's only HQQ configurations: group
-    // sizes that are powers of two >= 16, hqq.py:66-70) and the trajectory fits the workspace; same bits as the loop below.
-    // iters < 0 never happens (checked above); iters == 0 takes the loop (no round: the given zero points).
-    if ((g == 16 || g == 32 || g == 64 || g == 128) && iters >= 1 && iters <= kHqqFusedMaxIters && !per_round_launches) {
+    if (one_pass) {
         float* traj = reinterpret_cast<float*>(base + 64 + parts * 8 * kHqqFusedMaxIters);
         HqqBetas betas;
         double b2 = beta;
@@ -409,54 +473,87 @@ int32_t oq_hqq_optimize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, i
             b2 *= kappa;                                         // :128
         }
         a.zp_cur = traj; a.zp_next = nullptr; a.zp_best = nullptr;
-        switch (g) {
-            case 16: hipLaunchKernelGGL((hqq_rounds_reg_kernel<16>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
-            case 32: hipLaunchKernelGGL((hqq_rounds_reg_kernel<32>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
-            case 64: hipLaunchKernelGGL((hqq_rounds_reg_kernel<64>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
-            default: hipLaunchKernelGGL((hqq_rounds_reg_kernel<128>), grid, dim3(256), 0, s, a, zero_point_in, traj, a.partial, betas, iters); break;
-        }
+        hqq_launch_rounds<E>(g, grid, s, a, zero_point_in, traj, betas, iters);
         hipLaunchKernelGGL(hqq_decide_all_kernel, dim3(1), dim3(1024), 0, s, a.partial, parts, static_cast<double>(K) * static_cast<double>(N),
                            early_stop, iters, a.ctrl);
         int32_t st1 = check_launch("hqq_rounds_reg_kernel");
         if (st1 != OQ_OK) return st1;
-        OQ_REQUIRE(layout == OQ_LAYOUT_KN || q_out == nullptr || (reinterpret_cast<uintptr_t>(q_out) & 3u) == 0, OQ_ERR_UNSUPPORTED,
-                   "oq_hqq_optimize_f32: NBITS layout needs a 4-byte aligned output");
         a.round = iters;
-        hipLaunchKernelGGL(hqq_finish_kernel, grid, dim3(256), 0, s, a, static_cast<uint8_t*>(q_out), zero_point_out, layout);
+        hipLaunchKernelGGL(hqq_finish_kernel<E>, grid, dim3(256), 0, s, a, static_cast<uint8_t*>(q_out), zero_point_out, layout);
         st1 = check_launch("hqq_finish_kernel");
         if (st1 != OQ_OK) return st1;
         if (rounds_out != nullptr &&
             hipMemcpyAsync(rounds_out, &a.ctrl->rounds, sizeof(int32_t), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return fail(OQ_ERR_LAUNCH, "oq_hqq_optimize_f32: device copy failed");
+            return fail(OQ_ERR_LAUNCH, "%s: device copy failed", fn);
         return OQ_OK;
     }
 
     // hqq.py:115-116: best = zero_point.copy(); the first round evaluates the given zero points
     if (hipMemcpyAsync(a.zp_cur, zero_point_in, static_cast<size_t>(rows) * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipMemcpyAsync(a.zp_best, zero_point_in, static_cast<size_t>(rows) * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return fail(OQ_ERR_LAUNCH, "oq_hqq_optimize_f32: device copy failed");
+        return fail(OQ_ERR_LAUNCH, "%s: device copy failed", fn);
     hipLaunchKernelGGL(hqq_init_kernel, dim3(1), dim3(1), 0, s, a.ctrl);
     double b = beta;
     for (int32_t it = 0; it < iters; ++it) {
         a.round = it;
         a.inv_beta = static_cast<float>(1.0 / b);   // (1.0 / beta) meets an fp32 array: weak scalar -> fp32
         b *= kappa;                                 // :128
-        hipLaunchKernelGGL(hqq_round_kernel, grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(hqq_round_kernel<E>, grid, dim3(256), 0, s, a);
         hipLaunchKernelGGL(hqq_decide_kernel, dim3(1), dim3(1024), 0, s, a.partial, parts, static_cast<double>(K) * static_cast<double>(N),
                            early_stop, a.ctrl);
     }
     int32_t st = check_launch("hqq_round_kernel");
     if (st != OQ_OK) return st;
     a.round = iters;
-    OQ_REQUIRE(layout == OQ_LAYOUT_KN || q_out == nullptr || (g % 8 == 0 && (reinterpret_cast<uintptr_t>(q_out) & 3u) == 0), OQ_ERR_UNSUPPORTED,
-               "oq_hqq_optimize_f32: NBITS layout needs group_size %% 8 == 0 and a 4-byte aligned output");
-    hipLaunchKernelGGL(hqq_finish_kernel, grid, dim3(256), 0, s, a, static_cast<uint8_t*>(q_out), zero_point_out, layout);
+    hipLaunchKernelGGL(hqq_finish_kernel<E>, grid, dim3(256), 0, s, a, static_cast<uint8_t*>(q_out), zero_point_out, layout);
     st = check_launch("hqq_finish_kernel");
     if (st != OQ_OK) return st;
     if (rounds_out != nullptr &&
         hipMemcpyAsync(rounds_out, &a.ctrl->rounds, sizeof(int32_t), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return fail(OQ_ERR_LAUNCH, "oq_hqq_optimize_f32: device copy failed");
+        return fail(OQ_ERR_LAUNCH, "%s: device copy failed", fn);
     return OQ_OK;
+}
+
+}  // namespace oq
+
+extern "C" {
+
+using namespace oq;
+
+size_t oq_hqq_workspace_bytes(int64_t K, int64_t N, int64_t group_size) {
+    if (!oq::matrix_ok(K, N, N)) return 0;
+    int64_t g = group_size > K ? K : group_size;
+    if (g == -1) g = K;
+    if (g <= 0 || K % g != 0) return 0;
+    const int64_t rows = N * (K / g);
+    const int64_t parts = ceil_div(N, 256) * (K / g);
+    // per-round route: three zero-point arrays + one partial per workgroup; one-pass route (g = 16 .. 256, <= 32 rounds): the
+    // zero points of every round + the partials of every round
+    const size_t per_round = static_cast<size_t>(rows) * 4 * 3 + static_cast<size_t>(parts) * 8;
+    const size_t one_pass = static_cast<size_t>(rows) * 4 * (kHqqFusedMaxIters + 1) + static_cast<size_t>(parts) * 8 * kHqqFusedMaxIters;
+    return (per_round > one_pass ? per_round : one_pass) + 1024;
+}
+
+int32_t oq_hqq_optimize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, int64_t group_size, int32_t reduce_range,
+                            const float* scale, const float* zero_point_in, double lp_norm, double beta, double kappa, int32_t iters,
+                            int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout, float* zero_point_out, int32_t* rounds_out,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    return hqq_optimize<HqqF32>("oq_hqq_optimize_f32", W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters,
+                                early_stop, per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_hqq_optimize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int64_t group_size, int32_t reduce_range,
+                            const float* scale, const float* zero_point_in, double lp_norm, double beta, double kappa, int32_t iters,
+                            int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout, float* zero_point_out, int32_t* rounds_out,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    static const char fn[] = "oq_hqq_optimize_h16";
+    OQ_REQUIRE(wtype == OQ_W_F16 || wtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
+    OQ_REQUIRE((reinterpret_cast<uintptr_t>(W) & 1u) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned", fn);
+    if (wtype == OQ_W_F16)
+        return hqq_optimize<HqqF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
+                                    per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
+    return hqq_optimize<HqqBF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
+                                 per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

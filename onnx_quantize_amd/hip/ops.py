@@ -69,7 +69,7 @@ _ARENA_MAX_STREAMS = 4
 _ARENA: dict = {}     # (device index, stream handle) -> scratch tensor, grow-only; most recently used last
 
 
-def _workspace(nbytes: int, device) -> torch.Tensor | None:
+def _workspace(nbytes: int, device, keep: bool = False) -> torch.Tensor | None:
     """Scratch memory for ONE library call on the current stream.  Nothing a call returns lives in it.
 
     Small requests come from torch's allocator.  Requests of 32 MiB and more (the factor chain of a stack of eight
@@ -78,9 +78,10 @@ def _workspace(nbytes: int, device) -> torch.Tensor | None:
     out).  Why not `torch.empty` every time: when the
     caching allocator has split its one block of that size for a smaller request in between, the next call maps a new one,
     and `hipMalloc` of 15.5 GB takes 0.36 s on the MI355X host (measured, scripts/lab_alloc_trace.py) -- with the kernels of
-    the call waiting behind it.  `release_workspaces()` hands the buffers back."""
+    the call waiting behind it.  `release_workspaces()` hands the buffers back.  ``keep``: a small request is served from that
+    buffer as well (HQQ: the trajectory of every round, about a byte per weight next to an output of one byte per weight)."""
     nbytes = max(int(nbytes), 256)
-    if nbytes < _ARENA_MIN_BYTES:
+    if nbytes < _ARENA_MIN_BYTES and not keep:
         return torch.empty(nbytes, dtype=torch.uint8, device=device)
     dev = torch.device(device)
     index = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -280,14 +281,20 @@ def fingerprint64(t: torch.Tensor) -> int:
 
 def hqq_quantize(w: torch.Tensor, group_size: int, reduce_range=False, clip_ratio=1.0, mse=False, lp_norm=0.7, beta=1e1,
                  kappa=1.01, iters=20, early_stop=True, emit_q: bool = True, layout: str = "kn", per_round_launches: bool = False):
-    """hqq.py:147-213 on the GPU: uint4 / asymmetric / group with float zero points.  ``w`` [K, N] fp32 in HBM.
+    """hqq.py:147-213 on the GPU: uint4 / asymmetric / group with float zero points.  ``w`` [K, N] fp32, fp16 or bf16 in HBM.
     Returns (q [K, N] uint8 | MatMulNBits blob [N, K/g, g/2] for layout="nbits" | None, scale [N*K/g, 1] fp32,
-    zero_point [N*K/g, 1] fp32, rounds int32[1] on device).  An fp16 / bf16 ``w`` takes one device cast, ``w.float()``
-    (exact): the arithmetic of HQQ stays fp32."""
+    zero_point [N*K/g, 1] fp32, rounds int32[1] on device).
+
+    A half-precision ``w`` gives, by definition, the result of this function on ``w.float()`` (both conversions are exact, the
+    arithmetic of HQQ stays fp32): the same integers, scales, zero points and rounds, bit for bit.  oq_hqq_optimize_h16 reads the
+    2-byte matrix as it is, rows that are only 2-byte aligned included; no fp32 copy exists.  The initial parameters come from
+    `rtn_quantize` on the half matrix; only ``mse=True`` takes its one cast, ``w.float()``, for those parameters (no half MSE
+    search) -- the HQQ kernels read the half matrix there as well.  A group of 256 runs all rounds in one pass over a half ``w``
+    (the fp32 kernels re-read W every round at that size); ``per_round_launches=True`` forces the per-round route."""
     _require_device(w, "w")
-    if w.dtype in _HALF_WTYPE:
-        w = w.float()
-    _require_device(w, "w", torch.float32)
+    half = w.dtype in _HALF_WTYPE
+    if not half:
+        _require_device(w, "w", torch.float32)
     if w.dim() != 2:
         raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
     w, ldw = _row_major(w)
@@ -310,11 +317,14 @@ def hqq_quantize(w: torch.Tensor, group_size: int, reduce_range=False, clip_rati
         q = torch.empty((n, k // g, g // 2), dtype=torch.uint8, device=dev)
     rounds = torch.zeros(1, dtype=torch.int32, device=dev)
     gs = -1 if group_size is None else int(group_size)
-    ws = _workspace(lib.oq_hqq_workspace_bytes(k, n, gs), dev)
-    L.check(lib.oq_hqq_optimize_f32(_ptr(w), k, n, ldw, gs, int(reduce_range), _ptr(scale), _ptr(zp_in), float(lp_norm),
-                                    float(beta), float(kappa), int(iters), int(early_stop), int(bool(per_round_launches)), _ptr(q),
-                                    L.OQ_LAYOUT_KN if layout == "kn" else L.OQ_LAYOUT_NBITS, _ptr(zp), _ptr(rounds),
-                                    _ptr(ws), ws.numel(), _stream()))
+    ws = _workspace(lib.oq_hqq_workspace_bytes(k, n, gs), dev, keep=True)
+    tail = (k, n, ldw, gs, int(reduce_range), _ptr(scale), _ptr(zp_in), float(lp_norm), float(beta), float(kappa), int(iters),
+            int(early_stop), int(bool(per_round_launches)), _ptr(q), L.OQ_LAYOUT_KN if layout == "kn" else L.OQ_LAYOUT_NBITS, _ptr(zp),
+            _ptr(rounds), _ptr(ws), ws.numel(), _stream())
+    if half:
+        L.check(lib.oq_hqq_optimize_h16(_ptr(w), _HALF_WTYPE[w.dtype], *tail))
+    else:
+        L.check(lib.oq_hqq_optimize_f32(_ptr(w), *tail))
     return q, scale.reshape(rows, 1), zp.reshape(rows, 1), rounds
 
 

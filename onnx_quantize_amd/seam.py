@@ -157,7 +157,8 @@ def _strategy(s) -> str:
 def _upload(name, array):
     from .staging import upload
 
-    # an fp16 weight goes up as it is: RTN reads the 2-byte matrix (ops.rtn_quantize), GPTQ / HQQ cast it once on the device
+    # an fp16 weight goes up as it is: RTN and HQQ read the 2-byte matrix (ops.rtn_quantize, ops.hqq_quantize), GPTQ casts it once
+    # on the device
     return upload(array, keep_half=True)
 
 
