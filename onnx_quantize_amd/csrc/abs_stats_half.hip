@@ -11,18 +11,13 @@
 // (16-byte) or 16 (narrower) row loads in flight: two or four of the fours, summed in row order.
 //
 // No block waits for another and nothing is atomic: stage 1 writes [chunk][k] partial sums and maxima, stage 2 folds them.
-#include "oq_common.hpp"
-
-#include "../../include/oq_hip_half.h"
+#include "half_elem.hpp"
 
 namespace oq {
 
 constexpr int kStatChunks = 64;       // awq.hip: kColChunks -- part of the sum order
 constexpr int kStatBlock = 256;       // 4 waves
 constexpr int64_t kStatFillLanes = 256 * 4 * 64 * 4;   // four waves on every SIMD of 256 CUs
-
-typedef uint32_t su32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t su32x4 __attribute__((ext_vector_type(4)));
 
 struct StatItem {   // oq_abs_stats_item with X as a 2-byte pointer
     const uint16_t* X;
@@ -44,13 +39,14 @@ __host__ __device__ __forceinline__ int stat_width(const void* X, int64_t K, int
 
 template <bool BF16>
 __device__ __forceinline__ float abs_widen(uint32_t b /* the element in the low 16 bits */) {
+    // bf16: the shift and the sign mask on the word itself; fabsf(ElemBF16::one(..)) is the same value in 7 % more instructions
     if constexpr (BF16) return __uint_as_float((b << 16) & 0x7FFFFFFFu);
-    else return fabsf(static_cast<float>(__builtin_bit_cast(_Float16, static_cast<uint16_t>(b))));
+    else return fabsf(ElemF16::one(static_cast<uint16_t>(b)));
 }
 
 template <int V> struct StatRaw;
-template <> struct StatRaw<8> { typedef su32x4 type; };
-template <> struct StatRaw<4> { typedef su32x2 type; };
+template <> struct StatRaw<8> { typedef u32x4 type; };
+template <> struct StatRaw<4> { typedef u32x2 type; };
 template <> struct StatRaw<2> { typedef uint32_t type; };
 template <> struct StatRaw<1> { typedef uint16_t type; };
 
@@ -213,20 +209,18 @@ int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq
                                    void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(sizeof(oq_abs_stats_item) == 48 && sizeof(StatItem) == sizeof(oq_abs_stats_item), "six 8-byte fields");
     // every check on the host copy, before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(xtype == OQ_W_F16 || xtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: unknown xtype %d", xtype);
+    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: unknown xtype %d", xtype);
     OQ_REQUIRE(items_host != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: null items_host");
     OQ_REQUIRE(count >= 1 && count <= 65535, OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: bad count=%lld (1 <= count <= 65535)",
                (long long)count);
     OQ_REQUIRE(items_device != nullptr || count == 1, OQ_ERR_INVALID_ARGUMENT,
                "oq_abs_stats_cols_many_h16: null items_device (it may be NULL only when count == 1)");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(items_device) & 7u) == 0, OQ_ERR_INVALID_ARGUMENT,
-               "oq_abs_stats_cols_many_h16: items_device must be 8-byte aligned");
+    OQ_REQUIRE(aligned_to(items_device, 8), OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: items_device must be 8-byte aligned");
     for (int64_t i = 0; i < count; ++i) {
         const oq_abs_stats_item& it = items_host[i];
         OQ_REQUIRE(it.X != nullptr && it.abs_sum != nullptr && it.absmax != nullptr, OQ_ERR_INVALID_ARGUMENT,
                    "oq_abs_stats_cols_many_h16: item %lld: null X / abs_sum / absmax", (long long)i);
-        OQ_REQUIRE((reinterpret_cast<uintptr_t>(it.X) & 1u) == 0 && (reinterpret_cast<uintptr_t>(it.abs_sum) & 3u) == 0 &&
-                       (reinterpret_cast<uintptr_t>(it.absmax) & 3u) == 0,
+        OQ_REQUIRE(aligned_to(it.X, 2) && aligned_to(it.abs_sum, 4) && aligned_to(it.absmax, 4),
                    OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: item %lld: X must be 2-byte aligned, abs_sum and absmax 4-byte aligned",
                    (long long)i);
         OQ_REQUIRE(matrix_ok(it.T, it.K, it.ldx), OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: item %lld: bad shape T=%lld K=%lld ldx=%lld",

@@ -1,7 +1,7 @@
 // fp32 TN GEMM on v_mfma_f32_32x32x2_f32 (see gemm_tn.hpp) and G1, the GPTQ Hessian accumulate.
 #include "gemm_tn.hpp"
 
-#include "../../include/oq_hip_half.h"
+#include "half_elem.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -420,7 +420,7 @@ size_t oq_hessian_half_workspace_bytes(int64_t T, int64_t K) {
 int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype, int64_t T, int64_t K, int64_t ldx, int64_t n_seen, int64_t n_add, float* H,
                                   void* workspace, size_t workspace_bytes, void* stream) {
     // every check before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(xtype == OQ_W_F16 || xtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: unknown xtype %d", xtype);
+    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: unknown xtype %d", xtype);
     OQ_REQUIRE(X != nullptr && H != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: null X / H");
     OQ_REQUIRE((reinterpret_cast<uintptr_t>(X) & 1u) == 0 && (reinterpret_cast<uintptr_t>(H) & 3u) == 0, OQ_ERR_INVALID_ARGUMENT,
                "oq_hessian_accumulate_h16: X must be 2-byte aligned and H 4-byte aligned");
@@ -446,7 +446,7 @@ size_t oq_hessian_many_half_workspace_bytes(const oq_hessian_item* items_host, i
 int32_t oq_hessian_accumulate_many_h16(const oq_hessian_item* items_host, const oq_hessian_item* items_device, int64_t count, int32_t xtype,
                                        void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(sizeof(oq_hessian_item) == 64, "eight 8-byte fields");
-    OQ_REQUIRE(xtype == OQ_W_F16 || xtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_many_h16: unknown xtype %d", xtype);
+    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_many_h16: unknown xtype %d", xtype);
     return launch_syrk_h16_many(reinterpret_cast<const int64_t*>(items_host), reinterpret_cast<const int64_t*>(items_device), count, xtype == OQ_W_BF16,
                                 workspace, workspace_bytes, as_stream(stream));
 }

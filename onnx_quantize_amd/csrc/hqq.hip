@@ -20,24 +20,15 @@
 // converted exactly at the load, the arithmetic is the fp32 one in every instantiation.  The work split (one thread = one
 // (column, k-group) row, 256 columns per block, grid (ceil(N / 256), K / g)) is the same for all three, so the float64 partials
 // of sum |w - w_r|, their fold and every decision are those of the fp32 kernels on the upcast matrix: the same bits.
-#include "oq_common.hpp"
-
-#include "../../include/oq_hip_half.h"
+#include "half_elem.hpp"
 
 namespace oq {
 
 // ------------------------------------------------------------------------------------ element types
+// fp16 and bf16 are ElemF16 / ElemBF16 of half_elem.hpp; fp32 has the same face
 struct HqqF32 {
     typedef float raw;
     static __device__ __forceinline__ float one(float b) { return b; }
-};
-struct HqqF16 {
-    typedef uint16_t raw;
-    static __device__ __forceinline__ float one(uint16_t b) { return static_cast<float>(__builtin_bit_cast(_Float16, b)); }
-};
-struct HqqBF16 {   // the upper half of an fp32
-    typedef uint16_t raw;
-    static __device__ __forceinline__ float one(uint16_t b) { return __uint_as_float(static_cast<uint32_t>(b) << 16); }
 };
 
 struct HqqCtrl {
@@ -436,7 +427,7 @@ static int32_t hqq_optimize(const char* fn, const void* W, int64_t K, int64_t N,
     const int64_t kgroups = K / g;
     OQ_REQUIRE(kgroups <= 65535, OQ_ERR_UNSUPPORTED, "%s: more than 65535 groups per column", fn);
     const size_t need = oq_hqq_workspace_bytes(K, N, group_size);
-    OQ_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, OQ_ERR_WORKSPACE,
+    OQ_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 8), OQ_ERR_WORKSPACE,
                "%s: 8-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace ? workspace_bytes : static_cast<size_t>(0));
     int64_t qmin, qmax;
     OQ_REQUIRE(qrange_host(OQ_UINT4, 0, reduce_range, &qmin, &qmax), OQ_ERR_INVALID_ARGUMENT, "%s: qrange", fn);
@@ -445,7 +436,7 @@ static int32_t hqq_optimize(const char* fn, const void* W, int64_t K, int64_t N,
     // workspace; same bits as the per-round loop.  iters == 0 takes the loop (no round: the given zero points).
     const bool tile = g == 16 || g == 32 || g == 64 || g == 128 || (g == 256 && sizeof(typename E::raw) == 2);
     const bool one_pass = tile && iters >= 1 && iters <= kHqqFusedMaxIters && !per_round_launches;
-    OQ_REQUIRE(layout == OQ_LAYOUT_KN || q_out == nullptr || ((one_pass || g % 8 == 0) && (reinterpret_cast<uintptr_t>(q_out) & 3u) == 0),
+    OQ_REQUIRE(layout == OQ_LAYOUT_KN || q_out == nullptr || ((one_pass || g % 8 == 0) && aligned_to(q_out, 4)),
                OQ_ERR_UNSUPPORTED, "%s: NBITS layout needs group_size %% 8 == 0 and a 4-byte aligned output", fn);
     hipStream_t s = as_stream(stream);
     const int64_t rows = N * kgroups;
@@ -547,12 +538,12 @@ int32_t oq_hqq_optimize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
                             int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout, float* zero_point_out, int32_t* rounds_out,
                             void* workspace, size_t workspace_bytes, void* stream) {
     static const char fn[] = "oq_hqq_optimize_h16";
-    OQ_REQUIRE(wtype == OQ_W_F16 || wtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(W) & 1u) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned", fn);
+    OQ_REQUIRE(half_type_ok(wtype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
+    OQ_REQUIRE(aligned_to(W, 2), OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned", fn);
     if (wtype == OQ_W_F16)
-        return hqq_optimize<HqqF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
+        return hqq_optimize<ElemF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
                                     per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
-    return hqq_optimize<HqqBF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
+    return hqq_optimize<ElemBF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
                                  per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
 }
 

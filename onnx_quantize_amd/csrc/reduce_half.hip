@@ -11,9 +11,7 @@
 // both extrema.  bf16 has no packed compare: a shift / a mask widens it exactly and v_minimum3_f32 / v_maximum3_f32 fold it,
 // two instructions per element.  A CU issues 64 lane-operations per cycle and HBM feeds it about 6.5 half elements per cycle,
 // so both stay far below the issue rate.
-#include "oq_common.hpp"
-
-#include "../../include/oq_hip_half.h"
+#include "half_elem.hpp"
 
 namespace oq {
 
@@ -21,15 +19,8 @@ constexpr int kHalfBlock = 512;       // 8 waves
 constexpr int kHalfMaxBlocks = 2048;  // <= 256 CUs x 8 blocks (cdna_hip_programming.md Guideline 11)
 constexpr int kHalfDepth = 8;         // 16-byte loads in flight per lane, as reduce.hip's stream_minmax
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) u32x4 global_u32x4;
-
-template <bool BF16>
-__device__ __forceinline__ float widen(uint16_t b) {
-    if constexpr (BF16) return __uint_as_float(static_cast<uint32_t>(b) << 16);
-    else return static_cast<float>(__builtin_bit_cast(_Float16, b));
-}
 
 // Running (min, max) of one lane over 16-byte words of eight elements.
 template <bool BF16> struct HalfRange;
@@ -102,8 +93,8 @@ __device__ __forceinline__ void half_range(const uint16_t* x, int64_t count, int
     for (; i < nvec; i += stride) acc.fold(__builtin_nontemporal_load(xv + i));
     mn = acc.lo();
     mx = acc.hi();
-    for (int64_t j = tid; j < vec_off; j += stride) { const float v = widen<BF16>(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
-    for (int64_t j = vec_off + nvec * 8 + tid; j < count; j += stride) { const float v = widen<BF16>(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
+    for (int64_t j = tid; j < vec_off; j += stride) { const float v = HalfElem<BF16>::one(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
+    for (int64_t j = vec_off + nvec * 8 + tid; j < count; j += stride) { const float v = HalfElem<BF16>::one(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
 }
 
 struct HalfDesc {   // device-resident, 24 bytes per tensor (oq_hip.h: oq_minmax_desc, x read as a 2-byte pointer)
@@ -177,8 +168,8 @@ __device__ __forceinline__ void absmax8(float (&mx)[8], const u32x4 a) {
     const uint32_t w[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        mx[2 * i] = nmax(mx[2 * i], fabsf(widen<BF16>(static_cast<uint16_t>(w[i] & 0xFFFFu))));
-        mx[2 * i + 1] = nmax(mx[2 * i + 1], fabsf(widen<BF16>(static_cast<uint16_t>(w[i] >> 16))));
+        mx[2 * i] = nmax(mx[2 * i], fabsf(HalfElem<BF16>::one(static_cast<uint16_t>(w[i] & 0xFFFFu))));
+        mx[2 * i + 1] = nmax(mx[2 * i + 1], fabsf(HalfElem<BF16>::one(static_cast<uint16_t>(w[i] >> 16))));
     }
 }
 
@@ -208,7 +199,7 @@ __global__ __launch_bounds__(512) void absmax_half_cols_partial(const uint16_t* 
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int64_t c = col0 + i * 64 + lane;
-                if (c < C && row0 + r < R) mx[i] = nmax(mx[i], fabsf(widen<BF16>(x[(row0 + r) * ldx + c])));
+                if (c < C && row0 + r < R) mx[i] = nmax(mx[i], fabsf(HalfElem<BF16>::one(x[(row0 + r) * ldx + c])));
             }
     }
 #pragma unroll
@@ -246,13 +237,11 @@ __global__ __launch_bounds__(256) void absmax_half_rows(const uint16_t* x, int64
         for (int64_t c = lane * 8; c < C; c += 512) absmax8<BF16>(mx, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + c)));
         m = nmax(nmax(nmax(mx[0], mx[1]), nmax(mx[2], mx[3])), nmax(nmax(mx[4], mx[5]), nmax(mx[6], mx[7])));
     } else {
-        for (int64_t c = lane; c < C; c += 64) m = nmax(m, fabsf(widen<BF16>(row[c])));
+        for (int64_t c = lane; c < C; c += 64) m = nmax(m, fabsf(HalfElem<BF16>::one(row[c])));
     }
     m = wave_max(m);
     if (lane == 0) out[r] = m;
 }
-
-static bool xtype_ok(int32_t xtype) { return xtype == OQ_W_F16 || xtype == OQ_W_BF16; }
 
 }  // namespace oq
 
@@ -268,9 +257,9 @@ size_t oq_minmax_half_workspace_bytes(int64_t count) {
 int32_t oq_minmax_collect_h16(const void* x, int32_t xtype, int64_t count, float* state, double momentum, void* workspace,
                               size_t workspace_bytes, void* stream) {
     // every check before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(xtype_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: unknown xtype %d", xtype);
+    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: unknown xtype %d", xtype);
     OQ_REQUIRE(x != nullptr && state != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: null x / state");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(x) & 1u) == 0 && (reinterpret_cast<uintptr_t>(state) & 3u) == 0, OQ_ERR_INVALID_ARGUMENT,
+    OQ_REQUIRE(aligned_to(x, 2) && aligned_to(state, 4), OQ_ERR_INVALID_ARGUMENT,
                "oq_minmax_collect_h16: x must be 2-byte aligned and state 4-byte aligned");
     OQ_REQUIRE(count_ok(count), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: bad count=%lld (1 <= count <= 2^40)", (long long)count);
     OQ_REQUIRE(momentum >= 0.0 && momentum < 1.0, OQ_ERR_INVALID_ARGUMENT, "Momentum must be in the range [0, 1) (momentum=%g).", momentum);
@@ -301,9 +290,9 @@ size_t oq_minmax_many_half_workspace_bytes(int64_t n) {
 int32_t oq_minmax_collect_many_h16(const void* desc, int64_t n, int32_t xtype, double momentum, void* workspace, size_t workspace_bytes,
                                    void* stream) {
     static_assert(sizeof(HalfDesc) == sizeof(oq_minmax_desc), "the descriptor of oq_hip.h");
-    OQ_REQUIRE(xtype_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: unknown xtype %d", xtype);
+    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: unknown xtype %d", xtype);
     OQ_REQUIRE(desc != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: null desc");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 7u) == 0, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: desc must be 8-byte aligned");
+    OQ_REQUIRE(aligned_to(desc, 8), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: desc must be 8-byte aligned");
     OQ_REQUIRE(n > 0 && n <= 65535, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: bad n=%lld (1 <= n <= 65535)", (long long)n);
     OQ_REQUIRE(momentum >= 0.0 && momentum < 1.0, OQ_ERR_INVALID_ARGUMENT, "Momentum must be in the range [0, 1) (momentum=%g).", momentum);
     const size_t need = oq_minmax_many_half_workspace_bytes(n);
@@ -330,13 +319,13 @@ size_t oq_absmax_half_workspace_bytes(int64_t R, int64_t C, int32_t transposed) 
 
 int32_t oq_absmax_h16(const void* x, int32_t xtype, int64_t R, int64_t C, int64_t ldx, int32_t transposed, float* out, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    OQ_REQUIRE(xtype_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: unknown xtype %d", xtype);
+    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: unknown xtype %d", xtype);
     OQ_REQUIRE(x != nullptr && out != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: null x / out");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(x) & 1u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0, OQ_ERR_INVALID_ARGUMENT,
+    OQ_REQUIRE(aligned_to(x, 2) && aligned_to(out, 4), OQ_ERR_INVALID_ARGUMENT,
                "oq_absmax_h16: x must be 2-byte aligned and out 4-byte aligned");
     OQ_REQUIRE(matrix_ok(R, C, ldx), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: bad shape R=%lld C=%lld ldx=%lld", (long long)R, (long long)C,
                (long long)ldx);
-    const bool vec8 = (C % 8 == 0) && (ldx % 8 == 0) && (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+    const bool vec8 = (C % 8 == 0) && (ldx % 8 == 0) && aligned_to(x, 16);
     hipStream_t s = as_stream(stream);
     const uint16_t* xh = static_cast<const uint16_t*>(x);
     if (transposed) {
@@ -349,7 +338,7 @@ int32_t oq_absmax_h16(const void* x, int32_t xtype, int64_t R, int64_t C, int64_
     const size_t need = static_cast<size_t>(chunks * C) * sizeof(float);
     OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_absmax_h16: workspace of %zu bytes needed, %zu given", need,
                workspace_bytes);
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 3u) == 0, OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: workspace must be 4-byte aligned");
+    OQ_REQUIRE(aligned_to(workspace, 4), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: workspace must be 4-byte aligned");
     const int64_t ncol_tiles = ceil_div(C, kHalfAbsTileCols);   // x chunks < 2^26: R * ldx <= 2^40, 128 x 512 elements per block
     float* partial = static_cast<float*>(workspace);
     const dim3 grid(static_cast<uint32_t>(ncol_tiles * chunks));

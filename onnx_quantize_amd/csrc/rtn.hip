@@ -1361,7 +1361,7 @@ static size_t twopass_ws(int64_t K, int64_t N, int64_t g) {
     return static_cast<size_t>(2 * kgroups * chunks * N) * sizeof(float);
 }
 
-static int32_t resolve_group(int32_t strategy, int64_t K, int64_t group_size, int64_t* g) {
+int32_t resolve_group(int32_t strategy, int64_t K, int64_t group_size, int64_t* g) {
     if (strategy == OQ_GROUP) {
         OQ_REQUIRE(group_size > 0 || group_size == -1, OQ_ERR_INVALID_ARGUMENT,
                    "group strategy needs group_size > 0 or -1, got %lld", (long long)group_size);

@@ -11,30 +11,9 @@
 //                                               costs what the fp32 kernels pay to read it once; nothing waits for another workgroup
 #include "rtn_internal.hpp"
 
-#include "../../include/oq_hip_half.h"
+#include "half_elem.hpp"
 
 namespace oq {
-
-// ------------------------------------------------------------------------------------ element types
-struct ElemF16 {
-    static __device__ __forceinline__ float one(uint16_t b) { return static_cast<float>(__builtin_bit_cast(_Float16, b)); }
-    static __device__ __forceinline__ void two(uint32_t w, float& lo, float& hi) {
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        const h2 v = __builtin_bit_cast(h2, w);
-        lo = static_cast<float>(v[0]);
-        hi = static_cast<float>(v[1]);
-    }
-};
-struct ElemBF16 {   // the upper half of an fp32: shift and mask
-    static __device__ __forceinline__ float one(uint16_t b) { return __uint_as_float(static_cast<uint32_t>(b) << 16); }
-    static __device__ __forceinline__ void two(uint32_t w, float& lo, float& hi) {
-        lo = __uint_as_float(w << 16);
-        hi = __uint_as_float(w & 0xffff0000u);
-    }
-};
-
-typedef uint32_t hu32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t hu32x4 __attribute__((ext_vector_type(4)));
 
 struct HalfArgs {
     const uint16_t* W;
@@ -134,7 +113,7 @@ __device__ __forceinline__ void half_wave_tile(const HalfArgs& a, const HalfPtrs
             const uint16_t* p = m.W + lrow * a.ldw + lc;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const hu32x4 u = __builtin_nontemporal_load(reinterpret_cast<const hu32x4*>(p + r * a.ldw));
+                const u32x4 u = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + r * a.ldw));
                 v[r][0] = u[0]; v[r][1] = u[1]; v[r][2] = u[2]; v[r][3] = u[3];
             }
         } else {       // rows that are not 16-byte aligned: 2-byte loads into the same registers
@@ -249,7 +228,7 @@ __device__ __forceinline__ void half_wave_tile(const HalfArgs& a, const HalfPtrs
             }
             uint8_t* o = m.q + (row0 + r) * a.N + col0;
             if (a.qvec) {
-                if (cv[0]) __builtin_nontemporal_store(hu32x2{w[0], w[1]}, reinterpret_cast<hu32x2*>(o));
+                if (cv[0]) __builtin_nontemporal_store(u32x2{w[0], w[1]}, reinterpret_cast<u32x2*>(o));
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
@@ -283,15 +262,15 @@ __device__ __forceinline__ void half_wave_tile(const HalfArgs& a, const HalfPtrs
         if (four) {
             o += hs * (R / 2);
             if constexpr (R == 16) {
-                *reinterpret_cast<hu32x2*>(o) = hu32x2{nibble_word(lw[0], lw[1]), nibble_word(lw[2], lw[3])};
+                *reinterpret_cast<u32x2*>(o) = u32x2{nibble_word(lw[0], lw[1]), nibble_word(lw[2], lw[3])};
             } else {
-                *reinterpret_cast<hu32x4*>(o) = hu32x4{nibble_word(lw[0], lw[1]), nibble_word(lw[2], lw[3]), nibble_word(lw[4], lw[5]), nibble_word(lw[6], lw[7])};
+                *reinterpret_cast<u32x4*>(o) = u32x4{nibble_word(lw[0], lw[1]), nibble_word(lw[2], lw[3]), nibble_word(lw[4], lw[5]), nibble_word(lw[6], lw[7])};
             }
         } else {
             o += hs * R;
 #pragma unroll
             for (int wd = 0; wd < R / 4; wd += 4)
-                *reinterpret_cast<hu32x4*>(o + 4 * wd) = hu32x4{lw[wd] ^ flip, lw[wd + 1] ^ flip, lw[wd + 2] ^ flip, lw[wd + 3] ^ flip};
+                *reinterpret_cast<u32x4*>(o + 4 * wd) = u32x4{lw[wd] ^ flip, lw[wd + 1] ^ flip, lw[wd + 2] ^ flip, lw[wd + 3] ^ flip};
         }
     }
 }
@@ -303,6 +282,8 @@ __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave(con
 
 // A list of matrices of one shape: blockIdx.y is the entry (wave-uniform: its four pointers come by scalar loads), blockIdx.x the tile in the single
 // matrix' order, so every matrix keeps its bands.  A null table is a list of one, whose pointers are in HalfArgs.
+// oq_rtn_quantize_h16 does not launch this form for its one matrix: on 4096 x 11008 it is up to 11 % slower than rtn_half_wave
+// (g = 256, [K, N] bytes; docs/LAB_NOTES_r17.md).
 template <typename E, int R, bool VEC>
 __global__ __launch_bounds__(256, R == 16 && VEC ? 3 : 1) void rtn_half_wave_many(const HalfArgs a, const HalfPtrs* __restrict__ table) {
     half_wave_tile<E, R, VEC, true>(a, table != nullptr ? table[blockIdx.y] : HalfPtrs{a.W, a.q, a.scale, a.zp});
@@ -333,8 +314,8 @@ __device__ __forceinline__ void quantize_rows(const HalfArgs& a, const HalfPtrs&
             lw[wd] = acc;
         }
         const int64_t in_group = r - kg * a.g;
-        if (a.grid.bits == 4) *reinterpret_cast<hu32x2*>(o + in_group / 2) = hu32x2{nibble_word(lw[0], lw[1]), nibble_word(lw[2], lw[3])};
-        else *reinterpret_cast<hu32x4*>(o + in_group) = hu32x4{lw[0], lw[1], lw[2], lw[3]};
+        if (a.grid.bits == 4) *reinterpret_cast<u32x2*>(o + in_group / 2) = u32x2{nibble_word(lw[0], lw[1]), nibble_word(lw[2], lw[3])};
+        else *reinterpret_cast<u32x4*>(o + in_group) = u32x4{lw[0], lw[1], lw[2], lw[3]};
     }
 }
 
@@ -435,42 +416,37 @@ __global__ __launch_bounds__(256) void half_quantize(const HalfArgs a) {
 }
 
 // ------------------------------------------------------------------------------------ host
-static bool half_aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-static int32_t half_group(int32_t strategy, int64_t K, int64_t group_size, int64_t* g) {   // rtn.hip's resolve_group
-    if (strategy == OQ_GROUP) {
-        OQ_REQUIRE(group_size > 0 || group_size == -1, OQ_ERR_INVALID_ARGUMENT, "group strategy needs group_size > 0 or -1, got %lld",
-                   (long long)group_size);
-        *g = (group_size == -1 || group_size > K) ? K : group_size;   // utils.py:19-22
-    } else if (strategy == OQ_CHANNEL || strategy == OQ_TENSOR) {
-        *g = K;
-    } else {
-        return fail(OQ_ERR_INVALID_ARGUMENT, "unknown strategy %d", strategy);
-    }
-    return OQ_OK;
-}
-
 static bool half_fused(int32_t strategy, int64_t g) { return strategy == OQ_GROUP && g <= 256; }
+static bool half_wave_group(int64_t g) { return g == 16 || g == 32 || g == 64 || g == 128 || g == 256; }   // rtn_half_wave has a build for it
 
 static size_t half_workspace(int32_t strategy, int64_t K, int64_t N, int64_t g) {
     if (half_fused(strategy, g)) return 0;
     return static_cast<size_t>(2 * (K / g) * ceil_div(g, kHalfChunk) * N) * sizeof(float);
 }
 
-template <typename E>
-static int32_t half_launch(HalfArgs& a, int32_t strategy, hipStream_t s) {
+// The fused route (half_fused): one launch of `batch` matrices of one shape.  LIST: entry b at table[b] (device memory; null:
+// batch == 1, the pointers are in `a`), the entry as grid y, the table kernels; otherwise the one matrix of `a` and the
+// single-matrix kernels.  The wave / column choice, the tile shape and the block order are one for both.
+template <typename E, bool LIST>
+static int32_t half_launch_fused(HalfArgs& a, const HalfPtrs* table, int64_t batch, hipStream_t s) {
     const int64_t g = a.g;
-    a.ncol_tiles = static_cast<uint32_t>(ceil_div(a.N, 256));
-    // the largest grid of any route: a block per (16-row slab or group, 256 columns)
-    OQ_REQUIRE(static_cast<int64_t>(a.ncol_tiles) * a.kgroups * ceil_div(g, 16) <= kMaxExtent, OQ_ERR_UNSUPPORTED,
-               "oq_rtn_quantize_h16: matrix too large for one launch (K=%lld N=%lld)", (long long)a.K, (long long)a.N);
-    if (half_fused(strategy, g)) {
+    const dim3 block(256);
+    if (half_wave_group(g)) {
         const int rows = g == 256 ? 32 : 16;
-        if (g == 16 || g == 32 || g == 64 || g == 128 || g == 256) {
-            a.spg = static_cast<int32_t>(g / rows);
-            a.nrow_tiles = static_cast<uint32_t>(ceil_div(a.K, 8 * rows));
-            a.gk = 4;
-            const dim3 grid(a.ncol_tiles * a.nrow_tiles), block(256);
+        a.spg = static_cast<int32_t>(g / rows);
+        a.nrow_tiles = static_cast<uint32_t>(ceil_div(a.K, 8 * rows));
+        a.gk = 4;
+        const dim3 grid(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(batch));
+        if constexpr (LIST) {
+            if (rows == 16) {
+                if (a.vec) hipLaunchKernelGGL((rtn_half_wave_many<E, 16, true>), grid, block, 0, s, a, table);
+                else hipLaunchKernelGGL((rtn_half_wave_many<E, 16, false>), grid, block, 0, s, a, table);
+            } else {
+                if (a.vec) hipLaunchKernelGGL((rtn_half_wave_many<E, 32, true>), grid, block, 0, s, a, table);
+                else hipLaunchKernelGGL((rtn_half_wave_many<E, 32, false>), grid, block, 0, s, a, table);
+            }
+            return check_launch("rtn_half_wave_many");
+        } else {
             if (rows == 16) {
                 if (a.vec) hipLaunchKernelGGL((rtn_half_wave<E, 16, true>), grid, block, 0, s, a);
                 else hipLaunchKernelGGL((rtn_half_wave<E, 16, false>), grid, block, 0, s, a);
@@ -480,9 +456,21 @@ static int32_t half_launch(HalfArgs& a, int32_t strategy, hipStream_t s) {
             }
             return check_launch("rtn_half_wave");
         }
-        hipLaunchKernelGGL(rtn_half_column<E>, dim3(a.ncol_tiles * static_cast<uint32_t>(a.kgroups)), dim3(256), 0, s, a);
+    }
+    const dim3 grid(a.ncol_tiles * static_cast<uint32_t>(a.kgroups), static_cast<uint32_t>(batch));
+    if constexpr (LIST) {
+        hipLaunchKernelGGL(rtn_half_column_many<E>, grid, block, 0, s, a, table);
+        return check_launch("rtn_half_column_many");
+    } else {
+        hipLaunchKernelGGL(rtn_half_column<E>, grid, block, 0, s, a);
         return check_launch("rtn_half_column");
     }
+}
+
+// The two-launch route of the one matrix of `a`: channel, tensor, groups taller than 256 rows.
+template <typename E>
+static int32_t half_launch(HalfArgs& a, hipStream_t s) {
+    const int64_t g = a.g;
     a.chunks = ceil_div(g, kHalfChunk);
     hipLaunchKernelGGL(half_range<E>, dim3(a.ncol_tiles * static_cast<uint32_t>(a.kgroups * a.chunks)), dim3(256), 0, s, a);
     int32_t st = check_launch("half_range");
@@ -500,29 +488,33 @@ static int32_t half_launch(HalfArgs& a, int32_t strategy, hipStream_t s) {
     return check_launch("half_quantize");
 }
 
-// oq_rtn_quantize_ptrs_h16: one launch of `batch` matrices of one shape, entry b at table[b] (device memory; null: batch == 1,
-// the pointers are in `a`).  The tile work, tile shape and block order of half_launch's fused arm with the entry as grid y.
-template <typename E>
-static int32_t half_launch_many(HalfArgs& a, const HalfPtrs* table, int64_t batch, hipStream_t s) {
-    const int64_t g = a.g;
-    const dim3 block(256);
-    if (g == 16 || g == 32 || g == 64 || g == 128 || g == 256) {
-        const int rows = g == 256 ? 32 : 16;
-        a.spg = static_cast<int32_t>(g / rows);
-        a.nrow_tiles = static_cast<uint32_t>(ceil_div(a.K, 8 * rows));
-        a.gk = 4;
-        const dim3 grid(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(batch));
-        if (rows == 16) {
-            if (a.vec) hipLaunchKernelGGL((rtn_half_wave_many<E, 16, true>), grid, block, 0, s, a, table);
-            else hipLaunchKernelGGL((rtn_half_wave_many<E, 16, false>), grid, block, 0, s, a, table);
-        } else {
-            if (a.vec) hipLaunchKernelGGL((rtn_half_wave_many<E, 32, true>), grid, block, 0, s, a, table);
-            else hipLaunchKernelGGL((rtn_half_wave_many<E, 32, false>), grid, block, 0, s, a, table);
-        }
-        return check_launch("rtn_half_wave_many");
-    }
-    hipLaunchKernelGGL(rtn_half_column_many<E>, dim3(a.ncol_tiles * static_cast<uint32_t>(a.kgroups), static_cast<uint32_t>(batch)), block, 0, s, a, table);
-    return check_launch("rtn_half_column_many");
+// What oq_rtn_quantize_h16 and oq_rtn_quantize_ptrs_h16 (`fn`) check alike, before any arithmetic on an extent and before any HIP
+// call; fills the shape, the grid, the group and the layout of `a`.
+static int32_t half_checks(const char* fn, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size,
+                           int32_t symmetric, int32_t reduce_range, float clip_ratio, int32_t layout, HalfArgs* a) {
+    OQ_REQUIRE(half_type_ok(wtype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
+    OQ_REQUIRE(K > 0 && N > 0 && ldw >= N, OQ_ERR_INVALID_ARGUMENT, "%s: bad shape K=%lld N=%lld ldw=%lld", fn, (long long)K, (long long)N,
+               (long long)ldw);
+    OQ_REQUIRE(matrix_ok(K, N, ldw), OQ_ERR_UNSUPPORTED, "%s: matrix too large (K=%lld N=%lld ldw=%lld)", fn, (long long)K, (long long)N,
+               (long long)ldw);
+    OQ_REQUIRE(clip_ratio > 0.0f && clip_ratio <= 1.0f, OQ_ERR_INVALID_ARGUMENT, "clip_ratio must be in (0.0, 1.0], got %g", clip_ratio);
+    OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS || layout == OQ_LAYOUT_KN_PACKED4, OQ_ERR_INVALID_ARGUMENT, "%s: bad layout %d", fn,
+               layout);
+    int32_t st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &a->grid);
+    if (st != OQ_OK) return st;
+    int64_t g;
+    st = resolve_group(strategy, K, group_size, &g);
+    if (st != OQ_OK) return st;
+    OQ_REQUIRE(K % g == 0, OQ_ERR_UNSUPPORTED,
+               "%s: group_size %lld does not divide K=%lld (groups that straddle columns have no half-precision kernel)", fn, (long long)g,
+               (long long)K);
+    a->K = K; a->N = N; a->ldw = ldw; a->g = g; a->kgroups = K / g;
+    a->layout = layout;
+    a->ncol_tiles = static_cast<uint32_t>(ceil_div(N, 256));
+    // the largest grid of any route: a block per (16-row slab or group, 256 columns)
+    OQ_REQUIRE(static_cast<int64_t>(a->ncol_tiles) * a->kgroups * ceil_div(g, 16) <= kMaxExtent, OQ_ERR_UNSUPPORTED,
+               "%s: matrix too large for one launch (K=%lld N=%lld)", fn, (long long)K, (long long)N);
+    return OQ_OK;
 }
 
 }  // namespace oq
@@ -537,7 +529,7 @@ size_t oq_rtn_half_workspace_bytes(int64_t K, int64_t N, int32_t strategy, int64
         return 0;
     }
     int64_t g;
-    if (oq::half_group(strategy, K, group_size, &g) != OQ_OK) return 0;
+    if (oq::resolve_group(strategy, K, group_size, &g) != OQ_OK) return 0;
     if (strategy == OQ_GROUP && K % g != 0) {
         oq::set_error("oq_rtn_half_workspace_bytes: groups that straddle columns (K %% group_size != 0) have no half-precision kernel");
         return 0;
@@ -550,51 +542,38 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
                             float* scale_out, void* zp_out, int32_t layout, void* workspace, size_t workspace_bytes, void* stream) {
     using namespace oq;
     // every check before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(wtype == OQ_W_F16 || wtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_h16: unknown wtype %d", wtype);
     OQ_REQUIRE(W != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_h16: null W");
     OQ_REQUIRE(scale_out != nullptr && zp_out != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_h16: null scale_out / zp_out");
-    OQ_REQUIRE(half_aligned(W, 2) && half_aligned(scale_out, 4), OQ_ERR_INVALID_ARGUMENT,
+    OQ_REQUIRE(aligned_to(W, 2) && aligned_to(scale_out, 4), OQ_ERR_INVALID_ARGUMENT,
                "oq_rtn_quantize_h16: W must be 2-byte aligned and scale_out 4-byte aligned");
-    OQ_REQUIRE(K > 0 && N > 0 && ldw >= N, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_h16: bad shape K=%lld N=%lld ldw=%lld", (long long)K,
-               (long long)N, (long long)ldw);
-    OQ_REQUIRE(matrix_ok(K, N, ldw), OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_h16: matrix too large (K=%lld N=%lld ldw=%lld)", (long long)K,
-               (long long)N, (long long)ldw);
-    OQ_REQUIRE(clip_ratio > 0.0f && clip_ratio <= 1.0f, OQ_ERR_INVALID_ARGUMENT, "clip_ratio must be in (0.0, 1.0], got %g", clip_ratio);
-    OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS || layout == OQ_LAYOUT_KN_PACKED4, OQ_ERR_INVALID_ARGUMENT,
-               "oq_rtn_quantize_h16: bad layout %d", layout);
+    HalfArgs a{};
+    const int32_t st = half_checks("oq_rtn_quantize_h16", wtype, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(layout != OQ_LAYOUT_KN_PACKED4, OQ_ERR_UNSUPPORTED,
                "oq_rtn_quantize_h16: layout KN_PACKED4 is not produced here; quantize to KN and pack with oq_pack_nibbles");
-    HalfArgs a{};
-    int32_t st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &a.grid);
-    if (st != OQ_OK) return st;
-    int64_t g;
-    st = half_group(strategy, K, group_size, &g);
-    if (st != OQ_OK) return st;
-    OQ_REQUIRE(K % g == 0, OQ_ERR_UNSUPPORTED,
-               "oq_rtn_quantize_h16: group_size %lld does not divide K=%lld (groups that straddle columns have no half-precision kernel)",
-               (long long)g, (long long)K);
+    const int64_t g = a.g;
     if (layout == OQ_LAYOUT_NBITS) {
         OQ_REQUIRE(strategy == OQ_GROUP && q_out != nullptr, OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_h16: NBITS layout needs the group strategy and q_out");
-        OQ_REQUIRE(g % 16 == 0 && half_aligned(q_out, 16), OQ_ERR_UNSUPPORTED,
+        OQ_REQUIRE(g % 16 == 0 && aligned_to(q_out, 16), OQ_ERR_UNSUPPORTED,
                    "oq_rtn_quantize_h16: NBITS layout needs group_size %% 16 == 0 and a 16-byte aligned q_out");
     }
     const size_t need = half_workspace(strategy, K, N, g);
-    OQ_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need && half_aligned(workspace, 4)), OQ_ERR_WORKSPACE,
+    OQ_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need && aligned_to(workspace, 4)), OQ_ERR_WORKSPACE,
                "oq_rtn_quantize_h16: workspace of %zu bytes (4-byte aligned) needed, %zu given", need, workspace ? workspace_bytes : static_cast<size_t>(0));
 
     a.W = static_cast<const uint16_t*>(W);
-    a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = K / g;
     a.q = static_cast<uint8_t*>(q_out); a.scale = scale_out; a.zp = static_cast<uint8_t*>(zp_out);
-    a.layout = layout;
-    a.vec = (N % 8 == 0 && ldw % 8 == 0 && half_aligned(W, 16)) ? 1 : 0;
-    a.qvec = (N % 8 == 0 && half_aligned(q_out, 8)) ? 1 : 0;
+    a.vec = (N % 8 == 0 && ldw % 8 == 0 && aligned_to(W, 16)) ? 1 : 0;
+    a.qvec = (N % 8 == 0 && aligned_to(q_out, 8)) ? 1 : 0;
     a.tensor = strategy == OQ_TENSOR ? 1 : 0;
     if (need != 0) {
         a.pmin = static_cast<float*>(workspace);
         a.pmax = a.pmin + need / (2 * sizeof(float));
     }
     const hipStream_t s = as_stream(stream);
-    return wtype == OQ_W_F16 ? half_launch<ElemF16>(a, strategy, s) : half_launch<ElemBF16>(a, strategy, s);
+    if (half_fused(strategy, g))
+        return wtype == OQ_W_F16 ? half_launch_fused<ElemF16, false>(a, nullptr, 1, s) : half_launch_fused<ElemBF16, false>(a, nullptr, 1, s);
+    return wtype == OQ_W_F16 ? half_launch<ElemF16>(a, s) : half_launch<ElemBF16>(a, s);
 }
 
 int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn_ptrs_h16* table_device, int64_t count, int32_t wtype,
@@ -603,37 +582,23 @@ int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn
     using namespace oq;
     static_assert(sizeof(HalfPtrs) == sizeof(oq_rtn_ptrs_h16) && sizeof(oq_rtn_ptrs_h16) == sizeof(oq_rtn_ptrs), "device view of oq_rtn_ptrs_h16");
     // every check on the host copy, before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(wtype == OQ_W_F16 || wtype == OQ_W_BF16, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: unknown wtype %d", wtype);
     OQ_REQUIRE(table_host != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: null table_host");
     OQ_REQUIRE(count >= 1 && count <= 65535, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: count %lld outside 1 .. 65535", (long long)count);
     OQ_REQUIRE(table_device != nullptr || count == 1, OQ_ERR_INVALID_ARGUMENT,
                "oq_rtn_quantize_ptrs_h16: null table_device with count %lld (it may be null for count 1 only)", (long long)count);
-    OQ_REQUIRE(K > 0 && N > 0 && ldw >= N, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: bad shape K=%lld N=%lld ldw=%lld", (long long)K,
-               (long long)N, (long long)ldw);
-    OQ_REQUIRE(matrix_ok(K, N, ldw), OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: matrix too large (K=%lld N=%lld ldw=%lld)", (long long)K,
-               (long long)N, (long long)ldw);
-    OQ_REQUIRE(clip_ratio > 0.0f && clip_ratio <= 1.0f, OQ_ERR_INVALID_ARGUMENT, "clip_ratio must be in (0.0, 1.0], got %g", clip_ratio);
-    OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS || layout == OQ_LAYOUT_KN_PACKED4, OQ_ERR_INVALID_ARGUMENT,
-               "oq_rtn_quantize_ptrs_h16: bad layout %d", layout);
     HalfArgs a{};
-    int32_t st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &a.grid);
+    int32_t st = half_checks("oq_rtn_quantize_ptrs_h16", wtype, K, N, ldw, qtype, OQ_GROUP, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
     if (st != OQ_OK) return st;
-    int64_t g;
-    st = half_group(OQ_GROUP, K, group_size, &g);
-    if (st != OQ_OK) return st;
-    OQ_REQUIRE(K % g == 0, OQ_ERR_UNSUPPORTED,
-               "oq_rtn_quantize_ptrs_h16: group_size %lld does not divide K=%lld (groups that straddle columns have no half-precision kernel)",
-               (long long)g, (long long)K);
+    const int64_t g = a.g;
     OQ_REQUIRE(half_fused(OQ_GROUP, g), OQ_ERR_UNSUPPORTED,
                "oq_rtn_quantize_ptrs_h16: group_size %lld is taller than the fused kernels hold (256 rows); call oq_rtn_quantize_h16 per matrix",
                (long long)g);
-    const bool wave = g == 16 || g == 32 || g == 64 || g == 128 || g == 256;
     if (layout == OQ_LAYOUT_NBITS)
         OQ_REQUIRE(g % 16 == 0, OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: NBITS layout needs group_size %% 16 == 0, got %lld", (long long)g);
     if (layout == OQ_LAYOUT_KN_PACKED4) {
         OQ_REQUIRE(a.grid.bits == 4, OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: KN_PACKED4 layout needs a 4-bit type");
         OQ_REQUIRE(N % 2 == 0, OQ_ERR_UNSUPPORTED, "oq_rtn_quantize_ptrs_h16: KN_PACKED4 layout needs an even number of columns, got N=%lld", (long long)N);
-        OQ_REQUIRE(wave, OQ_ERR_UNSUPPORTED,
+        OQ_REQUIRE(half_wave_group(g), OQ_ERR_UNSUPPORTED,
                    "oq_rtn_quantize_ptrs_h16: KN_PACKED4 layout needs a group_size of 16, 32, 64, 128 or 256 (the wave kernel), got %lld", (long long)g);
     }
     // the load and store widths are chosen for the call: every entry has to meet what they promise, or the call runs the narrow build
@@ -642,20 +607,15 @@ int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn
     for (int64_t i = 0; i < count; ++i) {
         const oq_rtn_ptrs_h16& p = table_host[i];
         OQ_REQUIRE(p.W && p.q_out && p.scale_out && p.zp_out, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_h16: null pointer in entry %lld", (long long)i);
-        OQ_REQUIRE(half_aligned(p.W, 2) && half_aligned(p.scale_out, 4), OQ_ERR_INVALID_ARGUMENT,
+        OQ_REQUIRE(aligned_to(p.W, 2) && aligned_to(p.scale_out, 4), OQ_ERR_INVALID_ARGUMENT,
                    "oq_rtn_quantize_ptrs_h16: entry %lld: W must be 2-byte aligned and scale_out 4-byte aligned", (long long)i);
-        OQ_REQUIRE(layout != OQ_LAYOUT_NBITS || half_aligned(p.q_out, 16), OQ_ERR_UNSUPPORTED,
+        OQ_REQUIRE(layout != OQ_LAYOUT_NBITS || aligned_to(p.q_out, 16), OQ_ERR_UNSUPPORTED,
                    "oq_rtn_quantize_ptrs_h16: entry %lld: NBITS layout needs a 16-byte aligned q_out", (long long)i);
-        vec = vec && half_aligned(p.W, 16);
-        qvec = qvec && half_aligned(p.q_out, q_store);
+        vec = vec && aligned_to(p.W, 16);
+        qvec = qvec && aligned_to(p.q_out, q_store);
     }
-    a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = K / g;
-    a.layout = layout;
     a.vec = vec ? 1 : 0;
     a.qvec = qvec ? 1 : 0;
-    a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, 256));
-    OQ_REQUIRE(static_cast<int64_t>(a.ncol_tiles) * a.kgroups * ceil_div(g, 16) <= kMaxExtent, OQ_ERR_UNSUPPORTED,
-               "oq_rtn_quantize_ptrs_h16: matrix too large for one launch (K=%lld N=%lld)", (long long)K, (long long)N);
 
     // How many matrices share a launch (blockIdx.y = entry): the rule of the fp32 entry point, oq::matrices_per_launch.
     const int64_t per_launch = matrices_per_launch(K, N, count);
@@ -666,7 +626,7 @@ int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn
         const oq_rtn_ptrs_h16& p = table_host[i];   // read by the kernel only where there is no device table (count == 1)
         a.W = static_cast<const uint16_t*>(p.W);
         a.q = static_cast<uint8_t*>(p.q_out); a.scale = p.scale_out; a.zp = static_cast<uint8_t*>(p.zp_out);
-        st = wtype == OQ_W_F16 ? half_launch_many<ElemF16>(a, table, batch, s) : half_launch_many<ElemBF16>(a, table, batch, s);
+        st = wtype == OQ_W_F16 ? half_launch_fused<ElemF16, true>(a, table, batch, s) : half_launch_fused<ElemBF16, true>(a, table, batch, s);
         if (st != OQ_OK) return st;
     }
     return OQ_OK;

@@ -39,6 +39,8 @@ struct RtnCall {
 
 // rtn.hip
 int32_t rtn_impl(const RtnCall& c);
+// rows per (scale, zp) of a strategy: utils.py:16-22 for groups, K for channel / tensor; refuses a bad group_size or strategy
+int32_t resolve_group(int32_t strategy, int64_t K, int64_t group_size, int64_t* g);
 // matrices of one shape that share a launch of a pointer-table entry point (oq_rtn_quantize_ptrs_f32 / _h16): a parameter budget
 // per launch, capped by blockIdx.y
 int64_t matrices_per_launch(int64_t K, int64_t N, int64_t count);

@@ -150,10 +150,33 @@ def _refuse_half(w, fn: str) -> None:
                         f"(one matrix per call) and rtn_quantize_model (a list of matrices); convert with w.float() to use {fn}")
 
 
+def _require_matrix(w, dtype=torch.float32) -> None:
+    """``w`` is a 2-D device tensor (of ``dtype``, where one is given), or the error names what it is instead."""
+    if not isinstance(w, torch.Tensor) or w.dim() != 2:
+        _require_device(w, "w", dtype)
+        raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
+
+
+def _rtn_param_shape(strategy: str, k: int, n: int, g: int):
+    """(number of (scale, zp) pairs, the shape they are returned in) of a [K, N] matrix: rtn.py:98-109."""
+    if strategy == "group":
+        return (k * n) // g, ((k * n) // g, 1)
+    if strategy == "channel":
+        return n, (n,)
+    return 1, ()
+
+
+def _rtn_outputs(layout, k, n, g, qtype, count, dev, emit_q, out):
+    """(q, scale, zp) of one matrix: the caller's ``out``, or new buffers (q None without ``emit_q``)."""
+    if out is not None:
+        return out
+    q = _q_buffer(layout, (), k, n, g, qtype, dev) if emit_q else None
+    return q, torch.empty(count, dtype=torch.float32, device=dev), torch.empty(count, dtype=container_dtype(qtype), device=dev)
+
+
 def _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out):
     """`rtn_quantize` on an fp16 / bf16 matrix through oq_rtn_quantize_h16 (csrc/rtn_half.hip): W is read as it is."""
-    if w.dim() != 2:
-        raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
+    _require_matrix(w, None)
     _layout_code(layout)
     if layout == "kn_packed4":
         # no packed epilogue in the half kernels: the [K, N] route followed by the packer (the same bytes, core/_pack.py:8-22)
@@ -172,19 +195,9 @@ def _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, 
     k, n = w.shape
     lib = L.load()
     g = resolve_group(strategy, k, group_size if group_size is not None else -1)
-    if strategy == "group":
-        count, shape = (k * n) // g, ((k * n) // g, 1)
-    elif strategy == "channel":
-        count, shape = n, (n,)
-    else:
-        count, shape = 1, ()
+    count, shape = _rtn_param_shape(strategy, k, n, g)
     dev = w.device
-    if out is not None:
-        q, scale, zp = out
-    else:
-        q = _q_buffer(layout, (), k, n, g, qtype, dev) if emit_q else None
-        scale = torch.empty(count, dtype=torch.float32, device=dev)
-        zp = torch.empty(count, dtype=container_dtype(qtype), device=dev)
+    q, scale, zp = _rtn_outputs(layout, k, n, g, qtype, count, dev, emit_q, out)
     gs = -1 if group_size is None else int(group_size)
     ws = _workspace(lib.oq_rtn_half_workspace_bytes(k, n, L.STRATEGY_CODE[strategy], gs), dev)
     L.check(lib.oq_rtn_quantize_h16(_ptr(w), _HALF_WTYPE[w.dtype], k, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
@@ -221,31 +234,16 @@ def rtn_quantize(w: torch.Tensor, qtype: str, strategy: str, group_size=-1, symm
                 return _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out)
         w = w.float()      # the documented cast route: mse, straddling groups
     _require_device(w, "w", torch.float32)
-    if w.dim() != 2:
-        raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
+    _require_matrix(w)
     w, ldw = _row_major(w)
     k, n = w.shape
     lib = L.load()
     g = resolve_group(strategy, k, group_size if group_size is not None else -1)
-    if strategy == "group":
-        if g <= 0 or (k * n) % g:
-            raise ValueError(f"cannot reshape array of size {k * n} into shape (-1, {g})")
-        count, shape = (k * n) // g, ((k * n) // g, 1)
-    elif strategy == "channel":
-        count, shape = n, (n,)
-    else:
-        count, shape = 1, ()
-    cdt = container_dtype(qtype)
+    if strategy == "group" and (g <= 0 or (k * n) % g):
+        raise ValueError(f"cannot reshape array of size {k * n} into shape (-1, {g})")
+    count, shape = _rtn_param_shape(strategy, k, n, g)
     dev = w.device
-    if out is not None:
-        q, scale, zp = out
-    else:
-        if not emit_q:
-            q = None
-        else:
-            q = _q_buffer(layout, (), k, n, g, qtype, dev)
-        scale = torch.empty(count, dtype=torch.float32, device=dev)
-        zp = torch.empty(count, dtype=cdt, device=dev)
+    q, scale, zp = _rtn_outputs(layout, k, n, g, qtype, count, dev, emit_q, out)
     gs = -1 if group_size is None else int(group_size)
     ws_bytes = lib.oq_rtn_workspace_bytes(k, n, L.STRATEGY_CODE[strategy], gs, int(mse))
     ws = _workspace(ws_bytes, dev)
@@ -404,6 +402,32 @@ def _table_stage(dev, rows: int):
     return pin, side
 
 
+def _table_rows(layout: str, cnt: int, k: int, n: int, g: int, qtype: str, dev, w_ptrs, pin_np, row: int):
+    """One C call of a pointer-table entry point (oq_rtn_ptrs / oq_rtn_ptrs_h16: {W, q_out, scale_out, zp_out}): allocate the
+    stacked outputs of its ``cnt`` matrices of one shape and write rows [row, row + cnt) of the page-locked table (host side
+    only).  Returns (q, scale, zp) with the matrix as the leading dimension."""
+    q = _q_buffer(layout, (cnt,), k, n, g, qtype, dev)
+    sc = torch.empty((cnt, n * k // g, 1), dtype=torch.float32, device=dev)
+    zp = torch.empty((cnt, n * k // g, 1), dtype=container_dtype(qtype), device=dev)
+    # output pointers by arithmetic (the per-matrix views the caller gets back are made AFTER the launches)
+    rows = pin_np[row:row + cnt]
+    steps = np.arange(cnt, dtype=np.int64)
+    rows[:, 0] = w_ptrs
+    rows[:, 1] = q.data_ptr() + steps * (q[0].numel() * q.element_size())
+    rows[:, 2] = sc.data_ptr() + steps * (sc[0].numel() * 4)
+    rows[:, 3] = zp.data_ptr() + steps * (zp[0].numel() * zp.element_size())
+    return q, sc, zp
+
+
+def _upload_rows(pin, table_dev, side, row: int, cnt: int) -> None:
+    """Rows [row, row + cnt) of the table to the device on the side stream; the launch stream waits for them."""
+    cur = torch.cuda.current_stream()
+    with torch.cuda.stream(side):
+        table_dev[row:row + cnt].copy_(pin[row:row + cnt], non_blocking=True)
+        ready = side.record_event()
+    cur.wait_event(ready)
+
+
 def rtn_quantize_many(ws, qtype: str, group_size: int, symmetric=False, reduce_range=False, clip_ratio=1.0, layout: str = "kn"):
     """rtn.py:54-109 (group strategy) for a LIST of [K, N] fp32 weights of any shapes living anywhere in HBM -- the MatMul
     weights of a model, which the reference quantizes node by node (qrules/_common.py:126-142).  Weights of one shape go
@@ -421,18 +445,24 @@ def rtn_quantize_many(ws, qtype: str, group_size: int, symmetric=False, reduce_r
     if not ws:
         return []
     lib = L.load()
-    cdt = container_dtype(qtype)
     lay = _layout_code(layout)
 
-    def key_of(w):
-        return (w.shape, w.stride())           # two attribute reads per weight: the scan of 224 weights is 0.1 ms of head otherwise
+    def by_shape(indices):
+        """The weights at ``indices`` by (shape, strides): the members of one C call."""
+        groups: dict = {}
+        for i in indices:
+            w = ws[i]
+            if not isinstance(w, torch.Tensor) or w.dim() != 2:     # tested here: no helper call per weight on the way that passes
+                _require_matrix(w)
+            # two attribute reads per weight: the scan of 224 weights is 0.1 ms of head otherwise
+            groups.setdefault((w.shape, w.stride()), []).append(i)
+        return groups
 
     dev = ws[0].device
     out = [None] * len(ws)
     pin, side = _table_stage(dev, len(ws))
     table_dev = torch.empty((len(ws), 4), dtype=torch.int64, device=dev)
     table_dev.record_stream(side)
-    cur = torch.cuda.current_stream()
     state = {"wsb": None, "row": 0}
     made = []
 
@@ -461,29 +491,13 @@ def rtn_quantize_many(ws, qtype: str, group_size: int, symmetric=False, reduce_r
                 w2, ldw = _row_major(w)
             mats.append(w2)
         cnt, row = len(idx), state["row"]
-        q = _q_buffer(layout, (cnt,), k, n, g, qtype, dev)
-        sc = torch.empty((cnt, n * k // g, 1), dtype=torch.float32, device=dev)
-        zp = torch.empty((cnt, n * k // g, 1), dtype=cdt, device=dev)
+        q, sc, zp = _table_rows(layout, cnt, k, n, g, qtype, dev, [m.data_ptr() for m in mats], pin_np, row)
         need = lib.oq_rtn_batched_workspace_bytes(cnt, k, n, int(group_size))
         if state["wsb"] is None or state["wsb"].numel() < need:
             state["wsb"] = _workspace(need, dev)     # calls on one stream run in order: a later, larger shape may take a new buffer
-        # output pointers by arithmetic (the per-matrix views the caller gets back are made AFTER the launches)
-        rows = pin_np[row:row + cnt]
-        rows[:, 0] = [m.data_ptr() for m in mats]
-        steps = np.arange(cnt, dtype=np.int64)
-        rows[:, 1] = q.data_ptr() + steps * (q[0].numel() * q.element_size())
-        rows[:, 2] = sc.data_ptr() + steps * (sc[0].numel() * 4)
-        rows[:, 3] = zp.data_ptr() + steps * (zp[0].numel() * zp.element_size())
         made.append((idx, q, sc, zp, mats))      # operands stay referenced until the views are made
         state["row"] = row + cnt
         return (k, n, ldw, cnt, row, state["wsb"])
-
-    def upload(row, cnt):
-        """Rows [row, row + cnt) of the table to the device on the side stream; the launch stream waits for them."""
-        with torch.cuda.stream(side):
-            table_dev[row:row + cnt].copy_(pin[row:row + cnt], non_blocking=True)
-            ready = side.record_event()
-        cur.wait_event(ready)
 
     def launch(call):
         k, n, ldw, cnt, row, wsb = call
@@ -495,13 +509,15 @@ def rtn_quantize_many(ws, qtype: str, group_size: int, symmetric=False, reduce_r
         """One C call: prepare, copy its table rows, launch."""
         call = prepare(key, idx)
         if call[3] > 1:
-            upload(call[4], call[3])
+            _upload_rows(pin, table_dev, side, call[4], call[3])
         launch(call)
 
-    for w in ws[:1]:
-        if not isinstance(w, torch.Tensor) or w.dim() != 2:
-            _require_device(w, "w", torch.float32)
-            raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
+    def views():
+        for idx, q, sc, zp, _mats in made:
+            for j, i in enumerate(idx):
+                out[i] = (q[j], sc[j], zp[j])
+        return out
+
     # Host work beside the kernels.  (1) Look at the first 24 weights only and launch up to 8 of the shape that carries the
     # most parameters among them: the GPU starts after ~50 us of head.  (2) Group everything else by shape while those
     # kernels run.  (3) Shape by shape, fewest matrices first; the first shape in pieces (4, 8, rest) so that every call is
@@ -510,50 +526,24 @@ def rtn_quantize_many(ws, qtype: str, group_size: int, symmetric=False, reduce_r
     # everything is prepared first, the table goes up in ONE copy and the C calls follow back to back (0.90 -> see the bench's
     # `model_rtn.small_matrices`).  The interleaving below pays from a few hundred million parameters on.
     if sum(w.shape[0] * w.shape[1] for w in ws if isinstance(w, torch.Tensor) and w.dim() == 2) < (1 << 29):
-        small: dict = {}
-        for i, w in enumerate(ws):
-            if not isinstance(w, torch.Tensor) or w.dim() != 2:
-                _require_device(w, "w", torch.float32)
-                raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
-            small.setdefault(key_of(w), []).append(i)
-        calls = [prepare(key, idx) for key, idx in small.items()]
+        calls = [prepare(key, idx) for key, idx in by_shape(range(len(ws))).items()]
         if any(c[3] > 1 for c in calls):
-            upload(0, state["row"])
+            _upload_rows(pin, table_dev, side, 0, state["row"])
         for c in calls:
             launch(c)
-        for idx, q, sc, zp, _mats in made:
-            for j, i in enumerate(idx):
-                out[i] = (q[j], sc[j], zp[j])
-        return out
-    early: dict = {}
-    for i, w in enumerate(ws[:24]):
-        if not isinstance(w, torch.Tensor) or w.dim() != 2:
-            _require_device(w, "w", torch.float32)
-            raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
-        early.setdefault(key_of(w), []).append(i)
+        return views()
     taken = set()
     if len(ws) > 24:
-        key0, idx0 = max(early.items(), key=lambda kv: len(kv[1]) * kv[0][0][0] * kv[0][0][1])
+        key0, idx0 = max(by_shape(range(24)).items(), key=lambda kv: len(kv[1]) * kv[0][0][0] * kv[0][0][1])
         run(key0, idx0[:8])
         taken = set(idx0[:8])
-    groups: dict = {}
-    for i, w in enumerate(ws):
-        if i in taken:
-            continue
-        if not isinstance(w, torch.Tensor) or w.dim() != 2:
-            _require_device(w, "w", torch.float32)
-            raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
-        groups.setdefault(key_of(w), []).append(i)
-    order = sorted(groups.items(), key=lambda kv: len(kv[1]))
+    order = sorted(by_shape([i for i in range(len(ws)) if i not in taken]).items(), key=lambda kv: len(kv[1]))
     if order and len(order[0][1]) > 12:
         key1, idx1 = order[0]
         order = [(key1, idx1[:4]), (key1, idx1[4:12]), (key1, idx1[12:])] + order[1:]
     for key, idx in order:
         run(key, idx)
-    for idx, q, sc, zp, _mats in made:
-        for j, i in enumerate(idx):
-            out[i] = (q[j], sc[j], zp[j])
-    return out
+    return views()
 
 
 _HALF_WAVE_GROUPS = (16, 32, 64, 128, 256)     # csrc/rtn_half.hip: the group sizes rtn_half_wave has a build for
@@ -606,8 +596,7 @@ def rtn_quantize_model(ws, qtype: str, group_size: int, symmetric=False, reduce_
         key = (dt, w.shape, w.stride(), (ptr & 15) == 0)
         slot = groups.get(key)
         if slot is None:                    # the first of its key: the checks every member shares
-            if w.dim() != 2:
-                raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
+            _require_matrix(w, None)
             k, n = w.shape
             if k == 0 or n == 0:
                 raise ValueError(f"rtn_quantize_model: weight {i} is empty ({k} x {n})")
@@ -624,7 +613,6 @@ def rtn_quantize_model(ws, qtype: str, group_size: int, symmetric=False, reduce_
             out[i] = r
     if groups:
         lib = L.load()
-        cdt = container_dtype(qtype)
         total = sum(len(slot[1]) for slot in groups.values())
         pin, side = _table_stage(here, total)
         table_dev = torch.empty((total, 4), dtype=torch.int64, device=here)
@@ -632,26 +620,13 @@ def rtn_quantize_model(ws, qtype: str, group_size: int, symmetric=False, reduce_
         pin_np = pin.numpy()
         calls, made, row = [], [], 0
         for (dtype, (k, n), strides, _aligned), (_ok, idx, ptrs) in groups.items():     # host side only: outputs and table rows of every call
-            g = resolve_group("group", k, group_size)
             cnt = len(idx)
-            q = _q_buffer(layout, (cnt,), k, n, g, qtype, here)
-            sc = torch.empty((cnt, n * k // g, 1), dtype=torch.float32, device=here)
-            zp = torch.empty((cnt, n * k // g, 1), dtype=cdt, device=here)
-            rows = pin_np[row:row + cnt]
-            steps = np.arange(cnt, dtype=np.int64)
-            rows[:, 0] = ptrs
-            rows[:, 1] = q.data_ptr() + steps * (q[0].numel() * q.element_size())
-            rows[:, 2] = sc.data_ptr() + steps * (sc[0].numel() * 4)
-            rows[:, 3] = zp.data_ptr() + steps * (zp[0].numel() * zp.element_size())
+            q, sc, zp = _table_rows(layout, cnt, k, n, resolve_group("group", k, group_size), qtype, here, ptrs, pin_np, row)
             calls.append((_HALF_WTYPE[dtype], k, n, strides[0] if k > 1 else max(n, strides[0]), cnt, row))
             made.append((idx, q, sc, zp))
             row += cnt
-        if any(c[4] > 1 for c in calls):           # one copy on the side stream; the launch stream waits for it
-            cur = torch.cuda.current_stream()
-            with torch.cuda.stream(side):
-                table_dev.copy_(pin[:total], non_blocking=True)
-                ready = side.record_event()
-            cur.wait_event(ready)
+        if any(c[4] > 1 for c in calls):           # one copy for every call
+            _upload_rows(pin, table_dev, side, 0, total)
         host0, dev0, stream = pin.data_ptr(), table_dev.data_ptr(), _stream()
         for wtype, k, n, ldw, cnt, row in calls:
             L.check(lib.oq_rtn_quantize_ptrs_h16(C.c_void_p(host0 + 32 * row), C.c_void_p(dev0 + 32 * row if cnt > 1 else 0), cnt, wtype, k, n, ldw,

@@ -36,7 +36,7 @@ def test_hqq_register_tiles_of_every_element_type_do_not_spill(tmp_path):
         return sorted(int(m.group(1)) for m in (re.search(r"hqq_rounds_reg_kernelINS_\d+%sELi(\d+)E" % elem, k) for k in tiles) if m)
 
     assert built("HqqF32") == list(FP32_GROUPS), sorted(tiles)                    # still four: no fp32 tile of 256
-    assert built("HqqF16") == built("HqqBF16") == list(HALF_GROUPS), sorted(tiles)    # two half ones per built G
+    assert built("ElemF16") == built("ElemBF16") == list(HALF_GROUPS), sorted(tiles)    # two half ones per built G (half_elem.hpp)
     assert len(tiles) == len(FP32_GROUPS) + 2 * len(HALF_GROUPS), sorted(tiles)
     for name, (vgprs, scratch, occ, sgpr_spill, vgpr_spill) in tiles.items():
         assert scratch == 0 and sgpr_spill == 0 and vgpr_spill == 0, (name, vgprs, scratch, sgpr_spill, vgpr_spill)
