@@ -28,7 +28,7 @@ int32_t oq_half_extension_version(void);
 
 /* ---------------------------------------------------------------------------------------------
  * A1  core/_algorithms/rtn.py:54-109  _rtn_quantize on W.astype(np.float32), without the fp32 copy: replaces the cast
- *     followed by oq_rtn_quantize_f32 (mse == 0).
+ *     followed by oq_rtn_quantize_f32 with mse == 0 (mse == 1: oq_rtn_mse_h16 below).
  *
  *   W          [K, N], 2 bytes per element of type `wtype`, leading dimension ldw >= N (elements).  Rows that are not
  *              16-byte aligned (odd N, odd ldw, an unaligned base) take narrower loads and give the same bytes.
@@ -47,6 +47,33 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
                             int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range,
                             float clip_ratio, void* q_out /* NULL: parameters only */, float* scale_out,
                             void* zp_out, int32_t layout, void* workspace, size_t workspace_bytes, void* stream);
+
+/* A1 with the MSE range search (utils.py:140-239): _rtn_quantize(..., mse=True) on W.astype(np.float32), without the fp32 copy:
+ *     replaces the cast followed by oq_rtn_quantize_f32 / oq_rtn_qparams_f32 with mse == 1.  Both conversions are exact and the
+ *     search arithmetic stays fp32 -- per element, per candidate and in the order of every sum that of the fp32 kernels -- so the
+ *     result is DEFINED as that of the fp32 entry points on the upcast matrix: integers, zero points and fp32 scales match it
+ *     byte for byte, NaN patterns included.
+ *
+ *   W          [K, N], 2 bytes per element of type `wtype`, leading dimension ldw >= N (elements), 2-byte aligned; no other
+ *              alignment is needed (every lane reads its own column, 2 bytes a row).
+ *   routes     those of the fp32 search: group_size 32 / 64 / 128 hold a group in registers across the 20 candidates (converted
+ *              at the load); every other group size, channel and tensor re-read W per candidate.  group_size 256: the register
+ *              route as well, the group held as PACKED 2-byte elements (128 registers) -- fp32 has no such route.
+ *   group_size GROUP only: > 0 (clamped to K), or -1 (= K); K % group_size must be 0 (groups that straddle columns:
+ *              OQ_ERR_UNSUPPORTED, as with mse in oq_rtn_quantize_f32).
+ *   clip_ratio validated, then not applied: the MSE range replaces the clipped one, as in oq_rtn_quantize_f32 with mse.
+ *   q_out      OQ_LAYOUT_KN only: K*N bytes, or NULL: parameters only.  OQ_LAYOUT_NBITS / OQ_LAYOUT_KN_PACKED4:
+ *              OQ_ERR_UNSUPPORTED, as the fp32 entry points answer with mse.
+ *   scale_out  fp32, 4-byte aligned; zp_out 1 byte each: the arrays of oq_rtn_quantize_f32 (group: entry n*(K/g)+kg).
+ *   workspace  oq_rtn_mse_half_workspace_bytes (4-byte aligned): 12 bytes per (scale, zp) pair + 82432.  The query returns 0
+ *              and sets the error for a request outside the bounds, like oq_rtn_half_workspace_bytes.
+ *   checks     null pointers, wtype, alignment, the shape bounds, clip_ratio, the layout, the group and the workspace, all
+ *              before the first device call: on any refusal no output is touched. */
+size_t oq_rtn_mse_half_workspace_bytes(int64_t K, int64_t N, int32_t strategy, int64_t group_size);
+int32_t oq_rtn_mse_h16(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
+                       int64_t group_size, int32_t symmetric, int32_t reduce_range, float clip_ratio,
+                       void* q_out /* NULL: parameters only */, float* scale_out, void* zp_out, int32_t layout,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* A1 over a LIST of equally shaped 2-byte matrices of ONE element type that live anywhere in device memory (the MatMul weights of
  *     a resident fp16 / bf16 model): what oq_rtn_quantize_ptrs_f32 (oq_hip.h) is for fp32 weights.  Entry i of the table holds the

@@ -9,6 +9,8 @@
 //                                               (rtn_half_wave_many / rtn_half_column_many, oq_rtn_quantize_ptrs_h16)
 //   channel, tensor, g > 256                    two launches over W (half_range + a fold, half_quantize): reading 2-byte W twice
 //                                               costs what the fp32 kernels pay to read it once; nothing waits for another workgroup
+//   with the MSE range search (oq_rtn_mse_h16)  the checks here, the search in rtn_mse.hip (templates on the element type), then
+//                                               half_quantize with the stored parameters (launch_half_quantize_kn)
 #include "rtn_internal.hpp"
 
 #include "half_elem.hpp"
@@ -467,6 +469,27 @@ static int32_t half_launch_fused(HalfArgs& a, const HalfPtrs* table, int64_t bat
     }
 }
 
+// K1 with the stored parameters of `a`: launch 2 of the two-launch route, and (launch_half_quantize_kn) the final pass of the MSE search.
+template <typename E>
+static int32_t half_launch_quantize(const HalfArgs& a, hipStream_t s) {
+    const int64_t slabs = a.kgroups * ceil_div(a.g, 16);
+    hipLaunchKernelGGL(half_quantize<E>, dim3(a.ncol_tiles * static_cast<uint32_t>(slabs)), dim3(256), 0, s, a);
+    return check_launch("half_quantize");
+}
+
+int32_t launch_half_quantize_kn(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int64_t g, int64_t kgroups, float* scale,
+                                uint8_t* zp, uint8_t* q, const QGrid& grid, bool tensor, hipStream_t s) {
+    HalfArgs a{};
+    a.W = static_cast<const uint16_t*>(W);
+    a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = kgroups;
+    a.q = q; a.scale = scale; a.zp = zp;
+    a.grid = grid;
+    a.layout = OQ_LAYOUT_KN;
+    a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, 256));
+    a.tensor = tensor ? 1 : 0;
+    return wtype == OQ_W_F16 ? half_launch_quantize<ElemF16>(a, s) : half_launch_quantize<ElemBF16>(a, s);
+}
+
 // The two-launch route of the one matrix of `a`: channel, tensor, groups taller than 256 rows.
 template <typename E>
 static int32_t half_launch(HalfArgs& a, hipStream_t s) {
@@ -483,9 +506,7 @@ static int32_t half_launch(HalfArgs& a, hipStream_t s) {
     }
     st = check_launch("half_fold");
     if (st != OQ_OK || a.q == nullptr) return st;
-    const int64_t slabs = a.kgroups * ceil_div(g, 16);
-    hipLaunchKernelGGL(half_quantize<E>, dim3(a.ncol_tiles * static_cast<uint32_t>(slabs)), dim3(256), 0, s, a);
-    return check_launch("half_quantize");
+    return half_launch_quantize<E>(a, s);
 }
 
 // What oq_rtn_quantize_h16 and oq_rtn_quantize_ptrs_h16 (`fn`) check alike, before any arithmetic on an extent and before any HIP
@@ -574,6 +595,45 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
     if (half_fused(strategy, g))
         return wtype == OQ_W_F16 ? half_launch_fused<ElemF16, false>(a, nullptr, 1, s) : half_launch_fused<ElemBF16, false>(a, nullptr, 1, s);
     return wtype == OQ_W_F16 ? half_launch<ElemF16>(a, s) : half_launch<ElemBF16>(a, s);
+}
+
+size_t oq_rtn_mse_half_workspace_bytes(int64_t K, int64_t N, int32_t strategy, int64_t group_size) {
+    if (!oq::matrix_ok(K, N, N)) {
+        oq::set_error("oq_rtn_mse_half_workspace_bytes: bad shape K=%lld N=%lld", (long long)K, (long long)N);
+        return 0;
+    }
+    int64_t g;
+    if (oq::resolve_group(strategy, K, group_size, &g) != OQ_OK) return 0;
+    if (strategy == OQ_GROUP && K % g != 0) {
+        oq::set_error("oq_rtn_mse_half_workspace_bytes: groups that straddle columns (K %% group_size != 0) have no MSE search");
+        return 0;
+    }
+    return oq::rtn_mse_workspace(K, N, strategy, g);
+}
+
+int32_t oq_rtn_mse_h16(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size,
+                       int32_t symmetric, int32_t reduce_range, float clip_ratio, void* q_out, float* scale_out, void* zp_out, int32_t layout,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace oq;
+    static const char fn[] = "oq_rtn_mse_h16";
+    // every check before any arithmetic on an extent and before any HIP call
+    OQ_REQUIRE(W != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null W", fn);
+    OQ_REQUIRE(scale_out != nullptr && zp_out != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null scale_out / zp_out", fn);
+    OQ_REQUIRE(aligned_to(W, 2) && aligned_to(scale_out, 4), OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned and scale_out 4-byte aligned", fn);
+    HalfArgs a{};
+    const int32_t st = half_checks(fn, wtype, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
+    if (st != OQ_OK) return st;
+    OQ_REQUIRE(layout == OQ_LAYOUT_KN, OQ_ERR_UNSUPPORTED, "%s: layout %s with mse is not supported (the MSE search writes [K, N] bytes)", fn,
+               layout == OQ_LAYOUT_NBITS ? "NBITS" : "KN_PACKED4");
+    // the search's grid: a block per (256 columns, group) with the group as y; the resolve pass: a thread per (column, group)
+    OQ_REQUIRE(strategy == OQ_TENSOR || (a.kgroups <= 65535 && ceil_div(N * a.kgroups, 256) <= kMaxExtent), OQ_ERR_UNSUPPORTED,
+               "%s: more than 65535 groups per column or too many groups for one launch (K=%lld N=%lld group_size %lld)", fn, (long long)K,
+               (long long)N, (long long)a.g);
+    const size_t need = rtn_mse_workspace(K, N, strategy, a.g);
+    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need && aligned_to(workspace, 4), OQ_ERR_WORKSPACE,
+               "%s: workspace of %zu bytes (4-byte aligned) needed, %zu given", fn, need, workspace ? workspace_bytes : static_cast<size_t>(0));
+    // clip_ratio is validated and then not applied: the MSE range replaces the clipped one (rtn_mse_impl)
+    return rtn_mse_half_impl(W, wtype, K, N, ldw, a.grid, strategy, a.g, q_out, scale_out, zp_out, workspace, as_stream(stream));
 }
 
 int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn_ptrs_h16* table_device, int64_t count, int32_t wtype,

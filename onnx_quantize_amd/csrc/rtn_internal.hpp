@@ -54,6 +54,14 @@ int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QG
                      int64_t g, void* q_out, float* scale_out, void* zp_out, int32_t zp_signed, void* workspace,
                      size_t workspace_bytes, hipStream_t s, bool emit_q);
 size_t rtn_mse_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g);
+// the same search on a 2-byte matrix (`wtype`: an oq_wtype); q_out null: parameters only.  The caller (oq_rtn_mse_h16) has made every check.
+int32_t rtn_mse_half_impl(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g,
+                          void* q_out, float* scale_out, void* zp_out, void* workspace, hipStream_t s);
+
+// rtn_half.hip: the stored-parameter pass of the two-launch route (half_quantize: [K, N] bytes, the IEEE division), also the final
+// pass of the half MSE search; parameter col * kgroups + kg, or the one pair of a tensor
+int32_t launch_half_quantize_kn(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int64_t g, int64_t kgroups, float* scale,
+                                uint8_t* zp, uint8_t* q, const QGrid& grid, bool tensor, hipStream_t s);
 
 // rtn_resident.hip: the one-read channel / tensor / tall-group kernels ("ticketed": their workgroups wait for one another)
 bool rtn_resident_eligible(int64_t K, int64_t N, int64_t ldw, const float* W, const void* q, int32_t strategy, int64_t g, int32_t layout,

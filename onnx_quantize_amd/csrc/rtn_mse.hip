@@ -10,7 +10,7 @@
 // until the stop), the masks are OR-ed into one device word, and a resolve kernel derives the stop
 // iteration from that word and picks, per row, the last improving iteration not after it.  The search is
 // ALU-bound (an IEEE divide and |d|^2.4 per element and candidate, 20 candidates); W is re-read from
-// L2 / Infinity Cache per candidate instead of being tiled (g > 128), or held in registers (g <= 128, mse_rows_reg_kernel: the division
+// L2 / Infinity Cache per candidate instead of being tiled (g > 128), or held in registers (g = 32 / 64 / 128, and 256 of a 2-byte matrix, mse_rows_reg_kernel: the division
 // there is the proven-equal reciprocal product of the RTN kernels with an exact redo inside the tie band).  The power runs on the hardware log / exp units (the library
 // powf was 3/4 of the kernel: 4.6 -> 1.2 ms on the 4096 x 11008 matrix).
 //
@@ -31,9 +31,25 @@
 // wave with a tiny one takes the second path with a shift of 0 (fma(2.4, L, +0) is the rounded product, ldexp by 0 the
 // identity, and the plain division is what the reciprocal path is proved equal to), so its bits do not change either;
 // test_mse_tiny_and_ordinary_columns_in_one_wave holds it to that.
+//
+// Element types: W is fp32, fp16 or bf16 (oq_rtn_mse_h16, oq_hip_half.h).  The kernels that read W are templates on the element
+// (MseF32, ElemF16 / ElemBF16 of half_elem.hpp); the 2-byte types are read as they are and converted exactly at the load, and
+// everything behind the load -- the arithmetic per element and candidate, the order of every sum, the grid-stride mapping and the
+// block count of the tensor route, the tie-band redo, the shifted power, the masks and the resolve -- is one source for all three.
+// So the search on a half matrix gives the bytes of the fp32 search on the upcast matrix (tests/test_mse_half_gpu.py), and the
+// fp32 instantiations are the kernels this file had before it was a template.  Groups of 256 of a 2-byte matrix have a register
+// tile too (packed, see mse_rows_reg_kernel); the final pass of a half matrix is rtn_half.hip's stored-parameter pass.
 #include "rtn_internal.hpp"
 
+#include "half_elem.hpp"
+
 namespace oq {
+
+// fp16 and bf16 are ElemF16 / ElemBF16 of half_elem.hpp; fp32 has the same face
+struct MseF32 {
+    typedef float raw;
+    static __device__ __forceinline__ float one(float b) { return b; }
+};
 
 constexpr int kMseSteps = 20;      // int(maxshrink * grid) = int(0.20 * 100.0), utils.py:197
 constexpr int kMsePatience = 5;    // utils.py:150
@@ -73,16 +89,17 @@ struct MseRow {
 };
 
 // channel / group: one thread per (column, k-group); lanes walk neighbouring columns -> coalesced rows
-__global__ __launch_bounds__(256) void mse_rows_kernel(const float* W, int64_t K, int64_t N, int64_t ldw, int64_t g,
+template <typename E>
+__global__ __launch_bounds__(256) void mse_rows_kernel(const typename E::raw* W, int64_t K, int64_t N, int64_t ldw, int64_t g,
                                                        int64_t kgroups, QGrid grid, MseRow* rows, uint32_t* any_mask) {
     const int64_t n = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const int64_t kg = blockIdx.y;
     const bool live = n < N;
     const int64_t nc = live ? n : N - 1;
-    const float* col = W + kg * g * ldw + nc;
+    const typename E::raw* col = W + kg * g * ldw + nc;
     float mn = INFINITY, mx = -INFINITY;
     for (int64_t r = 0; r < g; ++r) {
-        const float x = col[r * ldw];
+        const float x = E::one(col[r * ldw]);
         mn = nmin(mn, x);
         mx = nmax(mx, x);
     }
@@ -96,9 +113,9 @@ __global__ __launch_bounds__(256) void mse_rows_kernel(const float* W, int64_t K
         const QParam qp = qparam_from_range(p * lo0, p * hi0, grid);
         float err = 0.f;
         if (shifted) {
-            for (int64_t r = 0; r < g; ++r) err += fake_quant_error_shifted(col[r * ldw], qp, grid, shift);
+            for (int64_t r = 0; r < g; ++r) err += fake_quant_error_shifted(E::one(col[r * ldw]), qp, grid, shift);
         } else {
-            for (int64_t r = 0; r < g; ++r) err += fake_quant_error(col[r * ldw], qp, grid);
+            for (int64_t r = 0; r < g; ++r) err += fake_quant_error(E::one(col[r * ldw]), qp, grid);
         }
         if (err < best) {  // utils.py:225
             best = err;
@@ -122,25 +139,60 @@ __global__ __launch_bounds__(256) void mse_rows_kernel(const float* W, int64_t K
 // and the candidate loop is pure ALU.  Same per-element arithmetic and the same summation order (r = 0 .. G-1 into one fp32
 // accumulator) as mse_rows_kernel: bit-identical masks.  G <= 128 keeps the tile within 256 VGPRs (two waves per SIMD: an
 // ALU-bound loop with G independent chains per candidate needs no more).
-template <int G>
-__global__ __launch_bounds__(256, 2) void mse_rows_reg_kernel(const float* W, int64_t N, int64_t ldw, int64_t kgroups, QGrid grid,
+//
+// Element types: fp32 as it is; fp16 / bf16 converted exactly at the load for G <= 128 (the tile is the fp32 one from there on).
+// G = 256 exists for the 2-byte types only and keeps the tile PACKED, elements 2 i and 2 i + 1 of the group in one register (128
+// registers; as fp32 the tile alone would be the whole budget of two waves per SIMD): a chunk's 16 elements are unpacked where a
+// candidate uses them.  Same chunks, same order of the sum: the masks mse_rows_kernel gives at g = 256.  Every lane loads one
+// element a row, so rows that are only 2-byte aligned need no path of their own.
+template <typename E, int G>
+__global__ __launch_bounds__(256, 2) void mse_rows_reg_kernel(const typename E::raw* W, int64_t N, int64_t ldw, int64_t kgroups, QGrid grid,
                                                              MseRow* rows, uint32_t* any_mask) {
+    typedef typename E::raw raw;
+    constexpr bool kPacked = G > 128;
+    static_assert(G % kMseChunk == 0 && G <= 256 && (!kPacked || sizeof(raw) == 2), "register tile");
     const int64_t n = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const int64_t kg = blockIdx.y;
     const bool live = n < N;
     const int64_t nc = live ? n : N - 1;
     // wave-uniform row base + one 32-bit lane offset for all G loads (no 64-bit per-lane address per row)
     const char* base = reinterpret_cast<const char*>(W + kg * G * ldw);
-    const uint32_t lane_off = static_cast<uint32_t>(nc) * 4u;
-    const int64_t row_bytes = ldw * 4;
-    float x[G];
+    const uint32_t lane_off = static_cast<uint32_t>(nc) * static_cast<uint32_t>(sizeof(raw));
+    const int64_t row_bytes = ldw * static_cast<int64_t>(sizeof(raw));
+    float x[kPacked ? 1 : G];
+    uint32_t xp[kPacked ? G / 2 : 1];
+    (void)x; (void)xp;
+    float mn, mx;
+    if constexpr (kPacked) {
+        // 16 loads in flight, then their 8 packed registers, pinned HERE (the device of hqq_rounds_reg_kernel): left alone all 256
+        // loads are issued first, each into a register of its own, and the tile spills on the way.  The range is folded batch by
+        // batch from the pinned registers, r = 0 .. G-1 as below.
+        mn = mx = 0.f;
 #pragma unroll
-    for (int r = 0; r < G; ++r) x[r] = *reinterpret_cast<const float*>(base + r * row_bytes + lane_off);
-    float mn = x[0], mx = x[0];
+        for (int tb = 0; tb < G; tb += 16) {
 #pragma unroll
-    for (int r = 1; r < G; ++r) {
-        mn = nmin(mn, x[r]);
-        mx = nmax(mx, x[r]);
+            for (int u = 0; u < 16; u += 2)
+                xp[(tb + u) / 2] = static_cast<uint32_t>(*reinterpret_cast<const raw*>(base + (tb + u) * row_bytes + lane_off)) |
+                                   (static_cast<uint32_t>(*reinterpret_cast<const raw*>(base + (tb + u + 1) * row_bytes + lane_off)) << 16);
+            asm volatile("" : "+v"(xp[tb / 2]), "+v"(xp[tb / 2 + 1]), "+v"(xp[tb / 2 + 2]), "+v"(xp[tb / 2 + 3]), "+v"(xp[tb / 2 + 4]),
+                              "+v"(xp[tb / 2 + 5]), "+v"(xp[tb / 2 + 6]), "+v"(xp[tb / 2 + 7]));
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const float v = E::one(static_cast<raw>(xp[(tb + u) / 2] >> (16 * (u & 1))));
+                mn = tb + u == 0 ? v : nmin(mn, v);
+                mx = tb + u == 0 ? v : nmax(mx, v);
+            }
+            asm volatile("" : "+v"(mn), "+v"(mx));   // the batch's range exists before the next batch's loads land
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < G; ++r) x[r] = E::one(*reinterpret_cast<const raw*>(base + r * row_bytes + lane_off));
+        mn = x[0]; mx = x[0];
+#pragma unroll
+        for (int r = 1; r < G; ++r) {
+            mn = nmin(mn, x[r]);
+            mx = nmax(mx, x[r]);
+        }
     }
     const float lo0 = nmin(mn, 0.0f), hi0 = nmax(mx, 0.0f);
     float best = FLT_MAX;   // np.finfo(float32).max, utils.py:190
@@ -156,7 +208,8 @@ __global__ __launch_bounds__(256, 2) void mse_rows_reg_kernel(const float* W, in
         const ColQ c = make_colq(qp, mn, mx, 0);
         const float lo_f = static_cast<float>(grid.qmin), hi_f = static_cast<float>(grid.qmax);
         float err = 0.f;
-#pragma unroll
+        // (unroll(full): `#pragma unroll` leaves the 16 chunks of G = 256 rolled, and a rolled loop indexes the tile in scratch)
+#pragma clang loop unroll(full)
         for (int r0 = 0; r0 < G; r0 += kMseChunk) {
             float e[kMseChunk];
             float off = 0.f;   // max |t - rint(t)| of the chunk (t is finite whenever c.thr > 0, make_colq)
@@ -164,22 +217,33 @@ __global__ __launch_bounds__(256, 2) void mse_rows_reg_kernel(const float* W, in
             // runs several chunks' temporaries at once and spills the tile at G = 128)
             float rinv = c.rinv;
             asm volatile("" : "+v"(rinv), "+v"(err));
+            // the chunk's values: the tile's own registers, or unpacked HERE from the chunk's 8 packed ones (opaque per candidate:
+            // the unpacked values do not change from candidate to candidate, and kept they are the fp32 tile)
+            float xu[kPacked ? kMseChunk : 1];
+            (void)xu;
+            if constexpr (kPacked) {
+                asm volatile("" : "+v"(xp[r0 / 2]), "+v"(xp[r0 / 2 + 1]), "+v"(xp[r0 / 2 + 2]), "+v"(xp[r0 / 2 + 3]), "+v"(xp[r0 / 2 + 4]),
+                                  "+v"(xp[r0 / 2 + 5]), "+v"(xp[r0 / 2 + 6]), "+v"(xp[r0 / 2 + 7]));
+#pragma unroll
+                for (int r = 0; r < kMseChunk; ++r) xu[r] = E::one(static_cast<raw>(xp[(r0 + r) / 2] >> (16 * (r & 1))));
+            }
+            const float* xc = kPacked ? xu : x + r0;
 #pragma unroll
             for (int r = 0; r < kMseChunk; ++r) {
-                const float t = x[r0 + r] * rinv;
+                const float t = xc[r] * rinv;
                 const float k = rintf(t);
                 off = fmaxf(off, fabsf(t - k));
                 const float lvl = __builtin_amdgcn_fmed3f(k + c.zpb, lo_f, hi_f);
-                const float d = (lvl - c.zpb) * c.scale - x[r0 + r];
+                const float d = (lvl - c.zpb) * c.scale - xc[r];
                 e[r] = __builtin_amdgcn_exp2f(kMseNorm * __builtin_amdgcn_logf(fabsf(d)));
             }
             if (shifted) {   // tiny magnitudes (wave-uniform, see the header): the plain division and the shifted power
                 const int shift = mse_pow_shift(lo0, hi0, grid);
 #pragma unroll
-                for (int r = 0; r < kMseChunk; ++r) e[r] = fake_quant_error_shifted(x[r0 + r], qp, grid, shift);
+                for (int r = 0; r < kMseChunk; ++r) e[r] = fake_quant_error_shifted(xc[r], qp, grid, shift);
             } else if (__builtin_amdgcn_ballot_w64(!(off < c.thr)) != 0) {
 #pragma unroll
-                for (int r = 0; r < kMseChunk; ++r) e[r] = fake_quant_error(x[r0 + r], qp, grid);
+                for (int r = 0; r < kMseChunk; ++r) e[r] = fake_quant_error(xc[r], qp, grid);
             }
 #pragma unroll
             for (int r = 0; r < kMseChunk; ++r) err += e[r];
@@ -201,7 +265,8 @@ __global__ __launch_bounds__(256, 2) void mse_rows_reg_kernel(const float* W, in
 }
 
 // tensor: per-block partial sums of all 20 candidate errors
-__global__ __launch_bounds__(256) void mse_tensor_partial(const float* W, int64_t K, int64_t N, int64_t ldw, const float* range,
+template <typename E>
+__global__ __launch_bounds__(256) void mse_tensor_partial(const typename E::raw* W, int64_t K, int64_t N, int64_t ldw, const float* range,
                                                           QGrid grid, float* partial /* [blocks][20] */) {
     __shared__ float s_sum[4][kMseSteps];
     const float lo0 = nmin(range[0], 0.0f), hi0 = nmax(range[1], 0.0f);
@@ -216,7 +281,7 @@ __global__ __launch_bounds__(256) void mse_tensor_partial(const float* W, int64_
     for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total;
          t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
         const int64_t k = t / N, n = t - k * N;
-        const float x = W[k * ldw + n];
+        const float x = E::one(W[k * ldw + n]);
         if (shift != 0) {
 #pragma unroll
             for (int i = 0; i < kMseSteps; ++i) acc[i] += fake_quant_error_shifted(x, qp[i], grid, shift);
@@ -255,13 +320,14 @@ __global__ void mse_tensor_mask(const float* partial, int nblocks, const float* 
 }
 
 // raw (min, max) of the whole tensor -> range[2] (single block; the tensor strategy is the plumbing case)
-__global__ __launch_bounds__(1024) void tensor_minmax_kernel(const float* W, int64_t K, int64_t N, int64_t ldw, float* range) {
+template <typename E>
+__global__ __launch_bounds__(1024) void tensor_minmax_kernel(const typename E::raw* W, int64_t K, int64_t N, int64_t ldw, float* range) {
     __shared__ float s_mn[16], s_mx[16];
     float mn = INFINITY, mx = -INFINITY;
     const int64_t total = K * N;
     for (int64_t t = threadIdx.x; t < total; t += blockDim.x) {
         const int64_t k = t / N, n = t - k * N;
-        const float x = W[k * ldw + n];
+        const float x = E::one(W[k * ldw + n]);
         mn = nmin(mn, x);
         mx = nmax(mx, x);
     }
@@ -305,14 +371,11 @@ size_t rtn_mse_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
     return static_cast<size_t>(rows) * sizeof(MseRow) + 1024 * kMseSteps * sizeof(float) + 512;
 }
 
-int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid_in, int32_t strategy, int64_t g,
-                     void* q_out, float* scale_out, void* zp_out, int32_t zp_signed, void* workspace, size_t workspace_bytes,
-                     hipStream_t s, bool emit_q) {
-    const size_t need = rtn_mse_workspace(K, N, strategy, g);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "rtn(mse): workspace of %zu bytes needed, %zu given", need,
-               workspace_bytes);
-    QGrid grid = grid_in;
-    grid.clip_ratio = 1.0f;  // utils.py:188 and :334-344: the MSE range replaces the clipped one
+// The search itself, from the cleared stop word to the resolved (scale, zp) of every row: one implementation for the three
+// element types.  `grid` is the search's own (clip_ratio 1); the workspace has been checked.
+template <typename E>
+static int32_t mse_search(const typename E::raw* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g,
+                          float* scale_out, void* zp_out, void* workspace, hipStream_t s) {
     const int64_t kgroups = strategy == OQ_TENSOR ? 1 : K / g;
     const int64_t rows = strategy == OQ_TENSOR ? 1 : N * kgroups;
     char* base = static_cast<char*>(workspace);
@@ -324,25 +387,54 @@ int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QG
     int32_t st;
     if (strategy == OQ_TENSOR) {
         const int nblocks = 1024;
-        hipLaunchKernelGGL(tensor_minmax_kernel, dim3(1), dim3(1024), 0, s, W, K, N, ldw, range);
-        hipLaunchKernelGGL(mse_tensor_partial, dim3(nblocks), dim3(256), 0, s, W, K, N, ldw, range, grid, partial);
+        hipLaunchKernelGGL(tensor_minmax_kernel<E>, dim3(1), dim3(1024), 0, s, W, K, N, ldw, range);
+        hipLaunchKernelGGL(mse_tensor_partial<E>, dim3(nblocks), dim3(256), 0, s, W, K, N, ldw, range, grid, partial);
         hipLaunchKernelGGL(mse_tensor_mask, dim3(1), dim3(64), 0, s, partial, nblocks, range, rowbuf, any_mask);
         st = check_launch("mse_tensor");
     } else {
         const dim3 gd(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups));
-        if (g == 128) hipLaunchKernelGGL((mse_rows_reg_kernel<128>), gd, dim3(256), 0, s, W, N, ldw, kgroups, grid, rowbuf, any_mask);
-        else if (g == 64) hipLaunchKernelGGL((mse_rows_reg_kernel<64>), gd, dim3(256), 0, s, W, N, ldw, kgroups, grid, rowbuf, any_mask);
-        else if (g == 32) hipLaunchKernelGGL((mse_rows_reg_kernel<32>), gd, dim3(256), 0, s, W, N, ldw, kgroups, grid, rowbuf, any_mask);
-        else hipLaunchKernelGGL(mse_rows_kernel, gd, dim3(256), 0, s, W, K, N, ldw, g, kgroups, grid, rowbuf, any_mask);
+        constexpr bool half = sizeof(typename E::raw) == 2;   // group 256: the packed tile, which exists for the 2-byte types only
+        if (g == 128) hipLaunchKernelGGL((mse_rows_reg_kernel<E, 128>), gd, dim3(256), 0, s, W, N, ldw, kgroups, grid, rowbuf, any_mask);
+        else if (g == 64) hipLaunchKernelGGL((mse_rows_reg_kernel<E, 64>), gd, dim3(256), 0, s, W, N, ldw, kgroups, grid, rowbuf, any_mask);
+        else if (g == 32) hipLaunchKernelGGL((mse_rows_reg_kernel<E, 32>), gd, dim3(256), 0, s, W, N, ldw, kgroups, grid, rowbuf, any_mask);
+        else if (half && g == 256) {
+            if constexpr (half) hipLaunchKernelGGL((mse_rows_reg_kernel<E, 256>), gd, dim3(256), 0, s, W, N, ldw, kgroups, grid, rowbuf, any_mask);
+        } else hipLaunchKernelGGL(mse_rows_kernel<E>, gd, dim3(256), 0, s, W, K, N, ldw, g, kgroups, grid, rowbuf, any_mask);
         st = check_launch("mse_rows_kernel");
     }
     if (st != OQ_OK) return st;
     hipLaunchKernelGGL(mse_resolve_kernel, dim3(static_cast<uint32_t>(ceil_div(rows, 256))), dim3(256), 0, s, rowbuf, rows, any_mask, grid,
                        scale_out, static_cast<uint8_t*>(zp_out));
-    st = check_launch("mse_resolve_kernel");
+    return check_launch("mse_resolve_kernel");
+}
+
+int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid_in, int32_t strategy, int64_t g,
+                     void* q_out, float* scale_out, void* zp_out, int32_t zp_signed, void* workspace, size_t workspace_bytes,
+                     hipStream_t s, bool emit_q) {
+    const size_t need = rtn_mse_workspace(K, N, strategy, g);
+    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "rtn(mse): workspace of %zu bytes needed, %zu given", need,
+               workspace_bytes);
+    QGrid grid = grid_in;
+    grid.clip_ratio = 1.0f;  // utils.py:188 and :334-344: the MSE range replaces the clipped one
+    const int64_t kgroups = strategy == OQ_TENSOR ? 1 : K / g;
+    const int32_t st = mse_search<MseF32>(W, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s);
     if (st != OQ_OK || !emit_q) return st;
     return launch_quantize_kn(W, K, N, ldw, g, kgroups, scale_out, static_cast<const uint8_t*>(zp_out), static_cast<uint8_t*>(q_out),
                               grid, zp_signed, strategy == OQ_TENSOR, s, OQ_LAYOUT_KN);
+}
+
+// oq_rtn_mse_h16 (rtn_half.hip makes every check): the same search on the 2-byte matrix, then the stored-parameter pass of the
+// half kernels (IEEE division: the integers launch_quantize_kn gives on the upcast matrix).
+int32_t rtn_mse_half_impl(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, const QGrid& grid_in, int32_t strategy, int64_t g,
+                          void* q_out, float* scale_out, void* zp_out, void* workspace, hipStream_t s) {
+    QGrid grid = grid_in;
+    grid.clip_ratio = 1.0f;  // as above
+    const uint16_t* w = static_cast<const uint16_t*>(W);
+    const int32_t st = wtype == OQ_W_F16 ? mse_search<ElemF16>(w, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s)
+                                         : mse_search<ElemBF16>(w, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s);
+    if (st != OQ_OK || q_out == nullptr) return st;
+    return launch_half_quantize_kn(W, wtype, K, N, ldw, g, strategy == OQ_TENSOR ? 1 : K / g, scale_out, static_cast<uint8_t*>(zp_out),
+                                   static_cast<uint8_t*>(q_out), grid, strategy == OQ_TENSOR, s);
 }
 
 }  // namespace oq

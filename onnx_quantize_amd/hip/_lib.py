@@ -125,6 +125,8 @@ HALF_PROTOTYPES = {
     "oq_half_extension_version": (_i32, []),
     "oq_rtn_half_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
     "oq_rtn_quantize_h16": (_i32, [_p, _i32, _i64, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _f32, _p, _p, _p, _i32, _p, _sz, _p]),
+    "oq_rtn_mse_half_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "oq_rtn_mse_h16": (_i32, [_p, _i32, _i64, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _f32, _p, _p, _p, _i32, _p, _sz, _p]),
     "oq_rtn_quantize_ptrs_h16": (_i32, [_p, _p, _i64, _i32, _i64, _i64, _i64, _i32, _i64, _i32, _i32, _f32, _i32, _p]),
     "oq_hqq_optimize_h16": (_i32, [_p, _i32, _i64, _i64, _i64, _i64, _i32, _p, _p, _f64, _f64, _f64, _i32, _i32, _i32, _p, _i32, _p, _p,
                                    _p, _sz, _p]),

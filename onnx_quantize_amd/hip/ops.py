@@ -174,8 +174,9 @@ def _rtn_outputs(layout, k, n, g, qtype, count, dev, emit_q, out):
     return q, torch.empty(count, dtype=torch.float32, device=dev), torch.empty(count, dtype=container_dtype(qtype), device=dev)
 
 
-def _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out):
-    """`rtn_quantize` on an fp16 / bf16 matrix through oq_rtn_quantize_h16 (csrc/rtn_half.hip): W is read as it is."""
+def _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out, mse=False):
+    """`rtn_quantize` on an fp16 / bf16 matrix through oq_rtn_quantize_h16 (csrc/rtn_half.hip), or with ``mse`` (layout "kn"
+    only, the caller's rule) through oq_rtn_mse_h16 (csrc/rtn_mse.hip): W is read as it is."""
     _require_matrix(w, None)
     _layout_code(layout)
     if layout == "kn_packed4":
@@ -199,10 +200,12 @@ def _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, 
     dev = w.device
     q, scale, zp = _rtn_outputs(layout, k, n, g, qtype, count, dev, emit_q, out)
     gs = -1 if group_size is None else int(group_size)
-    ws = _workspace(lib.oq_rtn_half_workspace_bytes(k, n, L.STRATEGY_CODE[strategy], gs), dev)
-    L.check(lib.oq_rtn_quantize_h16(_ptr(w), _HALF_WTYPE[w.dtype], k, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
-                                    int(symmetric), int(reduce_range), float(clip_ratio), _ptr(q if emit_q else None), _ptr(scale),
-                                    _ptr(zp), _layout_code(layout), _ptr(ws), ws.numel(), _stream()))
+    # the two entry points take the same arguments
+    query, entry = (lib.oq_rtn_mse_half_workspace_bytes, lib.oq_rtn_mse_h16) if mse else (lib.oq_rtn_half_workspace_bytes, lib.oq_rtn_quantize_h16)
+    ws = _workspace(query(k, n, L.STRATEGY_CODE[strategy], gs), dev)
+    L.check(entry(_ptr(w), _HALF_WTYPE[w.dtype], k, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
+                  int(symmetric), int(reduce_range), float(clip_ratio), _ptr(q if emit_q else None), _ptr(scale),
+                  _ptr(zp), _layout_code(layout), _ptr(ws), ws.numel(), _stream()))
     return (q if emit_q else None), scale.reshape(shape), zp.reshape(shape)
 
 
@@ -222,17 +225,19 @@ def rtn_quantize(w: torch.Tensor, qtype: str, strategy: str, group_size=-1, symm
       - layouts "kn" / "nbits", any strategy, groups that divide K, no mse: oq_rtn_quantize_h16 reads the 2-byte matrix
         as it is (one fused launch for groups of up to 256 rows, a range pass and a quantize pass otherwise);
       - layout "kn_packed4": the "kn" route followed by `pack_nibbles`;
-      - ``mse=True`` and groups that straddle columns (K % group_size != 0) have no half kernel: ONE device cast,
-        ``w.float()``, then the fp32 path below.
+      - ``mse=True`` (layout "kn", groups that divide K): oq_rtn_mse_h16 runs the fp32 search's arithmetic on the 2-byte
+        matrix, no fp32 copy; a group of 256 is held in registers as packed halves, which the fp32 search cannot do;
+      - groups that straddle columns (K % group_size != 0) have no half kernel: ONE device cast, ``w.float()``, then the
+        fp32 path below (``mse=True`` with a layout other than "kn" goes there too, for the fp32 path's refusal).
     A LIST of half matrices (a resident model) goes through `rtn_quantize_model`: one launch for the matrices of a shape.
     """
     _require_device(w, "w")
     if w.dtype in _HALF_WTYPE:
         if w.dim() == 2:
             g_h = resolve_group(strategy, w.shape[0], group_size if group_size is not None else -1)
-            if not mse and g_h > 0 and w.shape[0] % g_h == 0:
-                return _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out)
-        w = w.float()      # the documented cast route: mse, straddling groups
+            if g_h > 0 and w.shape[0] % g_h == 0 and (not mse or layout == "kn"):
+                return _rtn_quantize_half(w, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, emit_q, out, mse)
+        w = w.float()      # the documented cast route: straddling groups (and mse with a layout it refuses: the fp32 path's error)
     _require_device(w, "w", torch.float32)
     _require_matrix(w)
     w, ldw = _row_major(w)
@@ -286,8 +291,8 @@ def hqq_quantize(w: torch.Tensor, group_size: int, reduce_range=False, clip_rati
     A half-precision ``w`` gives, by definition, the result of this function on ``w.float()`` (both conversions are exact, the
     arithmetic of HQQ stays fp32): the same integers, scales, zero points and rounds, bit for bit.  oq_hqq_optimize_h16 reads the
     2-byte matrix as it is, rows that are only 2-byte aligned included; no fp32 copy exists.  The initial parameters come from
-    `rtn_quantize` on the half matrix; only ``mse=True`` takes its one cast, ``w.float()``, for those parameters (no half MSE
-    search) -- the HQQ kernels read the half matrix there as well.  A group of 256 runs all rounds in one pass over a half ``w``
+    `rtn_quantize` on the half matrix, with ``mse=True`` from its half MSE search (oq_rtn_mse_h16): no route makes an fp32
+    copy.  A group of 256 runs all rounds in one pass over a half ``w``
     (the fp32 kernels re-read W every round at that size); ``per_round_launches=True`` forces the per-round route."""
     _require_device(w, "w")
     half = w.dtype in _HALF_WTYPE
