@@ -254,7 +254,8 @@ template <bool PIECES>
 __global__ __launch_bounds__(512, 2) void awq_group_diff_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, int64_t g, QGrid grid, int wpg,
                                                                 const float* __restrict__ row_scale, float* __restrict__ D,
                                                                 float* __restrict__ absmax_partial, const float* __restrict__ piece_scale,
-                                                                float* __restrict__ piece_header, u32x4a* __restrict__ P, int64_t Np) {
+                                                                float* __restrict__ piece_header, u32x4a* __restrict__ P, int64_t Np,
+                                                                const float* __restrict__ act) {
     __shared__ float4 s_mn[8][64];
     __shared__ float4 s_mx[8][64];
     __shared__ float s_abs[8];
@@ -272,10 +273,12 @@ __global__ __launch_bounds__(512, 2) void awq_group_diff_kernel(const float* __r
     const int64_t lcol = col_ok ? tile_col0 + lane * 4 : N - 4;
     float4 w[16];
     float sr[16];
+    uint32_t dead = 0;      // PIECES: bit r = row r's input channel is dead (mean |x| == 0); uniform, lives in a scalar register
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         w[r] = *reinterpret_cast<const float4*>(W + (row0 + r) * ldw + lcol);
         sr[r] = row_scale != nullptr ? row_scale[row0 + r] : 1.0f;     // uniform: scalar loads
+        if constexpr (PIECES) dead |= (act != nullptr && act[row0 + r] == 0.0f) ? (1u << r) : 0u;
     }
     auto scaled = [&](int r, int i) -> float {      // what the candidate quantizes: w * s (awq.py:156), or w (the clip search)
         const float x = i == 0 ? w[r].x : i == 1 ? w[r].y : i == 2 ? w[r].z : w[r].w;
@@ -370,7 +373,9 @@ __global__ __launch_bounds__(512, 2) void awq_group_diff_kernel(const float* __r
                     const float4 a = w[8 * c + 2 * rp], b = w[8 * c + 2 * rp + 1];
                     const float xa = i == 0 ? a.x : i == 1 ? a.y : i == 2 ? a.z : a.w;
                     const float xb = i == 0 ? b.x : i == 1 ? b.y : i == 2 ? b.z : b.w;
-                    const f16x2a h2 = {static_cast<_Float16>(col_ok ? xa * sc : 0.f), static_cast<_Float16>(col_ok ? xb * sc : 0.f)};
+                    // a dead channel's row is outside the bound that made `sc` (awq_bound_kernel) and multiplies zeros of X: zeros
+                    const bool oka = col_ok && !(dead >> (8 * c + 2 * rp) & 1u), okb = col_ok && !(dead >> (8 * c + 2 * rp + 1) & 1u);
+                    const f16x2a h2 = {static_cast<_Float16>(oka ? xa * sc : 0.f), static_cast<_Float16>(okb ? xb * sc : 0.f)};
                     v[rp] = __builtin_bit_cast(uint32_t, h2);
                 }
                 stage[lane * 4 + i] = v;
@@ -444,19 +449,26 @@ __global__ __launch_bounds__(256) void row_absmax_kernel(const float* __restrict
 // candidate that was 6 % of the search): blockIdx.y = candidate (row scales at row_scales + y * K; nullptr: the clip
 // search, whose ten candidates share one bound), one wave per group, then one block per candidate folds the groups into
 // the pieces' scale triple [s, 1 / s^2, 1 / s] (the form of syrk_bf16x3.hip::absmax_scale_body).
-__global__ __launch_bounds__(64) void awq_bound_kernel(const float* __restrict__ rowmax, const float* __restrict__ row_scales, int64_t K, int64_t g,
-                                                       float* __restrict__ bound) {
+// DEAD input channels (act[k] == mean |x[:, k]| == 0; act == nullptr: none are known) stay out of the bound: their candidate
+// scale is the 1e-4 clamp, so one of them next to an outlier channel in its group (scale 1e2 .. 1e3 after normalisation) makes
+// max(rowmax s) / min(s) seven orders of magnitude larger than any |D| -- 96 x 256 x 64 with one dead and one x1000 channel: bound
+// 5e6, max |D| 0.2 -- and the first pieces of the rows that carry the loss sink into fp16's subnormals (loss off by 2.7e-3,
+// tests/test_awq_edges_gpu.py section 4).  Such a row multiplies a zero column of X: awq_group_diff_kernel writes its pieces
+// as zeros, and what the bound covers is every row that reaches the loss.
+__global__ __launch_bounds__(64) void awq_bound_kernel(const float* __restrict__ rowmax, const float* __restrict__ row_scales, const float* __restrict__ act,
+                                                       int64_t K, int64_t g, float* __restrict__ bound) {
     const float* row_scale = row_scales != nullptr ? row_scales + static_cast<int64_t>(blockIdx.y) * K : nullptr;
     const int64_t k0 = static_cast<int64_t>(blockIdx.x) * g;
     float top = 0.f, smin = INFINITY;
     for (int64_t k = k0 + threadIdx.x; k < k0 + g; k += 64) {
+        if (act != nullptr && act[k] == 0.0f) continue;
         const float sk = row_scale != nullptr ? fabsf(row_scale[k]) : 1.0f;
         top = nmax(top, rowmax[k] * sk);
         smin = nmin(smin, sk);
     }
     top = wave_max(top);
     smin = -wave_max(-smin);
-    if (threadIdx.x == 0) bound[static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x] = 2.2f * top / smin;
+    if (threadIdx.x == 0) bound[static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x] = 2.2f * top / smin;   // a group of dead rows only: 0 / inf = 0
 }
 
 __global__ __launch_bounds__(256) void awq_piece_scales_kernel(const float* __restrict__ bound, const int ngroups, float* __restrict__ triples) {
@@ -590,11 +602,12 @@ static bool pieces_route(const AwqWs& w, int64_t K) {
 }
 
 // once per search, fused route: row maxima of W, the bounds and the pieces' scales of all candidates (three launches)
-static int32_t prepare_piece_scales(const AwqWs& w, const float* W, int64_t K, int64_t N, int64_t ldw, int64_t g, const float* row_scales, int n_cand,
-                                    hipStream_t s) {
+// (`act`: the scale search's mean |x| per channel, whose zeros are the dead channels; nullptr for the clip search)
+static int32_t prepare_piece_scales(const AwqWs& w, const float* W, int64_t K, int64_t N, int64_t ldw, int64_t g, const float* row_scales, const float* act,
+                                    int n_cand, hipStream_t s) {
     hipLaunchKernelGGL(row_absmax_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, w.rowmax);
     const int nc = row_scales != nullptr ? n_cand : 1;
-    hipLaunchKernelGGL(awq_bound_kernel, dim3(static_cast<uint32_t>(K / g), static_cast<uint32_t>(nc)), dim3(64), 0, s, w.rowmax, row_scales, K, g, w.bounds);
+    hipLaunchKernelGGL(awq_bound_kernel, dim3(static_cast<uint32_t>(K / g), static_cast<uint32_t>(nc)), dim3(64), 0, s, w.rowmax, row_scales, act, K, g, w.bounds);
     hipLaunchKernelGGL(awq_piece_scales_kernel, dim3(static_cast<uint32_t>(nc)), dim3(256), 0, s, w.bounds, static_cast<int>(K / g), w.triples);
     return check_launch("awq piece scales");
 }
@@ -617,14 +630,16 @@ static int32_t candidate_loss(const AwqWs& w, const float* W, int64_t ldw, const
             // (prepare_piece_scales: all candidates ahead of the loop)
             hipLaunchKernelGGL(awq_group_diff_kernel<true>, dgrid, dim3(512), 0, s, W, K, N, ldw, g, grid, wpg, row_scale, static_cast<float*>(nullptr),
                                static_cast<float*>(nullptr), w.triples + 4 * (row_scale != nullptr ? candidate : 0), reinterpret_cast<float*>(w.pieces_d),
-                               reinterpret_cast<u32x4a*>(w.pieces_d + gemm_f16x3_header_bytes()), gemm_f16x3_padded_cols(N));
+                               reinterpret_cast<u32x4a*>(w.pieces_d + gemm_f16x3_header_bytes()), gemm_f16x3_padded_cols(N),
+                               row_scale != nullptr ? static_cast<const float*>(w.act) : nullptr);      // dead channels: see awq_bound_kernel
             st = check_launch("awq_group_diff_kernel (pieces)");
             if (st != OQ_OK) return st;
             float* part = w.gemm_part + static_cast<int64_t>(candidate) * loss_stride(T, K, N);
             return launch_gemm_f16x3(w.pieces_x, w.pieces_d, T, N, K, 1.0f, 0.0f, nullptr, 0, part, s);
         }
         hipLaunchKernelGGL(awq_group_diff_kernel<false>, dgrid, dim3(512), 0, s, W, K, N, ldw, g, grid, wpg, row_scale, w.D, w.diff_part,
-                           static_cast<const float*>(nullptr), static_cast<float*>(nullptr), static_cast<u32x4a*>(nullptr), static_cast<int64_t>(0));
+                           static_cast<const float*>(nullptr), static_cast<float*>(nullptr), static_cast<u32x4a*>(nullptr), static_cast<int64_t>(0),
+                           static_cast<const float*>(nullptr));
         nparts = static_cast<int>(dgrid.x * dgrid.y);
     } else {
         const float* Wq = W;
@@ -737,7 +752,7 @@ int32_t oq_awq_scale_search_f32(const float* X, int64_t T, int64_t K, int64_t ld
     st = prepare_activations(w, X, T, K, ldx, stream, s);
     if (st != OQ_OK) return st;
     if (pieces_route(w, K) && group_fused(strategy, g, K, N, ldw, W)) {
-        st = prepare_piece_scales(w, W, K, N, ldw, g, scales_out, n_grid, s);
+        st = prepare_piece_scales(w, W, K, N, ldw, g, scales_out, w.act, n_grid, s);
         if (st != OQ_OK) return st;
     }
     for (int i = 0; i < n_grid; ++i) {
@@ -767,7 +782,7 @@ int32_t oq_awq_clip_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx
     st = prepare_activations(w, X, T, K, ldx, stream, s);
     if (st != OQ_OK) return st;
     if (pieces_route(w, K) && group_fused(strategy, g, K, N, ldw, W)) {
-        st = prepare_piece_scales(w, W, K, N, ldw, g, nullptr, 10, s);
+        st = prepare_piece_scales(w, W, K, N, ldw, g, nullptr, nullptr, 10, s);
         if (st != OQ_OK) return st;
     }
     for (int i = 0; i < 10; ++i) {
