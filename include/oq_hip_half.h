@@ -1,7 +1,7 @@
 /*
- * oq_hip_half.h -- half-precision extension of the C ABI of oq_hip.h: RTN and HQQ on fp16 / bf16 weights, the GPTQ Hessian and the
- * calibration statistics (running min / max, absmax, the |x| column statistics of the AWQ / SmoothQuant searches) of fp16 / bf16
- * activations, all read as they are.
+ * oq_hip_half.h -- half-precision extension of the C ABI of oq_hip.h: RTN, HQQ and the AWQ / SmoothQuant searches on fp16 / bf16
+ * weights, the GPTQ Hessian and the calibration statistics (running min / max, absmax, the |x| column statistics of the AWQ /
+ * SmoothQuant searches) of fp16 / bf16 activations, all read as they are.
  *
  * oq_hip.h stays what it is (OQ_ABI_VERSION 2); the entry points below live in the same library and follow the same
  * conventions (device pointers, asynchronous on `stream`, no allocation, 0 or a negative oq_status, oq_last_error()).
@@ -260,6 +260,60 @@ typedef struct {
 size_t oq_abs_stats_many_half_workspace_bytes(const oq_abs_stats_item* items_host, int64_t count);
 int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq_abs_stats_item* items_device, int64_t count,
                                    int32_t xtype /* oq_wtype */, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N2h pre_passes/awq.py:114-184 (scale search), :207-259 (clip search) and pre_passes/smooth_quant.py:62-74, :111-113 on
+ *     W.astype(np.float32), without the fp32 copy: replace the cast followed by oq_awq_scale_search_f32,
+ *     oq_awq_clip_search_f32, oq_awq_scale_search_stats_f32, oq_awq_clip_search_stats_f32 and oq_smooth_quant_scale_f32
+ *     (oq_hip.h).  A search reads W once per candidate (20 + 10 passes) and for its weight statistics; every one of those
+ *     reads takes the 2-byte matrix as it is and converts at the load.  Both conversions are exact, every lane owns the
+ *     elements it owns in the fp32 kernels and every sum keeps its order, so the result is DEFINED as that of the `_f32`
+ *     entry point on the upcast matrix: `scales_out` (all n_grid rows), `losses_out`, `best_out` and `scale_out` match it
+ *     byte for byte, NaN patterns included.
+ *
+ *   arguments  those of the `_f32` twins, with `const void* W, int32_t wtype` in place of `const float* W`.  X, act_sum and G
+ *              stay fp32 (half activations become statistics through N2s and oq_hessian_accumulate_h16).
+ *   W          [K, N], 2 bytes per element of type `wtype`, leading dimension ldw >= N (elements), 2-byte aligned.
+ *              N % 4 == 0, ldw % 4 == 0 and an 8-byte aligned base give 8-byte loads (four elements) on the fused group
+ *              kernel, the four-column difference kernel and the row-scale kernel; anything else -- rows that are only
+ *              2-byte aligned are legal -- takes the one-column kernels and gives the same bytes.
+ *   routes     those of the fp32 searches.  The general route quantizes through the fp32 RTN: for the scale search on the
+ *              candidate's scaled weights, which are written as fp32 from the 2-byte W (as for fp32); for the clip search
+ *              on W itself, through oq_rtn_quantize_h16 -- no fp32 copy of W exists on any route.
+ *   workspace  256-byte aligned.
+ *                oq_awq_half_workspace_bytes(T, K, N)     = oq_awq_workspace_bytes(T, K, N)     + R(K, N)
+ *                oq_awq_stats_half_workspace_bytes(K, N)  = oq_awq_stats_workspace_bytes(K, N)  + R(K, N)
+ *                R(K, N) = 8 * N * (ceil(K / 64) + K / 257 + 1) rounded up to 256, + 256
+ *              (R: the partial ranges of oq_rtn_quantize_h16 for channel, tensor and groups of more than 256 rows, behind the
+ *              fp32 layout).  Both return 0 where the fp32 query returns 0 (a shape outside the bounds, K > 65535).
+ *              oq_smooth_quant_scale_h16 takes oq_smooth_quant_workspace_bytes(K), as its twin.
+ *   checks     an unknown wtype and a W that is not 2-byte aligned OQ_ERR_INVALID_ARGUMENT; then every refusal of the twin
+ *              with its status (n_grid outside 1 .. 64, a group below 4 or one that does not divide K, K > 65535, a
+ *              missing, short or misaligned workspace, null pointers) -- all on the host before the first launch: on any
+ *              refusal no output is touched.
+ * ------------------------------------------------------------------------------------------- */
+size_t oq_awq_half_workspace_bytes(int64_t T, int64_t K, int64_t N);
+size_t oq_awq_stats_half_workspace_bytes(int64_t K, int64_t N);
+int32_t oq_awq_scale_search_h16(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int32_t wtype, int64_t N,
+                                int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size, int32_t symmetric,
+                                int32_t reduce_range, int32_t n_grid, float* scales_out /* [n_grid, K] */, float* losses_out,
+                                int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream);
+int32_t oq_awq_clip_search_h16(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int32_t wtype, int64_t N,
+                               int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size, int32_t symmetric,
+                               int32_t reduce_range, float* losses_out /* [10] */, int32_t* best_out, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int32_t oq_awq_scale_search_stats_h16(const float* act_sum, const float* G, int64_t T, int64_t K, const void* W, int32_t wtype,
+                                      int64_t N, int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size,
+                                      int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
+                                      float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+int32_t oq_awq_clip_search_stats_h16(const float* G, int64_t T, int64_t K, const void* W, int32_t wtype, int64_t N, int64_t ldw,
+                                     int32_t qtype, int32_t strategy, int64_t group_size, int32_t symmetric,
+                                     int32_t reduce_range, float* losses_out, int32_t* best_out, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int32_t oq_smooth_quant_scale_h16(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int32_t wtype, int64_t N,
+                                  int64_t ldw, float alpha, float* scale_out, void* workspace, size_t workspace_bytes,
+                                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,12 @@
 //   scale rows -> oq RTN kernels (rtn.hip) -> awq_diff_kernel (D = W - dequant / s, absmax partials) -> split -> GEMM.
 // Round 2 ran the same composition through torch elementwise kernels and rocBLAS (23.4 ms per 4096^3 layer, bound by 20
 // fp32 GEMMs of 137 GFLOP).
+//
+// Element types: W is fp32, fp16 or bf16 (the _h16 entry points, oq_hip_half.h).  Every kernel that reads W is a template on the
+// element (half_elem.hpp); a 2-byte W is converted exactly at the load and nothing else changes -- every lane owns the elements it
+// owns for fp32 and every sum keeps its order, so all results are those of the fp32 kernels on the upcast matrix, byte for byte.
 #include "gemm_tn.hpp"
+#include "half_elem.hpp"
 #include "row_params.hpp"
 #include "rtn_internal.hpp"
 
@@ -16,6 +21,28 @@ namespace oq {
 
 constexpr int kAwqMaxGrid = 64;
 constexpr int kColChunks = 64;   // row chunks of the column reductions
+
+// fp16 and bf16 are ElemF16 / ElemBF16 of half_elem.hpp; fp32 has the same face
+struct AwqF32 {
+    typedef float raw;
+    static __device__ __forceinline__ float one(float b) { return b; }
+};
+// four neighbouring elements of a row: 16 bytes of fp32, 8 bytes of a 2-byte type (the pointer aligned to that)
+template <typename E>
+__device__ __forceinline__ float4 load4(const typename E::raw* p) {
+    if constexpr (sizeof(typename E::raw) == 4) {
+        return *reinterpret_cast<const float4*>(p);
+    } else {
+        const u32x2 v = *reinterpret_cast<const u32x2*>(p);
+        float4 r;
+        E::two(v[0], r.x, r.y);
+        E::two(v[1], r.z, r.w);
+        return r;
+    }
+}
+// the alignment of a base whose rows `load4` reads (with N % 4 == 0 and ldw % 4 == 0)
+template <typename E>
+static bool vec_base_ok(const void* W) { return aligned_to(W, 4 * sizeof(typename E::raw)); }
 
 // ---- column sums of |x| (awq.py:47-50) / column max of |x| (smooth_quant.py:62-69): partial[chunk][k]
 template <bool MAX>
@@ -60,7 +87,8 @@ __global__ __launch_bounds__(256) void col_abs_accumulate_kernel(const float* __
 
 // ---- awq.py:52-72: |w| / absmax of its quantization group, mean over the output channels -> ws[k].
 // gmax[kg][n] = absmax over rows [kg g, kg g + g) of column n (g = K: one row of maxima per column).
-__global__ __launch_bounds__(256) void group_absmax_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, int64_t g, float* __restrict__ gmax) {
+template <typename E>
+__global__ __launch_bounds__(256) void group_absmax_kernel(const typename E::raw* __restrict__ W, int64_t K, int64_t N, int64_t ldw, int64_t g, float* __restrict__ gmax) {
     const int64_t n = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (n >= N) return;
     const int64_t kg = blockIdx.y;
@@ -68,8 +96,8 @@ __global__ __launch_bounds__(256) void group_absmax_kernel(const float* __restri
     float m = 0.f;
     int64_t r = r0;
     for (; r + 3 < r1; r += 4)
-        m = nmax(nmax(m, fabsf(W[r * ldw + n])), nmax(fabsf(W[(r + 1) * ldw + n]), nmax(fabsf(W[(r + 2) * ldw + n]), fabsf(W[(r + 3) * ldw + n]))));
-    for (; r < r1; ++r) m = nmax(m, fabsf(W[r * ldw + n]));
+        m = nmax(nmax(m, fabsf(E::one(W[r * ldw + n]))), nmax(fabsf(E::one(W[(r + 1) * ldw + n])), nmax(fabsf(E::one(W[(r + 2) * ldw + n])), fabsf(E::one(W[(r + 3) * ldw + n])))));
+    for (; r < r1; ++r) m = nmax(m, fabsf(E::one(W[r * ldw + n])));
     gmax[kg * N + n] = m;
 }
 
@@ -91,14 +119,15 @@ __global__ __launch_bounds__(1024) void fold_to_scalar_kernel(float* v, int64_t 
     for (int64_t i = threadIdx.x; i < count; i += blockDim.x) v[i] = m;
 }
 
-__global__ __launch_bounds__(256) void weight_scale_rows_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, int64_t g,
+template <typename E>
+__global__ __launch_bounds__(256) void weight_scale_rows_kernel(const typename E::raw* __restrict__ W, int64_t K, int64_t N, int64_t ldw, int64_t g,
                                                                 const float* __restrict__ gmax, float* __restrict__ ws) {
     __shared__ float sm[4];
     const int64_t k = blockIdx.x;
-    const float* row = W + k * ldw;
+    const typename E::raw* row = W + k * ldw;
     const float* mx = gmax + (k / g) * N;
     float acc = 0.f;
-    for (int64_t n = threadIdx.x; n < N; n += 256) acc += fabsf(row[n]) / mx[n];
+    for (int64_t n = threadIdx.x; n < N; n += 256) acc += fabsf(E::one(row[n])) / mx[n];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
@@ -136,24 +165,28 @@ __global__ __launch_bounds__(1024) void grid_scales_kernel(const float* __restri
     for (int64_t k = threadIdx.x; k < K; k += blockDim.x) out[k] = out[k] / norm;
 }
 
-// ---- W * s[:, None] (awq.py:156) -> Ws, four columns per thread
-__global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, const float* __restrict__ s,
+// ---- W * s[:, None] (awq.py:156) -> Ws, four columns per thread (a 2-byte W: one 8-byte load where its base allows that)
+template <typename E>
+__global__ __launch_bounds__(256) void scale_rows_kernel(const typename E::raw* __restrict__ W, int64_t K, int64_t N, int64_t ldw, const float* __restrict__ s,
                                                          float* __restrict__ out) {
     const int64_t n4 = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
     const int64_t k = blockIdx.y;
     if (n4 >= N) return;
     const float sk = s[k];
-    if (n4 + 3 < N && (ldw & 3) == 0 && (N & 3) == 0) {
-        const float4 v = *reinterpret_cast<const float4*>(W + k * ldw + n4);
+    bool vec = n4 + 3 < N && (ldw & 3) == 0 && (N & 3) == 0;
+    if constexpr (sizeof(typename E::raw) == 2) vec = vec && (reinterpret_cast<uintptr_t>(W) & 7u) == 0;     // uniform
+    if (vec) {
+        const float4 v = load4<E>(W + k * ldw + n4);
         *reinterpret_cast<float4*>(out + k * N + n4) = make_float4(v.x * sk, v.y * sk, v.z * sk, v.w * sk);
     } else {
-        for (int64_t n = n4; n < N && n < n4 + 4; ++n) out[k * N + n] = W[k * ldw + n] * sk;
+        for (int64_t n = n4; n < N && n < n4 + 4; ++n) out[k * N + n] = E::one(W[k * ldw + n]) * sk;
     }
 }
 
 // ---- D = W - dequant(q) / s[:, None]  (awq.py:166-175; s == null: the clip search's D = W - dequant(q), awq.py:236-245),
 // with the block's max |D| for the fp16 pieces' power-of-two scale.  One thread = one column x 8 rows.
-__global__ __launch_bounds__(256) void awq_diff_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, const uint8_t* __restrict__ q,
+template <typename E>
+__global__ __launch_bounds__(256) void awq_diff_kernel(const typename E::raw* __restrict__ W, int64_t K, int64_t N, int64_t ldw, const uint8_t* __restrict__ q,
                                                        const float* __restrict__ qscale, const uint8_t* __restrict__ qzp, ParamIndex pi, int32_t is_signed,
                                                        const float* __restrict__ s, float* __restrict__ D, float* __restrict__ absmax_partial) {
     __shared__ float sm[4];
@@ -171,7 +204,7 @@ __global__ __launch_bounds__(256) void awq_diff_kernel(const float* __restrict__
             const int32_t zp = is_signed ? static_cast<int32_t>(static_cast<int8_t>(qzp[p])) : static_cast<int32_t>(qzp[p]);
             float w_hat = dequantize_one(qi, qscale[p], zp);          // utils.py:130-132
             if (s != nullptr) w_hat = w_hat / s[r];                    // awq.py:175
-            const float d = W[r * ldw + n] - w_hat;
+            const float d = E::one(W[r * ldw + n]) - w_hat;
             D[r * N + n] = d;
             m = nmax(m, fabsf(d));
         }
@@ -182,9 +215,10 @@ __global__ __launch_bounds__(256) void awq_diff_kernel(const float* __restrict__
     if (threadIdx.x == 0) absmax_partial[static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x] = nmax(nmax(sm[0], sm[1]), nmax(sm[2], sm[3]));
 }
 
-// The same for vector-aligned operands: four neighbouring columns per thread (16-byte loads of W, 4-byte loads of q, 16-byte
-// stores of D), parameters fetched once for the thread's 8 rows (8 divides every group size this path accepts).
-__global__ __launch_bounds__(256) void awq_diff4_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, const uint8_t* __restrict__ q,
+// The same for vector-aligned operands: four neighbouring columns per thread (16-byte loads of W -- 8-byte ones of a 2-byte W --,
+// 4-byte loads of q, 16-byte stores of D), parameters fetched once for the thread's 8 rows (8 divides every group size this path accepts).
+template <typename E>
+__global__ __launch_bounds__(256) void awq_diff4_kernel(const typename E::raw* __restrict__ W, int64_t K, int64_t N, int64_t ldw, const uint8_t* __restrict__ q,
                                                         const float* __restrict__ qscale, const uint8_t* __restrict__ qzp, ParamIndex pi, int32_t is_signed,
                                                         const float* __restrict__ s, float* __restrict__ D, float* __restrict__ absmax_partial) {
     __shared__ float sm[4];
@@ -205,7 +239,7 @@ __global__ __launch_bounds__(256) void awq_diff4_kernel(const float* __restrict_
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int64_t r = r0 + u < K ? r0 + u : K - 1;   // clamped, never predicated
-            w[u] = *reinterpret_cast<const float4*>(W + r * ldw + n);
+            w[u] = load4<E>(W + r * ldw + n);
             qb[u] = *reinterpret_cast<const uint32_t*>(q + r * N + n);
         }
 #pragma unroll
@@ -250,8 +284,8 @@ __global__ __launch_bounds__(256) void awq_diff4_kernel(const float* __restrict_
 // same products, same loss bits.
 typedef uint32_t u32x4a __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2a __attribute__((ext_vector_type(2)));
-template <bool PIECES>
-__global__ __launch_bounds__(512, 2) void awq_group_diff_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, int64_t g, QGrid grid, int wpg,
+template <typename E, bool PIECES>
+__global__ __launch_bounds__(512, 2) void awq_group_diff_kernel(const typename E::raw* __restrict__ W, int64_t K, int64_t N, int64_t ldw, int64_t g, QGrid grid, int wpg,
                                                                 const float* __restrict__ row_scale, float* __restrict__ D,
                                                                 float* __restrict__ absmax_partial, const float* __restrict__ piece_scale,
                                                                 float* __restrict__ piece_header, u32x4a* __restrict__ P, int64_t Np,
@@ -276,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void awq_group_diff_kernel(const float* __r
     uint32_t dead = 0;      // PIECES: bit r = row r's input channel is dead (mean |x| == 0); uniform, lives in a scalar register
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        w[r] = *reinterpret_cast<const float4*>(W + (row0 + r) * ldw + lcol);
+        w[r] = load4<E>(W + (row0 + r) * ldw + lcol);      // a 2-byte W: 16 words of 8 bytes, converted here
         sr[r] = row_scale != nullptr ? row_scale[row0 + r] : 1.0f;     // uniform: scalar loads
         if constexpr (PIECES) dead |= (act != nullptr && act[row0 + r] == 0.0f) ? (1u << r) : 0u;
     }
@@ -431,11 +465,12 @@ __global__ __launch_bounds__(256) void smooth_scale_kernel(const float* __restri
     out[k] = powf(nmax(act[k], 1e-5f), alpha) / powf(wmax[k] + 1e-9f, one_minus);
 }
 
-__global__ __launch_bounds__(256) void row_absmax_kernel(const float* __restrict__ W, int64_t K, int64_t N, int64_t ldw, float* __restrict__ out) {
+template <typename E>
+__global__ __launch_bounds__(256) void row_absmax_kernel(const typename E::raw* __restrict__ W, int64_t K, int64_t N, int64_t ldw, float* __restrict__ out) {
     __shared__ float sm[4];
     const int64_t k = blockIdx.x;
     float m = 0.f;
-    for (int64_t n = threadIdx.x; n < N; n += 256) m = nmax(m, fabsf(W[k * ldw + n]));
+    for (int64_t n = threadIdx.x; n < N; n += 256) m = nmax(m, fabsf(E::one(W[k * ldw + n])));
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -514,6 +549,8 @@ struct AwqWs {   // carving of the caller's workspace
     float* triples;     // [candidates][4] the pieces' scale triples made from them, once per search
     char* rtn_ws;
     size_t rtn_ws_bytes;
+    char* rtn_half_ws;  // the _h16 entry points only: the partial ranges of oq_rtn_quantize_h16 behind the fp32 layout (general clip route)
+    size_t rtn_half_ws_bytes;
     // Gram route (T >= kAwqGramRatio K): sum_n ||X d_n||^2 = <D, (X^T X) D>, the K x K Gram matrix made ONCE per search
     bool gram;
     float* G;           // [K, K] = (2 / T) X^T X (the GPTQ Hessian kernel, gptq.py:246-260 with n = T)
@@ -580,6 +617,7 @@ static size_t awq_workspace(int64_t T, int64_t K, int64_t N, AwqWs* w, char* bas
         w->colpart = reinterpret_cast<float*>(colpart); w->gemm_part = reinterpret_cast<float*>(gpart); w->diff_part = reinterpret_cast<float*>(dpart);
         w->rowmax = reinterpret_cast<float*>(rmax); w->bounds = reinterpret_cast<float*>(bnd); w->triples = reinterpret_cast<float*>(trp);
         w->rtn_ws = rtn; w->rtn_ws_bytes = rtn_bytes;
+        w->rtn_half_ws = nullptr; w->rtn_half_ws_bytes = 0;
         w->gram = gram; w->G = reinterpret_cast<float*>(G); w->pieces_g = pg; w->hess_ws = hws; w->hess_ws_bytes = hess_bytes;
     }
     return off + 256;
@@ -594,8 +632,9 @@ static int32_t param_index(int32_t strategy, int64_t K, int64_t g, ParamIndex* p
 
 // the fused route of candidate_loss: direct product (the Gram route reads D itself in its epilogue) and a contraction length
 // that fills its last stage (no zero chunks to write behind the rows); otherwise D goes through fp32 and a split launch
-static bool group_fused(int32_t strategy, int64_t g, int64_t K, int64_t N, int64_t ldw, const float* W) {      // the fused quantize-residual kernel takes the candidate
-    return N % 4 == 0 && ldw % 4 == 0 && (reinterpret_cast<uintptr_t>(W) & 15u) == 0 && strategy == OQ_GROUP && (g == 16 || g == 32 || g == 64 || g == 128) && K % g == 0;
+template <typename E>
+static bool group_fused(int32_t strategy, int64_t g, int64_t K, int64_t N, int64_t ldw, const void* W) {      // the fused quantize-residual kernel takes the candidate
+    return N % 4 == 0 && ldw % 4 == 0 && vec_base_ok<E>(W) && strategy == OQ_GROUP && (g == 16 || g == 32 || g == 64 || g == 128) && K % g == 0;
 }
 static bool pieces_route(const AwqWs& w, int64_t K) {
     return !w.gram && gemm_f16x3_chunks(K) * 8 == K;
@@ -603,9 +642,10 @@ static bool pieces_route(const AwqWs& w, int64_t K) {
 
 // once per search, fused route: row maxima of W, the bounds and the pieces' scales of all candidates (three launches)
 // (`act`: the scale search's mean |x| per channel, whose zeros are the dead channels; nullptr for the clip search)
-static int32_t prepare_piece_scales(const AwqWs& w, const float* W, int64_t K, int64_t N, int64_t ldw, int64_t g, const float* row_scales, const float* act,
+template <typename E>
+static int32_t prepare_piece_scales(const AwqWs& w, const typename E::raw* W, int64_t K, int64_t N, int64_t ldw, int64_t g, const float* row_scales, const float* act,
                                     int n_cand, hipStream_t s) {
-    hipLaunchKernelGGL(row_absmax_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, w.rowmax);
+    hipLaunchKernelGGL(row_absmax_kernel<E>, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, w.rowmax);
     const int nc = row_scales != nullptr ? n_cand : 1;
     hipLaunchKernelGGL(awq_bound_kernel, dim3(static_cast<uint32_t>(K / g), static_cast<uint32_t>(nc)), dim3(64), 0, s, w.rowmax, row_scales, act, K, g, w.bounds);
     hipLaunchKernelGGL(awq_piece_scales_kernel, dim3(static_cast<uint32_t>(nc)), dim3(256), 0, s, w.bounds, static_cast<int>(K / g), w.triples);
@@ -613,12 +653,14 @@ static int32_t prepare_piece_scales(const AwqWs& w, const float* W, int64_t K, i
 }
 
 // one candidate: quantize `Wq` (the weights as the candidate sees them), D = W - dequant (/ s), loss -> loss_out
-static int32_t candidate_loss(const AwqWs& w, const float* W, int64_t ldw, const float* row_scale, int64_t T, int64_t K,
+template <typename E>
+static int32_t candidate_loss(const AwqWs& w, const typename E::raw* W, int64_t ldw, const float* row_scale, int64_t T, int64_t K,
                               int64_t N, int32_t qtype, int32_t strategy, int64_t group_size, int64_t g, int32_t symmetric, int32_t reduce_range,
                               float clip_ratio, int candidate, hipStream_t s) {
     int32_t st;
     int nparts;
-    const bool vec = N % 4 == 0 && ldw % 4 == 0 && (reinterpret_cast<uintptr_t>(W) & 15u) == 0 && (strategy != OQ_GROUP || g % 8 == 0);
+    // four elements per load: 16 bytes of fp32, 8 bytes of a 2-byte W (rows that are only 2-byte aligned take the scalar kernels)
+    const bool vec = N % 4 == 0 && ldw % 4 == 0 && vec_base_ok<E>(W) && (strategy != OQ_GROUP || g % 8 == 0);
     if (vec && strategy == OQ_GROUP && (g == 16 || g == 32 || g == 64 || g == 128) && K % g == 0) {
         QGrid grid;
         st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &grid);
@@ -628,7 +670,7 @@ static int32_t candidate_loss(const AwqWs& w, const float* W, int64_t ldw, const
         if (pieces_route(w, K)) {
             // the first pieces of D straight from the quantize-residual kernel (see it); their scale from a bound of |D|
             // (prepare_piece_scales: all candidates ahead of the loop)
-            hipLaunchKernelGGL(awq_group_diff_kernel<true>, dgrid, dim3(512), 0, s, W, K, N, ldw, g, grid, wpg, row_scale, static_cast<float*>(nullptr),
+            hipLaunchKernelGGL((awq_group_diff_kernel<E, true>), dgrid, dim3(512), 0, s, W, K, N, ldw, g, grid, wpg, row_scale, static_cast<float*>(nullptr),
                                static_cast<float*>(nullptr), w.triples + 4 * (row_scale != nullptr ? candidate : 0), reinterpret_cast<float*>(w.pieces_d),
                                reinterpret_cast<u32x4a*>(w.pieces_d + gemm_f16x3_header_bytes()), gemm_f16x3_padded_cols(N),
                                row_scale != nullptr ? static_cast<const float*>(w.act) : nullptr);      // dead channels: see awq_bound_kernel
@@ -637,32 +679,34 @@ static int32_t candidate_loss(const AwqWs& w, const float* W, int64_t ldw, const
             float* part = w.gemm_part + static_cast<int64_t>(candidate) * loss_stride(T, K, N);
             return launch_gemm_f16x3(w.pieces_x, w.pieces_d, T, N, K, 1.0f, 0.0f, nullptr, 0, part, s);
         }
-        hipLaunchKernelGGL(awq_group_diff_kernel<false>, dgrid, dim3(512), 0, s, W, K, N, ldw, g, grid, wpg, row_scale, w.D, w.diff_part,
+        hipLaunchKernelGGL((awq_group_diff_kernel<E, false>), dgrid, dim3(512), 0, s, W, K, N, ldw, g, grid, wpg, row_scale, w.D, w.diff_part,
                            static_cast<const float*>(nullptr), static_cast<float*>(nullptr), static_cast<u32x4a*>(nullptr), static_cast<int64_t>(0),
                            static_cast<const float*>(nullptr));
         nparts = static_cast<int>(dgrid.x * dgrid.y);
     } else {
-        const float* Wq = W;
-        int64_t ldq = ldw;
-        if (row_scale != nullptr) {   // awq.py:156: the candidate's weights, materialised for the general RTN entry point
-            hipLaunchKernelGGL(scale_rows_kernel, dim3(static_cast<uint32_t>(ceil_div(ceil_div(N, 4), 256)), static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N,
+        if (row_scale != nullptr) {   // awq.py:156: the candidate's weights, materialised (as fp32) for the general RTN entry point
+            hipLaunchKernelGGL(scale_rows_kernel<E>, dim3(static_cast<uint32_t>(ceil_div(ceil_div(N, 4), 256)), static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N,
                                ldw, row_scale, w.Ws);
-            Wq = w.Ws;
-            ldq = N;
+            st = rtn_impl(RtnCall{w.Ws, K, N, N, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, 0, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN,
+                                  w.rtn_ws, w.rtn_ws_bytes, s});
+        } else if constexpr (sizeof(typename E::raw) == 4) {
+            st = rtn_impl(RtnCall{W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, 0, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN,
+                                  w.rtn_ws, w.rtn_ws_bytes, s});
+        } else {   // the clip search quantizes W itself: the half RTN (rtn_half.hip) gives the bytes of rtn_impl on the upcast matrix, no fp32 copy
+            st = oq_rtn_quantize_h16(W, std::is_same_v<E, ElemBF16> ? OQ_W_BF16 : OQ_W_F16, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range,
+                                     clip_ratio, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN, w.rtn_half_ws, w.rtn_half_ws_bytes, s);
         }
-        st = rtn_impl(RtnCall{Wq, K, N, ldq, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, 0, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN,
-                              w.rtn_ws, w.rtn_ws_bytes, s});
         if (st != OQ_OK) return st;
         ParamIndex pi;
         param_index(strategy, K, g, &pi);
         const int32_t is_signed = (qtype == OQ_INT4 || qtype == OQ_INT8) ? 1 : 0;
         if (vec) {
             const dim3 dgrid(static_cast<uint32_t>(ceil_div(N, 1024)), static_cast<uint32_t>(ceil_div(K, 8)));
-            hipLaunchKernelGGL(awq_diff4_kernel, dgrid, dim3(256), 0, s, W, K, N, ldw, w.q, w.qscale, w.qzp, pi, is_signed, row_scale, w.D, w.diff_part);
+            hipLaunchKernelGGL(awq_diff4_kernel<E>, dgrid, dim3(256), 0, s, W, K, N, ldw, w.q, w.qscale, w.qzp, pi, is_signed, row_scale, w.D, w.diff_part);
             nparts = static_cast<int>(dgrid.x * dgrid.y);
         } else {
             const dim3 dgrid(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(ceil_div(K, 8)));
-            hipLaunchKernelGGL(awq_diff_kernel, dgrid, dim3(256), 0, s, W, K, N, ldw, w.q, w.qscale, w.qzp, pi, is_signed, row_scale, w.D, w.diff_part);
+            hipLaunchKernelGGL(awq_diff_kernel<E>, dgrid, dim3(256), 0, s, W, K, N, ldw, w.q, w.qscale, w.qzp, pi, is_signed, row_scale, w.D, w.diff_part);
             nparts = static_cast<int>(dgrid.x * dgrid.y);
         }
     }
@@ -696,7 +740,7 @@ static int32_t prepare_activations(const AwqWs& w, const float* X, int64_t T, in
     return make_f16x2_pieces(w.G, K, K, K, false, w.pieces_g, s);
 }
 
-static int32_t check_common(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
+static int32_t check_common(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
                             int64_t group_size, int64_t* g) {
     OQ_REQUIRE(X && W && matrix_ok(T, K, ldx) && matrix_ok(K, N, ldw), OQ_ERR_INVALID_ARGUMENT, "awq: bad argument");
     OQ_REQUIRE(qtype == OQ_INT4 || qtype == OQ_UINT4 || qtype == OQ_INT8 || qtype == OQ_UINT8, OQ_ERR_UNSUPPORTED, "awq: 4- and 8-bit types only");
@@ -713,51 +757,61 @@ static int32_t check_common(const float* X, int64_t T, int64_t K, int64_t ldx, c
     return OQ_OK;
 }
 
-}  // namespace oq
+// ---- the element type of W on the host.  A 2-byte W adds one buffer behind the fp32 layout of the workspace: the partial ranges of
+// oq_rtn_quantize_h16 on the general clip route, 2 floats x N per 64-row chunk of a group.  (K / g) ceil(g / 64) chunks, which is
+// <= ceil(K / 64) + K / 257 for the groups of more than 256 rows (and channel / tensor) that use them.  The largest grid of that call,
+// ceil(N / 256) (K / 16 + K / g) blocks, stays below 2^31 for every shape the checks above let through (K N <= 2^40, g >= 4).
+template <typename E> constexpr bool kHalfW = sizeof(typename E::raw) == 2;
+template <typename E> constexpr int32_t kWtype = std::is_same_v<E, ElemBF16> ? OQ_W_BF16 : OQ_W_F16;
+static size_t half_rtn_bytes(int64_t K, int64_t N) { return align256(static_cast<size_t>(8) * N * (ceil_div(K, 64) + K / 257 + 1)) + 256; }
 
-extern "C" {
-
-using namespace oq;
-
-size_t oq_awq_workspace_bytes(int64_t T, int64_t K, int64_t N) {
-    if (!oq::matrix_ok(T, K, K) || !oq::matrix_ok(K, N, N) || K > 65535) return 0;
-    return awq_workspace(T, K, N, nullptr, nullptr);
+template <typename E>
+static void carve(int64_t T, int64_t K, int64_t N, AwqWs* w, void* workspace) {
+    const size_t fp32_bytes = awq_workspace(T, K, N, w, static_cast<char*>(workspace));
+    if constexpr (kHalfW<E>) {
+        w->rtn_half_ws = static_cast<char*>(workspace) + fp32_bytes;     // a multiple of 256 behind a 256-byte aligned base
+        w->rtn_half_ws_bytes = half_rtn_bytes(K, N);
+    }
 }
 
-int32_t oq_awq_scale_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype,
+// oq_awq_scale_search_f32 / _h16: one implementation, `fn` is the entry point's name in the messages.  Every check stands in front of
+// the first launch: a refused call touches no output.
+template <typename E>
+static int32_t awq_scale_search(const char* fn, const float* X, int64_t T, int64_t K, int64_t ldx, const void* Wv, int64_t N, int64_t ldw, int32_t qtype,
                                 int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
                                 float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const typename E::raw* W = static_cast<const typename E::raw*>(Wv);
     int64_t g;
     int32_t st = check_common(X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, &g);
     if (st != OQ_OK) return st;
-    OQ_REQUIRE(scales_out && losses_out && best_out && n_grid >= 1 && n_grid <= kAwqMaxGrid, OQ_ERR_INVALID_ARGUMENT, "oq_awq_scale_search_f32: bad argument");
-    const size_t need = oq_awq_workspace_bytes(T, K, N);
-    OQ_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
-               "oq_awq_scale_search_f32: 256-byte aligned workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+    OQ_REQUIRE(scales_out && losses_out && best_out && n_grid >= 1 && n_grid <= kAwqMaxGrid, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
+    const size_t need = kHalfW<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
+    OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
+               "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
     hipStream_t s = as_stream(stream);
     AwqWs w;
-    awq_workspace(T, K, N, &w, static_cast<char*>(workspace));
+    carve<E>(T, K, N, &w, workspace);
     // awq.py:47-50: mean |x| per input channel
     const dim3 cgrid(static_cast<uint32_t>(ceil_div(K, 256)), static_cast<uint32_t>(T < kColChunks ? T : kColChunks));
     hipLaunchKernelGGL(col_abs_partial_kernel<false>, cgrid, dim3(256), 0, s, X, T, K, ldx, w.colpart);
     hipLaunchKernelGGL(col_abs_finish_kernel<false>, dim3(cgrid.x), dim3(256), 0, s, w.colpart, static_cast<int>(cgrid.y), K, 1.0f / static_cast<float>(T), w.act);
     // awq.py:52-72: weight scale
     const int64_t kgroups = K / g;
-    hipLaunchKernelGGL(group_absmax_kernel, dim3(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax);
+    hipLaunchKernelGGL(group_absmax_kernel<E>, dim3(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax);
     if (strategy == OQ_TENSOR) hipLaunchKernelGGL(fold_to_scalar_kernel, dim3(1), dim3(1024), 0, s, w.gmax, N);
-    hipLaunchKernelGGL(weight_scale_rows_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax, w.wsc);
+    hipLaunchKernelGGL(weight_scale_rows_kernel<E>, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax, w.wsc);
     hipLaunchKernelGGL(grid_scales_kernel, dim3(static_cast<uint32_t>(n_grid)), dim3(1024), 0, s, w.act, w.wsc, K, n_grid, scales_out);
     st = check_launch("awq statistics");
     if (st != OQ_OK) return st;
     st = prepare_activations(w, X, T, K, ldx, stream, s);
     if (st != OQ_OK) return st;
-    if (pieces_route(w, K) && group_fused(strategy, g, K, N, ldw, W)) {
-        st = prepare_piece_scales(w, W, K, N, ldw, g, scales_out, w.act, n_grid, s);
+    if (pieces_route(w, K) && group_fused<E>(strategy, g, K, N, ldw, W)) {
+        st = prepare_piece_scales<E>(w, W, K, N, ldw, g, scales_out, w.act, n_grid, s);
         if (st != OQ_OK) return st;
     }
     for (int i = 0; i < n_grid; ++i) {
         const float* si = scales_out + static_cast<int64_t>(i) * K;
-        st = candidate_loss(w, W, ldw, si, T, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, 1.0f, i, s);
+        st = candidate_loss<E>(w, W, ldw, si, T, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, 1.0f, i, s);
         if (st != OQ_OK) return st;
     }
     st = finish_losses(w.gemm_part, n_grid, T, K, N, losses_out, s);
@@ -766,28 +820,30 @@ int32_t oq_awq_scale_search_f32(const float* X, int64_t T, int64_t K, int64_t ld
     return check_launch("argmin_first_kernel");
 }
 
-int32_t oq_awq_clip_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype,
+template <typename E>
+static int32_t awq_clip_search(const char* fn, const float* X, int64_t T, int64_t K, int64_t ldx, const void* Wv, int64_t N, int64_t ldw, int32_t qtype,
                                int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
                                void* workspace, size_t workspace_bytes, void* stream) {
+    const typename E::raw* W = static_cast<const typename E::raw*>(Wv);
     int64_t g;
     int32_t st = check_common(X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, &g);
     if (st != OQ_OK) return st;
-    OQ_REQUIRE(losses_out && best_out, OQ_ERR_INVALID_ARGUMENT, "oq_awq_clip_search_f32: bad argument");
-    const size_t need = oq_awq_workspace_bytes(T, K, N);
-    OQ_REQUIRE(workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
-               "oq_awq_clip_search_f32: 256-byte aligned workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+    OQ_REQUIRE(losses_out && best_out, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
+    const size_t need = kHalfW<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
+    OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
+               "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
     hipStream_t s = as_stream(stream);
     AwqWs w;
-    awq_workspace(T, K, N, &w, static_cast<char*>(workspace));
+    carve<E>(T, K, N, &w, workspace);
     st = prepare_activations(w, X, T, K, ldx, stream, s);
     if (st != OQ_OK) return st;
-    if (pieces_route(w, K) && group_fused(strategy, g, K, N, ldw, W)) {
-        st = prepare_piece_scales(w, W, K, N, ldw, g, nullptr, nullptr, 10, s);
+    if (pieces_route(w, K) && group_fused<E>(strategy, g, K, N, ldw, W)) {
+        st = prepare_piece_scales<E>(w, W, K, N, ldw, g, nullptr, nullptr, 10, s);
         if (st != OQ_OK) return st;
     }
     for (int i = 0; i < 10; ++i) {
         const float ratio = static_cast<float>(1.0 - static_cast<double>(i) / 100.0);   // awq.py:227
-        st = candidate_loss(w, W, ldw, nullptr, T, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, ratio, i, s);
+        st = candidate_loss<E>(w, W, ldw, nullptr, T, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, ratio, i, s);
         if (st != OQ_OK) return st;
     }
     st = finish_losses(w.gemm_part, 10, T, K, N, losses_out, s);
@@ -801,13 +857,9 @@ int32_t oq_awq_clip_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx
 // take anyway) and the candidate scales need mean |x| per input channel only.  Both are running sums over batches.
 static int64_t stats_rows(int64_t K) { return kAwqGramRatio * K; }   // a row count that selects the Gram layout of the workspace
 
-size_t oq_awq_stats_workspace_bytes(int64_t K, int64_t N) {
-    if (!oq::matrix_ok(K, N, N) || K > 65535 || !oq::extent_ok(stats_rows(K))) return 0;
-    return awq_workspace(stats_rows(K), K, N, nullptr, nullptr);
-}
-
 // act_sum[k] = sum over all T calibration rows of |x[t, k]|; G [K, K] = (2 / T) X^T X (oq_hessian_accumulate_f32 with n counting rows)
-static int32_t stats_begin(const float* act_sum, const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype,
+template <typename E>
+static int32_t stats_begin(const float* act_sum, const float* G, int64_t T, int64_t K, const void* W, int64_t N, int64_t ldw, int32_t qtype,
                            int32_t strategy, int64_t group_size, int64_t* g, void* workspace, size_t workspace_bytes, AwqWs* w, hipStream_t s,
                            const char* who) {
     OQ_REQUIRE(G && W && T > 0 && count_ok(T, kMaxSamples) && matrix_ok(K, K, K) && matrix_ok(K, N, ldw), OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
@@ -822,10 +874,10 @@ static int32_t stats_begin(const float* act_sum, const float* G, int64_t T, int6
         *g = gs;
     }
     OQ_REQUIRE(ceil_div(K, 8) <= 65535 && K <= 65535 && ceil_div(K, *g) <= 65535, OQ_ERR_UNSUPPORTED, "awq: K too large");
-    const size_t need = oq_awq_stats_workspace_bytes(K, N);
+    const size_t need = kHalfW<E> ? oq_awq_stats_half_workspace_bytes(K, N) : oq_awq_stats_workspace_bytes(K, N);
     OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
                "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-    awq_workspace(stats_rows(K), K, N, w, static_cast<char*>(workspace));
+    carve<E>(stats_rows(K), K, N, w, workspace);
     OQ_REQUIRE(w->gram, OQ_ERR_LAUNCH, "%s: the Gram layout was not selected", who);
     OQ_REQUIRE(hipMemcpyAsync(w->G, G, static_cast<size_t>(K) * K * 4, hipMemcpyDeviceToDevice, s) == hipSuccess, OQ_ERR_LAUNCH, "%s: copy of G failed", who);
     if (act_sum != nullptr)   // awq.py:47-50: mean |x| per input channel
@@ -834,25 +886,26 @@ static int32_t stats_begin(const float* act_sum, const float* G, int64_t T, int6
     return make_f16x2_pieces(w->G, K, K, K, false, w->pieces_g, s);
 }
 
-int32_t oq_awq_scale_search_stats_f32(const float* act_sum, const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype,
-                                      int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
-                                      float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
-    OQ_REQUIRE(act_sum && scales_out && losses_out && best_out && n_grid >= 1 && n_grid <= kAwqMaxGrid, OQ_ERR_INVALID_ARGUMENT,
-               "oq_awq_scale_search_stats_f32: bad argument");
+template <typename E>
+static int32_t awq_scale_search_stats(const char* fn, const float* act_sum, const float* G, int64_t T, int64_t K, const void* Wv, int64_t N, int64_t ldw,
+                                      int32_t qtype, int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid,
+                                      float* scales_out, float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const typename E::raw* W = static_cast<const typename E::raw*>(Wv);
+    OQ_REQUIRE(act_sum && scales_out && losses_out && best_out && n_grid >= 1 && n_grid <= kAwqMaxGrid, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
     hipStream_t s = as_stream(stream);
     AwqWs w;
     int64_t g;
-    int32_t st = stats_begin(act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, &g, workspace, workspace_bytes, &w, s, "oq_awq_scale_search_stats_f32");
+    int32_t st = stats_begin<E>(act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, &g, workspace, workspace_bytes, &w, s, fn);
     if (st != OQ_OK) return st;
     const int64_t Tg = stats_rows(K), kgroups = K / g;
-    hipLaunchKernelGGL(group_absmax_kernel, dim3(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax);
+    hipLaunchKernelGGL(group_absmax_kernel<E>, dim3(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax);
     if (strategy == OQ_TENSOR) hipLaunchKernelGGL(fold_to_scalar_kernel, dim3(1), dim3(1024), 0, s, w.gmax, N);
-    hipLaunchKernelGGL(weight_scale_rows_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax, w.wsc);
+    hipLaunchKernelGGL(weight_scale_rows_kernel<E>, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, g, w.gmax, w.wsc);
     hipLaunchKernelGGL(grid_scales_kernel, dim3(static_cast<uint32_t>(n_grid)), dim3(1024), 0, s, w.act, w.wsc, K, n_grid, scales_out);
     st = check_launch("awq statistics");
     if (st != OQ_OK) return st;
     for (int i = 0; i < n_grid; ++i) {
-        st = candidate_loss(w, W, ldw, scales_out + static_cast<int64_t>(i) * K, Tg, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, 1.0f, i, s);
+        st = candidate_loss<E>(w, W, ldw, scales_out + static_cast<int64_t>(i) * K, Tg, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, 1.0f, i, s);
         if (st != OQ_OK) return st;
     }
     st = finish_losses(w.gemm_part, n_grid, Tg, K, N, losses_out, s);
@@ -861,25 +914,162 @@ int32_t oq_awq_scale_search_stats_f32(const float* act_sum, const float* G, int6
     return check_launch("argmin_first_kernel");
 }
 
-int32_t oq_awq_clip_search_stats_f32(const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
-                                     int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-    OQ_REQUIRE(losses_out && best_out, OQ_ERR_INVALID_ARGUMENT, "oq_awq_clip_search_stats_f32: bad argument");
+template <typename E>
+static int32_t awq_clip_search_stats(const char* fn, const float* G, int64_t T, int64_t K, const void* Wv, int64_t N, int64_t ldw, int32_t qtype,
+                                     int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    const typename E::raw* W = static_cast<const typename E::raw*>(Wv);
+    OQ_REQUIRE(losses_out && best_out, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
     hipStream_t s = as_stream(stream);
     AwqWs w;
     int64_t g;
-    int32_t st = stats_begin(nullptr, G, T, K, W, N, ldw, qtype, strategy, group_size, &g, workspace, workspace_bytes, &w, s, "oq_awq_clip_search_stats_f32");
+    int32_t st = stats_begin<E>(nullptr, G, T, K, W, N, ldw, qtype, strategy, group_size, &g, workspace, workspace_bytes, &w, s, fn);
     if (st != OQ_OK) return st;
     const int64_t Tg = stats_rows(K);
     for (int i = 0; i < 10; ++i) {
         const float ratio = static_cast<float>(1.0 - static_cast<double>(i) / 100.0);   // awq.py:227
-        st = candidate_loss(w, W, ldw, nullptr, Tg, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, ratio, i, s);
+        st = candidate_loss<E>(w, W, ldw, nullptr, Tg, K, N, qtype, strategy, group_size, g, symmetric, reduce_range, ratio, i, s);
         if (st != OQ_OK) return st;
     }
     st = finish_losses(w.gemm_part, 10, Tg, K, N, losses_out, s);
     if (st != OQ_OK) return st;
     hipLaunchKernelGGL(argmin_first_kernel, dim3(1), dim3(64), 0, s, losses_out, 10, best_out);
     return check_launch("argmin_first_kernel");
+}
+
+template <typename E>
+static int32_t smooth_quant_scale(const char* fn, const float* X, int64_t T, int64_t K, int64_t ldx, const void* Wv, int64_t N, int64_t ldw, float alpha,
+                                  float* scale_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const typename E::raw* W = static_cast<const typename E::raw*>(Wv);
+    OQ_REQUIRE(X && W && scale_out && matrix_ok(T, K, ldx) && matrix_ok(K, N, ldw), OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
+    const size_t need = align256(static_cast<size_t>(kColChunks) * K * 4) + 2 * align256(static_cast<size_t>(K) * 4) + 256;
+    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
+    hipStream_t s = as_stream(stream);
+    char* base = static_cast<char*>(workspace);
+    base += (256 - reinterpret_cast<uintptr_t>(base) % 256) % 256;
+    float* colpart = reinterpret_cast<float*>(base);
+    float* act = reinterpret_cast<float*>(base + align256(static_cast<size_t>(kColChunks) * K * 4));
+    float* wmax = act + align256(static_cast<size_t>(K) * 4) / 4;
+    const dim3 cgrid(static_cast<uint32_t>(ceil_div(K, 256)), static_cast<uint32_t>(T < kColChunks ? T : kColChunks));
+    hipLaunchKernelGGL(col_abs_partial_kernel<true>, cgrid, dim3(256), 0, s, X, T, K, ldx, colpart);                 // smooth_quant.py:62-69
+    hipLaunchKernelGGL(col_abs_finish_kernel<true>, dim3(cgrid.x), dim3(256), 0, s, colpart, static_cast<int>(cgrid.y), K, 1.0f, act);
+    hipLaunchKernelGGL(row_absmax_kernel<E>, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, wmax);      // :71-74
+    hipLaunchKernelGGL(smooth_scale_kernel, dim3(static_cast<uint32_t>(ceil_div(K, 256))), dim3(256), 0, s, act, wmax, K, alpha,
+                       static_cast<float>(1.0 - static_cast<double>(alpha)), scale_out);
+    return check_launch("smooth_scale_kernel");
+}
+
+// what every _h16 entry point checks of its W in front of everything its fp32 twin checks
+static int32_t half_weight_ok(const char* fn, const void* W, int32_t wtype) {
+    OQ_REQUIRE(half_type_ok(wtype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
+    OQ_REQUIRE(aligned_to(W, 2), OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned", fn);
+    return OQ_OK;
+}
+
+}  // namespace oq
+
+extern "C" {
+
+using namespace oq;
+
+size_t oq_awq_workspace_bytes(int64_t T, int64_t K, int64_t N) {
+    if (!oq::matrix_ok(T, K, K) || !oq::matrix_ok(K, N, N) || K > 65535) return 0;
+    return awq_workspace(T, K, N, nullptr, nullptr);
+}
+
+size_t oq_awq_half_workspace_bytes(int64_t T, int64_t K, int64_t N) {
+    const size_t fp32_bytes = oq_awq_workspace_bytes(T, K, N);
+    return fp32_bytes == 0 ? 0 : fp32_bytes + oq::half_rtn_bytes(K, N);
+}
+
+int32_t oq_awq_scale_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype,
+                                int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
+                                float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return awq_scale_search<AwqF32>("oq_awq_scale_search_f32", X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid,
+                                    scales_out, losses_out, best_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_awq_scale_search_h16(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int32_t wtype, int64_t N, int64_t ldw, int32_t qtype,
+                                int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
+                                float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char fn[] = "oq_awq_scale_search_h16";
+    const int32_t st = half_weight_ok(fn, W, wtype);
+    if (st != OQ_OK) return st;
+    if (wtype == OQ_W_F16)
+        return awq_scale_search<ElemF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out, losses_out,
+                                         best_out, workspace, workspace_bytes, stream);
+    return awq_scale_search<ElemBF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out, losses_out,
+                                      best_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_awq_clip_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype,
+                               int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    return awq_clip_search<AwqF32>("oq_awq_clip_search_f32", X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out,
+                                   best_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_awq_clip_search_h16(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int32_t wtype, int64_t N, int64_t ldw, int32_t qtype,
+                               int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    static const char fn[] = "oq_awq_clip_search_h16";
+    const int32_t st = half_weight_ok(fn, W, wtype);
+    if (st != OQ_OK) return st;
+    if (wtype == OQ_W_F16)
+        return awq_clip_search<ElemF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
+                                        workspace_bytes, stream);
+    return awq_clip_search<ElemBF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
+                                     workspace_bytes, stream);
+}
+
+size_t oq_awq_stats_workspace_bytes(int64_t K, int64_t N) {
+    if (!oq::matrix_ok(K, N, N) || K > 65535 || !oq::extent_ok(stats_rows(K))) return 0;
+    return awq_workspace(stats_rows(K), K, N, nullptr, nullptr);
+}
+
+size_t oq_awq_stats_half_workspace_bytes(int64_t K, int64_t N) {
+    const size_t fp32_bytes = oq_awq_stats_workspace_bytes(K, N);
+    return fp32_bytes == 0 ? 0 : fp32_bytes + oq::half_rtn_bytes(K, N);
+}
+
+int32_t oq_awq_scale_search_stats_f32(const float* act_sum, const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype,
+                                      int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
+                                      float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return awq_scale_search_stats<AwqF32>("oq_awq_scale_search_stats_f32", act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range,
+                                          n_grid, scales_out, losses_out, best_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_awq_scale_search_stats_h16(const float* act_sum, const float* G, int64_t T, int64_t K, const void* W, int32_t wtype, int64_t N, int64_t ldw,
+                                      int32_t qtype, int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid,
+                                      float* scales_out, float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char fn[] = "oq_awq_scale_search_stats_h16";
+    const int32_t st = half_weight_ok(fn, W, wtype);
+    if (st != OQ_OK) return st;
+    if (wtype == OQ_W_F16)
+        return awq_scale_search_stats<ElemF16>(fn, act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out,
+                                               losses_out, best_out, workspace, workspace_bytes, stream);
+    return awq_scale_search_stats<ElemBF16>(fn, act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out,
+                                            losses_out, best_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_awq_clip_search_stats_f32(const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
+                                     int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return awq_clip_search_stats<AwqF32>("oq_awq_clip_search_stats_f32", G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out,
+                                         best_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_awq_clip_search_stats_h16(const float* G, int64_t T, int64_t K, const void* W, int32_t wtype, int64_t N, int64_t ldw, int32_t qtype,
+                                     int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    static const char fn[] = "oq_awq_clip_search_stats_h16";
+    const int32_t st = half_weight_ok(fn, W, wtype);
+    if (st != OQ_OK) return st;
+    if (wtype == OQ_W_F16)
+        return awq_clip_search_stats<ElemF16>(fn, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
+                                              workspace_bytes, stream);
+    return awq_clip_search_stats<ElemBF16>(fn, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
+                                           workspace_bytes, stream);
 }
 
 // sum over the T rows of |x[t, k]| added to `sum_inout` [K] (a running statistic over calibration batches; awq.py:47-50 divides by T)
@@ -905,23 +1095,16 @@ int32_t oq_abs_sum_cols_f32(const float* X, int64_t T, int64_t K, int64_t ldx, f
 
 int32_t oq_smooth_quant_scale_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, float alpha, float* scale_out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-    OQ_REQUIRE(X && W && scale_out && matrix_ok(T, K, ldx) && matrix_ok(K, N, ldw), OQ_ERR_INVALID_ARGUMENT,
-               "oq_smooth_quant_scale_f32: bad argument");
-    const size_t need = align256(static_cast<size_t>(kColChunks) * K * 4) + 2 * align256(static_cast<size_t>(K) * 4) + 256;
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_smooth_quant_scale_f32: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    hipStream_t s = as_stream(stream);
-    char* base = static_cast<char*>(workspace);
-    base += (256 - reinterpret_cast<uintptr_t>(base) % 256) % 256;
-    float* colpart = reinterpret_cast<float*>(base);
-    float* act = reinterpret_cast<float*>(base + align256(static_cast<size_t>(kColChunks) * K * 4));
-    float* wmax = act + align256(static_cast<size_t>(K) * 4) / 4;
-    const dim3 cgrid(static_cast<uint32_t>(ceil_div(K, 256)), static_cast<uint32_t>(T < kColChunks ? T : kColChunks));
-    hipLaunchKernelGGL(col_abs_partial_kernel<true>, cgrid, dim3(256), 0, s, X, T, K, ldx, colpart);                 // smooth_quant.py:62-69
-    hipLaunchKernelGGL(col_abs_finish_kernel<true>, dim3(cgrid.x), dim3(256), 0, s, colpart, static_cast<int>(cgrid.y), K, 1.0f, act);
-    hipLaunchKernelGGL(row_absmax_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, ldw, wmax);      // :71-74
-    hipLaunchKernelGGL(smooth_scale_kernel, dim3(static_cast<uint32_t>(ceil_div(K, 256))), dim3(256), 0, s, act, wmax, K, alpha,
-                       static_cast<float>(1.0 - static_cast<double>(alpha)), scale_out);
-    return check_launch("smooth_scale_kernel");
+    return smooth_quant_scale<AwqF32>("oq_smooth_quant_scale_f32", X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
+}
+
+int32_t oq_smooth_quant_scale_h16(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int32_t wtype, int64_t N, int64_t ldw, float alpha,
+                                  float* scale_out, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char fn[] = "oq_smooth_quant_scale_h16";
+    const int32_t st = half_weight_ok(fn, W, wtype);
+    if (st != OQ_OK) return st;
+    if (wtype == OQ_W_F16) return smooth_quant_scale<ElemF16>(fn, X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
+    return smooth_quant_scale<ElemBF16>(fn, X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
 }
 
 size_t oq_smooth_quant_workspace_bytes(int64_t K) {

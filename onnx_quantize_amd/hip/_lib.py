@@ -142,6 +142,14 @@ HALF_PROTOTYPES = {
     "oq_absmax_h16": (_i32, [_p, _i32, _i64, _i64, _i64, _i32, _p, _p, _sz, _p]),
     "oq_abs_stats_many_half_workspace_bytes": (_sz, [_p, _i64]),
     "oq_abs_stats_cols_many_h16": (_i32, [_p, _p, _i64, _i32, _p, _sz, _p]),
+    "oq_awq_half_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "oq_awq_stats_half_workspace_bytes": (_sz, [_i64, _i64]),
+    "oq_awq_scale_search_h16": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
+    "oq_awq_clip_search_h16": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "oq_awq_scale_search_stats_h16": (_i32, [_p, _p, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _sz,
+                                             _p]),
+    "oq_awq_clip_search_stats_h16": (_i32, [_p, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i32, _i64, _i32, _i32, _p, _p, _p, _sz, _p]),
+    "oq_smooth_quant_scale_h16": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i64, _i64, _f32, _p, _p, _sz, _p]),
 }
 
 _lock = threading.Lock()

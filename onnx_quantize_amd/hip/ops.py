@@ -894,9 +894,26 @@ def _flat_inputs(x: torch.Tensor) -> torch.Tensor:
     return x.reshape(-1, x.shape[-1])
 
 
+def _search_weight(w):
+    """The weight of a search as the library takes it: fp32 for the `_f32` entry points, fp16 / bf16 AS IT IS for their `_h16`
+    twins (csrc/awq.hip reads 2-byte elements and converts at the load).  No cast is made; any other dtype is refused by name."""
+    if isinstance(w, torch.Tensor) and w.dtype in _HALF_WTYPE:
+        _require_device(w, "w")
+    else:
+        _require_device(w, "w", torch.float32)
+    return w
+
+
+def _w_args(w2: torch.Tensor) -> tuple:
+    """The ``W[, wtype]`` arguments of a search entry point and the suffix of its name."""
+    if w2.dtype in _HALF_WTYPE:
+        return (_ptr(w2), _HALF_WTYPE[w2.dtype]), "h16"
+    return (_ptr(w2),), "f32"
+
+
 def _search_args(x, w, qtype, strategy, group_size):
     x2, ldx = _row_major(_flat_inputs(x))
-    _require_device(w, "w", torch.float32)
+    w = _search_weight(w)
     if w.dim() != 2 or w.shape[0] != x2.shape[1]:
         raise ValueError(f"weights must be [K, N] with K = {x2.shape[1]}, got {tuple(w.shape)}")
     w2, ldw = _row_major(w)
@@ -911,6 +928,8 @@ def awq_scale_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str
     """pre_passes/awq.py:114-184 on the device, one C call (oq_awq_scale_search_f32): activation / weight statistics, the
     n_grid candidate scales, and per candidate RTN -> dequantize -> X (W - W^) on the matrix cores with the squared error
     reduced in the GEMM's epilogue.  Nothing leaves the GPU until the losses and the winning scale are read.
+    ``x`` is fp32.  An fp16 / bf16 ``w`` is read as it is (oq_awq_scale_search_h16, no fp32 copy): every candidate scale, loss and
+    the winner are those of the fp32 call on ``w.float()``, byte for byte.
     Returns (best_scale [K] on device, losses float64[n_grid] on host)."""
     x2, ldx, w2, ldw, gs = _search_args(x, w, qtype, strategy, group_size)
     t, k = x2.shape
@@ -920,18 +939,20 @@ def awq_scale_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str
     scales = torch.empty((n_grid, k), dtype=torch.float32, device=dev)
     losses = torch.empty(n_grid, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.oq_awq_workspace_bytes(t, k, n) + 256, dev)
+    wargs, kind = _w_args(w2)
+    ws = _workspace((lib.oq_awq_half_workspace_bytes if kind == "h16" else lib.oq_awq_workspace_bytes)(t, k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
-    L.check(lib.oq_awq_scale_search_f32(_ptr(x2), t, k, ldx, _ptr(w2), n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
-                                        int(symmetric), int(reduce_range), int(n_grid), _ptr(scales), _ptr(losses), _ptr(best),
-                                        C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
+    L.check(getattr(lib, "oq_awq_scale_search_" + kind)(_ptr(x2), t, k, ldx, *wargs, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
+                                                        int(symmetric), int(reduce_range), int(n_grid), _ptr(scales), _ptr(losses), _ptr(best),
+                                                        C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
     lv = losses.double().cpu().numpy()
     return scales[int(best.item())], lv
 
 
 def awq_clip_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
                     reduce_range=False):
-    """pre_passes/awq.py:207-259 (oq_awq_clip_search_f32): (best clip_ratio, losses[10])."""
+    """pre_passes/awq.py:207-259 (oq_awq_clip_search_f32): (best clip_ratio, losses[10]).  ``x`` is fp32; an fp16 / bf16 ``w`` is
+    read as it is (oq_awq_clip_search_h16, no fp32 copy) and gives the losses and the ratio of ``w.float()``, byte for byte."""
     x2, ldx, w2, ldw, gs = _search_args(x, w, qtype, strategy, group_size)
     t, k = x2.shape
     n = w2.shape[1]
@@ -939,11 +960,12 @@ def awq_clip_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str,
     dev = w2.device
     losses = torch.empty(10, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.oq_awq_workspace_bytes(t, k, n) + 256, dev)
+    wargs, kind = _w_args(w2)
+    ws = _workspace((lib.oq_awq_half_workspace_bytes if kind == "h16" else lib.oq_awq_workspace_bytes)(t, k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
-    L.check(lib.oq_awq_clip_search_f32(_ptr(x2), t, k, ldx, _ptr(w2), n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
-                                       int(symmetric), int(reduce_range), _ptr(losses), _ptr(best), C.c_void_p(ws.data_ptr() + off),
-                                       ws.numel() - off, _stream()))
+    L.check(getattr(lib, "oq_awq_clip_search_" + kind)(_ptr(x2), t, k, ldx, *wargs, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
+                                                       int(symmetric), int(reduce_range), _ptr(losses), _ptr(best),
+                                                       C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
     return 1 - int(best.item()) / 100, losses.double().cpu().numpy()
 
 
@@ -1021,17 +1043,8 @@ class SearchStatistics:
         self.gram /= s.reshape(1, -1)
 
 
-def _search_weight(w):
-    """The searches run in fp32: an fp16 / bf16 ``w`` takes ONE device cast, `w.float()`, as `gptq_quantize` does (exact, so the
-    result is that of the fp32 weight with the same values)."""
-    if isinstance(w, torch.Tensor) and w.is_cuda and w.dtype in _HALF_WTYPE:
-        return w.float()
-    return w
-
-
 def _stats_args(stats: "SearchStatistics", w, qtype, group_size):
     w = _search_weight(w)
-    _require_device(w, "w", torch.float32)
     k = stats.gram.shape[0]
     if w.dim() != 2 or w.shape[0] != k:
         raise ValueError(f"weights must be [K, N] with K = {k}, got {tuple(w.shape)}")
@@ -1046,50 +1059,54 @@ def _stats_args(stats: "SearchStatistics", w, qtype, group_size):
 def awq_scale_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
                            reduce_range=False, n_grid: int = 20):
     """`awq_scale_search` from running statistics (oq_awq_scale_search_stats_f32): (best_scale [K] on device, losses[n_grid]).
-    An fp16 / bf16 ``w`` is cast once (`w.float()`); the arithmetic of the search is fp32."""
+    An fp16 / bf16 ``w`` is read as it is (oq_awq_scale_search_stats_h16, no fp32 copy); the arithmetic of the search is fp32 and the
+    result that of ``w.float()``, byte for byte."""
     w2, ldw, k, n, gs = _stats_args(stats, w, qtype, group_size)
     lib = L.load()
     dev = w2.device
     scales = torch.empty((n_grid, k), dtype=torch.float32, device=dev)
     losses = torch.empty(n_grid, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.oq_awq_stats_workspace_bytes(k, n) + 256, dev)
+    wargs, kind = _w_args(w2)
+    ws = _workspace((lib.oq_awq_stats_half_workspace_bytes if kind == "h16" else lib.oq_awq_stats_workspace_bytes)(k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
-    L.check(lib.oq_awq_scale_search_stats_f32(_ptr(stats.abs_sum), _ptr(stats.gram), stats.rows, k, _ptr(w2), n, ldw, L.QTYPE_CODE[qtype],
-                                              L.STRATEGY_CODE[strategy], gs, int(symmetric), int(reduce_range), int(n_grid), _ptr(scales),
-                                              _ptr(losses), _ptr(best), C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
+    L.check(getattr(lib, "oq_awq_scale_search_stats_" + kind)(_ptr(stats.abs_sum), _ptr(stats.gram), stats.rows, k, *wargs, n, ldw,
+                                                              L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs, int(symmetric),
+                                                              int(reduce_range), int(n_grid), _ptr(scales), _ptr(losses), _ptr(best),
+                                                              C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
     return scales[int(best.item())], losses.double().cpu().numpy()
 
 
 def awq_clip_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
                           reduce_range=False):
     """`awq_clip_search` from running statistics (oq_awq_clip_search_stats_f32): (best clip_ratio, losses[10]).
-    An fp16 / bf16 ``w`` is cast once (`w.float()`)."""
+    An fp16 / bf16 ``w`` is read as it is (oq_awq_clip_search_stats_h16, no fp32 copy): the result of ``w.float()``, byte for byte."""
     w2, ldw, k, n, gs = _stats_args(stats, w, qtype, group_size)
     lib = L.load()
     dev = w2.device
     losses = torch.empty(10, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _workspace(lib.oq_awq_stats_workspace_bytes(k, n) + 256, dev)
+    wargs, kind = _w_args(w2)
+    ws = _workspace((lib.oq_awq_stats_half_workspace_bytes if kind == "h16" else lib.oq_awq_stats_workspace_bytes)(k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
-    L.check(lib.oq_awq_clip_search_stats_f32(_ptr(stats.gram), stats.rows, k, _ptr(w2), n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy],
-                                             gs, int(symmetric), int(reduce_range), _ptr(losses), _ptr(best), C.c_void_p(ws.data_ptr() + off),
-                                             ws.numel() - off, _stream()))
+    L.check(getattr(lib, "oq_awq_clip_search_stats_" + kind)(_ptr(stats.gram), stats.rows, k, *wargs, n, ldw, L.QTYPE_CODE[qtype],
+                                                             L.STRATEGY_CODE[strategy], gs, int(symmetric), int(reduce_range), _ptr(losses),
+                                                             _ptr(best), C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
     return 1 - int(best.item()) / 100, losses.double().cpu().numpy()
 
 
 def smooth_quant_scale_stats(stats: "SearchStatistics", w: torch.Tensor, alpha: float) -> torch.Tensor:
     """`smooth_quant_scale` from the running per-channel absmax: the kernel's column absmax of a one-row matrix is that row.
-    An fp16 / bf16 ``w`` is cast once (`w.float()`)."""
+    An fp16 / bf16 ``w`` is read as it is (oq_smooth_quant_scale_h16)."""
     return smooth_quant_scale(stats.absmax.reshape(1, -1), w, alpha)
 
 
 def smooth_quant_scale(x: torch.Tensor, w: torch.Tensor, alpha: float) -> torch.Tensor:
     """pre_passes/smooth_quant.py:62-74, :111-113 (oq_smooth_quant_scale_f32): the smoothing scale [K] on the device.  ``x`` is
-    fp32; an fp16 / bf16 ``w`` is cast once (`w.float()`)."""
+    fp32; an fp16 / bf16 ``w`` is read as it is (oq_smooth_quant_scale_h16, no fp32 copy) and gives the scale of ``w.float()``, byte
+    for byte."""
     x2, ldx = _row_major(_flat_inputs(x))
     w = _search_weight(w)
-    _require_device(w, "w", torch.float32)
     t, k = x2.shape
     if w.dim() != 2 or w.shape[0] != k:           # the kernel reads K rows of W: a shorter W would be read out of bounds
         raise ValueError(f"weights must be [K, N] with K = {k}, got {tuple(w.shape)}")
@@ -1099,8 +1116,9 @@ def smooth_quant_scale(x: torch.Tensor, w: torch.Tensor, alpha: float) -> torch.
     lib = L.load()
     out = torch.empty(k, dtype=torch.float32, device=w2.device)
     ws = _workspace(lib.oq_smooth_quant_workspace_bytes(k), w2.device)
-    L.check(lib.oq_smooth_quant_scale_f32(_ptr(x2), t, k, ldx, _ptr(w2), w2.shape[1], ldw, float(alpha), _ptr(out), _ptr(ws), ws.numel(),
-                                          _stream()))
+    wargs, kind = _w_args(w2)
+    L.check(getattr(lib, "oq_smooth_quant_scale_" + kind)(_ptr(x2), t, k, ldx, *wargs, w2.shape[1], ldw, float(alpha), _ptr(out), _ptr(ws),
+                                                          ws.numel(), _stream()))
     return out
 
 

@@ -552,8 +552,8 @@ def _calibrate(model: Message, G: _Graph, targets, qconfig: QConfig, device, kee
 # ------------------------------------------------------------------------------------------------------------ AWQ / SmoothQuant
 class DeviceSearches:
     """The numeric cores of the two pre-processing passes on the GPU (hip/ops.py: `oq_smooth_quant_scale_f32`,
-    `oq_awq_scale_search_f32`, `oq_awq_clip_search_f32`).  `x`: the node's calibration input in HBM, `w`: the weight [K, N]
-    as NumPy (uploaded once per node)."""
+    `oq_awq_scale_search_f32`, `oq_awq_clip_search_f32` and their `_h16` twins).  `x`: the node's calibration input in HBM, `w`: the
+    weight [K, N] as NumPy (uploaded once per node; an `np.float16` weight as its 2-byte elements, searched on as it is)."""
 
     def __init__(self):
         self._w = (None, None)
@@ -561,12 +561,14 @@ class DeviceSearches:
     def _dev(self, w):
         from .staging import upload
         if self._w[0] is not w:
-            self._w = (w, upload(w))
+            # a FLOAT16 weight goes up as its 2 bytes per element: the searches read it as it is (ops: the `_h16` entry points)
+            self._w = (w, upload(w, keep_half=True))
         return self._w[1]
 
     def resident(self, w, tensor) -> None:
-        """`tensor` is `w` in HBM already (same shape, fp32, contiguous): searched on as it is."""
-        if tuple(tensor.shape) == tuple(w.shape) and tensor.is_cuda and tensor.is_contiguous() and str(tensor.dtype) == "torch.float32":
+        """`tensor` is `w` in HBM already (same shape, fp32 -- or fp16 for a FLOAT16 weight --, contiguous): searched on as it is."""
+        want = "torch.float16" if getattr(w, "dtype", None) == np.float16 else "torch.float32"
+        if tuple(tensor.shape) == tuple(w.shape) and tensor.is_cuda and tensor.is_contiguous() and str(tensor.dtype) == want:
             self._w = (w, tensor)
 
     @staticmethod
@@ -597,7 +599,9 @@ class DeviceSearches:
     def scale_rows(self, w, scale, want_host=True):
         """awq.py:187 / smooth_quant.py:114 (`scale.reshape(-1, 1) * weights`) on the copy of the weight the search already
         uploaded: (the product on the host, the same product in HBM for the seam -- no second upload, no pass over the weight in
-        NumPy).  One fp32 multiply per element either way: the same bits."""
+        NumPy).  One fp32 multiply per element either way: the same bits.  A FLOAT16 weight meets the fp32 scale in torch's type
+        promotion: the product is fp32, one multiply on the exact upcast of each element in one pass (no `w.float()` temporary),
+        and is never rounded back."""
         import torch
         from .staging import download
         updated = self._dev(w) * torch.from_numpy(np.ascontiguousarray(scale, dtype=np.float32)).to(self._dev(w).device).reshape(-1, 1)
@@ -628,13 +632,37 @@ def _divide_in_place(x, scale: np.ndarray) -> None:
     x.div_(s.to(x.device).reshape(1, -1))
 
 
-def _preprocess(G: _Graph, targets, qconfig: QConfig, meta: dict, searches, defer_host: bool = False) -> dict:
+def _half_mul_scale(scale: np.ndarray, node_name: str):
+    """The scale pair of a FLOAT16 target.  The `Mul` in front of the node runs in the activation's type, so its
+    initializer is FLOAT16: r16 = fp16(1 / s), round to nearest even.  The weight's rows (and the running statistics) then take
+    s_eff = 1 / fp32(r16) instead of the searched s, so that `Mul` and weight stay exact inverses up to one fp32 rounding --
+    s_eff / s - 1 reaches 2^-11, which applied to one side only would be an error of that size in every product.
+    Returns (r16 float16[K], s_eff float32[K]); a channel whose r16 is zero, subnormal, infinite or NaN raises ValueError."""
+    s = np.asarray(scale, dtype=np.float32)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        r16 = (np.float32(1) / s).astype(np.float16)
+        bad = ~np.isfinite(r16) | (np.abs(r16) < np.finfo(np.float16).tiny)
+        if bad.any():
+            k = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"node '{node_name}': the reciprocal of the scale of input channel {k} (scale {float(s[k]):.6g}) is not a normal "
+                             f"float16 ({float(r16[k])!r}); the FLOAT16 graph cannot carry this Mul initializer")
+        s_eff = np.float32(1) / r16.astype(np.float32)
+    return r16, s_eff
+
+
+def _preprocess(G: _Graph, targets, qconfig: QConfig, meta: dict, searches, defer_host: bool = False, half_targets=()) -> dict:
     """pre_passes/__init__.py:72-83: every preprocessor's pass over the target nodes in graph order.  Both passes do the same
     surgery around different searches (smooth_quant.py:91-134, awq.py:114-204): the scale is folded into the weight's rows,
     a `Mul` by 1 / scale goes in front of the node (initializer `<node output>_scale`), the node's calibration input is
     divided by the scale.  AWQ's clip search (awq.py:206-259) leaves a per-node `clip_ratio`.  Returns {id(node): QConfig}
-    for the nodes whose configuration changed."""
+    for the nodes whose configuration changed.
+
+    `half_targets` (id(node) of the FLOAT16 targets, `half_weights="native_calibrated"`): the search runs on the fp16 weight as it
+    is (`DeviceSearches`), the `Mul` initializer is FLOAT16 and the rescaled weight is the fp32 product s_eff[:, None] * W
+    (`_half_mul_scale`), never rounded back.  With a NumPy provider (no `scale_rows`) the pass works on float32 copies of the
+    weight and of a held half input; consumers of one value keep sharing one object."""
     per_node: dict = {}
+    upcast_inputs: dict = {}                                 # id(held half input) -> its float32 copy, one per value
     if len([p for p in qconfig.preprocessors if p.preprocessing_type in ("awq", "smooth_quant")]) > 1:
         raise NotImplementedError("more than one rescaling preprocessor: both would register the initializer '<output>_scale'")
     for pre in qconfig.preprocessors:
@@ -649,21 +677,30 @@ def _preprocess(G: _Graph, targets, qconfig: QConfig, meta: dict, searches, defe
             w_name, out_name = node.input[1], node.output[0]
             w = G.array(w_name)
             cfg = per_node.get(id(node), qconfig)
+            is_half = id(node) in half_targets
+            if is_half and not hasattr(searches, "scale_rows"):
+                w = np.asarray(w).astype(np.float32)
+                if isinstance(x, np.ndarray) and x.dtype != np.float32:
+                    x = upcast_inputs.setdefault(id(x), (x, x.astype(np.float32)))[1]       # (the original is kept alive: its id stays its own)
+                    node_meta["input"] = x
             if hasattr(searches, "resident") and G.device_values.get(w_name) is not None:
                 searches.resident(w, G.device_values[w_name])           # the calibration walk left this weight in HBM
             if kind == "smooth_quant":
                 scale = np.asarray(searches.smooth_quant_scale(x, w, pre.alpha), dtype=np.float32)
             else:
                 scale = np.asarray(searches.awq_scale_search(x, w, cfg.weights), dtype=np.float32)
+            name = f"{out_name}_scale"
+            if name in G.inits:
+                raise ValueError(f"an initializer named '{name}' exists already")
+            reciprocal = (1.0 / scale).astype(np.float32)
+            if is_half:
+                reciprocal, scale = _half_mul_scale(scale, node.name)       # the scale the FLOAT16 file can carry, and its inverse
             resident = None
             if hasattr(searches, "scale_rows"):
                 updated, resident = searches.scale_rows(w, scale, want_host=not defer_host)
             else:
                 updated = np.multiply(scale.reshape(-1, 1), w)
-            name = f"{out_name}_scale"
-            if name in G.inits:
-                raise ValueError(f"an initializer named '{name}' exists already")
-            G.set_initializer(name, (1.0 / scale).astype(np.float32))
+            G.set_initializer(name, reciprocal)
             _divide_in_place(x, scale)
             mul_out = f"{out_name}_scaled_input"
             mul = make_node("Mul", [node.input[0], name], [mul_out], name=f"{node.name}/scale_input")
@@ -810,11 +847,13 @@ def _half_candidates(G: _Graph, qconfig: QConfig, element_types) -> list:
             and len(G.inits[n.input[1]].dims) == 2 and G.inits[n.input[1]].data_type in element_types]
 
 
-def _check_half_native(G: _Graph, qconfig: QConfig, targets, half_weights: str = "native") -> set:
+def _check_half_native(G: _Graph, qconfig: QConfig, targets, half_weights: str = "native", post_calibration: str = "if_read") -> set:
     """`half_weights="native"`: FLOAT16 [K, N] weights are quantized as they are by the MatMulNBits rule of a weight-only
     RTN configuration.  `half_weights="native_calibrated"`: the same, and weight-only GPTQ as well -- the calibration walk
     runs the FLOAT16 graph as it is and its fp16 activations go to the Hessian without an fp32 copy
-    (`oq_hessian_accumulate_h16`).  Everything else says what is unsupported."""
+    (`oq_hessian_accumulate_h16`) --, and the preprocessors (AWQ with and without the clip search, SmoothQuant) in front of
+    weight-only RTN: the walk folds the fp16 activations into `ops.SearchStatistics`, the searches read the fp16 weight as it is
+    (DESIGN.md 4.21).  Everything else says what is unsupported."""
     opt = f"half_weights='{half_weights}'"
     bf16 = _half_candidates(G, qconfig, (DataType.BFLOAT16,))
     if bf16:
@@ -827,9 +866,20 @@ def _check_half_native(G: _Graph, qconfig: QConfig, targets, half_weights: str =
     if qconfig.input_activations is not None or qconfig.output_activations is not None:
         raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): activation quantization (the QDQ / QLinear rules with "
                                   "activation arguments) is unsupported on half-precision models; only weight-only MatMulNBits is")
-    if qconfig.preprocessors:
-        raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): preprocessors (AWQ / SmoothQuant) are unsupported on half-precision models")
     algorithm = getattr(qconfig.weights.algorithm, "algorithm_type", None)
+    if qconfig.preprocessors and half_weights != "native_calibrated":
+        raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): preprocessors (AWQ / SmoothQuant) are unsupported on half-precision models with "
+                                  "this value; half_weights='native_calibrated' takes them in front of weight-only RTN")
+    if qconfig.preprocessors:
+        # the rescaled weight exists as fp32 in HBM only: a second walk of the FLOAT16 graph cannot run on it
+        if algorithm == "gptq":
+            raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): preprocessors (AWQ / SmoothQuant) combined with the gptq algorithm are "
+                                      "unsupported on half-precision models (GPTQ needs a calibration walk on the rescaled weights, which exist "
+                                      "as fp32 only); preprocessors take weight-only RTN, GPTQ takes no preprocessor")
+        if post_calibration == "always":
+            raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): post_calibration='always' is unsupported with preprocessors on "
+                                      "half-precision models (the rescaled weights exist as fp32 only, the FLOAT16 graph cannot be walked "
+                                      "on them); use post_calibration='if_read'")
     if half_weights == "native_calibrated":
         if algorithm not in ("rtn", "gptq"):
             raise NotImplementedError(f"{opt} ('{name}' is FLOAT16): the {algorithm} algorithm is unsupported on half-precision models (HQQ "
@@ -857,7 +907,7 @@ def apply_pre_passes(model, qconfig: QConfig, *, device="cuda", calibrate=None, 
         raise ValueError(f"half_weights must be one of {HALF_WEIGHTS}, got {half_weights!r}")
     G = _structural_passes(model)
     targets = _target_nodes(G, qconfig, half_native=half_weights != "error")
-    half_targets = _check_half_native(G, qconfig, targets, half_weights) if half_weights != "error" else set()
+    half_targets = _check_half_native(G, qconfig, targets, half_weights, post_calibration) if half_weights != "error" else set()
     if not targets:
         # an fp16 / bf16 export (the usual half-precision form) has constant MatMul / Gemm weights and not one fp32
         # matrix among them; returning it untouched with a success status would look like a quantized model
@@ -874,7 +924,7 @@ def apply_pre_passes(model, qconfig: QConfig, *, device="cuda", calibrate=None, 
         keep = (getattr(searches, "wants", True) if calibrate is _calibrate else True) if qconfig.preprocessors else False
         meta = calibrate(model, G, targets, qconfig, device, keep_inputs=keep)
     if qconfig.preprocessors and targets:                   # pre_passes/__init__.py:72-88
-        per_node = _preprocess(G, targets, qconfig, meta, searches, defer_host=_defer_host_copies)
+        per_node = _preprocess(G, targets, qconfig, meta, searches, defer_host=_defer_host_copies, half_targets=half_targets)
         _name_nodes(G)
         read = any(a is not None and a.is_static for a in (qconfig.input_activations, qconfig.output_activations)) or \
             bool(qconfig.weights.algorithm.requires_calibration)
@@ -919,7 +969,11 @@ def quantize_model(model, qconfig: QConfig, *, device="cuda", weight_arrays=None
     "native_calibrated" is "native" plus weight-only GPTQ: the calibration walk runs the FLOAT16 graph as it is (random
     calibration data takes the input's own type), the tapped fp16 activations go to the Hessian without an fp32 copy
     (`ops.hessian_accumulate` on half tensors), the weight is upcast exactly for the loop, and the scales are stored as FLOAT16 by
-    the same rule.  Activation arguments, preprocessors, HQQ and BFLOAT16 initializers stay refused by name."""
+    the same rule.  It also takes the preprocessors (AWQ with and without `clip_search`, SmoothQuant) in front of
+    weight-only RTN: the fp16 activations become running statistics, the searches read the fp16 weight as it is, the `Mul`
+    initializer is FLOAT16 and the weight is rescaled by the exact inverse of what that initializer holds.
+    Activation arguments, HQQ, BFLOAT16 initializers, a preprocessor combined with GPTQ and `post_calibration="always"` stay
+    refused by name; "native" keeps refusing preprocessors."""
     if not isinstance(qconfig, QConfig):
         raise TypeError(f"qconfig must be a QConfig, got {type(qconfig)}")
     if qconfig.weights is None and qconfig.input_activations is None and qconfig.output_activations is None:

@@ -29,7 +29,8 @@ def quantize(model, qconfig: QConfig, *, half_weights: str = "error"):
     """Same signature and error behaviour as the reference: TypeError for anything that is not a model; the model is
     returned unchanged when ``qconfig`` selects nothing to quantize.  ``half_weights="native"`` (this package's own writer
     only): FLOAT16 weights are quantized as they are by the weight-only MatMulNBits rule; ``"native_calibrated"`` also takes
-    weight-only GPTQ on them, calibrated on the FLOAT16 graph (`model_quantize.quantize_model`)."""
+    weight-only GPTQ on them, calibrated on the FLOAT16 graph, and the preprocessors (AWQ, SmoothQuant) in front of weight-only RTN
+    (`model_quantize.quantize_model`)."""
     from .onnx_proto import Message, serialize
 
     own_input = isinstance(model, (bytes, bytearray, memoryview, str, os.PathLike)) or \
