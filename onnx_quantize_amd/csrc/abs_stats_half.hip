@@ -37,11 +37,11 @@ __host__ __device__ __forceinline__ int stat_width(const void* X, int64_t K, int
     return 1;
 }
 
-template <bool BF16>
+template <typename E>
 __device__ __forceinline__ float abs_widen(uint32_t b /* the element in the low 16 bits */) {
     // bf16: the shift and the sign mask on the word itself; fabsf(ElemBF16::one(..)) is the same value in 7 % more instructions
-    if constexpr (BF16) return __uint_as_float((b << 16) & 0x7FFFFFFFu);
-    else return fabsf(ElemF16::one(static_cast<uint16_t>(b)));
+    if constexpr (std::is_same_v<E, ElemBF16>) return __uint_as_float((b << 16) & 0x7FFFFFFFu);
+    else return fabsf(E::one(static_cast<uint16_t>(b)));
 }
 
 template <int V> struct StatRaw;
@@ -57,24 +57,24 @@ __device__ __forceinline__ typename StatRaw<V>::type stat_load(const uint16_t* p
     return __builtin_nontemporal_load((const __attribute__((address_space(1))) raw*)p);
 }
 
-template <bool BF16, int V>
+template <typename E, int V>
 __device__ __forceinline__ void stat_unpack(const typename StatRaw<V>::type r, float (&a)[V]) {
     if constexpr (V == 1) {
-        a[0] = abs_widen<BF16>(r);
+        a[0] = abs_widen<E>(r);
     } else if constexpr (V == 2) {
-        a[0] = abs_widen<BF16>(r & 0xFFFFu);
-        a[1] = abs_widen<BF16>(r >> 16);
+        a[0] = abs_widen<E>(r & 0xFFFFu);
+        a[1] = abs_widen<E>(r >> 16);
     } else {
 #pragma unroll
         for (int i = 0; i < V / 2; ++i) {
-            a[2 * i] = abs_widen<BF16>(r[i] & 0xFFFFu);
-            a[2 * i + 1] = abs_widen<BF16>(r[i] >> 16);
+            a[2 * i] = abs_widen<E>(r[i] & 0xFFFFu);
+            a[2 * i + 1] = abs_widen<E>(r[i] >> 16);
         }
     }
 }
 
 // One lane's V columns over the `rows` rows of its chunk, `x` at the chunk's first row.
-template <bool BF16, int V, int DEPTH>
+template <typename E, int V, int DEPTH>
 __device__ __forceinline__ void stat_lane(const uint16_t* x, int64_t ldx, int64_t rows, float* psum, float* pmax) {
     static_assert(DEPTH % 4 == 0, "whole fours");
     typedef typename StatRaw<V>::type raw;
@@ -83,10 +83,10 @@ __device__ __forceinline__ void stat_lane(const uint16_t* x, int64_t ldx, int64_
     for (int i = 0; i < V; ++i) s[i] = m[i] = 0.f;
     auto four = [&](const raw r0, const raw r1, const raw r2, const raw r3) {
         float a[V], b[V], c[V], d[V];
-        stat_unpack<BF16, V>(r0, a);
-        stat_unpack<BF16, V>(r1, b);
-        stat_unpack<BF16, V>(r2, c);
-        stat_unpack<BF16, V>(r3, d);
+        stat_unpack<E, V>(r0, a);
+        stat_unpack<E, V>(r1, b);
+        stat_unpack<E, V>(r2, c);
+        stat_unpack<E, V>(r3, d);
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             s[i] += (a[i] + b[i]) + (c[i] + d[i]);
@@ -108,7 +108,7 @@ __device__ __forceinline__ void stat_lane(const uint16_t* x, int64_t ldx, int64_
     }
     for (; t < rows; ++t) {
         float a[V];
-        stat_unpack<BF16, V>(stat_load<V>(x + t * ldx), a);
+        stat_unpack<E, V>(stat_load<V>(x + t * ldx), a);
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             s[i] += a[i];
@@ -124,7 +124,7 @@ __device__ __forceinline__ void stat_lane(const uint16_t* x, int64_t ldx, int64_
 
 // Stage 1.  blockIdx.y = item, blockIdx.x = column tile * chunks + chunk of that item (blocks past its last tile leave at once).
 // partial: `slot` floats of sums [chunk][k] and `slot` floats of maxima per item.  table == nullptr: the one item `one`.
-template <bool BF16>
+template <typename E>
 __global__ __launch_bounds__(kStatBlock) void abs_stats_half_partial(const StatItem* table, const StatItem one, int cap, int64_t slot, float* partial) {
     StatItem it = one;
     if (table != nullptr) it = table[blockIdx.y];            // uniform: scalar loads
@@ -140,10 +140,10 @@ __global__ __launch_bounds__(kStatBlock) void abs_stats_half_partial(const StatI
     float* pmax = psum + static_cast<int64_t>(chunks) * it.K;
     const uint16_t* x = it.X + t0 * it.ldx + c;
     switch (v) {                                             // uniform over the block
-        case 8: stat_lane<BF16, 8, 8>(x, it.ldx, rows, psum, pmax); break;
-        case 4: stat_lane<BF16, 4, 16>(x, it.ldx, rows, psum, pmax); break;
-        case 2: stat_lane<BF16, 2, 16>(x, it.ldx, rows, psum, pmax); break;
-        default: stat_lane<BF16, 1, 16>(x, it.ldx, rows, psum, pmax); break;
+        case 8: stat_lane<E, 8, 8>(x, it.ldx, rows, psum, pmax); break;
+        case 4: stat_lane<E, 4, 16>(x, it.ldx, rows, psum, pmax); break;
+        case 2: stat_lane<E, 2, 16>(x, it.ldx, rows, psum, pmax); break;
+        default: stat_lane<E, 1, 16>(x, it.ldx, rows, psum, pmax); break;
     }
 }
 
@@ -209,7 +209,8 @@ int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq
                                    void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(sizeof(oq_abs_stats_item) == 48 && sizeof(StatItem) == sizeof(oq_abs_stats_item), "six 8-byte fields");
     // every check on the host copy, before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: unknown xtype %d", xtype);
+    int32_t st = half_operand_ok("oq_abs_stats_cols_many_h16", "x", xtype, nullptr);   // the items' X: entry by entry below
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(items_host != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: null items_host");
     OQ_REQUIRE(count >= 1 && count <= 65535, OQ_ERR_INVALID_ARGUMENT, "oq_abs_stats_cols_many_h16: bad count=%lld (1 <= count <= 65535)",
                (long long)count);
@@ -254,9 +255,8 @@ int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq
     one.absmax = items_host[0].absmax;
     hipStream_t s = as_stream(stream);
     const dim3 grid(static_cast<uint32_t>(grid_x), static_cast<uint32_t>(count));
-    if (xtype == OQ_W_BF16) hipLaunchKernelGGL(abs_stats_half_partial<true>, grid, dim3(kStatBlock), 0, s, table, one, cap, p.slot, partial);
-    else hipLaunchKernelGGL(abs_stats_half_partial<false>, grid, dim3(kStatBlock), 0, s, table, one, cap, p.slot, partial);
-    int32_t st = check_launch("abs_stats_half_partial");
+    with_half_elem(xtype, [&](auto e) { hipLaunchKernelGGL(abs_stats_half_partial<decltype(e)>, grid, dim3(kStatBlock), 0, s, table, one, cap, p.slot, partial); });
+    st = check_launch("abs_stats_half_partial");
     if (st != OQ_OK) return st;
     const dim3 fgrid(static_cast<uint32_t>(ceil_div(p.max_k, kStatBlock)), static_cast<uint32_t>(count));
     hipLaunchKernelGGL(abs_stats_half_fold, fgrid, dim3(kStatBlock), 0, s, table, one, p.slot, static_cast<const float*>(partial));

@@ -22,11 +22,6 @@ namespace oq {
 constexpr int kAwqMaxGrid = 64;
 constexpr int kColChunks = 64;   // row chunks of the column reductions
 
-// fp16 and bf16 are ElemF16 / ElemBF16 of half_elem.hpp; fp32 has the same face
-struct AwqF32 {
-    typedef float raw;
-    static __device__ __forceinline__ float one(float b) { return b; }
-};
 // four neighbouring elements of a row: 16 bytes of fp32, 8 bytes of a 2-byte type (the pointer aligned to that)
 template <typename E>
 __device__ __forceinline__ float4 load4(const typename E::raw* p) {
@@ -693,7 +688,7 @@ static int32_t candidate_loss(const AwqWs& w, const typename E::raw* W, int64_t 
             st = rtn_impl(RtnCall{W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, 0, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN,
                                   w.rtn_ws, w.rtn_ws_bytes, s});
         } else {   // the clip search quantizes W itself: the half RTN (rtn_half.hip) gives the bytes of rtn_impl on the upcast matrix, no fp32 copy
-            st = oq_rtn_quantize_h16(W, std::is_same_v<E, ElemBF16> ? OQ_W_BF16 : OQ_W_F16, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range,
+            st = oq_rtn_quantize_h16(W, kWtype<E>, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range,
                                      clip_ratio, w.q, w.qscale, w.qzp, OQ_LAYOUT_KN, w.rtn_half_ws, w.rtn_half_ws_bytes, s);
         }
         if (st != OQ_OK) return st;
@@ -757,18 +752,16 @@ static int32_t check_common(const float* X, int64_t T, int64_t K, int64_t ldx, c
     return OQ_OK;
 }
 
-// ---- the element type of W on the host.  A 2-byte W adds one buffer behind the fp32 layout of the workspace: the partial ranges of
+// ---- A 2-byte W adds one buffer behind the fp32 layout of the workspace: the partial ranges of
 // oq_rtn_quantize_h16 on the general clip route, 2 floats x N per 64-row chunk of a group.  (K / g) ceil(g / 64) chunks, which is
 // <= ceil(K / 64) + K / 257 for the groups of more than 256 rows (and channel / tensor) that use them.  The largest grid of that call,
 // ceil(N / 256) (K / 16 + K / g) blocks, stays below 2^31 for every shape the checks above let through (K N <= 2^40, g >= 4).
-template <typename E> constexpr bool kHalfW = sizeof(typename E::raw) == 2;
-template <typename E> constexpr int32_t kWtype = std::is_same_v<E, ElemBF16> ? OQ_W_BF16 : OQ_W_F16;
 static size_t half_rtn_bytes(int64_t K, int64_t N) { return align256(static_cast<size_t>(8) * N * (ceil_div(K, 64) + K / 257 + 1)) + 256; }
 
 template <typename E>
 static void carve(int64_t T, int64_t K, int64_t N, AwqWs* w, void* workspace) {
     const size_t fp32_bytes = awq_workspace(T, K, N, w, static_cast<char*>(workspace));
-    if constexpr (kHalfW<E>) {
+    if constexpr (kTwoByteElem<E>) {
         w->rtn_half_ws = static_cast<char*>(workspace) + fp32_bytes;     // a multiple of 256 behind a 256-byte aligned base
         w->rtn_half_ws_bytes = half_rtn_bytes(K, N);
     }
@@ -785,7 +778,7 @@ static int32_t awq_scale_search(const char* fn, const float* X, int64_t T, int64
     int32_t st = check_common(X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, &g);
     if (st != OQ_OK) return st;
     OQ_REQUIRE(scales_out && losses_out && best_out && n_grid >= 1 && n_grid <= kAwqMaxGrid, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
-    const size_t need = kHalfW<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
+    const size_t need = kTwoByteElem<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
     OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
                "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
     hipStream_t s = as_stream(stream);
@@ -829,7 +822,7 @@ static int32_t awq_clip_search(const char* fn, const float* X, int64_t T, int64_
     int32_t st = check_common(X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, &g);
     if (st != OQ_OK) return st;
     OQ_REQUIRE(losses_out && best_out, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
-    const size_t need = kHalfW<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
+    const size_t need = kTwoByteElem<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
     OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
                "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
     hipStream_t s = as_stream(stream);
@@ -874,7 +867,7 @@ static int32_t stats_begin(const float* act_sum, const float* G, int64_t T, int6
         *g = gs;
     }
     OQ_REQUIRE(ceil_div(K, 8) <= 65535 && K <= 65535 && ceil_div(K, *g) <= 65535, OQ_ERR_UNSUPPORTED, "awq: K too large");
-    const size_t need = kHalfW<E> ? oq_awq_stats_half_workspace_bytes(K, N) : oq_awq_stats_workspace_bytes(K, N);
+    const size_t need = kTwoByteElem<E> ? oq_awq_stats_half_workspace_bytes(K, N) : oq_awq_stats_workspace_bytes(K, N);
     OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
                "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
     carve<E>(stats_rows(K), K, N, w, workspace);
@@ -959,13 +952,6 @@ static int32_t smooth_quant_scale(const char* fn, const float* X, int64_t T, int
     return check_launch("smooth_scale_kernel");
 }
 
-// what every _h16 entry point checks of its W in front of everything its fp32 twin checks
-static int32_t half_weight_ok(const char* fn, const void* W, int32_t wtype) {
-    OQ_REQUIRE(half_type_ok(wtype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
-    OQ_REQUIRE(aligned_to(W, 2), OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned", fn);
-    return OQ_OK;
-}
-
 }  // namespace oq
 
 extern "C" {
@@ -985,7 +971,7 @@ size_t oq_awq_half_workspace_bytes(int64_t T, int64_t K, int64_t N) {
 int32_t oq_awq_scale_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype,
                                 int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
                                 float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return awq_scale_search<AwqF32>("oq_awq_scale_search_f32", X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid,
+    return awq_scale_search<ElemF32>("oq_awq_scale_search_f32", X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid,
                                     scales_out, losses_out, best_out, workspace, workspace_bytes, stream);
 }
 
@@ -993,19 +979,18 @@ int32_t oq_awq_scale_search_h16(const float* X, int64_t T, int64_t K, int64_t ld
                                 int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
                                 float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
     static const char fn[] = "oq_awq_scale_search_h16";
-    const int32_t st = half_weight_ok(fn, W, wtype);
+    const int32_t st = half_operand_ok(fn, "W", wtype, W);
     if (st != OQ_OK) return st;
-    if (wtype == OQ_W_F16)
-        return awq_scale_search<ElemF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out, losses_out,
-                                         best_out, workspace, workspace_bytes, stream);
-    return awq_scale_search<ElemBF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out, losses_out,
-                                      best_out, workspace, workspace_bytes, stream);
+    return with_half_elem(wtype, [&](auto e) {
+        return awq_scale_search<decltype(e)>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out,
+                                             losses_out, best_out, workspace, workspace_bytes, stream);
+    });
 }
 
 int32_t oq_awq_clip_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype,
                                int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
                                void* workspace, size_t workspace_bytes, void* stream) {
-    return awq_clip_search<AwqF32>("oq_awq_clip_search_f32", X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out,
+    return awq_clip_search<ElemF32>("oq_awq_clip_search_f32", X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out,
                                    best_out, workspace, workspace_bytes, stream);
 }
 
@@ -1013,13 +998,12 @@ int32_t oq_awq_clip_search_h16(const float* X, int64_t T, int64_t K, int64_t ldx
                                int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
                                void* workspace, size_t workspace_bytes, void* stream) {
     static const char fn[] = "oq_awq_clip_search_h16";
-    const int32_t st = half_weight_ok(fn, W, wtype);
+    const int32_t st = half_operand_ok(fn, "W", wtype, W);
     if (st != OQ_OK) return st;
-    if (wtype == OQ_W_F16)
-        return awq_clip_search<ElemF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
-                                        workspace_bytes, stream);
-    return awq_clip_search<ElemBF16>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
-                                     workspace_bytes, stream);
+    return with_half_elem(wtype, [&](auto e) {
+        return awq_clip_search<decltype(e)>(fn, X, T, K, ldx, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out,
+                                            workspace, workspace_bytes, stream);
+    });
 }
 
 size_t oq_awq_stats_workspace_bytes(int64_t K, int64_t N) {
@@ -1035,7 +1019,7 @@ size_t oq_awq_stats_half_workspace_bytes(int64_t K, int64_t N) {
 int32_t oq_awq_scale_search_stats_f32(const float* act_sum, const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype,
                                       int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid, float* scales_out,
                                       float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return awq_scale_search_stats<AwqF32>("oq_awq_scale_search_stats_f32", act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range,
+    return awq_scale_search_stats<ElemF32>("oq_awq_scale_search_stats_f32", act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range,
                                           n_grid, scales_out, losses_out, best_out, workspace, workspace_bytes, stream);
 }
 
@@ -1043,19 +1027,18 @@ int32_t oq_awq_scale_search_stats_h16(const float* act_sum, const float* G, int6
                                       int32_t qtype, int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, int32_t n_grid,
                                       float* scales_out, float* losses_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream) {
     static const char fn[] = "oq_awq_scale_search_stats_h16";
-    const int32_t st = half_weight_ok(fn, W, wtype);
+    const int32_t st = half_operand_ok(fn, "W", wtype, W);
     if (st != OQ_OK) return st;
-    if (wtype == OQ_W_F16)
-        return awq_scale_search_stats<ElemF16>(fn, act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out,
-                                               losses_out, best_out, workspace, workspace_bytes, stream);
-    return awq_scale_search_stats<ElemBF16>(fn, act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid, scales_out,
-                                            losses_out, best_out, workspace, workspace_bytes, stream);
+    return with_half_elem(wtype, [&](auto e) {
+        return awq_scale_search_stats<decltype(e)>(fn, act_sum, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, n_grid,
+                                                   scales_out, losses_out, best_out, workspace, workspace_bytes, stream);
+    });
 }
 
 int32_t oq_awq_clip_search_stats_f32(const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
                                      int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    return awq_clip_search_stats<AwqF32>("oq_awq_clip_search_stats_f32", G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out,
+    return awq_clip_search_stats<ElemF32>("oq_awq_clip_search_stats_f32", G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out,
                                          best_out, workspace, workspace_bytes, stream);
 }
 
@@ -1063,13 +1046,12 @@ int32_t oq_awq_clip_search_stats_h16(const float* G, int64_t T, int64_t K, const
                                      int32_t strategy, int64_t group_size, int32_t symmetric, int32_t reduce_range, float* losses_out, int32_t* best_out,
                                      void* workspace, size_t workspace_bytes, void* stream) {
     static const char fn[] = "oq_awq_clip_search_stats_h16";
-    const int32_t st = half_weight_ok(fn, W, wtype);
+    const int32_t st = half_operand_ok(fn, "W", wtype, W);
     if (st != OQ_OK) return st;
-    if (wtype == OQ_W_F16)
-        return awq_clip_search_stats<ElemF16>(fn, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
-                                              workspace_bytes, stream);
-    return awq_clip_search_stats<ElemBF16>(fn, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out, workspace,
-                                           workspace_bytes, stream);
+    return with_half_elem(wtype, [&](auto e) {
+        return awq_clip_search_stats<decltype(e)>(fn, G, T, K, W, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, losses_out, best_out,
+                                                  workspace, workspace_bytes, stream);
+    });
 }
 
 // sum over the T rows of |x[t, k]| added to `sum_inout` [K] (a running statistic over calibration batches; awq.py:47-50 divides by T)
@@ -1095,16 +1077,17 @@ int32_t oq_abs_sum_cols_f32(const float* X, int64_t T, int64_t K, int64_t ldx, f
 
 int32_t oq_smooth_quant_scale_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, float alpha, float* scale_out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-    return smooth_quant_scale<AwqF32>("oq_smooth_quant_scale_f32", X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
+    return smooth_quant_scale<ElemF32>("oq_smooth_quant_scale_f32", X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
 }
 
 int32_t oq_smooth_quant_scale_h16(const float* X, int64_t T, int64_t K, int64_t ldx, const void* W, int32_t wtype, int64_t N, int64_t ldw, float alpha,
                                   float* scale_out, void* workspace, size_t workspace_bytes, void* stream) {
     static const char fn[] = "oq_smooth_quant_scale_h16";
-    const int32_t st = half_weight_ok(fn, W, wtype);
+    const int32_t st = half_operand_ok(fn, "W", wtype, W);
     if (st != OQ_OK) return st;
-    if (wtype == OQ_W_F16) return smooth_quant_scale<ElemF16>(fn, X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
-    return smooth_quant_scale<ElemBF16>(fn, X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
+    return with_half_elem(wtype, [&](auto e) {
+        return smooth_quant_scale<decltype(e)>(fn, X, T, K, ldx, W, N, ldw, alpha, scale_out, workspace, workspace_bytes, stream);
+    });
 }
 
 size_t oq_smooth_quant_workspace_bytes(int64_t K) {

@@ -420,10 +420,10 @@ size_t oq_hessian_half_workspace_bytes(int64_t T, int64_t K) {
 int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype, int64_t T, int64_t K, int64_t ldx, int64_t n_seen, int64_t n_add, float* H,
                                   void* workspace, size_t workspace_bytes, void* stream) {
     // every check before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: unknown xtype %d", xtype);
+    const int32_t st = half_operand_ok("oq_hessian_accumulate_h16", "X", xtype, X);
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(X != nullptr && H != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: null X / H");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(X) & 1u) == 0 && (reinterpret_cast<uintptr_t>(H) & 3u) == 0, OQ_ERR_INVALID_ARGUMENT,
-               "oq_hessian_accumulate_h16: X must be 2-byte aligned and H 4-byte aligned");
+    OQ_REQUIRE(aligned_to(H, 4), OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: H must be 4-byte aligned");
     OQ_REQUIRE(T > 0 && K > 0 && ldx >= K, OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_h16: bad shape T=%lld K=%lld ldx=%lld", (long long)T,
                (long long)K, (long long)ldx);
     OQ_REQUIRE(matrix_ok(T, K, ldx) && K <= kMaxHessianWidth, OQ_ERR_UNSUPPORTED, "oq_hessian_accumulate_h16: operand too large (T=%lld K=%lld ldx=%lld)",
@@ -433,7 +433,9 @@ int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype, int64_t T, int64
     const int64_t n_total = n_seen + n_add;
     const float beta = n_seen == 0 ? 0.0f : static_cast<float>(static_cast<double>(n_seen) / static_cast<double>(n_total));   // gptq.py:254
     const float alpha = static_cast<float>(2.0 / static_cast<double>(n_total));   // 2 / n on the sum, as the piece methods of oq_hessian_accumulate_f32
-    return launch_syrk_h16(X, xtype == OQ_W_BF16, T, K, ldx, alpha, beta, H, workspace, workspace_bytes, as_stream(stream));
+    return with_half_elem(xtype, [&](auto e) {      // the piece kernels are templates on the MFMA operand, chosen by `bool bf16`
+        return launch_syrk_h16(X, std::is_same_v<decltype(e), ElemBF16>, T, K, ldx, alpha, beta, H, workspace, workspace_bytes, as_stream(stream));
+    });
 }
 
 // G1 for the fp16 / bf16 tensors of one calibration batch in one launch chain (syrk_bf16x3.hip, section 4b)
@@ -446,9 +448,12 @@ size_t oq_hessian_many_half_workspace_bytes(const oq_hessian_item* items_host, i
 int32_t oq_hessian_accumulate_many_h16(const oq_hessian_item* items_host, const oq_hessian_item* items_device, int64_t count, int32_t xtype,
                                        void* workspace, size_t workspace_bytes, void* stream) {
     static_assert(sizeof(oq_hessian_item) == 64, "eight 8-byte fields");
-    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_many_h16: unknown xtype %d", xtype);
-    return launch_syrk_h16_many(reinterpret_cast<const int64_t*>(items_host), reinterpret_cast<const int64_t*>(items_device), count, xtype == OQ_W_BF16,
-                                workspace, workspace_bytes, as_stream(stream));
+    const int32_t st = half_operand_ok("oq_hessian_accumulate_many_h16", "X", xtype, nullptr);   // the items' X: checked with the table
+    if (st != OQ_OK) return st;
+    return with_half_elem(xtype, [&](auto e) {
+        return launch_syrk_h16_many(reinterpret_cast<const int64_t*>(items_host), reinterpret_cast<const int64_t*>(items_device), count,
+                                    std::is_same_v<decltype(e), ElemBF16>, workspace, workspace_bytes, as_stream(stream));
+    });
 }
 
 // G1 for the tensors of one calibration batch (calibrate.py:292-305 hands `_accumulate_hessian` one input per node): one

@@ -16,20 +16,13 @@
 // use NumPy's summation tree (8 strided partial sums per <= 128 elements, halves above) to stay as close as
 // possible.  tests/test_hqq_gpu.py states the tolerances.
 //
-// Element types: W is fp32, fp16 or bf16 (oq_hqq_optimize_h16, oq_hip_half.h); the 2-byte types are read as they are and
+// Element types: W is fp32, fp16 or bf16 (half_elem.hpp; oq_hqq_optimize_h16, oq_hip_half.h); the 2-byte types are read as they are and
 // converted exactly at the load, the arithmetic is the fp32 one in every instantiation.  The work split (one thread = one
 // (column, k-group) row, 256 columns per block, grid (ceil(N / 256), K / g)) is the same for all three, so the float64 partials
 // of sum |w - w_r|, their fold and every decision are those of the fp32 kernels on the upcast matrix: the same bits.
 #include "half_elem.hpp"
 
 namespace oq {
-
-// ------------------------------------------------------------------------------------ element types
-// fp16 and bf16 are ElemF16 / ElemBF16 of half_elem.hpp; fp32 has the same face
-struct HqqF32 {
-    typedef float raw;
-    static __device__ __forceinline__ float one(float b) { return b; }
-};
 
 struct HqqCtrl {
     double best_err;
@@ -529,7 +522,7 @@ int32_t oq_hqq_optimize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, i
                             const float* scale, const float* zero_point_in, double lp_norm, double beta, double kappa, int32_t iters,
                             int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout, float* zero_point_out, int32_t* rounds_out,
                             void* workspace, size_t workspace_bytes, void* stream) {
-    return hqq_optimize<HqqF32>("oq_hqq_optimize_f32", W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters,
+    return hqq_optimize<ElemF32>("oq_hqq_optimize_f32", W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters,
                                 early_stop, per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
 }
 
@@ -538,13 +531,12 @@ int32_t oq_hqq_optimize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
                             int32_t early_stop, int32_t per_round_launches, void* q_out, int32_t layout, float* zero_point_out, int32_t* rounds_out,
                             void* workspace, size_t workspace_bytes, void* stream) {
     static const char fn[] = "oq_hqq_optimize_h16";
-    OQ_REQUIRE(half_type_ok(wtype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
-    OQ_REQUIRE(aligned_to(W, 2), OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned", fn);
-    if (wtype == OQ_W_F16)
-        return hqq_optimize<ElemF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
-                                    per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
-    return hqq_optimize<ElemBF16>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
-                                 per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
+    const int32_t st = half_operand_ok(fn, "W", wtype, W);
+    if (st != OQ_OK) return st;
+    return with_half_elem(wtype, [&](auto e) {
+        return hqq_optimize<decltype(e)>(fn, W, K, N, ldw, group_size, reduce_range, scale, zero_point_in, lp_norm, beta, kappa, iters, early_stop,
+                                         per_round_launches, q_out, layout, zero_point_out, rounds_out, workspace, workspace_bytes, stream);
+    });
 }
 
 }  // extern "C"

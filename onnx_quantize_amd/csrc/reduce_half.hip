@@ -23,9 +23,9 @@ typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) u32x4 global_u32x4;
 
 // Running (min, max) of one lane over 16-byte words of eight elements.
-template <bool BF16> struct HalfRange;
+template <typename E> struct HalfRange;
 
-template <> struct HalfRange<false> {   // fp16: two packed lanes per extremum, joined at the end
+template <> struct HalfRange<ElemF16> {   // fp16: two packed lanes per extremum, joined at the end
     h16x2 mn, mx;
     __device__ __forceinline__ HalfRange() {
         const _Float16 inf = __builtin_bit_cast(_Float16, static_cast<uint16_t>(0x7C00)), ninf = __builtin_bit_cast(_Float16, static_cast<uint16_t>(0xFC00));
@@ -45,7 +45,7 @@ template <> struct HalfRange<false> {   // fp16: two packed lanes per extremum, 
     __device__ __forceinline__ float hi() const { return nmax(static_cast<float>(mx.x), static_cast<float>(mx.y)); }
 };
 
-template <> struct HalfRange<true> {    // bf16: widened by a shift (low half) / a mask (high half), folded in fp32
+template <> struct HalfRange<ElemBF16> {   // bf16: widened by a shift (low half) / a mask (high half), folded in fp32
     float mn, mx;
     __device__ __forceinline__ HalfRange() : mn(INFINITY), mx(-INFINITY) {}
     __device__ __forceinline__ void word(uint32_t w) {
@@ -74,14 +74,14 @@ __device__ __forceinline__ void block_minmax_f32(float& mn, float& mx, float* s_
 
 // One block's share of a flat 2-byte array: grid-stride over the 16-byte body with kHalfDepth loads in flight, then the head
 // (< 8 elements in front of the first 16-byte boundary) and the tail (< 8 elements) one element per lane.
-template <bool BF16>
+template <typename E>
 __device__ __forceinline__ void half_range(const uint16_t* x, int64_t count, int64_t tid, int64_t stride, float& mn, float& mx) {
     int64_t vec_off = static_cast<int64_t>(((16 - reinterpret_cast<uintptr_t>(x) % 16) % 16) / 2);
     if (vec_off > count) vec_off = count;
     const int64_t nvec = (count - vec_off) / 8;
     // a pointer that came out of a descriptor is a generic one to the compiler: say that it is global memory (global_load, not flat_load)
     const global_u32x4* xv = (const global_u32x4*)(x + vec_off);
-    HalfRange<BF16> acc;
+    HalfRange<E> acc;
     int64_t i = tid;
     for (; i + (kHalfDepth - 1) * stride < nvec; i += kHalfDepth * stride) {
         u32x4 a[kHalfDepth];
@@ -93,8 +93,8 @@ __device__ __forceinline__ void half_range(const uint16_t* x, int64_t count, int
     for (; i < nvec; i += stride) acc.fold(__builtin_nontemporal_load(xv + i));
     mn = acc.lo();
     mx = acc.hi();
-    for (int64_t j = tid; j < vec_off; j += stride) { const float v = HalfElem<BF16>::one(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
-    for (int64_t j = vec_off + nvec * 8 + tid; j < count; j += stride) { const float v = HalfElem<BF16>::one(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
+    for (int64_t j = tid; j < vec_off; j += stride) { const float v = E::one(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
+    for (int64_t j = vec_off + nvec * 8 + tid; j < count; j += stride) { const float v = E::one(x[j]); mn = nmin(mn, v); mx = nmax(mx, v); }
 }
 
 struct HalfDesc {   // device-resident, 24 bytes per tensor (oq_hip.h: oq_minmax_desc, x read as a 2-byte pointer)
@@ -104,7 +104,7 @@ struct HalfDesc {   // device-resident, 24 bytes per tensor (oq_hip.h: oq_minmax
 };
 
 // Stage 1.  desc == nullptr: the one tensor (x, count), blockIdx.x = slice.  Otherwise blockIdx.y = tensor of the list.
-template <bool BF16>
+template <typename E>
 __global__ __launch_bounds__(kHalfBlock) void minmax_half_partial(const HalfDesc* desc, const uint16_t* x, int64_t count,
                                                                   float* partial /* [tensors][gridDim.x][2] */) {
     __shared__ float s_mn[kHalfBlock / 64], s_mx[kHalfBlock / 64];
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(kHalfBlock) void minmax_half_partial(const HalfDesc
     const int64_t tid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     float mn, mx;
-    half_range<BF16>(x, count, tid, stride, mn, mx);
+    half_range<E>(x, count, tid, stride, mn, mx);
     block_minmax_f32(mn, mx, s_mn, s_mx);
     if (threadIdx.x == 0) {
         float* o = partial + (static_cast<int64_t>(blockIdx.y) * gridDim.x + blockIdx.x) * 2;
@@ -163,19 +163,19 @@ static int half_many_slices(int64_t n) {   // ~4096 blocks in total, 4..64 slice
 constexpr int kHalfAbsChunkRows = 128;   // rows per block: 8 waves x 16 rows
 constexpr int kHalfAbsTileCols = 512;    // columns per block: 64 lanes x 8 elements
 
-template <bool BF16>
+template <typename E>
 __device__ __forceinline__ void absmax8(float (&mx)[8], const u32x4 a) {
     const uint32_t w[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        mx[2 * i] = nmax(mx[2 * i], fabsf(HalfElem<BF16>::one(static_cast<uint16_t>(w[i] & 0xFFFFu))));
-        mx[2 * i + 1] = nmax(mx[2 * i + 1], fabsf(HalfElem<BF16>::one(static_cast<uint16_t>(w[i] >> 16))));
+        mx[2 * i] = nmax(mx[2 * i], fabsf(E::one(static_cast<uint16_t>(w[i] & 0xFFFFu))));
+        mx[2 * i + 1] = nmax(mx[2 * i + 1], fabsf(E::one(static_cast<uint16_t>(w[i] >> 16))));
     }
 }
 
 // vec8: every row starts on a 16-byte boundary and C % 8 == 0 -- lane l owns columns col0 + 8 l .. + 7 (one 16-byte load per
 // row).  Otherwise lane l owns columns col0 + 64 i + l, i = 0..7, read one element at a time.
-template <bool BF16>
+template <typename E>
 __global__ __launch_bounds__(512) void absmax_half_cols_partial(const uint16_t* x, int64_t R, int64_t C, int64_t ldx, bool vec8,
                                                                 float* partial, uint32_t ncol_tiles) {
     __shared__ float s_mx[8][8][64];
@@ -192,14 +192,14 @@ __global__ __launch_bounds__(512) void absmax_half_cols_partial(const uint16_t* 
             for (int r = 0; r < 16; ++r)
                 t[r] = (row0 + r < R) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + (row0 + r) * ldx + c)) : u32x4{0, 0, 0, 0};
 #pragma unroll
-            for (int r = 0; r < 16; ++r) absmax8<BF16>(mx, t[r]);
+            for (int r = 0; r < 16; ++r) absmax8<E>(mx, t[r]);
         }
     } else {
         for (int r = 0; r < 16; ++r)
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int64_t c = col0 + i * 64 + lane;
-                if (c < C && row0 + r < R) mx[i] = nmax(mx[i], fabsf(HalfElem<BF16>::one(x[(row0 + r) * ldx + c])));
+                if (c < C && row0 + r < R) mx[i] = nmax(mx[i], fabsf(E::one(x[(row0 + r) * ldx + c])));
             }
     }
 #pragma unroll
@@ -225,7 +225,7 @@ __global__ void absmax_half_cols_finalize(const float* partial, int64_t chunks, 
 }
 
 // one wave per row
-template <bool BF16>
+template <typename E>
 __global__ __launch_bounds__(256) void absmax_half_rows(const uint16_t* x, int64_t R, int64_t C, int64_t ldx, bool vec8, float* out) {
     const int lane = threadIdx.x & 63;
     const int64_t r = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
@@ -234,10 +234,10 @@ __global__ __launch_bounds__(256) void absmax_half_rows(const uint16_t* x, int64
     float m = 0.f;
     if (vec8) {
         float mx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int64_t c = lane * 8; c < C; c += 512) absmax8<BF16>(mx, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + c)));
+        for (int64_t c = lane * 8; c < C; c += 512) absmax8<E>(mx, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row + c)));
         m = nmax(nmax(nmax(mx[0], mx[1]), nmax(mx[2], mx[3])), nmax(nmax(mx[4], mx[5]), nmax(mx[6], mx[7])));
     } else {
-        for (int64_t c = lane; c < C; c += 64) m = nmax(m, fabsf(HalfElem<BF16>::one(row[c])));
+        for (int64_t c = lane; c < C; c += 64) m = nmax(m, fabsf(E::one(row[c])));
     }
     m = wave_max(m);
     if (lane == 0) out[r] = m;
@@ -257,10 +257,10 @@ size_t oq_minmax_half_workspace_bytes(int64_t count) {
 int32_t oq_minmax_collect_h16(const void* x, int32_t xtype, int64_t count, float* state, double momentum, void* workspace,
                               size_t workspace_bytes, void* stream) {
     // every check before any arithmetic on an extent and before any HIP call
-    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: unknown xtype %d", xtype);
+    int32_t st = half_operand_ok("oq_minmax_collect_h16", "x", xtype, x);
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(x != nullptr && state != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: null x / state");
-    OQ_REQUIRE(aligned_to(x, 2) && aligned_to(state, 4), OQ_ERR_INVALID_ARGUMENT,
-               "oq_minmax_collect_h16: x must be 2-byte aligned and state 4-byte aligned");
+    OQ_REQUIRE(aligned_to(state, 4), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: state must be 4-byte aligned");
     OQ_REQUIRE(count_ok(count), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: bad count=%lld (1 <= count <= 2^40)", (long long)count);
     OQ_REQUIRE(momentum >= 0.0 && momentum < 1.0, OQ_ERR_INVALID_ARGUMENT, "Momentum must be in the range [0, 1) (momentum=%g).", momentum);
     const size_t need = static_cast<size_t>(kHalfMaxBlocks) * 2 * sizeof(float);
@@ -274,9 +274,8 @@ int32_t oq_minmax_collect_h16(const void* x, int32_t xtype, int64_t count, float
     const uint16_t* xh = static_cast<const uint16_t*>(x);
     float* partial = static_cast<float*>(workspace);
     const dim3 grid(static_cast<uint32_t>(nblocks));
-    if (xtype == OQ_W_BF16) hipLaunchKernelGGL(minmax_half_partial<true>, grid, dim3(kHalfBlock), 0, s, nullptr, xh, count, partial);
-    else hipLaunchKernelGGL(minmax_half_partial<false>, grid, dim3(kHalfBlock), 0, s, nullptr, xh, count, partial);
-    int32_t st = check_launch("minmax_half_partial");
+    with_half_elem(xtype, [&](auto e) { hipLaunchKernelGGL(minmax_half_partial<decltype(e)>, grid, dim3(kHalfBlock), 0, s, nullptr, xh, count, partial); });
+    st = check_launch("minmax_half_partial");
     if (st != OQ_OK) return st;
     hipLaunchKernelGGL(minmax_half_update, dim3(1), dim3(kHalfBlock), 0, s, nullptr, state, partial, static_cast<int>(nblocks), momentum);
     return check_launch("minmax_half_update");
@@ -290,7 +289,8 @@ size_t oq_minmax_many_half_workspace_bytes(int64_t n) {
 int32_t oq_minmax_collect_many_h16(const void* desc, int64_t n, int32_t xtype, double momentum, void* workspace, size_t workspace_bytes,
                                    void* stream) {
     static_assert(sizeof(HalfDesc) == sizeof(oq_minmax_desc), "the descriptor of oq_hip.h");
-    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: unknown xtype %d", xtype);
+    int32_t st = half_operand_ok("oq_minmax_collect_many_h16", "x", xtype, nullptr);   // the tensors' pointers: device memory, not looked at
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(desc != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: null desc");
     OQ_REQUIRE(aligned_to(desc, 8), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: desc must be 8-byte aligned");
     OQ_REQUIRE(n > 0 && n <= 65535, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_many_h16: bad n=%lld (1 <= n <= 65535)", (long long)n);
@@ -303,9 +303,8 @@ int32_t oq_minmax_collect_many_h16(const void* desc, int64_t n, int32_t xtype, d
     const HalfDesc* d = static_cast<const HalfDesc*>(desc);
     float* partial = static_cast<float*>(workspace);
     const dim3 grid(static_cast<uint32_t>(slices), static_cast<uint32_t>(n));
-    if (xtype == OQ_W_BF16) hipLaunchKernelGGL(minmax_half_partial<true>, grid, dim3(kHalfBlock), 0, s, d, nullptr, int64_t{0}, partial);
-    else hipLaunchKernelGGL(minmax_half_partial<false>, grid, dim3(kHalfBlock), 0, s, d, nullptr, int64_t{0}, partial);
-    int32_t st = check_launch("minmax_half_partial");
+    with_half_elem(xtype, [&](auto e) { hipLaunchKernelGGL(minmax_half_partial<decltype(e)>, grid, dim3(kHalfBlock), 0, s, d, nullptr, int64_t{0}, partial); });
+    st = check_launch("minmax_half_partial");
     if (st != OQ_OK) return st;
     hipLaunchKernelGGL(minmax_half_update, dim3(static_cast<uint32_t>(n)), dim3(kHalfBlock), 0, s, d, nullptr, partial, slices, momentum);
     return check_launch("minmax_half_update");
@@ -319,10 +318,10 @@ size_t oq_absmax_half_workspace_bytes(int64_t R, int64_t C, int32_t transposed) 
 
 int32_t oq_absmax_h16(const void* x, int32_t xtype, int64_t R, int64_t C, int64_t ldx, int32_t transposed, float* out, void* workspace,
                       size_t workspace_bytes, void* stream) {
-    OQ_REQUIRE(half_type_ok(xtype), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: unknown xtype %d", xtype);
+    int32_t st = half_operand_ok("oq_absmax_h16", "x", xtype, x);
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(x != nullptr && out != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: null x / out");
-    OQ_REQUIRE(aligned_to(x, 2) && aligned_to(out, 4), OQ_ERR_INVALID_ARGUMENT,
-               "oq_absmax_h16: x must be 2-byte aligned and out 4-byte aligned");
+    OQ_REQUIRE(aligned_to(out, 4), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: out must be 4-byte aligned");
     OQ_REQUIRE(matrix_ok(R, C, ldx), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: bad shape R=%lld C=%lld ldx=%lld", (long long)R, (long long)C,
                (long long)ldx);
     const bool vec8 = (C % 8 == 0) && (ldx % 8 == 0) && aligned_to(x, 16);
@@ -330,8 +329,7 @@ int32_t oq_absmax_h16(const void* x, int32_t xtype, int64_t R, int64_t C, int64_
     const uint16_t* xh = static_cast<const uint16_t*>(x);
     if (transposed) {
         const dim3 grid(static_cast<uint32_t>(ceil_div(R, 4)));
-        if (xtype == OQ_W_BF16) hipLaunchKernelGGL(absmax_half_rows<true>, grid, dim3(256), 0, s, xh, R, C, ldx, vec8, out);
-        else hipLaunchKernelGGL(absmax_half_rows<false>, grid, dim3(256), 0, s, xh, R, C, ldx, vec8, out);
+        with_half_elem(xtype, [&](auto e) { hipLaunchKernelGGL(absmax_half_rows<decltype(e)>, grid, dim3(256), 0, s, xh, R, C, ldx, vec8, out); });
         return check_launch("absmax_half_rows");
     }
     const int64_t chunks = ceil_div(R, kHalfAbsChunkRows);
@@ -342,11 +340,10 @@ int32_t oq_absmax_h16(const void* x, int32_t xtype, int64_t R, int64_t C, int64_
     const int64_t ncol_tiles = ceil_div(C, kHalfAbsTileCols);   // x chunks < 2^26: R * ldx <= 2^40, 128 x 512 elements per block
     float* partial = static_cast<float*>(workspace);
     const dim3 grid(static_cast<uint32_t>(ncol_tiles * chunks));
-    if (xtype == OQ_W_BF16)
-        hipLaunchKernelGGL(absmax_half_cols_partial<true>, grid, dim3(512), 0, s, xh, R, C, ldx, vec8, partial, static_cast<uint32_t>(ncol_tiles));
-    else
-        hipLaunchKernelGGL(absmax_half_cols_partial<false>, grid, dim3(512), 0, s, xh, R, C, ldx, vec8, partial, static_cast<uint32_t>(ncol_tiles));
-    int32_t st = check_launch("absmax_half_cols_partial");
+    with_half_elem(xtype, [&](auto e) {
+        hipLaunchKernelGGL(absmax_half_cols_partial<decltype(e)>, grid, dim3(512), 0, s, xh, R, C, ldx, vec8, partial, static_cast<uint32_t>(ncol_tiles));
+    });
+    st = check_launch("absmax_half_cols_partial");
     if (st != OQ_OK) return st;
     hipLaunchKernelGGL(absmax_half_cols_finalize, dim3(static_cast<uint32_t>(ceil_div(C, 256))), dim3(256), 0, s, partial, chunks, C, out);
     return check_launch("absmax_half_cols_finalize");

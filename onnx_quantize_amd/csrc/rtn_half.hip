@@ -487,7 +487,7 @@ int32_t launch_half_quantize_kn(const void* W, int32_t wtype, int64_t K, int64_t
     a.layout = OQ_LAYOUT_KN;
     a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, 256));
     a.tensor = tensor ? 1 : 0;
-    return wtype == OQ_W_F16 ? half_launch_quantize<ElemF16>(a, s) : half_launch_quantize<ElemBF16>(a, s);
+    return with_half_elem(wtype, [&](auto e) { return half_launch_quantize<decltype(e)>(a, s); });
 }
 
 // The two-launch route of the one matrix of `a`: channel, tensor, groups taller than 256 rows.
@@ -509,11 +509,12 @@ static int32_t half_launch(HalfArgs& a, hipStream_t s) {
     return half_launch_quantize<E>(a, s);
 }
 
-// What oq_rtn_quantize_h16 and oq_rtn_quantize_ptrs_h16 (`fn`) check alike, before any arithmetic on an extent and before any HIP
-// call; fills the shape, the grid, the group and the layout of `a`.
-static int32_t half_checks(const char* fn, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size,
+// What oq_rtn_quantize_h16, oq_rtn_mse_h16 and oq_rtn_quantize_ptrs_h16 (`fn`) check alike, before any arithmetic on an extent and
+// before any HIP call; fills the shape, the grid, the group and the layout of `a`.  `W`: the one matrix, null for a table of them.
+static int32_t half_checks(const char* fn, const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy, int64_t group_size,
                            int32_t symmetric, int32_t reduce_range, float clip_ratio, int32_t layout, HalfArgs* a) {
-    OQ_REQUIRE(half_type_ok(wtype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown wtype %d", fn, wtype);
+    int32_t st = half_operand_ok(fn, "W", wtype, W);
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(K > 0 && N > 0 && ldw >= N, OQ_ERR_INVALID_ARGUMENT, "%s: bad shape K=%lld N=%lld ldw=%lld", fn, (long long)K, (long long)N,
                (long long)ldw);
     OQ_REQUIRE(matrix_ok(K, N, ldw), OQ_ERR_UNSUPPORTED, "%s: matrix too large (K=%lld N=%lld ldw=%lld)", fn, (long long)K, (long long)N,
@@ -521,7 +522,7 @@ static int32_t half_checks(const char* fn, int32_t wtype, int64_t K, int64_t N, 
     OQ_REQUIRE(clip_ratio > 0.0f && clip_ratio <= 1.0f, OQ_ERR_INVALID_ARGUMENT, "clip_ratio must be in (0.0, 1.0], got %g", clip_ratio);
     OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS || layout == OQ_LAYOUT_KN_PACKED4, OQ_ERR_INVALID_ARGUMENT, "%s: bad layout %d", fn,
                layout);
-    int32_t st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &a->grid);
+    st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &a->grid);
     if (st != OQ_OK) return st;
     int64_t g;
     st = resolve_group(strategy, K, group_size, &g);
@@ -565,10 +566,9 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
     // every check before any arithmetic on an extent and before any HIP call
     OQ_REQUIRE(W != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_h16: null W");
     OQ_REQUIRE(scale_out != nullptr && zp_out != nullptr, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_h16: null scale_out / zp_out");
-    OQ_REQUIRE(aligned_to(W, 2) && aligned_to(scale_out, 4), OQ_ERR_INVALID_ARGUMENT,
-               "oq_rtn_quantize_h16: W must be 2-byte aligned and scale_out 4-byte aligned");
+    OQ_REQUIRE(aligned_to(scale_out, 4), OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_h16: scale_out must be 4-byte aligned");
     HalfArgs a{};
-    const int32_t st = half_checks("oq_rtn_quantize_h16", wtype, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
+    const int32_t st = half_checks("oq_rtn_quantize_h16", W, wtype, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
     if (st != OQ_OK) return st;
     OQ_REQUIRE(layout != OQ_LAYOUT_KN_PACKED4, OQ_ERR_UNSUPPORTED,
                "oq_rtn_quantize_h16: layout KN_PACKED4 is not produced here; quantize to KN and pack with oq_pack_nibbles");
@@ -592,9 +592,9 @@ int32_t oq_rtn_quantize_h16(const void* W, int32_t wtype, int64_t K, int64_t N, 
         a.pmax = a.pmin + need / (2 * sizeof(float));
     }
     const hipStream_t s = as_stream(stream);
-    if (half_fused(strategy, g))
-        return wtype == OQ_W_F16 ? half_launch_fused<ElemF16, false>(a, nullptr, 1, s) : half_launch_fused<ElemBF16, false>(a, nullptr, 1, s);
-    return wtype == OQ_W_F16 ? half_launch<ElemF16>(a, s) : half_launch<ElemBF16>(a, s);
+    return with_half_elem(wtype, [&](auto e) {
+        return half_fused(strategy, g) ? half_launch_fused<decltype(e), false>(a, nullptr, 1, s) : half_launch<decltype(e)>(a, s);
+    });
 }
 
 size_t oq_rtn_mse_half_workspace_bytes(int64_t K, int64_t N, int32_t strategy, int64_t group_size) {
@@ -619,9 +619,9 @@ int32_t oq_rtn_mse_h16(const void* W, int32_t wtype, int64_t K, int64_t N, int64
     // every check before any arithmetic on an extent and before any HIP call
     OQ_REQUIRE(W != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null W", fn);
     OQ_REQUIRE(scale_out != nullptr && zp_out != nullptr, OQ_ERR_INVALID_ARGUMENT, "%s: null scale_out / zp_out", fn);
-    OQ_REQUIRE(aligned_to(W, 2) && aligned_to(scale_out, 4), OQ_ERR_INVALID_ARGUMENT, "%s: W must be 2-byte aligned and scale_out 4-byte aligned", fn);
+    OQ_REQUIRE(aligned_to(scale_out, 4), OQ_ERR_INVALID_ARGUMENT, "%s: scale_out must be 4-byte aligned", fn);
     HalfArgs a{};
-    const int32_t st = half_checks(fn, wtype, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
+    const int32_t st = half_checks(fn, W, wtype, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
     if (st != OQ_OK) return st;
     OQ_REQUIRE(layout == OQ_LAYOUT_KN, OQ_ERR_UNSUPPORTED, "%s: layout %s with mse is not supported (the MSE search writes [K, N] bytes)", fn,
                layout == OQ_LAYOUT_NBITS ? "NBITS" : "KN_PACKED4");
@@ -647,7 +647,7 @@ int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn
     OQ_REQUIRE(table_device != nullptr || count == 1, OQ_ERR_INVALID_ARGUMENT,
                "oq_rtn_quantize_ptrs_h16: null table_device with count %lld (it may be null for count 1 only)", (long long)count);
     HalfArgs a{};
-    int32_t st = half_checks("oq_rtn_quantize_ptrs_h16", wtype, K, N, ldw, qtype, OQ_GROUP, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
+    int32_t st = half_checks("oq_rtn_quantize_ptrs_h16", nullptr, wtype, K, N, ldw, qtype, OQ_GROUP, group_size, symmetric, reduce_range, clip_ratio, layout, &a);
     if (st != OQ_OK) return st;
     const int64_t g = a.g;
     OQ_REQUIRE(half_fused(OQ_GROUP, g), OQ_ERR_UNSUPPORTED,
@@ -686,7 +686,7 @@ int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn
         const oq_rtn_ptrs_h16& p = table_host[i];   // read by the kernel only where there is no device table (count == 1)
         a.W = static_cast<const uint16_t*>(p.W);
         a.q = static_cast<uint8_t*>(p.q_out); a.scale = p.scale_out; a.zp = static_cast<uint8_t*>(p.zp_out);
-        st = wtype == OQ_W_F16 ? half_launch_fused<ElemF16, true>(a, table, batch, s) : half_launch_fused<ElemBF16, true>(a, table, batch, s);
+        st = with_half_elem(wtype, [&](auto e) { return half_launch_fused<decltype(e), true>(a, table, batch, s); });
         if (st != OQ_OK) return st;
     }
     return OQ_OK;

@@ -33,7 +33,7 @@
 // test_mse_tiny_and_ordinary_columns_in_one_wave holds it to that.
 //
 // Element types: W is fp32, fp16 or bf16 (oq_rtn_mse_h16, oq_hip_half.h).  The kernels that read W are templates on the element
-// (MseF32, ElemF16 / ElemBF16 of half_elem.hpp); the 2-byte types are read as they are and converted exactly at the load, and
+// (ElemF32 / ElemF16 / ElemBF16 of half_elem.hpp); the 2-byte types are read as they are and converted exactly at the load, and
 // everything behind the load -- the arithmetic per element and candidate, the order of every sum, the grid-stride mapping and the
 // block count of the tensor route, the tie-band redo, the shifted power, the masks and the resolve -- is one source for all three.
 // So the search on a half matrix gives the bytes of the fp32 search on the upcast matrix (tests/test_mse_half_gpu.py), and the
@@ -44,12 +44,6 @@
 #include "half_elem.hpp"
 
 namespace oq {
-
-// fp16 and bf16 are ElemF16 / ElemBF16 of half_elem.hpp; fp32 has the same face
-struct MseF32 {
-    typedef float raw;
-    static __device__ __forceinline__ float one(float b) { return b; }
-};
 
 constexpr int kMseSteps = 20;      // int(maxshrink * grid) = int(0.20 * 100.0), utils.py:197
 constexpr int kMsePatience = 5;    // utils.py:150
@@ -417,7 +411,7 @@ int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QG
     QGrid grid = grid_in;
     grid.clip_ratio = 1.0f;  // utils.py:188 and :334-344: the MSE range replaces the clipped one
     const int64_t kgroups = strategy == OQ_TENSOR ? 1 : K / g;
-    const int32_t st = mse_search<MseF32>(W, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s);
+    const int32_t st = mse_search<ElemF32>(W, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s);
     if (st != OQ_OK || !emit_q) return st;
     return launch_quantize_kn(W, K, N, ldw, g, kgroups, scale_out, static_cast<const uint8_t*>(zp_out), static_cast<uint8_t*>(q_out),
                               grid, zp_signed, strategy == OQ_TENSOR, s, OQ_LAYOUT_KN);
@@ -430,8 +424,7 @@ int32_t rtn_mse_half_impl(const void* W, int32_t wtype, int64_t K, int64_t N, in
     QGrid grid = grid_in;
     grid.clip_ratio = 1.0f;  // as above
     const uint16_t* w = static_cast<const uint16_t*>(W);
-    const int32_t st = wtype == OQ_W_F16 ? mse_search<ElemF16>(w, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s)
-                                         : mse_search<ElemBF16>(w, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s);
+    const int32_t st = with_half_elem(wtype, [&](auto e) { return mse_search<decltype(e)>(w, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s); });
     if (st != OQ_OK || q_out == nullptr) return st;
     return launch_half_quantize_kn(W, wtype, K, N, ldw, g, strategy == OQ_TENSOR ? 1 : K / g, scale_out, static_cast<uint8_t*>(zp_out),
                                    static_cast<uint8_t*>(q_out), grid, strategy == OQ_TENSOR, s);

@@ -143,6 +143,23 @@ def resolve_group(strategy: str, k: int, group_size) -> int:
 _HALF_WTYPE = {torch.float16: L.OQ_W_F16, torch.bfloat16: L.OQ_W_BF16}
 
 
+def _twin(t: torch.Tensor) -> tuple:
+    """For an entry point that exists as an `_f32` / `_h16` pair: the leading ``pointer[, type code]`` arguments for the
+    operand ``t`` and the suffix of the name that takes them."""
+    if t.dtype in _HALF_WTYPE:
+        return (_ptr(t), _HALF_WTYPE[t.dtype]), "h16"
+    return (_ptr(t),), "f32"
+
+
+# the workspace queries of such pairs (their names are part of the ABI and follow no rule)
+_TWIN_WORKSPACE = {
+    "awq": {"f32": "oq_awq_workspace_bytes", "h16": "oq_awq_half_workspace_bytes"},
+    "awq_stats": {"f32": "oq_awq_stats_workspace_bytes", "h16": "oq_awq_stats_half_workspace_bytes"},
+    "absmax": {"f32": "oq_absmax_workspace_bytes", "h16": "oq_absmax_half_workspace_bytes"},
+    "hessian": {"f32": "oq_hessian_workspace_bytes", "h16": "oq_hessian_half_workspace_bytes"},
+}
+
+
 def _refuse_half(w, fn: str) -> None:
     """The entry points that stay fp32-only say so by name instead of a bare dtype mismatch."""
     if isinstance(w, torch.Tensor) and w.dtype in _HALF_WTYPE:
@@ -295,8 +312,7 @@ def hqq_quantize(w: torch.Tensor, group_size: int, reduce_range=False, clip_rati
     copy.  A group of 256 runs all rounds in one pass over a half ``w``
     (the fp32 kernels re-read W every round at that size); ``per_round_launches=True`` forces the per-round route."""
     _require_device(w, "w")
-    half = w.dtype in _HALF_WTYPE
-    if not half:
+    if w.dtype not in _HALF_WTYPE:
         _require_device(w, "w", torch.float32)
     if w.dim() != 2:
         raise ValueError(f"weights must be 2-D [K, N], got shape {tuple(w.shape)}")
@@ -321,13 +337,11 @@ def hqq_quantize(w: torch.Tensor, group_size: int, reduce_range=False, clip_rati
     rounds = torch.zeros(1, dtype=torch.int32, device=dev)
     gs = -1 if group_size is None else int(group_size)
     ws = _workspace(lib.oq_hqq_workspace_bytes(k, n, gs), dev, keep=True)
-    tail = (k, n, ldw, gs, int(reduce_range), _ptr(scale), _ptr(zp_in), float(lp_norm), float(beta), float(kappa), int(iters),
-            int(early_stop), int(bool(per_round_launches)), _ptr(q), L.OQ_LAYOUT_KN if layout == "kn" else L.OQ_LAYOUT_NBITS, _ptr(zp),
-            _ptr(rounds), _ptr(ws), ws.numel(), _stream())
-    if half:
-        L.check(lib.oq_hqq_optimize_h16(_ptr(w), _HALF_WTYPE[w.dtype], *tail))
-    else:
-        L.check(lib.oq_hqq_optimize_f32(_ptr(w), *tail))
+    wargs, kind = _twin(w)
+    L.check(getattr(lib, "oq_hqq_optimize_" + kind)(*wargs, k, n, ldw, gs, int(reduce_range), _ptr(scale), _ptr(zp_in), float(lp_norm), float(beta),
+                                                    float(kappa), int(iters), int(early_stop), int(bool(per_round_launches)), _ptr(q),
+                                                    L.OQ_LAYOUT_KN if layout == "kn" else L.OQ_LAYOUT_NBITS, _ptr(zp), _ptr(rounds), _ptr(ws),
+                                                    ws.numel(), _stream()))
     return q, scale.reshape(rows, 1), zp.reshape(rows, 1), rounds
 
 
@@ -843,12 +857,9 @@ def absmax(x: torch.Tensor, per_row: bool = False) -> torch.Tensor:
     r, c = x2.shape
     lib = L.load()
     out = torch.empty(r if per_row else c, dtype=torch.float32, device=x.device)
-    if half:
-        ws = _workspace(lib.oq_absmax_half_workspace_bytes(r, c, int(per_row)), x.device)
-        L.check(lib.oq_absmax_h16(_ptr(x2), _HALF_WTYPE[x.dtype], r, c, ldx, int(per_row), _ptr(out), _ptr(ws), ws.numel(), _stream()))
-        return out
-    ws = _workspace(lib.oq_absmax_workspace_bytes(r, c, int(per_row)), x.device)
-    L.check(lib.oq_absmax_f32(_ptr(x2), r, c, ldx, int(per_row), _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    xargs, kind = _twin(x2)
+    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["absmax"][kind])(r, c, int(per_row)), x.device)
+    L.check(getattr(lib, "oq_absmax_" + kind)(*xargs, r, c, ldx, int(per_row), _ptr(out), _ptr(ws), ws.numel(), _stream()))
     return out
 
 
@@ -904,13 +915,6 @@ def _search_weight(w):
     return w
 
 
-def _w_args(w2: torch.Tensor) -> tuple:
-    """The ``W[, wtype]`` arguments of a search entry point and the suffix of its name."""
-    if w2.dtype in _HALF_WTYPE:
-        return (_ptr(w2), _HALF_WTYPE[w2.dtype]), "h16"
-    return (_ptr(w2),), "f32"
-
-
 def _search_args(x, w, qtype, strategy, group_size):
     x2, ldx = _row_major(_flat_inputs(x))
     w = _search_weight(w)
@@ -939,8 +943,8 @@ def awq_scale_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str
     scales = torch.empty((n_grid, k), dtype=torch.float32, device=dev)
     losses = torch.empty(n_grid, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _w_args(w2)
-    ws = _workspace((lib.oq_awq_half_workspace_bytes if kind == "h16" else lib.oq_awq_workspace_bytes)(t, k, n) + 256, dev)
+    wargs, kind = _twin(w2)
+    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq"][kind])(t, k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
     L.check(getattr(lib, "oq_awq_scale_search_" + kind)(_ptr(x2), t, k, ldx, *wargs, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
                                                         int(symmetric), int(reduce_range), int(n_grid), _ptr(scales), _ptr(losses), _ptr(best),
@@ -960,8 +964,8 @@ def awq_clip_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str,
     dev = w2.device
     losses = torch.empty(10, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _w_args(w2)
-    ws = _workspace((lib.oq_awq_half_workspace_bytes if kind == "h16" else lib.oq_awq_workspace_bytes)(t, k, n) + 256, dev)
+    wargs, kind = _twin(w2)
+    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq"][kind])(t, k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
     L.check(getattr(lib, "oq_awq_clip_search_" + kind)(_ptr(x2), t, k, ldx, *wargs, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
                                                        int(symmetric), int(reduce_range), _ptr(losses), _ptr(best),
@@ -1067,8 +1071,8 @@ def awq_scale_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: st
     scales = torch.empty((n_grid, k), dtype=torch.float32, device=dev)
     losses = torch.empty(n_grid, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _w_args(w2)
-    ws = _workspace((lib.oq_awq_stats_half_workspace_bytes if kind == "h16" else lib.oq_awq_stats_workspace_bytes)(k, n) + 256, dev)
+    wargs, kind = _twin(w2)
+    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq_stats"][kind])(k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
     L.check(getattr(lib, "oq_awq_scale_search_stats_" + kind)(_ptr(stats.abs_sum), _ptr(stats.gram), stats.rows, k, *wargs, n, ldw,
                                                               L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs, int(symmetric),
@@ -1086,8 +1090,8 @@ def awq_clip_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str
     dev = w2.device
     losses = torch.empty(10, dtype=torch.float32, device=dev)
     best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _w_args(w2)
-    ws = _workspace((lib.oq_awq_stats_half_workspace_bytes if kind == "h16" else lib.oq_awq_stats_workspace_bytes)(k, n) + 256, dev)
+    wargs, kind = _twin(w2)
+    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq_stats"][kind])(k, n) + 256, dev)
     off = (-ws.data_ptr()) % 256
     L.check(getattr(lib, "oq_awq_clip_search_stats_" + kind)(_ptr(stats.gram), stats.rows, k, *wargs, n, ldw, L.QTYPE_CODE[qtype],
                                                              L.STRATEGY_CODE[strategy], gs, int(symmetric), int(reduce_range), _ptr(losses),
@@ -1116,7 +1120,7 @@ def smooth_quant_scale(x: torch.Tensor, w: torch.Tensor, alpha: float) -> torch.
     lib = L.load()
     out = torch.empty(k, dtype=torch.float32, device=w2.device)
     ws = _workspace(lib.oq_smooth_quant_workspace_bytes(k), w2.device)
-    wargs, kind = _w_args(w2)
+    wargs, kind = _twin(w2)
     L.check(getattr(lib, "oq_smooth_quant_scale_" + kind)(_ptr(x2), t, k, ldx, *wargs, w2.shape[1], ldw, float(alpha), _ptr(out), _ptr(ws),
                                                           ws.numel(), _stream()))
     return out
@@ -1217,25 +1221,11 @@ def hessian_accumulate(x: torch.Tensor, h: torch.Tensor, n_seen: int, method: st
     products are exact in fp32, so the one matrix-core product that route runs carries no operand split and no product
     rounding -- it is at least as exact as each of the fp32 methods, "f32" included, and there is nothing to choose."""
     _require_device(x, "x")
-    if x.dtype in _HALF_WTYPE:
+    half = x.dtype in _HALF_WTYPE
+    if half:
         _method_code(method)                       # an unknown name is still an error
-        return _hessian_accumulate_half(x, h, n_seen)
-    _require_device(x, "x", torch.float32)
-    _require_device(h, "H", torch.float32)
-    n_add = int(x.shape[0])
-    x2 = x.reshape(-1, x.shape[-1])
-    x2, ldx = _row_major(x2)
-    t, k = x2.shape
-    if h.shape != (k, k) or not h.is_contiguous():
-        raise ValueError(f"H must be a contiguous [{k}, {k}] tensor")
-    lib = L.load()
-    ws = _workspace(lib.oq_hessian_workspace_bytes(t, k), x.device)
-    L.check(lib.oq_hessian_accumulate_f32(_ptr(x2), t, k, ldx, int(n_seen), n_add, _ptr(h), _method_code(method), _ptr(ws), ws.numel(),
-                                          _stream()))
-    return int(n_seen) + n_add
-
-
-def _hessian_accumulate_half(x: torch.Tensor, h: torch.Tensor, n_seen: int) -> int:
+    else:
+        _require_device(x, "x", torch.float32)
     _require_device(h, "H", torch.float32)
     n_add = int(x.shape[0])
     x2, ldx = _row_major(x.reshape(-1, x.shape[-1]))
@@ -1243,8 +1233,10 @@ def _hessian_accumulate_half(x: torch.Tensor, h: torch.Tensor, n_seen: int) -> i
     if h.shape != (k, k) or not h.is_contiguous():
         raise ValueError(f"H must be a contiguous [{k}, {k}] tensor")
     lib = L.load()
-    ws = _workspace(lib.oq_hessian_half_workspace_bytes(t, k), x.device)
-    L.check(lib.oq_hessian_accumulate_h16(_ptr(x2), _HALF_WTYPE[x.dtype], t, k, ldx, int(n_seen), n_add, _ptr(h), _ptr(ws), ws.numel(), _stream()))
+    xargs, kind = _twin(x2)
+    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["hessian"][kind])(t, k), x.device)
+    method_arg = () if half else (_method_code(method),)      # the `_h16` entry point has no such argument
+    L.check(getattr(lib, "oq_hessian_accumulate_" + kind)(*xargs, t, k, ldx, int(n_seen), n_add, _ptr(h), *method_arg, _ptr(ws), ws.numel(), _stream()))
     return int(n_seen) + n_add
 
 

@@ -7,17 +7,15 @@ device memory and nothing may be launched on them."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from conftest import ROOT
+from kernel_report import HALF_ELEMS, element_types, needs_hipcc, report
 
 HEADER = os.path.join(ROOT, "include", "oq_hip_half.h")
 NEW = {"oq_minmax_half_workspace_bytes": 1, "oq_minmax_collect_h16": 8, "oq_minmax_many_half_workspace_bytes": 1,
        "oq_minmax_collect_many_h16": 7, "oq_absmax_half_workspace_bytes": 3, "oq_absmax_h16": 10}
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
@@ -166,22 +164,15 @@ def test_absmax_workspace_query_returns_zero_outside_the_bounds(lib, shape, tran
 
 
 # ------------------------------------------------------------------------------------ kernel resources
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_reduce_half_kernels_do_not_spill(tmp_path):
+@needs_hipcc
+def test_reduce_half_kernels_do_not_spill():
     """HBM-bound streams: eight 16-byte loads per lane are 32 registers; scratch traffic would compete with the stream itself."""
-    from onnx_quantize_amd import _build
-    src = os.path.join(ROOT, "onnx_quantize_amd", "csrc", "reduce_half.hip")
-    r = subprocess.run([HIPCC, *_build.flags_for(src), "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o",
-                        str(tmp_path / "reduce_half.s"), src], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    seen = {}
-    for m in re.finditer(r"Function Name: (\S+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+).*?"
-                         r"SGPRs Spill: (\d+).*?VGPRs Spill: (\d+)", r.stderr, re.S):
-        seen[m.group(1)] = tuple(int(m.group(i)) for i in (2, 3, 4, 5, 6))
-    for key, copies in (("minmax_half_partial", 2), ("minmax_half_update", 1), ("absmax_half_cols_partial", 2), ("absmax_half_cols_finalize", 1),
-                        ("absmax_half_rows", 2)):
-        assert sum(key in name for name in seen) == copies, (key, list(seen))          # fp16 and bf16 instantiations
+    seen = report("reduce_half.hip").kernels
+    for key in ("minmax_half_partial", "absmax_half_cols_partial", "absmax_half_rows"):
+        assert element_types(seen, key) == HALF_ELEMS, (key, list(seen))               # fp16 and bf16 instantiations
+    for key in ("minmax_half_update", "absmax_half_cols_finalize"):
+        assert sum(key in name for name in seen) == 1, (key, list(seen))
     assert len(seen) == 8, list(seen)
-    for name, (vgprs, scratch, occ, sgpr_spill, vgpr_spill) in seen.items():
-        assert scratch == 0 and sgpr_spill == 0 and vgpr_spill == 0, (name, vgprs, scratch, sgpr_spill, vgpr_spill)
-        assert occ >= 4, (name, vgprs, occ)                 # 512-thread blocks, two per CU at the least: <= 128 registers
+    for name, k in seen.items():
+        assert k.scratch == 0 and k.sgpr_spill == 0 and k.vgpr_spill == 0, (name, k)
+        assert k.occupancy >= 4, (name, k)                  # 512-thread blocks, two per CU at the least: <= 128 registers

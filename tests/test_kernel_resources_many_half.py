@@ -4,28 +4,12 @@ single-matrix twins, from the compiler's own resource report (hipcc cross-compil
 Both forms run ONE __device__ body; the table form adds four scalar loads and the [K, N/2] epilogue.  The 16-row build with
 16-byte loads sits right at the boundary of three waves per SIMD (docs/LAB_NOTES_r07.md), so neither addition may cost a wave or
 scratch traffic there.  The kernels are compared with each other: no figure of a particular compiler is written down here."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-from conftest import ROOT
-
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from kernel_report import needs_hipcc, report
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_table_kernels_keep_the_occupancy_of_their_single_matrix_twins(tmp_path):
-    from onnx_quantize_amd import _build
-    src = os.path.join(ROOT, "onnx_quantize_amd", "csrc", "rtn_half.hip")
-    r = subprocess.run([HIPCC, *_build.flags_for(src), "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o",
-                        str(tmp_path / "rtn_half.s"), src], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    seen = {}
-    for m in re.finditer(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)", r.stderr, re.S):
-        seen[m.group(1)] = (int(m.group(2)), int(m.group(3)))            # (scratch, occupancy)
+@needs_hipcc
+def test_table_kernels_keep_the_occupancy_of_their_single_matrix_twins():
+    seen = {name: (k.scratch, k.occupancy) for name, k in report("rtn_half.hip").kernels.items()}
     pairs = []
     for elem in ("NS_7ElemF16E", "NS_8ElemBF16E"):
         for rows in (16, 32):

@@ -195,6 +195,25 @@ def test_shipped_library_has_no_attribution_switches():
         assert not re.match(r"-D\s*\w*_LAB\b", flag) and "OQ_RTN_ATTRIBUTION" not in flag, flag
 
 
+def test_element_types_live_in_one_header():
+    """csrc/half_elem.hpp is the one place that knows the element types of W and X: no other source defines an
+    element struct (a `typedef ... raw;` inside a `struct`), none names the element by a `bool BF16` template parameter or through
+    the `HalfElem<>` adapter that served those, and none compares a runtime value with OQ_W_F16 / OQ_W_BF16 (`==`, `!=`, `?`):
+    a type code becomes an element type in `with_half_elem` only."""
+    from onnx_quantize_amd import _build
+    code = r"\bOQ_W_B?F16\b"
+    compared = re.compile(r"(?:==|!=)\s*%s|%s\s*(?:==|!=|\?)|\?[^;\n]*%s" % (code, code, code))
+    header = open(os.path.join(_build.SRC, "half_elem.hpp")).read()
+    assert len(re.findall(r"struct\s+\w+\s*\{[^}]*?typedef[^;}]*\braw\s*;", header)) == 3 and compared.search(header)     # the patterns see what they look for
+    for name in sorted(os.listdir(_build.SRC)):
+        if name == "half_elem.hpp":
+            continue
+        text = open(os.path.join(_build.SRC, name)).read()
+        assert not re.search(r"struct\s+\w+\s*\{[^}]*?typedef[^;}]*\braw\s*;", text), name
+        assert "HalfElem<" not in text and not re.search(r"template\s*<[^>]*\bbool\s+BF16\b", text), name
+        assert not compared.search(text), (name, compared.search(text).group(0))
+
+
 @pytest.mark.gpu
 def test_environment_knobs_cannot_change_the_bytes():
     """one stray environment variable (OQ_RTN_NT=56 dropped the parameter and blob stores in round 2) must not
