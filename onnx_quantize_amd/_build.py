@@ -32,7 +32,10 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # Per-file additions.  hqq.hip: the SLP vectoriser pairs the register tile's values for v_pk_mul / v_pk_add; the aligned
 # register pairs fragment the allocation until the G = 128 tile of hqq_rounds_reg_kernel spills (256 registers + scratch against
 # 165 registers without pairing; tests/test_kernel_resources.py watches it).
-PER_FILE_FLAGS = {"hqq.hip": ("-fno-slp-vectorize",)}
+# matmul_nbits.hip: paired, the per-group fold `sum = fma(acc, scale, sum)` becomes v_pk_fma_f32 with an op_sel on the scale pair, and
+# on the MI355X those gave wrong low halves in lanes 48 .. 63 whenever several waves shared a SIMD (docs/LAB_NOTES_r22.md;
+# tests/test_matmul_nbits_gpu.py holds exact products on large grids against it).
+PER_FILE_FLAGS = {"hqq.hip": ("-fno-slp-vectorize",), "matmul_nbits.hip": ("-fno-slp-vectorize",)}
 
 
 def flags_for(src: str) -> list[str]:
@@ -52,7 +55,7 @@ def sources() -> list[str]:
 
 def _deps_mtime() -> float:
     hdrs = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith((".hpp", ".h"))]
-    hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h"))
+    hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 

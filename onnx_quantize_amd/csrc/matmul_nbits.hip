@@ -1,0 +1,435 @@
+// com.microsoft::MatMulNBits run from the packed blob (include/oq_hip_nbits.h):
+//
+//       Y[M, N] = A[M, K] . dequant(B)^T (+ bias)          dequant(B)[n, k] = (q[n, k] - zp[n, k / g]) * scale[n, k / g]
+//
+// q - zp is an integer in [-255, 255] and so exact in fp16 and bf16: per k-group the product A_g . (q - zp)_g runs on
+// v_mfma_f32_16x16x32_f16 / _bf16 with an exact B operand into an fp32 accumulator, which is then folded into the running sum with the
+// group's fp32 scale (one fma per group and output element).  The [N, K] weight never exists, in memory or in LDS: a workgroup
+// dequantizes the 128 x 64 integers of its current k-step into LDS, as 2-byte operands, and nothing else.
+//
+//   block     256 threads = 2 x 2 waves; tile 32 * MT rows (MT = 4: 128; MT = 1: 32, for M <= 32) x 128 columns; k-step 64.
+//   wave      16 * MT x 64 outputs = MT x 4 MFMA tiles; per tile 4 fp32 of the group accumulator and 4 of the running sum.
+//   operands  both have k as their fast axis in memory, which is what the 16x16x32 lane map wants (lane l: row / column l & 15,
+//             k = 8 (l >> 4) ... + 7): a 16-byte ds_read per fragment, rows padded to 144 bytes (conflict-free).
+//   staging   registers: the global loads of step i + 1 are issued before the MFMAs of step i; one LDS buffer, two barriers a step.
+//   fp32 A    nbits_split_rows_kernel writes two fp16 pieces per element under one power-of-two scale per row (the row's largest
+//             lands in [2^14, 2^15)): hi = fp16(x s), lo = fp16((x s - hi) 2^11).  lo meets B 2^-11 (exact: |q - zp| >= 1 keeps
+//             it a normal fp16), so both products share the accumulator.  A hi that would be an fp16 subnormal is dropped into lo.
+//   split K   few output tiles (small M): blockIdx.y takes a range of k-steps, writes its sum to slab y; nbits_reduce_kernel adds
+//             the slabs in slab order and finishes.  No atomics anywhere.
+//   guards    every global access is guarded by M, N, K: rows >= M, columns >= N and k >= K are zeros in LDS (A) or never read
+//             (B, scales, zero points); a padded blob position meets a zero of A and its bytes are finite integers whatever they hold.
+#include "half_elem.hpp"
+
+#include "../../include/oq_hip_nbits.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace oq {
+namespace {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kBN = 128;             // columns of a block tile
+constexpr int kBK = 64;              // k of a step: two MFMA depths
+constexpr int kRow = kBK * 2 + 16;   // bytes of a tile row in LDS: 16 lanes x 16 bytes land in 16 different bank quads
+constexpr int kThreads = 256;
+
+struct OpF16 : ElemF16 {
+    typedef f16x8 frag;
+    static __device__ __forceinline__ uint32_t pack(float a, float b) {      // exact integers: the rounding mode is irrelevant
+        return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
+    }
+    static __device__ __forceinline__ uint16_t round(float v) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); }
+};
+struct OpBF16 : ElemBF16 {
+    typedef bf16x8 frag;
+    static __device__ __forceinline__ uint32_t pack(float a, float b) {      // |a|, |b| <= 255: eight significand bits, the upper halves
+        return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
+    }
+    static __device__ __forceinline__ uint16_t round(float v) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v)); }
+};
+
+__device__ __forceinline__ f32x4 mfma16(const f16x8& a, const f16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+struct NbitsArgs {
+    const uint16_t* A;      // 2-byte operand: A itself, or the hi pieces
+    const uint16_t* A_lo;   // fp32 A: the lo pieces
+    int64_t lda, Ka;        // Ka: columns of A that exist (K; the pieces: K padded to 8, zero-filled)
+    int32_t a_vec;          // rows of A are 16-byte aligned
+    const uint8_t* B;
+    const void* scales;
+    int32_t scales_f32;
+    const uint8_t* zp;
+    const void* bias;
+    const int32_t* row_exp; // fp32 A: Y row m = sum * 2^row_exp[m]
+    void* Y;
+    int64_t ldy;
+    float* slab;            // split K: [splits, M, N]
+    int64_t M, N, K, g, blocks, tiles_m, steps_per_split;
+};
+
+// ---- the one rounding: fp32 sum -> (row scale) -> + bias -> Y's type.  OUT: an oq_nbits_type
+template <int OUT>
+__device__ __forceinline__ void finish(const NbitsArgs& p, int64_t m, int64_t n, float v) {
+    typedef std::conditional_t<OUT == OQ_NBITS_BF16, OpBF16, OpF16> OP;
+    if constexpr (OUT == OQ_NBITS_F32) {
+        v = ldexpf(v, p.row_exp[m]);
+        if (p.bias) v += static_cast<const float*>(p.bias)[n];
+        static_cast<float*>(p.Y)[m * p.ldy + n] = v;
+    } else {
+        if (p.bias) v += OP::one(static_cast<const uint16_t*>(p.bias)[n]);
+        static_cast<uint16_t*>(p.Y)[m * p.ldy + n] = OP::round(v);
+    }
+}
+
+// eight 2-byte elements of row `row` from column k on; zeros past Ka
+__device__ __forceinline__ u32x4 load_a8(const uint16_t* row, int64_t k, int64_t Ka, bool vec) {
+    if (vec && k + 8 <= Ka) return *reinterpret_cast<const u32x4*>(row + k);
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t e0 = (k + 2 * j < Ka) ? row[k + 2 * j] : 0u;
+        const uint32_t e1 = (k + 2 * j + 1 < Ka) ? row[k + 2 * j + 1] : 0u;
+        w[j] = e0 | (e1 << 16);
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// 32 stored values (k ascending) minus the zero point -> 32 exact 2-byte operands
+template <typename OP, int BITS>
+__device__ __forceinline__ void dequant32(const u32x4 (&raw)[BITS / 4], float zpf, u32x4 (&out)[4]) {
+    if constexpr (BITS == 4) {
+#pragma unroll
+        for (int wi = 0; wi < 4; ++wi) {
+            const uint32_t w = raw[0][wi];
+            const uint32_t ev = w & 0x0F0F0F0Fu, od = (w >> 4) & 0x0F0F0F0Fu;     // bytes: values 0 2 4 6 and 1 3 5 7
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                out[wi][j] = OP::pack(static_cast<float>((ev >> (8 * j)) & 0xFFu) - zpf, static_cast<float>((od >> (8 * j)) & 0xFFu) - zpf);
+        }
+    } else {
+#pragma unroll
+        for (int wi = 0; wi < 8; ++wi) {
+            const uint32_t w = raw[wi >> 2][wi & 3];
+            out[wi >> 1][2 * (wi & 1)] = OP::pack(static_cast<float>(w & 0xFFu) - zpf, static_cast<float>((w >> 8) & 0xFFu) - zpf);
+            out[wi >> 1][2 * (wi & 1) + 1] = OP::pack(static_cast<float>((w >> 16) & 0xFFu) - zpf, static_cast<float>(w >> 24) - zpf);
+        }
+    }
+}
+
+// Two waves per SIMD (<= 256 registers, no scratch) for a 2-byte A: unbounded, the 128-row tile takes 230 VGPRs + 64 AGPRs, one wave
+// per SIMD, and runs at less than half the speed (0.92 against 0.42 ms at 2048 x 4096 x 11008).  The fp32-A kernels stage two A pieces
+// and keep one wave per SIMD (the 8-bit one needs scratch under the bound).
+// This file is built with -fno-slp-vectorize (_build.py): paired, the fold below becomes v_pk_fma_f32 with an op_sel on the scale
+// pair, which on the MI355X gave wrong low halves in lanes 48 .. 63 whenever several waves shared a SIMD (docs/LAB_NOTES_r22.md).
+template <int OUT, int BITS, int MT>
+__global__ __launch_bounds__(kThreads, OUT == OQ_NBITS_F32 ? 1 : 2) void nbits_gemm_kernel(const NbitsArgs p) {
+    typedef std::conditional_t<OUT == OQ_NBITS_BF16, OpBF16, OpF16> OP;
+    typedef typename OP::frag frag;
+    constexpr int PIECES = OUT == OQ_NBITS_F32 ? 2 : 1;
+    constexpr int BM = 32 * MT;
+    constexpr int NT = 4;
+    constexpr int A_CHUNKS = PIECES * BM * 8 / kThreads;      // 16-byte chunks of the A tile(s) per thread: PIECES * MT
+    __shared__ __attribute__((aligned(16))) unsigned char lds[(PIECES * BM + kBN) * kRow];
+    unsigned char* const lds_b = lds + PIECES * BM * kRow;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int64_t m0 = static_cast<int64_t>(blockIdx.x % p.tiles_m) * BM;
+    const int64_t n0 = static_cast<int64_t>(blockIdx.x / p.tiles_m) * kBN;
+    const int64_t k_begin = static_cast<int64_t>(blockIdx.y) * p.steps_per_split * kBK;
+    const int64_t k_end = min(p.K, k_begin + p.steps_per_split * kBK);
+
+    // what this thread stages: A_CHUNKS chunks of A, and 32 values of one row of B
+    u32x4 a_regs[A_CHUNKS];
+    u32x4 b_regs[BITS / 4];
+    uint32_t zp_raw = 0;      // the staged group's zero point, converted where it is used: no wait for it in front of the MFMAs
+    const int b_row = tid >> 1, b_half = tid & 1;
+    const int64_t b_n = n0 + b_row;
+
+    auto load_step = [&](int64_t k) {
+#pragma unroll
+        for (int i = 0; i < A_CHUNKS; ++i) {
+            const int id = tid + i * kThreads;
+            const int piece = id / (BM * 8), r = (id >> 3) % BM, kc = id & 7;
+            const int64_t m = m0 + r;
+            const uint16_t* base = (PIECES == 2 && piece == 1) ? p.A_lo : p.A;
+            a_regs[i] = (m < p.M && k + kc * 8 < p.Ka) ? load_a8(base + m * p.lda, k + kc * 8, p.Ka, p.a_vec != 0) : u32x4{0u, 0u, 0u, 0u};
+        }
+        const int64_t kb_k = k + 32 * b_half;
+#pragma unroll
+        for (int i = 0; i < BITS / 4; ++i) b_regs[i] = u32x4{0u, 0u, 0u, 0u};
+        zp_raw = 1u << (BITS - 1);
+        if (b_n < p.N && kb_k < k_end) {
+            const int64_t kb = kb_k / p.g, within = kb_k - kb * p.g;
+            const uint8_t* src = p.B + ((b_n * p.blocks + kb) * p.g + within) * BITS / 8;
+#pragma unroll
+            for (int i = 0; i < BITS / 4; ++i) b_regs[i] = reinterpret_cast<const u32x4*>(src)[i];
+            if (p.zp != nullptr) {
+                if constexpr (BITS == 4) zp_raw = static_cast<uint32_t>(p.zp[b_n * ((p.blocks + 1) >> 1) + (kb >> 1)]) >> (4 * (kb & 1));
+                else zp_raw = p.zp[b_n * p.blocks + kb];
+            }
+        }
+    };
+    auto store_step = [&]() {
+#pragma unroll
+        for (int i = 0; i < A_CHUNKS; ++i) {
+            const int id = tid + i * kThreads;
+            *reinterpret_cast<u32x4*>(lds + (id >> 3) * kRow + (id & 7) * 16) = a_regs[i];      // id >> 3 = piece * BM + r
+        }
+        u32x4 d[4];
+        dequant32<OP, BITS>(b_regs, static_cast<float>(zp_raw & ((1u << BITS) - 1)), d);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(lds_b + b_row * kRow + b_half * 64 + i * 16) = d[i];
+    };
+
+    f32x4 sum[MT][NT], acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) sum[mt][nt] = acc[mt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    const int64_t col = n0 + wn * 64 + (lane & 15);          // + 16 nt: the output column of this lane in tile nt
+    auto load_scales = [&](int64_t kb, float (&sc)[NT]) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int64_t n = col + 16 * nt;
+            sc[nt] = 0.0f;
+            if (n < p.N) sc[nt] = p.scales_f32 ? static_cast<const float*>(p.scales)[n * p.blocks + kb] : OP::one(static_cast<const uint16_t*>(p.scales)[n * p.blocks + kb]);
+        }
+    };
+    float sc[NT];
+    int64_t in_group = k_begin % p.g;      // k of the next MFMA depth inside its group
+    if (k_begin < k_end) load_scales(k_begin / p.g, sc);
+
+    const unsigned char* const a_frag = lds + (wm * 16 * MT + (lane & 15)) * kRow + (lane >> 4) * 16;
+    const unsigned char* const b_frag = lds_b + (wn * 64 + (lane & 15)) * kRow + (lane >> 4) * 16;
+
+    if (k_begin < k_end) load_step(k_begin);
+    for (int64_t k = k_begin; k < k_end; k += kBK) {
+        store_step();
+        __syncthreads();
+        if (k + kBK < k_end) load_step(k + kBK);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int64_t ks = k + 32 * s;
+            if (ks < k_end) {
+                frag b[NT];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) b[nt] = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(b_frag + nt * 16 * kRow + s * 64));
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + mt * 16 * kRow + s * 64));
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16(a, b[nt], acc[mt][nt]);
+                }
+                if constexpr (PIECES == 2) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) b[nt] = b[nt] * static_cast<_Float16>(0.00048828125f);      // 2^-11, exact
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) {
+                        const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + (BM + mt * 16) * kRow + s * 64));
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16(a, b[nt], acc[mt][nt]);
+                    }
+                }
+                in_group += 32;
+                if (in_group == p.g || ks + 32 >= k_end) {      // the group (or this block's part of it) is complete
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) sum[mt][nt][r] = __builtin_fmaf(acc[mt][nt][r], sc[nt], sum[mt][nt][r]);
+                            acc[mt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                        }
+                    in_group = 0;
+                    if (ks + 32 < k_end) load_scales((ks + 32) / p.g, sc);
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // C/D map of the 16x16 MFMAs: column = lane & 15, row = 4 (lane >> 4) + r
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t m = m0 + wm * 16 * MT + mt * 16 + 4 * (lane >> 4) + r, n = col + 16 * nt;
+                if (m < p.M && n < p.N) {
+                    if (p.slab) p.slab[(static_cast<int64_t>(blockIdx.y) * p.M + m) * p.N + n] = sum[mt][nt][r];
+                    else finish<OUT>(p, m, n, sum[mt][nt][r]);
+                }
+            }
+}
+
+// the slabs of a split K, added in slab order
+template <int OUT>
+__global__ __launch_bounds__(kThreads) void nbits_reduce_kernel(const NbitsArgs p, const int splits) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    if (i >= p.M * p.N) return;
+    float v = p.slab[i];
+    for (int s = 1; s < splits; ++s) v += p.slab[s * p.M * p.N + i];
+    finish<OUT>(p, i / p.N, i % p.N, v);
+}
+
+// fp32 A -> two fp16 pieces per element and one exponent per row (one block per row)
+__global__ __launch_bounds__(kThreads) void nbits_split_rows_kernel(const float* A, int64_t K, int64_t lda, int64_t Kp, uint16_t* hi, uint16_t* lo,
+                                                                    int32_t* row_exp) {
+    __shared__ float part[kThreads / kWave];
+    const int64_t m = blockIdx.x;
+    const float* row = A + m * lda;
+    float mx = 0.0f;
+    for (int64_t k = threadIdx.x; k < K; k += kThreads) mx = nmax(mx, fabsf(row[k]));
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = nmax(nmax(part[0], part[1]), nmax(part[2], part[3]));
+    int shift = 0;                               // a zero row, and a row with a NaN or an infinity (it stays what it is): unscaled
+    if (mx > 0.0f && mx < INFINITY) {
+        int e;
+        frexpf(mx, &e);                          // mx in [2^(e-1), 2^e)  ->  scaled into [2^14, 2^15)
+        shift = 15 - e;
+    }
+    for (int64_t k = threadIdx.x; k < Kp; k += kThreads) {
+        const float xs = ldexpf(k < K ? row[k] : 0.0f, shift);
+        _Float16 h = static_cast<_Float16>(xs);
+        if (fabsf(static_cast<float>(h)) < 6.103515625e-05f) h = static_cast<_Float16>(0.0f);      // no fp16 subnormal reaches the matrix core as hi
+        const _Float16 l = static_cast<_Float16>((xs - static_cast<float>(h)) * 2048.0f);
+        hi[m * Kp + k] = __builtin_bit_cast(uint16_t, h);
+        lo[m * Kp + k] = __builtin_bit_cast(uint16_t, l);
+    }
+    if (threadIdx.x == 0) row_exp[m] = -shift;
+}
+
+// ---- host
+size_t r256(int64_t n) { return (static_cast<size_t>(n) + 255) / 256 * 256; }
+
+struct Plan {
+    int bm;
+    int64_t tiles_m, tiles, steps_per_split, splits, kp;
+    size_t piece_bytes, exp_bytes, slab_bytes;
+    size_t total() const { return 2 * piece_bytes + exp_bytes + slab_bytes; }
+};
+
+bool shape_ok(int64_t M, int64_t K, int64_t N, int64_t g) {
+    return extent_ok(M) && extent_ok(K) && extent_ok(N) && extent_ok(g) && count_ok(M * ((K + 7) / 8 * 8)) && count_ok(M * N) &&
+           count_ok(N * (ceil_div(K, g) * g));
+}
+
+Plan make_plan(int64_t M, int64_t K, int64_t N, int32_t atype) {
+    Plan pl;
+    pl.bm = M <= 32 ? 32 : 128;
+    pl.tiles_m = ceil_div(M, pl.bm);
+    pl.tiles = pl.tiles_m * ceil_div(N, kBN);
+    const int64_t steps = ceil_div(K, kBK);
+    const int64_t want = pl.tiles >= 128 ? 1 : std::min<int64_t>(std::min<int64_t>(8, steps), 256 / pl.tiles);
+    pl.steps_per_split = ceil_div(steps, want);
+    pl.splits = ceil_div(steps, pl.steps_per_split);
+    pl.kp = (K + 7) / 8 * 8;
+    pl.piece_bytes = atype == OQ_NBITS_F32 ? r256(M * pl.kp * 2) : 0;
+    pl.exp_bytes = atype == OQ_NBITS_F32 ? r256(M * 4) : 0;
+    pl.slab_bytes = pl.splits > 1 ? r256(pl.splits * M * N * 4) : 0;
+    return pl;
+}
+
+template <int OUT, int BITS>
+void launch_gemm(const NbitsArgs& p, const Plan& pl, hipStream_t s) {
+    const dim3 grid(static_cast<unsigned>(pl.tiles), static_cast<unsigned>(pl.splits));
+    if (pl.bm == 32) nbits_gemm_kernel<OUT, BITS, 1><<<grid, kThreads, 0, s>>>(p);
+    else nbits_gemm_kernel<OUT, BITS, 4><<<grid, kThreads, 0, s>>>(p);
+}
+
+template <int OUT>
+int32_t run(const NbitsArgs& p, const Plan& pl, int32_t bits, hipStream_t s) {
+    if (bits == 4) launch_gemm<OUT, 4>(p, pl, s);
+    else launch_gemm<OUT, 8>(p, pl, s);
+    const int32_t st = check_launch("nbits_gemm_kernel");
+    if (st != OQ_OK || pl.splits == 1) return st;
+    nbits_reduce_kernel<OUT><<<static_cast<unsigned>(ceil_div(p.M * p.N, kThreads)), kThreads, 0, s>>>(p, static_cast<int>(pl.splits));
+    return check_launch("nbits_reduce_kernel");
+}
+
+bool type_ok(int32_t t) { return t == OQ_NBITS_F32 || t == OQ_NBITS_F16 || t == OQ_NBITS_BF16; }
+
+}  // namespace
+}  // namespace oq
+
+using namespace oq;
+
+extern "C" {
+
+int32_t oq_nbits_extension_version(void) { return OQ_NBITS_EXTENSION_VERSION; }
+
+size_t oq_matmul_nbits_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t group_size, int32_t atype) {
+    if (!type_ok(atype) || !shape_ok(M, K, N, group_size)) {
+        set_error("oq_matmul_nbits_workspace_bytes: M=%lld K=%lld N=%lld group_size=%lld atype=%d outside the bounds", (long long)M, (long long)K,
+                  (long long)N, (long long)group_size, atype);
+        return 0;
+    }
+    return make_plan(M, K, N, atype).total();
+}
+
+int32_t oq_matmul_nbits(const void* A, int32_t atype, int64_t M, int64_t K, int64_t lda, const void* B, int32_t bits, int64_t N, int64_t group_size,
+                        const void* scales, int32_t scales_type, const uint8_t* zero_points, const void* bias, int32_t flags, void* Y, int64_t ldy,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "oq_matmul_nbits";
+    OQ_REQUIRE(A && B && scales && Y, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (A, B, scales and Y are required)", fn);
+    OQ_REQUIRE(type_ok(atype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown atype %d", fn, atype);
+    OQ_REQUIRE(scales_type == OQ_NBITS_F32 || scales_type == atype, OQ_ERR_INVALID_ARGUMENT, "%s: scales_type %d is neither fp32 nor atype %d", fn,
+               scales_type, atype);
+    OQ_REQUIRE(extent_ok(M) && extent_ok(K) && extent_ok(N) && matrix_ok(M, K, lda) && matrix_ok(M, N, ldy), OQ_ERR_INVALID_ARGUMENT,
+               "%s: M=%lld K=%lld N=%lld lda=%lld ldy=%lld outside the bounds", fn, (long long)M, (long long)K, (long long)N, (long long)lda,
+               (long long)ldy);
+    OQ_REQUIRE(bits == 4 || bits == 8, OQ_ERR_UNSUPPORTED, "%s: bits = %d (4 and 8 have a kernel)", fn, bits);
+    OQ_REQUIRE(extent_ok(group_size) && group_size % 32 == 0, OQ_ERR_UNSUPPORTED,
+               "%s: group_size = %lld is no multiple of 32 (two groups would share one 32-deep matrix instruction)", fn, (long long)group_size);
+    OQ_REQUIRE(!(flags & OQ_NBITS_FLOAT_ZERO_POINTS), OQ_ERR_UNSUPPORTED,
+               "%s: float zero points (q - zp is no integer: no exact matrix-core operand)", fn);
+    OQ_REQUIRE(!(flags & OQ_NBITS_G_IDX), OQ_ERR_UNSUPPORTED, "%s: g_idx has no kernel", fn);
+    OQ_REQUIRE((flags & ~(OQ_NBITS_FLOAT_ZERO_POINTS | OQ_NBITS_G_IDX)) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: unknown flags %d", fn, flags);
+    OQ_REQUIRE(shape_ok(M, K, N, group_size), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld group_size=%lld: an operand beyond 2^40 elements", fn,
+               (long long)M, (long long)K, (long long)N, (long long)group_size);
+    const uintptr_t elem = atype == OQ_NBITS_F32 ? 4 : 2;
+    OQ_REQUIRE(aligned_to(A, elem) && aligned_to(Y, elem) && aligned_to(bias, elem) && aligned_to(scales, scales_type == OQ_NBITS_F32 ? 4 : 2),
+               OQ_ERR_INVALID_ARGUMENT, "%s: A, Y, bias and scales must be aligned to their element", fn);
+    OQ_REQUIRE(aligned_to(B, 16), OQ_ERR_INVALID_ARGUMENT, "%s: B must be 16-byte aligned", fn);
+    const Plan pl = make_plan(M, K, N, atype);
+    OQ_REQUIRE(pl.total() == 0 || (workspace && workspace_bytes >= pl.total() && aligned_to(workspace, 256)), OQ_ERR_WORKSPACE,
+               "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, pl.total(), workspace ? workspace_bytes : (size_t)0);
+
+    hipStream_t s = as_stream(stream);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    NbitsArgs p{};
+    p.B = static_cast<const uint8_t*>(B);
+    p.scales = scales;
+    p.scales_f32 = scales_type == OQ_NBITS_F32;
+    p.zp = zero_points;
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
+    p.M = M, p.N = N, p.K = K, p.g = group_size, p.blocks = ceil_div(K, group_size);
+    p.tiles_m = pl.tiles_m, p.steps_per_split = pl.steps_per_split;
+    p.slab = pl.splits > 1 ? reinterpret_cast<float*>(ws + 2 * pl.piece_bytes + pl.exp_bytes) : nullptr;
+    if (atype == OQ_NBITS_F32) {
+        uint16_t* hi = reinterpret_cast<uint16_t*>(ws);
+        uint16_t* lo = reinterpret_cast<uint16_t*>(ws + pl.piece_bytes);
+        int32_t* row_exp = reinterpret_cast<int32_t*>(ws + 2 * pl.piece_bytes);
+        nbits_split_rows_kernel<<<static_cast<unsigned>(M), kThreads, 0, s>>>(static_cast<const float*>(A), K, lda, pl.kp, hi, lo, row_exp);
+        const int32_t st = check_launch("nbits_split_rows_kernel");
+        if (st != OQ_OK) return st;
+        p.A = hi, p.A_lo = lo, p.lda = pl.kp, p.Ka = pl.kp, p.a_vec = 1, p.row_exp = row_exp;
+        return run<OQ_NBITS_F32>(p, pl, bits, s);
+    }
+    p.A = static_cast<const uint16_t*>(A), p.lda = lda, p.Ka = K, p.a_vec = aligned_to(A, 16) && lda % 8 == 0;
+    return atype == OQ_NBITS_BF16 ? run<OQ_NBITS_BF16>(p, pl, bits, s) : run<OQ_NBITS_F16>(p, pl, bits, s);
+}
+
+}  // extern "C"

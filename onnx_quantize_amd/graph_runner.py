@@ -60,7 +60,8 @@ class GraphRunner:
 
     takes_sink = True        # `runner(feed, sink=...)` hands every wanted value over as it is produced (calibration_driver.run_calibration)
 
-    def __init__(self, model: Message, outputs=None, device="cuda", capture: bool = False, matmul: str = "torch", constants=None):
+    def __init__(self, model: Message, outputs=None, device="cuda", capture: bool = False, matmul: str = "torch", constants=None,
+                 matmul_nbits: str = "torch"):
         """`constants`: {initializer name: tensor on the device} for initializers the caller already holds in HBM (a second
         calibration walk over the weights the first one uploaded; a weight that was rescaled on the device and whose TensorProto
         still has the old bytes): used as they are instead of the file's bytes when device, element type and shape fit."""
@@ -84,6 +85,13 @@ class GraphRunner:
             raise ValueError(f"GraphRunner: matmul must be 'torch' or 'pieces', got {matmul!r}")
         self.matmul = matmul if self.device.type == "cuda" else "torch"
         self._weight_pieces: dict = {}       # id(constant weight) -> (the weight, its MatmulOperand)
+        # matmul_nbits = "fused": a MatMulNBits node the library has a kernel for (`ops.matmul_nbits`: integer zero points, a block
+        # size that is a multiple of 32, 4 / 8 bits, a constant B on the GPU) runs from the blob as stored -- no [N, K] weight is
+        # expanded.  Every other node, and every node under "torch", takes the expansion of `_op_MatMulNBits`.
+        if matmul_nbits not in ("torch", "fused"):
+            raise ValueError(f"GraphRunner: matmul_nbits must be 'torch' or 'fused', got {matmul_nbits!r}")
+        self.matmul_nbits = matmul_nbits if self.device.type == "cuda" else "torch"
+        self.nbits_calls = {"fused": 0, "torch": 0}      # MatMulNBits nodes run per route (a replayed graph counts its recording only)
         self.functions = {(f.domain or "", f.name, f.overload or ""): f for f in model.functions}
         self.opset = max([int(o.version or 1) for o in model.opset_import if not o.domain] or [1])
         self.wanted = list(outputs) if outputs is not None else [o.name for o in self.graph.output]
@@ -118,6 +126,7 @@ class GraphRunner:
         self.device = torch.device("cpu")
         self.functions, self.opset, self.wanted, self.input_names, self.constants, self.nodes, self.last_use = {}, opset, [], [], {}, [], {}
         self.capture, self._graphs, self._seen, self._moved, self._const_nodes = False, {}, set(), {}, {}
+        self.matmul_nbits, self.nbits_calls = "torch", {"fused": 0, "torch": 0}
         return self
 
     def evaluate(self, node, arrays) -> list:
@@ -1211,6 +1220,12 @@ class GraphRunner:
         import torch
         K, N, bits, g = a["K"], a["N"], a.get("bits", 4), a["block_size"]
         blocks = (K + g - 1) // g
+        if self.matmul_nbits == "fused" and self._nbits_fusable(x, bits, g):
+            from .hip import ops
+            self.nbits_calls["fused"] += 1
+            return ops.matmul_nbits(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g,
+                                    bias=x[5] if len(x) > 5 else None)
+        self.nbits_calls["torch"] += 1
         blob = x[1].reshape(N, blocks, -1).to(torch.uint8)
         if bits == 4:
             q = torch.stack([blob & 0x0F, blob >> 4], dim=-1).reshape(N, blocks, g)
@@ -1238,6 +1253,25 @@ class GraphRunner:
         if len(x) > 5 and x[5] is not None:
             out = out + x[5]
         return out
+
+
+    def _nbits_fusable(self, x, bits, g) -> bool:
+        """Whether `ops.matmul_nbits` takes this MatMulNBits node: what the kernel supports, on the GPU, with B, scales and zero
+        points constants of the model as the writer stores them."""
+        import torch
+        from .hip import ops
+        zp = x[3] if len(x) > 3 else None
+        g_idx = x[4] if len(x) > 4 else None
+        bias = x[5] if len(x) > 5 else None
+        if not (isinstance(x[0], torch.Tensor) and x[0].is_cuda and x[0].ndim >= 1 and x[0].numel() > 0):
+            return False
+        if ops.matmul_nbits_unsupported(x[0].dtype, bits, g, zp, g_idx) is not None:
+            return False
+        held = list(self.constants.values())
+        if not all(t is None or (t.is_cuda and any(t is c for c in held)) for t in (x[1], x[2], zp)):
+            return False
+        return (x[1].dtype == torch.uint8 and x[2].dtype in (torch.float32, x[0].dtype) and (zp is None or zp.dtype == torch.uint8)
+                and (bias is None or (bias.is_cuda and bias.dtype == x[0].dtype)))
 
 
 _CAPTURE_MAX_INPUT_ELEMENTS = 1 << 20      # recording pays when a pass is hundreds of small launches (one short sequence), not above

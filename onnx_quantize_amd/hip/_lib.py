@@ -29,6 +29,10 @@ STRATEGY_CODE = {"tensor": OQ_TENSOR, "channel": OQ_CHANNEL, "group": OQ_GROUP}
 OQ_W_F16, OQ_W_BF16 = range(2)
 OQ_HALF_EXTENSION_VERSION = 1
 WTYPE_CODE = {"float16": OQ_W_F16, "bfloat16": OQ_W_BF16}
+# include/oq_hip_nbits.h
+OQ_NBITS_F32, OQ_NBITS_F16, OQ_NBITS_BF16 = range(3)
+OQ_NBITS_FLOAT_ZERO_POINTS, OQ_NBITS_G_IDX = 1, 2
+OQ_NBITS_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -152,6 +156,13 @@ HALF_PROTOTYPES = {
     "oq_smooth_quant_scale_h16": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i64, _i64, _f32, _p, _p, _sz, _p]),
 }
 
+# the MatMulNBits extension: mirrors include/oq_hip_nbits.h one to one (tests/test_matmul_nbits_abi.py checks the set)
+NBITS_PROTOTYPES = {
+    "oq_nbits_extension_version": (_i32, []),
+    "oq_matmul_nbits_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i32]),
+    "oq_matmul_nbits": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _p, _i32, _p, _p, _i32, _p, _i64, _p, _sz, _p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -178,7 +189,7 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:  # missing ROCm runtime etc.
             raise OqHipMissing(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in [*PROTOTYPES.items(), *HALF_PROTOTYPES.items()]:
+        for name, (res, args) in [*PROTOTYPES.items(), *HALF_PROTOTYPES.items(), *NBITS_PROTOTYPES.items()]:
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -190,6 +201,9 @@ def load() -> C.CDLL:
         if lib.oq_half_extension_version() != OQ_HALF_EXTENSION_VERSION:
             raise OqHipMissing(f"{LIB_PATH} has half-precision extension {lib.oq_half_extension_version()}, "
                                f"expected {OQ_HALF_EXTENSION_VERSION}")
+        if lib.oq_nbits_extension_version() != OQ_NBITS_EXTENSION_VERSION:
+            raise OqHipMissing(f"{LIB_PATH} has MatMulNBits extension {lib.oq_nbits_extension_version()}, "
+                               f"expected {OQ_NBITS_EXTENSION_VERSION}")
         _lib = lib
     return _lib
 

@@ -1210,6 +1210,77 @@ def matmul_pieces(x: torch.Tensor, w: MatmulOperand | torch.Tensor) -> torch.Ten
     return out.reshape(*x.shape[:-1], w.cols)
 
 
+# ----------------------------------------------------------------------------- running a MatMulNBits node from its blob
+_NBITS_TYPE = {torch.float32: L.OQ_NBITS_F32, torch.float16: L.OQ_NBITS_F16, torch.bfloat16: L.OQ_NBITS_BF16}
+
+
+def matmul_nbits_unsupported(x_dtype, bits: int, block_size: int, zero_points=None, g_idx=None) -> str | None:
+    """Why `matmul_nbits` has no kernel for such a node (include/oq_hip_nbits.h, "left out"), or None when it has one."""
+    if x_dtype not in _NBITS_TYPE:
+        return f"an input of {x_dtype} (fp32, fp16 and bf16 have a kernel)"
+    if bits not in (4, 8):
+        return f"bits = {bits} (4 and 8 have a kernel)"
+    if block_size <= 0 or block_size % 32:
+        return f"block_size = {block_size} is no multiple of 32 (two groups would share one 32-deep matrix instruction)"
+    if zero_points is not None and zero_points.is_floating_point():
+        return "float zero points (q - zp is no integer: no exact matrix-core operand)"
+    if g_idx is not None:
+        return "g_idx"
+    return None
+
+
+def matmul_nbits(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero_points: torch.Tensor | None = None, *, K: int, N: int,
+                 bits: int, block_size: int, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """com.microsoft::MatMulNBits from the packed blob as stored (`oq_matmul_nbits`, csrc/matmul_nbits.hip): ``x`` [..., K] fp32,
+    fp16 or bf16 times dequant(B)^T, B [N, ceil(K / block_size), block_size * bits / 8] uint8; ``scales`` [N, blocks] fp32 or of
+    x's type; ``zero_points`` None (2^(bits - 1)) or uint8, for 4 bits packed two per byte; ``bias`` [N] of x's type.  Returns
+    [..., N] of x's type.  (q - zp) meets x on the matrix cores as an exact integer operand, group sums are scaled in fp32: no
+    [N, K] weight exists at any point.  Nothing synchronises with the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out: float zero points (HQQ), block sizes that are no
+    multiple of 32 (16), bits other than 4 / 8."""
+    _require_device(x, "x")
+    why = matmul_nbits_unsupported(x.dtype, int(bits), int(block_size), zero_points)
+    if why is not None:
+        raise NotImplementedError(f"matmul_nbits: {why}")
+    K, N, bits, g = int(K), int(N), int(bits), int(block_size)
+    if x.shape[-1] != K:
+        raise ValueError(f"matmul_nbits: x has {x.shape[-1]} columns, the node K = {K}")
+    blocks = (K + g - 1) // g
+    _require_device(blob, "blob", torch.uint8)
+    if blob.numel() != N * blocks * (g * bits // 8):
+        raise ValueError(f"matmul_nbits: a blob of {N} x {blocks} x {g * bits // 8} bytes is expected, got {tuple(blob.shape)}")
+    blob = blob.contiguous()
+    _require_device(scales, "scales")
+    if scales.dtype not in (torch.float32, x.dtype) or scales.numel() != N * blocks:
+        raise ValueError(f"matmul_nbits: scales must be {N * blocks} values of float32 or {x.dtype}, got {scales.numel()} of {scales.dtype}")
+    scales = scales.contiguous()
+    if zero_points is not None:
+        _require_device(zero_points, "zero_points", torch.uint8)
+        expect = N * ((blocks + 1) // 2) if bits == 4 else N * blocks
+        if zero_points.numel() != expect:
+            raise ValueError(f"matmul_nbits: {expect} zero-point bytes are expected, got {zero_points.numel()}")
+        zero_points = zero_points.contiguous()
+    if bias is not None:
+        _require_device(bias, "bias", x.dtype)
+        if bias.numel() != N:
+            raise ValueError(f"matmul_nbits: bias must hold {N} values, got {bias.numel()}")
+        bias = bias.contiguous()
+    x2 = x.reshape(-1, K)
+    if x2.shape[0] == 0:
+        return torch.zeros((*x.shape[:-1], N), dtype=x.dtype, device=x.device)
+    x2, lda = _row_major(x2)
+    m = x2.shape[0]
+    out = torch.empty((m, N), dtype=x.dtype, device=x.device)
+    lib = L.load()
+    atype = _NBITS_TYPE[x.dtype]
+    need = lib.oq_matmul_nbits_workspace_bytes(m, K, N, g, atype)
+    ws = _workspace(need, x.device) if need else None
+    L.check(lib.oq_matmul_nbits(_ptr(x2), atype, m, K, lda, _ptr(blob), bits, N, g, _ptr(scales), _NBITS_TYPE[scales.dtype], _ptr(zero_points),
+                                _ptr(bias), 0, _ptr(out), N, _ptr(ws), need, _stream()))
+    return out.reshape(*x.shape[:-1], N)
+
+
 # ----------------------------------------------------------------------------- G1 - G4
 def hessian_accumulate(x: torch.Tensor, h: torch.Tensor, n_seen: int, method: str | None = None) -> int:
     """gptq.py:246-260, in place on ``h`` [K, K]; ``x`` [n_add, ..., K] fp32, fp16 or bf16.  Returns the new sample
