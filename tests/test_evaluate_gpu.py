@@ -169,3 +169,61 @@ def test_the_fused_route_scores_within_twice_the_logit_distance_of_the_expansion
     b = oq.perplexity(quantized, tokens, max_length=64, stride=512, matmul_nbits="torch")
     assert abs(np.log(a) - np.log(b)) <= 2 * distance, (a, b, distance)
     assert distance < 1e-3
+
+
+# ------------------------------------------------------------------------------------ routing of nodes the writer here does not emit
+def one_node_model(bits, block_size, bias_dtype=None, K=128, N=48):
+    """X [M, K] fp32 -> MatMulNBits -> Y, built by hand: q, integer zero points and scales drawn here, a bias of `bias_dtype`."""
+    rng = np.random.default_rng(bits * 1000 + block_size)
+    blocks = K // block_size
+    q = rng.integers(0, 1 << bits, (N, blocks, block_size)).astype(np.uint8)
+    zp = rng.integers(0, 1 << bits, (N, blocks)).astype(np.uint8)
+    scales = (rng.random((N, blocks)) * 0.02 + 0.001).astype(np.float32)
+    if bits == 4:
+        blob, zp_stored = q[..., 0::2] | (q[..., 1::2] << 4), zp[:, 0::2] | (zp[:, 1::2] << 4)
+    else:
+        blob, zp_stored = q, zp
+    inits = [P.numpy_to_tensor("B", blob), P.numpy_to_tensor("S", scales), P.numpy_to_tensor("Z", zp_stored)]
+    names = ["X", "B", "S", "Z"]
+    if bias_dtype is not None:
+        inits.append(P.numpy_to_tensor("bias", rng.standard_normal(N).astype(bias_dtype)))
+        names += [None, "bias"]
+    node = P.make_node("MatMulNBits", names, ["Y"], name="fc", domain="com.microsoft", K=K, N=N, bits=bits, block_size=block_size)
+    g = P.Message("GraphProto", name="one_node", node=[node], initializer=inits, input=[P.make_value_info("X", P.DataType.FLOAT, ["M", K])],
+                  output=[P.make_value_info("Y", P.DataType.FLOAT, ["M", N])])
+    model = P.Message("ModelProto", ir_version=10, graph=g, opset_import=[P.Message("OperatorSetIdProto", domain="", version=21),
+                                                                          P.Message("OperatorSetIdProto", domain="com.microsoft", version=1)])
+    return model
+
+
+@pytest.fixture(scope="module")
+def rows():
+    return torch.from_numpy(np.random.default_rng(7).standard_normal((50, 128)).astype(np.float32))
+
+
+def test_an_8_bit_node_of_group_64_takes_the_fused_route_and_holds_the_kernel_bound(rows):
+    model = one_node_model(8, 64, np.float32)
+    runner = GraphRunner(model, device="cuda", matmul_nbits="fused")
+    got = runner(rows)["Y"]
+    assert runner.nbits_calls == {"fused": 1, "torch": 0}
+    # the float64 dequantized product of the file's own initializers
+    inits = {t.name: P.tensor_to_numpy(t) for t in P.parse_model(P.serialize(model)).graph.initializer}
+    K, N, blocks = 128, 48, 2
+    w64 = ((inits["B"].reshape(N, blocks, 64).astype(np.float64) - inits["Z"].reshape(N, blocks, 1)) * inits["S"].reshape(N, blocks, 1).astype(np.float64)).reshape(N, K)
+    bias64 = inits["bias"].astype(np.float64)
+    a64 = rows.double().numpy()
+    y64 = a64 @ w64.T + bias64
+    s = np.abs(a64) @ np.abs(w64).T + np.abs(bias64)
+    term = (K + 2 * blocks + 4) * 2.0 ** -23 * s + 2.0 ** -21 * s + K * 2.0 ** -38 * np.abs(a64).max(axis=1, keepdims=True) * np.abs(w64).max()
+    bound = term + 2.0 ** -24 * (np.abs(y64) + term)
+    err = np.abs(got.double().cpu().numpy() - y64)
+    assert got.dtype == torch.float32 and (err <= bound).all(), (err - bound).max()
+
+
+@pytest.mark.parametrize("what", ["block_size = 16", "a bias of another element type than A"])
+def test_nodes_the_kernel_leaves_out_stay_on_the_expansion_route(rows, what):
+    model = one_node_model(4, 16, np.float32) if what == "block_size = 16" else one_node_model(4, 32, np.float16)
+    fused, default = GraphRunner(model, device="cuda", matmul_nbits="fused"), GraphRunner(model, device="cuda")
+    a, b = fused(rows)["Y"], default(rows)["Y"]
+    assert a.dtype == b.dtype == torch.float32 and torch.equal(a.view(torch.uint8), b.view(torch.uint8))
+    assert fused.nbits_calls == default.nbits_calls == {"fused": 0, "torch": 1}

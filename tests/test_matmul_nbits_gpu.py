@@ -9,10 +9,9 @@ blob.  The reference value everywhere is float64:  w64 = (q - zp) * float64(scal
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from nbits_cases import ATYPE, DTYPES, Case, Plan, describe, gen
 
-DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -25,82 +24,6 @@ def ops():
 def lib():
     from onnx_quantize_amd.hip import _lib
     return _lib
-
-
-def gen(seed):
-    return torch.Generator(device="cuda").manual_seed(seed)
-
-
-def pack_blob(q, bits):
-    """q [N, blocks, g] uint8 values -> the MatMulNBits blob [N, blocks, g * bits / 8] (4 bits: the even k in the low nibble)."""
-    return q.contiguous() if bits == 8 else (q[..., 0::2] | (q[..., 1::2] << 4)).contiguous()
-
-
-def pack_zero_points(zp, bits):
-    """zp [N, blocks] uint8 -> uint8 [N, blocks] (8 bits) or two per byte, low nibble first, the pad nibble of an odd count 0xF."""
-    if bits == 8:
-        return zp.contiguous()
-    if zp.shape[1] % 2:
-        zp = torch.cat([zp, torch.full_like(zp[:, :1], 0xF)], dim=1)
-    return (zp[:, 0::2] | (zp[:, 1::2] << 4)).contiguous()
-
-
-class Case:
-    """One node and one input: the device tensors `ops.matmul_nbits` takes, and Y64."""
-
-    def __init__(self, g, M, K, N, group, bits, dtype, *, zero_points=True, bias=True, integer=False, scale_dtype=torch.float32):
-        self.M, self.K, self.N, self.group, self.bits, self.dtype = M, K, N, group, bits, dtype
-        blocks = (K + group - 1) // group
-        top = (1 << bits) - 1
-        q = torch.randint(0, top + 1, (N, blocks * group), device="cuda", generator=g, dtype=torch.int32)
-        q[:, K:] = top                                             # every padded position: all bits set (0xFF bytes in the blob)
-        zp = torch.randint(0, top + 1, (N, blocks), device="cuda", generator=g, dtype=torch.int32) if zero_points else None
-        if integer:
-            a = torch.randint(-4, 5, (M, K), device="cuda", generator=g).to(dtype)
-            scales = torch.tensor([0.125, 0.5, 1.0], device="cuda")[torch.randint(0, 3, (N, blocks), device="cuda", generator=g)]
-            b = torch.randint(-8, 9, (N,), device="cuda", generator=g).to(dtype) if bias else None
-        else:
-            a = torch.randn((M, K), device="cuda", generator=g).to(dtype)
-            scales = (torch.rand((N, blocks), device="cuda", generator=g) * 0.02 + 0.001)
-            b = torch.randn((N,), device="cuda", generator=g).to(dtype) if bias else None
-        self.x, self.bias = a, b
-        self.scales = scales.to(scale_dtype)
-        self.blob = pack_blob(q.to(torch.uint8).reshape(N, blocks, group), bits)
-        self.zero_points = None if zp is None else pack_zero_points(zp.to(torch.uint8), bits)
-        zp64 = (zp if zp is not None else torch.full((N, blocks), 1 << (bits - 1), device="cuda")).to(torch.float64)
-        w = (q.reshape(N, blocks, group).to(torch.float64) - zp64[:, :, None]) * self.scales.to(torch.float64)[:, :, None]
-        self.w64 = w.reshape(N, blocks * group)[:, :K].contiguous()
-
-    def y64(self, x=None):
-        y = (self.x if x is None else x).to(torch.float64) @ self.w64.t()
-        return y if self.bias is None else y + self.bias.to(torch.float64)
-
-    def bound(self, x=None):
-        """|Y - Y64| allowed, elementwise (the module docstring)."""
-        x64 = (self.x if x is None else x).to(torch.float64)
-        s = x64.abs() @ self.w64.abs().t()
-        if self.bias is not None:
-            s = s + self.bias.to(torch.float64).abs()
-        blocks = (self.K + self.group - 1) // self.group
-        term = (self.K + 2 * blocks + 4) * 2.0 ** -23 * s
-        if self.dtype == torch.float32:           # the two-piece operand: 22 bits, doubled; elements below 2^-17 of their row's largest
-            term = term + 2.0 ** -21 * s + self.K * 2.0 ** -38 * x64.abs().amax(dim=1, keepdim=True) * self.w64.abs().max()
-        return term + UNIT[self.dtype] * (self.y64(x).abs() + term)
-
-    def run(self, ops, x=None):
-        return ops.matmul_nbits(self.x if x is None else x, self.blob, self.scales, self.zero_points, K=self.K, N=self.N, bits=self.bits,
-                                block_size=self.group, bias=self.bias)
-
-    def parent(self, x=None):
-        """The expansion route a holder of a quantized file had before the kernel: `GraphRunner._op_MatMulNBits` itself."""
-        from onnx_quantize_amd.graph_runner import GraphRunner
-        runner = GraphRunner.evaluator(21)
-        attrs = {"K": self.K, "N": self.N, "bits": self.bits, "block_size": self.group}
-        return GraphRunner._op_MatMulNBits(runner, None, [self.x if x is None else x, self.blob, self.scales, self.zero_points, None, self.bias],
-                                           attrs, None)
-
-    def rounded(self, y64):
-        return y64.float().to(self.dtype)
 
 
 # ------------------------------------------------------------------------------------ 1. exact integers
@@ -137,16 +60,36 @@ def test_exact_integers_with_a_tail_group_and_an_odd_block_count(ops, dt, bits, 
         assert torch.equal(c.run(ops), c.rounded(c.y64()))
 
 
-@pytest.mark.parametrize("shape", [(2048, 256, 4096), (16, 256, 65536)], ids=str)
+# (shape, bits, g): 4 bits at g = 128 on the first two shapes are the cases of round 22 and keep their ids
+LARGE_GRID_PLANS = {(2048, 256, 4096): Plan(128, 16, 32, 4, 4, 1, 4), (16, 256, 65536): Plan(32, 1, 512, 4, 4, 1, 4),
+                    (16, 64, 131072): Plan(32, 1, 1024, 1, 1, 1, 1)}
+LARGE_GRIDS = [(shape, bits, group) for shape in LARGE_GRID_PLANS for bits in (4, 8) for group in (128, 32)]
+
+
+def large_grid_id(case):
+    shape, bits, group = case
+    return str(shape) if (bits, group) == (4, 128) and shape[1] == 256 else f"{shape}-{bits}bit-g{group}"
+
+
+@pytest.mark.parametrize("case", LARGE_GRIDS, ids=large_grid_id)
 @pytest.mark.parametrize("dt", sorted(DTYPES))
-def test_exact_integers_on_grids_of_several_workgroups_per_cu(ops, dt, shape):
+def test_exact_integers_on_grids_of_several_workgroups_per_cu(ops, lib, dt, case):
     """512 tiles of each tile height, K in one pass (no slabs): more workgroups than the 256 CUs, so waves of different workgroups
     share a SIMD.  A build whose per-group fold was paired into v_pk_fma_f32 got exactly this wrong (rows 12 and 14 of a tile's
-    second 16 columns, differently from run to run) while every smaller grid passed (docs/LAB_NOTES_r22.md): four calls, exact."""
-    M, K, N = shape
-    c = Case(gen(13), M, K, N, 128, 4, DTYPES[dt], integer=True)
+    second 16 columns, differently from run to run) while every smaller grid passed (docs/LAB_NOTES_r22.md): four calls, exact.
+    Both widths of q, a fold after every MFMA depth (g = 32) as well as one per two steps (g = 128), and 1024 tiles of the 32-row
+    kernel with K in one step (16 x 64 x 131072): four workgroups of that kernel fit a CU."""
+    (M, K, N), bits, group = case
+    c = Case(gen(13), M, K, N, group, bits, DTYPES[dt], integer=True)
+    pl = c.plan()
+    assert pl == LARGE_GRID_PLANS[(M, K, N)] and pl.tiles >= 512, pl
+    assert lib.load().oq_matmul_nbits_workspace_bytes(M, K, N, group, ATYPE[c.dtype]) == c.workspace()
     want = c.rounded(c.y64())
-    assert [int((c.run(ops) != want).sum()) for _ in range(4)] == [0, 0, 0, 0]
+    wrong = [c.run(ops) != want for _ in range(4)]
+    for i, w in enumerate(wrong):
+        if w.any():
+            print(f"call {i}: {describe(w, pl)}")
+    assert [int(w.sum()) for w in wrong] == [0, 0, 0, 0]
 
 
 @pytest.mark.parametrize("dt", sorted(DTYPES))
