@@ -1,0 +1,485 @@
+// QLinearMatMul / com.microsoft::QGemm / MatMulInteger on the int8 matrix cores (include/oq_hip_qlinear.h):
+//
+//       acc[m, n] = sum_k (A[m, k] - a_zp) * (B[k, n] - b_zp[n])  (+ C[n])       exact, int32 (two's-complement wrap)
+//       Y[m, n]   = epilogue(acc[m, n])
+//
+// v_mfma_i32_16x16x64_i8 is signed x signed: an unsigned operand is flipped while it is staged (x ^ 0x80 per byte, one VALU op per
+// dword) and its zero point moves by 128.  With a' = a - 128 [A unsigned], za' = a_zp - 128 [A unsigned], and b', zb' likewise:
+//
+//       acc = S - zb'[n] rowsum_k(a')[m] - za' colsum_k(b')[n] + K za' zb'[n],           S = sum_k a' b' from the MFMAs.
+//
+//   block     256 threads = 2 x 2 waves; tile 32 * MT rows (MT = 4: 128; MT = 1: 32, for M <= 32) x 128 columns; k-step 64 = one
+//             MFMA depth.  Tiling, plan and split K are those of matmul_nbits.hip.
+//   operands  both tiles lie in LDS with k as the fast axis, 64 bytes a row, padded to 80: lane l reads 16 bytes of row / column
+//             l & 15 at byte 16 (l >> 4) -- 16 different bank quads.  Which k of the 64 the instruction takes from which byte does
+//             not matter: A and B are read from the same image, so byte j of lane group g meets byte j of lane group g.
+//   A, B (NK) staged directly: 16-byte global loads along k (byte loads where rows are not 16-byte aligned, or at K's end).
+//   B (KN)    the fast axis in memory is n: a thread loads 8 dwords -- 4 columns of 8 consecutive k -- with the 32 lanes of a half
+//             wave on the 128 consecutive bytes of one k, transposes the two 4 x 4 byte blocks in registers (v_perm_b32) and writes
+//             4 x 8 bytes, each 8 consecutive k of one column, into the [n][k] image.  Columns of equal n mod 4 share a bank quad,
+//             so column 4 q + j lies in row 4 q + (j + (q >> 2)) mod 4: the half wave's writes land in 16 bank quads, two lanes
+//             each, and the 16 columns of a fragment read still cover 16.  Rows that are not 4-byte aligned take byte loads.
+//   staging   registers: the global loads of step i + 1 are issued before the MFMAs of step i; one LDS buffer, two barriers a step.
+//   guards    rows >= M and k >= K are zeros in LDS AFTER the flip (a pad of 0 is 0 of the flipped operand): the flip is applied on
+//             the way into LDS, and a padded position is staged as the flip's own byte.  Columns >= N are computed on whatever the
+//             guarded loads gave and never stored.
+//   sums      ql_sum_rows_kernel / ql_sum_cols_kernel write rowsum(a') and colsum(b') into the workspace.  The column sums of a KN
+//             matrix are written as 8 partial sums over eighths of K (blocks enough to fill the device on a [4096, 4096] weight,
+//             no second pass and no atomics); whoever reads a column sum adds the 8.
+//   split K   blockIdx.y takes a range of k-steps and writes S to int32 slab y; ql_reduce_kernel adds the slabs, corrects and
+//             finishes.  No atomics anywhere.
+#include "half_elem.hpp"
+
+#include "../../include/oq_hip_qlinear.h"
+
+#include <algorithm>
+
+namespace oq {
+namespace {
+
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kBN = 128;          // columns of a block tile
+constexpr int kBK = 64;           // k of a step: one MFMA depth
+constexpr int kRow = kBK + 16;    // bytes of a tile row in LDS: 16 lanes x 16 bytes land in 16 different bank quads
+constexpr int kThreads = 256;
+constexpr int kColSlices = 8;      // partial column sums of a KN matrix: slices of K
+
+struct QlArgs {
+    const uint8_t* A;
+    const uint8_t* B;
+    int64_t lda, ldb;
+    uint32_t a_flip, b_flip;       // 0x80808080 for an unsigned operand
+    int32_t a_signed, b_signed;
+    int32_t a_vec, b_vec;          // rows are 16-byte aligned (A, B in NK) / 4-byte aligned (B in KN)
+    const float* a_scale;
+    const void* a_zp;
+    const float* b_scale;
+    const void* b_zp;
+    int32_t b_per_column;
+    const int32_t* C;
+    const float* y_scale;
+    const void* y_zp;
+    int32_t out;
+    void* Y;
+    int64_t ldy;
+    const int32_t* rowsum;         // NULL: its multiplier zb' is zero
+    const int32_t* colsum;         // NULL: its multiplier za' is zero; [colsum_slices][colsum_stride] partial sums
+    uint32_t colsum_slices, colsum_stride;
+    uint32_t* slab;                // split K: [splits, M, N]
+    uint32_t M, N, K, tiles_m, steps_per_split;      // extents are below 2^31: 32-bit indices, 64-bit only where an offset is formed
+};
+
+__device__ __forceinline__ int32_t read_zp(const void* zp, int32_t is_signed, int64_t i) {
+    if (zp == nullptr) return 0;
+    return is_signed ? static_cast<int32_t>(static_cast<const int8_t*>(zp)[i]) : static_cast<int32_t>(static_cast<const uint8_t*>(zp)[i]);
+}
+
+// what an output column needs: zb'[n], the terms of the correction that do not depend on the row, and the fp32 scale
+struct ColTerms {
+    uint32_t zb, add;
+    float scale;
+};
+
+__device__ __forceinline__ ColTerms col_terms(const QlArgs& p, uint32_t n) {
+    ColTerms c;
+    const uint32_t za = static_cast<uint32_t>(read_zp(p.a_zp, p.a_signed, 0) - (p.a_signed ? 0 : 128));
+    c.zb = static_cast<uint32_t>(read_zp(p.b_zp, p.b_signed, p.b_per_column ? n : 0) - (p.b_signed ? 0 : 128));
+    c.add = p.K * za * c.zb;
+    if (p.colsum) {
+        uint32_t cs = 0u;
+        for (uint32_t s = 0; s < p.colsum_slices; ++s) cs += static_cast<uint32_t>(p.colsum[static_cast<int64_t>(s) * p.colsum_stride + n]);
+        c.add -= za * cs;
+    }
+    if (p.C) c.add += static_cast<uint32_t>(p.C[n]);
+    c.scale = p.out == OQ_QL_OUT_I32 ? 0.0f : p.a_scale[0] * p.b_scale[p.b_per_column ? n : 0];
+    return c;
+}
+
+// S -> acc -> Y.  Every fp32 step is one rounding, in the order the header states.
+__device__ __forceinline__ void finish(const QlArgs& p, uint32_t m, uint32_t n, uint32_t S, const ColTerms& c) {
+    const uint32_t rs = p.rowsum ? static_cast<uint32_t>(p.rowsum[m]) : 0u;
+    const int32_t acc = static_cast<int32_t>(S - c.zb * rs + c.add);
+    const int64_t at = static_cast<int64_t>(m) * p.ldy + n;
+    if (p.out == OQ_QL_OUT_I32) {
+        static_cast<int32_t*>(p.Y)[at] = acc;
+        return;
+    }
+    const float t = static_cast<float>(acc) * c.scale;
+    if (p.out == OQ_QL_OUT_F32) {
+        static_cast<float*>(p.Y)[at] = t;
+        return;
+    }
+    const bool i8 = p.out == OQ_QL_OUT_I8;
+    float q = rintf(t / p.y_scale[0]) + static_cast<float>(read_zp(p.y_zp, i8, 0));
+    q = fminf(fmaxf(q, i8 ? -128.0f : 0.0f), i8 ? 127.0f : 255.0f);
+    static_cast<uint8_t*>(p.Y)[at] = static_cast<uint8_t>(static_cast<int32_t>(q));
+}
+
+// 16 bytes of `row` from k on, as they are: the flip is applied when they are written to LDS, so that no load is followed by an
+// instruction that waits for it.  Past K: the flip's byte, which the flip turns into the pad, a zero of the flipped operand.
+__device__ __forceinline__ u32x4 load_k16(const uint8_t* row, uint32_t k, uint32_t K, bool vec, uint32_t flip) {
+    if (vec && k + 16u <= K) return *reinterpret_cast<const u32x4*>(row + k);
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        w[j] = 0u;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const uint32_t kk = k + 4 * j + b;
+            w[j] |= (kk < K ? static_cast<uint32_t>(row[kk]) : flip & 0xFFu) << (8 * b);
+        }
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// 4 bytes of one row of a KN matrix from column n on, `at` pointing at column n (raw; zeros past N)
+__device__ __forceinline__ uint32_t load_n4(const uint8_t* at, uint32_t n, uint32_t N, bool vec) {
+    if (vec && n + 4u <= N) return *reinterpret_cast<const uint32_t*>(at);
+    uint32_t w = 0u;
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (n + b < N) w |= static_cast<uint32_t>(at[b]) << (8 * b);
+    return w;
+}
+
+template <int MT, int LAYOUT>
+__global__ __launch_bounds__(kThreads, 2) void ql_gemm_kernel(const QlArgs p) {
+    constexpr int BM = 32 * MT;
+    constexpr int NT = 4;
+    constexpr int A_CHUNKS = (BM * 4 + kThreads - 1) / kThreads;      // 16-byte chunks of the A tile per thread
+    __shared__ __attribute__((aligned(16))) unsigned char lds[(BM + kBN) * kRow];
+    unsigned char* const lds_b = lds + BM * kRow;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    // the row tiles of one column tile are neighbours in the tile order, and each XCD takes one contiguous range of it: a tile of B is
+    // read into one L2, not into all eight (speed only)
+    const uint32_t tile = xcd_remap(blockIdx.x, gridDim.x);
+    const uint32_t m0 = (tile % p.tiles_m) * BM, n0 = (tile / p.tiles_m) * kBN;      // below 2^31 + a tile
+    const uint32_t k_begin = blockIdx.y * p.steps_per_split * kBK;                                 // below K + 64 splits
+    const uint32_t k_end = min(p.K, k_begin + p.steps_per_split * kBK);
+
+    u32x4 a_regs[A_CHUNKS];
+    u32x4 b_regs[2];
+    // KN: this thread's two 4 x 4 byte blocks: columns 4 nb ... + 3 at k = 8 kb ... + 7
+    const int kn_nb = tid & 31, kn_kb = tid >> 5;
+
+    // the pointers this thread loads through are formed once; a step only adds to them
+    const uint8_t* a_row[A_CHUNKS];      // the row of chunk i; NULL: a row >= M, or no chunk (the 32-row tile has 128)
+    const uint8_t* b_row[2];             // NK: likewise; KN: [0] points at (k_begin + 8 kb, n) and moves on by 64 rows a step
+#pragma unroll
+    for (int i = 0; i < A_CHUNKS; ++i) {
+        const int id = tid + i * kThreads;
+        const uint32_t m = m0 + (id >> 2);
+        a_row[i] = (id < BM * 4 && m < p.M) ? p.A + static_cast<int64_t>(m) * p.lda : nullptr;
+    }
+    const uint32_t kn_n = n0 + 4 * kn_nb;
+    if constexpr (LAYOUT == OQ_QL_NK) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t n = n0 + ((tid + i * kThreads) >> 2);
+            b_row[i] = n < p.N ? p.B + static_cast<int64_t>(n) * p.ldb : nullptr;
+        }
+    } else {
+        b_row[0] = kn_n < p.N ? p.B + static_cast<int64_t>(k_begin + 8 * kn_kb) * p.ldb + kn_n : nullptr;
+        b_row[1] = nullptr;
+    }
+
+    auto load_step = [&](uint32_t k) {      // called for k_begin, k_begin + 64, ... in this order
+#pragma unroll
+        for (int i = 0; i < A_CHUNKS; ++i) {
+            a_regs[i] = u32x4{p.a_flip, p.a_flip, p.a_flip, p.a_flip};
+            if (a_row[i]) a_regs[i] = load_k16(a_row[i], k + (tid & 3) * 16, p.K, p.a_vec != 0, p.a_flip);
+        }
+        if constexpr (LAYOUT == OQ_QL_NK) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                b_regs[i] = u32x4{p.b_flip, p.b_flip, p.b_flip, p.b_flip};
+                if (b_row[i]) b_regs[i] = load_k16(b_row[i], k + (tid & 3) * 16, p.K, p.b_vec != 0, p.b_flip);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t kk = k + 8 * kn_kb + 4 * i + j;
+                    b_regs[i][j] = (kk < p.K && b_row[0]) ? load_n4(b_row[0] + (4 * i + j) * p.ldb, kn_n, p.N, p.b_vec != 0) : p.b_flip;
+                }
+            if (b_row[0]) b_row[0] += kBK * p.ldb;
+        }
+    };
+    auto store_step = [&]() {
+#pragma unroll
+        for (int i = 0; i < A_CHUNKS; ++i) {
+            const int id = tid + i * kThreads;
+            if (id < BM * 4) *reinterpret_cast<u32x4*>(lds + (id >> 2) * kRow + (id & 3) * 16) = a_regs[i] ^ u32x4{p.a_flip, p.a_flip, p.a_flip, p.a_flip};
+        }
+        if constexpr (LAYOUT == OQ_QL_NK) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int id = tid + i * kThreads;
+                *reinterpret_cast<u32x4*>(lds_b + (id >> 2) * kRow + (id & 3) * 16) = b_regs[i] ^ u32x4{p.b_flip, p.b_flip, p.b_flip, p.b_flip};
+            }
+        } else {
+            uint32_t c[2][4];      // r[j]: columns n .. n + 3 at k + j  ->  c[j]: k .. k + 3 of column n + j
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const uint32_t r0 = b_regs[i][0] ^ p.b_flip, r1 = b_regs[i][1] ^ p.b_flip, r2 = b_regs[i][2] ^ p.b_flip, r3 = b_regs[i][3] ^ p.b_flip;
+                const uint32_t t0 = __builtin_amdgcn_perm(r1, r0, 0x05010400u), t1 = __builtin_amdgcn_perm(r1, r0, 0x07030602u);
+                const uint32_t t2 = __builtin_amdgcn_perm(r3, r2, 0x05010400u), t3 = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
+                c[i][0] = __builtin_amdgcn_perm(t2, t0, 0x05040100u), c[i][1] = __builtin_amdgcn_perm(t2, t0, 0x07060302u);
+                c[i][2] = __builtin_amdgcn_perm(t3, t1, 0x05040100u), c[i][3] = __builtin_amdgcn_perm(t3, t1, 0x07060302u);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                *reinterpret_cast<u32x2*>(lds_b + (4 * kn_nb + ((j + (kn_nb >> 2)) & 3)) * kRow + 8 * kn_kb) = u32x2{c[0][j], c[1][j]};
+        }
+    };
+
+    i32x4 acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = i32x4{0, 0, 0, 0};
+
+    const unsigned char* const a_frag = lds + (wm * 16 * MT + (lane & 15)) * kRow + (lane >> 4) * 16;
+    const unsigned char* b_frag[NT];      // KN: the column's rotated row (store_step)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int c16 = lane & 15, row = LAYOUT == OQ_QL_NK ? c16 : (c16 & 12) | ((c16 + nt) & 3);
+        b_frag[nt] = lds_b + (wn * 64 + nt * 16 + row) * kRow + (lane >> 4) * 16;
+    }
+
+    if (k_begin < k_end) load_step(k_begin);
+    for (uint32_t k = k_begin; k < k_end; k += kBK) {
+        store_step();
+        __syncthreads();
+        if (k + kBK < k_end) load_step(k + kBK);
+        i32x4 b[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) b[nt] = *reinterpret_cast<const i32x4*>(b_frag[nt]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const i32x4 a = *reinterpret_cast<const i32x4*>(a_frag + mt * 16 * kRow);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b[nt], acc[mt][nt], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+
+    // C/D map of the 16x16 MFMAs: column = lane & 15, row = 4 (lane >> 4) + r
+    const uint32_t col = n0 + wn * 64 + (lane & 15);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const uint32_t n = col + 16 * nt;
+        if (n >= p.N) continue;
+        ColTerms c{};
+        if (!p.slab) c = col_terms(p, n);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const uint32_t m = m0 + wm * 16 * MT + mt * 16 + 4 * (lane >> 4) + r;
+                if (m < p.M) {
+                    const uint32_t S = static_cast<uint32_t>(acc[mt][nt][r]);
+                    if (p.slab) p.slab[(static_cast<int64_t>(blockIdx.y) * p.M + m) * p.N + n] = S;
+                    else finish(p, m, n, S, c);
+                }
+            }
+    }
+}
+
+// the slabs of a split K, added (uint32: any order gives the same bits), corrected and finished
+__global__ __launch_bounds__(kThreads) void ql_reduce_kernel(const QlArgs p, const int splits) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+    const int64_t count = static_cast<int64_t>(p.M) * p.N;
+    if (i >= count) return;
+    uint32_t S = p.slab[i];
+    for (int s = 1; s < splits; ++s) S += p.slab[s * count + i];
+    const uint32_t n = static_cast<uint32_t>(i % p.N);
+    finish(p, static_cast<uint32_t>(i / p.N), n, S, col_terms(p, n));
+}
+
+__device__ __forceinline__ int64_t ceil_div_dev(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// sums[r] = sum_k x'[r, k] of a [rows, K] matrix whose fast axis is k (A; B in NK): one wave per row.  x' = (x ^ ubias) - 128 as an
+// unsigned byte, ubias = 0x80 for a signed operand: v_sad_u8 adds the four bytes of a dword in one instruction.
+__global__ __launch_bounds__(kThreads) void ql_sum_rows_kernel(const uint8_t* X, int64_t rows, int64_t K, int64_t ld, uint32_t ubias, int32_t vec,
+                                                               int32_t* sums) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = static_cast<int64_t>(blockIdx.x) * (kThreads / kWave) + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const uint8_t* x = X + row * ld;
+    uint32_t s = 0u;
+    int64_t done = 0;
+    if (vec) {                                  // rows are 4-byte aligned
+        const int64_t K4 = K / 4;
+        for (int64_t i = lane; i < K4; i += kWave) s = __builtin_amdgcn_sad_u8(reinterpret_cast<const uint32_t*>(x)[i] ^ ubias, 0u, s);
+        done = K4 * 4;
+    }
+    for (int64_t k = done + lane; k < K; k += kWave) s += (static_cast<uint32_t>(x[k]) ^ ubias) & 0xFFu;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += static_cast<uint32_t>(__shfl_xor(static_cast<int>(s), off, 64));
+    if (lane == 0) sums[row] = static_cast<int32_t>(s - 128u * static_cast<uint32_t>(K));
+}
+
+// sums[y][n] = sum of x'[k, n] over slice y of K, of a [K, N] matrix whose fast axis is n (B in KN): a block takes 64 columns of
+// one slice, as 16 dwords x 16 phases of k
+__global__ __launch_bounds__(kThreads) void ql_sum_cols_kernel(const uint8_t* X, int64_t K, int64_t N, int64_t ld, uint32_t ubias, int32_t vec,
+                                                               int32_t* sums, int64_t stride) {
+    __shared__ uint32_t part[16][64];
+    const int cg = threadIdx.x & 15, ph = threadIdx.x >> 4;
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * 64 + 4 * cg;
+    uint32_t s[4] = {0u, 0u, 0u, 0u};
+    const int64_t per_slice = ceil_div_dev(K, gridDim.y), k_begin = min(K, blockIdx.y * per_slice), k_end = min(K, k_begin + per_slice);
+    if (n < N)
+        for (int64_t k = k_begin + ph; k < k_end; k += 16) {
+            const uint32_t w = load_n4(X + k * ld + n, static_cast<uint32_t>(n), static_cast<uint32_t>(N), vec != 0) ^ ubias;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) s[b] += (w >> (8 * b)) & 0xFFu;
+        }
+#pragma unroll
+    for (int b = 0; b < 4; ++b) part[ph][4 * cg + b] = s[b];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        uint32_t total = 0u;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) total += part[i][threadIdx.x];
+        const int64_t c = static_cast<int64_t>(blockIdx.x) * 64 + threadIdx.x;
+        if (c < N) sums[blockIdx.y * stride + c] = static_cast<int32_t>(total - 128u * static_cast<uint32_t>(k_end - k_begin));
+    }
+}
+
+// ---- host
+size_t r256(int64_t n) { return (static_cast<size_t>(n) + 255) / 256 * 256; }
+
+struct Plan {
+    int bm;
+    int64_t tiles_m, tiles, steps_per_split, splits;
+    size_t row_bytes, col_bytes, slab_bytes;
+    size_t total() const { return row_bytes + col_bytes + slab_bytes; }
+};
+
+bool shape_ok(int64_t M, int64_t K, int64_t N) {
+    return extent_ok(M) && extent_ok(K) && extent_ok(N) && count_ok(M * K) && count_ok(M * N) && count_ok(N * K);
+}
+
+Plan make_plan(int64_t M, int64_t K, int64_t N) {      // the plan of matmul_nbits.hip
+    Plan pl;
+    pl.bm = M <= 32 ? 32 : 128;
+    pl.tiles_m = ceil_div(M, pl.bm);
+    pl.tiles = pl.tiles_m * ceil_div(N, kBN);
+    const int64_t steps = ceil_div(K, kBK);
+    const int64_t want = pl.tiles >= 128 ? 1 : std::min<int64_t>(std::min<int64_t>(8, steps), 256 / pl.tiles);
+    pl.steps_per_split = ceil_div(steps, want);
+    pl.splits = ceil_div(steps, pl.steps_per_split);
+    pl.row_bytes = r256(M * 4);
+    pl.col_bytes = kColSlices * r256(N * 4);
+    pl.slab_bytes = pl.splits > 1 ? r256(pl.splits * M * N * 4) : 0;
+    return pl;
+}
+
+template <int LAYOUT>
+void launch_gemm(const QlArgs& p, const Plan& pl, hipStream_t s) {
+    const dim3 grid(static_cast<unsigned>(pl.tiles), static_cast<unsigned>(pl.splits));
+    if (pl.bm == 32) ql_gemm_kernel<1, LAYOUT><<<grid, kThreads, 0, s>>>(p);
+    else ql_gemm_kernel<4, LAYOUT><<<grid, kThreads, 0, s>>>(p);
+}
+
+bool type_ok(int32_t t) { return t == OQ_QL_U8 || t == OQ_QL_I8; }
+
+}  // namespace
+}  // namespace oq
+
+using namespace oq;
+
+extern "C" {
+
+int32_t oq_qlinear_extension_version(void) { return OQ_QLINEAR_EXTENSION_VERSION; }
+
+size_t oq_qlinear_matmul_workspace_bytes(int64_t M, int64_t K, int64_t N) {
+    if (!shape_ok(M, K, N)) {
+        set_error("oq_qlinear_matmul_workspace_bytes: M=%lld K=%lld N=%lld outside the bounds", (long long)M, (long long)K, (long long)N);
+        return 0;
+    }
+    return make_plan(M, K, N).total();
+}
+
+int32_t oq_qlinear_matmul(const void* A, int32_t a_type, int64_t M, int64_t K, int64_t lda, const float* a_scale, const void* a_zero_point,
+                          const void* B, int32_t b_type, int32_t b_layout, int64_t N, int64_t ldb, const float* b_scale, const void* b_zero_point,
+                          int32_t b_per_column, const int32_t* C, const float* y_scale, const void* y_zero_point, int32_t flags, int32_t out, void* Y,
+                          int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "oq_qlinear_matmul";
+    OQ_REQUIRE(A && B && Y, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (A, B and Y are required)", fn);
+    OQ_REQUIRE(type_ok(a_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown a_type %d", fn, a_type);
+    OQ_REQUIRE(type_ok(b_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_type %d", fn, b_type);
+    OQ_REQUIRE(b_layout == OQ_QL_KN || b_layout == OQ_QL_NK, OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_layout %d", fn, b_layout);
+    OQ_REQUIRE(out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 || out == OQ_QL_OUT_U8 || out == OQ_QL_OUT_I8, OQ_ERR_INVALID_ARGUMENT,
+               "%s: unknown out %d", fn, out);
+    OQ_REQUIRE((flags & ~(OQ_QL_PER_ROW_A | OQ_QL_TRANS_A | OQ_QL_ALPHA)) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: unknown flags %d", fn, flags);
+    OQ_REQUIRE(out == OQ_QL_OUT_I32 || (a_scale && b_scale), OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (a_scale and b_scale are required for out %d)",
+               fn, out);
+    OQ_REQUIRE((out != OQ_QL_OUT_U8 && out != OQ_QL_OUT_I8) || y_scale, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (y_scale is required for out %d)",
+               fn, out);
+    const bool kn = b_layout == OQ_QL_KN;
+    OQ_REQUIRE(extent_ok(M) && extent_ok(K) && extent_ok(N) && matrix_ok(M, K, lda) && matrix_ok(kn ? K : N, kn ? N : K, ldb) && matrix_ok(M, N, ldy),
+               OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld lda=%lld ldb=%lld ldy=%lld outside the bounds", fn, (long long)M, (long long)K,
+               (long long)N, (long long)lda, (long long)ldb, (long long)ldy);
+    OQ_REQUIRE(shape_ok(M, K, N), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld: an operand beyond 2^40 elements", fn, (long long)M,
+               (long long)K, (long long)N);
+    OQ_REQUIRE(!(flags & OQ_QL_PER_ROW_A), OQ_ERR_UNSUPPORTED, "%s: per-row a_scale / a_zero_point have no kernel", fn);
+    OQ_REQUIRE(!(flags & OQ_QL_TRANS_A), OQ_ERR_UNSUPPORTED, "%s: transA has no kernel", fn);
+    OQ_REQUIRE(!(flags & OQ_QL_ALPHA), OQ_ERR_UNSUPPORTED, "%s: alpha != 1 has no kernel", fn);
+    OQ_REQUIRE(aligned_to(a_scale, 4) && aligned_to(b_scale, 4) && aligned_to(y_scale, 4) && aligned_to(C, 4) &&
+                   aligned_to(Y, out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 ? 4 : 1),
+               OQ_ERR_INVALID_ARGUMENT, "%s: the scales, C and Y must be aligned to their element", fn);
+    const Plan pl = make_plan(M, K, N);
+    OQ_REQUIRE(workspace && workspace_bytes >= pl.total() && aligned_to(workspace, 256), OQ_ERR_WORKSPACE,
+               "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, pl.total(), workspace ? workspace_bytes : (size_t)0);
+
+    hipStream_t s = as_stream(stream);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    QlArgs p{};
+    p.A = static_cast<const uint8_t*>(A), p.B = static_cast<const uint8_t*>(B);
+    p.lda = lda, p.ldb = ldb;
+    p.a_signed = a_type == OQ_QL_I8, p.b_signed = b_type == OQ_QL_I8;
+    p.a_flip = p.a_signed ? 0u : 0x80808080u, p.b_flip = p.b_signed ? 0u : 0x80808080u;
+    p.a_vec = aligned_to(A, 16) && lda % 16 == 0;
+    p.b_vec = kn ? (aligned_to(B, 4) && ldb % 4 == 0) : (aligned_to(B, 16) && ldb % 16 == 0);
+    p.a_scale = a_scale, p.a_zp = a_zero_point, p.b_scale = b_scale, p.b_zp = b_zero_point, p.b_per_column = b_per_column != 0;
+    p.C = C, p.y_scale = y_scale, p.y_zp = y_zero_point, p.out = out, p.Y = Y, p.ldy = ldy;
+    p.M = static_cast<uint32_t>(M), p.N = static_cast<uint32_t>(N), p.K = static_cast<uint32_t>(K);
+    p.tiles_m = static_cast<uint32_t>(pl.tiles_m), p.steps_per_split = static_cast<uint32_t>(pl.steps_per_split);
+    // a sum is needed unless its multiplier -- the OTHER operand's shifted zero point -- is zero whatever the device holds
+    int32_t* rowsum = (p.b_signed && !b_zero_point) ? nullptr : reinterpret_cast<int32_t*>(ws);
+    int32_t* colsum = (p.a_signed && !a_zero_point) ? nullptr : reinterpret_cast<int32_t*>(ws + pl.row_bytes);
+    p.rowsum = rowsum, p.colsum = colsum;
+    p.colsum_slices = kn ? kColSlices : 1, p.colsum_stride = static_cast<uint32_t>(r256(N * 4) / 4);
+    p.slab = pl.splits > 1 ? reinterpret_cast<uint32_t*>(ws + pl.row_bytes + pl.col_bytes) : nullptr;
+
+    // the sums run over x ^ ubias read as an unsigned byte, minus 128: ubias flips a SIGNED operand
+    const uint32_t a_ubias = p.a_flip ^ 0x80808080u, b_ubias = p.b_flip ^ 0x80808080u;
+    constexpr int kRowsPerBlock = kThreads / kWave;
+    if (rowsum) {
+        ql_sum_rows_kernel<<<static_cast<unsigned>(ceil_div(M, kRowsPerBlock)), kThreads, 0, s>>>(p.A, M, K, lda, a_ubias,
+                                                                                                  aligned_to(A, 4) && lda % 4 == 0, rowsum);
+        const int32_t st = check_launch("ql_sum_rows_kernel");
+        if (st != OQ_OK) return st;
+    }
+    if (colsum) {
+        const int32_t vec4 = aligned_to(B, 4) && ldb % 4 == 0;
+        if (kn) ql_sum_cols_kernel<<<dim3(static_cast<unsigned>(ceil_div(N, 64)), kColSlices), kThreads, 0, s>>>(p.B, K, N, ldb, b_ubias, vec4, colsum, p.colsum_stride);
+        else ql_sum_rows_kernel<<<static_cast<unsigned>(ceil_div(N, kRowsPerBlock)), kThreads, 0, s>>>(p.B, N, K, ldb, b_ubias, vec4, colsum);
+        const int32_t st = check_launch(kn ? "ql_sum_cols_kernel" : "ql_sum_rows_kernel");
+        if (st != OQ_OK) return st;
+    }
+    if (kn) launch_gemm<OQ_QL_KN>(p, pl, s);
+    else launch_gemm<OQ_QL_NK>(p, pl, s);
+    const int32_t st = check_launch("ql_gemm_kernel");
+    if (st != OQ_OK || pl.splits == 1) return st;
+    ql_reduce_kernel<<<static_cast<unsigned>(ceil_div(M * N, kThreads)), kThreads, 0, s>>>(p, static_cast<int>(pl.splits));
+    return check_launch("ql_reduce_kernel");
+}
+
+}  // extern "C"

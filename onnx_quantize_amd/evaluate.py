@@ -43,7 +43,7 @@ def _as_model(model) -> Message:
 
 
 def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, extra_feeds=None, device="cuda",
-               matmul_nbits: str = "fused") -> float:
+               matmul_nbits: str = "fused", qlinear: str = "torch") -> float:
     """exp(mean negative log-likelihood) of ``input_ids`` (1-D integers) under the causal LM ``model`` (a path, bytes or a parsed
     ModelProto), over the sliding windows of `perplexity_windows`.
 
@@ -51,7 +51,11 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     ``position_ids`` (0 ... n - 1).  ``extra_feeds`` -- a dict, or a callable of the window length n returning one -- supplies
     every other declared input (empty past-key tensors, say); a declared input nobody feeds raises by name.  The logits are the
     output named ``logits``, or the model's single output; position t predicts token t + 1.  Log-softmax and the sum of the
-    negative log-likelihoods run in float64 on the device, and one scalar comes back to the host per call, not per window."""
+    negative log-likelihoods run in float64 on the device, and one scalar comes back to the host per call, not per window.
+
+    ``qlinear="fused"`` runs the QLinearMatMul / QGemm nodes of a `format="qlinear"` file on the int8 matrix cores
+    (`ops.qlinear_matmul`: exact int32 sums).  The default stays the expansion route: a fused output may differ from it by one
+    output level, where the expansion's fp32 sum lands on the other side of a rounding boundary."""
     import torch
 
     from .graph_runner import GraphRunner
@@ -69,7 +73,7 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
         wanted = outputs[0]
     else:
         raise ValueError(f"perplexity: the model has outputs {outputs}, none of them named 'logits'")
-    runner = GraphRunner(proto, outputs=[wanted], device=device, matmul_nbits=matmul_nbits)
+    runner = GraphRunner(proto, outputs=[wanted], device=device, matmul_nbits=matmul_nbits, qlinear=qlinear)
     if "input_ids" not in runner.input_names:
         raise ValueError(f"perplexity: the model declares no input 'input_ids' (inputs: {runner.input_names})")
     dev = runner.device

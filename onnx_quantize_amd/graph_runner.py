@@ -61,7 +61,7 @@ class GraphRunner:
     takes_sink = True        # `runner(feed, sink=...)` hands every wanted value over as it is produced (calibration_driver.run_calibration)
 
     def __init__(self, model: Message, outputs=None, device="cuda", capture: bool = False, matmul: str = "torch", constants=None,
-                 matmul_nbits: str = "torch"):
+                 matmul_nbits: str = "torch", qlinear: str = "torch"):
         """`constants`: {initializer name: tensor on the device} for initializers the caller already holds in HBM (a second
         calibration walk over the weights the first one uploaded; a weight that was rescaled on the device and whose TensorProto
         still has the old bytes): used as they are instead of the file's bytes when device, element type and shape fit."""
@@ -92,6 +92,13 @@ class GraphRunner:
             raise ValueError(f"GraphRunner: matmul_nbits must be 'torch' or 'fused', got {matmul_nbits!r}")
         self.matmul_nbits = matmul_nbits if self.device.type == "cuda" else "torch"
         self.nbits_calls = {"fused": 0, "torch": 0}      # MatMulNBits nodes run per route (a replayed graph counts its recording only)
+        # qlinear = "fused": a QLinearMatMul / QGemm node the library has a kernel for (`ops.qlinear_matmul`: 8-bit operands on the
+        # GPU, per-tensor activation parameters, fp32 scales, a constant 2-D B, alpha = 1, no transA) runs on the int8 matrix cores
+        # with an exact int32 sum -- no operand is dequantized.  Every other node, and every node under "torch", takes the expansion.
+        if qlinear not in ("torch", "fused"):
+            raise ValueError(f"GraphRunner: qlinear must be 'torch' or 'fused', got {qlinear!r}")
+        self.qlinear = qlinear if self.device.type == "cuda" else "torch"
+        self.qlinear_calls = {"fused": 0, "torch": 0}    # QLinearMatMul / QGemm nodes run per route (counted like nbits_calls)
         self.functions = {(f.domain or "", f.name, f.overload or ""): f for f in model.functions}
         self.opset = max([int(o.version or 1) for o in model.opset_import if not o.domain] or [1])
         self.wanted = list(outputs) if outputs is not None else [o.name for o in self.graph.output]
@@ -127,6 +134,7 @@ class GraphRunner:
         self.functions, self.opset, self.wanted, self.input_names, self.constants, self.nodes, self.last_use = {}, opset, [], [], {}, [], {}
         self.capture, self._graphs, self._seen, self._moved, self._const_nodes = False, {}, set(), {}, {}
         self.matmul_nbits, self.nbits_calls = "torch", {"fused": 0, "torch": 0}
+        self.qlinear, self.qlinear_calls = "torch", {"fused": 0, "torch": 0}
         return self
 
     def evaluate(self, node, arrays) -> list:
@@ -1193,6 +1201,11 @@ class GraphRunner:
 
     def _op_QLinearMatMul(self, n, x, a, e):
         import torch
+        if self.qlinear == "fused" and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False):
+            from .hip import ops
+            self.qlinear_calls["fused"] += 1
+            return ops.qlinear_matmul(*x[:8])
+        self.qlinear_calls["torch"] += 1
         A = (x[0].to(torch.float32) - x[2].to(torch.float32)) * x[1]
         bz = self._per_axis(x[5].to(torch.float32), x[3], x[3].ndim - 1)
         B = (x[3].to(torch.float32) - bz) * self._per_axis(x[4], x[3], x[3].ndim - 1)
@@ -1201,6 +1214,15 @@ class GraphRunner:
     def _op_QGemm(self, n, x, a, e):
         """com.microsoft::QGemm: A, a_scale, a_zp, B, b_scale, b_zp, C (int32, scale a_scale * b_scale), y_scale, y_zp."""
         import torch
+        bias = x[6] if len(x) > 6 else None
+        y_scale = x[7] if len(x) > 7 else None
+        y_zp = x[8] if len(x) > 8 else None
+        trans_b, alpha, trans_a = bool(a.get("transB", 0)), a.get("alpha", 1.0), bool(a.get("transA", 0))
+        if self.qlinear == "fused" and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b, alpha, trans_a):
+            from .hip import ops
+            self.qlinear_calls["fused"] += 1
+            return ops.qlinear_matmul(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias=bias, trans_b=trans_b)
+        self.qlinear_calls["torch"] += 1
         A = (x[0].to(torch.float32) - x[2].to(torch.float32)) * x[1]
         if a.get("transA", 0):
             A = A.t()
@@ -1272,6 +1294,22 @@ class GraphRunner:
             return False
         return (x[1].dtype == torch.uint8 and x[2].dtype in (torch.float32, x[0].dtype) and (zp is None or zp.dtype == torch.uint8)
                 and (bias is None or (bias.is_cuda and bias.dtype == x[0].dtype)))
+
+    def _qlinear_fusable(self, A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias, trans_b, alpha, trans_a) -> bool:
+        """Whether `ops.qlinear_matmul` takes this QLinearMatMul / QGemm node: A an 8-bit tensor on the GPU, every parameter a tensor
+        on the GPU, B, its parameters and C constants of the model, and nothing the kernel leaves out."""
+        import torch
+        from .hip import ops
+        if not (isinstance(A, torch.Tensor) and A.is_cuda and A.dtype in (torch.uint8, torch.int8) and A.ndim >= 1 and A.numel() > 0):
+            return False
+        every = (a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias)
+        if a_scale is None or B is None or b_scale is None or not all(t is None or (isinstance(t, torch.Tensor) and t.is_cuda) for t in every):
+            return False
+        held = list(self.constants.values())
+        if not all(t is None or any(t is c for c in held) for t in (B, b_scale, b_zp, bias)):
+            return False
+        return ops.qlinear_matmul_unsupported(A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias=bias, trans_b=trans_b, alpha=alpha,
+                                              trans_a=trans_a) is None
 
 
 _CAPTURE_MAX_INPUT_ELEMENTS = 1 << 20      # recording pays when a pass is hundreds of small launches (one short sequence), not above

@@ -1281,6 +1281,116 @@ def matmul_nbits(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero
     return out.reshape(*x.shape[:-1], N)
 
 
+# ----------------------------------------------------------------------------- QLinearMatMul / QGemm / MatMulInteger on the int8 matrix cores
+_QL_TYPE = {torch.uint8: L.OQ_QL_U8, torch.int8: L.OQ_QL_I8}
+_QL_OUT = {torch.int32: L.OQ_QL_OUT_I32, torch.float32: L.OQ_QL_OUT_F32, torch.uint8: L.OQ_QL_OUT_U8, torch.int8: L.OQ_QL_OUT_I8}
+
+
+def qlinear_matmul_unsupported(a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale=None, y_zero_point=None, *, bias=None,
+                               trans_b: bool = False, alpha: float = 1.0, trans_a: bool = False) -> str | None:
+    """Why `qlinear_matmul` has no kernel for such operands (include/oq_hip_qlinear.h, "left out"), or None when it has one.
+    The scales may be None (`matmul_integer`)."""
+    if trans_a:
+        return "transA"
+    if alpha != 1.0:
+        return f"alpha = {alpha} (only alpha = 1 has a kernel)"
+    if a.dtype not in _QL_TYPE or b.dtype not in _QL_TYPE:
+        return f"operands of {a.dtype} and {b.dtype} (uint8 and int8 have a kernel)"
+    if b.ndim != 2:
+        return f"a {b.ndim}-D b (a 2-D weight has a kernel)"
+    if a.ndim < 1 or a.shape[-1] != b.shape[1 if trans_b else 0]:
+        return f"shapes {tuple(a.shape)} and {tuple(b.shape)} do not meet (trans_b = {bool(trans_b)})"
+    n = b.shape[0 if trans_b else 1]
+    for name, s in (("a_scale", a_scale), ("b_scale", b_scale), ("y_scale", y_scale)):
+        if s is not None and s.dtype != torch.float32:
+            return f"{name} of {s.dtype} (scales that are not fp32 have no kernel)"
+    if (a_scale is not None and a_scale.numel() != 1) or (a_zero_point is not None and a_zero_point.numel() != 1):
+        return "a per-row a_scale / a_zero_point (activation parameters per tensor have a kernel)"
+    if b_scale is not None and b_scale.numel() not in (1, n):
+        return f"b_scale of {b_scale.numel()} values (1 or N = {n})"
+    if b_zero_point is not None and b_zero_point.numel() not in (1, n):
+        return f"b_zero_point of {b_zero_point.numel()} values (1 or N = {n})"
+    if b_scale is not None and b_zero_point is not None and b_scale.numel() != b_zero_point.numel() and 1 not in (b_scale.numel(), b_zero_point.numel()):
+        return "b_scale and b_zero_point of different lengths"
+    if (y_scale is not None and y_scale.numel() != 1) or (y_zero_point is not None and y_zero_point.numel() != 1):
+        return "a per-row or per-column y_scale / y_zero_point"
+    if a_zero_point is not None and a_zero_point.dtype != a.dtype:
+        return f"a_zero_point of {a_zero_point.dtype} for an a of {a.dtype}"
+    if b_zero_point is not None and b_zero_point.dtype != b.dtype:
+        return f"b_zero_point of {b_zero_point.dtype} for a b of {b.dtype}"
+    if y_zero_point is not None and y_zero_point.dtype not in _QL_TYPE:
+        return f"y_zero_point of {y_zero_point.dtype}"
+    if bias is not None and (bias.dtype != torch.int32 or bias.numel() != n):
+        return f"a bias of {bias.numel()} values of {bias.dtype} (int32 [N = {n}])"
+    return None
+
+
+def _qlinear_call(fn, a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias, trans_b, alpha, trans_a, out_dtype):
+    _require_device(a, "a")
+    _require_device(b, "b")
+    params = dict(a_scale=a_scale, a_zero_point=a_zero_point, b_scale=b_scale, b_zero_point=b_zero_point, y_scale=y_scale,
+                  y_zero_point=y_zero_point, bias=bias)
+    for name, t in params.items():
+        if t is not None:
+            _require_device(t, name)
+    why = qlinear_matmul_unsupported(a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias=bias, trans_b=trans_b,
+                                     alpha=alpha, trans_a=trans_a)
+    if why is not None:
+        raise NotImplementedError(f"{fn}: {why}")
+    k = a.shape[-1]
+    n = b.shape[0 if trans_b else 1]
+    a2 = a.reshape(-1, k)
+    if a2.shape[0] == 0:
+        return torch.zeros((*a.shape[:-1], n), dtype=out_dtype, device=a.device)
+    a2, lda = _row_major(a2)
+    b, ldb = _row_major(b)
+    m = a2.shape[0]
+    # one zero point for every column next to per-column scales (or the reverse): the library takes one flag for both
+    per_column = any(t is not None and t.numel() == n and n > 1 for t in (b_scale, b_zero_point))
+    if per_column:
+        if b_scale is not None and b_scale.numel() == 1:
+            b_scale = b_scale.reshape(1).expand(n)
+        if b_zero_point is not None and b_zero_point.numel() == 1:
+            b_zero_point = b_zero_point.reshape(1).expand(n)
+    a_scale, a_zero_point, b_scale, b_zero_point, y_scale, y_zero_point, bias = (
+        None if t is None else t.contiguous() for t in (a_scale, a_zero_point, b_scale, b_zero_point, y_scale, y_zero_point, bias))
+    out = torch.empty((m, n), dtype=out_dtype, device=a.device)
+    lib = L.load()
+    need = lib.oq_qlinear_matmul_workspace_bytes(m, k, n)
+    ws = _workspace(need, a.device)
+    L.check(lib.oq_qlinear_matmul(_ptr(a2), _QL_TYPE[a.dtype], m, k, lda, _ptr(a_scale), _ptr(a_zero_point), _ptr(b), _QL_TYPE[b.dtype],
+                                  L.OQ_QL_NK if trans_b else L.OQ_QL_KN, n, ldb, _ptr(b_scale), _ptr(b_zero_point), int(per_column), _ptr(bias),
+                                  _ptr(y_scale), _ptr(y_zero_point), 0, _QL_OUT[out_dtype], _ptr(out), n, _ptr(ws), need, _stream()))
+    return out.reshape(*a.shape[:-1], n)
+
+
+def qlinear_matmul(a: torch.Tensor, a_scale: torch.Tensor, a_zero_point: torch.Tensor | None, b: torch.Tensor, b_scale: torch.Tensor,
+                   b_zero_point: torch.Tensor | None, y_scale: torch.Tensor | None = None, y_zero_point: torch.Tensor | None = None, *,
+                   bias: torch.Tensor | None = None, trans_b: bool = False, alpha: float = 1.0, trans_a: bool = False) -> torch.Tensor:
+    """QLinearMatMul / com.microsoft::QGemm on the int8 matrix cores (`oq_qlinear_matmul`, csrc/qlinear_gemm.hip): ``a`` [..., K]
+    uint8 / int8 times ``b`` [K, N] (``trans_b``: [N, K]) uint8 / int8, each minus its zero point, summed exactly in int32, plus
+    ``bias`` (int32 [N], at scale a_scale * b_scale).  Every parameter is a tensor on the device: ``a_scale`` / ``a_zero_point``
+    per tensor, ``b_scale`` / ``b_zero_point`` per tensor or [N]; a zero point of None is 0.  With ``y_scale`` the result is
+    rint(fp32(acc) * fl(a_scale * b_scale) / y_scale) + y_zero_point, saturated, in ``y_zero_point``'s type (uint8 without one);
+    without ``y_scale`` it is the fp32 value fp32(acc) * fl(a_scale * b_scale).  No operand is ever dequantized in memory, and
+    nothing synchronises with the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out: per-row activation parameters, a ``b`` that is not
+    2-D, scales that are not fp32, ``alpha`` != 1, ``trans_a``."""
+    if a_scale is None or b_scale is None:
+        raise ValueError("qlinear_matmul: a_scale and b_scale are required (matmul_integer runs without scales)")
+    out_dtype = torch.float32 if y_scale is None else (torch.uint8 if y_zero_point is None else y_zero_point.dtype)
+    return _qlinear_call("qlinear_matmul", a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, None if y_scale is None else y_zero_point,
+                         bias, trans_b, alpha, trans_a, out_dtype)
+
+
+def matmul_integer(a: torch.Tensor, b: torch.Tensor, a_zero_point: torch.Tensor | None = None, b_zero_point: torch.Tensor | None = None, *,
+                   trans_b: bool = False) -> torch.Tensor:
+    """MatMulInteger: sum_k (a - a_zero_point) * (b - b_zero_point) as int32, exact (two's-complement wrap), on the int8 matrix
+    cores; operands and zero points as in `qlinear_matmul`."""
+    return _qlinear_call("matmul_integer", a, None, a_zero_point, b, None, b_zero_point, None, None, None, trans_b, 1.0, False, torch.int32)
+
+
 # ----------------------------------------------------------------------------- G1 - G4
 def hessian_accumulate(x: torch.Tensor, h: torch.Tensor, n_seen: int, method: str | None = None) -> int:
     """gptq.py:246-260, in place on ``h`` [K, K]; ``x`` [n_add, ..., K] fp32, fp16 or bf16.  Returns the new sample
