@@ -186,8 +186,9 @@ static int64_t stat_plan(const oq_abs_stats_item* items, int64_t count, StatPlan
     return -1;
 }
 
-static size_t stat_workspace_bytes(const StatPlan& p, int64_t count) {
-    return static_cast<size_t>(count) * static_cast<size_t>(p.slot) * 2 * sizeof(float) + 256;
+// the workspace (workspace.hpp): per item one slot of partial sums and one of partial maxima
+static float* stat_layout(const StatPlan& p, int64_t count, Workspace& ws) {
+    return ws.take<float>(static_cast<size_t>(count) * static_cast<size_t>(p.slot) * 2 * sizeof(float), 8);
 }
 
 }  // namespace oq
@@ -202,7 +203,9 @@ size_t oq_abs_stats_many_half_workspace_bytes(const oq_abs_stats_item* items_hos
         set_error("oq_abs_stats_many_half_workspace_bytes: bad table (count=%lld)", (long long)count);
         return 0;
     }
-    return stat_workspace_bytes(p, count);
+    Workspace ws;
+    stat_layout(p, count, ws);
+    return ws.total();
 }
 
 int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq_abs_stats_item* items_device, int64_t count, int32_t xtype,
@@ -229,9 +232,9 @@ int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq
     }
     StatPlan p;
     stat_plan(items_host, count, &p);
-    const size_t need = stat_workspace_bytes(p, count);
-    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE,
-               "oq_abs_stats_cols_many_h16: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+    Workspace ws(workspace, workspace_bytes);
+    float* const partial = stat_layout(p, count, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "oq_abs_stats_cols_many_h16: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
     // narrower loads while the table is too small to fill the device with waves at 8 columns per lane (a single 5120 x 640
     // tensor is 80 waves of them); the per-column sums do not depend on it
     const int cap = p.lanes8 >= kStatFillLanes ? 8 : (2 * p.lanes8 >= kStatFillLanes ? 4 : 2);
@@ -242,9 +245,6 @@ int32_t oq_abs_stats_cols_many_h16(const oq_abs_stats_item* items_host, const oq
         const int64_t blocks = ceil_div(it.K, static_cast<int64_t>(kStatBlock) * v) * stat_chunks(it.T);   // < 2^23 x 64
         if (blocks > grid_x) grid_x = blocks;
     }
-    char* base = static_cast<char*>(workspace);
-    base += (256 - reinterpret_cast<uintptr_t>(base) % 256) % 256;
-    float* partial = reinterpret_cast<float*>(base);
     const StatItem* table = count == 1 ? nullptr : reinterpret_cast<const StatItem*>(items_device);
     StatItem one;
     one.X = static_cast<const uint16_t*>(items_host[0].X);

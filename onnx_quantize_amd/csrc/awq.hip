@@ -569,17 +569,23 @@ static int64_t loss_stride(int64_t T, int64_t K, int64_t N) { return (loss_tiles
 // all candidates' partial sums -> their losses, one launch
 static int32_t finish_losses(const float* gemm_part, int n_cand, int64_t T, int64_t K, int64_t N, float* losses_out, hipStream_t s);
 
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 // Smallest group the searches take (the reference's own AWQ tests use 8, test/pre_passes/test_awq.py:68); the parameter
 // buffers of the workspace are sized for it.
 constexpr int kAwqMinGroup = 4;
 
+// A 2-byte W adds one buffer behind the fp32 layout of the workspace: the partial ranges of oq_rtn_quantize_h16 on the general clip
+// route, 2 floats x N per 64-row chunk of a group.  (K / g) ceil(g / 64) chunks, which is <= ceil(K / 64) + K / 257 for the groups of
+// more than 256 rows (and channel / tensor) that use them.  The largest grid of that call, ceil(N / 256) (K / 16 + K / g) blocks, stays
+// below 2^31 for every shape the entry points let through (K N <= 2^40, g >= 4).  R(K, N) of include/oq_hip_half.h, its `+ 256` included.
+static size_t half_rtn_bytes(int64_t K, int64_t N) {
+    return Workspace::padded(static_cast<size_t>(8) * N * (ceil_div(K, 64) + K / 257 + 1)) + Workspace::kAlign;
+}
+
 static int64_t diff_blocks(int64_t K, int64_t N) { return ceil_div(N, 256) * ceil_div(K, 8); }
 
-static size_t awq_workspace(int64_t T, int64_t K, int64_t N, AwqWs* w, char* base) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
+// The workspace of a search, measured and carved by this one function (workspace.hpp); `half`: with the buffer of the _h16 entry points.
+static void awq_workspace(int64_t T, int64_t K, int64_t N, bool half, AwqWs* w, Workspace& ws) {
+    auto take = [&ws](size_t bytes) { return ws.take(bytes); };
     const bool gram = awq_use_gram(T, K);
     char* px = take(gram ? 0 : gemm_f16x3_pieces_bytes(K, T));
     char* pd = take(gemm_f16x3_pieces_bytes(K, N));
@@ -605,6 +611,8 @@ static size_t awq_workspace(int64_t T, int64_t K, int64_t N, AwqWs* w, char* bas
     const size_t rtn_bytes = oq_rtn_workspace_bytes(K, N, OQ_GROUP, kAwqMinGroup, 0) + oq_rtn_workspace_bytes(K, N, OQ_GROUP, 16, 0) +
                              oq_rtn_workspace_bytes(K, N, OQ_TENSOR, -1, 0) + 1024;
     char* rtn = take(rtn_bytes);
+    const size_t rtn_half_bytes = half ? half_rtn_bytes(K, N) : 0;
+    char* rtn_half = take(rtn_half_bytes);
     if (w) {
         w->pieces_x = px; w->pieces_d = pd; w->Ws = reinterpret_cast<float*>(Ws); w->D = reinterpret_cast<float*>(D);
         w->q = reinterpret_cast<uint8_t*>(q); w->qscale = reinterpret_cast<float*>(qs); w->qzp = reinterpret_cast<uint8_t*>(qz);
@@ -612,10 +620,9 @@ static size_t awq_workspace(int64_t T, int64_t K, int64_t N, AwqWs* w, char* bas
         w->colpart = reinterpret_cast<float*>(colpart); w->gemm_part = reinterpret_cast<float*>(gpart); w->diff_part = reinterpret_cast<float*>(dpart);
         w->rowmax = reinterpret_cast<float*>(rmax); w->bounds = reinterpret_cast<float*>(bnd); w->triples = reinterpret_cast<float*>(trp);
         w->rtn_ws = rtn; w->rtn_ws_bytes = rtn_bytes;
-        w->rtn_half_ws = nullptr; w->rtn_half_ws_bytes = 0;
+        w->rtn_half_ws = rtn_half; w->rtn_half_ws_bytes = rtn_half_bytes;
         w->gram = gram; w->G = reinterpret_cast<float*>(G); w->pieces_g = pg; w->hess_ws = hws; w->hess_ws_bytes = hess_bytes;
     }
-    return off + 256;
 }
 
 static int32_t param_index(int32_t strategy, int64_t K, int64_t g, ParamIndex* pi) {
@@ -752,19 +759,18 @@ static int32_t check_common(const float* X, int64_t T, int64_t K, int64_t ldx, c
     return OQ_OK;
 }
 
-// ---- A 2-byte W adds one buffer behind the fp32 layout of the workspace: the partial ranges of
-// oq_rtn_quantize_h16 on the general clip route, 2 floats x N per 64-row chunk of a group.  (K / g) ceil(g / 64) chunks, which is
-// <= ceil(K / 64) + K / 257 for the groups of more than 256 rows (and channel / tensor) that use them.  The largest grid of that call,
-// ceil(N / 256) (K / 16 + K / g) blocks, stays below 2^31 for every shape the checks above let through (K N <= 2^40, g >= 4).
-static size_t half_rtn_bytes(int64_t K, int64_t N) { return align256(static_cast<size_t>(8) * N * (ceil_div(K, 64) + K / 257 + 1)) + 256; }
-
+// carves the caller's workspace, which the entry points want 256-byte aligned; false: it does not hold the layout (no pointer is used then)
 template <typename E>
-static void carve(int64_t T, int64_t K, int64_t N, AwqWs* w, void* workspace) {
-    const size_t fp32_bytes = awq_workspace(T, K, N, w, static_cast<char*>(workspace));
-    if constexpr (kTwoByteElem<E>) {
-        w->rtn_half_ws = static_cast<char*>(workspace) + fp32_bytes;     // a multiple of 256 behind a 256-byte aligned base
-        w->rtn_half_ws_bytes = half_rtn_bytes(K, N);
-    }
+static bool carve(int64_t T, int64_t K, int64_t N, AwqWs* w, void* workspace, size_t workspace_bytes) {
+    Workspace ws(workspace, workspace_bytes, /* aligned_base */ true);
+    awq_workspace(T, K, N, kTwoByteElem<E>, w, ws);
+    return ws.fits();
+}
+
+static size_t awq_workspace_bytes(int64_t T, int64_t K, int64_t N, bool half) {
+    Workspace ws(/* aligned_base */ true);
+    awq_workspace(T, K, N, half, nullptr, ws);
+    return ws.total();
 }
 
 // oq_awq_scale_search_f32 / _h16: one implementation, `fn` is the entry point's name in the messages.  Every check stands in front of
@@ -779,11 +785,10 @@ static int32_t awq_scale_search(const char* fn, const float* X, int64_t T, int64
     if (st != OQ_OK) return st;
     OQ_REQUIRE(scales_out && losses_out && best_out && n_grid >= 1 && n_grid <= kAwqMaxGrid, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
     const size_t need = kTwoByteElem<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
-    OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
+    AwqWs w;
+    OQ_REQUIRE(need != 0 && carve<E>(T, K, N, &w, workspace, workspace_bytes), OQ_ERR_WORKSPACE,
                "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
     hipStream_t s = as_stream(stream);
-    AwqWs w;
-    carve<E>(T, K, N, &w, workspace);
     // awq.py:47-50: mean |x| per input channel
     const dim3 cgrid(static_cast<uint32_t>(ceil_div(K, 256)), static_cast<uint32_t>(T < kColChunks ? T : kColChunks));
     hipLaunchKernelGGL(col_abs_partial_kernel<false>, cgrid, dim3(256), 0, s, X, T, K, ldx, w.colpart);
@@ -823,11 +828,10 @@ static int32_t awq_clip_search(const char* fn, const float* X, int64_t T, int64_
     if (st != OQ_OK) return st;
     OQ_REQUIRE(losses_out && best_out, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
     const size_t need = kTwoByteElem<E> ? oq_awq_half_workspace_bytes(T, K, N) : oq_awq_workspace_bytes(T, K, N);
-    OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
+    AwqWs w;
+    OQ_REQUIRE(need != 0 && carve<E>(T, K, N, &w, workspace, workspace_bytes), OQ_ERR_WORKSPACE,
                "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
     hipStream_t s = as_stream(stream);
-    AwqWs w;
-    carve<E>(T, K, N, &w, workspace);
     st = prepare_activations(w, X, T, K, ldx, stream, s);
     if (st != OQ_OK) return st;
     if (pieces_route(w, K) && group_fused<E>(strategy, g, K, N, ldw, W)) {
@@ -868,9 +872,8 @@ static int32_t stats_begin(const float* act_sum, const float* G, int64_t T, int6
     }
     OQ_REQUIRE(ceil_div(K, 8) <= 65535 && K <= 65535 && ceil_div(K, *g) <= 65535, OQ_ERR_UNSUPPORTED, "awq: K too large");
     const size_t need = kTwoByteElem<E> ? oq_awq_stats_half_workspace_bytes(K, N) : oq_awq_stats_workspace_bytes(K, N);
-    OQ_REQUIRE(need != 0 && workspace && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, OQ_ERR_WORKSPACE,
+    OQ_REQUIRE(need != 0 && carve<E>(stats_rows(K), K, N, w, workspace, workspace_bytes), OQ_ERR_WORKSPACE,
                "%s: 256-byte aligned workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
-    carve<E>(stats_rows(K), K, N, w, workspace);
     OQ_REQUIRE(w->gram, OQ_ERR_LAUNCH, "%s: the Gram layout was not selected", who);
     OQ_REQUIRE(hipMemcpyAsync(w->G, G, static_cast<size_t>(K) * K * 4, hipMemcpyDeviceToDevice, s) == hipSuccess, OQ_ERR_LAUNCH, "%s: copy of G failed", who);
     if (act_sum != nullptr)   // awq.py:47-50: mean |x| per input channel
@@ -930,19 +933,36 @@ static int32_t awq_clip_search_stats(const char* fn, const float* G, int64_t T, 
     return check_launch("argmin_first_kernel");
 }
 
+// The workspace of the column statistics (workspace.hpp): the partial sums or maxima of every column chunk, and for SmoothQuant the
+// folded activation maxima and the row maxima of W.
+struct SmoothWs {
+    float *colpart, *act, *wmax;
+};
+static SmoothWs smooth_layout(int64_t K, bool smooth_quant, Workspace& ws) {
+    SmoothWs w{};
+    w.colpart = ws.take<float>(static_cast<size_t>(kColChunks) * K * 4);
+    if (smooth_quant) {
+        w.act = ws.take<float>(static_cast<size_t>(K) * 4);
+        w.wmax = ws.take<float>(static_cast<size_t>(K) * 4);
+    }
+    return w;
+}
+static size_t smooth_workspace_bytes(int64_t K, bool smooth_quant) {
+    Workspace ws;
+    smooth_layout(K, smooth_quant, ws);
+    return ws.total();
+}
+
 template <typename E>
 static int32_t smooth_quant_scale(const char* fn, const float* X, int64_t T, int64_t K, int64_t ldx, const void* Wv, int64_t N, int64_t ldw, float alpha,
                                   float* scale_out, void* workspace, size_t workspace_bytes, void* stream) {
     const typename E::raw* W = static_cast<const typename E::raw*>(Wv);
     OQ_REQUIRE(X && W && scale_out && matrix_ok(T, K, ldx) && matrix_ok(K, N, ldw), OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", fn);
-    const size_t need = align256(static_cast<size_t>(kColChunks) * K * 4) + 2 * align256(static_cast<size_t>(K) * 4) + 256;
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", fn, need, workspace_bytes);
+    Workspace ws(workspace, workspace_bytes);
+    const SmoothWs sw = smooth_layout(K, true, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", fn, ws.total(), workspace_bytes);
     hipStream_t s = as_stream(stream);
-    char* base = static_cast<char*>(workspace);
-    base += (256 - reinterpret_cast<uintptr_t>(base) % 256) % 256;
-    float* colpart = reinterpret_cast<float*>(base);
-    float* act = reinterpret_cast<float*>(base + align256(static_cast<size_t>(kColChunks) * K * 4));
-    float* wmax = act + align256(static_cast<size_t>(K) * 4) / 4;
+    float *const colpart = sw.colpart, *const act = sw.act, *const wmax = sw.wmax;
     const dim3 cgrid(static_cast<uint32_t>(ceil_div(K, 256)), static_cast<uint32_t>(T < kColChunks ? T : kColChunks));
     hipLaunchKernelGGL(col_abs_partial_kernel<true>, cgrid, dim3(256), 0, s, X, T, K, ldx, colpart);                 // smooth_quant.py:62-69
     hipLaunchKernelGGL(col_abs_finish_kernel<true>, dim3(cgrid.x), dim3(256), 0, s, colpart, static_cast<int>(cgrid.y), K, 1.0f, act);
@@ -960,12 +980,11 @@ using namespace oq;
 
 size_t oq_awq_workspace_bytes(int64_t T, int64_t K, int64_t N) {
     if (!oq::matrix_ok(T, K, K) || !oq::matrix_ok(K, N, N) || K > 65535) return 0;
-    return awq_workspace(T, K, N, nullptr, nullptr);
+    return awq_workspace_bytes(T, K, N, false);
 }
 
 size_t oq_awq_half_workspace_bytes(int64_t T, int64_t K, int64_t N) {
-    const size_t fp32_bytes = oq_awq_workspace_bytes(T, K, N);
-    return fp32_bytes == 0 ? 0 : fp32_bytes + oq::half_rtn_bytes(K, N);
+    return oq_awq_workspace_bytes(T, K, N) == 0 ? 0 : awq_workspace_bytes(T, K, N, true);
 }
 
 int32_t oq_awq_scale_search_f32(const float* X, int64_t T, int64_t K, int64_t ldx, const float* W, int64_t N, int64_t ldw, int32_t qtype,
@@ -1008,12 +1027,11 @@ int32_t oq_awq_clip_search_h16(const float* X, int64_t T, int64_t K, int64_t ldx
 
 size_t oq_awq_stats_workspace_bytes(int64_t K, int64_t N) {
     if (!oq::matrix_ok(K, N, N) || K > 65535 || !oq::extent_ok(stats_rows(K))) return 0;
-    return awq_workspace(stats_rows(K), K, N, nullptr, nullptr);
+    return awq_workspace_bytes(stats_rows(K), K, N, false);
 }
 
 size_t oq_awq_stats_half_workspace_bytes(int64_t K, int64_t N) {
-    const size_t fp32_bytes = oq_awq_stats_workspace_bytes(K, N);
-    return fp32_bytes == 0 ? 0 : fp32_bytes + oq::half_rtn_bytes(K, N);
+    return oq_awq_stats_workspace_bytes(K, N) == 0 ? 0 : awq_workspace_bytes(stats_rows(K), K, N, true);
 }
 
 int32_t oq_awq_scale_search_stats_f32(const float* act_sum, const float* G, int64_t T, int64_t K, const float* W, int64_t N, int64_t ldw, int32_t qtype,
@@ -1057,18 +1075,16 @@ int32_t oq_awq_clip_search_stats_h16(const float* G, int64_t T, int64_t K, const
 // sum over the T rows of |x[t, k]| added to `sum_inout` [K] (a running statistic over calibration batches; awq.py:47-50 divides by T)
 size_t oq_abs_sum_cols_workspace_bytes(int64_t K) {
     if (!oq::extent_ok(K)) return 0;
-    return oq::align256(static_cast<size_t>(oq::kColChunks) * K * 4) + 512;
+    return oq::smooth_workspace_bytes(K, false);
 }
 
 int32_t oq_abs_sum_cols_f32(const float* X, int64_t T, int64_t K, int64_t ldx, float* sum_inout, int32_t accumulate, void* workspace,
                             size_t workspace_bytes, void* stream) {
     OQ_REQUIRE(X && sum_inout && matrix_ok(T, K, ldx), OQ_ERR_INVALID_ARGUMENT, "oq_abs_sum_cols_f32: bad argument");
-    const size_t need = oq_abs_sum_cols_workspace_bytes(K);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_abs_sum_cols_f32: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
+    Workspace ws(workspace, workspace_bytes);
+    float* const colpart = smooth_layout(K, false, ws).colpart;
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "oq_abs_sum_cols_f32: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
     hipStream_t s = as_stream(stream);
-    char* base = static_cast<char*>(workspace);
-    base += (256 - reinterpret_cast<uintptr_t>(base) % 256) % 256;
-    float* colpart = reinterpret_cast<float*>(base);
     const dim3 cgrid(static_cast<uint32_t>(ceil_div(K, 256)), static_cast<uint32_t>(T < kColChunks ? T : kColChunks));
     hipLaunchKernelGGL(col_abs_partial_kernel<false>, cgrid, dim3(256), 0, s, X, T, K, ldx, colpart);
     hipLaunchKernelGGL(col_abs_accumulate_kernel, dim3(cgrid.x), dim3(256), 0, s, colpart, static_cast<int>(cgrid.y), K, accumulate, sum_inout);
@@ -1092,7 +1108,7 @@ int32_t oq_smooth_quant_scale_h16(const float* X, int64_t T, int64_t K, int64_t 
 
 size_t oq_smooth_quant_workspace_bytes(int64_t K) {
     if (!oq::extent_ok(K)) return 0;
-    return oq::align256(static_cast<size_t>(oq::kColChunks) * K * 4) + 2 * oq::align256(static_cast<size_t>(K) * 4) + 512;
+    return oq::smooth_workspace_bytes(K, true);
 }
 
 }  // extern "C"

@@ -290,32 +290,45 @@ __global__ void finish_factor_kernel(const float* X, int64_t K, const int32_t* i
     }
 }
 
-static size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace oq
 
 extern "C" {
 
 using namespace oq;
 
+// actorder: the permuted copies of W and H (workspace.hpp); nothing without it
+struct PrepareWs {
+    float *Wt, *Ht;
+};
+static PrepareWs prepare_layout(int64_t K, int64_t N, int32_t actorder, Workspace& ws) {
+    PrepareWs w{};
+    if (!actorder) return w;
+    w.Wt = ws.take<float>(static_cast<size_t>(K) * N * 4);
+    w.Ht = ws.take<float>(static_cast<size_t>(K) * K * 4);
+    return w;
+}
+
 size_t oq_gptq_prepare_workspace_bytes(int64_t K, int64_t N, int32_t actorder) {
-    if (!actorder || !matrix_ok(K, N, N) || K > kMaxHessianWidth) return 256;
-    return align256(static_cast<size_t>(K) * N * 4) + align256(static_cast<size_t>(K) * K * 4) + 256;
+    Workspace ws;
+    if (matrix_ok(K, N, N) && K <= kMaxHessianWidth) prepare_layout(K, N, actorder, ws);
+    return ws.total();
 }
 
 int32_t oq_gptq_prepare_f32(float* W, int64_t K, int64_t N, float* H, int32_t actorder, int32_t* perm_out, void* workspace,
                             size_t workspace_bytes, void* stream) {
     OQ_REQUIRE(W && H && matrix_ok(K, N, N) && K <= kMaxHessianWidth, OQ_ERR_INVALID_ARGUMENT, "oq_gptq_prepare_f32: bad argument");
+    Workspace ws(workspace, workspace_bytes);
+    const PrepareWs pw = prepare_layout(K, N, actorder, ws);
+    if (actorder) {      // every check in front of the first launch: a refused call leaves W and H as they were
+        OQ_REQUIRE(perm_out, OQ_ERR_INVALID_ARGUMENT, "oq_gptq_prepare_f32: actorder needs perm_out");
+        OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "oq_gptq_prepare_f32: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
+    }
     hipStream_t s = as_stream(stream);
     hipLaunchKernelGGL(dead_channels_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, K, N, H);
     int32_t st = check_launch("dead_channels_kernel");
     if (st != OQ_OK || !actorder) return st;
-    OQ_REQUIRE(perm_out, OQ_ERR_INVALID_ARGUMENT, "oq_gptq_prepare_f32: actorder needs perm_out");
-    const size_t need = oq_gptq_prepare_workspace_bytes(K, N, 1);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_gptq_prepare_f32: workspace of %zu bytes needed, %zu given",
-               need, workspace_bytes);
-    float* Wt = static_cast<float*>(workspace);
-    float* Ht = reinterpret_cast<float*>(static_cast<char*>(workspace) + align256(static_cast<size_t>(K) * N * 4));
+    float* const Wt = pw.Wt;
+    float* const Ht = pw.Ht;
     hipLaunchKernelGGL(rank_desc_kernel, dim3(static_cast<uint32_t>(ceil_div(K, 256))), dim3(256), 0, s, H, K, perm_out);
     hipLaunchKernelGGL(gather_rows_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, W, N, perm_out, Wt);
     hipLaunchKernelGGL(gather_sym_kernel, dim3(static_cast<uint32_t>(K)), dim3(256), 0, s, H, K, perm_out, Ht);
@@ -330,8 +343,8 @@ int32_t oq_gptq_prepare_f32(float* W, int64_t K, int64_t N, float* H, int32_t ac
 // Workspace of a batch: [P x count][Lt x count][X x count][Y x count][Dinv x count] -- P is reversed, damped and factored in
 // place (later the S scratch of the inverse), Y = X^T, Dinv the inverted diagonal blocks.  One region per role, so the
 // matrices of a role are a strided batch (stride kk) and X, Y are cleared by one memset.
-static size_t factor_matrix_bytes(int64_t K) { return align256(static_cast<size_t>(K) * K * 4); }
-static size_t factor_dinv_bytes(int64_t K) { return align256(static_cast<size_t>(ceil_div(K, kNB)) * kNB * kNB * 4); }
+static size_t factor_matrix_bytes(int64_t K) { return Workspace::padded(static_cast<size_t>(K) * K * 4); }
+static size_t factor_dinv_bytes(int64_t K) { return Workspace::padded(static_cast<size_t>(ceil_div(K, kNB)) * kNB * kNB * 4); }
 
 // levels of the recursive-doubling inverse from this block size on run on the fp16-piece kernels (section 3b of syrk_bf16x3.hip)
 constexpr int64_t kPieceInverseMin = 2048;
@@ -345,12 +358,32 @@ static size_t inverse_pieces_bytes(int64_t K, int64_t count) {
         if (full > 0) most = std::max(most, inverse_level_f16x3_bytes(b, b, full * count));
         if (npairs > full) most = std::max(most, inverse_level_f16x3_bytes(b, K - (full * 2 * b + b), (npairs - full) * count));
     }
-    return most ? most + 256 : 0;
+    return most;
+}
+
+struct FactorWs {
+    float *P, *Lt, *X, *Y, *Dinv;
+    unsigned char* inv_pieces;
+    size_t inv_pieces_bytes;
+};
+static FactorWs factor_layout(int64_t K, int64_t count, Workspace& ws) {
+    const size_t role = static_cast<size_t>(count) * factor_matrix_bytes(K);
+    FactorWs w;
+    w.P = ws.take<float>(role);
+    w.Lt = ws.take<float>(role);
+    w.X = ws.take<float>(role);       // X and Y follow one another: one memset clears both
+    w.Y = ws.take<float>(role);
+    w.Dinv = ws.take<float>(static_cast<size_t>(count) * factor_dinv_bytes(K));
+    w.inv_pieces_bytes = inverse_pieces_bytes(K, count);
+    w.inv_pieces = ws.take<unsigned char>(w.inv_pieces_bytes);
+    return w;
 }
 
 size_t oq_gptq_factor_batched_workspace_bytes(int64_t K, int64_t count) {
     if (K <= 0 || K > kMaxHessianWidth || count <= 0 || count > 65535) return 0;
-    return static_cast<size_t>(count) * (4 * factor_matrix_bytes(K) + factor_dinv_bytes(K)) + inverse_pieces_bytes(K, count) + 256;
+    Workspace ws;
+    factor_layout(K, count, ws);
+    return ws.total();
 }
 
 size_t oq_gptq_factor_workspace_bytes(int64_t K) { return oq_gptq_factor_batched_workspace_bytes(K, 1); }
@@ -364,21 +397,17 @@ static int32_t factor_batched(const float* H, int64_t K, int64_t h_stride, int64
     OQ_REQUIRE(method >= OQ_HESSIAN_AUTO && method <= OQ_HESSIAN_F16X3, OQ_ERR_INVALID_ARGUMENT, "%s: unknown method %d", who, method);
     OQ_REQUIRE(H && U_out && info && K > 0 && K <= kMaxHessianWidth && count > 0 && count <= 65535, OQ_ERR_INVALID_ARGUMENT, "%s: bad argument", who);
     OQ_REQUIRE(count == 1 || (h_stride >= K * K && u_stride >= K * K), OQ_ERR_INVALID_ARGUMENT, "%s: matrices of the batch overlap", who);
-    const size_t need = oq_gptq_factor_batched_workspace_bytes(K, count);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, need, workspace_bytes);
+    Workspace ws(workspace, workspace_bytes);
+    const FactorWs fw = factor_layout(K, count, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "%s: workspace of %zu bytes needed, %zu given", who, ws.total(), workspace_bytes);
     const size_t kk = factor_matrix_bytes(K);
     const int64_t ms = static_cast<int64_t>(kk / 4);                      // floats between the matrices of one role
     const int64_t ds = static_cast<int64_t>(factor_dinv_bytes(K) / 4);
     const int64_t nb = ceil_div(K, kNB);
     const uint32_t cnt = static_cast<uint32_t>(count);
-    char* base = static_cast<char*>(workspace);
-    float* P = reinterpret_cast<float*>(base);
-    float* Lt = reinterpret_cast<float*>(base + count * kk);
-    float* X = reinterpret_cast<float*>(base + 2 * count * kk);
-    float* Y = reinterpret_cast<float*>(base + 3 * count * kk);
-    float* Dinv = reinterpret_cast<float*>(base + 4 * count * kk);
-    unsigned char* inv_pieces = reinterpret_cast<unsigned char*>(base + 4 * count * kk + static_cast<size_t>(count) * factor_dinv_bytes(K));
-    const size_t inv_pieces_bytes = inverse_pieces_bytes(K, count);
+    float *const P = fw.P, *const Lt = fw.Lt, *const X = fw.X, *const Y = fw.Y, *const Dinv = fw.Dinv;
+    unsigned char* const inv_pieces = fw.inv_pieces;
+    const size_t inv_pieces_bytes = fw.inv_pieces_bytes;
     float* S = P;   // P is dead once the Cholesky loop has finished
 
     if (hipMemsetAsync(info, 0, sizeof(int32_t) * count, s) != hipSuccess) return fail(OQ_ERR_LAUNCH, "%s: memset failed", who);

@@ -3,6 +3,7 @@
 
 #include "half_elem.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -374,9 +375,8 @@ static size_t hessian_slab_budget(int64_t K) { return (K <= 0 || K > kMaxHessian
 
 size_t oq_hessian_workspace_bytes(int64_t T, int64_t K) {
     if (!matrix_ok(T, K, K) || K > kMaxHessianWidth) return 256;
-    const size_t f32 = K <= 8192 ? syrk_slab_bytes(T, K) : 0;
-    const size_t split = syrk_bf16x3_pieces_bytes(T, K) + hessian_slab_budget(K);
-    return (f32 > split ? f32 : split) + 512;
+    const size_t f32 = K <= 8192 ? syrk_slab_bytes(T, K) : 0;      // the fp32 kernel's slabs lie at the caller's pointer: one array
+    return std::max(f32, syrk_bf16x3_workspace_bytes(T, K, hessian_slab_budget(K)));
 }
 
 int32_t oq_hessian_accumulate_f32(const float* X, int64_t T, int64_t K, int64_t ldx, int64_t n_seen, int64_t n_add, float* H,
@@ -394,7 +394,7 @@ int32_t oq_hessian_accumulate_f32(const float* X, int64_t T, int64_t K, int64_t 
     // auto: the split-operand kernels where their 256-wide tiles are worth it and the caller's workspace holds the
     // pieces; small problems stay on the fp32 MFMA
     if (method == OQ_HESSIAN_AUTO)
-        method = (K >= 1024 && (T >= 2048 || K >= 2048) && workspace != nullptr && workspace_bytes >= syrk_bf16x3_pieces_bytes(T, K) + 256)
+        method = (K >= 1024 && (T >= 2048 || K >= 2048) && workspace != nullptr && workspace_bytes >= syrk_bf16x3_workspace_bytes(T, K, 0))
                      ? OQ_HESSIAN_F16X3 : OQ_HESSIAN_F32;   // measured cross-over: K = 1024-1536 with ~1000 rows is faster on the fp32 kernel
     if (method != OQ_HESSIAN_F32) {
         // gptq.py:257 scales the operand by sqrt(2 / n); here the factor 2 / n goes onto the sum (one rounding per
@@ -414,7 +414,7 @@ size_t oq_hessian_half_workspace_bytes(int64_t T, int64_t K) {
         set_error("oq_hessian_half_workspace_bytes: bad shape T=%lld K=%lld", (long long)T, (long long)K);
         return 0;
     }
-    return syrk_h16_pieces_bytes(T, K) + hessian_slab_budget(K) + 512;
+    return syrk_h16_workspace_bytes(T, K, hessian_slab_budget(K)) + 256;      // + 256: the header's formula (oq_hip_half.h), kept to the byte
 }
 
 int32_t oq_hessian_accumulate_h16(const void* X, int32_t xtype, int64_t T, int64_t K, int64_t ldx, int64_t n_seen, int64_t n_add, float* H,
@@ -471,13 +471,13 @@ int32_t oq_hessian_accumulate_many_f32(const oq_hessian_item* items_host, const 
 
 // G1 in two halves (fp16-piece method): the HBM-bound preparation of a batch and its matrix-core bound product, so that a
 // caller can run the preparation of batch i + 1 on a side stream while the product of batch i occupies the matrix cores.
-size_t oq_hessian_pieces_bytes(int64_t T, int64_t K) { return (!matrix_ok(T, K, K) || K > kMaxHessianWidth) ? 0 : syrk_bf16x3_pieces_bytes(T, K) + 256; }
+size_t oq_hessian_pieces_bytes(int64_t T, int64_t K) { return (!matrix_ok(T, K, K) || K > kMaxHessianWidth) ? 0 : syrk_bf16x3_workspace_bytes(T, K, 0); }
 size_t oq_hessian_slab_bytes(int64_t K) { return hessian_slab_budget(K) + 256; }
 
 int32_t oq_hessian_prepare_f32(const float* X, int64_t T, int64_t K, int64_t ldx, int64_t n_total, void* pieces, size_t pieces_bytes, void* stream) {
     OQ_REQUIRE(X && pieces && matrix_ok(T, K, ldx) && K <= kMaxHessianWidth && n_total > 0 && n_total <= 2 * kMaxSamples, OQ_ERR_INVALID_ARGUMENT,
                "oq_hessian_prepare_f32: bad argument");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(pieces) & 255u) == 0 && pieces_bytes >= syrk_bf16x3_pieces_bytes(T, K), OQ_ERR_WORKSPACE,
+    OQ_REQUIRE(aligned_to(pieces, 256) && pieces_bytes >= syrk_bf16x3_pieces_bytes(T, K), OQ_ERR_WORKSPACE,
                "oq_hessian_prepare_f32: 256-byte aligned buffer of %zu bytes needed, %zu given", syrk_bf16x3_pieces_bytes(T, K), pieces_bytes);
     const float alpha = static_cast<float>(2.0 / static_cast<double>(n_total));
     return syrk_pieces_phases(X, T, K, ldx, alpha, 0.0f, nullptr, static_cast<unsigned char*>(pieces), nullptr, 0, 3, 1, as_stream(stream));
@@ -486,31 +486,36 @@ int32_t oq_hessian_prepare_f32(const float* X, int64_t T, int64_t K, int64_t ldx
 int32_t oq_hessian_accumulate_prepared_f32(const void* pieces, int64_t T, int64_t K, int64_t n_seen, int64_t n_add, float* H, void* slabs,
                                            size_t slab_bytes, void* stream) {
     OQ_REQUIRE(pieces && H && matrix_ok(T, K, K) && K <= kMaxHessianWidth && n_seen >= 0 && n_add > 0 && n_seen <= kMaxSamples && n_add <= kMaxSamples &&
-                   (reinterpret_cast<uintptr_t>(pieces) & 255u) == 0,
+                   aligned_to(pieces, 256),
                OQ_ERR_INVALID_ARGUMENT, "oq_hessian_accumulate_prepared_f32: bad argument");
     const int64_t n_total = n_seen + n_add;
     const float beta = n_seen == 0 ? 0.0f : static_cast<float>(static_cast<double>(n_seen) / static_cast<double>(n_total));   // gptq.py:254
     const float alpha = static_cast<float>(2.0 / static_cast<double>(n_total));
-    unsigned char* sl = static_cast<unsigned char*>(slabs);
-    if (sl != nullptr) {
-        const size_t pad = (256 - (reinterpret_cast<uintptr_t>(sl) & 255u)) & 255u;
-        sl = slab_bytes > pad ? sl + pad : nullptr;
-        slab_bytes = sl ? slab_bytes - pad : 0;
-    }
+    Workspace ws(slabs, slab_bytes);      // slabs as far as the buffer goes, from its first 256-byte boundary
+    slab_bytes = ws.left(4);
     return syrk_pieces_phases(nullptr, T, K, K, alpha, beta, H, const_cast<unsigned char*>(static_cast<const unsigned char*>(pieces)),
-                              reinterpret_cast<float*>(sl), slab_bytes, 3, 2, as_stream(stream));
+                              ws.take<float>(slab_bytes, 4), slab_bytes, 3, 2, as_stream(stream));
 }
 
 // N1  the calibration walk's large products (calibrate.py:244-251 runs them in onnxruntime): Y = X W on the fp16 matrix cores
 // with two-piece operands (22 significand bits, fp32 accumulate) -- the Hessian's arithmetic class, ~5 x an fp32 GEMM.
-size_t oq_matmul_pieces_bytes(int64_t Kd, int64_t cols) {
-    if (!extent_ok(Kd) || !extent_ok(cols) || !count_ok(Kd * cols, kMaxElements) || Kd > 8 * 65535 * 4) return 0;
-    return gemm_f16x3_pieces_bytes(Kd, cols) + ((static_cast<size_t>(cols) * 8 + 255) / 256) * 256;   // + room for one scale pair per row
+// an operand's buffer (workspace.hpp): its pieces, and behind them one scale pair per row -- [cols] s_t, [cols] 1 / s_t; returns the scales
+static float* matmul_pieces_layout(int64_t Kd, int64_t cols, Workspace& ws) {
+    ws.take(gemm_f16x3_pieces_bytes(Kd, cols));
+    return ws.take<float>(static_cast<size_t>(cols) * 8);
 }
 
-// the per-row scales of an operand live behind its pieces: [cols] s_t, [cols] 1 / s_t
+size_t oq_matmul_pieces_bytes(int64_t Kd, int64_t cols) {
+    if (!extent_ok(Kd) || !extent_ok(cols) || !count_ok(Kd * cols, kMaxElements) || Kd > 8 * 65535 * 4) return 0;
+    Workspace ws(/* aligned_base */ true);
+    matmul_pieces_layout(Kd, cols, ws);
+    return ws.total();
+}
+
+// the per-row scales of an operand: `pieces` is a buffer the prepare call has checked
 static float* matmul_row_scales(void* pieces, int64_t Kd, int64_t cols) {
-    return reinterpret_cast<float*>(static_cast<unsigned char*>(pieces) + gemm_f16x3_pieces_bytes(Kd, cols));
+    Workspace ws(pieces, oq_matmul_pieces_bytes(Kd, cols), /* aligned_base */ true);
+    return matmul_pieces_layout(Kd, cols, ws);
 }
 
 int32_t oq_matmul_prepare_f32(const float* X, int64_t Kd, int64_t cols, int64_t ldx, int32_t contraction_is_fast_axis, int32_t per_row_scales,
@@ -521,7 +526,7 @@ int32_t oq_matmul_prepare_f32(const float* X, int64_t Kd, int64_t cols, int64_t 
                "oq_matmul_prepare_f32: per-row scales are for sources with the contraction on the fast axis (activations [M, Kd])");
     const size_t need = oq_matmul_pieces_bytes(Kd, cols);
     OQ_REQUIRE(need != 0, OQ_ERR_UNSUPPORTED, "oq_matmul_prepare_f32: contraction of %lld too long", (long long)Kd);
-    OQ_REQUIRE(pieces_bytes >= need && (reinterpret_cast<uintptr_t>(pieces) & 255u) == 0, OQ_ERR_WORKSPACE,
+    OQ_REQUIRE(pieces_bytes >= need && aligned_to(pieces, 256), OQ_ERR_WORKSPACE,
                "oq_matmul_prepare_f32: a 256-byte aligned buffer of %zu bytes is needed, %zu given", need, pieces_bytes);
     return make_f16x2_pieces(X, Kd, cols, ldx, contraction_is_fast_axis != 0, pieces, as_stream(stream), true,
                              per_row_scales ? matmul_row_scales(pieces, Kd, cols) : nullptr);
@@ -530,8 +535,8 @@ int32_t oq_matmul_prepare_f32(const float* X, int64_t Kd, int64_t cols, int64_t 
 int32_t oq_matmul_pieces_f32(const void* pieces_a, const void* pieces_b, int64_t M, int64_t N, int64_t Kd, float alpha, float beta, float* C,
                              int64_t ldc, int32_t a_per_row_scales, void* stream) {
     OQ_REQUIRE(pieces_a && pieces_b && C && matrix_ok(M, N, ldc) && extent_ok(Kd) && oq_matmul_pieces_bytes(Kd, M) != 0 &&
-               oq_matmul_pieces_bytes(Kd, N) != 0 && (reinterpret_cast<uintptr_t>(pieces_a) & 255u) == 0 &&
-               (reinterpret_cast<uintptr_t>(pieces_b) & 255u) == 0, OQ_ERR_INVALID_ARGUMENT, "oq_matmul_pieces_f32: bad argument");
+               oq_matmul_pieces_bytes(Kd, N) != 0 && aligned_to(pieces_a, 256) && aligned_to(pieces_b, 256), OQ_ERR_INVALID_ARGUMENT,
+               "oq_matmul_pieces_f32: bad argument");
     const float* unscale = a_per_row_scales ? matmul_row_scales(const_cast<void*>(pieces_a), Kd, M) + M : nullptr;
     return launch_gemm_f16x3(pieces_a, pieces_b, M, N, Kd, alpha, beta, C, ldc, nullptr, as_stream(stream), false, unscale);
 }

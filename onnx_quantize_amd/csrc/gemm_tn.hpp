@@ -82,8 +82,10 @@ int32_t launch_syrk_reduce(const float* slab, int splits, int64_t K, float alpha
 // every fp32 element is split into three bf16 pieces whose sum is the element exactly, and 6 (piece products down to 2^-16,
 // the dropped ones are below fp32 rounding of a product) or all 9 products run on syrk_pieces_kernel<terms>.  `terms` = 3: two
 // fp16 pieces of the power-of-two scaled element and three products, on syrk_f16_m16_kernel.
-// workspace = the pieces (syrk_bf16x3_pieces_bytes) followed by optional T-slice slabs of K x K floats.
+// workspace = the pieces (syrk_bf16x3_pieces_bytes) followed by optional T-slice slabs of K x K floats: syrk_bf16x3_workspace_bytes
+// with room for `slab_budget` bytes of them (0: what a call needs at the least).
 size_t syrk_bf16x3_pieces_bytes(int64_t T, int64_t K);
+size_t syrk_bf16x3_workspace_bytes(int64_t T, int64_t K, size_t slab_budget);
 int32_t launch_syrk_bf16x3(const float* X, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C,
                            void* workspace, size_t workspace_bytes, int terms, hipStream_t s);
 
@@ -91,9 +93,9 @@ int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, fl
                            size_t slab_bytes, int terms, int phases, hipStream_t s);   // phases: 1 = X -> pieces, 2 = pieces -> C, 3 = both
 
 // The same update for an X that IS fp16 / bf16 (syrk_bf16x3.hip, section 4): X is packed as it is (2 bytes per element) and every
-// pair of elements meets in ONE matrix-core product with fp32 accumulation.  workspace = the packed operand
-// (syrk_h16_pieces_bytes) + 256, followed by optional T-slice slabs of K x K floats.
-size_t syrk_h16_pieces_bytes(int64_t T, int64_t K);
+// pair of elements meets in ONE matrix-core product with fp32 accumulation.  workspace = the packed operand followed by optional
+// T-slice slabs of K x K floats: syrk_h16_workspace_bytes with room for `slab_budget` bytes of them (0: what a call needs at the least).
+size_t syrk_h16_workspace_bytes(int64_t T, int64_t K, size_t slab_budget);
 int32_t launch_syrk_h16(const void* X, bool bf16, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, void* workspace,
                         size_t workspace_bytes, hipStream_t s);
 

@@ -699,20 +699,44 @@ static size_t coef_image_bytes(int64_t K, int64_t block_size) {
     return static_cast<size_t>(ceil_div(K, block_size) * launches_per_block(block_size)) * kCoefFloats * sizeof(float);
 }
 
-// operand pieces of the lazy batch update behind a super-block on the fp16-piece GEMM (gemm_tn.hpp): U rows x all columns, Err
-static size_t piece_gemm_bytes(int64_t K, int64_t N, int64_t block_size) {
-    const int64_t s = super_rows_bound(K, block_size);
-    return gemm_f16x3_pieces_bytes(s, K) + gemm_f16x3_pieces_bytes(s, N) + 1024;
+// The workspace of oq_gptq_loop_f32, measured and carved by this one function (workspace.hpp).
+struct LoopWs {
+    float* err;            // Err [super-block rows, N]
+    float* carry_scale;    // carried (scale, zp) [N]
+    int32_t* carry_zp;
+    float* pre_scale;      // (mse) per-group parameters of one launch [128, N]
+    uint8_t* pre_zp;
+    float* wb;             // block_size > 128: the block's working copy W1 [block_size, N]
+    float* image;          // coefficient images of all launches (rows-over-lanes kernel)
+    char* pieces_a;        // lazy batch update behind a super-block on the fp16-piece GEMM (gemm_tn.hpp): pieces of U[s0:s_end, s_end:] ...
+    char* pieces_b;        // ... and of the super-block's Err
+    char* mse_ws;          // the MSE search's own workspace for one [group, N] slice
+    size_t mse_ws_bytes;
+};
+
+static LoopWs loop_layout(int64_t K, int64_t N, int64_t block_size, Workspace& ws) {
+    const int64_t err_rows = super_rows_bound(K, block_size);
+    const bool tall = block_size > kLoopMaxRows;
+    LoopWs w;
+    w.err = ws.take<float>(static_cast<size_t>(err_rows) * N * 4);
+    w.carry_scale = ws.take<float>(static_cast<size_t>(N) * 4);
+    w.carry_zp = ws.take<int32_t>(static_cast<size_t>(N) * 4);
+    w.pre_scale = ws.take<float>(static_cast<size_t>(kLoopMaxRows) * N * 4);
+    w.pre_zp = ws.take<uint8_t>(static_cast<size_t>(kLoopMaxRows) * N);
+    w.wb = ws.take<float>(tall ? static_cast<size_t>(block_size < K ? block_size : K) * N * 4 : 0);
+    w.image = ws.take<float>(coef_image_bytes(K, block_size));
+    w.pieces_a = ws.take(gemm_f16x3_pieces_bytes(err_rows, K));
+    w.pieces_b = ws.take(gemm_f16x3_pieces_bytes(err_rows, N));
+    w.mse_ws_bytes = oq_rtn_workspace_bytes(K, N, OQ_CHANNEL, -1, 1);      // a slice has no more rows than W and as many columns
+    w.mse_ws = ws.take(w.mse_ws_bytes);
+    return w;
 }
 
 size_t oq_gptq_loop_workspace_bytes(int64_t K, int64_t N, int64_t block_size) {
     if (!matrix_ok(K, N, N) || K > kMaxHessianWidth || block_size <= 0 || block_size > kMaxExtent) return 0;
-    // Err [super-block rows, N] + carried (scale, zp) [N] + (mse) per-group parameters of one launch [128, N] x (4 + 1) B
-    // + (block_size > 128) the block's working copy [block_size, N] + the MSE search's own workspace for one [group, N] slice
-    // + the coefficient images of all launches (rows-over-lanes kernel)
-    const size_t tall = block_size > kLoopMaxRows ? static_cast<size_t>(block_size < K ? block_size : K) * N * 4 : 0;
-    return static_cast<size_t>(super_rows_bound(K, block_size)) * N * 4 + static_cast<size_t>(N) * 8 + static_cast<size_t>(kLoopMaxRows) * N * 5 + tall +
-           coef_image_bytes(K, block_size) + piece_gemm_bytes(K, N, block_size) + oq_rtn_workspace_bytes(K, N, OQ_CHANNEL, -1, 1) + 4096;
+    Workspace ws;
+    loop_layout(K, N, block_size, ws);
+    return ws.total();
 }
 
 int32_t oq_gptq_loop_f32(float* W, int64_t K, int64_t N, const float* U, int32_t qtype, int64_t group_size, int32_t symmetric,
@@ -737,9 +761,9 @@ int32_t oq_gptq_loop_f32(float* W, int64_t K, int64_t N, const float* U, int32_t
     QGrid grid;
     int32_t st = make_grid(qtype, symmetric, reduce_range, clip_ratio, &grid);
     if (st != OQ_OK) return st;
-    const size_t need = oq_gptq_loop_workspace_bytes(K, N, block_size);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_gptq_loop_f32: workspace of %zu bytes needed, %zu given", need,
-               workspace_bytes);
+    Workspace ws(workspace, workspace_bytes);
+    const LoopWs lw = loop_layout(K, N, block_size, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "oq_gptq_loop_f32: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
     hipStream_t s = as_stream(stream);
 
     LoopArgs a;
@@ -749,27 +773,16 @@ int32_t oq_gptq_loop_f32(float* W, int64_t K, int64_t N, const float* U, int32_t
     a.used_scale = (group_size > 0) ? used_scale : nullptr;
     a.used_zp = used_zp;
     if (a.used_scale != nullptr && used_zp == nullptr) return fail(OQ_ERR_INVALID_ARGUMENT, "oq_gptq_loop_f32: used_zp missing");
-    const int64_t err_rows = super_rows_bound(K, block_size);
     const bool tall = block_size > kLoopMaxRows;
-    char* wsp = static_cast<char*>(workspace);
-    a.err = reinterpret_cast<float*>(wsp);                              wsp += static_cast<size_t>(err_rows) * N * 4;
-    a.carry_scale = reinterpret_cast<float*>(wsp);                      wsp += static_cast<size_t>(N) * 4;
-    a.carry_zp = reinterpret_cast<int32_t*>(wsp);                       wsp += static_cast<size_t>(N) * 4;
-    float* pre_scale = reinterpret_cast<float*>(wsp);                   wsp += static_cast<size_t>(kLoopMaxRows) * N * 4;
-    uint8_t* pre_zp = reinterpret_cast<uint8_t*>(wsp);                  wsp += static_cast<size_t>(kLoopMaxRows) * N;
-    wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
-    float* wb = reinterpret_cast<float*>(wsp);                          // block_size > 128: the block's working copy W1
-    if (tall) wsp += static_cast<size_t>(block_size < K ? block_size : K) * N * 4;
-    wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
-    float* image = reinterpret_cast<float*>(wsp);                       // coefficient images of all launches
-    wsp += coef_image_bytes(K, block_size);
-    wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
-    char* pieces_a = wsp;                                               // fp16 pieces of U[s0:s_end, s_end:] ...
-    wsp += (gemm_f16x3_pieces_bytes(err_rows, K) + 255) / 256 * 256;
-    char* pieces_b = wsp;                                               // ... and of the super-block's Err
-    wsp += (gemm_f16x3_pieces_bytes(err_rows, N) + 255) / 256 * 256;
-    char* mse_ws = wsp + (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
-    const size_t mse_ws_bytes = static_cast<size_t>(static_cast<char*>(workspace) + workspace_bytes - mse_ws);
+    a.err = lw.err; a.carry_scale = lw.carry_scale; a.carry_zp = lw.carry_zp;
+    float* const pre_scale = lw.pre_scale;
+    uint8_t* const pre_zp = lw.pre_zp;
+    float* const wb = lw.wb;
+    float* const image = lw.image;
+    char* const pieces_a = lw.pieces_a;
+    char* const pieces_b = lw.pieces_b;
+    char* const mse_ws = lw.mse_ws;
+    const size_t mse_ws_bytes = lw.mse_ws_bytes;
     a.pre_scale = nullptr; a.pre_zp = nullptr; a.pre_first_group = 0;
     a.zp_signed = (qtype == OQ_INT4 || qtype == OQ_INT8) ? 1 : 0;
     a.Wt = W; a.wt_row0 = 0; a.err_row0 = 0; a.coef = nullptr; a.params_from_tile = tall ? 0 : 1;

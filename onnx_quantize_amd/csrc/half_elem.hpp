@@ -50,8 +50,6 @@ auto with_half_elem(int32_t type, F&& f) { return type == OQ_W_BF16 ? f(ElemBF16
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-inline bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }   // n: a power of two
-
 // What entry point `fn` checks of its 2-byte operand `name` ("W", "X" or "x"; the type argument is called after it, wtype / xtype):
 // a known type code and a pointer aligned to the element.  Null is aligned: whether it is allowed stays with the entry point, and
 // an entry point whose operands come in a table passes null here and checks the pointers entry by entry.

@@ -22,6 +22,8 @@
 // of sum |w - w_r|, their fold and every decision are those of the fp32 kernels on the upcast matrix: the same bits.
 #include "half_elem.hpp"
 
+#include <algorithm>
+
 namespace oq {
 
 struct HqqCtrl {
@@ -397,6 +399,36 @@ static void hqq_launch_rounds(int64_t g, dim3 grid, hipStream_t s, const HqqArgs
     }
 }
 
+// utils.py:19-22: the rows of a group
+static int64_t hqq_group(int64_t K, int64_t group_size) {
+    const int64_t g = group_size > K ? K : group_size;
+    return g == -1 ? K : g;
+}
+
+// The workspace of a call, measured and carved by this one function (workspace.hpp).  Per-round route: one partial per workgroup and
+// three zero-point arrays; one-pass route (g = 16 .. 256, <= kHqqFusedMaxIters rounds): the partials and the zero points of every round.
+struct HqqWs {
+    HqqCtrl* ctrl;
+    double* partial;
+    float *zp_cur, *zp_next, *zp_best;   // per-round route
+    float* traj;                         // one-pass route
+};
+
+static HqqWs hqq_layout(int64_t K, int64_t N, int64_t g, bool one_pass, Workspace& ws) {
+    const size_t rows = static_cast<size_t>(N) * (K / g), parts = static_cast<size_t>(ceil_div(N, 256)) * (K / g);
+    HqqWs w{};
+    w.ctrl = ws.take<HqqCtrl>(64, 64);
+    w.partial = ws.take<double>(parts * 8 * (one_pass ? kHqqFusedMaxIters : 1), 8);
+    if (one_pass) {
+        w.traj = ws.take<float>(rows * 4 * (kHqqFusedMaxIters + 1), 4);
+    } else {
+        w.zp_cur = ws.take<float>(rows * 4, 4);
+        w.zp_next = ws.take<float>(rows * 4, 4);
+        w.zp_best = ws.take<float>(rows * 4, 4);
+    }
+    return w;
+}
+
 // oq_hqq_optimize_f32 and oq_hqq_optimize_h16: one implementation, `fn` is the entry point's name in the messages.  Every check
 // stands in front of the first device call: a refused call touches no output.
 template <typename E>
@@ -412,16 +444,12 @@ static int32_t hqq_optimize(const char* fn, const void* W, int64_t K, int64_t N,
                (long long)ldw);
     OQ_REQUIRE(iters >= 0 && beta > 0.0, OQ_ERR_INVALID_ARGUMENT, "%s: iters >= 0 and beta > 0 needed (iters=%d beta=%g)", fn, iters, beta);
     OQ_REQUIRE(layout == OQ_LAYOUT_KN || layout == OQ_LAYOUT_NBITS, OQ_ERR_INVALID_ARGUMENT, "%s: bad layout %d", fn, layout);
-    int64_t g = group_size > K ? K : group_size;   // utils.py:19-22
-    if (g == -1) g = K;
+    const int64_t g = hqq_group(K, group_size);
     OQ_REQUIRE(g > 0, OQ_ERR_INVALID_ARGUMENT, "%s: bad group_size %lld", fn, (long long)group_size);
     OQ_REQUIRE(K % g == 0, OQ_ERR_UNSUPPORTED, "%s: groups that straddle columns (K %% group_size != 0) are not supported (K=%lld group_size %lld)",
                fn, (long long)K, (long long)g);
     const int64_t kgroups = K / g;
     OQ_REQUIRE(kgroups <= 65535, OQ_ERR_UNSUPPORTED, "%s: more than 65535 groups per column", fn);
-    const size_t need = oq_hqq_workspace_bytes(K, N, group_size);
-    OQ_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 8), OQ_ERR_WORKSPACE,
-               "%s: 8-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace ? workspace_bytes : static_cast<size_t>(0));
     int64_t qmin, qmax;
     OQ_REQUIRE(qrange_host(OQ_UINT4, 0, reduce_range, &qmin, &qmax), OQ_ERR_INVALID_ARGUMENT, "%s: qrange", fn);
     // One pass over W for all rounds where the group fits the register tile (the reference's only HQQ configurations: group
@@ -429,6 +457,12 @@ static int32_t hqq_optimize(const char* fn, const void* W, int64_t K, int64_t N,
     // workspace; same bits as the per-round loop.  iters == 0 takes the loop (no round: the given zero points).
     const bool tile = g == 16 || g == 32 || g == 64 || g == 128 || (g == 256 && sizeof(typename E::raw) == 2);
     const bool one_pass = tile && iters >= 1 && iters <= kHqqFusedMaxIters && !per_round_launches;
+    // refused by the query's size, which serves either route
+    const size_t need = oq_hqq_workspace_bytes(K, N, group_size);
+    Workspace ws(workspace, workspace_bytes);
+    const HqqWs hw = hqq_layout(K, N, g, one_pass, ws);
+    OQ_REQUIRE(workspace && workspace_bytes >= need && aligned_to(workspace, 8) && ws.fits(), OQ_ERR_WORKSPACE,
+               "%s: 8-byte aligned workspace of %zu bytes needed, %zu given", fn, need, workspace ? workspace_bytes : static_cast<size_t>(0));
     OQ_REQUIRE(layout == OQ_LAYOUT_KN || q_out == nullptr || ((one_pass || g % 8 == 0) && aligned_to(q_out, 4)),
                OQ_ERR_UNSUPPORTED, "%s: NBITS layout needs group_size %% 8 == 0 and a 4-byte aligned output", fn);
     hipStream_t s = as_stream(stream);
@@ -436,20 +470,17 @@ static int32_t hqq_optimize(const char* fn, const void* W, int64_t K, int64_t N,
     const dim3 grid(static_cast<uint32_t>(ceil_div(N, 256)), static_cast<uint32_t>(kgroups));
     const int64_t parts = static_cast<int64_t>(grid.x) * grid.y;
 
-    char* base = static_cast<char*>(workspace);
     HqqArgs a;
-    a.ctrl = reinterpret_cast<HqqCtrl*>(base);
-    a.partial = reinterpret_cast<double*>(base + 64);
-    a.zp_cur = reinterpret_cast<float*>(base + 64 + parts * 8);
-    a.zp_next = a.zp_cur + rows;
-    a.zp_best = a.zp_next + rows;
+    a.ctrl = hw.ctrl;
+    a.partial = hw.partial;
+    a.zp_cur = hw.zp_cur; a.zp_next = hw.zp_next; a.zp_best = hw.zp_best;
     a.W = W; a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = kgroups; a.scale = scale;
     a.qmin = static_cast<float>(qmin); a.qmax = static_cast<float>(qmax);
     a.expo = static_cast<float>(lp_norm - 1.0);
     a.round = 0; a.inv_beta = 0.f;
 
     if (one_pass) {
-        float* traj = reinterpret_cast<float*>(base + 64 + parts * 8 * kHqqFusedMaxIters);
+        float* traj = hw.traj;
         HqqBetas betas;
         double b2 = beta;
         for (int32_t it = 0; it < kHqqFusedMaxIters; ++it) {
@@ -506,16 +537,12 @@ using namespace oq;
 
 size_t oq_hqq_workspace_bytes(int64_t K, int64_t N, int64_t group_size) {
     if (!oq::matrix_ok(K, N, N)) return 0;
-    int64_t g = group_size > K ? K : group_size;
-    if (g == -1) g = K;
+    const int64_t g = hqq_group(K, group_size);
     if (g <= 0 || K % g != 0) return 0;
-    const int64_t rows = N * (K / g);
-    const int64_t parts = ceil_div(N, 256) * (K / g);
-    // per-round route: three zero-point arrays + one partial per workgroup; one-pass route (g = 16 .. 256, <= 32 rounds): the
-    // zero points of every round + the partials of every round
-    const size_t per_round = static_cast<size_t>(rows) * 4 * 3 + static_cast<size_t>(parts) * 8;
-    const size_t one_pass = static_cast<size_t>(rows) * 4 * (kHqqFusedMaxIters + 1) + static_cast<size_t>(parts) * 8 * kHqqFusedMaxIters;
-    return (per_round > one_pass ? per_round : one_pass) + 1024;
+    Workspace per_round, one_pass;      // the route depends on arguments the query does not see
+    hqq_layout(K, N, g, false, per_round);
+    hqq_layout(K, N, g, true, one_pass);
+    return std::max(per_round.total(), one_pass.total());
 }
 
 int32_t oq_hqq_optimize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, int64_t group_size, int32_t reduce_range,

@@ -20,10 +20,10 @@
 //   guards    every global access is guarded by M, N, K: rows >= M, columns >= N and k >= K are zeros in LDS (A) or never read
 //             (B, scales, zero points); a padded blob position meets a zero of A and its bytes are finite integers whatever they hold.
 #include "half_elem.hpp"
+#include "tile_plan.hpp"
 
 #include "../../include/oq_hip_nbits.h"
 
-#include <algorithm>
 #include <cmath>
 
 namespace oq {
@@ -33,10 +33,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBN = 128;             // columns of a block tile
-constexpr int kBK = 64;              // k of a step: two MFMA depths
-constexpr int kRow = kBK * 2 + 16;   // bytes of a tile row in LDS: 16 lanes x 16 bytes land in 16 different bank quads
-constexpr int kThreads = 256;
+constexpr int kRow = kBK * 2 + 16;   // bytes of a tile row in LDS (kBK: two MFMA depths): 16 lanes x 16 bytes land in 16 different bank quads
 
 struct OpF16 : ElemF16 {
     typedef f16x8 frag;
@@ -310,13 +307,11 @@ __global__ __launch_bounds__(kThreads) void nbits_split_rows_kernel(const float*
 }
 
 // ---- host
-size_t r256(int64_t n) { return (static_cast<size_t>(n) + 255) / 256 * 256; }
-
-struct Plan {
-    int bm;
-    int64_t tiles_m, tiles, steps_per_split, splits, kp;
-    size_t piece_bytes, exp_bytes, slab_bytes;
-    size_t total() const { return 2 * piece_bytes + exp_bytes + slab_bytes; }
+struct Plan : TilePlan {      // and the workspace: include/oq_hip_nbits.h, `workspace`
+    int64_t kp;               // fp32 A: K padded to 8, the width of its pieces
+    uint16_t *hi, *lo;        // fp32 A: its two fp16 pieces [M, kp]
+    int32_t* row_exp;         // fp32 A: the scale exponent of every row
+    float* slab;
 };
 
 bool shape_ok(int64_t M, int64_t K, int64_t N, int64_t g) {
@@ -324,27 +319,21 @@ bool shape_ok(int64_t M, int64_t K, int64_t N, int64_t g) {
            count_ok(N * (ceil_div(K, g) * g));
 }
 
-Plan make_plan(int64_t M, int64_t K, int64_t N, int32_t atype) {
-    Plan pl;
-    pl.bm = M <= 32 ? 32 : 128;
-    pl.tiles_m = ceil_div(M, pl.bm);
-    pl.tiles = pl.tiles_m * ceil_div(N, kBN);
-    const int64_t steps = ceil_div(K, kBK);
-    const int64_t want = pl.tiles >= 128 ? 1 : std::min<int64_t>(std::min<int64_t>(8, steps), 256 / pl.tiles);
-    pl.steps_per_split = ceil_div(steps, want);
-    pl.splits = ceil_div(steps, pl.steps_per_split);
+Plan make_plan(int64_t M, int64_t K, int64_t N, int32_t atype, Workspace& ws) {
+    Plan pl{make_tile_plan(M, K, N)};
     pl.kp = (K + 7) / 8 * 8;
-    pl.piece_bytes = atype == OQ_NBITS_F32 ? r256(M * pl.kp * 2) : 0;
-    pl.exp_bytes = atype == OQ_NBITS_F32 ? r256(M * 4) : 0;
-    pl.slab_bytes = pl.splits > 1 ? r256(pl.splits * M * N * 4) : 0;
+    const size_t piece_bytes = atype == OQ_NBITS_F32 ? static_cast<size_t>(M) * pl.kp * 2 : 0;
+    pl.hi = ws.take<uint16_t>(piece_bytes);
+    pl.lo = ws.take<uint16_t>(piece_bytes);
+    pl.row_exp = ws.take<int32_t>(atype == OQ_NBITS_F32 ? static_cast<size_t>(M) * 4 : 0);
+    pl.slab = ws.take<float>(pl.slab_bytes);
     return pl;
 }
 
 template <int OUT, int BITS>
 void launch_gemm(const NbitsArgs& p, const Plan& pl, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>(pl.tiles), static_cast<unsigned>(pl.splits));
-    if (pl.bm == 32) nbits_gemm_kernel<OUT, BITS, 1><<<grid, kThreads, 0, s>>>(p);
-    else nbits_gemm_kernel<OUT, BITS, 4><<<grid, kThreads, 0, s>>>(p);
+    with_row_tiles(pl, [&](auto mt) { nbits_gemm_kernel<OUT, BITS, decltype(mt)::value><<<grid, kThreads, 0, s>>>(p); });
 }
 
 template <int OUT>
@@ -374,7 +363,9 @@ size_t oq_matmul_nbits_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t 
                   (long long)N, (long long)group_size, atype);
         return 0;
     }
-    return make_plan(M, K, N, atype).total();
+    Workspace ws(/* aligned_base */ true);
+    make_plan(M, K, N, atype, ws);
+    return ws.total();
 }
 
 int32_t oq_matmul_nbits(const void* A, int32_t atype, int64_t M, int64_t K, int64_t lda, const void* B, int32_t bits, int64_t N, int64_t group_size,
@@ -401,12 +392,12 @@ int32_t oq_matmul_nbits(const void* A, int32_t atype, int64_t M, int64_t K, int6
     OQ_REQUIRE(aligned_to(A, elem) && aligned_to(Y, elem) && aligned_to(bias, elem) && aligned_to(scales, scales_type == OQ_NBITS_F32 ? 4 : 2),
                OQ_ERR_INVALID_ARGUMENT, "%s: A, Y, bias and scales must be aligned to their element", fn);
     OQ_REQUIRE(aligned_to(B, 16), OQ_ERR_INVALID_ARGUMENT, "%s: B must be 16-byte aligned", fn);
-    const Plan pl = make_plan(M, K, N, atype);
-    OQ_REQUIRE(pl.total() == 0 || (workspace && workspace_bytes >= pl.total() && aligned_to(workspace, 256)), OQ_ERR_WORKSPACE,
-               "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, pl.total(), workspace ? workspace_bytes : (size_t)0);
+    Workspace ws(workspace, workspace_bytes, /* aligned_base */ true);
+    const Plan pl = make_plan(M, K, N, atype, ws);
+    OQ_REQUIRE(ws.total() == 0 || ws.fits(), OQ_ERR_WORKSPACE, "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, ws.total(),
+               workspace ? workspace_bytes : (size_t)0);
 
     hipStream_t s = as_stream(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
     NbitsArgs p{};
     p.B = static_cast<const uint8_t*>(B);
     p.scales = scales;
@@ -417,15 +408,12 @@ int32_t oq_matmul_nbits(const void* A, int32_t atype, int64_t M, int64_t K, int6
     p.ldy = ldy;
     p.M = M, p.N = N, p.K = K, p.g = group_size, p.blocks = ceil_div(K, group_size);
     p.tiles_m = pl.tiles_m, p.steps_per_split = pl.steps_per_split;
-    p.slab = pl.splits > 1 ? reinterpret_cast<float*>(ws + 2 * pl.piece_bytes + pl.exp_bytes) : nullptr;
+    p.slab = pl.slab;
     if (atype == OQ_NBITS_F32) {
-        uint16_t* hi = reinterpret_cast<uint16_t*>(ws);
-        uint16_t* lo = reinterpret_cast<uint16_t*>(ws + pl.piece_bytes);
-        int32_t* row_exp = reinterpret_cast<int32_t*>(ws + 2 * pl.piece_bytes);
-        nbits_split_rows_kernel<<<static_cast<unsigned>(M), kThreads, 0, s>>>(static_cast<const float*>(A), K, lda, pl.kp, hi, lo, row_exp);
+        nbits_split_rows_kernel<<<static_cast<unsigned>(M), kThreads, 0, s>>>(static_cast<const float*>(A), K, lda, pl.kp, pl.hi, pl.lo, pl.row_exp);
         const int32_t st = check_launch("nbits_split_rows_kernel");
         if (st != OQ_OK) return st;
-        p.A = hi, p.A_lo = lo, p.lda = pl.kp, p.Ka = pl.kp, p.a_vec = 1, p.row_exp = row_exp;
+        p.A = pl.hi, p.A_lo = pl.lo, p.lda = pl.kp, p.Ka = pl.kp, p.a_vec = 1, p.row_exp = pl.row_exp;
         return run<OQ_NBITS_F32>(p, pl, bits, s);
     }
     p.A = static_cast<const uint16_t*>(A), p.lda = lda, p.Ka = K, p.a_vec = aligned_to(A, 16) && lda % 8 == 0;

@@ -9,6 +9,7 @@
 #include <cstdio>
 
 #include "../../include/oq_hip.h"
+#include "workspace.hpp"
 
 namespace oq {
 
@@ -227,5 +228,7 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nblk) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }   // n: a power of two
 
 }  // namespace oq

@@ -29,10 +29,10 @@
 //   split K   blockIdx.y takes a range of k-steps and writes S to int32 slab y; ql_reduce_kernel adds the slabs, corrects and
 //             finishes.  No atomics anywhere.
 #include "half_elem.hpp"
+#include "tile_plan.hpp"
 
 #include "../../include/oq_hip_qlinear.h"
 
-#include <algorithm>
 
 namespace oq {
 namespace {
@@ -40,10 +40,7 @@ namespace {
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kBN = 128;          // columns of a block tile
-constexpr int kBK = 64;           // k of a step: one MFMA depth
-constexpr int kRow = kBK + 16;    // bytes of a tile row in LDS: 16 lanes x 16 bytes land in 16 different bank quads
-constexpr int kThreads = 256;
+constexpr int kRow = kBK + 16;    // bytes of a tile row in LDS (kBK: one MFMA depth): 16 lanes x 16 bytes land in 16 different bank quads
 constexpr int kColSlices = 8;      // partial column sums of a KN matrix: slices of K
 
 struct QlArgs {
@@ -352,39 +349,31 @@ __global__ __launch_bounds__(kThreads) void ql_sum_cols_kernel(const uint8_t* X,
 }
 
 // ---- host
-size_t r256(int64_t n) { return (static_cast<size_t>(n) + 255) / 256 * 256; }
-
-struct Plan {
-    int bm;
-    int64_t tiles_m, tiles, steps_per_split, splits;
-    size_t row_bytes, col_bytes, slab_bytes;
-    size_t total() const { return row_bytes + col_bytes + slab_bytes; }
+struct Plan : TilePlan {      // and the workspace: include/oq_hip_qlinear.h, `workspace`
+    int32_t* rowsum;          // [M] sums of A's rows
+    int32_t* colsum;          // [kColSlices] partial sums of B's columns, `colsum_stride` entries apart
+    uint32_t colsum_stride;
+    uint32_t* slab;
 };
 
 bool shape_ok(int64_t M, int64_t K, int64_t N) {
     return extent_ok(M) && extent_ok(K) && extent_ok(N) && count_ok(M * K) && count_ok(M * N) && count_ok(N * K);
 }
 
-Plan make_plan(int64_t M, int64_t K, int64_t N) {      // the plan of matmul_nbits.hip
-    Plan pl;
-    pl.bm = M <= 32 ? 32 : 128;
-    pl.tiles_m = ceil_div(M, pl.bm);
-    pl.tiles = pl.tiles_m * ceil_div(N, kBN);
-    const int64_t steps = ceil_div(K, kBK);
-    const int64_t want = pl.tiles >= 128 ? 1 : std::min<int64_t>(std::min<int64_t>(8, steps), 256 / pl.tiles);
-    pl.steps_per_split = ceil_div(steps, want);
-    pl.splits = ceil_div(steps, pl.steps_per_split);
-    pl.row_bytes = r256(M * 4);
-    pl.col_bytes = kColSlices * r256(N * 4);
-    pl.slab_bytes = pl.splits > 1 ? r256(pl.splits * M * N * 4) : 0;
+Plan make_plan(int64_t M, int64_t K, int64_t N, Workspace& ws) {
+    Plan pl{make_tile_plan(M, K, N)};
+    const size_t slice_bytes = Workspace::padded(static_cast<size_t>(N) * 4);
+    pl.rowsum = ws.take<int32_t>(static_cast<size_t>(M) * 4);
+    pl.colsum = ws.take<int32_t>(kColSlices * slice_bytes);
+    pl.colsum_stride = static_cast<uint32_t>(slice_bytes / 4);
+    pl.slab = ws.take<uint32_t>(pl.slab_bytes);
     return pl;
 }
 
 template <int LAYOUT>
 void launch_gemm(const QlArgs& p, const Plan& pl, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>(pl.tiles), static_cast<unsigned>(pl.splits));
-    if (pl.bm == 32) ql_gemm_kernel<1, LAYOUT><<<grid, kThreads, 0, s>>>(p);
-    else ql_gemm_kernel<4, LAYOUT><<<grid, kThreads, 0, s>>>(p);
+    with_row_tiles(pl, [&](auto mt) { ql_gemm_kernel<decltype(mt)::value, LAYOUT><<<grid, kThreads, 0, s>>>(p); });
 }
 
 bool type_ok(int32_t t) { return t == OQ_QL_U8 || t == OQ_QL_I8; }
@@ -403,7 +392,9 @@ size_t oq_qlinear_matmul_workspace_bytes(int64_t M, int64_t K, int64_t N) {
         set_error("oq_qlinear_matmul_workspace_bytes: M=%lld K=%lld N=%lld outside the bounds", (long long)M, (long long)K, (long long)N);
         return 0;
     }
-    return make_plan(M, K, N).total();
+    Workspace ws(/* aligned_base */ true);
+    make_plan(M, K, N, ws);
+    return ws.total();
 }
 
 int32_t oq_qlinear_matmul(const void* A, int32_t a_type, int64_t M, int64_t K, int64_t lda, const float* a_scale, const void* a_zero_point,
@@ -434,12 +425,12 @@ int32_t oq_qlinear_matmul(const void* A, int32_t a_type, int64_t M, int64_t K, i
     OQ_REQUIRE(aligned_to(a_scale, 4) && aligned_to(b_scale, 4) && aligned_to(y_scale, 4) && aligned_to(C, 4) &&
                    aligned_to(Y, out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 ? 4 : 1),
                OQ_ERR_INVALID_ARGUMENT, "%s: the scales, C and Y must be aligned to their element", fn);
-    const Plan pl = make_plan(M, K, N);
-    OQ_REQUIRE(workspace && workspace_bytes >= pl.total() && aligned_to(workspace, 256), OQ_ERR_WORKSPACE,
-               "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, pl.total(), workspace ? workspace_bytes : (size_t)0);
+    Workspace ws(workspace, workspace_bytes, /* aligned_base */ true);
+    const Plan pl = make_plan(M, K, N, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, ws.total(),
+               workspace ? workspace_bytes : (size_t)0);
 
     hipStream_t s = as_stream(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
     QlArgs p{};
     p.A = static_cast<const uint8_t*>(A), p.B = static_cast<const uint8_t*>(B);
     p.lda = lda, p.ldb = ldb;
@@ -452,11 +443,11 @@ int32_t oq_qlinear_matmul(const void* A, int32_t a_type, int64_t M, int64_t K, i
     p.M = static_cast<uint32_t>(M), p.N = static_cast<uint32_t>(N), p.K = static_cast<uint32_t>(K);
     p.tiles_m = static_cast<uint32_t>(pl.tiles_m), p.steps_per_split = static_cast<uint32_t>(pl.steps_per_split);
     // a sum is needed unless its multiplier -- the OTHER operand's shifted zero point -- is zero whatever the device holds
-    int32_t* rowsum = (p.b_signed && !b_zero_point) ? nullptr : reinterpret_cast<int32_t*>(ws);
-    int32_t* colsum = (p.a_signed && !a_zero_point) ? nullptr : reinterpret_cast<int32_t*>(ws + pl.row_bytes);
+    int32_t* rowsum = (p.b_signed && !b_zero_point) ? nullptr : pl.rowsum;
+    int32_t* colsum = (p.a_signed && !a_zero_point) ? nullptr : pl.colsum;
     p.rowsum = rowsum, p.colsum = colsum;
-    p.colsum_slices = kn ? kColSlices : 1, p.colsum_stride = static_cast<uint32_t>(r256(N * 4) / 4);
-    p.slab = pl.splits > 1 ? reinterpret_cast<uint32_t*>(ws + pl.row_bytes + pl.col_bytes) : nullptr;
+    p.colsum_slices = kn ? kColSlices : 1, p.colsum_stride = pl.colsum_stride;
+    p.slab = pl.slab;
 
     // the sums run over x ^ ubias read as an unsigned byte, minus 128: ubias flips a SIGNED operand
     const uint32_t a_ubias = p.a_flip ^ 0x80808080u, b_ubias = p.b_flip ^ 0x80808080u;

@@ -104,16 +104,19 @@ __global__ __launch_bounds__(kRedBlock) void minmax_update(const T* partial, int
     }
 }
 
+// The workspaces of this file are single arrays of partial results, used from the caller's pointer on: one formula each, shared
+// by the query and the entry point.  (The `+ 256` of two queries is room the entry points never asked for; the header states it.)
+constexpr size_t kMinmaxPartialBytes = static_cast<size_t>(kRedMaxBlocks) * 2 * sizeof(double);      // one (min, max) per block, as doubles
 template <typename T>
 static int32_t minmax_collect(const T* x, int64_t count, T* state, double momentum, void* ws, size_t ws_bytes,
                               void* stream) {
     OQ_REQUIRE(x && state && count_ok(count), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect: bad argument");
     OQ_REQUIRE(momentum >= 0.0 && momentum < 1.0, OQ_ERR_INVALID_ARGUMENT, "Momentum must be in the range [0, 1).");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(x) % sizeof(T)) == 0, OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect: misaligned input");
+    OQ_REQUIRE(aligned_to(x, sizeof(T)), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect: misaligned input");
     int64_t nblocks = ceil_div(count, static_cast<int64_t>(kRedBlock) * 8);
     if (nblocks > kRedMaxBlocks) nblocks = kRedMaxBlocks;
     if (nblocks < 1) nblocks = 1;
-    const size_t need = static_cast<size_t>(kRedMaxBlocks) * 2 * sizeof(double);
+    const size_t need = kMinmaxPartialBytes;
     OQ_REQUIRE(ws && ws_bytes >= need, OQ_ERR_WORKSPACE, "oq_minmax_collect: workspace of %zu bytes needed, %zu given", need, ws_bytes);
     // peel to the vector alignment (4 elements)
     const uintptr_t addr = reinterpret_cast<uintptr_t>(x);
@@ -327,6 +330,8 @@ __global__ __launch_bounds__(kRedBlock) void fingerprint_kernel(const uint4* x, 
     if ((threadIdx.x & 63) == 0) atomicAdd(out, static_cast<unsigned long long>(acc));
 }
 
+static size_t absmax_partial_bytes(int64_t R, int64_t C) { return static_cast<size_t>(ceil_div(R, kAbsChunkRows) * C) * sizeof(float); }
+
 }  // namespace oq
 
 extern "C" {
@@ -335,7 +340,7 @@ using namespace oq;
 
 int32_t oq_fingerprint64(const void* data, int64_t nbytes, uint64_t* out, void* stream) {
     OQ_REQUIRE(data && out && nbytes > 0 && nbytes <= kMaxElements, OQ_ERR_INVALID_ARGUMENT, "oq_fingerprint64: bad argument (1 <= nbytes <= 2^40)");
-    OQ_REQUIRE((reinterpret_cast<uintptr_t>(data) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0, OQ_ERR_INVALID_ARGUMENT,
+    OQ_REQUIRE(aligned_to(data, 16) && aligned_to(out, 8), OQ_ERR_INVALID_ARGUMENT,
                "oq_fingerprint64: data must be 16-byte aligned, out 8-byte aligned");
     hipStream_t s = as_stream(stream);
     if (hipMemsetAsync(out, 0, sizeof(uint64_t), s) != hipSuccess) return fail(OQ_ERR_LAUNCH, "oq_fingerprint64: cannot clear the result");
@@ -350,7 +355,7 @@ int32_t oq_fingerprint64(const void* data, int64_t nbytes, uint64_t* out, void* 
 
 size_t oq_minmax_workspace_bytes(int64_t count) {
     (void)count;
-    return static_cast<size_t>(kRedMaxBlocks) * 2 * sizeof(double);
+    return kMinmaxPartialBytes;
 }
 
 int32_t oq_minmax_collect_f32(const float* x, int64_t count, float* state, double momentum, void* workspace,
@@ -387,20 +392,20 @@ int32_t oq_minmax_collect_many_f32(const void* desc, int64_t n, double momentum,
 
 size_t oq_absmax_workspace_bytes(int64_t R, int64_t C, int32_t transposed) {
     if (transposed || !matrix_ok(R, C, C)) return 256;
-    return static_cast<size_t>(ceil_div(R, kAbsChunkRows) * C) * sizeof(float) + 256;
+    return absmax_partial_bytes(R, C) + 256;
 }
 
 int32_t oq_absmax_f32(const float* x, int64_t R, int64_t C, int64_t ldx, int32_t transposed, float* out,
                       void* workspace, size_t workspace_bytes, void* stream) {
     OQ_REQUIRE(x && out && matrix_ok(R, C, ldx), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_f32: bad argument");
-    const bool vec4 = (C % 4 == 0) && (ldx % 4 == 0) && (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+    const bool vec4 = (C % 4 == 0) && (ldx % 4 == 0) && aligned_to(x, 16);
     hipStream_t s = as_stream(stream);
     if (transposed) {
         hipLaunchKernelGGL(absmax_rows, dim3(static_cast<uint32_t>(ceil_div(R, 4))), dim3(256), 0, s, x, R, C, ldx, vec4, out);
         return check_launch("absmax_rows");
     }
     const int64_t chunks = ceil_div(R, kAbsChunkRows);
-    const size_t need = static_cast<size_t>(chunks * C) * sizeof(float);
+    const size_t need = absmax_partial_bytes(R, C);
     OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_absmax_f32: workspace of %zu bytes needed, %zu given",
                need, workspace_bytes);
     const uint32_t ncol_tiles = static_cast<uint32_t>(ceil_div(C, 256));
@@ -415,7 +420,7 @@ int32_t oq_absmax_f32(const float* x, int64_t R, int64_t C, int64_t ldx, int32_t
 
 int32_t oq_minmax_rows_f32(const float* x, int64_t R, int64_t C, int64_t ldx, float* min_out, float* max_out, void* stream) {
     OQ_REQUIRE(x && min_out && max_out && matrix_ok(R, C, ldx), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_rows_f32: bad argument");
-    const bool vec4 = (C % 4 == 0) && (ldx % 4 == 0) && (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+    const bool vec4 = (C % 4 == 0) && (ldx % 4 == 0) && aligned_to(x, 16);
     hipLaunchKernelGGL(minmax_rows, dim3(static_cast<uint32_t>(ceil_div(R, 4))), dim3(256), 0, as_stream(stream), x, R, C, ldx,
                        vec4, min_out, max_out);
     return check_launch("minmax_rows");

@@ -249,9 +249,14 @@ extern "C" {
 
 using namespace oq;
 
+// The workspaces of this file are single arrays of partial results, used from the caller's pointer on: one formula each, shared
+// by the query and the entry point.  (The `+ 256` of two queries is room the entry points never asked for; the header states it.)
+constexpr size_t kMinmaxHalfPartialBytes = static_cast<size_t>(kHalfMaxBlocks) * 2 * sizeof(float);      // one (min, max) per block
+static size_t absmax_half_partial_bytes(int64_t R, int64_t C) { return static_cast<size_t>(ceil_div(R, kHalfAbsChunkRows) * C) * sizeof(float); }
+
 size_t oq_minmax_half_workspace_bytes(int64_t count) {
     if (!count_ok(count)) return 0;
-    return static_cast<size_t>(kHalfMaxBlocks) * 2 * sizeof(float);
+    return kMinmaxHalfPartialBytes;
 }
 
 int32_t oq_minmax_collect_h16(const void* x, int32_t xtype, int64_t count, float* state, double momentum, void* workspace,
@@ -263,7 +268,7 @@ int32_t oq_minmax_collect_h16(const void* x, int32_t xtype, int64_t count, float
     OQ_REQUIRE(aligned_to(state, 4), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: state must be 4-byte aligned");
     OQ_REQUIRE(count_ok(count), OQ_ERR_INVALID_ARGUMENT, "oq_minmax_collect_h16: bad count=%lld (1 <= count <= 2^40)", (long long)count);
     OQ_REQUIRE(momentum >= 0.0 && momentum < 1.0, OQ_ERR_INVALID_ARGUMENT, "Momentum must be in the range [0, 1) (momentum=%g).", momentum);
-    const size_t need = static_cast<size_t>(kHalfMaxBlocks) * 2 * sizeof(float);
+    const size_t need = kMinmaxHalfPartialBytes;
     OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_minmax_collect_h16: workspace of %zu bytes needed, %zu given",
                need, workspace_bytes);
     // every block gets at least one eight-deep round of its 512 lanes (32768 elements) before a second block is started
@@ -313,7 +318,7 @@ int32_t oq_minmax_collect_many_h16(const void* desc, int64_t n, int32_t xtype, d
 size_t oq_absmax_half_workspace_bytes(int64_t R, int64_t C, int32_t transposed) {
     if (!matrix_ok(R, C, C)) return 0;
     if (transposed) return 256;
-    return static_cast<size_t>(ceil_div(R, kHalfAbsChunkRows) * C) * sizeof(float) + 256;
+    return absmax_half_partial_bytes(R, C) + 256;
 }
 
 int32_t oq_absmax_h16(const void* x, int32_t xtype, int64_t R, int64_t C, int64_t ldx, int32_t transposed, float* out, void* workspace,
@@ -333,7 +338,7 @@ int32_t oq_absmax_h16(const void* x, int32_t xtype, int64_t R, int64_t C, int64_
         return check_launch("absmax_half_rows");
     }
     const int64_t chunks = ceil_div(R, kHalfAbsChunkRows);
-    const size_t need = static_cast<size_t>(chunks * C) * sizeof(float);
+    const size_t need = absmax_half_partial_bytes(R, C);
     OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "oq_absmax_h16: workspace of %zu bytes needed, %zu given", need,
                workspace_bytes);
     OQ_REQUIRE(aligned_to(workspace, 4), OQ_ERR_INVALID_ARGUMENT, "oq_absmax_h16: workspace must be 4-byte aligned");

@@ -5,6 +5,7 @@
 // registers.  Nothing is reshaped into a GEMM and no transposed copy (utils.py:24) is ever made.
 #include "rtn_internal.hpp"
 
+#include <algorithm>
 #include <type_traits>
 
 namespace oq {
@@ -1288,7 +1289,7 @@ __global__ __launch_bounds__(256) void transpose_qparams(const float* scale_t, c
 }
 
 // ------------------------------------------------------------------------------------ dispatch
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static bool aligned16(const void* p) { return aligned_to(p, 16); }
 static int32_t zp_signed(int32_t qtype) { return (qtype == OQ_INT4 || qtype == OQ_INT8) ? 1 : 0; }
 
 // Rows per wave / waves per group for the fused kernel; false when the group is too tall.
@@ -1346,14 +1347,40 @@ static void launch_fused_kernel(int rpw, const RtnArgs& a, dim3 grid, dim3 block
 
 static const void* tr_build() { return reinterpret_cast<const void*>(rtn_group_fused<16, true, true, true>); }
 
+// The two buffers of the fused route, each measured and carved by one function (workspace.hpp).
 // the zeroed state of the in-launch transposition: [kgroups, N] fp32 scales + one 8-byte {four zero points, marker} granule per four columns
-static size_t fused_state_bytes(int64_t K, int64_t N, int64_t g) {
-    const int64_t kgroups = K / g;
-    return static_cast<size_t>((kgroups * N * 4 + 255) / 256 * 256 + kgroups * N * 2 + 256);
+struct FusedState {
+    float* scale;
+    uint2* zp;
+};
+static FusedState fused_state_layout(int64_t K, int64_t N, int64_t g, Workspace& ws) {
+    const size_t params = static_cast<size_t>(K / g) * N;
+    FusedState w;
+    w.scale = ws.take<float>(params * 4);
+    w.zp = ws.take<uint2>(params * 2, 8);
+    return w;
 }
-static size_t stage_ws(int64_t K, int64_t N, int64_t g) {  // [kgroups, N] fp32 scales + bytes, 256-byte aligned halves
-    const int64_t kgroups = K / g;
-    return static_cast<size_t>((kgroups * N * 4 + 255) / 256 * 256 + (kgroups * N + 255) / 256 * 256);
+static size_t fused_state_bytes(int64_t K, int64_t N, int64_t g) {
+    Workspace ws;
+    fused_state_layout(K, N, g, ws);
+    return ws.total();
+}
+// the staged parameters of `batch` matrices: [batch, kgroups, N] fp32 scales, then as many bytes
+struct StageWs {
+    float* scale;
+    uint8_t* zp;
+};
+static StageWs stage_layout(int64_t batch, int64_t K, int64_t N, int64_t g, Workspace& ws) {
+    const size_t params = static_cast<size_t>(batch) * (K / g) * N;
+    StageWs w;
+    w.scale = ws.take<float>(params * 4);
+    w.zp = ws.take<uint8_t>(params);
+    return w;
+}
+static size_t stage_ws(int64_t batch, int64_t K, int64_t N, int64_t g) {
+    Workspace ws;
+    stage_layout(batch, K, N, g, ws);
+    return ws.total();
 }
 
 static size_t twopass_ws(int64_t K, int64_t N, int64_t g) {
@@ -1388,7 +1415,7 @@ int32_t launch_quantize_kn(const float* W, int64_t K, int64_t N, int64_t ldw, in
     qa.grid = grid; qa.zp_signed = zp_signed; qa.tensor = tensor;
     qa.ncol_tiles = static_cast<uint32_t>(ceil_div(N, kColsPerWave));
     qa.nrow_tiles = static_cast<uint32_t>(kgroups * qa.chunks);
-    const bool vec4 = (N % 4 == 0) && (ldw % 4 == 0) && aligned16(W) && (reinterpret_cast<uintptr_t>(q) & 3u) == 0;
+    const bool vec4 = (N % 4 == 0) && (ldw % 4 == 0) && aligned16(W) && aligned_to(q, 4);
     OQ_REQUIRE(layout == OQ_LAYOUT_KN || (vec4 && g % kChunkRows == 0 && aligned16(q) && !tensor), OQ_ERR_UNSUPPORTED,
                "NBITS layout with group_size > 256 needs group_size %% 128 == 0, N %% 4 == 0 and 16-byte aligned buffers");
     const dim3 grid_dim(qa.ncol_tiles * qa.nrow_tiles), block(kMaxWaves * kWave);
@@ -1439,13 +1466,13 @@ static int32_t check_call(const RtnCall& c, RtnShape& sh) {
     const int64_t g = sh.g;
     sh.kgroups = K / g;
     sh.fused = c.strategy == OQ_GROUP && fused_shape(g, &sh.rpw, &sh.wpg);
-    sh.vec4 = (N % 4 == 0) && (ldw % 4 == 0) && aligned16(c.W) && (!c.emit_q || (reinterpret_cast<uintptr_t>(c.q) & 3u) == 0);
+    sh.vec4 = (N % 4 == 0) && (ldw % 4 == 0) && aligned16(c.W) && (!c.emit_q || aligned_to(c.q, 4));
     if (c.layout == OQ_LAYOUT_KN_PACKED4) {
         // two columns per byte, written by the fused group kernel's epilogue; everything else is refused loudly, never routed
         // through an unpacked result + a second launch
         OQ_REQUIRE(c.emit_q && sh.grid.bits == 4 && sh.fused && K % g == 0 && !c.mse, OQ_ERR_UNSUPPORTED,
                    "KN_PACKED4 layout needs a 4-bit type, the group strategy with K %% group_size == 0 and group_size <= 256, no mse");
-        OQ_REQUIRE(N % 4 == 0 && ldw % 4 == 0 && aligned16(c.W) && (reinterpret_cast<uintptr_t>(c.q) & 3u) == 0, OQ_ERR_UNSUPPORTED,
+        OQ_REQUIRE(N % 4 == 0 && ldw % 4 == 0 && aligned16(c.W) && aligned_to(c.q, 4), OQ_ERR_UNSUPPORTED,
                    "KN_PACKED4 layout needs N %% 4 == 0, ldw %% 4 == 0, a 16-byte aligned W and a 4-byte aligned output");
     }
     if (c.strategy == OQ_GROUP && K % g != 0) {   // the flat straddling groups: nothing below applies
@@ -1501,7 +1528,7 @@ static RtnPlan plan_route(const RtnCall& c, const RtnShape& sh, hipStream_t s) {
         const int64_t nct = ceil_div(N, kColsPerWave), nparams = kgroups * N;
         const bool direct = nct % 8 == 0 || nparams <= (256 << 10) || (nct % 2 == 0 && nparams <= (512 << 10));
         p.staged = c.layout != OQ_LAYOUT_NBITS && !direct && sh.vec4 && kgroups > 1 && c.workspace != nullptr &&
-                   c.workspace_bytes >= static_cast<size_t>(c.batch) * stage_ws(K, N, g) && aligned16(c.workspace);
+                   c.workspace_bytes >= stage_ws(c.batch, K, N, g) && aligned16(c.workspace);
         // With the caller's zeroed state (oq_rtn_quantize_stateful_f32) the staged parameters are transposed inside the
         // launch, by blocks appended to the grid, instead of by a second launch (see transposer_block).
         // Measured (scripts/lab_kn_inlaunch.py, same box, staged + launch -> in the launch, us; the shipped transposer: one block per 128
@@ -1512,7 +1539,7 @@ static RtnPlan plan_route(const RtnCall& c, const RtnShape& sh, hipStream_t s) {
         // launch: up to 64 k-groups.  Speed only.
         p.in_launch = p.staged && c.emit_q && (c.layout == OQ_LAYOUT_KN_PACKED4 || c.layout == OQ_LAYOUT_KN) && kgroups <= 64 &&
                       in_launch_shape(K, N, g) && c.batch == 1 && c.table == nullptr && c.state != nullptr &&
-                      c.state_bytes >= fused_state_bytes(K, N, g) && aligned16(c.scale) && (reinterpret_cast<uintptr_t>(c.zp) & 3u) == 0 &&
+                      c.state_bytes >= fused_state_bytes(K, N, g) && aligned16(c.scale) && aligned_to(c.zp, 4) &&
                       !rtn_stream_is_capturing(s) && in_launch_fits(N);
         return p;
     }
@@ -1586,12 +1613,16 @@ static int32_t launch_wave(const RtnCall& c, const RtnShape& sh, hipStream_t s) 
 static int32_t launch_fused(const RtnCall& c, const RtnShape& sh, const RtnPlan& p, hipStream_t s) {
     const int64_t N = c.N, kgroups = sh.kgroups;
     RtnArgs a = group_args(c, sh);
-    if (p.in_launch) {
-        a.tr_scale = static_cast<float*>(c.state);
-        a.tr_zp = reinterpret_cast<uint2*>(static_cast<uint8_t*>(c.state) + (kgroups * N * 4 + 255) / 256 * 256);
+    if (p.in_launch) {            // plan_route has checked that either buffer holds its layout
+        Workspace ws(c.state, c.state_bytes);
+        const FusedState st = fused_state_layout(c.K, N, sh.g, ws);
+        a.tr_scale = st.scale;
+        a.tr_zp = st.zp;
     } else if (p.staged) {
-        a.scale_t = static_cast<float*>(c.workspace);
-        a.zp_t = static_cast<uint8_t*>(c.workspace) + (c.batch * kgroups * N * 4 + 255) / 256 * 256;
+        Workspace ws(c.workspace, c.workspace_bytes);
+        const StageWs st = stage_layout(c.batch, c.K, N, sh.g, ws);
+        a.scale_t = st.scale;
+        a.zp_t = st.zp;
     }
     a.wpg = sh.wpg;
     for (uint32_t pr = 0; pr < 8; ++pr) a.pair_owner |= (pr % static_cast<uint32_t>(sh.wpg)) << (3 * pr);
@@ -1706,13 +1737,10 @@ size_t oq_rtn_workspace_bytes(int64_t K, int64_t N, int32_t strategy, int64_t gr
     int64_t g;
     if (oq::resolve_group(strategy, K, group_size, &g) != OQ_OK) return 0;
     if (strategy == OQ_GROUP && K % g != 0) return 0;
-    size_t need = oq::twopass_ws(K, N, g);
-    const size_t st = oq::stage_ws(K, N, g);
-    if (st > need) need = st;
-    const size_t rs = oq::rtn_resident_workspace(K, N, strategy, g);
-    if (rs > need) need = rs;
-    if (mse) need += oq::rtn_mse_workspace(K, N, strategy, g);
-    return need + 256;
+    // one workspace for whichever route takes the call: the partial ranges of the three launches (one array at the caller's pointer),
+    // the staged parameters of the fused route, the words of the ticketed kernels; the MSE search's comes on top
+    const size_t need = std::max({oq::twopass_ws(K, N, g), oq::stage_ws(1, K, N, g), oq::rtn_resident_workspace(K, N, strategy, g)});
+    return need + (mse ? oq::rtn_mse_workspace(K, N, strategy, g) : 0);
 }
 
 int32_t oq_rtn_quantize_f32(const float* W, int64_t K, int64_t N, int64_t ldw, int32_t qtype, int32_t strategy,
@@ -1737,7 +1765,7 @@ int32_t oq_rtn_quantize_stateful_f32(const float* W, int64_t K, int64_t N, int64
                                      int64_t group_size, int32_t symmetric, int32_t reduce_range, float clip_ratio,
                                      int32_t mse, void* q_out, float* scale_out, void* zp_out, int32_t layout,
                                      void* workspace, size_t workspace_bytes, void* state, size_t state_bytes, void* stream) {
-    OQ_REQUIRE(state == nullptr || (reinterpret_cast<uintptr_t>(state) & 15u) == 0, OQ_ERR_INVALID_ARGUMENT,
+    OQ_REQUIRE(state == nullptr || oq::aligned_to(state, 16), OQ_ERR_INVALID_ARGUMENT,
                "oq_rtn_quantize_stateful_f32: state must be 16-byte aligned");
     oq::RtnCall c{W, K, N, ldw, qtype, strategy, group_size, symmetric, reduce_range, clip_ratio, mse, q_out, scale_out, zp_out, layout,
                   workspace, workspace_bytes, stream};
@@ -1758,7 +1786,7 @@ size_t oq_rtn_batched_workspace_bytes(int64_t batch, int64_t K, int64_t N, int64
     if (batch <= 0 || batch > 65535 || !oq::matrix_ok(K, N, N)) return 0;
     int64_t g;
     if (oq::resolve_group(OQ_GROUP, K, group_size, &g) != OQ_OK || K % g != 0) return 0;
-    return static_cast<size_t>(batch) * oq::stage_ws(K, N, g) + 512;
+    return oq::stage_ws(batch, K, N, g);
 }
 
 int32_t oq_rtn_quantize_batched_f32(const float* W, int64_t batch, int64_t w_stride, int64_t K, int64_t N, int64_t ldw, int32_t qtype,
@@ -1805,7 +1833,7 @@ int32_t oq_rtn_quantize_ptrs_f32(const oq_rtn_ptrs* table_host, const oq_rtn_ptr
     for (int64_t i = 0; i < count; ++i) {
         const oq_rtn_ptrs& p = table_host[i];
         OQ_REQUIRE(p.W && p.q_out && p.scale_out && p.zp_out, OQ_ERR_INVALID_ARGUMENT, "oq_rtn_quantize_ptrs_f32: null pointer in entry %lld", (long long)i);
-        OQ_REQUIRE(oq::aligned16(p.W) && oq::aligned16(p.q_out) && (reinterpret_cast<uintptr_t>(p.scale_out) & 3u) == 0, OQ_ERR_UNSUPPORTED,
+        OQ_REQUIRE(oq::aligned16(p.W) && oq::aligned16(p.q_out) && oq::aligned_to(p.scale_out, 4), OQ_ERR_UNSUPPORTED,
                    "oq_rtn_quantize_ptrs_f32: entry %lld is not 16-byte aligned", (long long)i);
     }
     // How many matrices share a launch (blockIdx.y = entry): oq::matrices_per_launch.

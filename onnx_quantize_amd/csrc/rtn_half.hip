@@ -633,7 +633,7 @@ int32_t oq_rtn_mse_h16(const void* W, int32_t wtype, int64_t K, int64_t N, int64
     OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need && aligned_to(workspace, 4), OQ_ERR_WORKSPACE,
                "%s: workspace of %zu bytes (4-byte aligned) needed, %zu given", fn, need, workspace ? workspace_bytes : static_cast<size_t>(0));
     // clip_ratio is validated and then not applied: the MSE range replaces the clipped one (rtn_mse_impl)
-    return rtn_mse_half_impl(W, wtype, K, N, ldw, a.grid, strategy, a.g, q_out, scale_out, zp_out, workspace, as_stream(stream));
+    return rtn_mse_half_impl(W, wtype, K, N, ldw, a.grid, strategy, a.g, q_out, scale_out, zp_out, workspace, workspace_bytes, as_stream(stream));
 }
 
 int32_t oq_rtn_quantize_ptrs_h16(const oq_rtn_ptrs_h16* table_host, const oq_rtn_ptrs_h16* table_device, int64_t count, int32_t wtype,

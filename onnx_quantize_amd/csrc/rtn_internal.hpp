@@ -56,7 +56,7 @@ int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QG
 size_t rtn_mse_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g);
 // the same search on a 2-byte matrix (`wtype`: an oq_wtype); q_out null: parameters only.  The caller (oq_rtn_mse_h16) has made every check.
 int32_t rtn_mse_half_impl(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g,
-                          void* q_out, float* scale_out, void* zp_out, void* workspace, hipStream_t s);
+                          void* q_out, float* scale_out, void* zp_out, void* workspace, size_t workspace_bytes, hipStream_t s);
 
 // rtn_half.hip: the stored-parameter pass of the two-launch route (half_quantize: [K, N] bytes, the IEEE division), also the final
 // pass of the half MSE search; parameter col * kgroups + kg, or the one pair of a tensor

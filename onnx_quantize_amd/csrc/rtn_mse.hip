@@ -360,27 +360,50 @@ __global__ void mse_resolve_kernel(const MseRow* rows, int64_t count, const uint
     zp[r] = static_cast<uint8_t>(qp.zp);
 }
 
-size_t rtn_mse_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
+// The search's workspace, measured and carved by this one function (workspace.hpp).
+struct MseWs {
+    uint32_t* any_mask;   // the stop word
+    float* range;         // tensor strategy: raw (min, max) of the matrix
+    MseRow* rowbuf;       // [rows]
+    float* partial;       // tensor strategy: [blocks, kMseSteps] partial errors
+};
+constexpr int kMseTensorBlocks = 1024;
+
+static MseWs mse_layout(int64_t K, int64_t N, int32_t strategy, int64_t g, Workspace& ws) {
     const int64_t rows = strategy == OQ_TENSOR ? 1 : N * (K / g);
-    return static_cast<size_t>(rows) * sizeof(MseRow) + 1024 * kMseSteps * sizeof(float) + 512;
+    MseWs w;
+    char* const head = ws.take(256);      // a unit of its own for the two small ones; the sizes are those of include/oq_hip_half.h, to the byte
+    w.any_mask = reinterpret_cast<uint32_t*>(head);
+    w.range = head ? reinterpret_cast<float*>(head + 16) : nullptr;
+    w.rowbuf = ws.take<MseRow>(static_cast<size_t>(rows) * sizeof(MseRow), alignof(MseRow));
+    w.partial = ws.take<float>(static_cast<size_t>(kMseTensorBlocks) * kMseSteps * sizeof(float), 4);
+    return w;
+}
+
+size_t rtn_mse_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
+    Workspace ws;
+    mse_layout(K, N, strategy, g, ws);
+    return ws.total();
 }
 
 // The search itself, from the cleared stop word to the resolved (scale, zp) of every row: one implementation for the three
-// element types.  `grid` is the search's own (clip_ratio 1); the workspace has been checked.
+// element types.  `grid` is the search's own (clip_ratio 1).
 template <typename E>
 static int32_t mse_search(const typename E::raw* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid, int32_t strategy, int64_t g,
-                          float* scale_out, void* zp_out, void* workspace, hipStream_t s) {
+                          float* scale_out, void* zp_out, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const int64_t kgroups = strategy == OQ_TENSOR ? 1 : K / g;
     const int64_t rows = strategy == OQ_TENSOR ? 1 : N * kgroups;
-    char* base = static_cast<char*>(workspace);
-    uint32_t* any_mask = reinterpret_cast<uint32_t*>(base);
-    float* range = reinterpret_cast<float*>(base + 16);
-    MseRow* rowbuf = reinterpret_cast<MseRow*>(base + 256);
-    float* partial = reinterpret_cast<float*>(base + 256 + static_cast<size_t>(rows) * sizeof(MseRow));
+    Workspace ws(workspace, workspace_bytes);
+    const MseWs w = mse_layout(K, N, strategy, g, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "rtn(mse): workspace of %zu bytes needed, %zu given", ws.total(), workspace ? workspace_bytes : size_t{0});
+    uint32_t* any_mask = w.any_mask;
+    float* range = w.range;
+    MseRow* rowbuf = w.rowbuf;
+    float* partial = w.partial;
     if (hipMemsetAsync(any_mask, 0, 4, s) != hipSuccess) return fail(OQ_ERR_LAUNCH, "rtn(mse): memset failed");
     int32_t st;
     if (strategy == OQ_TENSOR) {
-        const int nblocks = 1024;
+        const int nblocks = kMseTensorBlocks;
         hipLaunchKernelGGL(tensor_minmax_kernel<E>, dim3(1), dim3(1024), 0, s, W, K, N, ldw, range);
         hipLaunchKernelGGL(mse_tensor_partial<E>, dim3(nblocks), dim3(256), 0, s, W, K, N, ldw, range, grid, partial);
         hipLaunchKernelGGL(mse_tensor_mask, dim3(1), dim3(64), 0, s, partial, nblocks, range, rowbuf, any_mask);
@@ -405,13 +428,10 @@ static int32_t mse_search(const typename E::raw* W, int64_t K, int64_t N, int64_
 int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QGrid& grid_in, int32_t strategy, int64_t g,
                      void* q_out, float* scale_out, void* zp_out, int32_t zp_signed, void* workspace, size_t workspace_bytes,
                      hipStream_t s, bool emit_q) {
-    const size_t need = rtn_mse_workspace(K, N, strategy, g);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "rtn(mse): workspace of %zu bytes needed, %zu given", need,
-               workspace_bytes);
     QGrid grid = grid_in;
     grid.clip_ratio = 1.0f;  // utils.py:188 and :334-344: the MSE range replaces the clipped one
     const int64_t kgroups = strategy == OQ_TENSOR ? 1 : K / g;
-    const int32_t st = mse_search<ElemF32>(W, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s);
+    const int32_t st = mse_search<ElemF32>(W, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, workspace_bytes, s);
     if (st != OQ_OK || !emit_q) return st;
     return launch_quantize_kn(W, K, N, ldw, g, kgroups, scale_out, static_cast<const uint8_t*>(zp_out), static_cast<uint8_t*>(q_out),
                               grid, zp_signed, strategy == OQ_TENSOR, s, OQ_LAYOUT_KN);
@@ -420,11 +440,11 @@ int32_t rtn_mse_impl(const float* W, int64_t K, int64_t N, int64_t ldw, const QG
 // oq_rtn_mse_h16 (rtn_half.hip makes every check): the same search on the 2-byte matrix, then the stored-parameter pass of the
 // half kernels (IEEE division: the integers launch_quantize_kn gives on the upcast matrix).
 int32_t rtn_mse_half_impl(const void* W, int32_t wtype, int64_t K, int64_t N, int64_t ldw, const QGrid& grid_in, int32_t strategy, int64_t g,
-                          void* q_out, float* scale_out, void* zp_out, void* workspace, hipStream_t s) {
+                          void* q_out, float* scale_out, void* zp_out, void* workspace, size_t workspace_bytes, hipStream_t s) {
     QGrid grid = grid_in;
     grid.clip_ratio = 1.0f;  // as above
     const uint16_t* w = static_cast<const uint16_t*>(W);
-    const int32_t st = with_half_elem(wtype, [&](auto e) { return mse_search<decltype(e)>(w, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, s); });
+    const int32_t st = with_half_elem(wtype, [&](auto e) { return mse_search<decltype(e)>(w, K, N, ldw, grid, strategy, g, scale_out, zp_out, workspace, workspace_bytes, s); });
     if (st != OQ_OK || q_out == nullptr) return st;
     return launch_half_quantize_kn(W, wtype, K, N, ldw, g, strategy == OQ_TENSOR ? 1 : K / g, scale_out, static_cast<uint8_t*>(zp_out),
                                    static_cast<uint8_t*>(q_out), grid, strategy == OQ_TENSOR, s);

@@ -1005,19 +1005,49 @@ static int groups_resident(int64_t g, int64_t ranges) {
     return resident_slots(cache[2], reinterpret_cast<const void*>(rtn_resident_groups<8>), kResWaves * kWave);
 }
 
-size_t rtn_resident_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
+// The words of the state (or of a workspace the host clears), measured and carved by this one function (workspace.hpp).  They follow
+// one another without gaps from a 256-byte boundary: the kernels clean them as one run.
+struct ResidentWs {
+    uint32_t* tickets;      // [0]: the one ticket counter of every kernel
+    uint32_t* done;         // a line of its own between the tickets and the counters (a zeroed state only)
+    uint32_t* counters;     // groups: one line per range; per-tensor: tiles counted
+    uint32_t* key_max;      // groups: [kgroups][columns]; per-tensor: one 16-byte slot {1, max key, complemented min key} per arrival (<= 512 workgroups)
+    uint32_t* key_nmin;     // groups: [kgroups][columns]; per-tensor: 64 replicas x 32 words {go, final max key, final complemented min key}
+};
+static ResidentWs resident_layout(int64_t K, int64_t N, int32_t strategy, int64_t g, Workspace& ws) {
     const int64_t kgroups = K / g, ncol_tiles = ceil_div(N, kResCols);
-    // per-tensor: the words behind the header are slack (a bitmap of kept tiles lived there until the kept tiles moved into the
-    // arrival slots); the size is part of what oq_rtn_workspace_bytes / oq_rtn_state_bytes promise and stays
-    if (strategy == OQ_TENSOR) return static_cast<size_t>(kResTensorHeader + (2 * ncol_tiles * ceil_div(K, kResTileRows) + 31) / 32 + 1) * 4 + 256;
-    return static_cast<size_t>(2 * kgroups * ncol_tiles * kResCols + ncol_tiles * kgroups * kResCtrPad + kResHeader) * 4 + 256;
+    const auto words = [&ws](int64_t n) { return ws.take<uint32_t>(static_cast<size_t>(n) * 4, 4); };
+    ResidentWs w;
+    if (strategy == OQ_TENSOR) {
+        static_assert(kResTensorHeader == 64 + 64 + 64 * 32 + 64 * 32, "the four pieces below");
+        w.tickets = words(64);
+        w.counters = words(64);
+        w.key_max = words(64 * 32);
+        w.key_nmin = words(64 * 32);
+        // slack (a bitmap of kept tiles lived here until the kept tiles moved into the arrival slots); the size is part of what
+        // oq_rtn_workspace_bytes / oq_rtn_state_bytes promise and stays
+        words((2 * ncol_tiles * ceil_div(K, kResTileRows) + 31) / 32 + 1);
+    } else {
+        w.tickets = words(kResHeader);
+        w.counters = words(ncol_tiles * kgroups * kResCtrPad);
+        w.key_max = words(kgroups * ncol_tiles * kResCols);
+        w.key_nmin = words(kgroups * ncol_tiles * kResCols);
+    }
+    w.done = w.tickets ? w.tickets + 40 : nullptr;
+    return w;
+}
+
+size_t rtn_resident_workspace(int64_t K, int64_t N, int32_t strategy, int64_t g) {
+    Workspace ws;
+    resident_layout(K, N, strategy, g, ws);
+    return ws.total();
 }
 
 // true when this path takes the call (the caller falls back to the three-launch path otherwise)
 bool rtn_resident_eligible(int64_t K, int64_t N, int64_t ldw, const float* W, const void* q, int32_t strategy, int64_t g, int32_t layout,
                            bool emit_q, size_t workspace_bytes) {
     if (!emit_q || layout != OQ_LAYOUT_KN) return false;
-    if ((N % 4) || (ldw % 4) || (reinterpret_cast<uintptr_t>(W) & 15u) || (reinterpret_cast<uintptr_t>(q) & 3u)) return false;
+    if ((N % 4) || (ldw % 4) || !aligned_to(W, 16) || !aligned_to(q, 4)) return false;
     if (K % g) return false;
     const int64_t chunks = ceil_div(g, strategy == OQ_TENSOR ? kResTileRows : groups_tile_rows(g, ranges_of(K, N, g)));
     const int64_t ntiles = ceil_div(N, kResCols) * (K / g) * chunks;
@@ -1114,23 +1144,21 @@ static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t
     a.W = W; a.K = K; a.N = N; a.ldw = ldw; a.g = g; a.kgroups = K / g; a.chunks = ceil_div(g, strategy == OQ_TENSOR ? kResTileRows : tile_rows);
     a.q = q; a.scale = scale; a.zp = zp; a.grid = grid;
     a.ncol_tiles = static_cast<uint32_t>(ceil_div(N, kResCols));
-    const size_t need = rtn_resident_workspace(K, N, strategy, g);
-    OQ_REQUIRE(workspace && workspace_bytes >= need, OQ_ERR_WORKSPACE, "rtn: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    uint32_t* base = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~static_cast<uintptr_t>(255));
-    a.done = nullptr; a.clean_base = base; a.clean_words = static_cast<uint32_t>((need - 256) / 4);
-    if (zeroed_state) {
-        a.done = base + 40;           // a line of its own between the tickets and the counters
-    } else {
-        const uint32_t n16 = static_cast<uint32_t>((need - 256 + 15) / 16);   // `need` counts whole words past the aligned base; the +256 slack covers the round-up
-        hipLaunchKernelGGL(clear_words_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, reinterpret_cast<uint4*>(base), n16);
-    }
-    a.tickets = base;                 // [0]: the one ticket counter of every kernel
-    a.counters = base + kResHeader;   // groups: one per range
+    Workspace ws(workspace, workspace_bytes);
+    const ResidentWs rw = resident_layout(K, N, strategy, g, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "rtn: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
+    // The words are cleaned 16 bytes at a time, by the host here and by the last workgroup of a kernel: whole 16 bytes only, so that no
+    // store leaves the workspace (the words of the groups are a multiple of four; of the per-tensor state up to three slack words stay out).
+    const uint32_t n16 = static_cast<uint32_t>((ws.total() - Workspace::kAlign) / 16);
+    a.done = nullptr; a.clean_base = rw.tickets; a.clean_words = 4 * n16;
+    if (zeroed_state) a.done = rw.done;
+    else hipLaunchKernelGGL(clear_words_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, reinterpret_cast<uint4*>(rw.tickets), n16);
+    a.tickets = rw.tickets;
+    a.counters = rw.counters;
+    a.key_max = rw.key_max;
+    a.key_nmin = rw.key_nmin;
     if (strategy == OQ_TENSOR) {
         a.ntiles = a.ncol_tiles * static_cast<uint32_t>(ceil_div(K, kResTileRows));
-        a.counters = base + 64;                  // tiles counted
-        a.key_max = base + 128;                  // one 16-byte slot {1, max key, complemented min key} per arrival (<= 512 workgroups)
-        a.key_nmin = base + 128 + 64 * 32;       // 64 replicas x 32 words: {go, final max key, final complemented min key}
         static std::atomic<int> cache[64];
         const int resident = resident_slots(cache, reinterpret_cast<const void*>(rtn_tensor_onepass), kResWaves * kWave, kParkBytes);
         OQ_REQUIRE(resident > 0, OQ_ERR_LAUNCH, "rtn: occupancy query failed");
@@ -1141,8 +1169,6 @@ static int32_t rtn_resident_launch(const float* W, int64_t K, int64_t N, int64_t
     }
     const int64_t ranges = static_cast<int64_t>(a.ncol_tiles) * a.kgroups;
     a.ntiles = static_cast<uint32_t>(ranges * a.chunks);
-    a.key_max = a.counters + ranges * kResCtrPad;
-    a.key_nmin = a.key_max + a.kgroups * static_cast<int64_t>(a.ncol_tiles) * kResCols;
     if (!groups_streamed(g, ranges)) {
         if (tile_rows == 256) hipLaunchKernelGGL((rtn_resident_groups<16>), dim3(a.ntiles), dim3(16 * kWave), 0, s, a);
         else hipLaunchKernelGGL((rtn_resident_groups<8>), dim3(a.ntiles), dim3(8 * kWave), 0, s, a);

@@ -1194,16 +1194,36 @@ size_t syrk_bf16x3_pieces_bytes(int64_t T, int64_t K) {
 int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, unsigned char* base, float* slab,
                            size_t slab_bytes, int terms, int phases, hipStream_t s);
 
+// The workspace of a single update (workspace.hpp): the operand's pieces (or its packed plane), then T-slice slabs -- `slab_budget`
+// bytes where it is measured, as far as the caller's workspace goes where it is carved.
+struct SyrkWs {
+    unsigned char* operand;
+    float* slab;
+    size_t slab_bytes;
+};
+static SyrkWs syrk_layout(size_t operand_bytes, size_t slab_budget, Workspace& ws) {
+    SyrkWs w;
+    w.operand = ws.take<unsigned char>(operand_bytes);
+    w.slab_bytes = ws.carving() ? ws.left(4) : slab_budget;
+    w.slab = ws.take<float>(w.slab_bytes, 4);
+    return w;
+}
+
+size_t syrk_bf16x3_workspace_bytes(int64_t T, int64_t K, size_t slab_budget) {
+    Workspace ws;
+    syrk_layout(syrk_bf16x3_pieces_bytes(T, K), slab_budget, ws);
+    return ws.total();
+}
+
 int32_t launch_syrk_bf16x3(const float* X, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, void* workspace,
                            size_t workspace_bytes, int terms, hipStream_t s) {
     OQ_REQUIRE(X != nullptr && C != nullptr && T > 0 && K >= 1 && ldx >= K, OQ_ERR_INVALID_ARGUMENT, "syrk_bf16x3: bad argument");
     OQ_REQUIRE(terms == 3 || terms == 6 || terms == 9, OQ_ERR_INVALID_ARGUMENT, "syrk_bf16x3: terms must be 3 (fp16 pieces), 6 or 9");
-    const size_t pieces = syrk_bf16x3_pieces_bytes(T, K);
-    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= pieces + 256, OQ_ERR_WORKSPACE,
-               "syrk_bf16x3: workspace of %zu bytes needed for the operand pieces, %zu given", pieces + 256, workspace_bytes);
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
-    return syrk_pieces_phases(X, T, K, ldx, alpha, beta, C, base, reinterpret_cast<float*>(base + pieces), workspace_bytes - pieces - 256, terms, 3, s);
+    Workspace ws(workspace, workspace_bytes);
+    const SyrkWs w = syrk_layout(syrk_bf16x3_pieces_bytes(T, K), 0, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "syrk_bf16x3: workspace of %zu bytes needed for the operand pieces, %zu given",
+               syrk_bf16x3_workspace_bytes(T, K, 0), workspace_bytes);
+    return syrk_pieces_phases(X, T, K, ldx, alpha, beta, C, w.operand, w.slab, w.slab_bytes, terms, 3, s);
 }
 
 // T-slices of a symmetric product on 256 x 256 tiles (one block per CU, 256 CUs): the slice count (<= 16, slices of >= 512 rows,
@@ -1286,17 +1306,34 @@ int32_t syrk_pieces_phases(const float* X, int64_t T, int64_t K, int64_t ldx, fl
 static size_t syrk_many_item_bytes(int64_t T, int64_t K) {
     return kScaleHeaderBytes + static_cast<size_t>(stages_of(T, F16Stage::ROWS)) * F16Stage::CH * 2 * static_cast<size_t>(padded_k(K)) * 16;
 }
-static size_t syrk_many_table_bytes(int64_t count) { return (static_cast<size_t>(count) * sizeof(SyrkItem) + 255) / 256 * 256; }
+// the workspace of a `many` chain (workspace.hpp): the device table of its items, then the items' pieces back to back
+struct SyrkManyWs {
+    SyrkItem* table;
+    unsigned char* pieces;
+};
+static SyrkManyWs syrk_many_layout(int64_t count, size_t pieces_bytes, Workspace& ws) {
+    SyrkManyWs w;
+    w.table = ws.take<SyrkItem>(static_cast<size_t>(count) * sizeof(SyrkItem));
+    w.pieces = ws.take<unsigned char>(pieces_bytes);
+    return w;
+}
 
-size_t syrk_f16x3_many_workspace_bytes(const int64_t* items_host, int64_t count) {
-    if (items_host == nullptr || count <= 0 || count > 65535) return 256;
-    size_t total = syrk_many_table_bytes(count) + 512;
+// pieces of all items of a public table; 0: an item outside the bounds (refused by the call itself)
+static size_t syrk_many_pieces_bytes(const int64_t* items_host, int64_t count) {
+    size_t total = 0;
     for (int64_t m = 0; m < count; ++m) {
         const int64_t T = items_host[m * 8 + 2], K = items_host[m * 8 + 3];
-        if (!matrix_ok(T, K, K) || K > kMaxHessianWidth) return 256;      // refused by the call itself
+        if (!matrix_ok(T, K, K) || K > kMaxHessianWidth) return 0;
         total += syrk_many_item_bytes(T, K);
     }
     return total;
+}
+
+size_t syrk_f16x3_many_workspace_bytes(const int64_t* items_host, int64_t count) {
+    Workspace ws;
+    const size_t pieces = (items_host == nullptr || count <= 0 || count > 65535) ? 0 : syrk_many_pieces_bytes(items_host, count);
+    if (pieces != 0) syrk_many_layout(count, pieces, ws);
+    return ws.total();
 }
 
 int32_t launch_syrk_f16x3_many(const int64_t* items_host, const int64_t* items_device, int64_t count, void* workspace, size_t workspace_bytes,
@@ -1314,12 +1351,11 @@ int32_t launch_syrk_f16x3_many(const int64_t* items_host, const int64_t* items_d
         tiles += tn * (tn + 1) / 2;
     }
     OQ_REQUIRE(split_blocks < (1ll << 31) && tiles < (1ll << 31), OQ_ERR_UNSUPPORTED, "hessian_many: too many blocks for one launch");
-    const size_t need = syrk_f16x3_many_workspace_bytes(items_host, count);
-    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "hessian_many: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
-    SyrkItem* table = reinterpret_cast<SyrkItem*>(base);
-    unsigned char* pieces = base + syrk_many_table_bytes(count);
+    Workspace ws(workspace, workspace_bytes);
+    const SyrkManyWs mw = syrk_many_layout(count, syrk_many_pieces_bytes(items_host, count), ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "hessian_many: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
+    SyrkItem* const table = mw.table;
+    unsigned char* const pieces = mw.pieces;
     const int n = static_cast<int>(count);
     hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&syrk_f16_m16_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F16Stage::LDS);
     OQ_REQUIRE(e1 == hipSuccess, OQ_ERR_LAUNCH, "hessian_many: cannot reserve %d bytes of LDS", F16Stage::LDS);
@@ -1335,19 +1371,20 @@ int32_t launch_syrk_f16x3_many(const int64_t* items_host, const int64_t* items_d
 
 size_t syrk_f16x3_factor_update_bytes(int64_t K, int64_t kd_max, int64_t count) {
     if (K <= 0 || kd_max <= 0 || count <= 0) return 0;
-    return syrk_many_table_bytes(count) + static_cast<size_t>(count) * syrk_many_item_bytes(kd_max, K) + 512;
+    Workspace ws;
+    syrk_many_layout(count, static_cast<size_t>(count) * syrk_many_item_bytes(kd_max, K), ws);
+    return ws.total();
 }
 
 int32_t launch_syrk_f16x3_factor_update(const float* Lt, float* P, int64_t ms, int64_t count, int64_t K, int64_t O, int64_t pend, void* workspace,
                                         size_t workspace_bytes, hipStream_t s) {
     const int64_t rest = K - pend, kd = pend - O;
     OQ_REQUIRE(Lt && P && count > 0 && count <= 65535 && rest > 0 && kd > 0, OQ_ERR_INVALID_ARGUMENT, "factor update: bad argument");
-    const size_t need = syrk_f16x3_factor_update_bytes(rest, kd, count);
-    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "factor update: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
-    SyrkItem* table = reinterpret_cast<SyrkItem*>(base);
-    unsigned char* pieces = base + syrk_many_table_bytes(count);
+    Workspace ws(workspace, workspace_bytes);
+    const SyrkManyWs mw = syrk_many_layout(count, static_cast<size_t>(count) * syrk_many_item_bytes(kd, rest), ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "factor update: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
+    SyrkItem* const table = mw.table;
+    unsigned char* const pieces = mw.pieces;
     const int n = static_cast<int>(count);
     const int64_t Kp = padded_k(rest), nchunks = stages_of(kd, F16Stage::ROWS) * F16Stage::CH, tn = Kp / kST;
     const int64_t split_blocks = count * (Kp / 256) * ceil_div(nchunks, 4), tiles = count * (tn * (tn + 1) / 2);
@@ -1367,23 +1404,38 @@ static size_t piece_bytes_host(int64_t T, int64_t cols) {
 }
 static int64_t split_blocks_host(int64_t T, int64_t cols) { return (padded_k(cols) / 256) * ceil_div(stages_of(T, F16Stage::ROWS) * F16Stage::CH, 4); }
 
+// the workspace of one level (workspace.hpp): per problem four preparation items and two products, then the operand pieces
+struct InverseLevelWs {
+    SyrkItem* prep;
+    PieceGemm* gemms;
+    unsigned char* pieces;
+};
+static InverseLevelWs inverse_level_layout(int64_t b, int64_t b2, int64_t problems, Workspace& ws) {
+    const size_t n = static_cast<size_t>(problems);
+    InverseLevelWs w;
+    w.prep = ws.take<SyrkItem>(n * 4 * sizeof(SyrkItem), alignof(SyrkItem));
+    w.gemms = ws.take<PieceGemm>(n * 2 * sizeof(PieceGemm), alignof(PieceGemm));
+    w.pieces = ws.take<unsigned char>(n * (piece_bytes_host(b, b2) + piece_bytes_host(b, b) + piece_bytes_host(b2, b2) + piece_bytes_host(b2, b)));
+    return w;
+}
+
 size_t inverse_level_f16x3_bytes(int64_t b, int64_t b2, int64_t problems) {
     if (b <= 0 || b2 <= 0 || problems <= 0) return 0;
-    const size_t tables = (static_cast<size_t>(problems) * (4 * sizeof(SyrkItem) + 2 * sizeof(PieceGemm)) + 255) / 256 * 256;
-    return tables + static_cast<size_t>(problems) * (piece_bytes_host(b, b2) + piece_bytes_host(b, b) + piece_bytes_host(b2, b2) + piece_bytes_host(b2, b)) + 512;
+    Workspace ws;
+    inverse_level_layout(b, b2, problems, ws);
+    return ws.total();
 }
 
 int32_t launch_inverse_level_f16x3(const float* Lt, float* X, float* Y, float* S, int64_t ms, int64_t count, int64_t K, int64_t b, int64_t first,
                                    int64_t pairs, int64_t b2, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const int64_t n = pairs * count;
     OQ_REQUIRE(Lt && X && Y && S && n > 0 && n <= 65535 && b > 0 && b2 > 0 && b2 <= b, OQ_ERR_INVALID_ARGUMENT, "inverse level: bad argument");
-    const size_t need = inverse_level_f16x3_bytes(b, b2, n);
-    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "inverse level: workspace of %zu bytes needed, %zu given", need, workspace_bytes);
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
-    SyrkItem* prep = reinterpret_cast<SyrkItem*>(base);
-    PieceGemm* gemms = reinterpret_cast<PieceGemm*>(base + static_cast<size_t>(n) * 4 * sizeof(SyrkItem));
-    unsigned char* pieces = base + (static_cast<size_t>(n) * (4 * sizeof(SyrkItem) + 2 * sizeof(PieceGemm)) + 255) / 256 * 256;
+    Workspace ws(workspace, workspace_bytes);
+    const InverseLevelWs lw = inverse_level_layout(b, b2, n, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "inverse level: workspace of %zu bytes needed, %zu given", ws.total(), workspace_bytes);
+    SyrkItem* const prep = lw.prep;
+    PieceGemm* const gemms = lw.gemms;
+    unsigned char* const pieces = lw.pieces;
     const int64_t split1 = n * (split_blocks_host(b, b2) + split_blocks_host(b, b) + split_blocks_host(b2, b2)), split2 = n * split_blocks_host(b2, b);
     const int64_t tiles = (padded_k(b2) / kST) * (padded_k(b) / kST);
     OQ_REQUIRE(split1 < (1ll << 31) && split2 < (1ll << 31) && tiles < (1ll << 31), OQ_ERR_UNSUPPORTED, "inverse level: too many blocks for one launch");
@@ -1580,7 +1632,11 @@ __global__ __launch_bounds__(kSThreads) void syrk_h16_kernel(const u32x4* __rest
 constexpr int kH16StageRows = 32;      // four 8-row chunks: one k-step of the 16x16x32 instructions
 static size_t syrk_h16_plane_bytes(int64_t T, int64_t K) { return static_cast<size_t>(stages_of(T, kH16StageRows)) * 4 * static_cast<size_t>(padded_k(K)) * 16; }
 
-size_t syrk_h16_pieces_bytes(int64_t T, int64_t K) { return (T <= 0 || K <= 0) ? 0 : syrk_h16_plane_bytes(T, K); }
+size_t syrk_h16_workspace_bytes(int64_t T, int64_t K, size_t slab_budget) {
+    Workspace ws;
+    syrk_layout(syrk_h16_plane_bytes(T, K), slab_budget, ws);
+    return ws.total();
+}
 
 template <typename FRAG>
 static int32_t launch_syrk_h16_typed(const u32x4* P, int64_t K, int64_t Kp, int64_t nstages, float alpha, float beta, float* C, float* slab,
@@ -1604,12 +1660,13 @@ static int32_t launch_syrk_h16_typed(const u32x4* P, int64_t K, int64_t Kp, int6
 int32_t launch_syrk_h16(const void* X, bool bf16, int64_t T, int64_t K, int64_t ldx, float alpha, float beta, float* C, void* workspace,
                         size_t workspace_bytes, hipStream_t s) {
     OQ_REQUIRE(X != nullptr && C != nullptr && T > 0 && K >= 1 && ldx >= K, OQ_ERR_INVALID_ARGUMENT, "syrk_h16: bad argument");
-    const size_t plane = syrk_h16_plane_bytes(T, K);
-    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= plane + 256, OQ_ERR_WORKSPACE, "syrk_h16: workspace of %zu bytes needed for the packed operand, %zu given",
-               plane + 256, workspace ? workspace_bytes : static_cast<size_t>(0));
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
-    u32x4* P = reinterpret_cast<u32x4*>(base);
+    Workspace ws(workspace, workspace_bytes);
+    const SyrkWs w = syrk_layout(syrk_h16_plane_bytes(T, K), 0, ws);
+    OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "syrk_h16: workspace of %zu bytes needed for the packed operand, %zu given",
+               syrk_h16_workspace_bytes(T, K, 0), workspace ? workspace_bytes : static_cast<size_t>(0));
+    u32x4* const P = reinterpret_cast<u32x4*>(w.operand);
+    float* const slab = w.slab;
+    const size_t slab_bytes = w.slab_bytes;
     const int64_t Kp = padded_k(K), nstages = stages_of(T, kH16StageRows), nchunks = nstages * 4;
     const dim3 grid(static_cast<uint32_t>(ceil_div(nchunks, 4)), static_cast<uint32_t>(ceil_div(Kp, 512)));     // x <= 2^26 (T < 2^31), y <= 256
     const uint16_t* X16 = static_cast<const uint16_t*>(X);
@@ -1619,8 +1676,6 @@ int32_t launch_syrk_h16(const void* X, bool bf16, int64_t T, int64_t K, int64_t 
         hipLaunchKernelGGL(pack_h16_kernel<false>, grid, dim3(256), 0, s, X16, T, K, ldx, Kp, nchunks, P);
     const int32_t st = check_launch("pack_h16_kernel");
     if (st != OQ_OK) return st;
-    float* slab = reinterpret_cast<float*>(base + plane);
-    const size_t slab_bytes = workspace_bytes - plane - 256;
     return bf16 ? launch_syrk_h16_typed<bf16x8>(P, K, Kp, nstages, alpha, beta, C, slab, slab_bytes, s)
                 : launch_syrk_h16_typed<f16x8>(P, K, Kp, nstages, alpha, beta, C, slab, slab_bytes, s);
 }
@@ -1694,17 +1749,27 @@ __global__ __launch_bounds__(kSThreads) void syrk_h16_many_kernel(const H16Item*
     syrk_h16_body<FRAG>(it.P, it.K, it.Kp, it.nstages, it.alpha, it.beta, it.C, nullptr, it.nstages, it.tn, static_cast<int>(id - it.tile0), 0, lds);
 }
 
-static size_t syrk_h16_many_table_bytes(int64_t count) { return (static_cast<size_t>(count) * sizeof(H16Item) + 255) / 256 * 256; }
+// the workspace of the chain (workspace.hpp): the device table of its items, then the items' planes back to back
+struct H16ManyWs {
+    H16Item* table;
+    unsigned char* planes;
+};
+static H16ManyWs syrk_h16_many_layout(const int64_t* items_host, int64_t count, Workspace& ws) {
+    size_t planes = 0;
+    for (int64_t m = 0; m < count; ++m) planes += syrk_h16_plane_bytes(items_host[m * 8 + 2], items_host[m * 8 + 3]);
+    H16ManyWs w;
+    w.table = ws.take<H16Item>(static_cast<size_t>(count) * sizeof(H16Item));
+    w.planes = ws.take<unsigned char>(planes);
+    return w;
+}
 
 size_t syrk_h16_many_workspace_bytes(const int64_t* items_host, int64_t count) {
     if (items_host == nullptr || count <= 0 || count > 65535) return 0;
-    size_t total = syrk_h16_many_table_bytes(count) + 512;
-    for (int64_t m = 0; m < count; ++m) {
-        const int64_t T = items_host[m * 8 + 2], K = items_host[m * 8 + 3];
-        if (!matrix_ok(T, K, K) || K > kMaxHessianWidth) return 0;
-        total += syrk_h16_plane_bytes(T, K);
-    }
-    return total;
+    for (int64_t m = 0; m < count; ++m)
+        if (!matrix_ok(items_host[m * 8 + 2], items_host[m * 8 + 3], items_host[m * 8 + 3]) || items_host[m * 8 + 3] > kMaxHessianWidth) return 0;
+    Workspace ws;
+    syrk_h16_many_layout(items_host, count, ws);
+    return ws.total() + 256;      // + 256: the formula of include/oq_hip_half.h asks a unit more than the layout takes; kept to the byte
 }
 
 template <typename FRAG>
@@ -1739,13 +1804,13 @@ int32_t launch_syrk_h16_many(const int64_t* items_host, const int64_t* items_dev
         tiles += tn * (tn + 1) / 2;
     }
     OQ_REQUIRE(pack_blocks < (1ll << 31) && tiles < (1ll << 31), OQ_ERR_UNSUPPORTED, "hessian_many_h16: too many blocks for one launch");
-    const size_t need = syrk_h16_many_workspace_bytes(items_host, count);
-    OQ_REQUIRE(workspace != nullptr && workspace_bytes >= need, OQ_ERR_WORKSPACE, "hessian_many_h16: workspace of %zu bytes needed, %zu given", need,
+    const size_t need = syrk_h16_many_workspace_bytes(items_host, count);      // the header's size: a call with less is refused as before
+    Workspace ws(workspace, workspace_bytes);
+    const H16ManyWs mw = syrk_h16_many_layout(items_host, count, ws);
+    OQ_REQUIRE(ws.fits() && workspace_bytes >= need, OQ_ERR_WORKSPACE, "hessian_many_h16: workspace of %zu bytes needed, %zu given", need,
                workspace ? workspace_bytes : static_cast<size_t>(0));
-    unsigned char* base = static_cast<unsigned char*>(workspace);
-    base += (256 - (reinterpret_cast<uintptr_t>(base) & 255u)) & 255u;
-    H16Item* table = reinterpret_cast<H16Item*>(base);
-    unsigned char* planes = base + syrk_h16_many_table_bytes(count);
+    H16Item* const table = mw.table;
+    unsigned char* const planes = mw.planes;
     const int n = static_cast<int>(count);
     hipLaunchKernelGGL(syrk_h16_many_plan_kernel, dim3(1), dim3(64), 0, s, items_device, n, planes, table);
     hipLaunchKernelGGL(pack_h16_many_kernel, dim3(static_cast<uint32_t>(pack_blocks)), dim3(256), 0, s, table, n);
