@@ -24,7 +24,8 @@
  *   group_size 16                   two groups would share one 32-deep matrix instruction (any g % 32 != 0 is refused).
  *   g_idx                           a permuted group index per k.
  *   bits other than 4 and 8.
- *   a decode-optimised GEMV route   M = 1 ... 16 are correct (a 32-row tile, K split across workgroups), not tuned.
+ * M = 1 ... 16 are correct here (a 32-row tile, K split across workgroups) but not tuned: the decode route is an entry point of its
+ * own, oq_matmul_nbits_decode (oq_hip_nbits_decode.h), which also takes float zero points and group_size 16.
  */
 #ifndef OQ_HIP_NBITS_H
 #define OQ_HIP_NBITS_H

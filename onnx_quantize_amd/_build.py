@@ -35,7 +35,10 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # matmul_nbits.hip: paired, the per-group fold `sum = fma(acc, scale, sum)` becomes v_pk_fma_f32 with an op_sel on the scale pair, and
 # on the MI355X those gave wrong low halves in lanes 48 .. 63 whenever several waves shared a SIMD (docs/LAB_NOTES_r22.md;
 # tests/test_matmul_nbits_gpu.py holds exact products on large grids against it).
-PER_FILE_FLAGS = {"hqq.hip": ("-fno-slp-vectorize",), "matmul_nbits.hip": ("-fno-slp-vectorize",)}
+# matmul_nbits_decode.hip: the same fold, sum = fma(acc, scale, sum), on the vector ALU throughout: built unpaired from its first compile
+# (tests/test_matmul_nbits_decode_resources.py finds no v_pk_fma_f32 in its assembly).
+PER_FILE_FLAGS = {"hqq.hip": ("-fno-slp-vectorize",), "matmul_nbits.hip": ("-fno-slp-vectorize",),
+                  "matmul_nbits_decode.hip": ("-fno-slp-vectorize",)}
 
 
 def flags_for(src: str) -> list[str]:
@@ -55,7 +58,7 @@ def sources() -> list[str]:
 
 def _deps_mtime() -> float:
     hdrs = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith((".hpp", ".h"))]
-    hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h", "oq_hip_qlinear.h"))
+    hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h", "oq_hip_nbits_decode.h", "oq_hip_qlinear.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 

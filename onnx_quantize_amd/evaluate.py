@@ -53,6 +53,9 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     output named ``logits``, or the model's single output; position t predicts token t + 1.  Log-softmax and the sum of the
     negative log-likelihoods run in float64 on the device, and one scalar comes back to the host per call, not per window.
 
+    ``matmul_nbits`` goes to `GraphRunner` as it is: "fused+decode" sends the MatMulNBits nodes of windows of at most 16 tokens to the
+    decode kernel (`ops.matmul_nbits_decode`: HQQ files and block size 16 included).  The default stays "fused".
+
     ``qlinear="fused"`` runs the QLinearMatMul / QGemm nodes of a `format="qlinear"` file on the int8 matrix cores
     (`ops.qlinear_matmul`: exact int32 sums).  The default stays the expansion route: a fused output may differ from it by one
     output level, where the expansion's fp32 sum lands on the other side of a rounding boundary."""

@@ -88,10 +88,15 @@ class GraphRunner:
         # matmul_nbits = "fused": a MatMulNBits node the library has a kernel for (`ops.matmul_nbits`: integer zero points, a block
         # size that is a multiple of 32, 4 / 8 bits, a constant B on the GPU) runs from the blob as stored -- no [N, K] weight is
         # expanded.  Every other node, and every node under "torch", takes the expansion of `_op_MatMulNBits`.
-        if matmul_nbits not in ("torch", "fused"):
-            raise ValueError(f"GraphRunner: matmul_nbits must be 'torch' or 'fused', got {matmul_nbits!r}")
+        # matmul_nbits = "fused+decode": a node whose flattened A has at most 16 rows and which the decode kernel takes
+        # (`ops.matmul_nbits_decode`: also float zero points -- HQQ files -- and block size 16) runs there; every other node goes as
+        # under "fused".  Only this mode counts a third route, "decode".
+        if matmul_nbits not in ("torch", "fused", "fused+decode"):
+            raise ValueError(f"GraphRunner: matmul_nbits must be 'torch', 'fused' or 'fused+decode', got {matmul_nbits!r}")
         self.matmul_nbits = matmul_nbits if self.device.type == "cuda" else "torch"
         self.nbits_calls = {"fused": 0, "torch": 0}      # MatMulNBits nodes run per route (a replayed graph counts its recording only)
+        if self.matmul_nbits == "fused+decode":
+            self.nbits_calls["decode"] = 0
         # qlinear = "fused": a QLinearMatMul / QGemm node the library has a kernel for (`ops.qlinear_matmul`: 8-bit operands on the
         # GPU, per-tensor activation parameters, fp32 scales, a constant 2-D B, alpha = 1, no transA) runs on the int8 matrix cores
         # with an exact int32 sum -- no operand is dequantized.  Every other node, and every node under "torch", takes the expansion.
@@ -1242,7 +1247,12 @@ class GraphRunner:
         import torch
         K, N, bits, g = a["K"], a["N"], a.get("bits", 4), a["block_size"]
         blocks = (K + g - 1) // g
-        if self.matmul_nbits == "fused" and self._nbits_fusable(x, bits, g):
+        if self.matmul_nbits == "fused+decode" and self._nbits_fusable(x, bits, g, decode=True):
+            from .hip import ops
+            self.nbits_calls["decode"] += 1
+            return ops.matmul_nbits_decode(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g,
+                                           bias=x[5] if len(x) > 5 else None)
+        if self.matmul_nbits in ("fused", "fused+decode") and self._nbits_fusable(x, bits, g):
             from .hip import ops
             self.nbits_calls["fused"] += 1
             return ops.matmul_nbits(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g,
@@ -1277,9 +1287,10 @@ class GraphRunner:
         return out
 
 
-    def _nbits_fusable(self, x, bits, g) -> bool:
-        """Whether `ops.matmul_nbits` takes this MatMulNBits node: what the kernel supports, on the GPU, with B, scales and zero
-        points constants of the model as the writer stores them."""
+    def _nbits_fusable(self, x, bits, g, decode: bool = False) -> bool:
+        """Whether `ops.matmul_nbits` (``decode``: `ops.matmul_nbits_decode`, which also wants at most 16 rows of A) takes this
+        MatMulNBits node: what the kernel supports, on the GPU, with B, scales and zero points constants of the model as the
+        writer stores them."""
         import torch
         from .hip import ops
         zp = x[3] if len(x) > 3 else None
@@ -1287,12 +1298,17 @@ class GraphRunner:
         bias = x[5] if len(x) > 5 else None
         if not (isinstance(x[0], torch.Tensor) and x[0].is_cuda and x[0].ndim >= 1 and x[0].numel() > 0):
             return False
-        if ops.matmul_nbits_unsupported(x[0].dtype, bits, g, zp, g_idx) is not None:
+        if decode:
+            rows = x[0].numel() // x[0].shape[-1] if x[0].shape[-1] else 0
+            if ops.matmul_nbits_decode_unsupported(x[0].dtype, bits, g, zp, g_idx, rows=rows) is not None:
+                return False
+        elif ops.matmul_nbits_unsupported(x[0].dtype, bits, g, zp, g_idx) is not None:
             return False
         held = list(self.constants.values())
         if not all(t is None or (t.is_cuda and any(t is c for c in held)) for t in (x[1], x[2], zp)):
             return False
-        return (x[1].dtype == torch.uint8 and x[2].dtype in (torch.float32, x[0].dtype) and (zp is None or zp.dtype == torch.uint8)
+        zp_types = (torch.uint8, torch.float32, x[0].dtype) if decode else (torch.uint8,)
+        return (x[1].dtype == torch.uint8 and x[2].dtype in (torch.float32, x[0].dtype) and (zp is None or zp.dtype in zp_types)
                 and (bias is None or (bias.is_cuda and bias.dtype == x[0].dtype)))
 
     def _qlinear_fusable(self, A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias, trans_b, alpha, trans_a) -> bool:

@@ -33,6 +33,9 @@ WTYPE_CODE = {"float16": OQ_W_F16, "bfloat16": OQ_W_BF16}
 OQ_NBITS_F32, OQ_NBITS_F16, OQ_NBITS_BF16 = range(3)
 OQ_NBITS_FLOAT_ZERO_POINTS, OQ_NBITS_G_IDX = 1, 2
 OQ_NBITS_EXTENSION_VERSION = 1
+# include/oq_hip_nbits_decode.h
+OQ_NBITS_ZP_PACKED_U8 = 3
+OQ_NBITS_DECODE_EXTENSION_VERSION = 1
 # include/oq_hip_qlinear.h
 OQ_QL_U8, OQ_QL_I8 = range(2)
 OQ_QL_KN, OQ_QL_NK = range(2)
@@ -169,6 +172,13 @@ NBITS_PROTOTYPES = {
     "oq_matmul_nbits": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _p, _i32, _p, _p, _i32, _p, _i64, _p, _sz, _p]),
 }
 
+# the decode route of MatMulNBits: mirrors include/oq_hip_nbits_decode.h one to one (tests/test_matmul_nbits_decode_abi.py checks the set)
+NBITS_DECODE_PROTOTYPES = {
+    "oq_nbits_decode_extension_version": (_i32, []),
+    "oq_matmul_nbits_decode_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i32]),
+    "oq_matmul_nbits_decode": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _p, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _sz, _p]),
+}
+
 # the QLinearMatMul / QGemm extension: mirrors include/oq_hip_qlinear.h one to one (tests/test_qlinear_matmul_abi.py checks the set)
 QLINEAR_PROTOTYPES = {
     "oq_qlinear_extension_version": (_i32, []),
@@ -204,7 +214,7 @@ def load() -> C.CDLL:
         except OSError as e:  # missing ROCm runtime etc.
             raise OqHipMissing(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in [*PROTOTYPES.items(), *HALF_PROTOTYPES.items(), *NBITS_PROTOTYPES.items(),
-                                   *QLINEAR_PROTOTYPES.items()]:
+                                   *NBITS_DECODE_PROTOTYPES.items(), *QLINEAR_PROTOTYPES.items()]:
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -219,6 +229,9 @@ def load() -> C.CDLL:
         if lib.oq_nbits_extension_version() != OQ_NBITS_EXTENSION_VERSION:
             raise OqHipMissing(f"{LIB_PATH} has MatMulNBits extension {lib.oq_nbits_extension_version()}, "
                                f"expected {OQ_NBITS_EXTENSION_VERSION}")
+        if lib.oq_nbits_decode_extension_version() != OQ_NBITS_DECODE_EXTENSION_VERSION:
+            raise OqHipMissing(f"{LIB_PATH} has MatMulNBits decode extension {lib.oq_nbits_decode_extension_version()}, "
+                               f"expected {OQ_NBITS_DECODE_EXTENSION_VERSION}")
         if lib.oq_qlinear_extension_version() != OQ_QLINEAR_EXTENSION_VERSION:
             raise OqHipMissing(f"{LIB_PATH} has QLinearMatMul extension {lib.oq_qlinear_extension_version()}, "
                                f"expected {OQ_QLINEAR_EXTENSION_VERSION}")

@@ -53,6 +53,12 @@ def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _raw_stream(device_index: int) -> int:
+    """The handle of the current stream of a device, without building a `torch.cuda.Stream` around it where torch offers that."""
+    raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    return raw(device_index) if raw is not None else torch.cuda.current_stream(device_index).cuda_stream
+
+
 def _require_device(t: torch.Tensor, name: str, dtype=None) -> None:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise TypeError(f"{name} must be a torch tensor in GPU memory (the HIP path has no CPU fallback)")
@@ -1278,6 +1284,95 @@ def matmul_nbits(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero
     ws = _workspace(need, x.device) if need else None
     L.check(lib.oq_matmul_nbits(_ptr(x2), atype, m, K, lda, _ptr(blob), bits, N, g, _ptr(scales), _NBITS_TYPE[scales.dtype], _ptr(zero_points),
                                 _ptr(bias), 0, _ptr(out), N, _ptr(ws), need, _stream()))
+    return out.reshape(*x.shape[:-1], N)
+
+
+DECODE_MAX_ROWS = 16      # include/oq_hip_nbits_decode.h: M of the decode route
+_DECODE_WORKSPACE: dict = {}      # (M, K, N, block size, type code) -> oq_matmul_nbits_decode_workspace_bytes
+
+
+def matmul_nbits_decode_unsupported(x_dtype, bits: int, block_size: int, zero_points=None, g_idx=None, rows: int | None = None) -> str | None:
+    """Why `matmul_nbits_decode` has no kernel for such a node (include/oq_hip_nbits_decode.h, "left out"), or None when it has
+    one.  ``rows``: the rows of the flattened input, where they are known."""
+    if x_dtype not in _NBITS_TYPE:
+        return f"an input of {x_dtype} (fp32, fp16 and bf16 have a kernel)"
+    if rows is not None and rows > DECODE_MAX_ROWS:
+        return f"{rows} rows (the decode route takes 1 ... {DECODE_MAX_ROWS}; matmul_nbits takes the rest)"
+    if bits not in (4, 8):
+        return f"bits = {bits} (4 and 8 have a kernel)"
+    if block_size <= 0 or block_size % 16:
+        return f"block_size = {block_size} is no multiple of 16 (a lane's unit of 16 k would straddle two groups)"
+    if zero_points is not None and zero_points.is_floating_point() and zero_points.dtype not in (torch.float32, x_dtype):
+        return f"zero points of {zero_points.dtype} (uint8, float32 and the input's type have a kernel)"
+    if g_idx is not None:
+        return "g_idx"
+    return None
+
+
+def matmul_nbits_decode(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero_points: torch.Tensor | None = None, *, K: int,
+                        N: int, bits: int, block_size: int, bias: torch.Tensor | None = None, g_idx: torch.Tensor | None = None) -> torch.Tensor:
+    """The decode route of com.microsoft::MatMulNBits (`oq_matmul_nbits_decode`, csrc/matmul_nbits_decode.hip): the operands and
+    shape conventions of `matmul_nbits`, for an ``x`` whose ``reshape(-1, K)`` has 1 ... 16 rows.  The blob is streamed once
+    from global memory into registers and dequantized there (fp32 on the vector ALU; from 5 rows on, where a group is a whole
+    number of wave spans, on the matrix cores), so ``zero_points`` may also be floating point [N, blocks] (float32 or x's type:
+    HQQ files) and ``block_size`` any multiple of 16.  Deterministic; nothing synchronises with the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out: more than 16 rows, block sizes that are no multiple
+    of 16, bits other than 4 / 8, and a node that carries ``g_idx``."""
+    current = torch.cuda.current_device() if torch.cuda.is_available() else -1
+
+    def on_device(t, name, dtype=None):      # `_require_device` with the current device asked for once: this call is made per token
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != current or (dtype is not None and t.dtype != dtype):
+            _require_device(t, name, dtype)
+
+    on_device(x, "x")
+    K, N, bits, g = int(K), int(N), int(bits), int(block_size)
+    if x.shape[-1] != K:
+        raise ValueError(f"matmul_nbits_decode: x has {x.shape[-1]} columns, the node K = {K}")
+    x2 = x.reshape(-1, K)
+    why = matmul_nbits_decode_unsupported(x.dtype, bits, g, zero_points, g_idx, rows=x2.shape[0])
+    if why is not None:
+        raise NotImplementedError(f"matmul_nbits_decode: {why}")
+    blocks = (K + g - 1) // g
+    on_device(blob, "blob", torch.uint8)
+    if blob.numel() != N * blocks * (g * bits // 8):
+        raise ValueError(f"matmul_nbits_decode: a blob of {N} x {blocks} x {g * bits // 8} bytes is expected, got {tuple(blob.shape)}")
+    blob = blob.contiguous()
+    on_device(scales, "scales")
+    if scales.dtype not in (torch.float32, x.dtype) or scales.numel() != N * blocks:
+        raise ValueError(f"matmul_nbits_decode: scales must be {N * blocks} values of float32 or {x.dtype}, got {scales.numel()} of {scales.dtype}")
+    scales = scales.contiguous()
+    zp_type = L.OQ_NBITS_ZP_PACKED_U8
+    if zero_points is not None:
+        on_device(zero_points, "zero_points")
+        if zero_points.is_floating_point():
+            expect, zp_type = N * blocks, _NBITS_TYPE[zero_points.dtype]
+        elif zero_points.dtype == torch.uint8:
+            expect = N * ((blocks + 1) // 2) if bits == 4 else N * blocks
+        else:
+            raise ValueError(f"matmul_nbits_decode: zero points must be uint8 or floating point, got {zero_points.dtype}")
+        if zero_points.numel() != expect:
+            raise ValueError(f"matmul_nbits_decode: {expect} zero points ({zero_points.dtype}) are expected, got {zero_points.numel()}")
+        zero_points = zero_points.contiguous()
+    if bias is not None:
+        on_device(bias, "bias", x.dtype)
+        if bias.numel() != N:
+            raise ValueError(f"matmul_nbits_decode: bias must hold {N} values, got {bias.numel()}")
+        bias = bias.contiguous()
+    if x2.shape[0] == 0:
+        return torch.zeros((*x.shape[:-1], N), dtype=x.dtype, device=x.device)
+    x2, lda = _row_major(x2)
+    m = x2.shape[0]
+    out = torch.empty((m, N), dtype=x.dtype, device=x.device)
+    lib = L.load()
+    atype = _NBITS_TYPE[x.dtype]
+    key = (m, K, N, g, atype)
+    need = _DECODE_WORKSPACE.get(key)
+    if need is None:                                   # a decode loop asks for the same few shapes thousands of times
+        need = _DECODE_WORKSPACE[key] = lib.oq_matmul_nbits_decode_workspace_bytes(*key)
+    ws = _workspace(need, x.device) if need else None
+    L.check(lib.oq_matmul_nbits_decode(_ptr(x2), atype, m, K, lda, _ptr(blob), bits, N, g, _ptr(scales), _NBITS_TYPE[scales.dtype],
+                                       _ptr(zero_points), zp_type, _ptr(bias), 0, _ptr(out), N, _ptr(ws), need, C.c_void_p(_raw_stream(current))))
     return out.reshape(*x.shape[:-1], N)
 
 
