@@ -29,6 +29,7 @@
 //   split K   blockIdx.y takes a range of k-steps and writes S to int32 slab y; ql_reduce_kernel adds the slabs, corrects and
 //             finishes.  No atomics anywhere.
 #include "half_elem.hpp"
+#include "qlinear_epilogue.hpp"
 #include "tile_plan.hpp"
 
 #include "../../include/oq_hip_qlinear.h"
@@ -67,79 +68,6 @@ struct QlArgs {
     uint32_t* slab;                // split K: [splits, M, N]
     uint32_t M, N, K, tiles_m, steps_per_split;      // extents are below 2^31: 32-bit indices, 64-bit only where an offset is formed
 };
-
-__device__ __forceinline__ int32_t read_zp(const void* zp, int32_t is_signed, int64_t i) {
-    if (zp == nullptr) return 0;
-    return is_signed ? static_cast<int32_t>(static_cast<const int8_t*>(zp)[i]) : static_cast<int32_t>(static_cast<const uint8_t*>(zp)[i]);
-}
-
-// what an output column needs: zb'[n], the terms of the correction that do not depend on the row, and the fp32 scale
-struct ColTerms {
-    uint32_t zb, add;
-    float scale;
-};
-
-__device__ __forceinline__ ColTerms col_terms(const QlArgs& p, uint32_t n) {
-    ColTerms c;
-    const uint32_t za = static_cast<uint32_t>(read_zp(p.a_zp, p.a_signed, 0) - (p.a_signed ? 0 : 128));
-    c.zb = static_cast<uint32_t>(read_zp(p.b_zp, p.b_signed, p.b_per_column ? n : 0) - (p.b_signed ? 0 : 128));
-    c.add = p.K * za * c.zb;
-    if (p.colsum) {
-        uint32_t cs = 0u;
-        for (uint32_t s = 0; s < p.colsum_slices; ++s) cs += static_cast<uint32_t>(p.colsum[static_cast<int64_t>(s) * p.colsum_stride + n]);
-        c.add -= za * cs;
-    }
-    if (p.C) c.add += static_cast<uint32_t>(p.C[n]);
-    c.scale = p.out == OQ_QL_OUT_I32 ? 0.0f : p.a_scale[0] * p.b_scale[p.b_per_column ? n : 0];
-    return c;
-}
-
-// S -> acc -> Y.  Every fp32 step is one rounding, in the order the header states.
-__device__ __forceinline__ void finish(const QlArgs& p, uint32_t m, uint32_t n, uint32_t S, const ColTerms& c) {
-    const uint32_t rs = p.rowsum ? static_cast<uint32_t>(p.rowsum[m]) : 0u;
-    const int32_t acc = static_cast<int32_t>(S - c.zb * rs + c.add);
-    const int64_t at = static_cast<int64_t>(m) * p.ldy + n;
-    if (p.out == OQ_QL_OUT_I32) {
-        static_cast<int32_t*>(p.Y)[at] = acc;
-        return;
-    }
-    const float t = static_cast<float>(acc) * c.scale;
-    if (p.out == OQ_QL_OUT_F32) {
-        static_cast<float*>(p.Y)[at] = t;
-        return;
-    }
-    const bool i8 = p.out == OQ_QL_OUT_I8;
-    float q = rintf(t / p.y_scale[0]) + static_cast<float>(read_zp(p.y_zp, i8, 0));
-    q = fminf(fmaxf(q, i8 ? -128.0f : 0.0f), i8 ? 127.0f : 255.0f);
-    static_cast<uint8_t*>(p.Y)[at] = static_cast<uint8_t>(static_cast<int32_t>(q));
-}
-
-// 16 bytes of `row` from k on, as they are: the flip is applied when they are written to LDS, so that no load is followed by an
-// instruction that waits for it.  Past K: the flip's byte, which the flip turns into the pad, a zero of the flipped operand.
-__device__ __forceinline__ u32x4 load_k16(const uint8_t* row, uint32_t k, uint32_t K, bool vec, uint32_t flip) {
-    if (vec && k + 16u <= K) return *reinterpret_cast<const u32x4*>(row + k);
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        w[j] = 0u;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const uint32_t kk = k + 4 * j + b;
-            w[j] |= (kk < K ? static_cast<uint32_t>(row[kk]) : flip & 0xFFu) << (8 * b);
-        }
-    }
-    return u32x4{w[0], w[1], w[2], w[3]};
-}
-
-// 4 bytes of one row of a KN matrix from column n on, `at` pointing at column n (raw; zeros past N)
-__device__ __forceinline__ uint32_t load_n4(const uint8_t* at, uint32_t n, uint32_t N, bool vec) {
-    if (vec && n + 4u <= N) return *reinterpret_cast<const uint32_t*>(at);
-    uint32_t w = 0u;
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (n + b < N) w |= static_cast<uint32_t>(at[b]) << (8 * b);
-    return w;
-}
 
 template <int MT, int LAYOUT>
 __global__ __launch_bounds__(kThreads, 2) void ql_gemm_kernel(const QlArgs p) {

@@ -58,7 +58,9 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
 
     ``qlinear="fused"`` runs the QLinearMatMul / QGemm nodes of a `format="qlinear"` file on the int8 matrix cores
     (`ops.qlinear_matmul`: exact int32 sums).  The default stays the expansion route: a fused output may differ from it by one
-    output level, where the expansion's fp32 sum lands on the other side of a rounding boundary."""
+    output level, where the expansion's fp32 sum lands on the other side of a rounding boundary.  ``qlinear="fused+decode"`` goes to
+    `GraphRunner` as it is: the nodes of windows of at most 16 tokens run on the decode kernel (`ops.qlinear_matmul_decode`), with
+    the bytes of ``"fused"``."""
     import torch
 
     from .graph_runner import GraphRunner

@@ -100,10 +100,15 @@ class GraphRunner:
         # qlinear = "fused": a QLinearMatMul / QGemm node the library has a kernel for (`ops.qlinear_matmul`: 8-bit operands on the
         # GPU, per-tensor activation parameters, fp32 scales, a constant 2-D B, alpha = 1, no transA) runs on the int8 matrix cores
         # with an exact int32 sum -- no operand is dequantized.  Every other node, and every node under "torch", takes the expansion.
-        if qlinear not in ("torch", "fused"):
-            raise ValueError(f"GraphRunner: qlinear must be 'torch' or 'fused', got {qlinear!r}")
+        # qlinear = "fused+decode": such a node whose flattened A has at most 16 rows runs on the decode kernel
+        # (`ops.qlinear_matmul_decode`: B streamed once, the same accumulator and epilogue, so the same bytes); every other node goes
+        # as under "fused".  Only this mode counts a third route, "decode".
+        if qlinear not in ("torch", "fused", "fused+decode"):
+            raise ValueError(f"GraphRunner: qlinear must be 'torch', 'fused' or 'fused+decode', got {qlinear!r}")
         self.qlinear = qlinear if self.device.type == "cuda" else "torch"
         self.qlinear_calls = {"fused": 0, "torch": 0}    # QLinearMatMul / QGemm nodes run per route (counted like nbits_calls)
+        if self.qlinear == "fused+decode":
+            self.qlinear_calls["decode"] = 0
         self.functions = {(f.domain or "", f.name, f.overload or ""): f for f in model.functions}
         self.opset = max([int(o.version or 1) for o in model.opset_import if not o.domain] or [1])
         self.wanted = list(outputs) if outputs is not None else [o.name for o in self.graph.output]
@@ -1206,8 +1211,11 @@ class GraphRunner:
 
     def _op_QLinearMatMul(self, n, x, a, e):
         import torch
-        if self.qlinear == "fused" and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False):
+        if self.qlinear in ("fused", "fused+decode") and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False):
             from .hip import ops
+            if self._qlinear_decodes(x[0]):
+                self.qlinear_calls["decode"] += 1
+                return ops.qlinear_matmul_decode(*x[:8])
             self.qlinear_calls["fused"] += 1
             return ops.qlinear_matmul(*x[:8])
         self.qlinear_calls["torch"] += 1
@@ -1223,8 +1231,12 @@ class GraphRunner:
         y_scale = x[7] if len(x) > 7 else None
         y_zp = x[8] if len(x) > 8 else None
         trans_b, alpha, trans_a = bool(a.get("transB", 0)), a.get("alpha", 1.0), bool(a.get("transA", 0))
-        if self.qlinear == "fused" and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b, alpha, trans_a):
+        if self.qlinear in ("fused", "fused+decode") and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b,
+                                                                                alpha, trans_a):
             from .hip import ops
+            if self._qlinear_decodes(x[0]):
+                self.qlinear_calls["decode"] += 1
+                return ops.qlinear_matmul_decode(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias=bias, trans_b=trans_b)
             self.qlinear_calls["fused"] += 1
             return ops.qlinear_matmul(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias=bias, trans_b=trans_b)
         self.qlinear_calls["torch"] += 1
@@ -1326,6 +1338,12 @@ class GraphRunner:
             return False
         return ops.qlinear_matmul_unsupported(A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias=bias, trans_b=trans_b, alpha=alpha,
                                               trans_a=trans_a) is None
+
+    def _qlinear_decodes(self, A) -> bool:
+        """Whether a node `_qlinear_fusable` accepted goes to `ops.qlinear_matmul_decode`: the mode asks for it and the flattened A has
+        at most 16 rows."""
+        from .hip import ops
+        return self.qlinear == "fused+decode" and A.numel() // A.shape[-1] <= ops.QL_DECODE_MAX_ROWS
 
 
 _CAPTURE_MAX_INPUT_ELEMENTS = 1 << 20      # recording pays when a pass is hundreds of small launches (one short sequence), not above

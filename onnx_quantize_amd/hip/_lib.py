@@ -42,6 +42,8 @@ OQ_QL_KN, OQ_QL_NK = range(2)
 OQ_QL_OUT_I32, OQ_QL_OUT_F32, OQ_QL_OUT_U8, OQ_QL_OUT_I8 = range(4)
 OQ_QL_PER_ROW_A, OQ_QL_TRANS_A, OQ_QL_ALPHA = 1, 2, 4
 OQ_QLINEAR_EXTENSION_VERSION = 1
+# include/oq_hip_qlinear_decode.h
+OQ_QLINEAR_DECODE_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -187,6 +189,14 @@ QLINEAR_PROTOTYPES = {
                                  _p, _sz, _p]),
 }
 
+# the decode route of QLinearMatMul / QGemm: mirrors include/oq_hip_qlinear_decode.h one to one (tests/test_qlinear_decode_abi.py checks the set)
+QLINEAR_DECODE_PROTOTYPES = {
+    "oq_qlinear_decode_extension_version": (_i32, []),
+    "oq_qlinear_matmul_decode_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "oq_qlinear_matmul_decode": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _p, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _p, _p, _i32, _i32, _p,
+                                        _i64, _p, _sz, _p]),
+}
+
 _lock = threading.Lock()
 _lib = None
 
@@ -214,7 +224,8 @@ def load() -> C.CDLL:
         except OSError as e:  # missing ROCm runtime etc.
             raise OqHipMissing(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in [*PROTOTYPES.items(), *HALF_PROTOTYPES.items(), *NBITS_PROTOTYPES.items(),
-                                   *NBITS_DECODE_PROTOTYPES.items(), *QLINEAR_PROTOTYPES.items()]:
+                                   *NBITS_DECODE_PROTOTYPES.items(), *QLINEAR_PROTOTYPES.items(),
+                                   *QLINEAR_DECODE_PROTOTYPES.items()]:
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -235,6 +246,9 @@ def load() -> C.CDLL:
         if lib.oq_qlinear_extension_version() != OQ_QLINEAR_EXTENSION_VERSION:
             raise OqHipMissing(f"{LIB_PATH} has QLinearMatMul extension {lib.oq_qlinear_extension_version()}, "
                                f"expected {OQ_QLINEAR_EXTENSION_VERSION}")
+        if lib.oq_qlinear_decode_extension_version() != OQ_QLINEAR_DECODE_EXTENSION_VERSION:
+            raise OqHipMissing(f"{LIB_PATH} has QLinearMatMul decode extension {lib.oq_qlinear_decode_extension_version()}, "
+                               f"expected {OQ_QLINEAR_DECODE_EXTENSION_VERSION}")
         _lib = lib
     return _lib
 

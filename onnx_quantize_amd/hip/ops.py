@@ -1420,16 +1420,48 @@ def qlinear_matmul_unsupported(a, a_scale, a_zero_point, b, b_scale, b_zero_poin
     return None
 
 
-def _qlinear_call(fn, a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias, trans_b, alpha, trans_a, out_dtype):
-    _require_device(a, "a")
-    _require_device(b, "b")
+def _tile_route(lib, m, k, n, trans_b, current):
+    """`oq_qlinear_matmul` with its workspace query, asked per call, on the current stream."""
+    return lib.oq_qlinear_matmul, lib.oq_qlinear_matmul_workspace_bytes(m, k, n), _stream()
+
+
+_QL_DECODE_WORKSPACE: dict = {}      # (M, K, N, layout code) -> oq_qlinear_matmul_decode_workspace_bytes
+
+
+def _decode_route(lib, m, k, n, trans_b, current):
+    """`oq_qlinear_matmul_decode`: the call is made per token, so the workspace size is remembered per shape and the stream handle
+    taken raw (docs/LAB_NOTES_r26.md, section 4)."""
+    key = (m, k, n, L.OQ_QL_NK if trans_b else L.OQ_QL_KN)
+    need = _QL_DECODE_WORKSPACE.get(key)
+    if need is None:
+        need = _QL_DECODE_WORKSPACE[key] = lib.oq_qlinear_matmul_decode_workspace_bytes(*key)
+    return lib.oq_qlinear_matmul_decode, need, C.c_void_p(_raw_stream(current))
+
+
+def _qlinear_call(fn, a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias, trans_b, alpha, trans_a, out_dtype,
+                  route=_tile_route, unsupported=None):
+    """What `qlinear_matmul` / `matmul_integer` and their decode twins share: the checks, the operands as the C ABI wants them, the
+    call.  ``route(lib, m, k, n, trans_b, current device)`` names the entry point, its workspace bytes and the stream;
+    ``unsupported`` the refusals of that entry point (by default `qlinear_matmul_unsupported`)."""
+    current = None
+    if route is _tile_route:
+        require = _require_device
+    else:
+        current = torch.cuda.current_device() if torch.cuda.is_available() else -1
+
+        def require(t, name):      # `_require_device` with the current device asked for once
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != current:
+                _require_device(t, name)
+
+    require(a, "a")
+    require(b, "b")
     params = dict(a_scale=a_scale, a_zero_point=a_zero_point, b_scale=b_scale, b_zero_point=b_zero_point, y_scale=y_scale,
                   y_zero_point=y_zero_point, bias=bias)
     for name, t in params.items():
         if t is not None:
-            _require_device(t, name)
-    why = qlinear_matmul_unsupported(a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias=bias, trans_b=trans_b,
-                                     alpha=alpha, trans_a=trans_a)
+            require(t, name)
+    why = (unsupported or qlinear_matmul_unsupported)(a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias=bias,
+                                                      trans_b=trans_b, alpha=alpha, trans_a=trans_a)
     if why is not None:
         raise NotImplementedError(f"{fn}: {why}")
     k = a.shape[-1]
@@ -1451,11 +1483,11 @@ def _qlinear_call(fn, a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scal
         None if t is None else t.contiguous() for t in (a_scale, a_zero_point, b_scale, b_zero_point, y_scale, y_zero_point, bias))
     out = torch.empty((m, n), dtype=out_dtype, device=a.device)
     lib = L.load()
-    need = lib.oq_qlinear_matmul_workspace_bytes(m, k, n)
-    ws = _workspace(need, a.device)
-    L.check(lib.oq_qlinear_matmul(_ptr(a2), _QL_TYPE[a.dtype], m, k, lda, _ptr(a_scale), _ptr(a_zero_point), _ptr(b), _QL_TYPE[b.dtype],
-                                  L.OQ_QL_NK if trans_b else L.OQ_QL_KN, n, ldb, _ptr(b_scale), _ptr(b_zero_point), int(per_column), _ptr(bias),
-                                  _ptr(y_scale), _ptr(y_zero_point), 0, _QL_OUT[out_dtype], _ptr(out), n, _ptr(ws), need, _stream()))
+    entry, need, stream = route(lib, m, k, n, trans_b, current)
+    ws = _workspace(need, a.device) if need or route is _tile_route else None
+    L.check(entry(_ptr(a2), _QL_TYPE[a.dtype], m, k, lda, _ptr(a_scale), _ptr(a_zero_point), _ptr(b), _QL_TYPE[b.dtype],
+                  L.OQ_QL_NK if trans_b else L.OQ_QL_KN, n, ldb, _ptr(b_scale), _ptr(b_zero_point), int(per_column), _ptr(bias),
+                  _ptr(y_scale), _ptr(y_zero_point), 0, _QL_OUT[out_dtype], _ptr(out), n, _ptr(ws), need, stream))
     return out.reshape(*a.shape[:-1], n)
 
 
@@ -1484,6 +1516,49 @@ def matmul_integer(a: torch.Tensor, b: torch.Tensor, a_zero_point: torch.Tensor 
     """MatMulInteger: sum_k (a - a_zero_point) * (b - b_zero_point) as int32, exact (two's-complement wrap), on the int8 matrix
     cores; operands and zero points as in `qlinear_matmul`."""
     return _qlinear_call("matmul_integer", a, None, a_zero_point, b, None, b_zero_point, None, None, None, trans_b, 1.0, False, torch.int32)
+
+
+QL_DECODE_MAX_ROWS = 16      # include/oq_hip_qlinear_decode.h: M of the decode route
+
+
+def qlinear_matmul_decode_unsupported(a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale=None, y_zero_point=None, *, bias=None,
+                                      trans_b: bool = False, alpha: float = 1.0, trans_a: bool = False, rows: int | None = None) -> str | None:
+    """Why `qlinear_matmul_decode` has no kernel for such operands (include/oq_hip_qlinear_decode.h, "left out"), or None when it has
+    one: what `qlinear_matmul_unsupported` names, and more than 16 rows.  ``rows``: the rows of the flattened ``a`` (asked from
+    ``a`` itself where it is None)."""
+    why = qlinear_matmul_unsupported(a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias=bias, trans_b=trans_b,
+                                     alpha=alpha, trans_a=trans_a)
+    if why is not None:
+        return why
+    if rows is None:
+        rows = a.numel() // a.shape[-1] if a.shape[-1] else 0
+    if rows > QL_DECODE_MAX_ROWS:
+        return f"{rows} rows (the decode route takes 1 ... {QL_DECODE_MAX_ROWS}; qlinear_matmul takes the rest)"
+    return None
+
+
+def qlinear_matmul_decode(a: torch.Tensor, a_scale: torch.Tensor, a_zero_point: torch.Tensor | None, b: torch.Tensor, b_scale: torch.Tensor,
+                          b_zero_point: torch.Tensor | None, y_scale: torch.Tensor | None = None, y_zero_point: torch.Tensor | None = None, *,
+                          bias: torch.Tensor | None = None, trans_b: bool = False, alpha: float = 1.0, trans_a: bool = False) -> torch.Tensor:
+    """The decode route of QLinearMatMul / com.microsoft::QGemm (`oq_qlinear_matmul_decode`, csrc/qlinear_decode.hip): the operands
+    and conventions of `qlinear_matmul`, for an ``a`` whose ``reshape(-1, K)`` has 1 ... 16 rows.  ``b`` is streamed once from
+    global memory into registers (signed dot4 products; its column sums come from the same registers), the accumulator and the
+    epilogue are those of `qlinear_matmul`, so the result has the same bytes.  Deterministic; nothing synchronises with the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out: more than 16 rows, and what `qlinear_matmul` refuses."""
+    if a_scale is None or b_scale is None:
+        raise ValueError("qlinear_matmul_decode: a_scale and b_scale are required (matmul_integer_decode runs without scales)")
+    out_dtype = torch.float32 if y_scale is None else (torch.uint8 if y_zero_point is None else y_zero_point.dtype)
+    return _qlinear_call("qlinear_matmul_decode", a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale,
+                         None if y_scale is None else y_zero_point, bias, trans_b, alpha, trans_a, out_dtype, route=_decode_route,
+                         unsupported=qlinear_matmul_decode_unsupported)
+
+
+def matmul_integer_decode(a: torch.Tensor, b: torch.Tensor, a_zero_point: torch.Tensor | None = None, b_zero_point: torch.Tensor | None = None, *,
+                          trans_b: bool = False) -> torch.Tensor:
+    """MatMulInteger on the decode route: `matmul_integer` for an ``a`` of 1 ... 16 rows, the same int32 values."""
+    return _qlinear_call("matmul_integer_decode", a, None, a_zero_point, b, None, b_zero_point, None, None, None, trans_b, 1.0, False, torch.int32,
+                         route=_decode_route, unsupported=qlinear_matmul_decode_unsupported)
 
 
 # ----------------------------------------------------------------------------- G1 - G4
