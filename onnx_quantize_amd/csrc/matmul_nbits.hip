@@ -19,39 +19,17 @@
 //             the slabs in slab order and finishes.  No atomics anywhere.
 //   guards    every global access is guarded by M, N, K: rows >= M, columns >= N and k >= K are zeros in LDS (A) or never read
 //             (B, scales, zero points); a padded blob position meets a zero of A and its bytes are finite integers whatever they hold.
-#include "half_elem.hpp"
+// The matrix-core operand, the decoders of the blob and of a packed zero point, and the checks of a call are those of the decode
+// route too: nbits_common.hpp.
+#include "nbits_common.hpp"
 #include "tile_plan.hpp"
-
-#include "../../include/oq_hip_nbits.h"
 
 #include <cmath>
 
 namespace oq {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kRow = kBK * 2 + 16;   // bytes of a tile row in LDS (kBK: two MFMA depths): 16 lanes x 16 bytes land in 16 different bank quads
-
-struct OpF16 : ElemF16 {
-    typedef f16x8 frag;
-    static __device__ __forceinline__ uint32_t pack(float a, float b) {      // exact integers: the rounding mode is irrelevant
-        return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
-    }
-    static __device__ __forceinline__ uint16_t round(float v) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); }
-};
-struct OpBF16 : ElemBF16 {
-    typedef bf16x8 frag;
-    static __device__ __forceinline__ uint32_t pack(float a, float b) {      // |a|, |b| <= 255: eight significand bits, the upper halves
-        return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-    }
-    static __device__ __forceinline__ uint16_t round(float v) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v)); }
-};
-
-__device__ __forceinline__ f32x4 mfma16(const f16x8& a, const f16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 struct NbitsArgs {
     const uint16_t* A;      // 2-byte operand: A itself, or the hi pieces
@@ -100,23 +78,11 @@ __device__ __forceinline__ u32x4 load_a8(const uint16_t* row, int64_t k, int64_t
 // 32 stored values (k ascending) minus the zero point -> 32 exact 2-byte operands
 template <typename OP, int BITS>
 __device__ __forceinline__ void dequant32(const u32x4 (&raw)[BITS / 4], float zpf, u32x4 (&out)[4]) {
-    if constexpr (BITS == 4) {
+    uint32_t d[16];
 #pragma unroll
-        for (int wi = 0; wi < 4; ++wi) {
-            const uint32_t w = raw[0][wi];
-            const uint32_t ev = w & 0x0F0F0F0Fu, od = (w >> 4) & 0x0F0F0F0Fu;     // bytes: values 0 2 4 6 and 1 3 5 7
+    for (int wi = 0; wi < BITS; ++wi) dequant_word<OP, BITS>(raw[wi >> 2][wi & 3], zpf, d + wi * (16 / BITS));
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                out[wi][j] = OP::pack(static_cast<float>((ev >> (8 * j)) & 0xFFu) - zpf, static_cast<float>((od >> (8 * j)) & 0xFFu) - zpf);
-        }
-    } else {
-#pragma unroll
-        for (int wi = 0; wi < 8; ++wi) {
-            const uint32_t w = raw[wi >> 2][wi & 3];
-            out[wi >> 1][2 * (wi & 1)] = OP::pack(static_cast<float>(w & 0xFFu) - zpf, static_cast<float>((w >> 8) & 0xFFu) - zpf);
-            out[wi >> 1][2 * (wi & 1) + 1] = OP::pack(static_cast<float>((w >> 16) & 0xFFu) - zpf, static_cast<float>(w >> 24) - zpf);
-        }
-    }
+    for (int i = 0; i < 4; ++i) out[i] = u32x4{d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]};
 }
 
 // Two waves per SIMD (<= 256 registers, no scratch) for a 2-byte A: unbounded, the 128-row tile takes 230 VGPRs + 64 AGPRs, one wave
@@ -167,8 +133,8 @@ __global__ __launch_bounds__(kThreads, OUT == OQ_NBITS_F32 ? 1 : 2) void nbits_g
 #pragma unroll
             for (int i = 0; i < BITS / 4; ++i) b_regs[i] = reinterpret_cast<const u32x4*>(src)[i];
             if (p.zp != nullptr) {
-                if constexpr (BITS == 4) zp_raw = static_cast<uint32_t>(p.zp[b_n * ((p.blocks + 1) >> 1) + (kb >> 1)]) >> (4 * (kb & 1));
-                else zp_raw = p.zp[b_n * p.blocks + kb];
+                zp_raw = zp_byte<BITS>(p.zp, b_n, p.blocks, kb);      // shifted here, masked where it is used (store_step), not by zp_of_byte
+                if constexpr (BITS == 4) zp_raw >>= 4 * (kb & 1);
             }
         }
     };
@@ -222,7 +188,7 @@ __global__ __launch_bounds__(kThreads, OUT == OQ_NBITS_F32 ? 1 : 2) void nbits_g
                 for (int mt = 0; mt < MT; ++mt) {
                     const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + mt * 16 * kRow + s * 64));
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16(a, b[nt], acc[mt][nt]);
+                    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = OP::mma(a, b[nt], acc[mt][nt]);
                 }
                 if constexpr (PIECES == 2) {
 #pragma unroll
@@ -231,7 +197,7 @@ __global__ __launch_bounds__(kThreads, OUT == OQ_NBITS_F32 ? 1 : 2) void nbits_g
                     for (int mt = 0; mt < MT; ++mt) {
                         const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + (BM + mt * 16) * kRow + s * 64));
 #pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = mfma16(a, b[nt], acc[mt][nt]);
+                        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = OP::mma(a, b[nt], acc[mt][nt]);
                     }
                 }
                 in_group += 32;
@@ -314,10 +280,11 @@ struct Plan : TilePlan {      // and the workspace: include/oq_hip_nbits.h, `wor
     float* slab;
 };
 
-bool shape_ok(int64_t M, int64_t K, int64_t N, int64_t g) {
-    return extent_ok(M) && extent_ok(K) && extent_ok(N) && extent_ok(g) && count_ok(M * ((K + 7) / 8 * 8)) && count_ok(M * N) &&
-           count_ok(N * (ceil_div(K, g) * g));
+bool tile_shape_ok(int64_t M, int64_t K, int64_t N, int64_t g) {      // and the pieces of an fp32 A
+    return shape_ok(M, K, N, g) && count_ok(M * ((K + 7) / 8 * 8));
 }
+
+constexpr NbitsRoute kRoute{"oq_matmul_nbits", kMaxExtent, 32, "two groups would share one 32-deep matrix instruction", false};
 
 Plan make_plan(int64_t M, int64_t K, int64_t N, int32_t atype, Workspace& ws) {
     Plan pl{make_tile_plan(M, K, N)};
@@ -346,8 +313,6 @@ int32_t run(const NbitsArgs& p, const Plan& pl, int32_t bits, hipStream_t s) {
     return check_launch("nbits_reduce_kernel");
 }
 
-bool type_ok(int32_t t) { return t == OQ_NBITS_F32 || t == OQ_NBITS_F16 || t == OQ_NBITS_BF16; }
-
 }  // namespace
 }  // namespace oq
 
@@ -358,7 +323,7 @@ extern "C" {
 int32_t oq_nbits_extension_version(void) { return OQ_NBITS_EXTENSION_VERSION; }
 
 size_t oq_matmul_nbits_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t group_size, int32_t atype) {
-    if (!type_ok(atype) || !shape_ok(M, K, N, group_size)) {
+    if (!type_ok(atype) || !tile_shape_ok(M, K, N, group_size)) {
         set_error("oq_matmul_nbits_workspace_bytes: M=%lld K=%lld N=%lld group_size=%lld atype=%d outside the bounds", (long long)M, (long long)K,
                   (long long)N, (long long)group_size, atype);
         return 0;
@@ -371,31 +336,20 @@ size_t oq_matmul_nbits_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t 
 int32_t oq_matmul_nbits(const void* A, int32_t atype, int64_t M, int64_t K, int64_t lda, const void* B, int32_t bits, int64_t N, int64_t group_size,
                         const void* scales, int32_t scales_type, const uint8_t* zero_points, const void* bias, int32_t flags, void* Y, int64_t ldy,
                         void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "oq_matmul_nbits";
-    OQ_REQUIRE(A && B && scales && Y, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (A, B, scales and Y are required)", fn);
-    OQ_REQUIRE(type_ok(atype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown atype %d", fn, atype);
-    OQ_REQUIRE(scales_type == OQ_NBITS_F32 || scales_type == atype, OQ_ERR_INVALID_ARGUMENT, "%s: scales_type %d is neither fp32 nor atype %d", fn,
-               scales_type, atype);
-    OQ_REQUIRE(extent_ok(M) && extent_ok(K) && extent_ok(N) && matrix_ok(M, K, lda) && matrix_ok(M, N, ldy), OQ_ERR_INVALID_ARGUMENT,
-               "%s: M=%lld K=%lld N=%lld lda=%lld ldy=%lld outside the bounds", fn, (long long)M, (long long)K, (long long)N, (long long)lda,
-               (long long)ldy);
-    OQ_REQUIRE(bits == 4 || bits == 8, OQ_ERR_UNSUPPORTED, "%s: bits = %d (4 and 8 have a kernel)", fn, bits);
-    OQ_REQUIRE(extent_ok(group_size) && group_size % 32 == 0, OQ_ERR_UNSUPPORTED,
-               "%s: group_size = %lld is no multiple of 32 (two groups would share one 32-deep matrix instruction)", fn, (long long)group_size);
-    OQ_REQUIRE(!(flags & OQ_NBITS_FLOAT_ZERO_POINTS), OQ_ERR_UNSUPPORTED,
-               "%s: float zero points (q - zp is no integer: no exact matrix-core operand)", fn);
-    OQ_REQUIRE(!(flags & OQ_NBITS_G_IDX), OQ_ERR_UNSUPPORTED, "%s: g_idx has no kernel", fn);
-    OQ_REQUIRE((flags & ~(OQ_NBITS_FLOAT_ZERO_POINTS | OQ_NBITS_G_IDX)) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: unknown flags %d", fn, flags);
-    OQ_REQUIRE(shape_ok(M, K, N, group_size), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld group_size=%lld: an operand beyond 2^40 elements", fn,
+    const char* fn = kRoute.fn;
+    int32_t st = operands_ok(fn, A, B, scales, Y, atype, scales_type);
+    if (st != OQ_OK) return st;
+    st = extents_and_flags_ok(kRoute, M, K, N, lda, ldy, bits, group_size, flags);
+    if (st != OQ_OK) return st;
+    OQ_REQUIRE(tile_shape_ok(M, K, N, group_size), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld group_size=%lld: an operand beyond 2^40 elements", fn,
                (long long)M, (long long)K, (long long)N, (long long)group_size);
     const uintptr_t elem = atype == OQ_NBITS_F32 ? 4 : 2;
     OQ_REQUIRE(aligned_to(A, elem) && aligned_to(Y, elem) && aligned_to(bias, elem) && aligned_to(scales, scales_type == OQ_NBITS_F32 ? 4 : 2),
                OQ_ERR_INVALID_ARGUMENT, "%s: A, Y, bias and scales must be aligned to their element", fn);
-    OQ_REQUIRE(aligned_to(B, 16), OQ_ERR_INVALID_ARGUMENT, "%s: B must be 16-byte aligned", fn);
     Workspace ws(workspace, workspace_bytes, /* aligned_base */ true);
     const Plan pl = make_plan(M, K, N, atype, ws);
-    OQ_REQUIRE(ws.total() == 0 || ws.fits(), OQ_ERR_WORKSPACE, "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, ws.total(),
-               workspace ? workspace_bytes : (size_t)0);
+    st = blob_and_workspace_ok(fn, B, ws, workspace, workspace_bytes);
+    if (st != OQ_OK) return st;
 
     hipStream_t s = as_stream(stream);
     NbitsArgs p{};
@@ -411,7 +365,7 @@ int32_t oq_matmul_nbits(const void* A, int32_t atype, int64_t M, int64_t K, int6
     p.slab = pl.slab;
     if (atype == OQ_NBITS_F32) {
         nbits_split_rows_kernel<<<static_cast<unsigned>(M), kThreads, 0, s>>>(static_cast<const float*>(A), K, lda, pl.kp, pl.hi, pl.lo, pl.row_exp);
-        const int32_t st = check_launch("nbits_split_rows_kernel");
+        st = check_launch("nbits_split_rows_kernel");
         if (st != OQ_OK) return st;
         p.A = pl.hi, p.A_lo = pl.lo, p.lda = pl.kp, p.Ka = pl.kp, p.a_vec = 1, p.row_exp = pl.row_exp;
         return run<OQ_NBITS_F32>(p, pl, bits, s);

@@ -21,8 +21,11 @@
 // The 8- and 16-row tiers of a node whose groups are whole wave spans run nbits_decode_mma_kernel (further down) instead: the same
 // streaming, the products on the matrix cores.
 // Built with -fno-slp-vectorize (_build.py), like matmul_nbits.hip and for its reason: no v_pk_fma_f32 folds (docs/LAB_NOTES_r22.md).
+// Shared: the matrix-core operand, the decoders of the blob and of a packed zero point and the checks of a call with matmul_nbits.hip
+// (nbits_common.hpp); the row tiers and the butterfly with qlinear_decode.hip (decode_plan.hpp, lanes_reduce.hpp).
 #include "decode_plan.hpp"
-#include "half_elem.hpp"
+#include "lanes_reduce.hpp"
+#include "nbits_common.hpp"
 
 #include "../../include/oq_hip_nbits_decode.h"
 
@@ -31,8 +34,6 @@
 
 namespace oq {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum ZpKind : int32_t { kZpNone = 0, kZpPacked = 1, kZpF32 = 2, kZpF16 = 3, kZpBF16 = 4 };
 
@@ -87,25 +88,6 @@ __device__ __forceinline__ f32x4 load_a4(const DecodeArgs& p, int64_t m, int64_t
     for (int e = 0; e < 4; ++e)
         if (k + e < p.K) v[e] = typed(load_typed(p.A, at + e, p.atype), p.atype);
     return v;
-}
-
-// CNT values per lane, LK lanes: the sum over the lanes of value (c mod the original CNT) ends in v[0] of lane c
-template <int CNT, int OFF, int LK>
-__device__ __forceinline__ void lanes_reduce(float* v, int c) {
-    if constexpr (OFF < LK) {
-        if constexpr (CNT > 1) {
-            const bool up = (c & OFF) != 0;
-#pragma unroll
-            for (int i = 0; i < CNT / 2; ++i) {
-                const float keep = up ? v[2 * i + 1] : v[2 * i], send = up ? v[2 * i] : v[2 * i + 1];
-                v[i] = keep + __shfl_xor(send, OFF, kWave);
-            }
-            lanes_reduce<CNT / 2, OFF * 2, LK>(v, c);
-        } else {
-            v[0] += __shfl_xor(v[0], OFF, kWave);
-            lanes_reduce<1, OFF * 2, LK>(v, c);
-        }
-    }
 }
 
 template <int BITS, int MT, int R>
@@ -171,8 +153,7 @@ __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_kernel(const Deco
                 if (!live[u]) continue;
                 st.s[r][u] = load_typed(p.scales, n * p.blocks + kb[u], p.scales_type);
                 if (p.zp_kind == kZpPacked) {
-                    if constexpr (BITS == 4) st.z[r][u] = static_cast<const uint8_t*>(p.zp)[n * ((p.blocks + 1) >> 1) + (kb[u] >> 1)];
-                    else st.z[r][u] = static_cast<const uint8_t*>(p.zp)[n * p.blocks + kb[u]];
+                    st.z[r][u] = zp_byte<BITS>(static_cast<const uint8_t*>(p.zp), n, p.blocks, kb[u]);
                 } else if (p.zp_kind != kZpNone) {
                     st.z[r][u] = load_typed(p.zp, n * p.blocks + kb[u], p.zp_kind - kZpF32);
                 }
@@ -201,7 +182,7 @@ __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_kernel(const Deco
                 const bool have = live[u] && row0 + r * RP + rp < p.N;
                 sc[r] = have ? typed(cur.s[r][u], p.scales_type) : 0.0f;
                 float z = zp_default;
-                if (p.zp_kind == kZpPacked) z = static_cast<float>(BITS == 4 ? (cur.z[r][u] >> (4 * (kb[u] & 1))) & 0xFu : cur.z[r][u]);
+                if (p.zp_kind == kZpPacked) z = static_cast<float>(zp_of_byte<BITS>(cur.z[r][u], kb[u]));
                 else if (p.zp_kind != kZpNone) z = typed(cur.z[r][u], p.zp_kind - kZpF32);
                 zpf[r] = have ? z : 0.0f;
             }
@@ -216,19 +197,9 @@ __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_kernel(const Deco
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     float d[4];
-                    if constexpr (BITS == 4) {                 // a word holds 8 values: byte b = values 2 b (low nibble) and 2 b + 1
-                        const uint32_t w = cur.b[r][j >> 1];
-                        const uint32_t ev = w & 0x0F0F0F0Fu, od = (w >> 4) & 0x0F0F0F0Fu;
-                        const int b0 = 2 * (j & 1);
-                        d[0] = static_cast<float>((ev >> (8 * b0)) & 0xFFu) - zpf[r];
-                        d[1] = static_cast<float>((od >> (8 * b0)) & 0xFFu) - zpf[r];
-                        d[2] = static_cast<float>((ev >> (8 * b0 + 8)) & 0xFFu) - zpf[r];
-                        d[3] = static_cast<float>((od >> (8 * b0 + 8)) & 0xFFu) - zpf[r];
-                    } else {
-                        const uint32_t w = cur.b[r][j];
+                    const uint32_t w = cur.b[r][4 * j * BITS / 32];      // the word of the step's four values, and where they begin in it
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) d[e] = static_cast<float>((w >> (8 * e)) & 0xFFu) - zpf[r];
-                    }
+                    for (int e = 0; e < 4; ++e) d[e] = stored<BITS>(w, 4 * j % (32 / BITS) + e) - zpf[r];
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -269,31 +240,11 @@ __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_kernel(const Deco
 //   A         LDS holds the slice as 2-byte operands, rows padded by 16 bytes (16 lanes x 16 bytes: every bank once).  fp16 and bf16
 //             as they are; fp32 as THREE bf16 pieces, a = b1 + b2 + b3 exactly (3 x 8 significand bits, bf16 has fp32's range: no row
 //             scale, rows at 1e30 and 1e-30 alike), each piece times an 8-bit integer exact in fp32.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-struct MmaF16 {
-    typedef f16x8 frag;
-    static constexpr uint32_t kOnes = 0x3C003C00u;
-    static __device__ __forceinline__ uint32_t pack(float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b)); }
-    static __device__ __forceinline__ uint16_t piece(float v) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); }
-    static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-struct MmaBF16 {
-    typedef bf16x8 frag;
-    static constexpr uint32_t kOnes = 0x3F803F80u;
-    static __device__ __forceinline__ uint32_t pack(float a, float b) {      // integers of at most 8 bits: the upper halves are the values
-        return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-    }
-    static __device__ __forceinline__ uint16_t piece(float v) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v)); }
-    static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
 constexpr int kMmaRow = kDecodeSlice * 2 + 16;      // bytes of a row of A in LDS
 
 template <int ATYPE, int BITS>
 __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_mma_kernel(const DecodeArgs p) {
-    typedef std::conditional_t<ATYPE == OQ_NBITS_F16, MmaF16, MmaBF16> OP;
+    typedef std::conditional_t<ATYPE == OQ_NBITS_F16, OpF16, OpBF16> OP;
     typedef typename OP::frag frag;
     constexpr int PIECES = ATYPE == OQ_NBITS_F32 ? 3 : 1;
     constexpr int VAL = 128 / BITS, SP = 4 * VAL, NS = kDecodeSlice / SP, NJ = VAL / 8;
@@ -313,7 +264,7 @@ __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_mma_kernel(const 
                 uint16_t h[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    h[e] = OP::piece(v[e]);
+                    h[e] = OP::round(v[e]);
                     if constexpr (PIECES > 1) {      // what the piece left; an infinity stays in the first piece alone
                         const float took = ElemBF16::one(h[e]);
                         v[e] = fabsf(took) < INFINITY ? v[e] - took : 0.0f;
@@ -349,8 +300,7 @@ __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_mma_kernel(const 
                 if (k0 + s * SP + VAL * qd < p.K) st.b[s] = *reinterpret_cast<const u32x4*>(p.B + n * p.row_bytes + byte_off + s * 64);
                 st.s[s] = load_typed(p.scales, n * p.blocks + kb, p.scales_type);
                 if (p.zp_kind == kZpPacked) {
-                    if constexpr (BITS == 4) st.z[s] = (static_cast<const uint8_t*>(p.zp)[n * ((p.blocks + 1) >> 1) + (kb >> 1)] >> (4 * (kb & 1))) & 0xFu;
-                    else st.z[s] = static_cast<const uint8_t*>(p.zp)[n * p.blocks + kb];
+                    st.z[s] = zp_of_byte<BITS>(zp_byte<BITS>(static_cast<const uint8_t*>(p.zp), n, p.blocks, kb), kb);
                 } else if (p.zp_kind != kZpNone) {
                     st.z[s] = load_typed(p.zp, n * p.blocks + kb, p.zp_kind - kZpF32);
                 }
@@ -385,21 +335,9 @@ __global__ __launch_bounds__(kDecodeThreads) void nbits_decode_mma_kernel(const 
             f32x4 acc{0.0f, 0.0f, 0.0f, 0.0f}, asum{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                uint32_t d[4];
-                if constexpr (BITS == 4) {      // a word: byte b holds values 2 b (low nibble) and 2 b + 1
-                    const uint32_t w = cur.b[s][j];
-                    const uint32_t ev = w & 0x0F0F0F0Fu, od = (w >> 4) & 0x0F0F0F0Fu;
+                uint32_t d[4];      // the lane's j-th eight values: one word at 4 bits, two at 8
 #pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        d[b] = OP::pack(static_cast<float>((ev >> (8 * b)) & 0xFFu) - zi, static_cast<float>((od >> (8 * b)) & 0xFFu) - zi);
-                } else {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const uint32_t w = cur.b[s][2 * j + h];
-                        d[2 * h] = OP::pack(static_cast<float>(w & 0xFFu) - zi, static_cast<float>((w >> 8) & 0xFFu) - zi);
-                        d[2 * h + 1] = OP::pack(static_cast<float>((w >> 16) & 0xFFu) - zi, static_cast<float>(w >> 24) - zi);
-                    }
-                }
+                for (int h = 0; h < BITS / 4; ++h) dequant_word<OP, BITS>(cur.b[s][j * BITS / 4 + h], zi, d + h * (16 / BITS));
                 const frag b = __builtin_bit_cast(frag, u32x4{d[0], d[1], d[2], d[3]});
 #pragma unroll
                 for (int piece = 0; piece < PIECES; ++piece) {
@@ -439,11 +377,7 @@ struct Plan : DecodePlan {      // and the workspace: include/oq_hip_nbits_decod
     float* slab;
 };
 
-bool type_ok(int32_t t) { return t == OQ_NBITS_F32 || t == OQ_NBITS_F16 || t == OQ_NBITS_BF16; }
-
-bool shape_ok(int64_t M, int64_t K, int64_t N, int64_t g) {
-    return extent_ok(M) && extent_ok(K) && extent_ok(N) && extent_ok(g) && count_ok(M * N) && count_ok(N * (ceil_div(K, g) * g));
-}
+constexpr NbitsRoute kRoute{"oq_matmul_nbits_decode", kDecodeMaxRows, 16, "a lane's unit of 16 k would straddle two groups", true};
 
 Plan make_plan(int64_t M, int64_t K, int64_t N, int32_t atype, Workspace& ws) {
     Plan pl{make_decode_plan(M, K, N, atype == OQ_NBITS_F32)};
@@ -463,7 +397,7 @@ void launch(const DecodeArgs& p, const Plan& pl, hipStream_t s) {
         else nbits_decode_mma_kernel<OQ_NBITS_F32, BITS><<<grid, kDecodeThreads, 0, s>>>(p);
         return;
     }
-    with_decode_tier(pl, [&](auto mt) {
+    with_decode_tier(pl.tier, [&](auto mt) {
         constexpr int MT = decltype(mt)::value;
         constexpr int R = MT == 16 ? 2 : 4;
         nbits_decode_kernel<BITS, MT, R><<<static_cast<unsigned>(pl.grid), kDecodeThreads, 0, s>>>(p);
@@ -493,23 +427,13 @@ size_t oq_matmul_nbits_decode_workspace_bytes(int64_t M, int64_t K, int64_t N, i
 int32_t oq_matmul_nbits_decode(const void* A, int32_t atype, int64_t M, int64_t K, int64_t lda, const void* B, int32_t bits, int64_t N,
                                int64_t group_size, const void* scales, int32_t scales_type, const void* zero_points, int32_t zero_points_type,
                                const void* bias, int32_t flags, void* Y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "oq_matmul_nbits_decode";
-    OQ_REQUIRE(A && B && scales && Y, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (A, B, scales and Y are required)", fn);
-    OQ_REQUIRE(type_ok(atype), OQ_ERR_INVALID_ARGUMENT, "%s: unknown atype %d", fn, atype);
-    OQ_REQUIRE(scales_type == OQ_NBITS_F32 || scales_type == atype, OQ_ERR_INVALID_ARGUMENT, "%s: scales_type %d is neither fp32 nor atype %d", fn,
-               scales_type, atype);
+    const char* fn = kRoute.fn;
+    int32_t st = operands_ok(fn, A, B, scales, Y, atype, scales_type);
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(zero_points_type == OQ_NBITS_ZP_PACKED_U8 || zero_points_type == OQ_NBITS_F32 || zero_points_type == atype, OQ_ERR_INVALID_ARGUMENT,
                "%s: zero_points_type %d is neither packed uint8 (%d), fp32 nor atype %d", fn, zero_points_type, OQ_NBITS_ZP_PACKED_U8, atype);
-    OQ_REQUIRE(extent_ok(M) && extent_ok(K) && extent_ok(N) && matrix_ok(M, K, lda) && matrix_ok(M, N, ldy), OQ_ERR_INVALID_ARGUMENT,
-               "%s: M=%lld K=%lld N=%lld lda=%lld ldy=%lld outside the bounds", fn, (long long)M, (long long)K, (long long)N, (long long)lda,
-               (long long)ldy);
-    OQ_REQUIRE(M <= kDecodeMaxRows, OQ_ERR_UNSUPPORTED, "%s: M = %lld rows (the decode route takes 1 ... %d; oq_matmul_nbits takes the rest)", fn,
-               (long long)M, kDecodeMaxRows);
-    OQ_REQUIRE(bits == 4 || bits == 8, OQ_ERR_UNSUPPORTED, "%s: bits = %d (4 and 8 have a kernel)", fn, bits);
-    OQ_REQUIRE(extent_ok(group_size) && group_size % 16 == 0, OQ_ERR_UNSUPPORTED,
-               "%s: group_size = %lld is no multiple of 16 (a lane's unit of 16 k would straddle two groups)", fn, (long long)group_size);
-    OQ_REQUIRE(!(flags & OQ_NBITS_G_IDX), OQ_ERR_UNSUPPORTED, "%s: g_idx has no kernel", fn);
-    OQ_REQUIRE((flags & ~(OQ_NBITS_FLOAT_ZERO_POINTS | OQ_NBITS_G_IDX)) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: unknown flags %d", fn, flags);
+    st = extents_and_flags_ok(kRoute, M, K, N, lda, ldy, bits, group_size, flags);
+    if (st != OQ_OK) return st;
     OQ_REQUIRE(!(flags & OQ_NBITS_FLOAT_ZERO_POINTS) || zero_points_type != OQ_NBITS_ZP_PACKED_U8, OQ_ERR_INVALID_ARGUMENT,
                "%s: flags say float zero points, zero_points_type says packed uint8", fn);
     OQ_REQUIRE(shape_ok(M, K, N, group_size), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld group_size=%lld: an operand beyond 2^40 elements", fn,
@@ -519,11 +443,10 @@ int32_t oq_matmul_nbits_decode(const void* A, int32_t atype, int64_t M, int64_t 
     OQ_REQUIRE(aligned_to(A, elem) && aligned_to(Y, elem) && aligned_to(bias, elem) && aligned_to(scales, scales_type == OQ_NBITS_F32 ? 4 : 2) &&
                    aligned_to(zero_points, zp_elem),
                OQ_ERR_INVALID_ARGUMENT, "%s: A, Y, bias, scales and zero_points must be aligned to their element", fn);
-    OQ_REQUIRE(aligned_to(B, 16), OQ_ERR_INVALID_ARGUMENT, "%s: B must be 16-byte aligned", fn);
     Workspace ws(workspace, workspace_bytes, /* aligned_base */ true);
     const Plan pl = make_plan(M, K, N, atype, ws);
-    OQ_REQUIRE(ws.total() == 0 || ws.fits(), OQ_ERR_WORKSPACE, "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, ws.total(),
-               workspace ? workspace_bytes : (size_t)0);
+    st = blob_and_workspace_ok(fn, B, ws, workspace, workspace_bytes);
+    if (st != OQ_OK) return st;
 
     hipStream_t s = as_stream(stream);
     DecodeArgs p{};
@@ -543,7 +466,7 @@ int32_t oq_matmul_nbits_decode(const void* A, int32_t atype, int64_t M, int64_t 
     p.g = static_cast<uint32_t>(group_size);
     if (bits == 4) launch<4>(p, pl, s);
     else launch<8>(p, pl, s);
-    const int32_t st = check_launch("nbits_decode_kernel");
+    st = check_launch("nbits_decode_kernel");
     if (st != OQ_OK || pl.splits == 1) return st;
     nbits_decode_reduce_kernel<<<static_cast<unsigned>(ceil_div(M * N, kDecodeThreads)), kDecodeThreads, 0, s>>>(p);
     return check_launch("nbits_decode_reduce_kernel");

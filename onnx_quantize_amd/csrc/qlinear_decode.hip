@@ -19,7 +19,7 @@
 //   NK        B[n, k]: lane c of a wave owns the 16 bytes at k = 16 c of the 1024-k slice, the 4 waves take different rows, 4 rows
 //             are in flight per lane (16 rows an iteration), those of the next iteration are issued before the arithmetic of this
 //             one.  A lies [row][k]: a lane reads its 16 bytes of each row (consecutive lanes, consecutive 16 bytes).  The 4 x MT sums
-//             and the 4 column sums of a lane are added over the 64 lanes by the transposing butterfly of matmul_nbits_decode.hip.
+//             and the 4 column sums of a lane are added over the 64 lanes by the transposing butterfly (lanes_reduce.hpp).
 //   KN        B[k, n]: a lane owns 4 columns -- a wave's 64 lanes cover 256 consecutive bytes of a row -- and walks k: 16 rows a
 //             stage, the next stage issued before the arithmetic of this one; each 4 x 4 byte block is transposed in registers
 //             (v_perm_b32) into four dwords, k ... k + 3 of one column each.  A lies [k / 4][row]: its dwords are wave-uniform, one
@@ -30,6 +30,9 @@
 //             order, adds C and finishes.  No atomics, no workgroup waits on another, nothing synchronises with the host.
 // The 8- and 16-row tiers of an NK matrix whose rows are 16-byte aligned (K a multiple of 16) run ql_decode_nk_mma_kernel (further down)
 // instead: the same streaming, the products on the matrix cores.
+// Shared: the guarded loads, the epilogue, the checks of a call and the operand block with qlinear_gemm.hip (qlinear_epilogue.hpp); the
+// row tiers and the butterfly with matmul_nbits_decode.hip (decode_plan.hpp, lanes_reduce.hpp).
+#include "lanes_reduce.hpp"
 #include "qlinear_decode_plan.hpp"
 #include "qlinear_epilogue.hpp"
 
@@ -65,25 +68,6 @@ struct QdArgs {
 
 __device__ __forceinline__ uint32_t dot4(uint32_t a, uint32_t b, uint32_t acc) {
     return static_cast<uint32_t>(__builtin_amdgcn_sdot4(static_cast<int>(a), static_cast<int>(b), static_cast<int>(acc), false));
-}
-
-// CNT values per lane: the sum over the 64 lanes of value (c mod the original CNT) ends in v[0] of lane c
-template <int CNT, int OFF>
-__device__ __forceinline__ void lanes_reduce(uint32_t* v, int c) {
-    if constexpr (OFF < kWave) {
-        if constexpr (CNT > 1) {
-            const bool up = (c & OFF) != 0;
-#pragma unroll
-            for (int i = 0; i < CNT / 2; ++i) {
-                const uint32_t keep = up ? v[2 * i + 1] : v[2 * i], send = up ? v[2 * i] : v[2 * i + 1];
-                v[i] = keep + static_cast<uint32_t>(__shfl_xor(static_cast<int>(send), OFF, kWave));
-            }
-            lanes_reduce<CNT / 2, OFF * 2>(v, c);
-        } else {
-            v[0] += static_cast<uint32_t>(__shfl_xor(static_cast<int>(v[0]), OFF, kWave));
-            lanes_reduce<1, OFF * 2>(v, c);
-        }
-    }
 }
 
 // lds_rs[m] = the sum of the staged (flipped) slice of row m, `quads` dwords: wave w takes rows w, w + 4, ...  Ends in a barrier.
@@ -202,10 +186,10 @@ __global__ __launch_bounds__(kQlDecodeThreads) void ql_decode_nk_kernel(const Qd
             }
         }
 
-        lanes_reduce<R * MT, 1>(acc, c);
+        lanes_reduce<R * MT, 1, kWave>(acc, c);
         uint32_t csv = 0u;
         if constexpr (CS) {
-            lanes_reduce<R, 1>(cs, c);                       // lane r holds the column sum of row r of the iteration
+            lanes_reduce<R, 1, kWave>(cs, c);                      // lane r holds the column sum of row r of the iteration
             csv = static_cast<uint32_t>(__shfl(static_cast<int>(cs[0]), (c % (R * MT)) / MT, kWave));
         }
         if (c < R * MT) {
@@ -457,13 +441,6 @@ struct Plan : QlDecodePlan {      // and the workspace: include/oq_hip_qlinear_d
     uint32_t* slab;
 };
 
-bool type_ok(int32_t t) { return t == OQ_QL_U8 || t == OQ_QL_I8; }
-bool layout_ok(int32_t l) { return l == OQ_QL_KN || l == OQ_QL_NK; }
-
-bool shape_ok(int64_t M, int64_t K, int64_t N) {
-    return extent_ok(M) && extent_ok(K) && extent_ok(N) && count_ok(M * K) && count_ok(M * N) && count_ok(N * K);
-}
-
 Plan make_plan(int64_t M, int64_t K, int64_t N, int32_t b_layout, Workspace& ws) {
     Plan pl{make_ql_decode_plan(M, K, N, b_layout)};
     pl.slab = ws.take<uint32_t>(pl.slab_bytes);
@@ -480,7 +457,7 @@ void launch(const QdArgs& p, const Plan& pl, bool kn, hipStream_t s) {
         ql_decode_nk_mma_kernel<CS><<<grid, kQlDecodeThreads, 0, s>>>(p);
         return;
     }
-    with_ql_decode_tier(pl, [&](auto mt) {
+    with_decode_tier(pl.tier, [&](auto mt) {
         constexpr int MT = decltype(mt)::value;
         if (kn) ql_decode_kn_kernel<MT, CS><<<grid, kQlDecodeThreads, 0, s>>>(p);
         else ql_decode_nk_kernel<MT, CS><<<grid, kQlDecodeThreads, 0, s>>>(p);
@@ -514,31 +491,9 @@ int32_t oq_qlinear_matmul_decode(const void* A, int32_t a_type, int64_t M, int64
                                  const void* b_zero_point, int32_t b_per_column, const int32_t* C, const float* y_scale, const void* y_zero_point,
                                  int32_t flags, int32_t out, void* Y, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
     const char* fn = "oq_qlinear_matmul_decode";
-    OQ_REQUIRE(A && B && Y, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (A, B and Y are required)", fn);
-    OQ_REQUIRE(type_ok(a_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown a_type %d", fn, a_type);
-    OQ_REQUIRE(type_ok(b_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_type %d", fn, b_type);
-    OQ_REQUIRE(layout_ok(b_layout), OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_layout %d", fn, b_layout);
-    OQ_REQUIRE(out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 || out == OQ_QL_OUT_U8 || out == OQ_QL_OUT_I8, OQ_ERR_INVALID_ARGUMENT,
-               "%s: unknown out %d", fn, out);
-    OQ_REQUIRE((flags & ~(OQ_QL_PER_ROW_A | OQ_QL_TRANS_A | OQ_QL_ALPHA)) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: unknown flags %d", fn, flags);
-    OQ_REQUIRE(out == OQ_QL_OUT_I32 || (a_scale && b_scale), OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (a_scale and b_scale are required for out %d)",
-               fn, out);
-    OQ_REQUIRE((out != OQ_QL_OUT_U8 && out != OQ_QL_OUT_I8) || y_scale, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (y_scale is required for out %d)",
-               fn, out);
+    int32_t st = call_ok(fn, kQlDecodeMaxRows, A, a_type, M, K, lda, a_scale, B, b_type, b_layout, N, ldb, b_scale, C, y_scale, flags, out, Y, ldy);
+    if (st != OQ_OK) return st;
     const bool kn = b_layout == OQ_QL_KN;
-    OQ_REQUIRE(extent_ok(M) && extent_ok(K) && extent_ok(N) && matrix_ok(M, K, lda) && matrix_ok(kn ? K : N, kn ? N : K, ldb) && matrix_ok(M, N, ldy),
-               OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld lda=%lld ldb=%lld ldy=%lld outside the bounds", fn, (long long)M, (long long)K,
-               (long long)N, (long long)lda, (long long)ldb, (long long)ldy);
-    OQ_REQUIRE(shape_ok(M, K, N), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld: an operand beyond 2^40 elements", fn, (long long)M,
-               (long long)K, (long long)N);
-    OQ_REQUIRE(M <= kQlDecodeMaxRows, OQ_ERR_UNSUPPORTED, "%s: M = %lld rows (the decode route takes 1 ... %d; oq_qlinear_matmul is the route)", fn,
-               (long long)M, kQlDecodeMaxRows);
-    OQ_REQUIRE(!(flags & OQ_QL_PER_ROW_A), OQ_ERR_UNSUPPORTED, "%s: per-row a_scale / a_zero_point have no kernel", fn);
-    OQ_REQUIRE(!(flags & OQ_QL_TRANS_A), OQ_ERR_UNSUPPORTED, "%s: transA has no kernel", fn);
-    OQ_REQUIRE(!(flags & OQ_QL_ALPHA), OQ_ERR_UNSUPPORTED, "%s: alpha != 1 has no kernel", fn);
-    OQ_REQUIRE(aligned_to(a_scale, 4) && aligned_to(b_scale, 4) && aligned_to(y_scale, 4) && aligned_to(C, 4) &&
-                   aligned_to(Y, out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 ? 4 : 1),
-               OQ_ERR_INVALID_ARGUMENT, "%s: the scales, C and Y must be aligned to their element", fn);
     Workspace ws(workspace, workspace_bytes, /* aligned_base */ true);
     const Plan pl = make_plan(M, K, N, b_layout, ws);
     OQ_REQUIRE(ws.total() == 0 || ws.fits(), OQ_ERR_WORKSPACE, "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, ws.total(),
@@ -546,23 +501,14 @@ int32_t oq_qlinear_matmul_decode(const void* A, int32_t a_type, int64_t M, int64
 
     hipStream_t s = as_stream(stream);
     QdArgs p{};
-    p.A = static_cast<const uint8_t*>(A), p.B = static_cast<const uint8_t*>(B);
-    p.lda = lda, p.ldb = ldb;
-    p.a_signed = a_type == OQ_QL_I8, p.b_signed = b_type == OQ_QL_I8;
-    p.a_flip = p.a_signed ? 0u : 0x80808080u, p.b_flip = p.b_signed ? 0u : 0x80808080u;
-    p.a_vec = aligned_to(A, 16) && lda % 16 == 0;
-    p.b_vec = kn ? (aligned_to(B, 4) && ldb % 4 == 0) : (aligned_to(B, 16) && ldb % 16 == 0);
-    p.a_scale = a_scale, p.a_zp = a_zero_point, p.b_scale = b_scale, p.b_zp = b_zero_point, p.b_per_column = b_per_column != 0;
-    p.C = C, p.y_scale = y_scale, p.y_zp = y_zero_point, p.out = out, p.Y = Y, p.ldy = ldy;
-    p.M = static_cast<uint32_t>(M), p.N = static_cast<uint32_t>(N), p.K = static_cast<uint32_t>(K);
+    fill_operands(p, A, a_type, M, K, lda, a_scale, a_zero_point, B, b_type, b_layout, N, ldb, b_scale, b_zero_point, b_per_column, C, y_scale,
+                  y_zero_point, out, Y, ldy);
     p.slice = static_cast<uint32_t>(pl.slice), p.splits = static_cast<uint32_t>(pl.splits), p.cols_per_block = static_cast<uint32_t>(pl.cols_per_block);
     p.slab = pl.slab;
-    // a sum is needed unless its multiplier -- the OTHER operand's shifted zero point -- is zero whatever the device holds
-    p.need_rowsum = !(p.b_signed && !b_zero_point);
-    const bool need_colsum = !(p.a_signed && !a_zero_point);
-    if (need_colsum) launch<true>(p, pl, kn, s);
+    p.need_rowsum = sum_needed(p.b_signed, b_zero_point);
+    if (sum_needed(p.a_signed, a_zero_point)) launch<true>(p, pl, kn, s);
     else launch<false>(p, pl, kn, s);
-    const int32_t st = check_launch(kn ? "ql_decode_kn_kernel" : "ql_decode_nk_kernel");
+    st = check_launch(kn ? "ql_decode_kn_kernel" : "ql_decode_nk_kernel");
     if (st != OQ_OK || pl.splits == 1) return st;
     ql_decode_reduce_kernel<<<static_cast<unsigned>(ceil_div(M * N, kQlDecodeThreads)), kQlDecodeThreads, 0, s>>>(p);
     return check_launch("ql_decode_reduce_kernel");

@@ -1,12 +1,10 @@
 // The launch plan of the decode route of QLinearMatMul / QGemm (qlinear_decode.hip; include/oq_hip_qlinear_decode.h restates it):
-// host arithmetic only, in the style of decode_plan.hpp.  The tile GEMM keeps its own plan; nothing here is shared with it.
+// host arithmetic only.  The row tiers, their switch and the slab size are those of decode_plan.hpp; the slice and block rules are
+// this route's own.  The tile GEMM keeps its own plan; nothing here is shared with it.
 // No HIP: tests/c/qlinear_decode_plan_walk.cpp replays it under AddressSanitizer with plain g++.
 #pragma once
 
-#include <algorithm>
-#include <cstddef>
-#include <cstdint>
-#include <type_traits>
+#include "decode_plan.hpp"
 
 namespace oq {
 
@@ -22,45 +20,33 @@ constexpr int kQlDecodeWorkgroups = 512;    // wanted: two per compute unit of t
                                             // (a slice more is M * N * 8 bytes of slab traffic, and only K slices fill the device there)
 
 struct QlDecodePlan {
-    int tier;                   // accumulator rows per instantiation: 1, 4, 8, 16 (M = 1 / 2-4 / 5-8 / 9-16)
+    int tier;                   // decode_tier(M)
     int64_t slice;              // k of one workgroup
     int64_t splits;             // slices of K (the last one short): > 1: each writes a slab, a second launch adds them
     int64_t cols_per_block;     // columns of Y of one workgroup
     int64_t col_blocks;
     int64_t grid;               // col_blocks * splits workgroups (blockIdx.x = col_block * splits + split)
-    size_t slab_bytes;          // [splits, M, N] int32 partial sums, 0 for one split
+    size_t slab_bytes;          // decode_slab_bytes(splits, M, N), int32 partial sums
 };
 
 inline QlDecodePlan make_ql_decode_plan(int64_t M, int64_t K, int64_t N, int layout) {
-    const auto ceil_div = [](int64_t a, int64_t b) { return (a + b - 1) / b; };
     QlDecodePlan pl;
-    pl.tier = M <= 1 ? 1 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
+    pl.tier = decode_tier(M);
     if (layout == kQlDecodeLayoutNK) {
         pl.slice = kQlDecodeSlice;
-        pl.splits = ceil_div(K, pl.slice);
+        pl.splits = plan_ceil_div(K, pl.slice);
         const int64_t want = std::max<int64_t>(1, kQlDecodeWorkgroups / pl.splits);
-        pl.cols_per_block = ceil_div(ceil_div(N, want), kQlDecodeColUnitNK) * kQlDecodeColUnitNK;
+        pl.cols_per_block = plan_ceil_div(plan_ceil_div(N, want), kQlDecodeColUnitNK) * kQlDecodeColUnitNK;
     } else {
         pl.cols_per_block = kQlDecodeColsKN;
-        const int64_t want = ceil_div(pl.tier >= 8 ? kQlDecodeWorkgroups / 2 : kQlDecodeWorkgroups, ceil_div(N, pl.cols_per_block));
-        pl.slice = std::min<int64_t>(kQlDecodeSlice, ceil_div(ceil_div(K, want), kQlDecodeSliceUnit) * kQlDecodeSliceUnit);
-        pl.splits = ceil_div(K, pl.slice);
+        const int64_t want = plan_ceil_div(pl.tier >= 8 ? kQlDecodeWorkgroups / 2 : kQlDecodeWorkgroups, plan_ceil_div(N, pl.cols_per_block));
+        pl.slice = std::min<int64_t>(kQlDecodeSlice, plan_ceil_div(plan_ceil_div(K, want), kQlDecodeSliceUnit) * kQlDecodeSliceUnit);
+        pl.splits = plan_ceil_div(K, pl.slice);
     }
-    pl.col_blocks = ceil_div(N, pl.cols_per_block);
+    pl.col_blocks = plan_ceil_div(N, pl.cols_per_block);
     pl.grid = pl.col_blocks * pl.splits;
-    pl.slab_bytes = pl.splits > 1 ? static_cast<size_t>(pl.splits) * M * N * 4 : 0;
+    pl.slab_bytes = decode_slab_bytes(pl.splits, M, N);
     return pl;
-}
-
-// the row-tier switch of the kernels: f(std::integral_constant<int, MT>)
-template <typename F>
-void with_ql_decode_tier(const QlDecodePlan& pl, F&& f) {
-    switch (pl.tier) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        default: f(std::integral_constant<int, 16>{}); break;
-    }
 }
 
 }  // namespace oq

@@ -1,7 +1,8 @@
-// What the kernels of include/oq_hip_qlinear.h and include/oq_hip_qlinear_decode.h share (qlinear_gemm.hip, qlinear_decode.hip;
-// DESIGN.md 4.24, 4.27): the guarded loads of an 8-bit operand, the terms of the zero-point correction that belong to an output
-// column, and the epilogue -- acc -> Y in the order the headers state, every fp32 step one rounding.  One text, so the two routes
-// give the same bytes.
+// What the two routes of include/oq_hip_qlinear.h and include/oq_hip_qlinear_decode.h share (qlinear_gemm.hip, qlinear_decode.hip;
+// DESIGN.md 4.24, 4.27).  Device: the guarded loads of an 8-bit operand, the terms of the zero-point correction that belong to an
+// output column, and the epilogue -- acc -> Y in the order the headers state, every fp32 step one rounding.  Host (at the end): the
+// checks of a call and the operand block of the argument structs.  One text, so the two routes give the same bytes and refuse the
+// same calls with the same words.
 //
 // `P` is a kernel's argument block.  It names a_zp, a_signed, b_zp, b_signed, b_per_column, a_scale, b_scale, C, K (col_terms: also
 // colsum, colsum_slices, colsum_stride), and y_scale, y_zp, out, Y, ldy (finish: also rowsum).
@@ -109,6 +110,65 @@ __device__ __forceinline__ uint32_t load_n4(const uint8_t* at, uint32_t n, uint3
     for (int b = 0; b < 4; ++b)
         if (n + b < N) w |= static_cast<uint32_t>(at[b]) << (8 * b);
     return w;
+}
+
+// ---- host: the front of both entry points -- what they require of a call, and the operand block of their argument structs
+inline bool type_ok(int32_t t) { return t == OQ_QL_U8 || t == OQ_QL_I8; }
+inline bool layout_ok(int32_t l) { return l == OQ_QL_KN || l == OQ_QL_NK; }
+
+inline bool shape_ok(int64_t M, int64_t K, int64_t N) {
+    return extent_ok(M) && extent_ok(K) && extent_ok(N) && count_ok(M * K) && count_ok(M * N) && count_ok(N * K);
+}
+
+// `max_rows`: of the route `fn` (the tile route: any number an extent can be)
+inline int32_t call_ok(const char* fn, int64_t max_rows, const void* A, int32_t a_type, int64_t M, int64_t K, int64_t lda, const float* a_scale,
+                       const void* B, int32_t b_type, int32_t b_layout, int64_t N, int64_t ldb, const float* b_scale, const int32_t* C,
+                       const float* y_scale, int32_t flags, int32_t out, const void* Y, int64_t ldy) {
+    OQ_REQUIRE(A && B && Y, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (A, B and Y are required)", fn);
+    OQ_REQUIRE(type_ok(a_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown a_type %d", fn, a_type);
+    OQ_REQUIRE(type_ok(b_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_type %d", fn, b_type);
+    OQ_REQUIRE(layout_ok(b_layout), OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_layout %d", fn, b_layout);
+    OQ_REQUIRE(out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 || out == OQ_QL_OUT_U8 || out == OQ_QL_OUT_I8, OQ_ERR_INVALID_ARGUMENT,
+               "%s: unknown out %d", fn, out);
+    OQ_REQUIRE((flags & ~(OQ_QL_PER_ROW_A | OQ_QL_TRANS_A | OQ_QL_ALPHA)) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: unknown flags %d", fn, flags);
+    OQ_REQUIRE(out == OQ_QL_OUT_I32 || (a_scale && b_scale), OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (a_scale and b_scale are required for out %d)",
+               fn, out);
+    OQ_REQUIRE((out != OQ_QL_OUT_U8 && out != OQ_QL_OUT_I8) || y_scale, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (y_scale is required for out %d)",
+               fn, out);
+    const bool kn = b_layout == OQ_QL_KN;
+    OQ_REQUIRE(extent_ok(M) && extent_ok(K) && extent_ok(N) && matrix_ok(M, K, lda) && matrix_ok(kn ? K : N, kn ? N : K, ldb) && matrix_ok(M, N, ldy),
+               OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld lda=%lld ldb=%lld ldy=%lld outside the bounds", fn, (long long)M, (long long)K,
+               (long long)N, (long long)lda, (long long)ldb, (long long)ldy);
+    OQ_REQUIRE(shape_ok(M, K, N), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld: an operand beyond 2^40 elements", fn, (long long)M,
+               (long long)K, (long long)N);
+    OQ_REQUIRE(M <= max_rows, OQ_ERR_UNSUPPORTED, "%s: M = %lld rows (the decode route takes 1 ... %lld; oq_qlinear_matmul is the route)", fn,
+               (long long)M, (long long)max_rows);
+    OQ_REQUIRE(!(flags & OQ_QL_PER_ROW_A), OQ_ERR_UNSUPPORTED, "%s: per-row a_scale / a_zero_point have no kernel", fn);
+    OQ_REQUIRE(!(flags & OQ_QL_TRANS_A), OQ_ERR_UNSUPPORTED, "%s: transA has no kernel", fn);
+    OQ_REQUIRE(!(flags & OQ_QL_ALPHA), OQ_ERR_UNSUPPORTED, "%s: alpha != 1 has no kernel", fn);
+    OQ_REQUIRE(aligned_to(a_scale, 4) && aligned_to(b_scale, 4) && aligned_to(y_scale, 4) && aligned_to(C, 4) &&
+                   aligned_to(Y, out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 ? 4 : 1),
+               OQ_ERR_INVALID_ARGUMENT, "%s: the scales, C and Y must be aligned to their element", fn);
+    return OQ_OK;
+}
+
+// a sum is needed unless its multiplier -- the OTHER operand's shifted zero point -- is zero whatever the device holds
+inline bool sum_needed(int32_t other_signed, const void* other_zero_point) { return !(other_signed && !other_zero_point); }
+
+// the fields A ... ldy, M, N, K of an argument block, from a call that call_ok has let through
+template <class P>
+void fill_operands(P& p, const void* A, int32_t a_type, int64_t M, int64_t K, int64_t lda, const float* a_scale, const void* a_zero_point,
+                   const void* B, int32_t b_type, int32_t b_layout, int64_t N, int64_t ldb, const float* b_scale, const void* b_zero_point,
+                   int32_t b_per_column, const int32_t* C, const float* y_scale, const void* y_zero_point, int32_t out, void* Y, int64_t ldy) {
+    p.A = static_cast<const uint8_t*>(A), p.B = static_cast<const uint8_t*>(B);
+    p.lda = lda, p.ldb = ldb;
+    p.a_signed = a_type == OQ_QL_I8, p.b_signed = b_type == OQ_QL_I8;
+    p.a_flip = p.a_signed ? 0u : 0x80808080u, p.b_flip = p.b_signed ? 0u : 0x80808080u;
+    p.a_vec = aligned_to(A, 16) && lda % 16 == 0;
+    p.b_vec = b_layout == OQ_QL_KN ? (aligned_to(B, 4) && ldb % 4 == 0) : (aligned_to(B, 16) && ldb % 16 == 0);
+    p.a_scale = a_scale, p.a_zp = a_zero_point, p.b_scale = b_scale, p.b_zp = b_zero_point, p.b_per_column = b_per_column != 0;
+    p.C = C, p.y_scale = y_scale, p.y_zp = y_zero_point, p.out = out, p.Y = Y, p.ldy = ldy;
+    p.M = static_cast<uint32_t>(M), p.N = static_cast<uint32_t>(N), p.K = static_cast<uint32_t>(K);
 }
 
 }  // namespace

@@ -28,6 +28,8 @@
 //             no second pass and no atomics); whoever reads a column sum adds the 8.
 //   split K   blockIdx.y takes a range of k-steps and writes S to int32 slab y; ql_reduce_kernel adds the slabs, corrects and
 //             finishes.  No atomics anywhere.
+// The guarded loads, the epilogue, the checks of a call and the operand block of the argument struct are those of the decode route
+// too: qlinear_epilogue.hpp.
 #include "half_elem.hpp"
 #include "qlinear_epilogue.hpp"
 #include "tile_plan.hpp"
@@ -284,10 +286,6 @@ struct Plan : TilePlan {      // and the workspace: include/oq_hip_qlinear.h, `w
     uint32_t* slab;
 };
 
-bool shape_ok(int64_t M, int64_t K, int64_t N) {
-    return extent_ok(M) && extent_ok(K) && extent_ok(N) && count_ok(M * K) && count_ok(M * N) && count_ok(N * K);
-}
-
 Plan make_plan(int64_t M, int64_t K, int64_t N, Workspace& ws) {
     Plan pl{make_tile_plan(M, K, N)};
     const size_t slice_bytes = Workspace::padded(static_cast<size_t>(N) * 4);
@@ -303,8 +301,6 @@ void launch_gemm(const QlArgs& p, const Plan& pl, hipStream_t s) {
     const dim3 grid(static_cast<unsigned>(pl.tiles), static_cast<unsigned>(pl.splits));
     with_row_tiles(pl, [&](auto mt) { ql_gemm_kernel<decltype(mt)::value, LAYOUT><<<grid, kThreads, 0, s>>>(p); });
 }
-
-bool type_ok(int32_t t) { return t == OQ_QL_U8 || t == OQ_QL_I8; }
 
 }  // namespace
 }  // namespace oq
@@ -330,29 +326,9 @@ int32_t oq_qlinear_matmul(const void* A, int32_t a_type, int64_t M, int64_t K, i
                           int32_t b_per_column, const int32_t* C, const float* y_scale, const void* y_zero_point, int32_t flags, int32_t out, void* Y,
                           int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
     const char* fn = "oq_qlinear_matmul";
-    OQ_REQUIRE(A && B && Y, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (A, B and Y are required)", fn);
-    OQ_REQUIRE(type_ok(a_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown a_type %d", fn, a_type);
-    OQ_REQUIRE(type_ok(b_type), OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_type %d", fn, b_type);
-    OQ_REQUIRE(b_layout == OQ_QL_KN || b_layout == OQ_QL_NK, OQ_ERR_INVALID_ARGUMENT, "%s: unknown b_layout %d", fn, b_layout);
-    OQ_REQUIRE(out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 || out == OQ_QL_OUT_U8 || out == OQ_QL_OUT_I8, OQ_ERR_INVALID_ARGUMENT,
-               "%s: unknown out %d", fn, out);
-    OQ_REQUIRE((flags & ~(OQ_QL_PER_ROW_A | OQ_QL_TRANS_A | OQ_QL_ALPHA)) == 0, OQ_ERR_INVALID_ARGUMENT, "%s: unknown flags %d", fn, flags);
-    OQ_REQUIRE(out == OQ_QL_OUT_I32 || (a_scale && b_scale), OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (a_scale and b_scale are required for out %d)",
-               fn, out);
-    OQ_REQUIRE((out != OQ_QL_OUT_U8 && out != OQ_QL_OUT_I8) || y_scale, OQ_ERR_INVALID_ARGUMENT, "%s: null pointer (y_scale is required for out %d)",
-               fn, out);
+    int32_t st = call_ok(fn, kMaxExtent, A, a_type, M, K, lda, a_scale, B, b_type, b_layout, N, ldb, b_scale, C, y_scale, flags, out, Y, ldy);
+    if (st != OQ_OK) return st;
     const bool kn = b_layout == OQ_QL_KN;
-    OQ_REQUIRE(extent_ok(M) && extent_ok(K) && extent_ok(N) && matrix_ok(M, K, lda) && matrix_ok(kn ? K : N, kn ? N : K, ldb) && matrix_ok(M, N, ldy),
-               OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld lda=%lld ldb=%lld ldy=%lld outside the bounds", fn, (long long)M, (long long)K,
-               (long long)N, (long long)lda, (long long)ldb, (long long)ldy);
-    OQ_REQUIRE(shape_ok(M, K, N), OQ_ERR_INVALID_ARGUMENT, "%s: M=%lld K=%lld N=%lld: an operand beyond 2^40 elements", fn, (long long)M,
-               (long long)K, (long long)N);
-    OQ_REQUIRE(!(flags & OQ_QL_PER_ROW_A), OQ_ERR_UNSUPPORTED, "%s: per-row a_scale / a_zero_point have no kernel", fn);
-    OQ_REQUIRE(!(flags & OQ_QL_TRANS_A), OQ_ERR_UNSUPPORTED, "%s: transA has no kernel", fn);
-    OQ_REQUIRE(!(flags & OQ_QL_ALPHA), OQ_ERR_UNSUPPORTED, "%s: alpha != 1 has no kernel", fn);
-    OQ_REQUIRE(aligned_to(a_scale, 4) && aligned_to(b_scale, 4) && aligned_to(y_scale, 4) && aligned_to(C, 4) &&
-                   aligned_to(Y, out == OQ_QL_OUT_I32 || out == OQ_QL_OUT_F32 ? 4 : 1),
-               OQ_ERR_INVALID_ARGUMENT, "%s: the scales, C and Y must be aligned to their element", fn);
     Workspace ws(workspace, workspace_bytes, /* aligned_base */ true);
     const Plan pl = make_plan(M, K, N, ws);
     OQ_REQUIRE(ws.fits(), OQ_ERR_WORKSPACE, "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, ws.total(),
@@ -360,19 +336,11 @@ int32_t oq_qlinear_matmul(const void* A, int32_t a_type, int64_t M, int64_t K, i
 
     hipStream_t s = as_stream(stream);
     QlArgs p{};
-    p.A = static_cast<const uint8_t*>(A), p.B = static_cast<const uint8_t*>(B);
-    p.lda = lda, p.ldb = ldb;
-    p.a_signed = a_type == OQ_QL_I8, p.b_signed = b_type == OQ_QL_I8;
-    p.a_flip = p.a_signed ? 0u : 0x80808080u, p.b_flip = p.b_signed ? 0u : 0x80808080u;
-    p.a_vec = aligned_to(A, 16) && lda % 16 == 0;
-    p.b_vec = kn ? (aligned_to(B, 4) && ldb % 4 == 0) : (aligned_to(B, 16) && ldb % 16 == 0);
-    p.a_scale = a_scale, p.a_zp = a_zero_point, p.b_scale = b_scale, p.b_zp = b_zero_point, p.b_per_column = b_per_column != 0;
-    p.C = C, p.y_scale = y_scale, p.y_zp = y_zero_point, p.out = out, p.Y = Y, p.ldy = ldy;
-    p.M = static_cast<uint32_t>(M), p.N = static_cast<uint32_t>(N), p.K = static_cast<uint32_t>(K);
+    fill_operands(p, A, a_type, M, K, lda, a_scale, a_zero_point, B, b_type, b_layout, N, ldb, b_scale, b_zero_point, b_per_column, C, y_scale,
+                  y_zero_point, out, Y, ldy);
     p.tiles_m = static_cast<uint32_t>(pl.tiles_m), p.steps_per_split = static_cast<uint32_t>(pl.steps_per_split);
-    // a sum is needed unless its multiplier -- the OTHER operand's shifted zero point -- is zero whatever the device holds
-    int32_t* rowsum = (p.b_signed && !b_zero_point) ? nullptr : pl.rowsum;
-    int32_t* colsum = (p.a_signed && !a_zero_point) ? nullptr : pl.colsum;
+    int32_t* rowsum = sum_needed(p.b_signed, b_zero_point) ? pl.rowsum : nullptr;
+    int32_t* colsum = sum_needed(p.a_signed, a_zero_point) ? pl.colsum : nullptr;
     p.rowsum = rowsum, p.colsum = colsum;
     p.colsum_slices = kn ? kColSlices : 1, p.colsum_stride = pl.colsum_stride;
     p.slab = pl.slab;
@@ -383,19 +351,19 @@ int32_t oq_qlinear_matmul(const void* A, int32_t a_type, int64_t M, int64_t K, i
     if (rowsum) {
         ql_sum_rows_kernel<<<static_cast<unsigned>(ceil_div(M, kRowsPerBlock)), kThreads, 0, s>>>(p.A, M, K, lda, a_ubias,
                                                                                                   aligned_to(A, 4) && lda % 4 == 0, rowsum);
-        const int32_t st = check_launch("ql_sum_rows_kernel");
+        st = check_launch("ql_sum_rows_kernel");
         if (st != OQ_OK) return st;
     }
     if (colsum) {
         const int32_t vec4 = aligned_to(B, 4) && ldb % 4 == 0;
         if (kn) ql_sum_cols_kernel<<<dim3(static_cast<unsigned>(ceil_div(N, 64)), kColSlices), kThreads, 0, s>>>(p.B, K, N, ldb, b_ubias, vec4, colsum, p.colsum_stride);
         else ql_sum_rows_kernel<<<static_cast<unsigned>(ceil_div(N, kRowsPerBlock)), kThreads, 0, s>>>(p.B, N, K, ldb, b_ubias, vec4, colsum);
-        const int32_t st = check_launch(kn ? "ql_sum_cols_kernel" : "ql_sum_rows_kernel");
+        st = check_launch(kn ? "ql_sum_cols_kernel" : "ql_sum_rows_kernel");
         if (st != OQ_OK) return st;
     }
     if (kn) launch_gemm<OQ_QL_KN>(p, pl, s);
     else launch_gemm<OQ_QL_NK>(p, pl, s);
-    const int32_t st = check_launch("ql_gemm_kernel");
+    st = check_launch("ql_gemm_kernel");
     if (st != OQ_OK || pl.splits == 1) return st;
     ql_reduce_kernel<<<static_cast<unsigned>(ceil_div(M * N, kThreads)), kThreads, 0, s>>>(p, static_cast<int>(pl.splits));
     return check_launch("ql_reduce_kernel");

@@ -1211,14 +1211,12 @@ class GraphRunner:
 
     def _op_QLinearMatMul(self, n, x, a, e):
         import torch
-        if self.qlinear in ("fused", "fused+decode") and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False):
+        route = self._route(self.qlinear, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False,
+                                                                              decode))
+        self.qlinear_calls[route] += 1
+        if route != "torch":
             from .hip import ops
-            if self._qlinear_decodes(x[0]):
-                self.qlinear_calls["decode"] += 1
-                return ops.qlinear_matmul_decode(*x[:8])
-            self.qlinear_calls["fused"] += 1
-            return ops.qlinear_matmul(*x[:8])
-        self.qlinear_calls["torch"] += 1
+            return (ops.qlinear_matmul_decode if route == "decode" else ops.qlinear_matmul)(*x[:8])
         A = (x[0].to(torch.float32) - x[2].to(torch.float32)) * x[1]
         bz = self._per_axis(x[5].to(torch.float32), x[3], x[3].ndim - 1)
         B = (x[3].to(torch.float32) - bz) * self._per_axis(x[4], x[3], x[3].ndim - 1)
@@ -1231,15 +1229,13 @@ class GraphRunner:
         y_scale = x[7] if len(x) > 7 else None
         y_zp = x[8] if len(x) > 8 else None
         trans_b, alpha, trans_a = bool(a.get("transB", 0)), a.get("alpha", 1.0), bool(a.get("transA", 0))
-        if self.qlinear in ("fused", "fused+decode") and self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b,
-                                                                                alpha, trans_a):
+        route = self._route(self.qlinear, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b, alpha,
+                                                                              trans_a, decode))
+        self.qlinear_calls[route] += 1
+        if route != "torch":
             from .hip import ops
-            if self._qlinear_decodes(x[0]):
-                self.qlinear_calls["decode"] += 1
-                return ops.qlinear_matmul_decode(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias=bias, trans_b=trans_b)
-            self.qlinear_calls["fused"] += 1
-            return ops.qlinear_matmul(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias=bias, trans_b=trans_b)
-        self.qlinear_calls["torch"] += 1
+            fn = ops.qlinear_matmul_decode if route == "decode" else ops.qlinear_matmul
+            return fn(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias=bias, trans_b=trans_b)
         A = (x[0].to(torch.float32) - x[2].to(torch.float32)) * x[1]
         if a.get("transA", 0):
             A = A.t()
@@ -1259,17 +1255,12 @@ class GraphRunner:
         import torch
         K, N, bits, g = a["K"], a["N"], a.get("bits", 4), a["block_size"]
         blocks = (K + g - 1) // g
-        if self.matmul_nbits == "fused+decode" and self._nbits_fusable(x, bits, g, decode=True):
+        route = self._route(self.matmul_nbits, lambda decode: self._nbits_fusable(x, bits, g, decode))
+        self.nbits_calls[route] += 1
+        if route != "torch":
             from .hip import ops
-            self.nbits_calls["decode"] += 1
-            return ops.matmul_nbits_decode(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g,
-                                           bias=x[5] if len(x) > 5 else None)
-        if self.matmul_nbits in ("fused", "fused+decode") and self._nbits_fusable(x, bits, g):
-            from .hip import ops
-            self.nbits_calls["fused"] += 1
-            return ops.matmul_nbits(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g,
-                                    bias=x[5] if len(x) > 5 else None)
-        self.nbits_calls["torch"] += 1
+            fn = ops.matmul_nbits_decode if route == "decode" else ops.matmul_nbits
+            return fn(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g, bias=x[5] if len(x) > 5 else None)
         blob = x[1].reshape(N, blocks, -1).to(torch.uint8)
         if bits == 4:
             q = torch.stack([blob & 0x0F, blob >> 4], dim=-1).reshape(N, blocks, g)
@@ -1298,6 +1289,15 @@ class GraphRunner:
             out = out + x[5]
         return out
 
+    @staticmethod
+    def _route(mode, fusable) -> str:
+        """Which route takes a MatMulNBits / QLinearMatMul / QGemm node under ``mode``: "decode", "fused" or "torch", the keys of the
+        call counters.  ``fusable(decode)``: whether the decode / the tile kernel takes the node."""
+        if mode == "fused+decode" and fusable(True):
+            return "decode"
+        if mode in ("fused", "fused+decode") and fusable(False):
+            return "fused"
+        return "torch"
 
     def _nbits_fusable(self, x, bits, g, decode: bool = False) -> bool:
         """Whether `ops.matmul_nbits` (``decode``: `ops.matmul_nbits_decode`, which also wants at most 16 rows of A) takes this
@@ -1323,9 +1323,10 @@ class GraphRunner:
         return (x[1].dtype == torch.uint8 and x[2].dtype in (torch.float32, x[0].dtype) and (zp is None or zp.dtype in zp_types)
                 and (bias is None or (bias.is_cuda and bias.dtype == x[0].dtype)))
 
-    def _qlinear_fusable(self, A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias, trans_b, alpha, trans_a) -> bool:
-        """Whether `ops.qlinear_matmul` takes this QLinearMatMul / QGemm node: A an 8-bit tensor on the GPU, every parameter a tensor
-        on the GPU, B, its parameters and C constants of the model, and nothing the kernel leaves out."""
+    def _qlinear_fusable(self, A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias, trans_b, alpha, trans_a, decode: bool = False) -> bool:
+        """Whether `ops.qlinear_matmul` (``decode``: `ops.qlinear_matmul_decode`, which also wants at most 16 rows of A) takes this
+        QLinearMatMul / QGemm node: A an 8-bit tensor on the GPU, every parameter a tensor on the GPU, B, its parameters and C
+        constants of the model, and nothing the kernel leaves out."""
         import torch
         from .hip import ops
         if not (isinstance(A, torch.Tensor) and A.is_cuda and A.dtype in (torch.uint8, torch.int8) and A.ndim >= 1 and A.numel() > 0):
@@ -1336,14 +1337,8 @@ class GraphRunner:
         held = list(self.constants.values())
         if not all(t is None or any(t is c for c in held) for t in (B, b_scale, b_zp, bias)):
             return False
-        return ops.qlinear_matmul_unsupported(A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias=bias, trans_b=trans_b, alpha=alpha,
-                                              trans_a=trans_a) is None
-
-    def _qlinear_decodes(self, A) -> bool:
-        """Whether a node `_qlinear_fusable` accepted goes to `ops.qlinear_matmul_decode`: the mode asks for it and the flattened A has
-        at most 16 rows."""
-        from .hip import ops
-        return self.qlinear == "fused+decode" and A.numel() // A.shape[-1] <= ops.QL_DECODE_MAX_ROWS
+        unsupported = ops.qlinear_matmul_decode_unsupported if decode else ops.qlinear_matmul_unsupported
+        return unsupported(A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias=bias, trans_b=trans_b, alpha=alpha, trans_a=trans_a) is None
 
 
 _CAPTURE_MAX_INPUT_ELEMENTS = 1 << 20      # recording pays when a pass is hundreds of small launches (one short sequence), not above

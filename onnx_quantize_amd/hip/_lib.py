@@ -197,6 +197,17 @@ QLINEAR_DECODE_PROTOTYPES = {
                                         _i64, _p, _sz, _p]),
 }
 
+# what `load` binds and pins: (prototypes, the function that reports the version, the version this package expects, what the
+# message calls it)
+EXTENSIONS = [
+    (PROTOTYPES, "oq_abi_version", OQ_ABI_VERSION, "ABI"),
+    (HALF_PROTOTYPES, "oq_half_extension_version", OQ_HALF_EXTENSION_VERSION, "half-precision extension"),
+    (NBITS_PROTOTYPES, "oq_nbits_extension_version", OQ_NBITS_EXTENSION_VERSION, "MatMulNBits extension"),
+    (NBITS_DECODE_PROTOTYPES, "oq_nbits_decode_extension_version", OQ_NBITS_DECODE_EXTENSION_VERSION, "MatMulNBits decode extension"),
+    (QLINEAR_PROTOTYPES, "oq_qlinear_extension_version", OQ_QLINEAR_EXTENSION_VERSION, "QLinearMatMul extension"),
+    (QLINEAR_DECODE_PROTOTYPES, "oq_qlinear_decode_extension_version", OQ_QLINEAR_DECODE_EXTENSION_VERSION, "QLinearMatMul decode extension"),
+]
+
 _lock = threading.Lock()
 _lib = None
 
@@ -223,32 +234,18 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:  # missing ROCm runtime etc.
             raise OqHipMissing(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in [*PROTOTYPES.items(), *HALF_PROTOTYPES.items(), *NBITS_PROTOTYPES.items(),
-                                   *NBITS_DECODE_PROTOTYPES.items(), *QLINEAR_PROTOTYPES.items(),
-                                   *QLINEAR_DECODE_PROTOTYPES.items()]:
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise OqHipMissing(f"{LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype = res
-            fn.argtypes = args
-        if lib.oq_abi_version() != OQ_ABI_VERSION:
-            raise OqHipMissing(f"{LIB_PATH} has ABI {lib.oq_abi_version()}, expected {OQ_ABI_VERSION}")
-        if lib.oq_half_extension_version() != OQ_HALF_EXTENSION_VERSION:
-            raise OqHipMissing(f"{LIB_PATH} has half-precision extension {lib.oq_half_extension_version()}, "
-                               f"expected {OQ_HALF_EXTENSION_VERSION}")
-        if lib.oq_nbits_extension_version() != OQ_NBITS_EXTENSION_VERSION:
-            raise OqHipMissing(f"{LIB_PATH} has MatMulNBits extension {lib.oq_nbits_extension_version()}, "
-                               f"expected {OQ_NBITS_EXTENSION_VERSION}")
-        if lib.oq_nbits_decode_extension_version() != OQ_NBITS_DECODE_EXTENSION_VERSION:
-            raise OqHipMissing(f"{LIB_PATH} has MatMulNBits decode extension {lib.oq_nbits_decode_extension_version()}, "
-                               f"expected {OQ_NBITS_DECODE_EXTENSION_VERSION}")
-        if lib.oq_qlinear_extension_version() != OQ_QLINEAR_EXTENSION_VERSION:
-            raise OqHipMissing(f"{LIB_PATH} has QLinearMatMul extension {lib.oq_qlinear_extension_version()}, "
-                               f"expected {OQ_QLINEAR_EXTENSION_VERSION}")
-        if lib.oq_qlinear_decode_extension_version() != OQ_QLINEAR_DECODE_EXTENSION_VERSION:
-            raise OqHipMissing(f"{LIB_PATH} has QLinearMatMul decode extension {lib.oq_qlinear_decode_extension_version()}, "
-                               f"expected {OQ_QLINEAR_DECODE_EXTENSION_VERSION}")
+        for prototypes, _, _, _ in EXTENSIONS:
+            for name, (res, args) in prototypes.items():
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError as e:
+                    raise OqHipMissing(f"{LIB_PATH} does not export {name}; rebuild it") from e
+                fn.restype = res
+                fn.argtypes = args
+        for _, version, expected, what in EXTENSIONS:
+            found = getattr(lib, version)()
+            if found != expected:
+                raise OqHipMissing(f"{LIB_PATH} has {what} {found}, expected {expected}")
         _lib = lib
     return _lib
 

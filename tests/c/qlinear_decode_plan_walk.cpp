@@ -3,6 +3,8 @@
 // model widths it replays who takes what, the way the kernels index: every k of [0, K) lies in exactly one slice (KN: in exactly one
 // wave's stage of it), every column of [0, N) in exactly one workgroup's range, and the slab the entry point carves -- the same
 // carver on a heap block of exactly the measured size -- is the measured one.  A count kept outside its array is an ASan abort.
+// The MatMulNBits decode route (csrc/decode_plan.hpp, which the header above includes for the row tiers both routes share) is walked
+// the same way: every k of [0, K) in exactly one slice, every row of B in exactly one workgroup's range and one iteration of it.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -93,6 +95,46 @@ static void walk(int64_t M, int64_t K, int64_t N, int layout) {
     free(block);
 }
 
+static void walk_nbits(int64_t M, int64_t K, int64_t N, bool a_is_fp32) {
+    const DecodePlan pl = make_decode_plan(M, K, N, a_is_fp32);
+    auto check = [&](bool ok, const char* what) { expect(ok, what, M, K, N, a_is_fp32 ? -32 : -16); };
+    check(pl.tier == decode_tier(M) && pl.tier >= M && pl.tier <= kDecodeMaxRows, "the tier does not hold M rows");
+    int switched = 0;
+    with_decode_tier(pl.tier, [&](auto mt) { switched = decltype(mt)::value; });
+    check(switched == pl.tier, "the tier switch instantiates another tier");
+    check(pl.grid == pl.row_blocks * pl.splits && pl.grid > 0 && pl.grid < (int64_t(1) << 31), "the grid");
+    check(pl.slab_bytes == (pl.splits > 1 ? static_cast<size_t>(pl.splits) * M * N * 4 : 0), "the slab bytes");
+
+    // k: a slice is LK lanes x VAL consecutive k -- 32 x 32 at 4 bits, 64 x 16 at 8
+    std::vector<unsigned char> k_seen(static_cast<size_t>(K), 0);
+    for (int64_t split = 0; split < pl.splits; ++split) {
+        const int64_t k0 = split * kDecodeSlice;
+        check(k0 < K, "an empty slice");
+        for (int lane = 0; lane < 64; ++lane)
+            for (int v = 0; v < 16; ++v)
+                if (k0 + 16 * lane + v < K) ++k_seen[static_cast<size_t>(k0 + 16 * lane + v)];
+    }
+    bool once = true;
+    for (unsigned char c : k_seen) once = once && c == 1;
+    check(once, "a k is covered not exactly once");
+
+    // rows of B: iterations of 8, 16 or 32 rows (vector ALU: rows of a pass x rows in flight) or 64 (matrix cores: 4 waves x 16)
+    check(pl.rows_per_block % kDecodeRowUnit == 0, "a workgroup's rows are no whole iterations");
+    for (int64_t step : {8, 16, 32, 64}) {
+        std::vector<unsigned char> n_seen(static_cast<size_t>(N), 0);
+        for (int64_t rb = 0; rb < pl.row_blocks; ++rb) {
+            const int64_t n_begin = rb * pl.rows_per_block, n_end = std::min(N, n_begin + pl.rows_per_block);
+            check(n_begin < N, "an empty row block");
+            for (int64_t row0 = n_begin; row0 < n_end; row0 += step)
+                for (int64_t i = 0; i < step; ++i)
+                    if (row0 + i < N) ++n_seen[static_cast<size_t>(row0 + i)];
+        }
+        once = true;
+        for (unsigned char c : n_seen) once = once && c == 1;
+        check(once, "a row of B is covered not exactly once");
+    }
+}
+
 int main() {
     const int64_t Ms[] = {1, 2, 4, 5, 8, 9, 16};
     const int64_t Ks[] = {1, 3, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2050, 4096, 11008};
@@ -111,6 +153,11 @@ int main() {
                 expect(pl.grid >= 192 && pl.grid <= 640, "a model width off one to two workgroups per compute unit", M, s[0], s[1], layout);
             }
         }
-    printf("walked=%d bad=%d\n", walked, bad);
+    int nbits_walked = 0;
+    for (int64_t M : {int64_t(1), int64_t(4), int64_t(5), int64_t(16)})
+        for (int64_t K : Ks)
+            for (int64_t N : Ns)
+                for (bool a_is_fp32 : {false, true}) walk_nbits(M, K, N, a_is_fp32), ++nbits_walked;
+    printf("walked=%d nbits_walked=%d bad=%d\n", walked, nbits_walked, bad);
     return bad != 0;
 }

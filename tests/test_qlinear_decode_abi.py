@@ -194,4 +194,4 @@ def test_the_plan_covers_every_k_and_every_column_once_under_asan(tmp_path):
                     "-I", CSRC, WALK, "-o", exe], check=True, capture_output=True, text=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "bad=0" in r.stdout and "walked=3332" in r.stdout
+    assert "bad=0" in r.stdout and "walked=3332" in r.stdout and "nbits_walked=1904" in r.stdout      # 4 M x 17 K x 14 N x 2 types of A
