@@ -105,12 +105,23 @@ inline int32_t extents_and_flags_ok(const NbitsRoute& r, int64_t M, int64_t K, i
     return OQ_OK;
 }
 
+// A, Y, bias and scales are aligned to their elements
+inline int32_t element_alignment_ok(const char* fn, const void* A, const void* Y, const void* bias, const void* scales, int32_t atype, int32_t scales_type) {
+    const uintptr_t elem = atype == OQ_NBITS_F32 ? 4 : 2;
+    OQ_REQUIRE(aligned_to(A, elem) && aligned_to(Y, elem) && aligned_to(bias, elem) && aligned_to(scales, scales_type == OQ_NBITS_F32 ? 4 : 2),
+               OQ_ERR_INVALID_ARGUMENT, "%s: A, Y, bias and scales must be aligned to their element", fn);
+    return OQ_OK;
+}
+
 // `ws` has carved the route's plan from (workspace, workspace_bytes)
-inline int32_t blob_and_workspace_ok(const char* fn, const void* B, const Workspace& ws, const void* workspace, size_t workspace_bytes) {
-    OQ_REQUIRE(aligned_to(B, 16), OQ_ERR_INVALID_ARGUMENT, "%s: B must be 16-byte aligned", fn);
+inline int32_t workspace_ok(const char* fn, const Workspace& ws, const void* workspace, size_t workspace_bytes) {
     OQ_REQUIRE(ws.total() == 0 || ws.fits(), OQ_ERR_WORKSPACE, "%s: a 256-byte aligned workspace of %zu bytes is needed, %zu given", fn, ws.total(),
                workspace ? workspace_bytes : (size_t)0);
     return OQ_OK;
+}
+inline int32_t blob_and_workspace_ok(const char* fn, const void* B, const Workspace& ws, const void* workspace, size_t workspace_bytes) {
+    OQ_REQUIRE(aligned_to(B, 16), OQ_ERR_INVALID_ARGUMENT, "%s: B must be 16-byte aligned", fn);
+    return workspace_ok(fn, ws, workspace, workspace_bytes);
 }
 
 }  // namespace

@@ -43,7 +43,7 @@ def _as_model(model) -> Message:
 
 
 def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, extra_feeds=None, device="cuda",
-               matmul_nbits: str = "fused", qlinear: str = "torch") -> float:
+               matmul_nbits: str = "fused", qlinear: str = "torch", qdq: str = "torch") -> float:
     """exp(mean negative log-likelihood) of ``input_ids`` (1-D integers) under the causal LM ``model`` (a path, bytes or a parsed
     ModelProto), over the sliding windows of `perplexity_windows`.
 
@@ -60,7 +60,11 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     (`ops.qlinear_matmul`: exact int32 sums).  The default stays the expansion route: a fused output may differ from it by one
     output level, where the expansion's fp32 sum lands on the other side of a rounding boundary.  ``qlinear="fused+decode"`` goes to
     `GraphRunner` as it is: the nodes of windows of at most 16 tokens run on the decode kernel (`ops.qlinear_matmul_decode`), with
-    the bytes of ``"fused"``."""
+    the bytes of ``"fused"``.
+
+    ``qdq="fused"`` runs the product of every `quant`-domain QDQ function call -- the default output format -- from the stored
+    integers (`ops.qdq_matmul`: no fp32 copy of the weight is made per call).  The default stays the function body: the fused sum
+    differs from torch's fp32 GEMM on the dequantized weight in its last bits."""
     import torch
 
     from .graph_runner import GraphRunner
@@ -78,7 +82,7 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
         wanted = outputs[0]
     else:
         raise ValueError(f"perplexity: the model has outputs {outputs}, none of them named 'logits'")
-    runner = GraphRunner(proto, outputs=[wanted], device=device, matmul_nbits=matmul_nbits, qlinear=qlinear)
+    runner = GraphRunner(proto, outputs=[wanted], device=device, matmul_nbits=matmul_nbits, qlinear=qlinear, qdq=qdq)
     if "input_ids" not in runner.input_names:
         raise ValueError(f"perplexity: the model declares no input 'input_ids' (inputs: {runner.input_names})")
     dev = runner.device

@@ -61,7 +61,7 @@ class GraphRunner:
     takes_sink = True        # `runner(feed, sink=...)` hands every wanted value over as it is produced (calibration_driver.run_calibration)
 
     def __init__(self, model: Message, outputs=None, device="cuda", capture: bool = False, matmul: str = "torch", constants=None,
-                 matmul_nbits: str = "torch", qlinear: str = "torch"):
+                 matmul_nbits: str = "torch", qlinear: str = "torch", qdq: str = "torch"):
         """`constants`: {initializer name: tensor on the device} for initializers the caller already holds in HBM (a second
         calibration walk over the weights the first one uploaded; a weight that was rescaled on the device and whose TensorProto
         still has the old bytes): used as they are instead of the file's bytes when device, element type and shape fit."""
@@ -109,6 +109,15 @@ class GraphRunner:
         self.qlinear_calls = {"fused": 0, "torch": 0}    # QLinearMatMul / QGemm nodes run per route (counted like nbits_calls)
         if self.qlinear == "fused+decode":
             self.qlinear_calls["decode"] = 0
+        # qdq = "fused": a call of a `quant`-domain QDQ function (onnx_functions: the default output format) whose body is the one
+        # `build_function` writes runs its product from the stored integers (`ops.qdq_matmul`: W [K, N] bytes, its scales and zero
+        # points as the file holds them; no fp32 weight is made).  The body's own operators around the product -- Q -> DQ of the
+        # input, of the output, DQ of the bias -- run as they are.  Every other call, and every call under "torch", walks the body.
+        if qdq not in ("torch", "fused"):
+            raise ValueError(f"GraphRunner: qdq must be 'torch' or 'fused', got {qdq!r}")
+        self.qdq = qdq if self.device.type == "cuda" else "torch"
+        self.qdq_calls = {"fused": 0, "torch": 0}        # calls of QDQ functions per route (counted like nbits_calls)
+        self._qdq_plans: dict = {}                       # id(function) -> (the function, _QdqPlan | None)
         self.functions = {(f.domain or "", f.name, f.overload or ""): f for f in model.functions}
         self.opset = max([int(o.version or 1) for o in model.opset_import if not o.domain] or [1])
         self.wanted = list(outputs) if outputs is not None else [o.name for o in self.graph.output]
@@ -145,6 +154,7 @@ class GraphRunner:
         self.capture, self._graphs, self._seen, self._moved, self._const_nodes = False, {}, set(), {}, {}
         self.matmul_nbits, self.nbits_calls = "torch", {"fused": 0, "torch": 0}
         self.qlinear, self.qlinear_calls = "torch", {"fused": 0, "torch": 0}
+        self.qdq, self.qdq_calls, self._qdq_plans = "torch", {"fused": 0, "torch": 0}, {}
         return self
 
     def evaluate(self, node, arrays) -> list:
@@ -350,7 +360,46 @@ class GraphRunner:
             env[name] = value
         for name in list(fn.input)[len(ins):]:
             env[name] = None
+        if _QdqPlan.named(fn):                 # counted per call, whatever route it takes
+            plan = self._qdq_plan(fn) if self.qdq == "fused" else None
+            outs = self._run_qdq_fused(fn, plan, dict(env)) if plan is not None else None
+            self.qdq_calls["torch" if outs is None else "fused"] += 1
+            if outs is not None:
+                return outs
         self._run(list(fn.node), env)          # a function body sees its inputs only (ONNX functions are closed)
+        return tuple(env[o] for o in fn.output)
+
+    def _qdq_plan(self, fn):
+        """The `_QdqPlan` of a `quant`-domain QDQ function whose body is the one `onnx_functions.build_function` writes under that
+        name; None for every other function -- a file may carry another function under a reference name."""
+        hit = self._qdq_plans.get(id(fn))
+        if hit is None or hit[0] is not fn:
+            hit = self._qdq_plans[id(fn)] = (fn, _QdqPlan.of(fn))
+        return hit[1]
+
+    def _run_qdq_fused(self, fn, plan, env):
+        """One call of a recognised QDQ function with its product on `ops.qdq_matmul`: the nodes of the body that dequantize W are
+        left out, the product node is replaced, every other node runs as it is.  Returns the function's outputs, or None --
+        nothing is kept -- where the kernel has no route for the call: the whole body then runs as under "torch"."""
+        import torch
+        from .hip import ops
+        w, scale, zp = env["W"], env["w_scale"], env["w_zero_point"]
+        held = list(self.constants.values())
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda and any(t is c for c in held) for t in (w, scale) + (() if zp is None else (zp,))):
+            return None
+        if plan.group_size:
+            shape = env.get("original_transposed_shape")
+            if not isinstance(shape, torch.Tensor) or shape.is_cuda or w.ndim != 2 or _ints(shape) != [w.shape[1], w.shape[0]]:
+                return None
+        nodes = list(fn.node)
+        self._run([n for i, n in enumerate(nodes[:plan.product]) if i not in plan.weight_nodes], env)      # the input side, the bias
+        x, bias = env[plan.x], env[plan.bias] if plan.bias else None
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.numel() > 0 and (bias is None or (isinstance(bias, torch.Tensor) and bias.is_cuda))):
+            return None
+        if w.ndim != 2 or ops.qdq_matmul_unsupported(x, w, scale, zp, group_size=plan.group_size, bias=bias) is not None:
+            return None
+        env[nodes[plan.product].output[0]] = ops.qdq_matmul(x, w, scale, zp, group_size=plan.group_size, bias=bias)
+        self._run(nodes[plan.product + 1:], env)                                                            # the output side
         return tuple(env[o] for o in fn.output)
 
     # ------------------------------------------------------------------------------------------------- operators
@@ -1347,6 +1396,57 @@ _PIECES_HEADROOM = 8                      # free HBM, in sizes of the weight, be
 _SCALAR_FRIENDLY = {"Add", "Sub", "Mul", "Div", "Pow"}
 _HOST_OPERANDS = {"GroupQueryAttention", "RotaryEmbedding", "CumSum", "Reshape", "Expand", "Slice", "Tile", "Unsqueeze", "Squeeze", "Split",
                   "ConstantOfShape", "Gather", "Trilu", "ReduceMean", "ReduceSum", "ReduceMax", "ReduceMin", "Range", "Clip", "Pad", "Resize", "TopK", "OneHot"}
+
+
+class _QdqPlan:
+    """How a `quant`-domain QDQ function (onnx_functions.py) is run with its product fused: which nodes of the body dequantize W
+    (left out), which one is the product (replaced), and what the product reads."""
+
+    def __init__(self, weight_nodes, product, x, bias, group_size):
+        self.weight_nodes, self.product, self.x, self.bias, self.group_size = weight_nodes, product, x, bias, group_size
+
+    @staticmethod
+    def _shape(fn):
+        """What is compared: inputs, outputs, and per node its operator, domain, wiring and attributes."""
+        return (list(fn.input), list(fn.output),
+                [(n.op_type, n.domain or "", list(n.input), list(n.output), sorted((a.name, repr(attribute_value(a))) for a in n.attribute))
+                 for n in fn.node])
+
+    @staticmethod
+    def named(fn) -> bool:
+        """`fn` carries the name of a QDQ function of the `quant` domain."""
+        from .onnx_functions import _QDQ, QUANT_DOMAIN
+        return (fn.domain or "") == QUANT_DOMAIN and (fn.name in _QDQ or fn.name in ("QMatMulWeightsOnlyGrouped", "QGemmWeightsOnlyGrouped"))
+
+    @classmethod
+    def of(cls, fn):
+        from .onnx_functions import _QDQ, build_function
+        if not cls.named(fn):
+            return None
+        nodes = list(fn.node)
+        if fn.name in _QDQ:
+            expected, group_size = build_function(fn.name), 0
+        elif fn.name in ("QMatMulWeightsOnlyGrouped", "QGemmWeightsOnlyGrouped"):
+            blocked = [n for n in nodes if n.op_type == "DequantizeLinear" and any(a.name == "block_size" for a in n.attribute)]
+            if len(blocked) != 1:
+                return None
+            group_size = int(attribute_value(next(a for a in blocked[0].attribute if a.name == "block_size")))
+            if group_size <= 0:
+                return None
+            expected = build_function(fn.name, group_size=group_size, four_bit=bool(nodes) and nodes[0].op_type == "Cast")
+        else:
+            return None
+        if cls._shape(fn) != cls._shape(expected):
+            return None
+        product = next(i for i, n in enumerate(nodes) if n.op_type in ("MatMul", "Gemm"))
+        node = nodes[product]
+        # the nodes between W and `dequantized_weights`: everything the product's second operand depends on
+        needed, weight_nodes = {node.input[1]}, set()
+        for i in range(product - 1, -1, -1):
+            if any(o in needed for o in nodes[i].output):
+                weight_nodes.add(i)
+                needed.update(name for name in nodes[i].input if name)
+        return cls(weight_nodes, product, node.input[0], node.input[2] if len(node.input) > 2 else None, group_size)
 
 
 class _Attrs:

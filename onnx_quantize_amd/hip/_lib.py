@@ -44,6 +44,8 @@ OQ_QL_PER_ROW_A, OQ_QL_TRANS_A, OQ_QL_ALPHA = 1, 2, 4
 OQ_QLINEAR_EXTENSION_VERSION = 1
 # include/oq_hip_qlinear_decode.h
 OQ_QLINEAR_DECODE_EXTENSION_VERSION = 1
+# include/oq_hip_qdq.h (its type codes are OQ_NBITS_*, OQ_UINT8 / OQ_INT8 and OQ_TENSOR / OQ_CHANNEL / OQ_GROUP above)
+OQ_QDQ_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -197,6 +199,13 @@ QLINEAR_DECODE_PROTOTYPES = {
                                         _i64, _p, _sz, _p]),
 }
 
+# the QDQ functions' fused product: mirrors include/oq_hip_qdq.h one to one (tests/test_qdq_matmul_abi.py checks the set)
+QDQ_PROTOTYPES = {
+    "oq_qdq_extension_version": (_i32, []),
+    "oq_qdq_matmul_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "oq_qdq_matmul": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i64, _p, _i32, _p, _p, _p, _i64, _p, _sz, _p]),
+}
+
 # what `load` binds and pins: (prototypes, the function that reports the version, the version this package expects, what the
 # message calls it)
 EXTENSIONS = [
@@ -206,6 +215,7 @@ EXTENSIONS = [
     (NBITS_DECODE_PROTOTYPES, "oq_nbits_decode_extension_version", OQ_NBITS_DECODE_EXTENSION_VERSION, "MatMulNBits decode extension"),
     (QLINEAR_PROTOTYPES, "oq_qlinear_extension_version", OQ_QLINEAR_EXTENSION_VERSION, "QLinearMatMul extension"),
     (QLINEAR_DECODE_PROTOTYPES, "oq_qlinear_decode_extension_version", OQ_QLINEAR_DECODE_EXTENSION_VERSION, "QLinearMatMul decode extension"),
+    (QDQ_PROTOTYPES, "oq_qdq_extension_version", OQ_QDQ_EXTENSION_VERSION, "QDQ matmul extension"),
 ]
 
 _lock = threading.Lock()

@@ -1287,6 +1287,87 @@ def matmul_nbits(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero
     return out.reshape(*x.shape[:-1], N)
 
 
+# ----------------------------------------------------------------------------- the product of a QDQ function from its stored integers
+_QDQ_WTYPE = {torch.uint8: L.OQ_UINT8, torch.int8: L.OQ_INT8}
+
+
+def _qdq_granularity(count: int, k: int, n: int, g: int) -> tuple[int, int] | None:
+    """(granularity code, group size handed to the library) read from the scale's element count: 1, N or N * K / g."""
+    if g > 0 and k % g == 0 and count == n * (k // g):      # first: a per-column count is also that of one group of K
+        return L.OQ_GROUP, g
+    if g > 0:
+        return None
+    if count == 1:
+        return L.OQ_TENSOR, 0
+    if count == n:
+        return L.OQ_CHANNEL, 0
+    return None
+
+
+def qdq_matmul_unsupported(x, w, scale, zero_point=None, *, group_size: int = 0, bias=None) -> str | None:
+    """Why `qdq_matmul` has no kernel for such a product (include/oq_hip_qdq.h), or None when it has one.  Element types, shapes
+    and the refusals of the entry point; where the tensors live is the caller's question."""
+    if x.dtype not in _NBITS_TYPE:
+        return f"an input of {x.dtype} (fp32, fp16 and bf16 have a kernel)"
+    if w.dtype not in _QDQ_WTYPE or w.ndim != 2:
+        return f"a weight of {w.dtype} and {w.ndim} axes (a uint8 / int8 [K, N] matrix has a kernel)"
+    k, n, g = int(w.shape[0]), int(w.shape[1]), int(group_size)
+    if x.ndim < 1 or x.shape[-1] != k:
+        return f"an input whose last axis is not K = {k}"
+    if g < 0 or (g and g % 32):
+        return f"group_size = {g} is no multiple of 32 (two groups would share one 32-deep matrix instruction)"
+    if g and k % g:
+        return f"K = {k} is no multiple of group_size = {g}"
+    if scale.dtype not in (torch.float32, x.dtype):
+        return f"scales of {scale.dtype} (float32 and the input's type have a kernel)"
+    if _qdq_granularity(scale.numel(), k, n, g) is None:
+        return f"{scale.numel()} scales for a [{k}, {n}] weight and group_size = {g} (1, N or N * K / group_size)"
+    if zero_point is not None and zero_point.dtype != w.dtype:
+        return f"a zero point of {zero_point.dtype} for a weight of {w.dtype}"
+    if zero_point is not None and zero_point.numel() != scale.numel():
+        return f"{zero_point.numel()} zero points for {scale.numel()} scales"
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != n):
+        return f"a bias of {bias.numel()} x {bias.dtype} (N values of the input's type)"
+    return None
+
+
+def qdq_matmul(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, zero_point: torch.Tensor | None = None, *, group_size: int = 0,
+               bias: torch.Tensor | None = None) -> torch.Tensor:
+    """The product of a `quant`-domain QDQ function from the integers it stores (`oq_qdq_matmul`, csrc/qdq_matmul.hip): ``x``
+    [..., K] fp32, fp16 or bf16 times dequant(W), ``w`` [K, N] uint8 or int8 (rows may be strided); ``scale`` fp32 or of x's type
+    with 1 (per tensor), N (per column) or N * K / group_size values (groups along K, entry n * (K / group_size) + k / group_size:
+    the flat order of the grouped functions' blocked DequantizeLinear); ``zero_point`` None (0) or of w's type, indexed like the
+    scale; ``bias`` [N] of x's type.  Returns [..., N] of x's type.  (q - zp) meets x on the matrix cores as an exact integer
+    operand, group sums are scaled in fp32: no fp32 [K, N] weight exists at any point.  Nothing synchronises with the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out (`qdq_matmul_unsupported`)."""
+    for t, name in ((x, "x"), (w, "w"), (scale, "scale")) + (((zero_point, "zero_point"),) if zero_point is not None else ()) + \
+            (((bias, "bias"),) if bias is not None else ()):
+        _require_device(t, name)
+    why = qdq_matmul_unsupported(x, w, scale, zero_point, group_size=group_size, bias=bias)
+    if why is not None:
+        raise NotImplementedError(f"qdq_matmul: {why}")
+    k, n = int(w.shape[0]), int(w.shape[1])
+    granularity, g = _qdq_granularity(scale.numel(), k, n, int(group_size))
+    w, ldw = _row_major(w)
+    scale = scale.contiguous()
+    zero_point = None if zero_point is None else zero_point.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    x2 = x.reshape(-1, k)
+    if x2.shape[0] == 0:
+        return torch.zeros((*x.shape[:-1], n), dtype=x.dtype, device=x.device)
+    x2, lda = _row_major(x2)
+    m = x2.shape[0]
+    out = torch.empty((m, n), dtype=x.dtype, device=x.device)
+    lib = L.load()
+    atype = _NBITS_TYPE[x.dtype]
+    need = lib.oq_qdq_matmul_workspace_bytes(m, k, n, atype)
+    ws = _workspace(need, x.device) if need else None
+    L.check(lib.oq_qdq_matmul(_ptr(x2), atype, m, k, lda, _ptr(w), _QDQ_WTYPE[w.dtype], n, ldw, granularity, g, _ptr(scale), _NBITS_TYPE[scale.dtype],
+                              _ptr(zero_point), _ptr(bias), _ptr(out), n, _ptr(ws), need, _stream()))
+    return out.reshape(*x.shape[:-1], n)
+
+
 DECODE_MAX_ROWS = 16      # include/oq_hip_nbits_decode.h: M of the decode route
 _DECODE_WORKSPACE: dict = {}      # (M, K, N, block size, type code) -> oq_matmul_nbits_decode_workspace_bytes
 
