@@ -32,9 +32,10 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # Per-file additions.  hqq.hip: the SLP vectoriser pairs the register tile's values for v_pk_mul / v_pk_add; the aligned
 # register pairs fragment the allocation until the G = 128 tile of hqq_rounds_reg_kernel spills (256 registers + scratch against
 # 165 registers without pairing; tests/test_kernel_resources.py watches it).
-# matmul_nbits.hip: paired, the per-group fold `sum = fma(acc, scale, sum)` becomes v_pk_fma_f32 with an op_sel on the scale pair, and
-# on the MI355X those gave wrong low halves in lanes 48 .. 63 whenever several waves shared a SIMD (docs/LAB_NOTES_r22.md;
-# tests/test_matmul_nbits_gpu.py holds exact products on large grids against it).
+# matmul_nbits.hip: paired, the per-group fold `sum = fma(acc, scale, sum)` of tile_gemm (csrc/nbits_tile.hpp) becomes v_pk_fma_f32 with
+# an op_sel on the scale pair, and on the MI355X those gave wrong low halves in lanes 48 .. 63 whenever several waves shared a SIMD
+# (docs/LAB_NOTES_r22.md; tests/test_matmul_nbits_gpu.py holds exact products on large grids against it, and
+# tests/test_qdq_matmul_resources.py finds no v_pk_fma_f32 in the file's assembly).
 # matmul_nbits_decode.hip: the same fold, sum = fma(acc, scale, sum), on the vector ALU throughout: built unpaired from its first compile
 # (tests/test_matmul_nbits_decode_resources.py finds no v_pk_fma_f32 in its assembly).
 # qdq_matmul.hip: the tile kernel of matmul_nbits.hip on a [K, N] byte matrix, the same fold: unpaired from its first compile too

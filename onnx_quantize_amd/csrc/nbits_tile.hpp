@@ -1,7 +1,23 @@
 // What the tile GEMMs on the exact (q - zp) matrix-core operand share (matmul_nbits.hip: B is the MatMulNBits blob; qdq_matmul.hip:
 // W is a [K, N] byte matrix): the argument block, the one rounding of a sum to Y's type, the guarded load
-// of eight elements of A, the kernel that adds the slabs of a split K, the kernel that splits an fp32 A into two fp16 pieces, and
-// the plan with its workspace.  Each file's GEMM kernel is its own: they differ in how B reaches LDS and in nothing else.
+// of eight elements of A, the body of the GEMM kernel (tile_gemm), the kernel that adds the slabs of a split K, the kernel that
+// splits an fp32 A into two fp16 pieces, the plan with its workspace, and the host tail of a call.  matmul_nbits.hip's GEMM kernel
+// is tile_gemm with the file's staging policy: how B reaches LDS and where a fragment finds it there, and nothing else.
+// qdq_matmul.hip's is a written-out copy of the same body with its staging in place: built on tile_gemm, its fp32-A kernel of the
+// 128-row tile measured 0.4 - 3 % slower at M = 2048, twice (docs/LAB_NOTES_r30.md).  A fix to the body is made in both.
+//
+//   block     256 threads = 2 x 2 waves; tile 32 * MT rows (MT = 4: 128; MT = 1: 32, for M <= 32) x 128 columns; k-step 64.
+//   wave      16 * MT x 64 outputs = MT x 4 MFMA tiles; per tile 4 fp32 of the group accumulator and 4 of the running sum.
+//   operands  both have k as their fast axis in LDS, which is what the 16x16x32 lane map wants (lane l: row / column l & 15,
+//             k = 8 (l >> 4) ... + 7): a 16-byte ds_read per fragment, rows padded to 144 bytes (conflict-free).
+//   staging   registers: the global loads of step i + 1 are issued before the MFMAs of step i; one LDS buffer, two barriers a step.
+//   fp32 A    nbits_split_rows_kernel writes two fp16 pieces per element under one power-of-two scale per row (the row's largest
+//             lands in [2^14, 2^15)): hi = fp16(x s), lo = fp16((x s - hi) 2^11).  lo meets B 2^-11 (exact: |q - zp| >= 1 keeps
+//             it a normal fp16), so both products share the accumulator.  A hi that would be an fp16 subnormal is dropped into lo.
+//   split K   few output tiles (small M): blockIdx.y takes a range of k-steps, writes its sum to slab y; nbits_reduce_kernel adds
+//             the slabs in slab order and finishes.  No atomics anywhere.
+//   guards    every global access is guarded by M, N, K: rows >= M, columns >= N and k >= K are zeros in LDS (A) or never read
+//             (scales); how a policy keeps its reads of B and of the zero points inside the operand is said where it reads them.
 #pragma once
 
 #include "nbits_common.hpp"
@@ -56,6 +72,141 @@ __device__ __forceinline__ u32x4 load_a8(const uint16_t* row, int64_t k, int64_t
         w[j] = e0 | (e1 << 16);
     }
     return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// ---- the GEMM.  Stage, a file's staging policy (today there is one, BlobStage<BITS> of matmul_nbits.hip), holds what one thread has
+// loaded of the next k-step of B:
+//   args                        the kernel's argument block, an NbitsArgs
+//   kRows, kFragStride          rows of the policy's LDS image of B; rows between a lane's fragments nt and nt + 1
+//   frag_row(wn, lane)          the image row of the lane's fragment nt = 0 in column half wn
+//   group(p, k), within(p, k)   the k-group of a k and k's place inside it
+//   Stage(p, tid, n0)           which part of the 64 x 128 step of B this thread stages
+//   load(p, k, k_begin, k_end)  global memory -> registers, for the step at k of the block's range [k_begin, k_end)
+//   store<OP>(p, lds_b)         registers -> (q - zp) as 2-byte operands in the image
+template <int OUT, int MT, typename Stage>
+__device__ __forceinline__ void tile_gemm(const typename Stage::args& p) {
+    typedef std::conditional_t<OUT == OQ_NBITS_BF16, OpBF16, OpF16> OP;
+    typedef typename OP::frag frag;
+    constexpr int PIECES = OUT == OQ_NBITS_F32 ? 2 : 1;
+    constexpr int BM = 32 * MT;
+    constexpr int NT = 4;
+    constexpr int A_CHUNKS = PIECES * BM * 8 / kThreads;      // 16-byte chunks of the A tile(s) per thread: PIECES * MT
+    __shared__ __attribute__((aligned(16))) unsigned char lds[(PIECES * BM + Stage::kRows) * kRow];
+    unsigned char* const lds_b = lds + PIECES * BM * kRow;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+    const int64_t m0 = static_cast<int64_t>(blockIdx.x % p.tiles_m) * BM;
+    const int64_t n0 = static_cast<int64_t>(blockIdx.x / p.tiles_m) * kBN;
+    const int64_t k_begin = static_cast<int64_t>(blockIdx.y) * p.steps_per_split * kBK;
+    const int64_t k_end = min(p.K, k_begin + p.steps_per_split * kBK);
+
+    // what this thread stages: A_CHUNKS chunks of A, and the policy's part of B
+    u32x4 a_regs[A_CHUNKS];
+    Stage b_stage(p, tid, n0);
+
+    auto load_step = [&](int64_t k) {
+#pragma unroll
+        for (int i = 0; i < A_CHUNKS; ++i) {
+            const int id = tid + i * kThreads;
+            const int piece = id / (BM * 8), r = (id >> 3) % BM, kc = id & 7;
+            const int64_t m = m0 + r;
+            const uint16_t* base = (PIECES == 2 && piece == 1) ? p.A_lo : p.A;
+            a_regs[i] = (m < p.M && k + kc * 8 < p.Ka) ? load_a8(base + m * p.lda, k + kc * 8, p.Ka, p.a_vec != 0) : u32x4{0u, 0u, 0u, 0u};
+        }
+        b_stage.load(p, k, k_begin, k_end);
+    };
+    auto store_step = [&]() {
+#pragma unroll
+        for (int i = 0; i < A_CHUNKS; ++i) {
+            const int id = tid + i * kThreads;
+            *reinterpret_cast<u32x4*>(lds + (id >> 3) * kRow + (id & 7) * 16) = a_regs[i];      // id >> 3 = piece * BM + r
+        }
+        b_stage.template store<OP>(p, lds_b);
+    };
+
+    f32x4 sum[MT][NT], acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) sum[mt][nt] = acc[mt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    const int64_t col = n0 + wn * 64 + (lane & 15);          // + 16 nt: the output column of this lane in tile nt
+    auto load_scales = [&](int64_t kb, float (&sc)[NT]) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int64_t n = col + 16 * nt;
+            sc[nt] = 0.0f;
+            if (n < p.N) sc[nt] = p.scales_f32 ? static_cast<const float*>(p.scales)[n * p.blocks + kb] : OP::one(static_cast<const uint16_t*>(p.scales)[n * p.blocks + kb]);
+        }
+    };
+    float sc[NT];
+    int64_t in_group = Stage::within(p, k_begin);      // k of the next MFMA depth inside its group
+    if (k_begin < k_end) load_scales(Stage::group(p, k_begin), sc);
+
+    const unsigned char* const a_frag = lds + (wm * 16 * MT + (lane & 15)) * kRow + (lane >> 4) * 16;
+    const unsigned char* const b_frag = lds_b + Stage::frag_row(wn, lane) * kRow + (lane >> 4) * 16;
+
+    if (k_begin < k_end) load_step(k_begin);
+    for (int64_t k = k_begin; k < k_end; k += kBK) {
+        store_step();
+        __syncthreads();
+        if (k + kBK < k_end) load_step(k + kBK);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int64_t ks = k + 32 * s;
+            if (ks < k_end) {
+                frag b[NT];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) b[nt] = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(b_frag + nt * Stage::kFragStride * kRow + s * 64));
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + mt * 16 * kRow + s * 64));
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = OP::mma(a, b[nt], acc[mt][nt]);
+                }
+                if constexpr (PIECES == 2) {
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) b[nt] = b[nt] * static_cast<_Float16>(0.00048828125f);      // 2^-11, exact
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) {
+                        const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + (BM + mt * 16) * kRow + s * 64));
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = OP::mma(a, b[nt], acc[mt][nt]);
+                    }
+                }
+                in_group += 32;
+                // The fold is one scalar fma per output element: the files that hold this body are built with -fno-slp-vectorize, paired
+                // (v_pk_fma_f32) it gave wrong sums on the MI355X (docs/LAB_NOTES_r22.md).
+                if (in_group == p.g || ks + 32 >= k_end) {      // the group (or this block's part of it) is complete
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) sum[mt][nt][r] = __builtin_fmaf(acc[mt][nt][r], sc[nt], sum[mt][nt][r]);
+                            acc[mt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                        }
+                    in_group = 0;
+                    if (ks + 32 < k_end) load_scales(Stage::group(p, ks + 32), sc);
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // C/D map of the 16x16 MFMAs: column = lane & 15, row = 4 (lane >> 4) + r
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t m = m0 + wm * 16 * MT + mt * 16 + 4 * (lane >> 4) + r, n = col + 16 * nt;
+                if (m < p.M && n < p.N) {
+                    if (p.slab) p.slab[(static_cast<int64_t>(blockIdx.y) * p.M + m) * p.N + n] = sum[mt][nt][r];
+                    else finish<OUT>(p, m, n, sum[mt][nt][r]);
+                }
+            }
 }
 
 // the slabs of a split K, added in slab order
@@ -120,6 +271,32 @@ Plan make_plan(int64_t M, int64_t K, int64_t N, int32_t atype, Workspace& ws) {
     return pl;
 }
 
+// the body of a file's workspace query: 0, after `refuse()` has set the file's message, for a type or a shape outside the bounds
+template <typename Refuse>
+size_t plan_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t g, int32_t atype, Refuse refuse) {
+    if (!type_ok(atype) || !tile_shape_ok(M, K, N, g)) {
+        refuse();
+        return 0;
+    }
+    Workspace ws(/* aligned_base */ true);
+    make_plan(M, K, N, atype, ws);
+    return ws.total();
+}
+
+// what every call fills in alike; B, g and blocks are the file's own
+inline void fill_args(NbitsArgs& p, const void* scales, int32_t scales_type, const void* zero_points, const void* bias, void* Y, int64_t ldy, int64_t M,
+                      int64_t N, int64_t K, const Plan& pl) {
+    p.scales = scales;
+    p.scales_f32 = scales_type == OQ_NBITS_F32;
+    p.zp = static_cast<const uint8_t*>(zero_points);
+    p.bias = bias;
+    p.Y = Y;
+    p.ldy = ldy;
+    p.M = M, p.N = N, p.K = K;
+    p.tiles_m = pl.tiles_m, p.steps_per_split = pl.steps_per_split;
+    p.slab = pl.slab;
+}
+
 // an fp32 A: its pieces and row exponents into the plan's workspace; `p` then reads them as its A
 inline int32_t split_rows(NbitsArgs& p, const Plan& pl, const void* A, int64_t M, int64_t K, int64_t lda, hipStream_t s) {
     nbits_split_rows_kernel<<<static_cast<unsigned>(M), kThreads, 0, s>>>(static_cast<const float*>(A), K, lda, pl.kp, pl.hi, pl.lo, pl.row_exp);
@@ -134,6 +311,18 @@ template <int OUT>
 int32_t reduce_slabs(const NbitsArgs& p, const Plan& pl, hipStream_t s) {
     nbits_reduce_kernel<OUT><<<static_cast<unsigned>(ceil_div(p.M * p.N, kThreads)), kThreads, 0, s>>>(p, static_cast<int>(pl.splits));
     return check_launch("nbits_reduce_kernel");
+}
+
+// the tail of a call: A as the kernel reads it, then the file's `run(out)`, out an integral constant of A's oq_nbits_type
+template <typename Run>
+int32_t run_for_a(NbitsArgs& p, const Plan& pl, const void* A, int32_t atype, int64_t M, int64_t K, int64_t lda, hipStream_t s, Run run) {
+    if (atype == OQ_NBITS_F32) {
+        const int32_t st = split_rows(p, pl, A, M, K, lda, s);
+        if (st != OQ_OK) return st;
+        return run(std::integral_constant<int, OQ_NBITS_F32>{});
+    }
+    p.A = static_cast<const uint16_t*>(A), p.lda = lda, p.Ka = K, p.a_vec = aligned_to(A, 16) && lda % 8 == 0;
+    return atype == OQ_NBITS_BF16 ? run(std::integral_constant<int, OQ_NBITS_BF16>{}) : run(std::integral_constant<int, OQ_NBITS_F16>{});
 }
 
 }  // namespace

@@ -28,6 +28,10 @@
 //   guards    rows >= M and k >= K of A are zeros in LDS.  No byte of W or of its parameters outside [K, N] is read: a thread whose
 //             rows run past K or whose columns run past N reads the last row / column again, which meets those zeros of A or
 //             lands in outputs that are never stored.
+//   body      the kernel below is tile_gemm (nbits_tile.hpp, the body of matmul_nbits.hip's kernels) written out with this file's
+//             staging in place.  Built on tile_gemm with the staging as a policy, the fp32-A kernel of the 128-row tile was 0.4 - 3 %
+//             slower at M = 2048 in two measurements (docs/LAB_NOTES_r30.md), so this copy stays: a fix to the k loop, the fold
+//             or the epilogue is made in both.
 // This file is built with -fno-slp-vectorize (_build.py) from its first compile: the fold below is the one that became v_pk_fma_f32
 // in matmul_nbits.hip and gave wrong sums on the MI355X (docs/LAB_NOTES_r22.md).
 #include "nbits_tile.hpp"
@@ -251,13 +255,9 @@ extern "C" {
 int32_t oq_qdq_extension_version(void) { return OQ_QDQ_EXTENSION_VERSION; }
 
 size_t oq_qdq_matmul_workspace_bytes(int64_t M, int64_t K, int64_t N, int32_t atype) {
-    if (!type_ok(atype) || !tile_shape_ok(M, K, N, K)) {
+    return plan_workspace_bytes(M, K, N, K, atype, [&] {
         set_error("oq_qdq_matmul_workspace_bytes: M=%lld K=%lld N=%lld atype=%d outside the bounds", (long long)M, (long long)K, (long long)N, atype);
-        return 0;
-    }
-    Workspace ws(/* aligned_base */ true);
-    make_plan(M, K, N, atype, ws);
-    return ws.total();
+    });
 }
 
 int32_t oq_qdq_matmul(const void* A, int32_t atype, int64_t M, int64_t K, int64_t lda, const void* W, int32_t wtype, int64_t N, int64_t ldw,
@@ -287,28 +287,14 @@ int32_t oq_qdq_matmul(const void* A, int32_t atype, int64_t M, int64_t K, int64_
 
     hipStream_t s = as_stream(stream);
     QdqArgs p{};
+    fill_args(p, scales, scales_type, zero_points, bias, Y, ldy, M, N, K, pl);
     p.B = static_cast<const uint8_t*>(W);
     p.ldw = ldw;
     p.flip = wtype == OQ_INT8 ? 0x80808080u : 0u;
     p.w_vec = aligned_to(W, 4) && ldw % 4 == 0;
-    p.scales = scales;
-    p.scales_f32 = scales_type == OQ_NBITS_F32;
-    p.zp = static_cast<const uint8_t*>(zero_points);
-    p.bias = bias;
-    p.Y = Y;
-    p.ldy = ldy;
-    p.M = M, p.N = N, p.K = K;
     p.g = grouped ? group_size : kOneGroup;
     p.blocks = grouped ? K / group_size : granularity == OQ_CHANNEL ? 1 : 0;
-    p.tiles_m = pl.tiles_m, p.steps_per_split = pl.steps_per_split;
-    p.slab = pl.slab;
-    if (atype == OQ_NBITS_F32) {
-        st = split_rows(p, pl, A, M, K, lda, s);
-        if (st != OQ_OK) return st;
-        return run<OQ_NBITS_F32>(p, pl, s);
-    }
-    p.A = static_cast<const uint16_t*>(A), p.lda = lda, p.Ka = K, p.a_vec = aligned_to(A, 16) && lda % 8 == 0;
-    return atype == OQ_NBITS_BF16 ? run<OQ_NBITS_BF16>(p, pl, s) : run<OQ_NBITS_F16>(p, pl, s);
+    return run_for_a(p, pl, A, atype, M, K, lda, s, [&](auto out) { return run<decltype(out)::value>(p, pl, s); });
 }
 
 }  // extern "C"

@@ -138,6 +138,16 @@ def _row_major(t: torch.Tensor) -> tuple[torch.Tensor, int]:
     return t, t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
 
 
+def _rows_and_out(x2: torch.Tensor, n: int, out_dtype):
+    """The tail of a matmul front, for ``x2`` = x.reshape(-1, k): (x2 row-major as the C ABI wants it, m, lda, a fresh [m, n] out),
+    or None where there are no rows (the front returns zeros and launches nothing)."""
+    m = x2.shape[0]
+    if m == 0:
+        return None
+    x2, lda = _row_major(x2)
+    return x2, m, lda, torch.empty((m, n), dtype=out_dtype, device=x2.device)
+
+
 def resolve_group(strategy: str, k: int, group_size) -> int:
     """Rows per (scale, zp): utils.py:16-22 for groups, K for channel / tensor."""
     if strategy != "group":
@@ -1245,46 +1255,7 @@ def matmul_nbits(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero
 
     NotImplementedError, naming the reason, for what the kernel leaves out: float zero points (HQQ), block sizes that are no
     multiple of 32 (16), bits other than 4 / 8."""
-    _require_device(x, "x")
-    why = matmul_nbits_unsupported(x.dtype, int(bits), int(block_size), zero_points)
-    if why is not None:
-        raise NotImplementedError(f"matmul_nbits: {why}")
-    K, N, bits, g = int(K), int(N), int(bits), int(block_size)
-    if x.shape[-1] != K:
-        raise ValueError(f"matmul_nbits: x has {x.shape[-1]} columns, the node K = {K}")
-    blocks = (K + g - 1) // g
-    _require_device(blob, "blob", torch.uint8)
-    if blob.numel() != N * blocks * (g * bits // 8):
-        raise ValueError(f"matmul_nbits: a blob of {N} x {blocks} x {g * bits // 8} bytes is expected, got {tuple(blob.shape)}")
-    blob = blob.contiguous()
-    _require_device(scales, "scales")
-    if scales.dtype not in (torch.float32, x.dtype) or scales.numel() != N * blocks:
-        raise ValueError(f"matmul_nbits: scales must be {N * blocks} values of float32 or {x.dtype}, got {scales.numel()} of {scales.dtype}")
-    scales = scales.contiguous()
-    if zero_points is not None:
-        _require_device(zero_points, "zero_points", torch.uint8)
-        expect = N * ((blocks + 1) // 2) if bits == 4 else N * blocks
-        if zero_points.numel() != expect:
-            raise ValueError(f"matmul_nbits: {expect} zero-point bytes are expected, got {zero_points.numel()}")
-        zero_points = zero_points.contiguous()
-    if bias is not None:
-        _require_device(bias, "bias", x.dtype)
-        if bias.numel() != N:
-            raise ValueError(f"matmul_nbits: bias must hold {N} values, got {bias.numel()}")
-        bias = bias.contiguous()
-    x2 = x.reshape(-1, K)
-    if x2.shape[0] == 0:
-        return torch.zeros((*x.shape[:-1], N), dtype=x.dtype, device=x.device)
-    x2, lda = _row_major(x2)
-    m = x2.shape[0]
-    out = torch.empty((m, N), dtype=x.dtype, device=x.device)
-    lib = L.load()
-    atype = _NBITS_TYPE[x.dtype]
-    need = lib.oq_matmul_nbits_workspace_bytes(m, K, N, g, atype)
-    ws = _workspace(need, x.device) if need else None
-    L.check(lib.oq_matmul_nbits(_ptr(x2), atype, m, K, lda, _ptr(blob), bits, N, g, _ptr(scales), _NBITS_TYPE[scales.dtype], _ptr(zero_points),
-                                _ptr(bias), 0, _ptr(out), N, _ptr(ws), need, _stream()))
-    return out.reshape(*x.shape[:-1], N)
+    return _nbits_call("matmul_nbits", x, blob, scales, zero_points, K, N, bits, block_size, bias, None, _nbits_tile_route)
 
 
 # ----------------------------------------------------------------------------- the product of a QDQ function from its stored integers
@@ -1353,12 +1324,10 @@ def qdq_matmul(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, zero_point
     scale = scale.contiguous()
     zero_point = None if zero_point is None else zero_point.contiguous()
     bias = None if bias is None else bias.contiguous()
-    x2 = x.reshape(-1, k)
-    if x2.shape[0] == 0:
+    rows = _rows_and_out(x.reshape(-1, k), n, x.dtype)
+    if rows is None:
         return torch.zeros((*x.shape[:-1], n), dtype=x.dtype, device=x.device)
-    x2, lda = _row_major(x2)
-    m = x2.shape[0]
-    out = torch.empty((m, n), dtype=x.dtype, device=x.device)
+    x2, m, lda, out = rows
     lib = L.load()
     atype = _NBITS_TYPE[x.dtype]
     need = lib.oq_qdq_matmul_workspace_bytes(m, k, n, atype)
@@ -1390,6 +1359,88 @@ def matmul_nbits_decode_unsupported(x_dtype, bits: int, block_size: int, zero_po
     return None
 
 
+def _nbits_tile_route(lib, key, current):
+    """`oq_matmul_nbits` with its workspace query, asked per call, on the current stream."""
+    return lib.oq_matmul_nbits, lib.oq_matmul_nbits_workspace_bytes(*key), _stream()
+
+
+def _nbits_decode_route(lib, key, current):
+    """`oq_matmul_nbits_decode`: the call is made per token, so the workspace size is remembered per shape (a decode loop asks for
+    the same few shapes thousands of times) and the stream handle taken raw."""
+    need = _DECODE_WORKSPACE.get(key)
+    if need is None:
+        need = _DECODE_WORKSPACE[key] = lib.oq_matmul_nbits_decode_workspace_bytes(*key)
+    return lib.oq_matmul_nbits_decode, need, C.c_void_p(_raw_stream(current))
+
+
+def _nbits_call(fn, x, blob, scales, zero_points, K, N, bits, block_size, bias, g_idx, route):
+    """What `matmul_nbits` and `matmul_nbits_decode` share: the checks, the operands as the C ABI wants them, the call.
+    ``route(lib, (M, K, N, block size, type code), current device)`` names the entry point, its workspace bytes and the stream.
+    The decode route also takes floating-point zero points (and says which kind they are: `zp_type`) and refuses by the rows."""
+    decode = route is _nbits_decode_route
+    current = None
+    if decode:
+        current = torch.cuda.current_device() if torch.cuda.is_available() else -1
+
+        def require(t, name, dtype=None):      # `_require_device` with the current device asked for once: this call is made per token
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != current or (dtype is not None and t.dtype != dtype):
+                _require_device(t, name, dtype)
+    else:
+        require = _require_device
+
+    require(x, "x")
+    K, N, bits, g = int(K), int(N), int(bits), int(block_size)
+    why = None if decode else matmul_nbits_unsupported(x.dtype, bits, g, zero_points)
+    if why is None and x.shape[-1] != K:
+        raise ValueError(f"{fn}: x has {x.shape[-1]} columns, the node K = {K}")
+    x2 = None
+    if decode:      # its refusals name the rows, which the columns have to be right for
+        x2 = x.reshape(-1, K)
+        why = matmul_nbits_decode_unsupported(x.dtype, bits, g, zero_points, g_idx, rows=x2.shape[0])
+    if why is not None:
+        raise NotImplementedError(f"{fn}: {why}")
+    blocks = (K + g - 1) // g
+    require(blob, "blob", torch.uint8)
+    if blob.numel() != N * blocks * (g * bits // 8):
+        raise ValueError(f"{fn}: a blob of {N} x {blocks} x {g * bits // 8} bytes is expected, got {tuple(blob.shape)}")
+    blob = blob.contiguous()
+    require(scales, "scales")
+    if scales.dtype not in (torch.float32, x.dtype) or scales.numel() != N * blocks:
+        raise ValueError(f"{fn}: scales must be {N * blocks} values of float32 or {x.dtype}, got {scales.numel()} of {scales.dtype}")
+    scales = scales.contiguous()
+    zp_type = (L.OQ_NBITS_ZP_PACKED_U8,) if decode else ()      # an argument of the decode entry point alone
+    if zero_points is not None:
+        expect = N * ((blocks + 1) // 2) if bits == 4 else N * blocks      # uint8, for 4 bits packed
+        if not decode:
+            require(zero_points, "zero_points", torch.uint8)
+            if zero_points.numel() != expect:
+                raise ValueError(f"{fn}: {expect} zero-point bytes are expected, got {zero_points.numel()}")
+        else:
+            require(zero_points, "zero_points")
+            if zero_points.is_floating_point():
+                expect, zp_type = N * blocks, (_NBITS_TYPE[zero_points.dtype],)
+            elif zero_points.dtype != torch.uint8:
+                raise ValueError(f"{fn}: zero points must be uint8 or floating point, got {zero_points.dtype}")
+            if zero_points.numel() != expect:
+                raise ValueError(f"{fn}: {expect} zero points ({zero_points.dtype}) are expected, got {zero_points.numel()}")
+        zero_points = zero_points.contiguous()
+    if bias is not None:
+        require(bias, "bias", x.dtype)
+        if bias.numel() != N:
+            raise ValueError(f"{fn}: bias must hold {N} values, got {bias.numel()}")
+        bias = bias.contiguous()
+    rows = _rows_and_out(x.reshape(-1, K) if x2 is None else x2, N, x.dtype)
+    if rows is None:
+        return torch.zeros((*x.shape[:-1], N), dtype=x.dtype, device=x.device)
+    x2, m, lda, out = rows
+    atype = _NBITS_TYPE[x.dtype]
+    entry, need, stream = route(L.load(), (m, K, N, g, atype), current)
+    ws = _workspace(need, x.device) if need else None
+    L.check(entry(_ptr(x2), atype, m, K, lda, _ptr(blob), bits, N, g, _ptr(scales), _NBITS_TYPE[scales.dtype], _ptr(zero_points), *zp_type,
+                  _ptr(bias), 0, _ptr(out), N, _ptr(ws), need, stream))
+    return out.reshape(*x.shape[:-1], N)
+
+
 def matmul_nbits_decode(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero_points: torch.Tensor | None = None, *, K: int,
                         N: int, bits: int, block_size: int, bias: torch.Tensor | None = None, g_idx: torch.Tensor | None = None) -> torch.Tensor:
     """The decode route of com.microsoft::MatMulNBits (`oq_matmul_nbits_decode`, csrc/matmul_nbits_decode.hip): the operands and
@@ -1400,61 +1451,7 @@ def matmul_nbits_decode(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tenso
 
     NotImplementedError, naming the reason, for what the kernel leaves out: more than 16 rows, block sizes that are no multiple
     of 16, bits other than 4 / 8, and a node that carries ``g_idx``."""
-    current = torch.cuda.current_device() if torch.cuda.is_available() else -1
-
-    def on_device(t, name, dtype=None):      # `_require_device` with the current device asked for once: this call is made per token
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != current or (dtype is not None and t.dtype != dtype):
-            _require_device(t, name, dtype)
-
-    on_device(x, "x")
-    K, N, bits, g = int(K), int(N), int(bits), int(block_size)
-    if x.shape[-1] != K:
-        raise ValueError(f"matmul_nbits_decode: x has {x.shape[-1]} columns, the node K = {K}")
-    x2 = x.reshape(-1, K)
-    why = matmul_nbits_decode_unsupported(x.dtype, bits, g, zero_points, g_idx, rows=x2.shape[0])
-    if why is not None:
-        raise NotImplementedError(f"matmul_nbits_decode: {why}")
-    blocks = (K + g - 1) // g
-    on_device(blob, "blob", torch.uint8)
-    if blob.numel() != N * blocks * (g * bits // 8):
-        raise ValueError(f"matmul_nbits_decode: a blob of {N} x {blocks} x {g * bits // 8} bytes is expected, got {tuple(blob.shape)}")
-    blob = blob.contiguous()
-    on_device(scales, "scales")
-    if scales.dtype not in (torch.float32, x.dtype) or scales.numel() != N * blocks:
-        raise ValueError(f"matmul_nbits_decode: scales must be {N * blocks} values of float32 or {x.dtype}, got {scales.numel()} of {scales.dtype}")
-    scales = scales.contiguous()
-    zp_type = L.OQ_NBITS_ZP_PACKED_U8
-    if zero_points is not None:
-        on_device(zero_points, "zero_points")
-        if zero_points.is_floating_point():
-            expect, zp_type = N * blocks, _NBITS_TYPE[zero_points.dtype]
-        elif zero_points.dtype == torch.uint8:
-            expect = N * ((blocks + 1) // 2) if bits == 4 else N * blocks
-        else:
-            raise ValueError(f"matmul_nbits_decode: zero points must be uint8 or floating point, got {zero_points.dtype}")
-        if zero_points.numel() != expect:
-            raise ValueError(f"matmul_nbits_decode: {expect} zero points ({zero_points.dtype}) are expected, got {zero_points.numel()}")
-        zero_points = zero_points.contiguous()
-    if bias is not None:
-        on_device(bias, "bias", x.dtype)
-        if bias.numel() != N:
-            raise ValueError(f"matmul_nbits_decode: bias must hold {N} values, got {bias.numel()}")
-        bias = bias.contiguous()
-    if x2.shape[0] == 0:
-        return torch.zeros((*x.shape[:-1], N), dtype=x.dtype, device=x.device)
-    x2, lda = _row_major(x2)
-    m = x2.shape[0]
-    out = torch.empty((m, N), dtype=x.dtype, device=x.device)
-    lib = L.load()
-    atype = _NBITS_TYPE[x.dtype]
-    key = (m, K, N, g, atype)
-    need = _DECODE_WORKSPACE.get(key)
-    if need is None:                                   # a decode loop asks for the same few shapes thousands of times
-        need = _DECODE_WORKSPACE[key] = lib.oq_matmul_nbits_decode_workspace_bytes(*key)
-    ws = _workspace(need, x.device) if need else None
-    L.check(lib.oq_matmul_nbits_decode(_ptr(x2), atype, m, K, lda, _ptr(blob), bits, N, g, _ptr(scales), _NBITS_TYPE[scales.dtype],
-                                       _ptr(zero_points), zp_type, _ptr(bias), 0, _ptr(out), N, _ptr(ws), need, C.c_void_p(_raw_stream(current))))
-    return out.reshape(*x.shape[:-1], N)
+    return _nbits_call("matmul_nbits_decode", x, blob, scales, zero_points, K, N, bits, block_size, bias, g_idx, _nbits_decode_route)
 
 
 # ----------------------------------------------------------------------------- QLinearMatMul / QGemm / MatMulInteger on the int8 matrix cores
