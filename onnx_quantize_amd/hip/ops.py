@@ -49,6 +49,13 @@ def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _item_table(rows, device):
+    """The per-item integer rows of a list entry point as the library takes them: (the contiguous int64 host array, its
+    pointer, its device copy -- one blocking copy; None for ``device`` None: an entry point that reads a list of one from the host)."""
+    host = np.asarray(rows, dtype=np.int64)
+    return host, C.c_void_p(host.ctypes.data), None if device is None else torch.from_numpy(host).to(device)
+
+
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -72,7 +79,29 @@ def _require_device(t: torch.Tensor, name: str, dtype=None) -> None:
 
 _ARENA_MIN_BYTES = 32 << 20
 _ARENA_MAX_STREAMS = 4
-_ARENA: dict = {}     # (device index, stream handle) -> scratch tensor, grow-only; most recently used last
+_ARENA: dict = {}       # the scratch tensors of `_workspace`
+_RTN_STATE: dict = {}    # the zero-filled state of the one-read channel / tensor RTN kernels
+_MINMAX_WS: dict = {}    # the workspace reused by every `minmax_collect` on a stream (plain dicts: that call reads its own with one `get`)
+
+
+def _stream_buffer(cache: dict, device, nbytes: int, alloc) -> torch.Tensor:
+    """What the three caches above have in common.  ``cache``: (device index, stream handle) -> ONE buffer of that stream, grow-only,
+    most recently used last, at most `_ARENA_MAX_STREAMS` entries; calls on a stream run in order, so the next call may
+    overwrite what the previous one left.  Returns the buffer of ``device``'s current stream, of at least ``nbytes``: a missing
+    or smaller one is replaced by ``alloc(nbytes, device)``.  "Used" means a call of this function: `minmax_collect` reads
+    `_MINMAX_WS` with a plain `get` on a hit, so that cache orders its streams by first use and a busy stream can lose its (small)
+    workspace to four newer ones; it then takes a new one here."""
+    dev = torch.device(device)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = (index, torch.cuda.current_stream(index).cuda_stream)
+    buf = cache.pop(key, None)
+    if buf is None or buf.numel() < nbytes:
+        del buf
+        buf = alloc(nbytes, torch.device("cuda", index))
+    cache[key] = buf                                   # (re-)inserted last: dicts keep insertion order
+    while len(cache) > _ARENA_MAX_STREAMS:             # a caller cycling through many streams must not pin one buffer per stream:
+        cache.pop(next(iter(cache)))                   # the least recently used one goes back to torch's allocator (stream-ordered)
+    return buf
 
 
 def _workspace(nbytes: int, device, keep: bool = False) -> torch.Tensor | None:
@@ -89,16 +118,7 @@ def _workspace(nbytes: int, device, keep: bool = False) -> torch.Tensor | None:
     nbytes = max(int(nbytes), 256)
     if nbytes < _ARENA_MIN_BYTES and not keep:
         return torch.empty(nbytes, dtype=torch.uint8, device=device)
-    dev = torch.device(device)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (index, torch.cuda.current_stream(index).cuda_stream)
-    buf = _ARENA.pop(key, None)
-    if buf is None or buf.numel() < nbytes:
-        del buf
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", index))
-    _ARENA[key] = buf                                   # (re-)inserted last: dicts keep insertion order
-    while len(_ARENA) > _ARENA_MAX_STREAMS:             # a caller cycling through many streams must not pin one buffer per stream:
-        _ARENA.pop(next(iter(_ARENA)))                  # the least recently used one goes back to torch's allocator (stream-ordered)
+    buf = _stream_buffer(_ARENA, device, nbytes, lambda n, dev: torch.empty(n, dtype=torch.uint8, device=dev))
     return buf[:nbytes]       # exactly what was asked for: some calls size their split-K slabs by the room they are given
 
 
@@ -109,25 +129,13 @@ def release_workspaces() -> None:
     _RTN_STATE.clear()
 
 
-_RTN_STATE: dict = {}     # (device index, stream handle) -> zero-filled state of the one-read channel / tensor RTN kernels
-
-
 def _rtn_state(nbytes: int, device) -> torch.Tensor | None:
     """The caller-kept state of `oq_rtn_quantize_stateful_f32`: zero before its first use and left zero by every call (the
     kernels clean up after themselves), so per-channel / per-tensor RTN needs no clear launch.  One buffer per (device,
     stream): calls on a stream run in order; at most four streams keep one.  A larger request takes a NEW zero-filled buffer."""
     if nbytes <= 0:
         return None
-    dev = torch.device(device)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (index, torch.cuda.current_stream(index).cuda_stream)
-    buf = _RTN_STATE.pop(key, None)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.zeros(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=torch.device("cuda", index))
-    _RTN_STATE[key] = buf
-    while len(_RTN_STATE) > _ARENA_MAX_STREAMS:
-        _RTN_STATE.pop(next(iter(_RTN_STATE)))
-    return buf
+    return _stream_buffer(_RTN_STATE, device, nbytes, lambda n, dev: torch.zeros(max(int(n), 1 << 20), dtype=torch.uint8, device=dev))
 
 
 def _row_major(t: torch.Tensor) -> tuple[torch.Tensor, int]:
@@ -173,6 +181,7 @@ _TWIN_WORKSPACE = {
     "awq_stats": {"f32": "oq_awq_stats_workspace_bytes", "h16": "oq_awq_stats_half_workspace_bytes"},
     "absmax": {"f32": "oq_absmax_workspace_bytes", "h16": "oq_absmax_half_workspace_bytes"},
     "hessian": {"f32": "oq_hessian_workspace_bytes", "h16": "oq_hessian_half_workspace_bytes"},
+    "hessian_many": {"f32": "oq_hessian_many_workspace_bytes", "h16": "oq_hessian_many_half_workspace_bytes"},
 }
 
 
@@ -386,8 +395,7 @@ def rtn_quantize_tensor_many(ws, qtype: str, symmetric=False, reduce_range=False
     s_all = torch.empty(len(flats), dtype=torch.float32, device=dev)
     z_all = torch.empty(len(flats), dtype=cdt, device=dev)
     qb, sb, zb = q_all.data_ptr(), s_all.data_ptr(), z_all.data_ptr()
-    table = torch.tensor([[f.data_ptr(), c, qb + o, sb + 4 * i, zb + i] for i, (f, c, o) in enumerate(zip(flats, counts, offs))],
-                         dtype=torch.int64).to(dev)
+    _, _, table = _item_table([[f.data_ptr(), c, qb + o, sb + 4 * i, zb + i] for i, (f, c, o) in enumerate(zip(flats, counts, offs))], dev)
     lib = L.load()
     wsb = _workspace(lib.oq_rtn_tensor_many_workspace_bytes(len(flats)), dev)
     L.check(lib.oq_rtn_tensor_many_f32(_ptr(table), len(flats), L.QTYPE_CODE[qtype], int(symmetric), int(reduce_range),
@@ -796,9 +804,6 @@ def minmax_state(device, dtype=torch.float32) -> torch.Tensor:
     return torch.zeros(4, dtype=dtype, device=device)
 
 
-_MINMAX_WS: dict = {}   # (device index, stream) -> workspace reused by every collect on that stream (calls are ordered)
-
-
 def minmax_collect(x: torch.Tensor, state: torch.Tensor, momentum: float = 0.0) -> None:
     """minmax.py:40-64: fold one activation batch into `state`, entirely on the device.  This sits in the
     calibration loop (thousands of tensors per run), so the host side is kept to one ctypes call.
@@ -819,10 +824,9 @@ def minmax_collect(x: torch.Tensor, state: torch.Tensor, momentum: float = 0.0) 
         raise ValueError("zero-size array to reduction operation minimum which has no identity")
     lib = L.load()
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    key = (x.device.index, stream)
-    ws = _MINMAX_WS.get(key)
+    ws = _MINMAX_WS.get((x.device.index, stream))      # a hit costs this lookup and no more: it does not move the entry to the end
     if ws is None:    # one workspace serves both entry points (neither size depends on the count)
-        ws = _MINMAX_WS[key] = _workspace(max(lib.oq_minmax_workspace_bytes(n), lib.oq_minmax_half_workspace_bytes(n)), x.device)
+        ws = _stream_buffer(_MINMAX_WS, x.device, max(lib.oq_minmax_workspace_bytes(n), lib.oq_minmax_half_workspace_bytes(n)), _workspace)
     if half:
         st = lib.oq_minmax_collect_h16(flat.data_ptr(), _HALF_WTYPE[x.dtype], n, state.data_ptr(), float(momentum), ws.data_ptr(),
                                        ws.numel(), stream)
@@ -851,8 +855,7 @@ def minmax_collect_many(xs, states, momentum: float = 0.0) -> None:
             raise ValueError("zero-size array to reduction operation minimum which has no identity")
         flats.append(f)
     dev = flats[0].device
-    table = torch.tensor([[f.data_ptr(), f.numel(), st.data_ptr()] for f, st in zip(flats, states)], dtype=torch.int64)
-    desc = table.to(dev, non_blocking=False)
+    _, _, desc = _item_table([[f.data_ptr(), f.numel(), st.data_ptr()] for f, st in zip(flats, states)], dev)
     lib = L.load()
     if dtype == torch.float32:
         ws = _workspace(lib.oq_minmax_many_workspace_bytes(len(flats)), dev)
@@ -908,9 +911,7 @@ def abs_stats_accumulate_many(xs, abs_sums, absmaxes) -> None:
         rows.append((x2.data_ptr(), t, k, ldx, sm.data_ptr(), mx.data_ptr()))
         keep.append(x2)
     lib = L.load()
-    host = np.asarray(rows, dtype=np.int64)
-    dev = torch.from_numpy(host).to(keep[0].device) if len(rows) > 1 else None          # 48 bytes per item, one blocking copy
-    hp = C.c_void_p(host.ctypes.data)
+    _host, hp, dev = _item_table(rows, keep[0].device if len(rows) > 1 else None)          # 48 bytes per item
     ws = _workspace(lib.oq_abs_stats_many_half_workspace_bytes(hp, len(rows)), keep[0].device)
     L.check(lib.oq_abs_stats_cols_many_h16(hp, _ptr(dev), len(rows), _HALF_WTYPE[dtype], _ptr(ws), ws.numel(), _stream()))
 
@@ -943,6 +944,30 @@ def _search_args(x, w, qtype, strategy, group_size):
     return x2, ldx, w2, ldw, gs
 
 
+def _awq_search(entry, query, query_args, lead, w2, ldw, quant, n_losses, scales_k=None):
+    """What the four AWQ searches share: the output buffers, the `_f32` / `_h16` twin of ``oq_<entry>``, its workspace (``query``
+    of `_TWIN_WORKSPACE` on ``query_args``) aligned to 256 bytes, the call and the read-back.  ``lead``: the arguments in front of
+    the weight (`_search_args`: X; `_stats_args`: the statistics); ``quant``: (qtype, strategy, gs, symmetric, reduce_range).
+    A scale search passes its grid as ``n_losses`` and K as ``scales_k`` (the entry point then takes the grid and the candidate
+    scales [n_losses, K]); a clip search passes its ten ratios and no ``scales_k``.
+    Returns (scales on device | None, the winner's index, losses float64 on host)."""
+    qtype, strategy, gs, symmetric, reduce_range = quant
+    n = w2.shape[1]
+    lib = L.load()
+    dev = w2.device
+    scales = None if scales_k is None else torch.empty((n_losses, scales_k), dtype=torch.float32, device=dev)
+    losses = torch.empty(n_losses, dtype=torch.float32, device=dev)
+    best = torch.zeros(1, dtype=torch.int32, device=dev)
+    wargs, kind = _twin(w2)
+    ws = _workspace(getattr(lib, _TWIN_WORKSPACE[query][kind])(*query_args) + 256, dev)
+    off = (-ws.data_ptr()) % 256
+    grid = () if scales is None else (int(n_losses), _ptr(scales))
+    L.check(getattr(lib, f"oq_{entry}_{kind}")(*lead, *wargs, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs, int(symmetric),
+                                               int(reduce_range), *grid, _ptr(losses), _ptr(best), C.c_void_p(ws.data_ptr() + off),
+                                               ws.numel() - off, _stream()))
+    return scales, int(best.item()), losses.double().cpu().numpy()
+
+
 def awq_scale_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
                      reduce_range=False, n_grid: int = 20):
     """pre_passes/awq.py:114-184 on the device, one C call (oq_awq_scale_search_f32): activation / weight statistics, the
@@ -953,20 +978,9 @@ def awq_scale_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str
     Returns (best_scale [K] on device, losses float64[n_grid] on host)."""
     x2, ldx, w2, ldw, gs = _search_args(x, w, qtype, strategy, group_size)
     t, k = x2.shape
-    n = w2.shape[1]
-    lib = L.load()
-    dev = w2.device
-    scales = torch.empty((n_grid, k), dtype=torch.float32, device=dev)
-    losses = torch.empty(n_grid, dtype=torch.float32, device=dev)
-    best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _twin(w2)
-    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq"][kind])(t, k, n) + 256, dev)
-    off = (-ws.data_ptr()) % 256
-    L.check(getattr(lib, "oq_awq_scale_search_" + kind)(_ptr(x2), t, k, ldx, *wargs, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
-                                                        int(symmetric), int(reduce_range), int(n_grid), _ptr(scales), _ptr(losses), _ptr(best),
-                                                        C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
-    lv = losses.double().cpu().numpy()
-    return scales[int(best.item())], lv
+    scales, best, lv = _awq_search("awq_scale_search", "awq", (t, k, w2.shape[1]), (_ptr(x2), t, k, ldx), w2, ldw,
+                                   (qtype, strategy, gs, symmetric, reduce_range), n_grid, scales_k=k)
+    return scales[best], lv
 
 
 def awq_clip_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
@@ -975,18 +989,9 @@ def awq_clip_search(x: torch.Tensor, w: torch.Tensor, qtype: str, strategy: str,
     read as it is (oq_awq_clip_search_h16, no fp32 copy) and gives the losses and the ratio of ``w.float()``, byte for byte."""
     x2, ldx, w2, ldw, gs = _search_args(x, w, qtype, strategy, group_size)
     t, k = x2.shape
-    n = w2.shape[1]
-    lib = L.load()
-    dev = w2.device
-    losses = torch.empty(10, dtype=torch.float32, device=dev)
-    best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _twin(w2)
-    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq"][kind])(t, k, n) + 256, dev)
-    off = (-ws.data_ptr()) % 256
-    L.check(getattr(lib, "oq_awq_clip_search_" + kind)(_ptr(x2), t, k, ldx, *wargs, n, ldw, L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs,
-                                                       int(symmetric), int(reduce_range), _ptr(losses), _ptr(best),
-                                                       C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
-    return 1 - int(best.item()) / 100, losses.double().cpu().numpy()
+    _, best, lv = _awq_search("awq_clip_search", "awq", (t, k, w2.shape[1]), (_ptr(x2), t, k, ldx), w2, ldw,
+                              (qtype, strategy, gs, symmetric, reduce_range), 10)
+    return 1 - best / 100, lv
 
 
 class SearchStatistics:
@@ -1015,12 +1020,16 @@ class SearchStatistics:
             return
         x2 = _flat_inputs(x if x.dtype == torch.float32 else x.to(torch.float32))
         x2, ldx = _row_major(x2)
+        self._fold_abs(x2, ldx)
+        self.rows = hessian_accumulate(x2, self.gram, self.rows)            # rows as samples: gram = (2 / rows) X^T X
+
+    def _fold_abs(self, x2: torch.Tensor, ldx: int) -> None:
+        """The |x| statistics of one fp32 batch ``x2`` [rows, K] with contiguous rows: the per-tensor kernels."""
         t, k = x2.shape
         lib = L.load()
         ws = _workspace(lib.oq_abs_sum_cols_workspace_bytes(k), x2.device)
         L.check(lib.oq_abs_sum_cols_f32(_ptr(x2), t, k, ldx, _ptr(self.abs_sum), 1, _ptr(ws), ws.numel(), _stream()))
         self.absmax = torch.maximum(self.absmax, absmax(x2))
-        self.rows = hessian_accumulate(x2, self.gram, self.rows)            # rows as samples: gram = (2 / rows) X^T X
 
     @staticmethod
     def add_many(stats: "list[SearchStatistics]", xs) -> None:
@@ -1036,16 +1045,12 @@ class SearchStatistics:
                 continue
             x2 = _flat_inputs(x if x.dtype == torch.float32 else x.to(torch.float32))
             flat.append(_row_major(x2)[0])
-        lib = L.load()
         half: dict = {}                   # element type -> positions
         for i, (st, x2) in enumerate(zip(stats, flat)):
             if x2.dtype in _HALF_WTYPE:
                 half.setdefault(x2.dtype, []).append(i)
-                continue
-            t, k = x2.shape
-            ws = _workspace(lib.oq_abs_sum_cols_workspace_bytes(k), x2.device)
-            L.check(lib.oq_abs_sum_cols_f32(_ptr(x2), t, k, x2.stride(0), _ptr(st.abs_sum), 1, _ptr(ws), ws.numel(), _stream()))
-            st.absmax = torch.maximum(st.absmax, absmax(x2))
+            else:
+                st._fold_abs(x2, x2.stride(0))
         for idx in half.values():
             abs_stats_accumulate_many([flat[i] for i in idx], [stats[i].abs_sum for i in idx], [stats[i].absmax for i in idx])
         if half or hessian_method() in ("auto", "f16x3"):                 # the method does not concern half items
@@ -1082,19 +1087,9 @@ def awq_scale_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: st
     An fp16 / bf16 ``w`` is read as it is (oq_awq_scale_search_stats_h16, no fp32 copy); the arithmetic of the search is fp32 and the
     result that of ``w.float()``, byte for byte."""
     w2, ldw, k, n, gs = _stats_args(stats, w, qtype, group_size)
-    lib = L.load()
-    dev = w2.device
-    scales = torch.empty((n_grid, k), dtype=torch.float32, device=dev)
-    losses = torch.empty(n_grid, dtype=torch.float32, device=dev)
-    best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _twin(w2)
-    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq_stats"][kind])(k, n) + 256, dev)
-    off = (-ws.data_ptr()) % 256
-    L.check(getattr(lib, "oq_awq_scale_search_stats_" + kind)(_ptr(stats.abs_sum), _ptr(stats.gram), stats.rows, k, *wargs, n, ldw,
-                                                              L.QTYPE_CODE[qtype], L.STRATEGY_CODE[strategy], gs, int(symmetric),
-                                                              int(reduce_range), int(n_grid), _ptr(scales), _ptr(losses), _ptr(best),
-                                                              C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
-    return scales[int(best.item())], losses.double().cpu().numpy()
+    scales, best, lv = _awq_search("awq_scale_search_stats", "awq_stats", (k, n), (_ptr(stats.abs_sum), _ptr(stats.gram), stats.rows, k), w2, ldw,
+                                   (qtype, strategy, gs, symmetric, reduce_range), n_grid, scales_k=k)
+    return scales[best], lv
 
 
 def awq_clip_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str, strategy: str, group_size, symmetric=False,
@@ -1102,17 +1097,9 @@ def awq_clip_search_stats(stats: "SearchStatistics", w: torch.Tensor, qtype: str
     """`awq_clip_search` from running statistics (oq_awq_clip_search_stats_f32): (best clip_ratio, losses[10]).
     An fp16 / bf16 ``w`` is read as it is (oq_awq_clip_search_stats_h16, no fp32 copy): the result of ``w.float()``, byte for byte."""
     w2, ldw, k, n, gs = _stats_args(stats, w, qtype, group_size)
-    lib = L.load()
-    dev = w2.device
-    losses = torch.empty(10, dtype=torch.float32, device=dev)
-    best = torch.zeros(1, dtype=torch.int32, device=dev)
-    wargs, kind = _twin(w2)
-    ws = _workspace(getattr(lib, _TWIN_WORKSPACE["awq_stats"][kind])(k, n) + 256, dev)
-    off = (-ws.data_ptr()) % 256
-    L.check(getattr(lib, "oq_awq_clip_search_stats_" + kind)(_ptr(stats.gram), stats.rows, k, *wargs, n, ldw, L.QTYPE_CODE[qtype],
-                                                             L.STRATEGY_CODE[strategy], gs, int(symmetric), int(reduce_range), _ptr(losses),
-                                                             _ptr(best), C.c_void_p(ws.data_ptr() + off), ws.numel() - off, _stream()))
-    return 1 - int(best.item()) / 100, losses.double().cpu().numpy()
+    _, best, lv = _awq_search("awq_clip_search_stats", "awq_stats", (k, n), (_ptr(stats.gram), stats.rows, k), w2, ldw,
+                              (qtype, strategy, gs, symmetric, reduce_range), 10)
+    return 1 - best / 100, lv
 
 
 def smooth_quant_scale_stats(stats: "SearchStatistics", w: torch.Tensor, alpha: float) -> torch.Tensor:
@@ -1710,28 +1697,22 @@ def hessian_accumulate_many(xs, hs, n_seen) -> list[int]:
         rows.append(row)
         keep.append(x2)
         out[i] = n_seen[i] + int(x.shape[0])
-    if rows:
-        import numpy as np
 
+    def launch(table, device, kind, *wtype):
+        """One launch chain: the items ``table`` (64 bytes each) of one element type."""
         lib = L.load()
-        host = np.asarray(rows, dtype=np.int64)
-        dev = torch.from_numpy(host).to(keep[0].device)                   # 64 bytes per item, one blocking copy
-        hp = C.c_void_p(host.ctypes.data)
-        ws = _workspace(lib.oq_hessian_many_workspace_bytes(hp, len(rows)), keep[0].device)
-        L.check(lib.oq_hessian_accumulate_many_f32(hp, _ptr(dev), len(rows), _ptr(ws), ws.numel(), _stream()))
+        _host, hp, dev = _item_table(table, device)
+        ws = _workspace(getattr(lib, _TWIN_WORKSPACE["hessian_many"][kind])(hp, len(table)), device)
+        L.check(getattr(lib, "oq_hessian_accumulate_many_" + kind)(hp, _ptr(dev), len(table), *wtype, _ptr(ws), ws.numel(), _stream()))
+
+    if rows:
+        launch(rows, keep[0].device, "f32")
     for dtype, items in half.items():
         if len(items) == 1:
             i = items[0][0]
             out[i] = hessian_accumulate(xs[i], hs[i], n_seen[i])
             continue
-        import numpy as np
-
-        lib = L.load()
-        host = np.asarray([row for _, row, _ in items], dtype=np.int64)
-        dev = torch.from_numpy(host).to(items[0][2].device)
-        hp = C.c_void_p(host.ctypes.data)
-        ws = _workspace(lib.oq_hessian_many_half_workspace_bytes(hp, len(items)), items[0][2].device)
-        L.check(lib.oq_hessian_accumulate_many_h16(hp, _ptr(dev), len(items), _HALF_WTYPE[dtype], _ptr(ws), ws.numel(), _stream()))
+        launch([row for _, row, _ in items], items[0][2].device, "h16", _HALF_WTYPE[dtype])
         for i, row, _ in items:
             out[i] = row[5] + row[6]
     return out
