@@ -197,7 +197,17 @@ int32_t oq_minmax_rows_f32(const float* x, int64_t R, int64_t C, int64_t ldx, fl
  *       per row  ([R] params) row_div=1 row_stride=1 col_stride=0   (the reference's preprocessed layout)
  *       per column ([C])      row_div=1 row_stride=0 col_stride=1   (channel params on [K, N])
  *       groups of g rows      row_div=g row_stride=1 col_stride=R/g (group params on [K, N])
- *     zp is int32 per entry; q is 1 byte per value (4/8-bit types) or int32 (32-bit types). */
+ *     zp is one 32-bit word per entry; q is 1 byte per value (4/8-bit types) or one 32-bit word (32-bit types).
+ *     Zero points (both functions): the word is read as a signed int32 for every type but OQ_UINT32, where it is read as
+ *     an UNSIGNED 32-bit integer (0 .. 2^32 - 1, the type's own range: a caller holding uint32 zero points passes their bits).
+ *     Nothing wraps: oq_quantize_f32 adds the zero point in exact integer arithmetic, oq_dequantize_f32 converts it to fp32
+ *     like NumPy's astype (exact below 2^24, round to nearest even above).
+ *     oq_quantize_f32 outside NumPy's defined casts: q = clamp(sat32(rint(x / scale)) + zp, qmin, qmax), the sum exact, where
+ *     sat32 saturates to [-2^31, 2^31 - 1] and maps NaN to 0.  So for the 4- / 8-bit types with a zero point inside the
+ *     type's range, x / scale = +inf or >= 2^31 gives qmax, -inf or < -2^31 gives qmin and NaN gives clamp(zp), whatever the
+ *     sign of zp; for the 32-bit types the same sums are clamped to the type's range.  (NumPy on x86-64 turns all of these
+ *     quotients into INT32_MIN and then wraps the int32 sum: qmin for zp >= 0, qmax for zp < 0.)  Wherever NumPy's cast is
+ *     defined and its int32 sum does not wrap, the result is NumPy's. */
 int32_t oq_quantize_f32(const float* x, int64_t R, int64_t C, int64_t ldx, const float* scale,
                         const int32_t* zp, int64_t row_div, int64_t row_stride, int64_t col_stride,
                         int32_t qtype, int32_t symmetric, int32_t reduce_range, void* q_out, void* stream);
@@ -212,7 +222,10 @@ int32_t oq_dequantize_fzp_f32(const void* q, int64_t R, int64_t C, int32_t qtype
                               float* x_out, int64_t ldo, void* stream);
 
 /* A3  core/_algorithms/rtn.py:112-138  _quantize_bias: bias_scale = w_scale * x_scale (fp32),
- *     q = clip(int32(rint(bias / bias_scale))).  w_scale has 1 or n entries. */
+ *     q = clip(int32(rint(bias / bias_scale))).  w_scale has 1 or n entries (anything else: OQ_ERR_INVALID_ARGUMENT,
+ *     nothing written).  A quotient outside int32 saturates (+inf and >= 2^31 give INT32_MAX, -inf and < -2^31 give
+ *     INT32_MIN) and NaN gives 0 -- a zero bias_scale included: bias / 0 is +-inf, 0 / 0 is NaN.  (NumPy's cast is
+ *     platform-defined there: INT32_MIN for all of them on x86-64.) */
 int32_t oq_quantize_bias_f32(const float* bias, int64_t n, const float* w_scale, int64_t n_w_scale,
                              float x_scale, int32_t* q_out, float* bias_scale_out, void* stream);
 

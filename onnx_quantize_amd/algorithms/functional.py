@@ -142,6 +142,17 @@ def _compute_qparams_from_array(array, quant_type, strategy, group_size, is_symm
 
 
 # ------------------------------------------------------------------ K1 - K3
+def _zero_point_words(zero_point, kind: str):
+    """Integer zero points on the device as the 32-bit words of oq_quantize_f32 / oq_dequantize_f32: read as unsigned for
+    "uint32", signed otherwise (include/oq_hip.h).  A value outside that reading's range would wrap on the way: ValueError."""
+    z = np.asarray(zero_point)
+    lo, hi = (0, 2**32 - 1) if kind == "uint32" else (-(2**31), 2**31 - 1)
+    if z.size and (int(z.min()) < lo or int(z.max()) > hi):
+        raise ValueError(f"zero point outside [{lo}, {hi}], the range the {kind} kernels read it in: min {int(z.min())}, max {int(z.max())}")
+    words = z.astype(np.uint32).view(np.int32) if kind == "uint32" else z.astype(np.int32)
+    return _dev(words, np.int32)
+
+
 def _param_mode(x: np.ndarray, scale) -> str:
     n = np.size(scale)
     if n == 1:
@@ -159,7 +170,7 @@ def _quantize_array_from_qparams(array, scale, zero_point, quant_type, is_symmet
 
     x = np.asarray(array, dtype=np.float32)
     mode = _param_mode(x, scale)
-    q = ops.quantize(_dev(x), _dev(scale), _dev(np.asarray(zero_point), np.int32), quant_type.key,
+    q = ops.quantize(_dev(x), _dev(scale), _zero_point_words(zero_point, quant_type.key), quant_type.key,
                      bool(is_symmetric), bool(reduce_range), mode=mode)
     return q.cpu().numpy().astype(quant_type.np_dtype, copy=False)
 
@@ -178,22 +189,22 @@ def _dequantize_array(q_array, scale, zero_point, *, preprocess=False, strategy=
     import torch
 
     qd = torch.from_numpy(np.ascontiguousarray(q)).cuda()
-    zdt = np.float32 if z.dtype.kind == "f" else np.int32          # HQQ's float zero points stay floats (utils.py:131)
+    zd = _dev(z, np.float32) if z.dtype.kind == "f" else _zero_point_words(z, kind)   # HQQ's float zero points stay floats (utils.py:131)
     if preprocess:
         assert strategy is not None, "strategy must be provided if preprocess is True"
         sname = _sname(strategy)
         if sname == "tensor":
-            out = ops.dequantize(qd, _dev(s), _dev(z, zdt), kind, mode="tensor")
+            out = ops.dequantize(qd, _dev(s), zd, kind, mode="tensor")
         elif sname == "channel":
-            out = ops.dequantize(qd, _dev(s), _dev(z, zdt), kind, mode="col")
+            out = ops.dequantize(qd, _dev(s), zd, kind, mode="col")
         else:
             k = q.shape[0]
             g = min(group_size, k)
             g = g if g != -1 else k
-            out = ops.dequantize(qd, _dev(s), _dev(z, zdt), kind, mode="group", group=g)   # ragged groups: flat addressing
+            out = ops.dequantize(qd, _dev(s), zd, kind, mode="group", group=g)   # ragged groups: flat addressing
         return out.cpu().numpy()
     mode = _param_mode(q, s)
-    return ops.dequantize(qd, _dev(s), _dev(z, zdt), kind, mode=mode).cpu().numpy()
+    return ops.dequantize(qd, _dev(s), zd, kind, mode=mode).cpu().numpy()
 
 
 def _fake_quantize_array(array, scale, zero_point, quant_type, is_symmetric, reduce_range):

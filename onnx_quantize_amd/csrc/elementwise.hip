@@ -1,6 +1,8 @@
 // Q1 / K1 / K2 / A3 and the wire-format packers as standalone gfx950 kernels.  These are the small
 // building blocks the reference calls by name (utils.py:72-137, :242-299; rtn.py:112-138;
 // qrules/_common.py:96-121; _pack.py:8-22); the bulk RTN path fuses them in rtn.hip instead.
+#include <type_traits>
+
 #include "oq_common.hpp"
 #include "row_params.hpp"
 
@@ -38,6 +40,30 @@ __global__ void qparams_kernel_f64(const double* rmin, const double* rmax, int64
     }
 }
 
+// K1 as oq_hip.h states it for the standalone entry point: q = clamp(sat32(rint(x / s)) + zp, qmin, qmax) with the sum taken
+// WITHOUT wrapping.  The float -> int32 conversion is v_cvt_i32_f32 (saturates, NaN -> 0) and the add clamps (v_add_i32 clamp), so
+// a quotient beyond int32 lands on the end of the range it left through, whatever the sign of zp.  On every input on which
+// oq_common.hpp::quantize_one does not wrap the two agree bit for bit; the RTN routes keep quantize_one (their quotients are bounded by the grid).
+__device__ __forceinline__ int32_t quantize_saturating(float x, float scale, int32_t zp, int32_t qmin, int32_t qmax) {
+    const int32_t r = static_cast<int32_t>(rintf(x / scale));
+    return min(max(__builtin_elementwise_add_sat(r, zp), qmin), qmax);
+}
+
+// The 32 bits of a zero point as the integer oq_hip.h says they are: unsigned for OQ_UINT32 (0 .. 2^32 - 1), signed otherwise.
+template <typename ContainerT>
+__device__ __forceinline__ int64_t zero_point_value(int32_t word) {
+    if constexpr (std::is_same_v<ContainerT, uint32_t>) return static_cast<int64_t>(static_cast<uint32_t>(word));
+    else return static_cast<int64_t>(word);
+}
+// ... and as the fp32 operand of K2 (utils.py:131 `zero_point.astype(float32)`: exact below 2^24, rounded to nearest even above)
+template <typename ContainerT>
+__device__ __forceinline__ float zero_point_f32(int32_t word) {
+    if constexpr (std::is_same_v<ContainerT, uint32_t>) return static_cast<float>(static_cast<uint32_t>(word));
+    else return static_cast<float>(word);
+}
+template <typename ContainerT>
+__device__ __forceinline__ float zero_point_f32(float z) { return z; }   // HQQ's float zero points are subtracted as they are
+
 template <typename OutT>
 __global__ __launch_bounds__(256) void quantize_kernel(const float* x, int64_t R, int64_t C, int64_t ldx,
                                                        const float* scale, const int32_t* zp, ParamIndex pi,
@@ -48,12 +74,12 @@ __global__ __launch_bounds__(256) void quantize_kernel(const float* x, int64_t R
         const int64_t r = t / C, c = t - r * C;
         const int64_t p = pi(r, c);
         if constexpr (sizeof(OutT) == 1) {
-            q[t] = static_cast<OutT>(quantize_one(x[r * ldx + c], scale[p], zp[p], static_cast<int32_t>(qmin),
-                                                  static_cast<int32_t>(qmax)));
+            q[t] = static_cast<OutT>(quantize_saturating(x[r * ldx + c], scale[p], zp[p], static_cast<int32_t>(qmin),
+                                                         static_cast<int32_t>(qmax)));
         } else {
-            // 32-bit containers: int32(rint(x / s)) + zp is evaluated in int64 before the clamp, which is
-            // what NumPy does for uint32 zero points and is equivalent for int32 ones inside the range.
-            const int64_t v = static_cast<int64_t>(static_cast<int32_t>(rintf(x[r * ldx + c] / scale[p]))) + zp[p];
+            // 32-bit containers: sat32(rint(x / s)) + zp is evaluated in int64 before the clamp, which is what NumPy does
+            // for uint32 zero points (read as unsigned here) and is equivalent for int32 ones while the sum stays inside int32.
+            const int64_t v = static_cast<int64_t>(static_cast<int32_t>(rintf(x[r * ldx + c] / scale[p]))) + zero_point_value<OutT>(zp[p]);
             q[t] = static_cast<OutT>(v < qmin ? qmin : (v > qmax ? qmax : v));
         }
     }
@@ -68,7 +94,7 @@ __global__ __launch_bounds__(256) void dequantize_kernel(const InT* q, int64_t R
         const int64_t r = t / C, c = t - r * C;
         const int64_t p = pi(r, c);
         // utils.py:130-132: both operands go to fp32 first (exact for |q| < 2^24; int32 rounds like astype)
-        out[r * ldo + c] = (static_cast<float>(q[t]) - static_cast<float>(zp[p])) * scale[p];
+        out[r * ldo + c] = (static_cast<float>(q[t]) - zero_point_f32<InT>(zp[p])) * scale[p];
     }
 }
 
@@ -118,7 +144,7 @@ __global__ __launch_bounds__(256) void tile_kernel(const float* __restrict__ xin
                     uint32_t o = 0;
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        o |= static_cast<uint32_t>(static_cast<uint8_t>(quantize_one(v[u][e], s[e], z[e], qmin, qmax))) << (8 * e);
+                        o |= static_cast<uint32_t>(static_cast<uint8_t>(quantize_saturating(v[u][e], s[e], z[e], qmin, qmax))) << (8 * e);
                     *reinterpret_cast<uint32_t*>(qout + (r + u) * C + c) = o;
                 } else {
                     f32x4 o;

@@ -14,7 +14,7 @@
 // Parity: np.power (fp32 powf) and NumPy's pairwise fp32 means are not bit-reproducible on a GPU, so zero points
 // agree to a few ulp and an integer may move where w / s + z lands within that distance of a tie; the row means
 // use NumPy's summation tree (8 strided partial sums per <= 128 elements, halves above) to stay as close as
-// possible.  tests/test_hqq_gpu.py states the tolerances.
+// possible.  tests/test_hqq.py states the tolerances.
 //
 // Element types: W is fp32, fp16 or bf16 (half_elem.hpp; oq_hqq_optimize_h16, oq_hip_half.h); the 2-byte types are read as they are and
 // converted exactly at the load, the arithmetic is the fp32 one in every instantiation.  The work split (one thread = one

@@ -741,6 +741,16 @@ def _ragged_group(r: int, c: int, mode: str, group: int) -> bool:
     return True
 
 
+def _zero_point_words(zp: torch.Tensor) -> torch.Tensor:
+    """Integer zero points as the flat 32-bit words of oq_quantize_f32 / oq_dequantize_f32 (include/oq_hip.h: read as unsigned
+    for uint32, signed otherwise).  A `torch.uint32` tensor hands over its bits; the other integer dtypes are narrowed to
+    32 bits, which keeps the bits of every value of either reading, so a uint32 zero point of 2^31 or more held in an int64
+    tensor arrives intact as well.  Values are not inspected (that would synchronise): they are the caller's contract."""
+    if zp.dtype == torch.uint32:
+        return zp.contiguous().reshape(-1).view(torch.int32)
+    return zp.to(torch.int32).contiguous().reshape(-1)
+
+
 def quantize(x: torch.Tensor, scale: torch.Tensor, zp: torch.Tensor, qtype: str, symmetric: bool,
              reduce_range: bool, mode: str = "tensor", group: int = 1) -> torch.Tensor:
     """utils.py:72-79.  x [R, C] fp32; (scale, zp) indexed per `mode` (see oq_quantize_f32)."""
@@ -752,7 +762,7 @@ def quantize(x: torch.Tensor, scale: torch.Tensor, zp: torch.Tensor, qtype: str,
     x2, ldx = _row_major(x2)
     r, c = x2.shape
     s = scale.to(torch.float32).contiguous().reshape(-1)
-    z = zp.to(torch.int32).contiguous().reshape(-1)
+    z = _zero_point_words(zp)
     q = torch.empty((r, c), dtype=container_dtype(qtype), device=x.device)
     rd, rs, cs = _param_index(mode, r, c, group)
     L.check(L.load().oq_quantize_f32(_ptr(x2), r, c, ldx, _ptr(s), _ptr(z), rd, rs, cs, L.QTYPE_CODE[qtype],
@@ -779,7 +789,7 @@ def dequantize(q: torch.Tensor, scale: torch.Tensor, zp: torch.Tensor, qtype: st
         L.check(L.load().oq_dequantize_fzp_f32(_ptr(q2), r, c, L.QTYPE_CODE[qtype], _ptr(s), _ptr(z), rd, rs, cs,
                                                _ptr(out), c, _stream()))
     else:
-        z = zp.to(torch.int32).contiguous().reshape(-1)
+        z = _zero_point_words(zp)
         L.check(L.load().oq_dequantize_f32(_ptr(q2), r, c, L.QTYPE_CODE[qtype], _ptr(s), _ptr(z), rd, rs, cs,
                                            _ptr(out), c, _stream()))
     return out.reshape(q.shape)
