@@ -27,8 +27,9 @@
  *   OQ_QL_OUT_U8/I8  q = rint(t / y_scale) + y_zp, saturated to the type               (rint: half to even; the division is IEEE)
  *
  * Left out, deliberately (OQ_ERR_UNSUPPORTED, by name -- such nodes stay on the caller's expanded route):
- *   per-row activation parameters, transA, alpha != 1 (`flags`), fp16 scales and outputs, fusing the QuantizeLinear in front or
- *   the DequantizeLinear behind, a cache of B's column sums across calls.
+ *   per-row activation parameters, transA, alpha != 1 (`flags`), fp16 scales and outputs, a cache of B's column sums across calls.
+ * The QuantizeLinear in front and the DequantizeLinear behind -- the body of a `quant`-domain QLinearMatMul / QLinearGemm function --
+ * are fused by the entry points of oq_hip_qlinear_function.h (fp32 in, fp32 out); this header's stay on 8-bit operands.
  */
 #ifndef OQ_HIP_QLINEAR_H
 #define OQ_HIP_QLINEAR_H

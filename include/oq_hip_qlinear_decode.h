@@ -39,8 +39,9 @@
  * synchronises with the host: the route can be captured into a graph.  Deterministic.
  *
  * Left out, deliberately (OQ_ERR_UNSUPPORTED, by name): M >= 17 (oq_qlinear_matmul is the route), per-row activation parameters,
- * transA, alpha != 1 (`flags`); as in oq_hip_qlinear.h: fp16 scales and outputs, fusing the QuantizeLinear in front or the
- * DequantizeLinear behind.  A cache of B's column sums across calls is not needed: the sums cost no read.
+ * transA, alpha != 1 (`flags`); as in oq_hip_qlinear.h: fp16 scales and outputs.  A cache of B's column sums across calls is not
+ * needed: the sums cost no read.  The QuantizeLinear in front and the DequantizeLinear behind are fused by
+ * oq_qlinear_function_decode (oq_hip_qlinear_function.h: fp32 in, fp32 out, this route's kernels and plan).
  */
 #ifndef OQ_HIP_QLINEAR_DECODE_H
 #define OQ_HIP_QLINEAR_DECODE_H

@@ -2,7 +2,8 @@
 // DESIGN.md 4.24, 4.27).  Device: the guarded loads of an 8-bit operand, the terms of the zero-point correction that belong to an
 // output column, and the epilogue -- acc -> Y in the order the headers state, every fp32 step one rounding.  Host (at the end): the
 // checks of a call and the operand block of the argument structs.  One text, so the two routes give the same bytes and refuse the
-// same calls with the same words.
+// same calls with the same words.  qlinear_function.hip (include/oq_hip_qlinear_function.h) runs the same routes on
+// an fp32 A and to an fp32 Y: its quantizer (quant_k16, a drop-in for load_k16) and the dequantizing step of finish_acc are here too.
 //
 // `P` is a kernel's argument block.  It names a_zp, a_signed, b_zp, b_signed, b_per_column, a_scale, b_scale, C, K (col_terms: also
 // colsum, colsum_slices, colsum_stride), and y_scale, y_zp, out, Y, ldy (finish: also rowsum).
@@ -59,8 +60,10 @@ __device__ __forceinline__ ColTerms col_terms(const P& p, uint32_t n) {
     return c;
 }
 
-// acc -> Y.  Every fp32 step is one rounding, in the order the header states.
-template <class P>
+// acc -> Y.  Every fp32 step is one rounding, in the order the header states.  DQ (include/oq_hip_qlinear_function.h; the 8-bit
+// output codes only): Y is fp32 and takes the dequantized value (fp32(q) - fp32(y_zp)) * y_scale in the place of q -- q is an
+// integer of the type's range held in fp32, so no conversion lies between.
+template <bool DQ = false, class P>
 __device__ __forceinline__ void finish_acc(const P& p, uint32_t m, uint32_t n, int32_t acc, float scale) {
     const int64_t at = static_cast<int64_t>(m) * p.ldy + n;
     if (p.out == OQ_QL_OUT_I32) {
@@ -75,14 +78,66 @@ __device__ __forceinline__ void finish_acc(const P& p, uint32_t m, uint32_t n, i
     const bool i8 = p.out == OQ_QL_OUT_I8;
     float q = rintf(t / p.y_scale[0]) + static_cast<float>(read_zp(p.y_zp, i8, 0));
     q = fminf(fmaxf(q, i8 ? -128.0f : 0.0f), i8 ? 127.0f : 255.0f);
+    if constexpr (DQ) {
+        static_cast<float*>(p.Y)[at] = (q - static_cast<float>(read_zp(p.y_zp, i8, 0))) * p.y_scale[0];
+        return;
+    }
     static_cast<uint8_t*>(p.Y)[at] = static_cast<uint8_t>(static_cast<int32_t>(q));
 }
 
 // S -> acc -> Y, for a kernel whose row sums lie in memory
-template <class P>
+template <bool DQ = false, class P>
 __device__ __forceinline__ void finish(const P& p, uint32_t m, uint32_t n, uint32_t S, const ColTerms& c) {
     const uint32_t rs = p.rowsum ? static_cast<uint32_t>(p.rowsum[m]) : 0u;
-    finish_acc(p, m, n, static_cast<int32_t>(S - c.zb * rs + c.add), c.scale);
+    finish_acc<DQ>(p, m, n, static_cast<int32_t>(S - c.zb * rs + c.add), c.scale);
+}
+
+// QuantizeLinear of an fp32 operand to an 8-bit type, per tensor (include/oq_hip_qlinear_function.h): what one element needs.
+struct QuantParams {
+    float scale, zp, lo, hi;
+};
+
+// of operand A of an argument block: a_scale, a_zp (NULL: 0) and the range of A's type
+template <class P>
+__device__ __forceinline__ QuantParams quant_of(const P& p) {
+    return QuantParams{p.a_scale[0], static_cast<float>(read_zp(p.a_zp, p.a_signed, 0)), p.a_signed ? -128.0f : 0.0f, p.a_signed ? 127.0f : 255.0f};
+}
+
+// q = sat(rint(x / scale) + zp) as the low byte of a dword: one IEEE division, rint to even, one addition, the clamp in fp32, then
+// the conversion.  +-inf and quotients beyond the range saturate; a NaN gives the bottom of the type (fmaxf returns its other operand),
+// as finish_acc does.  Not oq_common.hpp's quantize_one, which converts to int32 ahead of the zero point.
+__device__ __forceinline__ uint32_t quant_byte(float x, const QuantParams& q) {
+    const float v = fminf(fmaxf(rintf(x / q.scale) + q.zp, q.lo), q.hi);
+    return static_cast<uint32_t>(static_cast<int32_t>(v)) & 0xFFu;
+}
+
+// load_k16 for an fp32 row that is quantized on the way: 16 raw bytes of the 8-bit operand for k ... k + 15, past K the flip's byte.
+// No float at or beyond k = K is read.  `vec`: the row is 16-byte aligned (four 16-byte loads where the chunk lies inside K).
+__device__ __forceinline__ u32x4 quant_k16(const float* row, uint32_t k, uint32_t K, bool vec, const QuantParams& q, uint32_t flip) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    uint32_t w[4];
+    if (vec && k + 16u <= K) {
+        f32x4 x[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] = *reinterpret_cast<const f32x4*>(row + k + 4 * j);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            w[j] = 0u;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) w[j] |= quant_byte(x[j][b], q) << (8 * b);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            w[j] = 0u;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t kk = k + 4 * j + b;
+                w[j] |= (kk < K ? quant_byte(row[kk], q) : flip & 0xFFu) << (8 * b);
+            }
+        }
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
 }
 
 // 16 bytes of `row` from k on, as they are: the flip is applied by whoever consumes them, so that no load is followed by an

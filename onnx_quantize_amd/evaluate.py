@@ -60,7 +60,10 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     (`ops.qlinear_matmul`: exact int32 sums).  The default stays the expansion route: a fused output may differ from it by one
     output level, where the expansion's fp32 sum lands on the other side of a rounding boundary.  ``qlinear="fused+decode"`` goes to
     `GraphRunner` as it is: the nodes of windows of at most 16 tokens run on the decode kernel (`ops.qlinear_matmul_decode`), with
-    the bytes of ``"fused"``.
+    the bytes of ``"fused"``.  ``qlinear="function"`` and ``"function+decode"`` go to `GraphRunner` as they are too: every call of the
+    file's QLinearMatMul / QLinearGemm functions -- QuantizeLinear, the integer product, DequantizeLinear -- runs as one library call
+    (`ops.qlinear_function`; windows of at most 16 tokens on `ops.qlinear_function_decode` under ``"function+decode"``), with the bytes
+    of ``"fused"``, so the perplexity is the same number.
 
     ``qdq="fused"`` runs the product of every `quant`-domain QDQ function call -- the default output format -- from the stored
     integers (`ops.qdq_matmul`: no fp32 copy of the weight is made per call).  The default stays the function body: the fused sum

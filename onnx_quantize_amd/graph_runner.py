@@ -103,12 +103,23 @@ class GraphRunner:
         # qlinear = "fused+decode": such a node whose flattened A has at most 16 rows runs on the decode kernel
         # (`ops.qlinear_matmul_decode`: B streamed once, the same accumulator and epilogue, so the same bytes); every other node goes
         # as under "fused".  Only this mode counts a third route, "decode".
-        if qlinear not in ("torch", "fused", "fused+decode"):
-            raise ValueError(f"GraphRunner: qlinear must be 'torch', 'fused' or 'fused+decode', got {qlinear!r}")
+        # qlinear = "function": a call of a `quant`-domain function QLinearMatMul / QLinearGemm (onnx_functions: what a
+        # `format="qlinear"` file holds) whose body is the one `build_function` writes -- QuantizeLinear, the integer product,
+        # DequantizeLinear -- runs as ONE library call (`ops.qlinear_function`: fp32 in, fp32 out, the bytes of the three nodes), when
+        # W and every parameter are constants of the model on the GPU.  Every other call walks its body, whose integer node then goes
+        # as under "fused".  qlinear = "function+decode": such a call with at most 16 flattened rows runs on
+        # `ops.qlinear_function_decode`; everything else as under "function", the body's integer node as under "fused+decode".
+        if qlinear not in ("torch", "fused", "fused+decode", "function", "function+decode"):
+            raise ValueError(f"GraphRunner: qlinear must be 'torch', 'fused', 'fused+decode', 'function' or 'function+decode', got {qlinear!r}")
         self.qlinear = qlinear if self.device.type == "cuda" else "torch"
+        self._qlinear_node = _QLINEAR_NODE_MODE[self.qlinear]   # the route of a bare QLinearMatMul / QGemm node
         self.qlinear_calls = {"fused": 0, "torch": 0}    # QLinearMatMul / QGemm nodes run per route (counted like nbits_calls)
-        if self.qlinear == "fused+decode":
+        if self._qlinear_node == "fused+decode":
             self.qlinear_calls["decode"] = 0
+        self.qlinear_function_calls = {"function": 0, "body": 0}     # calls of the QLinear functions: one library call / the body walked
+        if self.qlinear == "function+decode":
+            self.qlinear_function_calls["decode"] = 0
+        self._qlinear_functions: dict = {}               # id(function) -> (the function, its body is the writer's)
         # qdq = "fused": a call of a `quant`-domain QDQ function (onnx_functions: the default output format) whose body is the one
         # `build_function` writes runs its product from the stored integers (`ops.qdq_matmul`: W [K, N] bytes, its scales and zero
         # points as the file holds them; no fp32 weight is made).  The body's own operators around the product -- Q -> DQ of the
@@ -153,7 +164,8 @@ class GraphRunner:
         self.functions, self.opset, self.wanted, self.input_names, self.constants, self.nodes, self.last_use = {}, opset, [], [], {}, [], {}
         self.capture, self._graphs, self._seen, self._moved, self._const_nodes = False, {}, set(), {}, {}
         self.matmul_nbits, self.nbits_calls = "torch", {"fused": 0, "torch": 0}
-        self.qlinear, self.qlinear_calls = "torch", {"fused": 0, "torch": 0}
+        self.qlinear, self._qlinear_node, self.qlinear_calls = "torch", "torch", {"fused": 0, "torch": 0}
+        self.qlinear_function_calls, self._qlinear_functions = {"function": 0, "body": 0}, {}
         self.qdq, self.qdq_calls, self._qdq_plans = "torch", {"fused": 0, "torch": 0}, {}
         return self
 
@@ -366,8 +378,41 @@ class GraphRunner:
             self.qdq_calls["torch" if outs is None else "fused"] += 1
             if outs is not None:
                 return outs
+        if self.qlinear in ("function", "function+decode") and _qlinear_function_named(fn):      # counted per call, like the QDQ functions
+            route, out = self._run_qlinear_function(fn, env)
+            self.qlinear_function_calls[route] += 1
+            if out is not None:
+                return (out,)
         self._run(list(fn.node), env)          # a function body sees its inputs only (ONNX functions are closed)
         return tuple(env[o] for o in fn.output)
+
+    def _run_qlinear_function(self, fn, env):
+        """One call of a `quant`-domain QLinearMatMul / QLinearGemm function as one library call: (route, the function's output), or
+        ("body", None) -- nothing was run -- where the body is not the one `onnx_functions.build_function` writes (a file may carry
+        another function under a reference name), W or a parameter is no constant of the model on the GPU, X is no fp32 tensor on
+        the GPU with elements, or the kernel has no route for the call: the body then runs node by node."""
+        import torch
+        from .hip import ops
+        hit = self._qlinear_functions.get(id(fn))
+        if hit is None or hit[0] is not fn:
+            from .onnx_functions import build_function
+            hit = self._qlinear_functions[id(fn)] = (fn, _QdqPlan._shape(fn) == _QdqPlan._shape(build_function(fn.name)))
+        if not hit[1]:
+            return "body", None
+        x = env["X"]
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim >= 1 and x.numel() > 0):
+            return "body", None
+        names = ("W", "w_scale", "w_zero_point", "x_scale", "x_zero_point", "out_scale", "out_zero_point") + (("B",) if fn.name == "QLinearGemm" else ())
+        held = list(self.constants.values())
+        if not all(env[n] is None or (isinstance(env[n], torch.Tensor) and env[n].is_cuda and any(env[n] is c for c in held)) for n in names):
+            return "body", None
+        args = (x, env["x_scale"], env["x_zero_point"], env["W"], env["w_scale"], env["w_zero_point"], env["out_scale"], env["out_zero_point"])
+        bias = env.get("B") if fn.name == "QLinearGemm" else None
+        if self.qlinear == "function+decode" and ops.qlinear_function_decode_unsupported(*args, bias=bias) is None:
+            return "decode", ops.qlinear_function_decode(*args, bias=bias)
+        if ops.qlinear_function_unsupported(*args, bias=bias) is None:
+            return "function", ops.qlinear_function(*args, bias=bias)
+        return "body", None
 
     def _qdq_plan(self, fn):
         """The `_QdqPlan` of a `quant`-domain QDQ function whose body is the one `onnx_functions.build_function` writes under that
@@ -1260,7 +1305,7 @@ class GraphRunner:
 
     def _op_QLinearMatMul(self, n, x, a, e):
         import torch
-        route = self._route(self.qlinear, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False,
+        route = self._route(self._qlinear_node, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False,
                                                                               decode))
         self.qlinear_calls[route] += 1
         if route != "torch":
@@ -1278,7 +1323,7 @@ class GraphRunner:
         y_scale = x[7] if len(x) > 7 else None
         y_zp = x[8] if len(x) > 8 else None
         trans_b, alpha, trans_a = bool(a.get("transB", 0)), a.get("alpha", 1.0), bool(a.get("transA", 0))
-        route = self._route(self.qlinear, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b, alpha,
+        route = self._route(self._qlinear_node, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b, alpha,
                                                                               trans_a, decode))
         self.qlinear_calls[route] += 1
         if route != "torch":
@@ -1390,7 +1435,17 @@ class GraphRunner:
         return unsupported(A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias=bias, trans_b=trans_b, alpha=alpha, trans_a=trans_a) is None
 
 
-_CAPTURE_MAX_INPUT_ELEMENTS = 1 << 20      # recording pays when a pass is hundreds of small launches (one short sequence), not above
+# `qlinear` -> how a bare QLinearMatMul / QGemm node is routed (`_route`): the function modes leave it to "fused" / "fused+decode"
+_QLINEAR_NODE_MODE = {"torch": "torch", "fused": "fused", "fused+decode": "fused+decode", "function": "fused", "function+decode": "fused+decode"}
+
+
+def _qlinear_function_named(fn) -> bool:
+    """`fn` carries the name of a QLinear function of the `quant` domain (onnx_functions._qlinear_function)."""
+    from .onnx_functions import QUANT_DOMAIN
+    return (fn.domain or "") == QUANT_DOMAIN and fn.name in ("QLinearMatMul", "QLinearGemm")
+
+
+_CAPTURE_MAX_INPUT_ELEMENTS = 1 << 20     # recording pays when a pass is hundreds of small launches (one short sequence), not above
 _PIECES_MIN_WIDTH, _PIECES_MIN_ROWS = 512, 256
 _PIECES_HEADROOM = 8                      # free HBM, in sizes of the weight, below which its fp16 pieces are not kept
 _SCALAR_FRIENDLY = {"Add", "Sub", "Mul", "Div", "Pow"}

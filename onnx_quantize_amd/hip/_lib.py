@@ -44,6 +44,8 @@ OQ_QL_PER_ROW_A, OQ_QL_TRANS_A, OQ_QL_ALPHA = 1, 2, 4
 OQ_QLINEAR_EXTENSION_VERSION = 1
 # include/oq_hip_qlinear_decode.h
 OQ_QLINEAR_DECODE_EXTENSION_VERSION = 1
+# include/oq_hip_qlinear_function.h
+OQ_QLINEAR_FUNCTION_EXTENSION_VERSION = 1
 # include/oq_hip_qdq.h (its type codes are OQ_NBITS_*, OQ_UINT8 / OQ_INT8 and OQ_TENSOR / OQ_CHANNEL / OQ_GROUP above)
 OQ_QDQ_EXTENSION_VERSION = 1
 
@@ -199,6 +201,18 @@ QLINEAR_DECODE_PROTOTYPES = {
                                         _i64, _p, _sz, _p]),
 }
 
+# a call of a QLinearMatMul / QLinearGemm function, fp32 in and out: mirrors include/oq_hip_qlinear_function.h one to one
+# (tests/test_qlinear_function_abi.py checks the set).  The argument list of oq_qlinear_matmul: A and Y are fp32, `out` is y_type.
+QLINEAR_FUNCTION_PROTOTYPES = {
+    "oq_qlinear_function_extension_version": (_i32, []),
+    "oq_qlinear_function_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "oq_qlinear_function": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _p, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _p, _p, _i32, _i32, _p, _i64,
+                                   _p, _sz, _p]),
+    "oq_qlinear_function_decode_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "oq_qlinear_function_decode": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _p, _p, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _p, _p, _i32, _i32, _p,
+                                          _i64, _p, _sz, _p]),
+}
+
 # the QDQ functions' fused product: mirrors include/oq_hip_qdq.h one to one (tests/test_qdq_matmul_abi.py checks the set)
 QDQ_PROTOTYPES = {
     "oq_qdq_extension_version": (_i32, []),
@@ -215,6 +229,7 @@ EXTENSIONS = [
     (NBITS_DECODE_PROTOTYPES, "oq_nbits_decode_extension_version", OQ_NBITS_DECODE_EXTENSION_VERSION, "MatMulNBits decode extension"),
     (QLINEAR_PROTOTYPES, "oq_qlinear_extension_version", OQ_QLINEAR_EXTENSION_VERSION, "QLinearMatMul extension"),
     (QLINEAR_DECODE_PROTOTYPES, "oq_qlinear_decode_extension_version", OQ_QLINEAR_DECODE_EXTENSION_VERSION, "QLinearMatMul decode extension"),
+    (QLINEAR_FUNCTION_PROTOTYPES, "oq_qlinear_function_extension_version", OQ_QLINEAR_FUNCTION_EXTENSION_VERSION, "QLinear function extension"),
     (QDQ_PROTOTYPES, "oq_qdq_extension_version", OQ_QDQ_EXTENSION_VERSION, "QDQ matmul extension"),
 ]
 

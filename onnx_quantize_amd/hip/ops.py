@@ -1514,10 +1514,12 @@ def _decode_route(lib, m, k, n, trans_b, current):
 
 
 def _qlinear_call(fn, a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scale, y_zero_point, bias, trans_b, alpha, trans_a, out_dtype,
-                  route=_tile_route, unsupported=None):
-    """What `qlinear_matmul` / `matmul_integer` and their decode twins share: the checks, the operands as the C ABI wants them, the
-    call.  ``route(lib, m, k, n, trans_b, current device)`` names the entry point, its workspace bytes and the stream;
-    ``unsupported`` the refusals of that entry point (by default `qlinear_matmul_unsupported`)."""
+                  route=_tile_route, unsupported=None, codes=None):
+    """What `qlinear_matmul` / `matmul_integer`, their decode twins and `qlinear_function` / `qlinear_function_decode` share: the
+    checks, the operands as the C ABI wants them, the call.  ``route(lib, m, k, n, trans_b, current device)`` names the entry
+    point, its workspace bytes and the stream; ``unsupported`` the refusals of that entry point (by default
+    `qlinear_matmul_unsupported`); ``codes``: (a_type, the code in the place of `out`) where they are not those of ``a``'s and the
+    result's element types (the function entry points: fp32 on both sides)."""
     current = None
     if route is _tile_route:
         require = _require_device
@@ -1560,9 +1562,10 @@ def _qlinear_call(fn, a, a_scale, a_zero_point, b, b_scale, b_zero_point, y_scal
     lib = L.load()
     entry, need, stream = route(lib, m, k, n, trans_b, current)
     ws = _workspace(need, a.device) if need or route is _tile_route else None
-    L.check(entry(_ptr(a2), _QL_TYPE[a.dtype], m, k, lda, _ptr(a_scale), _ptr(a_zero_point), _ptr(b), _QL_TYPE[b.dtype],
+    a_code, out_code = codes if codes is not None else (_QL_TYPE[a.dtype], _QL_OUT[out_dtype])
+    L.check(entry(_ptr(a2), a_code, m, k, lda, _ptr(a_scale), _ptr(a_zero_point), _ptr(b), _QL_TYPE[b.dtype],
                   L.OQ_QL_NK if trans_b else L.OQ_QL_KN, n, ldb, _ptr(b_scale), _ptr(b_zero_point), int(per_column), _ptr(bias),
-                  _ptr(y_scale), _ptr(y_zero_point), 0, _QL_OUT[out_dtype], _ptr(out), n, _ptr(ws), need, stream))
+                  _ptr(y_scale), _ptr(y_zero_point), 0, out_code, _ptr(out), n, _ptr(ws), need, stream))
     return out.reshape(*a.shape[:-1], n)
 
 
@@ -1634,6 +1637,93 @@ def matmul_integer_decode(a: torch.Tensor, b: torch.Tensor, a_zero_point: torch.
     """MatMulInteger on the decode route: `matmul_integer` for an ``a`` of 1 ... 16 rows, the same int32 values."""
     return _qlinear_call("matmul_integer_decode", a, None, a_zero_point, b, None, b_zero_point, None, None, None, trans_b, 1.0, False, torch.int32,
                          route=_decode_route, unsupported=qlinear_matmul_decode_unsupported)
+
+
+def qlinear_function_unsupported(x, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, *, bias=None,
+                                 trans_b: bool = False) -> str | None:
+    """Why `qlinear_function` has no kernel for such operands (include/oq_hip_qlinear_function.h, "left out"), or None when it has
+    one: an ``x`` that is not fp32, a missing scale, and what `qlinear_matmul_unsupported` names for the product inside."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        return f"an x of {getattr(x, 'dtype', type(x).__name__)} (fp32 has a kernel)"
+    if x_scale is None or w_scale is None or out_scale is None:
+        return "a missing x_scale, w_scale or out_scale (the function has all three)"
+    a_dtype = torch.uint8 if x_zero_point is None else x_zero_point.dtype
+    if a_dtype not in _QL_TYPE:
+        return f"x_zero_point of {a_dtype} (uint8 and int8 have a kernel)"
+    quantized = torch.empty(x.shape, dtype=a_dtype, device="meta")      # what QuantizeLinear would hand to the product: shape and type
+    return qlinear_matmul_unsupported(quantized, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, bias=bias,
+                                      trans_b=trans_b)
+
+
+def qlinear_function_decode_unsupported(x, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, *, bias=None,
+                                        trans_b: bool = False, rows: int | None = None) -> str | None:
+    """Why `qlinear_function_decode` has no kernel for such operands, or None when it has one: what `qlinear_function_unsupported`
+    names, and more than 16 rows.  ``rows``: the rows of the flattened ``x`` (asked from ``x`` itself where it is None)."""
+    why = qlinear_function_unsupported(x, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, bias=bias, trans_b=trans_b)
+    if why is not None:
+        return why
+    if rows is None:
+        rows = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    if rows > QL_DECODE_MAX_ROWS:
+        return f"{rows} rows (the decode route takes 1 ... {QL_DECODE_MAX_ROWS}; qlinear_function takes the rest)"
+    return None
+
+
+def _function_route(lib, m, k, n, trans_b, current):
+    """`oq_qlinear_function` with its workspace query, asked per call, on the current stream."""
+    return lib.oq_qlinear_function, lib.oq_qlinear_function_workspace_bytes(m, k, n), _stream()
+
+
+_QL_FUNCTION_DECODE_WORKSPACE: dict = {}      # (M, K, N, layout code) -> oq_qlinear_function_decode_workspace_bytes
+
+
+def _function_decode_route(lib, m, k, n, trans_b, current):
+    """`oq_qlinear_function_decode`, per token: the workspace size remembered per shape, the stream handle taken raw (`_decode_route`)."""
+    key = (m, k, n, L.OQ_QL_NK if trans_b else L.OQ_QL_KN)
+    need = _QL_FUNCTION_DECODE_WORKSPACE.get(key)
+    if need is None:
+        need = _QL_FUNCTION_DECODE_WORKSPACE[key] = lib.oq_qlinear_function_decode_workspace_bytes(*key)
+    return lib.oq_qlinear_function_decode, need, C.c_void_p(_raw_stream(current))
+
+
+def _qlinear_function_call(fn, x, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, bias, trans_b, route, unsupported):
+    def refusal(a, *rest, alpha, trans_a, **kw):      # `_qlinear_call` also names alpha and transA, which a function call has not
+        return unsupported(a, *rest, **kw)
+
+    codes = (_QL_TYPE.get(torch.uint8 if x_zero_point is None else x_zero_point.dtype, -1),
+             _QL_TYPE.get(torch.uint8 if out_zero_point is None else out_zero_point.dtype, -1))      # y_type: an oq_ql_type
+    return _qlinear_call(fn, x, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, bias, trans_b, 1.0, False,
+                         torch.float32, route=route, unsupported=refusal, codes=codes)
+
+
+def qlinear_function(x: torch.Tensor, x_scale: torch.Tensor, x_zero_point: torch.Tensor | None, w: torch.Tensor, w_scale: torch.Tensor,
+                     w_zero_point: torch.Tensor | None, out_scale: torch.Tensor, out_zero_point: torch.Tensor | None, *,
+                     bias: torch.Tensor | None = None, trans_b: bool = False) -> torch.Tensor:
+    """One call of a `quant`-domain function QLinearMatMul / QLinearGemm of a ``format="qlinear"`` file (`oq_qlinear_function`,
+    csrc/qlinear_function.hip): QuantizeLinear(x, x_scale, x_zero_point) -> QLinearMatMul / QGemm against ``w`` [K, N] (``trans_b``:
+    [N, K]) -> DequantizeLinear(., out_scale, out_zero_point), fp32 ``x`` [..., K] in and fp32 [..., N] out, with the bytes of the
+    three nodes run one after the other.  ``x`` is quantized to ``x_zero_point``'s type (uint8 without one) once, into the call's
+    workspace; the product is exact in int32 (``bias``: int32 [N] at scale x_scale * w_scale); the result is quantized to
+    ``out_zero_point``'s type (uint8 without one) and dequantized in the kernel's epilogue.  Every parameter is a tensor on the
+    device, per tensor (``w_scale`` / ``w_zero_point``: per tensor or [N]).  A NaN in ``x`` quantizes to the bottom of the type.
+    Deterministic; nothing synchronises with the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out: an ``x`` that is not fp32, and what `qlinear_matmul`
+    refuses for the product."""
+    return _qlinear_function_call("qlinear_function", x, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, bias, trans_b,
+                                  _function_route, qlinear_function_unsupported)
+
+
+def qlinear_function_decode(x: torch.Tensor, x_scale: torch.Tensor, x_zero_point: torch.Tensor | None, w: torch.Tensor, w_scale: torch.Tensor,
+                            w_zero_point: torch.Tensor | None, out_scale: torch.Tensor, out_zero_point: torch.Tensor | None, *,
+                            bias: torch.Tensor | None = None, trans_b: bool = False) -> torch.Tensor:
+    """The decode route of `qlinear_function` (`oq_qlinear_function_decode`): the same operands, for an ``x`` whose ``reshape(-1, K)``
+    has 1 ... 16 rows.  The kernels of `qlinear_matmul_decode` -- ``w`` streamed once -- quantize their slice of ``x`` on the way
+    into LDS and dequantize in the epilogue: at most two launches, and the bytes of `qlinear_function`.
+
+    NotImplementedError, naming the reason: more than 16 rows, and what `qlinear_function` refuses."""
+    return _qlinear_function_call("qlinear_function_decode", x, x_scale, x_zero_point, w, w_scale, w_zero_point, out_scale, out_zero_point, bias,
+                                  trans_b, _function_decode_route, qlinear_function_decode_unsupported)
 
 
 # ----------------------------------------------------------------------------- G1 - G4
