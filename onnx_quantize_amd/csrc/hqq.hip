@@ -11,10 +11,18 @@
 // the next round's kernel applies it.  One thread = one row; neighbouring lanes = neighbouring columns, so every
 // load of W [K, N] is coalesced and no transposed copy (utils.py:24) exists.
 //
-// Parity: np.power (fp32 powf) and NumPy's pairwise fp32 means are not bit-reproducible on a GPU, so zero points
-// agree to a few ulp and an integer may move where w / s + z lands within that distance of a tie; the row means
-// use NumPy's summation tree (8 strided partial sums per <= 128 elements, halves above) to stay as close as
-// possible.  tests/test_hqq.py states the tolerances.
+// Parity, the contract the tests hold (tests/test_hqq.py states it, tests/test_hqq_exact_gpu.py and tests/hqq_cases.py test it):
+//   * lp_norm = 1: the reference's BITS -- zero points of every round, integers, blob and round count.  The exponent of the
+//     shrink's power is 0 and the factor exactly 1 on both sides (np.power(x, 0) == 1; exp2(0 * log2(.)) = exp2(+-0) == 1);
+//     every other step of a round is one correctly rounded fp32 operation (no contraction, IEEE division: div_refined is the
+//     correctly rounded quotient on its domain), and the row means follow NumPy's summation tree (8 strided partial sums per
+//     <= 128 elements, halves above, the left half a multiple of 8; divided by float(g)).  The one thing done differently is
+//     the sum behind `err < best_err` -- float64 here, fp32 pairwise in NumPy, up to 1.5e-7 relative apart -- so the bits are
+//     owed where no two errors that meet in a decision lie within 1e-5 relative of each other, unless they come from
+//     bit-identical zero points (a fixed point: equal inputs, equal errors).
+//   * any lp_norm: the integers are exact GIVEN the zero points returned, q = clip(rint(w / s + z)) with IEEE division.
+//   * lp_norm != 1: np.power (fp32 powf) is not bit-reproducible on the hardware log / exp units, so zero points agree to
+//     2e-5 absolute and an integer may move by one level where w / s + z lands within that distance of a tie.
 //
 // Element types: W is fp32, fp16 or bf16 (half_elem.hpp; oq_hqq_optimize_h16, oq_hip_half.h); the 2-byte types are read as they are and
 // converted exactly at the load, the arithmetic is the fp32 one in every instantiation.  The work split (one thread = one

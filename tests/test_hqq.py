@@ -4,16 +4,23 @@ CPU: the oracle's restatement against golden vectors produced by the reference's
 (tests/golden/make_golden.py::gen_hqq) -- bit for bit -- and the reference's configuration rules
 (test/core/test_qconfig.py:315-395).  GPU (`-m gpu`): oq_hqq_optimize_f32 against the oracle.
 
-GPU tolerances: np.power (fp32) and NumPy's pairwise fp32 means are not bit-reproducible on a GPU.  The zero
-point update is a contraction-free fixed-point iteration, so a last-bit difference stays a last-bit difference:
-zero points agree to 2e-5 absolute (values live in [0, 15]), scales are bit-equal (same RTN kernel), and an
-integer may differ only where w / scale + zero_point is within that distance of a rounding tie -- bounded
-here by 0.1 % of the elements and never by more than one level.
+The GPU contract:
+  * lp_norm = 1: the oracle's BITS -- scales, zero points, integers, blob and round count.  The shrink's power is x^0 = 1 on
+    both sides, every other step of a round is one correctly rounded fp32 operation, and the row means follow NumPy's pairwise
+    summation tree.  tests/test_hqq_exact_gpu.py holds that on every route, block edge and group size; here the golden case c4
+    (lp_norm = 1; tests/test_hqq_cases.py asserts that its trace meets the decision condition) is compared byte for byte.
+  * any lp_norm: the integers are exact GIVEN the zero points the kernel returned, q == clip(round(w / s + z_kernel)): the
+    finish kernel's arithmetic is IEEE.  A differing integer can therefore come only from a differing zero point.
+  * lp_norm != 1: np.power (fp32) is not bit-reproducible on a GPU.  The zero point update is a contraction-free
+    fixed-point iteration, so a last-bit difference stays a last-bit difference: zero points agree to 2e-5 absolute (values
+    live in [0, 15]), scales are bit-equal (same RTN kernel), and an integer may differ only where w / scale + zero_point is
+    within that distance of a rounding tie -- bounded here by 0.1 % of the elements and never by more than one level.
 """
 import numpy as np
 import pytest
 
 import oq_oracle as O
+from hqq_cases import integers_given
 from conftest import load_json, load_npz, synth_weight
 from onnx_quantize_amd import HqqConfig, QConfig, QuantizationStrategy, QuantType, QWeightArgs
 
@@ -89,8 +96,11 @@ class TestHqqConfig:
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def _check_against_oracle(w, q, s, z, eq, es, ez, label):
+def _check_against_oracle(w, q, s, z, eq, es, ez, label, group_size, reduce_range=False, exact=False):
     assert s.tobytes() == es.tobytes(), f"{label}: scales differ"
+    assert q.tobytes() == integers_given(w, s, z, group_size, reduce_range).tobytes(), f"{label}: q is not clip(round(w / s + z)) of the returned z"
+    if exact:
+        assert z.tobytes() == ez.tobytes() and q.tobytes() == eq.tobytes(), f"{label}: lp_norm = 1 owes the oracle's bits"
     assert z.shape == ez.shape and z.dtype == np.float32
     dz = np.abs(z - ez).max()
     assert dz <= 2e-5, f"{label}: zero points differ by {dz}"
@@ -108,7 +118,8 @@ def test_gpu_matches_golden(case):
     w = synth_weight(case["kind"], case["seed"], case["k"], case["n"])
     q, s, z, rounds = ops.hqq_quantize(torch.from_numpy(w).cuda(), *_args(case))
     k = case["key"]
-    _check_against_oracle(w, q.cpu().numpy(), s.cpu().numpy(), z.cpu().numpy(), GOLD[k + "_q"], GOLD[k + "_s"], GOLD[k + "_z"], k)
+    _check_against_oracle(w, q.cpu().numpy(), s.cpu().numpy(), z.cpu().numpy(), GOLD[k + "_q"], GOLD[k + "_s"], GOLD[k + "_z"], k,
+                          case["group_size"], case["reduce_range"], exact=case["lp_norm"] == 1.0)
     assert 1 <= int(rounds.item()) <= case["iters"]
 
 
@@ -135,7 +146,7 @@ def test_gpu_plugin_seam_and_medium_matrix():
     q, s, z = _hqq_quantize(w, QuantType.QUInt4, 128)
     eq, es, ez = O.hqq_quantize(w, 128)
     assert q.shape == w.shape and s.shape == z.shape == (1024 * 1536 // 128, 1) and z.dtype == s.dtype == np.float32
-    _check_against_oracle(w, q.astype(np.uint8), s, z, eq, es, ez, "1024x1536")
+    _check_against_oracle(w, q.astype(np.uint8), s, z, eq, es, ez, "1024x1536", 128)
     # the optimisation does what it is for: lower mean |W - dequant| than plain RTN (hqq.py:131)
     rq, rs, rz = O.rtn_quantize(w, "uint4", "group", 128)
     err = lambda qq, ss, zz: np.abs(O.to_rows(w, "group", 128) - (O.to_rows(qq, "group", 128).astype(np.float32) - zz) * ss).mean()  # noqa: E731

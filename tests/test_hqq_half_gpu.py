@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oq_oracle as O
+from hqq_cases import integers_given
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +125,7 @@ def test_half_weights_against_the_oracle(dtype):
     q, s, z = q.cpu().numpy(), s.cpu().numpy(), z.cpu().numpy()
     assert s.tobytes() == es.tobytes()
     assert z.shape == ez.shape and z.dtype == np.float32
+    assert q.tobytes() == integers_given(w, s, z, 64).tobytes()        # exact given the zero points the kernel returned
     assert np.abs(z - ez).max() <= 2e-5
     diff = q.astype(np.int16) - eq.astype(np.int16)
     assert np.abs(diff).max() <= 1
