@@ -40,8 +40,11 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # (tests/test_matmul_nbits_decode_resources.py finds no v_pk_fma_f32 in its assembly).
 # qdq_matmul.hip: the tile kernel of matmul_nbits.hip on a [K, N] byte matrix, the same fold: unpaired from its first compile too
 # (tests/test_qdq_matmul_resources.py).
+# matmul_nbits_fzp.hip: tile_gemm once more, with a second scalar fma in the fold (the float zero point's correction): unpaired from its
+# first compile (tests/test_matmul_nbits_fzp_resources.py).
 PER_FILE_FLAGS = {"hqq.hip": ("-fno-slp-vectorize",), "matmul_nbits.hip": ("-fno-slp-vectorize",),
-                  "matmul_nbits_decode.hip": ("-fno-slp-vectorize",), "qdq_matmul.hip": ("-fno-slp-vectorize",)}
+                  "matmul_nbits_decode.hip": ("-fno-slp-vectorize",), "qdq_matmul.hip": ("-fno-slp-vectorize",),
+                  "matmul_nbits_fzp.hip": ("-fno-slp-vectorize",)}
 
 
 def flags_for(src: str) -> list[str]:
@@ -61,7 +64,7 @@ def sources() -> list[str]:
 
 def _deps_mtime() -> float:
     hdrs = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith((".hpp", ".h"))]
-    hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h", "oq_hip_nbits_decode.h", "oq_hip_qlinear.h",
+    hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h", "oq_hip_nbits_decode.h", "oq_hip_nbits_fzp.h", "oq_hip_qlinear.h",
                                                            "oq_hip_qlinear_decode.h", "oq_hip_qlinear_function.h", "oq_hip_qdq.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 

@@ -19,22 +19,13 @@
 namespace oq {
 namespace {
 
-// 32 stored values (k ascending) minus the zero point -> 32 exact 2-byte operands
-template <typename OP, int BITS>
-__device__ __forceinline__ void dequant32(const u32x4 (&raw)[BITS / 4], float zpf, u32x4 (&out)[4]) {
-    uint32_t d[16];
-#pragma unroll
-    for (int wi = 0; wi < BITS; ++wi) dequant_word<OP, BITS>(raw[wi >> 2][wi & 3], zpf, d + wi * (16 / BITS));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) out[i] = u32x4{d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]};
-}
-
 // How B reaches LDS (tile_gemm's staging policy): thread t stages 32 values of row t >> 1 of the step, as they lie in the blob, and
 // writes them as row t >> 1 of a [128 columns][64 k] image.
 template <int BITS>
 struct BlobStage {
     typedef NbitsArgs args;
     static constexpr int kRows = kBN, kFragStride = 16;
+    static constexpr bool kFloatZp = false;
     static __device__ __forceinline__ int frag_row(int wn, int lane) { return wn * 64 + (lane & 15); }
     static __device__ __forceinline__ int64_t group(const NbitsArgs& p, int64_t k) { return k / p.g; }
     static __device__ __forceinline__ int64_t within(const NbitsArgs& p, int64_t k) { return k % p.g; }

@@ -2,7 +2,8 @@
 // W is a [K, N] byte matrix): the argument block, the one rounding of a sum to Y's type, the guarded load
 // of eight elements of A, the body of the GEMM kernel (tile_gemm), the kernel that adds the slabs of a split K, the kernel that
 // splits an fp32 A into two fp16 pieces, the plan with its workspace, and the host tail of a call.  matmul_nbits.hip's GEMM kernel
-// is tile_gemm with the file's staging policy: how B reaches LDS and where a fragment finds it there, and nothing else.
+// is tile_gemm with the file's staging policy: how B reaches LDS and where a fragment finds it there, and nothing else; so is
+// matmul_nbits_fzp.hip's (float zero points), whose policy also switches on the row sums of A and their correction.
 // qdq_matmul.hip's is a written-out copy of the same body with its staging in place: built on tile_gemm, its fp32-A kernel of the
 // 128-row tile measured 0.4 - 3 % slower at M = 2048, twice (docs/LAB_NOTES_r30.md).  A fix to the body is made in both.
 //
@@ -74,15 +75,33 @@ __device__ __forceinline__ u32x4 load_a8(const uint16_t* row, int64_t k, int64_t
     return u32x4{w[0], w[1], w[2], w[3]};
 }
 
-// ---- the GEMM.  Stage, a file's staging policy (today there is one, BlobStage<BITS> of matmul_nbits.hip), holds what one thread has
-// loaded of the next k-step of B:
-//   args                        the kernel's argument block, an NbitsArgs
+// 32 stored values (k ascending) minus the zero point -> 32 exact 2-byte operands
+template <typename OP, int BITS>
+__device__ __forceinline__ void dequant32(const u32x4 (&raw)[BITS / 4], float zpf, u32x4 (&out)[4]) {
+    uint32_t d[16];
+#pragma unroll
+    for (int wi = 0; wi < BITS; ++wi) dequant_word<OP, BITS>(raw[wi >> 2][wi & 3], zpf, d + wi * (16 / BITS));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) out[i] = u32x4{d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]};
+}
+
+// ---- the GEMM.  Stage, a file's staging policy (BlobStage<BITS> of matmul_nbits.hip, FzpStage<BITS> of matmul_nbits_fzp.hip), holds
+// what one thread has loaded of the next k-step of B:
+//   args                        the kernel's argument block, an NbitsArgs or a struct derived from it
 //   kRows, kFragStride          rows of the policy's LDS image of B; rows between a lane's fragments nt and nt + 1
 //   frag_row(wn, lane)          the image row of the lane's fragment nt = 0 in column half wn
 //   group(p, k), within(p, k)   the k-group of a k and k's place inside it
 //   Stage(p, tid, n0)           which part of the 64 x 128 step of B this thread stages
 //   load(p, k, k_begin, k_end)  global memory -> registers, for the step at k of the block's range [k_begin, k_end)
 //   store<OP>(p, lds_b)         registers -> (q - zp) as 2-byte operands in the image
+//   kFloatZp                    the zero points are floating point (matmul_nbits_fzp.hip): the operand is q - zi,
+//                               zi = rint(zp) clamped, and a group's sum loses f * rowsum(A), f = zp - zi.  The row sums rs come from
+//                               one more MFMA per fragment of A, against a fragment of ones: they land in exactly the rows a lane's
+//                               accumulators hold.  Every line of it is under `if constexpr`: with kFloatZp false the body compiles
+//                               to the text it had without it (scripts/compare_kernel_asm.py).
+//   group_terms(s, wn, lane,    kFloatZp: the f and the scales of the lane's four columns, for the group of MFMA depth s of the stored
+//               f, sc)          step.  The policy stages the scale with the zero point and hands both over through LDS, so the body
+//                               loads no scales of its own: four registers, and their addresses, that the row sums need
 template <int OUT, int MT, typename Stage>
 __device__ __forceinline__ void tile_gemm(const typename Stage::args& p) {
     typedef std::conditional_t<OUT == OQ_NBITS_BF16, OpBF16, OpF16> OP;
@@ -129,6 +148,12 @@ __device__ __forceinline__ void tile_gemm(const typename Stage::args& p) {
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) sum[mt][nt] = acc[mt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 rs[Stage::kFloatZp ? MT : 1];      // kFloatZp: the sums of A's rows over the k that acc has seen
+    const frag ones = __builtin_bit_cast(frag, u32x4{OP::kOnes, OP::kOnes, OP::kOnes, OP::kOnes});
+    if constexpr (Stage::kFloatZp) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) rs[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
 
     const int64_t col = n0 + wn * 64 + (lane & 15);          // + 16 nt: the output column of this lane in tile nt
     auto load_scales = [&](int64_t kb, float (&sc)[NT]) {
@@ -141,7 +166,8 @@ __device__ __forceinline__ void tile_gemm(const typename Stage::args& p) {
     };
     float sc[NT];
     int64_t in_group = Stage::within(p, k_begin);      // k of the next MFMA depth inside its group
-    if (k_begin < k_end) load_scales(Stage::group(p, k_begin), sc);
+    if constexpr (!Stage::kFloatZp)
+        if (k_begin < k_end) load_scales(Stage::group(p, k_begin), sc);
 
     const unsigned char* const a_frag = lds + (wm * 16 * MT + (lane & 15)) * kRow + (lane >> 4) * 16;
     const unsigned char* const b_frag = lds_b + Stage::frag_row(wn, lane) * kRow + (lane >> 4) * 16;
@@ -163,6 +189,7 @@ __device__ __forceinline__ void tile_gemm(const typename Stage::args& p) {
                     const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + mt * 16 * kRow + s * 64));
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = OP::mma(a, b[nt], acc[mt][nt]);
+                    if constexpr (Stage::kFloatZp) rs[mt] = OP::mma(a, ones, rs[mt]);
                 }
                 if constexpr (PIECES == 2) {
 #pragma unroll
@@ -172,12 +199,25 @@ __device__ __forceinline__ void tile_gemm(const typename Stage::args& p) {
                         const frag a = __builtin_bit_cast(frag, *reinterpret_cast<const u32x4*>(a_frag + (BM + mt * 16) * kRow + s * 64));
 #pragma unroll
                         for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = OP::mma(a, b[nt], acc[mt][nt]);
+                        if constexpr (Stage::kFloatZp) rs[mt] = OP::mma(a, ones * static_cast<_Float16>(0.00048828125f), rs[mt]);
                     }
                 }
                 in_group += 32;
                 // The fold is one scalar fma per output element: the files that hold this body are built with -fno-slp-vectorize, paired
                 // (v_pk_fma_f32) it gave wrong sums on the MI355X (docs/LAB_NOTES_r22.md).
                 if (in_group == p.g || ks + 32 >= k_end) {      // the group (or this block's part of it) is complete
+                    if constexpr (Stage::kFloatZp) {            // acc holds sum a (q - zi): what f * sum a takes away is still missing
+                        float fz[NT];
+                        Stage::group_terms(s, wn, lane, fz, sc);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) {
+#pragma unroll
+                            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) acc[mt][nt][r] = __builtin_fmaf(-fz[nt], rs[mt][r], acc[mt][nt][r]);
+                            rs[mt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                        }
+                    }
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -187,7 +227,8 @@ __device__ __forceinline__ void tile_gemm(const typename Stage::args& p) {
                             acc[mt][nt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
                         }
                     in_group = 0;
-                    if (ks + 32 < k_end) load_scales(Stage::group(p, ks + 32), sc);
+                    if constexpr (!Stage::kFloatZp)
+                        if (ks + 32 < k_end) load_scales(Stage::group(p, ks + 32), sc);
                 }
             }
         }

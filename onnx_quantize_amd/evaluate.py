@@ -54,7 +54,9 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     negative log-likelihoods run in float64 on the device, and one scalar comes back to the host per call, not per window.
 
     ``matmul_nbits`` goes to `GraphRunner` as it is: "fused+decode" sends the MatMulNBits nodes of windows of at most 16 tokens to the
-    decode kernel (`ops.matmul_nbits_decode`: HQQ files and block size 16 included).  The default stays "fused".
+    decode kernel (`ops.matmul_nbits_decode`: HQQ files and block size 16 included); "fused+float_zp" and "fused+float_zp+decode"
+    also run the nodes of an HQQ file (floating-point zero points, block sizes that are multiples of 32) from the blob at any
+    window length (`ops.matmul_nbits_float_zp`), where "fused" expands their weight per call.  The default stays "fused".
 
     ``qlinear="fused"`` runs the QLinearMatMul / QGemm nodes of a `format="qlinear"` file on the int8 matrix cores
     (`ops.qlinear_matmul`: exact int32 sums).  The default stays the expansion route: a fused output may differ from it by one

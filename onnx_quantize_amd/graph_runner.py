@@ -91,11 +91,17 @@ class GraphRunner:
         # matmul_nbits = "fused+decode": a node whose flattened A has at most 16 rows and which the decode kernel takes
         # (`ops.matmul_nbits_decode`: also float zero points -- HQQ files -- and block size 16) runs there; every other node goes as
         # under "fused".  Only this mode counts a third route, "decode".
-        if matmul_nbits not in ("torch", "fused", "fused+decode"):
-            raise ValueError(f"GraphRunner: matmul_nbits must be 'torch', 'fused' or 'fused+decode', got {matmul_nbits!r}")
+        # matmul_nbits = "fused+float_zp" / "fused+float_zp+decode": as "fused" / "fused+decode", and a node with floating-point zero
+        # points (HQQ files) and a block size that is a multiple of 32, which the decode route has not taken, runs on
+        # `ops.matmul_nbits_float_zp` instead of the expansion.  Only these modes count the route "float_zp".
+        if matmul_nbits not in _NBITS_MODES:
+            raise ValueError("GraphRunner: matmul_nbits must be 'torch', 'fused', 'fused+decode', 'fused+float_zp' or 'fused+float_zp+decode', "
+                             f"got {matmul_nbits!r}")
         self.matmul_nbits = matmul_nbits if self.device.type == "cuda" else "torch"
         self.nbits_calls = {"fused": 0, "torch": 0}      # MatMulNBits nodes run per route (a replayed graph counts its recording only)
-        if self.matmul_nbits == "fused+decode":
+        if "float_zp" in self.matmul_nbits:
+            self.nbits_calls["float_zp"] = 0
+        if self.matmul_nbits.endswith("decode"):
             self.nbits_calls["decode"] = 0
         # qlinear = "fused": a QLinearMatMul / QGemm node the library has a kernel for (`ops.qlinear_matmul`: 8-bit operands on the
         # GPU, per-tensor activation parameters, fp32 scales, a constant 2-D B, alpha = 1, no transA) runs on the int8 matrix cores
@@ -1349,11 +1355,13 @@ class GraphRunner:
         import torch
         K, N, bits, g = a["K"], a["N"], a.get("bits", 4), a["block_size"]
         blocks = (K + g - 1) // g
-        route = self._route(self.matmul_nbits, lambda decode: self._nbits_fusable(x, bits, g, decode))
+        route = self._route(_NBITS_MODES[self.matmul_nbits], lambda decode: self._nbits_fusable(x, bits, g, decode))
+        if route == "torch" and "float_zp" in self.matmul_nbits and self._nbits_fusable(x, bits, g, float_zp=True):
+            route = "float_zp"
         self.nbits_calls[route] += 1
         if route != "torch":
             from .hip import ops
-            fn = ops.matmul_nbits_decode if route == "decode" else ops.matmul_nbits
+            fn = {"decode": ops.matmul_nbits_decode, "fused": ops.matmul_nbits, "float_zp": ops.matmul_nbits_float_zp}[route]
             return fn(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g, bias=x[5] if len(x) > 5 else None)
         blob = x[1].reshape(N, blocks, -1).to(torch.uint8)
         if bits == 4:
@@ -1393,10 +1401,10 @@ class GraphRunner:
             return "fused"
         return "torch"
 
-    def _nbits_fusable(self, x, bits, g, decode: bool = False) -> bool:
-        """Whether `ops.matmul_nbits` (``decode``: `ops.matmul_nbits_decode`, which also wants at most 16 rows of A) takes this
-        MatMulNBits node: what the kernel supports, on the GPU, with B, scales and zero points constants of the model as the
-        writer stores them."""
+    def _nbits_fusable(self, x, bits, g, decode: bool = False, float_zp: bool = False) -> bool:
+        """Whether `ops.matmul_nbits` (``decode``: `ops.matmul_nbits_decode`, which also wants at most 16 rows of A; ``float_zp``:
+        `ops.matmul_nbits_float_zp`, which wants floating-point zero points) takes this MatMulNBits node: what the kernel supports,
+        on the GPU, with B, scales and zero points constants of the model as the writer stores them."""
         import torch
         from .hip import ops
         zp = x[3] if len(x) > 3 else None
@@ -1408,12 +1416,15 @@ class GraphRunner:
             rows = x[0].numel() // x[0].shape[-1] if x[0].shape[-1] else 0
             if ops.matmul_nbits_decode_unsupported(x[0].dtype, bits, g, zp, g_idx, rows=rows) is not None:
                 return False
+        elif float_zp:
+            if ops.matmul_nbits_float_zp_unsupported(x[0].dtype, bits, g, zp, g_idx) is not None:
+                return False
         elif ops.matmul_nbits_unsupported(x[0].dtype, bits, g, zp, g_idx) is not None:
             return False
         held = list(self.constants.values())
         if not all(t is None or (t.is_cuda and any(t is c for c in held)) for t in (x[1], x[2], zp)):
             return False
-        zp_types = (torch.uint8, torch.float32, x[0].dtype) if decode else (torch.uint8,)
+        zp_types = (torch.uint8, torch.float32, x[0].dtype) if decode else (torch.float32, x[0].dtype) if float_zp else (torch.uint8,)
         return (x[1].dtype == torch.uint8 and x[2].dtype in (torch.float32, x[0].dtype) and (zp is None or zp.dtype in zp_types)
                 and (bias is None or (bias.is_cuda and bias.dtype == x[0].dtype)))
 
@@ -1434,6 +1445,9 @@ class GraphRunner:
         unsupported = ops.qlinear_matmul_decode_unsupported if decode else ops.qlinear_matmul_unsupported
         return unsupported(A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias=bias, trans_b=trans_b, alpha=alpha, trans_a=trans_a) is None
 
+
+# `matmul_nbits` -> how `_route` reads it: the float-zp modes are "fused" / "fused+decode" plus a route of their own for what those leave
+_NBITS_MODES = {"torch": "torch", "fused": "fused", "fused+decode": "fused+decode", "fused+float_zp": "fused", "fused+float_zp+decode": "fused+decode"}
 
 # `qlinear` -> how a bare QLinearMatMul / QGemm node is routed (`_route`): the function modes leave it to "fused" / "fused+decode"
 _QLINEAR_NODE_MODE = {"torch": "torch", "fused": "fused", "fused+decode": "fused+decode", "function": "fused", "function+decode": "fused+decode"}

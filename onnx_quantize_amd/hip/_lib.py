@@ -36,6 +36,8 @@ OQ_NBITS_EXTENSION_VERSION = 1
 # include/oq_hip_nbits_decode.h
 OQ_NBITS_ZP_PACKED_U8 = 3
 OQ_NBITS_DECODE_EXTENSION_VERSION = 1
+# include/oq_hip_nbits_fzp.h
+OQ_NBITS_FZP_EXTENSION_VERSION = 1
 # include/oq_hip_qlinear.h
 OQ_QL_U8, OQ_QL_I8 = range(2)
 OQ_QL_KN, OQ_QL_NK = range(2)
@@ -185,6 +187,13 @@ NBITS_DECODE_PROTOTYPES = {
     "oq_matmul_nbits_decode": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _p, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _sz, _p]),
 }
 
+# the tile route of MatMulNBits for float zero points: mirrors include/oq_hip_nbits_fzp.h one to one (tests/test_matmul_nbits_fzp_abi.py checks the set)
+NBITS_FZP_PROTOTYPES = {
+    "oq_nbits_fzp_extension_version": (_i32, []),
+    "oq_matmul_nbits_fzp_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _i32]),
+    "oq_matmul_nbits_fzp": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _p, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _sz, _p]),
+}
+
 # the QLinearMatMul / QGemm extension: mirrors include/oq_hip_qlinear.h one to one (tests/test_qlinear_matmul_abi.py checks the set)
 QLINEAR_PROTOTYPES = {
     "oq_qlinear_extension_version": (_i32, []),
@@ -227,6 +236,7 @@ EXTENSIONS = [
     (HALF_PROTOTYPES, "oq_half_extension_version", OQ_HALF_EXTENSION_VERSION, "half-precision extension"),
     (NBITS_PROTOTYPES, "oq_nbits_extension_version", OQ_NBITS_EXTENSION_VERSION, "MatMulNBits extension"),
     (NBITS_DECODE_PROTOTYPES, "oq_nbits_decode_extension_version", OQ_NBITS_DECODE_EXTENSION_VERSION, "MatMulNBits decode extension"),
+    (NBITS_FZP_PROTOTYPES, "oq_nbits_fzp_extension_version", OQ_NBITS_FZP_EXTENSION_VERSION, "MatMulNBits float-zero-point extension"),
     (QLINEAR_PROTOTYPES, "oq_qlinear_extension_version", OQ_QLINEAR_EXTENSION_VERSION, "QLinearMatMul extension"),
     (QLINEAR_DECODE_PROTOTYPES, "oq_qlinear_decode_extension_version", OQ_QLINEAR_DECODE_EXTENSION_VERSION, "QLinearMatMul decode extension"),
     (QLINEAR_FUNCTION_PROTOTYPES, "oq_qlinear_function_extension_version", OQ_QLINEAR_FUNCTION_EXTENSION_VERSION, "QLinear function extension"),

@@ -1370,11 +1370,17 @@ def _nbits_decode_route(lib, key, current):
     return lib.oq_matmul_nbits_decode, need, C.c_void_p(_raw_stream(current))
 
 
+def _nbits_float_zp_route(lib, key, current):
+    """`oq_matmul_nbits_fzp` with its workspace query, asked per call, on the current stream."""
+    return lib.oq_matmul_nbits_fzp, lib.oq_matmul_nbits_fzp_workspace_bytes(*key), _stream()
+
+
 def _nbits_call(fn, x, blob, scales, zero_points, K, N, bits, block_size, bias, g_idx, route):
-    """What `matmul_nbits` and `matmul_nbits_decode` share: the checks, the operands as the C ABI wants them, the call.
-    ``route(lib, (M, K, N, block size, type code), current device)`` names the entry point, its workspace bytes and the stream.
-    The decode route also takes floating-point zero points (and says which kind they are: `zp_type`) and refuses by the rows."""
-    decode = route is _nbits_decode_route
+    """What `matmul_nbits`, `matmul_nbits_decode` and `matmul_nbits_float_zp` share: the checks, the operands as the C ABI wants
+    them, the call.  ``route(lib, (M, K, N, block size, type code), current device)`` names the entry point, its workspace bytes
+    and the stream.  The decode route also takes floating-point zero points (and says which kind they are: `zp_type`) and refuses
+    by the rows; the float-zp route takes nothing else."""
+    decode, float_zp = route is _nbits_decode_route, route is _nbits_float_zp_route
     current = None
     if decode:
         current = torch.cuda.current_device() if torch.cuda.is_available() else -1
@@ -1387,7 +1393,8 @@ def _nbits_call(fn, x, blob, scales, zero_points, K, N, bits, block_size, bias, 
 
     require(x, "x")
     K, N, bits, g = int(K), int(N), int(bits), int(block_size)
-    why = None if decode else matmul_nbits_unsupported(x.dtype, bits, g, zero_points)
+    why = None if decode else matmul_nbits_float_zp_unsupported(x.dtype, bits, g, zero_points, g_idx) if float_zp else \
+        matmul_nbits_unsupported(x.dtype, bits, g, zero_points)
     if why is None and x.shape[-1] != K:
         raise ValueError(f"{fn}: x has {x.shape[-1]} columns, the node K = {K}")
     x2 = None
@@ -1408,7 +1415,12 @@ def _nbits_call(fn, x, blob, scales, zero_points, K, N, bits, block_size, bias, 
     zp_type = (L.OQ_NBITS_ZP_PACKED_U8,) if decode else ()      # an argument of the decode entry point alone
     if zero_points is not None:
         expect = N * ((blocks + 1) // 2) if bits == 4 else N * blocks      # uint8, for 4 bits packed
-        if not decode:
+        if float_zp:      # floating point, of float32 or x's type: `matmul_nbits_float_zp_unsupported` has seen to it
+            require(zero_points, "zero_points")
+            expect, zp_type = N * blocks, (_NBITS_TYPE[zero_points.dtype],)
+            if zero_points.numel() != expect:
+                raise ValueError(f"{fn}: {expect} zero points ({zero_points.dtype}) are expected, got {zero_points.numel()}")
+        elif not decode:
             require(zero_points, "zero_points", torch.uint8)
             if zero_points.numel() != expect:
                 raise ValueError(f"{fn}: {expect} zero-point bytes are expected, got {zero_points.numel()}")
@@ -1449,6 +1461,38 @@ def matmul_nbits_decode(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tenso
     NotImplementedError, naming the reason, for what the kernel leaves out: more than 16 rows, block sizes that are no multiple
     of 16, bits other than 4 / 8, and a node that carries ``g_idx``."""
     return _nbits_call("matmul_nbits_decode", x, blob, scales, zero_points, K, N, bits, block_size, bias, g_idx, _nbits_decode_route)
+
+
+def matmul_nbits_float_zp_unsupported(x_dtype, bits: int, block_size: int, zero_points, g_idx=None) -> str | None:
+    """Why `matmul_nbits_float_zp` has no kernel for such a node (include/oq_hip_nbits_fzp.h, "left out"), or None when it has
+    one."""
+    if x_dtype not in _NBITS_TYPE:
+        return f"an input of {x_dtype} (fp32, fp16 and bf16 have a kernel)"
+    if bits not in (4, 8):
+        return f"bits = {bits} (4 and 8 have a kernel)"
+    if block_size <= 0 or block_size % 32:
+        return f"block_size = {block_size} is no multiple of 32 (two groups would share one 32-deep matrix instruction)"
+    if zero_points is None or not zero_points.is_floating_point():
+        return "integer zero points (matmul_nbits is their route)"
+    if zero_points.dtype not in (torch.float32, x_dtype):
+        return f"zero points of {zero_points.dtype} (float32 and the input's type have a kernel)"
+    if g_idx is not None:
+        return "g_idx"
+    return None
+
+
+def matmul_nbits_float_zp(x: torch.Tensor, blob: torch.Tensor, scales: torch.Tensor, zero_points: torch.Tensor, *, K: int, N: int,
+                          bits: int, block_size: int, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """com.microsoft::MatMulNBits with floating-point zero points (HQQ files), any number of rows, from the packed blob as stored
+    (`oq_matmul_nbits_fzp`, csrc/matmul_nbits_fzp.hip): the operands and shape conventions of `matmul_nbits`, with
+    ``zero_points`` [N, blocks] of float32 or x's type.  Every zero point is split into zi = clamp(rint(zp), 0, 2^bits - 1) and
+    f = zp - zi: (q - zi) meets x on the matrix cores as an exact integer operand, and a group's sum loses f times the sum of
+    x's row over the group, taken by the same instructions.  No [N, K] weight exists at any point; nothing synchronises with
+    the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out: integer zero points (`matmul_nbits` is their
+    route), block sizes that are no multiple of 32, bits other than 4 / 8."""
+    return _nbits_call("matmul_nbits_float_zp", x, blob, scales, zero_points, K, N, bits, block_size, bias, None, _nbits_float_zp_route)
 
 
 # ----------------------------------------------------------------------------- QLinearMatMul / QGemm / MatMulInteger on the int8 matrix cores
