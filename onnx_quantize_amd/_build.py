@@ -65,7 +65,7 @@ def sources() -> list[str]:
 def _deps_mtime() -> float:
     hdrs = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith((".hpp", ".h"))]
     hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h", "oq_hip_nbits_decode.h", "oq_hip_nbits_fzp.h", "oq_hip_qlinear.h",
-                                                           "oq_hip_qlinear_decode.h", "oq_hip_qlinear_function.h", "oq_hip_qdq.h"))
+                                                           "oq_hip_qlinear_decode.h", "oq_hip_qlinear_function.h", "oq_hip_qdq.h", "oq_hip_qdq_function.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -92,6 +92,86 @@ __device__ __forceinline__ void finish(const P& p, uint32_t m, uint32_t n, uint3
     finish_acc<DQ>(p, m, n, static_cast<int32_t>(S - c.zb * rs + c.add), c.scale);
 }
 
+// What the tile bodies (qlinear_tile.hpp) end in: the 8-bit q, its dequantized value (the DQ of finish_acc), or the epilogue of a QDQ
+// function with quantized activations (include/oq_hip_qdq_function.h).
+enum : int { kEpQuantized = 0, kEpDequantized = 1, kEpQdqFunction = 2 };
+// the modes of an activation, as oq_qdq_mode numbers them (the header is not included here: it would pull the whole QDQ vocabulary in)
+enum : int { kQdqNone = 0, kQdqStatic = 1, kQdqDynamic = 2 };
+
+// a running (min, max) that propagates NaN; the identity of both folds
+struct MinMax {
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+};
+
+// DynamicQuantizeLinear's parameters from the (min, max) of a tensor, and its element function (include/oq_hip_qdq_function.h)
+struct DynParams {
+    float safe, scale, zp;
+};
+__device__ __forceinline__ DynParams dyn_params(const MinMax& t) {
+    const float lo = nmin(t.lo, 0.0f), hi = nmax(t.hi, 0.0f);
+    DynParams d;
+    d.scale = (hi - lo) / 255.0f;
+    d.safe = d.scale == 0.0f ? 1.0f : d.scale;
+    d.zp = rintf(fminf(fmaxf(-lo / d.safe, 0.0f), 255.0f));
+    return d;
+}
+__device__ __forceinline__ float dyn_qdq(float t, const DynParams& d) {
+    const float q = fminf(fmaxf(rintf(t / d.safe) + d.zp, 0.0f), 255.0f);
+    return (q - d.zp) * d.scale;
+}
+
+// the dequantized bias of a Gemm for column n (0 for a MatMul).  `P` also names bias, bias_scale, bias_zp.
+template <class P>
+__device__ __forceinline__ float qdq_bias(const P& p, uint32_t n) {
+    if (!p.bias) return 0.0f;
+    return (static_cast<float>(p.bias[n]) - static_cast<float>(p.bias_zp ? p.bias_zp[0] : 0)) * p.bias_scale[0];
+}
+
+// S -> v -> Y for kEpQdqFunction.  `P` also names out_mode and out_signed; y_scale / y_zp are the static output parameters.  A
+// dynamic output takes v as it is and folds it into `mm`: the finishing launch rewrites Y.
+template <class P>
+__device__ __forceinline__ void finish_qdq(const P& p, uint32_t m, uint32_t n, uint32_t S, const ColTerms& c, float bias, MinMax& mm) {
+    const uint32_t rs = p.rowsum ? static_cast<uint32_t>(p.rowsum[m]) : 0u;
+    float v = static_cast<float>(static_cast<int32_t>(S - c.zb * rs + c.add)) * c.scale;
+    if (p.bias) v = v + bias;
+    float* const y = static_cast<float*>(p.Y) + static_cast<int64_t>(m) * p.ldy + n;
+    if (p.out_mode == kQdqStatic && v == v) {      // a NaN (a dynamic input that holds one) passes
+        const float zp = static_cast<float>(read_zp(p.y_zp, p.out_signed, 0));
+        const float q = fminf(fmaxf(rintf(v / p.y_scale[0]) + zp, p.out_signed ? -128.0f : 0.0f), p.out_signed ? 127.0f : 255.0f);
+        v = (q - zp) * p.y_scale[0];
+    }
+    if (p.out_mode == kQdqDynamic) mm.lo = nmin(mm.lo, v), mm.hi = nmax(mm.hi, v);
+    *y = v;
+}
+
+// the fold of a wave's MinMax: every lane gets the result (min and max are exact in any order)
+__device__ __forceinline__ MinMax wave_minmax(MinMax mm) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mm.lo = nmin(mm.lo, __shfl_xor(mm.lo, off, kWave));
+        mm.hi = nmax(mm.hi, __shfl_xor(mm.hi, off, kWave));
+    }
+    return mm;
+}
+
+// the fold of a workgroup's MinMax, which every thread of it calls: every thread gets the result.  `red`: 2 floats per wave of LDS
+// that nobody reads any more.
+__device__ __forceinline__ MinMax block_minmax(MinMax mm, float* red) {
+    mm = wave_minmax(mm);
+    if ((threadIdx.x & 63) == 0) red[2 * (threadIdx.x >> 6)] = mm.lo, red[2 * (threadIdx.x >> 6) + 1] = mm.hi;
+    __syncthreads();
+    MinMax all;
+    for (unsigned w = 0; w < blockDim.x / kWave; ++w) all.lo = nmin(all.lo, red[2 * w]), all.hi = nmax(all.hi, red[2 * w + 1]);
+    return all;
+}
+
+// ... and into pairs[2 * block], pairs[2 * block + 1], as one 8-byte store
+__device__ __forceinline__ void block_minmax_store(const MinMax& mm, float* red, float* pairs, uint32_t block) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const MinMax all = block_minmax(mm, red);
+    if (threadIdx.x == 0) *reinterpret_cast<f32x2*>(pairs + 2 * static_cast<int64_t>(block)) = f32x2{all.lo, all.hi};
+}
+
 // QuantizeLinear of an fp32 operand to an 8-bit type, per tensor (include/oq_hip_qlinear_function.h): what one element needs.
 struct QuantParams {
     float scale, zp, lo, hi;

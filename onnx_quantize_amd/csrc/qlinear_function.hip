@@ -51,10 +51,10 @@ __global__ __launch_bounds__(kThreads) void qf_quantize_rows_kernel(const QlArgs
 template <int MT, int LAYOUT>
 __global__ __launch_bounds__(kThreads, 2) void qf_gemm_kernel(const QlArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[ql_gemm_lds_bytes(MT)];
-    ql_gemm_body<MT, LAYOUT, true>(p, lds);
+    ql_gemm_body<MT, LAYOUT, kEpDequantized>(p, lds);
 }
 
-__global__ __launch_bounds__(kThreads) void qf_reduce_kernel(const QlArgs p, const int splits) { ql_reduce_body<true>(p, splits); }
+__global__ __launch_bounds__(kThreads) void qf_reduce_kernel(const QlArgs p, const int splits) { ql_reduce_body<kEpDequantized>(p, splits); }
 
 __global__ __launch_bounds__(kThreads) void qf_sum_rows_kernel(const uint8_t* X, int64_t rows, int64_t K, int64_t ld, uint32_t ubias, int32_t vec,
                                                                int32_t* sums) {

@@ -1,13 +1,16 @@
 // The tile route of the 8-bit products as bodies, for qlinear_function.hip (include/oq_hip_qlinear_function.h): the text of the kernels
 // of qlinear_gemm.hip, each as a __device__ __forceinline__ function that a kernel wraps (the kernel declares the LDS and calls the
-// body), with one flag:
-//   DQ   the epilogue ends in Y = (fp32(q) - fp32(y_zp)) * y_scale as fp32 instead of the 8-bit q (finish_acc).
+// body), with one policy, EP (qlinear_epilogue.hpp):
+//   kEpQuantized     the epilogue of qlinear_gemm.hip (finish_acc);
+//   kEpDequantized   it ends in Y = (fp32(q) - fp32(y_zp)) * y_scale as fp32 instead of the 8-bit q (finish_acc<DQ>);
+//   kEpQdqFunction   the epilogue of a QDQ function with quantized activations (finish_qdq; qdq_function.hip): the bias dequantized
+//                    per column, the output Q -> DQ, and for a dynamic output one (min, max) of the workgroup's valid elements.
 // qlinear_gemm.hip keeps its own text and does NOT include this file: wrapped around these bodies with the flag off, six of its seven
 // kernels -- the twenty lines of ql_sum_rows_kernel included -- compile to another order of instructions and other register numbers
 // (docs/LAB_NOTES_r32.md, section 1), and scripts/compare_kernel_asm.py holds that file to its text.  So the argument struct, the
 // bodies and the workspace layout below are a copy, as qdq_matmul.hip's kernel is one of matmul_nbits.hip's; the guarded loads, the
-// correction terms and the epilogue (qlinear_epilogue.hpp) and the plan (tile_plan.hpp) are the one shared text.  The flag stays a
-// template argument although this file's one user sets it: it marks the only places where the copy departs from the original.
+// correction terms and the epilogue (qlinear_epilogue.hpp) and the plan (tile_plan.hpp) are the one shared text.  The policy marks
+// the only places where the copy departs from the original.
 // What the tile is and how it is staged: qlinear_gemm.hip.
 #pragma once
 
@@ -55,7 +58,7 @@ struct QlArgs {
 constexpr int ql_gemm_lds_bytes(int mt) { return (32 * mt + kBN) * kRow; }
 
 // `lds`: ql_gemm_lds_bytes(MT) bytes, 16-byte aligned, declared by the kernel
-template <int MT, int LAYOUT, bool DQ, class P>
+template <int MT, int LAYOUT, int EP, class P>
 __device__ __forceinline__ void ql_gemm_body(const P& p, unsigned char* const lds) {
     constexpr int BM = 32 * MT;
     constexpr int NT = 4;
@@ -180,12 +183,16 @@ __device__ __forceinline__ void ql_gemm_body(const P& p, unsigned char* const ld
 
     // C/D map of the 16x16 MFMAs: column = lane & 15, row = 4 (lane >> 4) + r
     const uint32_t col = n0 + wn * 64 + (lane & 15);
+    [[maybe_unused]] MinMax mm;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const uint32_t n = col + 16 * nt;
         if (n >= p.N) continue;
         ColTerms c{};
         if (!p.slab) c = col_terms(p, n);
+        [[maybe_unused]] float bias = 0.0f;
+        if constexpr (EP == kEpQdqFunction)
+            if (!p.slab) bias = qdq_bias(p, n);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -194,22 +201,37 @@ __device__ __forceinline__ void ql_gemm_body(const P& p, unsigned char* const ld
                 if (m < p.M) {
                     const uint32_t S = static_cast<uint32_t>(acc[mt][nt][r]);
                     if (p.slab) p.slab[(static_cast<int64_t>(blockIdx.y) * p.M + m) * p.N + n] = S;
-                    else finish<DQ>(p, m, n, S, c);
+                    else if constexpr (EP == kEpQdqFunction) finish_qdq(p, m, n, S, c, bias, mm);
+                    else finish<EP == kEpDequantized>(p, m, n, S, c);
                 }
             }
     }
+    if constexpr (EP == kEpQdqFunction)      // the k loop's last barrier is behind every read of the tiles: LDS is free
+        if (!p.slab && p.out_mode == kQdqDynamic) block_minmax_store(mm, reinterpret_cast<float*>(lds), p.pairs, blockIdx.x);
 }
 
 // the slabs of a split K, added (uint32: any order gives the same bits), corrected and finished
-template <bool DQ, class P>
-__device__ __forceinline__ void ql_reduce_body(const P& p, const int splits) {
+// `red` (kEpQdqFunction only): 2 floats per wave of LDS, declared by the kernel
+template <int EP, class P>
+__device__ __forceinline__ void ql_reduce_body(const P& p, const int splits, [[maybe_unused]] float* red = nullptr) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
     const int64_t count = static_cast<int64_t>(p.M) * p.N;
-    if (i >= count) return;
-    uint32_t S = p.slab[i];
-    for (int s = 1; s < splits; ++s) S += p.slab[s * count + i];
-    const uint32_t n = static_cast<uint32_t>(i % p.N);
-    finish<DQ>(p, static_cast<uint32_t>(i / p.N), n, S, col_terms(p, n));
+    if constexpr (EP == kEpQdqFunction) {      // every thread reaches the workgroup's fold
+        MinMax mm;
+        if (i < count) {
+            uint32_t S = p.slab[i];
+            for (int s = 1; s < splits; ++s) S += p.slab[s * count + i];
+            const uint32_t n = static_cast<uint32_t>(i % p.N);
+            finish_qdq(p, static_cast<uint32_t>(i / p.N), n, S, col_terms(p, n), qdq_bias(p, n), mm);
+        }
+        if (p.out_mode == kQdqDynamic) block_minmax_store(mm, red, p.pairs, blockIdx.x);
+    } else {
+        if (i >= count) return;
+        uint32_t S = p.slab[i];
+        for (int s = 1; s < splits; ++s) S += p.slab[s * count + i];
+        const uint32_t n = static_cast<uint32_t>(i % p.N);
+        finish<EP == kEpDequantized>(p, static_cast<uint32_t>(i / p.N), n, S, col_terms(p, n));
+    }
 }
 
 __device__ __forceinline__ int64_t ceil_div_dev(int64_t a, int64_t b) { return (a + b - 1) / b; }

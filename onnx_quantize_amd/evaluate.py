@@ -69,7 +69,9 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
 
     ``qdq="fused"`` runs the product of every `quant`-domain QDQ function call -- the default output format -- from the stored
     integers (`ops.qdq_matmul`: no fp32 copy of the weight is made per call).  The default stays the function body: the fused sum
-    differs from torch's fp32 GEMM on the dequantized weight in its last bits."""
+    differs from torch's fp32 GEMM on the dequantized weight in its last bits.  ``qdq="fused+integer"`` also runs every call of a QDQ
+    function with an input Q -> DQ (static or dynamic activations) as one library call on the int8 matrix cores (`ops.qdq_function`:
+    an exact int32 sum where the other routes accumulate the dequantized activations in fp32)."""
     import torch
 
     from .graph_runner import GraphRunner

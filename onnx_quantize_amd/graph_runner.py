@@ -130,10 +130,18 @@ class GraphRunner:
         # `build_function` writes runs its product from the stored integers (`ops.qdq_matmul`: W [K, N] bytes, its scales and zero
         # points as the file holds them; no fp32 weight is made).  The body's own operators around the product -- Q -> DQ of the
         # input, of the output, DQ of the bias -- run as they are.  Every other call, and every call under "torch", walks the body.
-        if qdq not in ("torch", "fused"):
-            raise ValueError(f"GraphRunner: qdq must be 'torch' or 'fused', got {qdq!r}")
+        # qdq = "fused+integer": as "fused", and a call of a QDQ function with an input Q -> DQ (static or dynamic; with or without an
+        # output Q -> DQ) whose body is the one `build_function` writes runs as ONE library call (`ops.qdq_function`: fp32 in, fp32
+        # out, the product of the 8-bit activations and the stored W as an exact int32 sum on the int8 matrix cores), when W, its
+        # parameters, the static activation parameters and the bias triple are constants of the model on the GPU and X is a
+        # non-empty fp32 tensor there.  Such calls are counted in `qdq_function_calls`: "integer", or "body" where a condition fails
+        # and the body is walked node by node.  Every other QDQ function goes, and is counted, as under "fused".
+        if qdq not in ("torch", "fused", "fused+integer"):
+            raise ValueError(f"GraphRunner: qdq must be 'torch', 'fused' or 'fused+integer', got {qdq!r}")
         self.qdq = qdq if self.device.type == "cuda" else "torch"
         self.qdq_calls = {"fused": 0, "torch": 0}        # calls of QDQ functions per route (counted like nbits_calls)
+        self.qdq_function_calls = {"integer": 0, "body": 0}      # under "fused+integer": calls of the functions with an input Q -> DQ
+        self._qdq_bias: dict = {}                        # id(constant B or b_zero_point) -> (the constant, its int32 copy)
         self._qdq_plans: dict = {}                       # id(function) -> (the function, _QdqPlan | None)
         self.functions = {(f.domain or "", f.name, f.overload or ""): f for f in model.functions}
         self.opset = max([int(o.version or 1) for o in model.opset_import if not o.domain] or [1])
@@ -173,6 +181,7 @@ class GraphRunner:
         self.qlinear, self._qlinear_node, self.qlinear_calls = "torch", "torch", {"fused": 0, "torch": 0}
         self.qlinear_function_calls, self._qlinear_functions = {"function": 0, "body": 0}, {}
         self.qdq, self.qdq_calls, self._qdq_plans = "torch", {"fused": 0, "torch": 0}, {}
+        self.qdq_function_calls, self._qdq_bias = {"integer": 0, "body": 0}, {}
         return self
 
     def evaluate(self, node, arrays) -> list:
@@ -378,8 +387,13 @@ class GraphRunner:
             env[name] = value
         for name in list(fn.input)[len(ins):]:
             env[name] = None
-        if _QdqPlan.named(fn):                 # counted per call, whatever route it takes
-            plan = self._qdq_plan(fn) if self.qdq == "fused" else None
+        if self.qdq == "fused+integer" and _QdqPlan.input_mode(fn) is not None:      # counted per call, in a dict of their own
+            out = self._run_qdq_function(fn, env)
+            self.qdq_function_calls["body" if out is None else "integer"] += 1
+            if out is not None:
+                return (out,)
+        elif _QdqPlan.named(fn):               # counted per call, whatever route it takes
+            plan = self._qdq_plan(fn) if self.qdq in ("fused", "fused+integer") else None
             outs = self._run_qdq_fused(fn, plan, dict(env)) if plan is not None else None
             self.qdq_calls["torch" if outs is None else "fused"] += 1
             if outs is not None:
@@ -426,6 +440,47 @@ class GraphRunner:
         hit = self._qdq_plans.get(id(fn))
         if hit is None or hit[0] is not fn:
             hit = self._qdq_plans[id(fn)] = (fn, _QdqPlan.of(fn))
+        return hit[1]
+
+    def _run_qdq_function(self, fn, env):
+        """One call of a QDQ function with an input Q -> DQ as one library call (`ops.qdq_function`): the function's output, or None --
+        nothing was run -- where the body is not the one `onnx_functions.build_function` writes, W, a parameter or a member of the
+        bias triple is no constant of the model on the GPU, X is no fp32 tensor on the GPU with elements, or the kernel has no route
+        for the call: the body then runs node by node."""
+        import torch
+        from .hip import ops
+        from .onnx_functions import _QDQ
+        if self._qdq_plan(fn) is None:
+            return None
+        x = env["X"]
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim >= 1 and x.numel() > 0):
+            return None
+        op, (x_mode, out_mode) = _QDQ[fn.name]
+        names = ["W", "w_scale", "w_zero_point"] + (["B", "b_scale", "b_zero_point"] if op == "Gemm" else []) + \
+            (["x_scale", "x_zero_point"] if x_mode == "static" else []) + (["out_scale", "out_zero_point"] if out_mode == "static" else [])
+        held = list(self.constants.values())
+        if not all(env[n] is None or (isinstance(env[n], torch.Tensor) and env[n].is_cuda and any(env[n] is c for c in held)) for n in names):
+            return None
+        if env["W"] is None or env["w_scale"] is None or (op == "Gemm" and env["B"] is None):
+            return None
+        args = dict(x_mode=x_mode, x_scale=env.get("x_scale") if x_mode == "static" else None,
+                    x_zero_point=env.get("x_zero_point") if x_mode == "static" else None, out_mode=out_mode,
+                    out_scale=env.get("out_scale") if out_mode == "static" else None,
+                    out_zero_point=env.get("out_zero_point") if out_mode == "static" else None,
+                    bias=(self._as_int32(env["B"]), env["b_scale"], self._as_int32(env["b_zero_point"])) if op == "Gemm" else None)
+        if ops.qdq_function_unsupported(x, env["W"], env["w_scale"], env["w_zero_point"], **args) is not None:
+            return None
+        return ops.qdq_function(x, env["W"], env["w_scale"], env["w_zero_point"], **args)
+
+    def _as_int32(self, t):
+        """A constant of the bias triple as the library call takes it.  The writer stores B and its zero point in the weight's 8-bit
+        type; the same integers as int32, made once per constant."""
+        import torch
+        if t is None or t.dtype == torch.int32 or t.dtype not in (torch.int8, torch.uint8):
+            return t
+        hit = self._qdq_bias.get(id(t))
+        if hit is None or hit[0] is not t:
+            hit = self._qdq_bias[id(t)] = (t, t.to(torch.int32))
         return hit[1]
 
     def _run_qdq_fused(self, fn, plan, env):
@@ -1486,6 +1541,12 @@ class _QdqPlan:
         """`fn` carries the name of a QDQ function of the `quant` domain."""
         from .onnx_functions import _QDQ, QUANT_DOMAIN
         return (fn.domain or "") == QUANT_DOMAIN and (fn.name in _QDQ or fn.name in ("QMatMulWeightsOnlyGrouped", "QGemmWeightsOnlyGrouped"))
+
+    @classmethod
+    def input_mode(cls, fn):
+        """`fn` carries the name of a QDQ function with an input Q -> DQ: "static" / "dynamic", else None."""
+        from .onnx_functions import _QDQ, QUANT_DOMAIN
+        return _QDQ[fn.name][1][0] if (fn.domain or "") == QUANT_DOMAIN and fn.name in _QDQ else None
 
     @classmethod
     def of(cls, fn):

@@ -50,6 +50,9 @@ OQ_QLINEAR_DECODE_EXTENSION_VERSION = 1
 OQ_QLINEAR_FUNCTION_EXTENSION_VERSION = 1
 # include/oq_hip_qdq.h (its type codes are OQ_NBITS_*, OQ_UINT8 / OQ_INT8 and OQ_TENSOR / OQ_CHANNEL / OQ_GROUP above)
 OQ_QDQ_EXTENSION_VERSION = 1
+# include/oq_hip_qdq_function.h (its codes: oq_qdq_mode below, OQ_NBITS_* for X, OQ_UINT8 / OQ_INT8 and OQ_TENSOR / OQ_CHANNEL for W, OQ_QL_U8 / _I8)
+OQ_QDQ_NONE, OQ_QDQ_STATIC, OQ_QDQ_DYNAMIC = range(3)
+OQ_QDQ_FUNCTION_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -229,6 +232,15 @@ QDQ_PROTOTYPES = {
     "oq_qdq_matmul": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i64, _p, _i32, _p, _p, _p, _i64, _p, _sz, _p]),
 }
 
+# a call of a QDQ function with quantized activations, fp32 in and out: mirrors include/oq_hip_qdq_function.h one to one
+# (tests/test_qdq_function_abi.py checks the set)
+QDQ_FUNCTION_PROTOTYPES = {
+    "oq_qdq_function_extension_version": (_i32, []),
+    "oq_qdq_function_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32]),
+    "oq_qdq_function": (_i32, [_p, _i32, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _i32, _i64, _i64, _i32, _i64, _p, _p, _p, _p, _p, _i32, _i32, _p, _p,
+                               _p, _i64, _p, _sz, _p]),
+}
+
 # what `load` binds and pins: (prototypes, the function that reports the version, the version this package expects, what the
 # message calls it)
 EXTENSIONS = [
@@ -241,6 +253,7 @@ EXTENSIONS = [
     (QLINEAR_DECODE_PROTOTYPES, "oq_qlinear_decode_extension_version", OQ_QLINEAR_DECODE_EXTENSION_VERSION, "QLinearMatMul decode extension"),
     (QLINEAR_FUNCTION_PROTOTYPES, "oq_qlinear_function_extension_version", OQ_QLINEAR_FUNCTION_EXTENSION_VERSION, "QLinear function extension"),
     (QDQ_PROTOTYPES, "oq_qdq_extension_version", OQ_QDQ_EXTENSION_VERSION, "QDQ matmul extension"),
+    (QDQ_FUNCTION_PROTOTYPES, "oq_qdq_function_extension_version", OQ_QDQ_FUNCTION_EXTENSION_VERSION, "QDQ function extension"),
 ]
 
 _lock = threading.Lock()

@@ -1770,6 +1770,99 @@ def qlinear_function_decode(x: torch.Tensor, x_scale: torch.Tensor, x_zero_point
                                   trans_b, _function_decode_route, qlinear_function_decode_unsupported)
 
 
+# ----------------------------------------------------------------------------- a QDQ function with quantized activations in one call
+QDQ_FUNCTION_MAX_K = 33025      # include/oq_hip_qdq_function.h, `bounds`: 255 * 255 * K stays an int32
+_QDQ_MODE = {"static": L.OQ_QDQ_STATIC, "dynamic": L.OQ_QDQ_DYNAMIC, None: L.OQ_QDQ_NONE}
+
+
+def qdq_function_unsupported(x, w, w_scale, w_zero_point=None, *, x_mode, x_scale=None, x_zero_point=None, out_mode=None, out_scale=None,
+                             out_zero_point=None, bias=None) -> str | None:
+    """Why `qdq_function` has no kernel for such a call (include/oq_hip_qdq_function.h, "left out"), or None when it has one.
+    Element types, shapes and the refusals of the entry point; where the tensors live is the caller's question."""
+    if x_mode not in ("static", "dynamic"):
+        return f"x_mode = {x_mode!r} ('static' and 'dynamic' have a kernel; a function without an input Q -> DQ keeps qdq_matmul)"
+    if out_mode not in (None, "static", "dynamic"):
+        return f"out_mode = {out_mode!r} (None, 'static' and 'dynamic' have a kernel)"
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        return f"an x of {getattr(x, 'dtype', type(x).__name__)} (fp32 has a kernel)"
+    if w.dtype not in _QDQ_WTYPE or w.ndim != 2:
+        return f"a weight of {w.dtype} and {w.ndim} axes (a uint8 / int8 [K, N] matrix has a kernel)"
+    k, n = int(w.shape[0]), int(w.shape[1])
+    if x.ndim < 1 or x.shape[-1] != k:
+        return f"an input whose last axis is not K = {k}"
+    if k > QDQ_FUNCTION_MAX_K:
+        return f"K = {k} (beyond {QDQ_FUNCTION_MAX_K} an int32 sum of 8-bit products could wrap)"
+    if w_scale is None:
+        return "a missing w_scale"
+    if w_scale.dtype != torch.float32 or w_scale.numel() not in (1, n):
+        return f"a w_scale of {w_scale.numel()} x {w_scale.dtype} (1 or N fp32 values: a grouped W keeps qdq_matmul)"
+    if w_zero_point is not None and (w_zero_point.dtype != w.dtype or w_zero_point.numel() not in (1, n)):
+        return f"a w_zero_point of {w_zero_point.numel()} x {w_zero_point.dtype} for a weight of {w.dtype}"
+    for mode, scale, zp, name in ((x_mode, x_scale, x_zero_point, "x"), (out_mode, out_scale, out_zero_point, "out")):
+        if mode != "static":
+            continue
+        if scale is None or scale.dtype != torch.float32 or scale.numel() != 1:
+            return f"a static {name}_scale that is not one fp32 value"
+        if zp is not None and (zp.dtype not in _QL_TYPE or zp.numel() != 1):
+            return f"a static {name}_zero_point of {zp.numel()} x {zp.dtype} (one uint8 or int8 value has a kernel)"
+    if bias is not None:
+        b, b_scale, b_zp = bias
+        if b.dtype != torch.int32 or b.numel() != n:
+            return f"a bias of {b.numel()} x {b.dtype} (N int32 values)"
+        if b_scale is None or b_scale.dtype != torch.float32 or b_scale.numel() != 1:
+            return "a b_scale that is not one fp32 value"
+        if b_zp is not None and (b_zp.dtype != torch.int32 or b_zp.numel() != 1):
+            return f"a b_zero_point of {b_zp.numel()} x {b_zp.dtype} (one int32 value)"
+    return None
+
+
+def qdq_function(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, w_zero_point: torch.Tensor | None = None, *, x_mode: str,
+                 x_scale: torch.Tensor | None = None, x_zero_point: torch.Tensor | None = None, out_mode: str | None = None,
+                 out_scale: torch.Tensor | None = None, out_zero_point: torch.Tensor | None = None, bias=None) -> torch.Tensor:
+    """One call of a `quant`-domain QDQ function with quantized activations (`oq_qdq_function`, csrc/qdq_function.hip): the input
+    Q -> DQ of ``x`` [..., K] fp32 (``x_mode`` "static": ``x_scale`` and ``x_zero_point``, whose type -- uint8 without one -- is the
+    one ``x`` is quantized to; "dynamic": uint8 with DynamicQuantizeLinear's parameters of ``x``), the MatMul / Gemm against
+    dequant(``w``) ([K, N] uint8 / int8, ``w_scale`` / ``w_zero_point`` per tensor or [N]), ``bias`` = (B int32 [N], b_scale,
+    b_zero_point or None) dequantized and added, and the output Q -> DQ (``out_mode`` None, "static" or "dynamic").  fp32 [..., N]
+    out.  The product is the exact int32 sum of (q_x - zp_x)(W - zp_w) on the int8 matrix cores; every parameter is a tensor on
+    the device.  A NaN in ``x``: the bottom of the type under "static", every element of the result NaN under "dynamic".
+    Deterministic; nothing synchronises with the host.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out (`qdq_function_unsupported`)."""
+    b, b_scale, b_zp = bias if bias is not None else (None, None, None)
+    named = dict(x=x, w=w, w_scale=w_scale, w_zero_point=w_zero_point, x_scale=x_scale, x_zero_point=x_zero_point, out_scale=out_scale,
+                 out_zero_point=out_zero_point, B=b, b_scale=b_scale, b_zero_point=b_zp)
+    for name, t in named.items():
+        if t is not None:
+            _require_device(t, name)
+    why = qdq_function_unsupported(x, w, w_scale, w_zero_point, x_mode=x_mode, x_scale=x_scale, x_zero_point=x_zero_point, out_mode=out_mode,
+                                   out_scale=out_scale, out_zero_point=out_zero_point, bias=bias)
+    if why is not None:
+        raise NotImplementedError(f"qdq_function: {why}")
+    k, n = int(w.shape[0]), int(w.shape[1])
+    rows = _rows_and_out(x.reshape(-1, k), n, torch.float32)
+    if rows is None:
+        return torch.zeros((*x.shape[:-1], n), dtype=torch.float32, device=x.device)
+    x2, m, lda, out = rows
+    w, ldw = _row_major(w)
+    per_column = n > 1 and any(t is not None and t.numel() == n for t in (w_scale, w_zero_point))
+    if per_column:      # one zero point for every column next to per-column scales (or the reverse): the library takes one code for both
+        w_scale = w_scale.reshape(-1).expand(n) if w_scale.numel() == 1 else w_scale
+        w_zero_point = w_zero_point.reshape(-1).expand(n) if w_zero_point is not None and w_zero_point.numel() == 1 else w_zero_point
+    w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, b, b_scale, b_zp = (
+        None if t is None else t.contiguous() for t in (w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, b, b_scale, b_zp))
+    x_code, out_code = _QDQ_MODE[x_mode], _QDQ_MODE[out_mode]
+    type_of = lambda zp: _QL_TYPE[torch.uint8 if zp is None else zp.dtype]      # noqa: E731
+    lib = L.load()
+    need = lib.oq_qdq_function_workspace_bytes(m, k, n, x_code, out_code)
+    ws = _workspace(need, x.device)
+    L.check(lib.oq_qdq_function(_ptr(x2), L.OQ_NBITS_F32, m, k, lda, x_code, type_of(x_zero_point), _ptr(x_scale), _ptr(x_zero_point), _ptr(w),
+                                _QDQ_WTYPE[w.dtype], n, ldw, L.OQ_CHANNEL if per_column else L.OQ_TENSOR, 0, _ptr(w_scale), _ptr(w_zero_point),
+                                _ptr(b), _ptr(b_scale), _ptr(b_zp), out_code, type_of(out_zero_point), _ptr(out_scale), _ptr(out_zero_point),
+                                _ptr(out), n, _ptr(ws), need, _stream()))
+    return out.reshape(*x.shape[:-1], n)
+
+
 # ----------------------------------------------------------------------------- G1 - G4
 def hessian_accumulate(x: torch.Tensor, h: torch.Tensor, n_seen: int, method: str | None = None) -> int:
     """gptq.py:246-260, in place on ``h`` [K, K]; ``x`` [n_add, ..., K] fp32, fp16 or bf16.  Returns the new sample
