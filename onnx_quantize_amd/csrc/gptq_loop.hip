@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void gptq_block_kernel(const LoopArgs a) {
 // so N / 4 waves -- one per SIMD at N = 4096 -- walk the steps, and a step is
 //     v_mov_dpp row_newbcast:R        the row's value to the 16 lanes of its column
 //     mul, fma x 4                    y = fl(w / scale), the IEEE quotient from the refined reciprocal of scale (below)
-//     add, med3                       + (1.5 * 2^23 + zp): round-half-even and zero point in one rounding; clamp
+//     add, med3                       + (1.5 * 2^23 + zp - (zp & 1)): round-half-even and zero point in one rounding; clamp
 //     sub, mul, sub                   dequantize, residual
 //     mul, fma x 4                    the IEEE quotient (w - q) / d from the refined reciprocal of d
 //     (LIVE + 1) / 2 x pk_mul, pk_add every lane updates its own later rows (product, then subtraction: gptq.py:198-200)
@@ -280,17 +280,27 @@ __device__ __forceinline__ float ror16(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + S /* row_ror:S */, 0xf, 0xf, true));
 }
 
+// The sum y + (M + zp) is rounded to the nearest integer with ties to the even SUM, the reference rounds y itself half to even and
+// adds zp afterwards (utils.py:72-79): the two agree on a tie only while M + zp is even.  So the parity of zp stays out of the sum:
+// zm = M + (zp - odd), odd = zp & 1, the clamp bounds move down by `odd`, and the level is the low byte of the clamped sum + odd --
+// added once per slab by the row's owner, not on the chain of the steps.  Dequantization needs level - zp = cl - zm as before.
 struct ColState {
-    float scale, neg_scale, rinv, zm;   // rinv = refined reciprocal of scale (div_refined), zm = float(zp) + 1.5 * 2^23
+    float scale, neg_scale, rinv, zm;   // rinv = refined reciprocal of scale (div_refined), zm = float(zp - odd) + 1.5 * 2^23
+    float lo_m, hi_m;                   // 1.5 * 2^23 + (qmin - odd), + (qmax - odd)
     int32_t zp;
+    uint32_t odd;
 };
-__device__ __forceinline__ ColState make_colstate(float scale, int32_t zp) {
+__device__ __forceinline__ ColState make_colstate(float scale, int32_t zp, const QGrid& grid) {
     ColState c;
     c.scale = scale;
     c.neg_scale = -scale;
     c.zp = zp;
+    c.odd = static_cast<uint32_t>(zp) & 1u;
+    const int32_t odd = static_cast<int32_t>(c.odd);
     c.rinv = refined_rcp(scale);
-    c.zm = static_cast<float>(zp) + kMagicF;
+    c.zm = static_cast<float>(zp - odd) + kMagicF;
+    c.lo_m = static_cast<float>(grid.qmin - odd) + kMagicF;
+    c.hi_m = static_cast<float>(grid.qmax - odd) + kMagicF;
     return c;
 }
 
@@ -309,7 +319,6 @@ struct SlabIn {
     const float* crow;    // LDS: plane A, row of the slab's first step, at this lane's r (plane B: + kCoefB)
     const float* drow;    // LDS: plane D, the same
     ColState cs;
-    float lo_m, hi_m;
     int r16, rows;
 };
 
@@ -340,10 +349,11 @@ __device__ __forceinline__ void row_step(f32x2 (&w2)[4], const SlabIn& in, StepC
     const f32x4 ca = cur.ca, cb = cur.cb;
     const f32x2 dd = cur.dd;
     const float wi = bcast16<R>(w2[0].x);
-    // K1 (gptq.py:186-188 = utils.py:72-79): y = fl(wi / s) (IEEE); adding M + zp (M = 1.5 * 2^23: fp32 spacing 1) rounds y
-    // half-to-even and adds the zero point in one correctly rounded operation; the clamp happens on M + level.
+    // K1 (gptq.py:186-188 = utils.py:72-79): y = fl(wi / s) (IEEE); adding M + zp - odd (M = 1.5 * 2^23: fp32 spacing 1, an even
+    // addend: ColState) rounds y half-to-even and adds the zero point in one correctly rounded operation; the clamp happens on
+    // M + level - odd.
     const float y = div_refined(wi, in.cs.neg_scale, in.cs.rinv);
-    const float cl = __builtin_amdgcn_fmed3f(y + in.cs.zm, in.lo_m, in.hi_m);
+    const float cl = __builtin_amdgcn_fmed3f(y + in.cs.zm, in.cs.lo_m, in.cs.hi_m);
     const float q = (cl - in.cs.zm) * in.cs.scale;                      // gptq.py:189 = utils.py:130-132
     const float t = wi - q;
     const float e = div_refined(t, dd.x, dd.y);                         // gptq.py:197: err = (w - q) / d
@@ -461,9 +471,7 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
         }
     }
     SlabIn in;
-    in.cs = make_colstate(scale, zp);
-    in.lo_m = static_cast<float>(a.grid.qmin) + kMagicF;
-    in.hi_m = static_cast<float>(a.grid.qmax) + kMagicF;
+    in.cs = make_colstate(scale, zp, a.grid);
     in.r16 = r16;
     int64_t grp = a.g > 0 ? a.i1 / a.g : 0;
     int64_t rem = a.g > 0 ? a.i1 - grp * a.g : 1;   // position of the slab's first row inside its group
@@ -507,7 +515,7 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
                 scale = p.scale;
                 zp = p.zp;
             }
-            in.cs = make_colstate(scale, zp);
+            in.cs = make_colstate(scale, zp, a.grid);
             if (live && r16 == 0 && a.used_scale != nullptr) {
                 a.used_scale[grp * a.N + c] = scale;
                 a.used_zp[grp * a.N + c] = zp;
@@ -531,7 +539,7 @@ __global__ __launch_bounds__(1024) void gptq_rows16_kernel(const LoopArgs a) {
                 default: slab16<7, false>(w2, in, save_e, save_cl); break;
             }
         }
-        store_level<16>(a, row0 + r16, c, live && r16 < in.rows, __float_as_uint(save_cl) & 0xffu);   // lanes 16 apart: columns c, c + 1, same row
+        store_level<16>(a, row0 + r16, c, live && r16 < in.rows, (__float_as_uint(save_cl) + in.cs.odd) & 0xffu);   // lanes 16 apart: columns c, c + 1, same row
         if (live && r16 < in.rows) {
             const int64_t row = row0 + r16;
             a.err[(a.err_row0 + 16 * k0 + r16) * a.N + c] = save_e;
