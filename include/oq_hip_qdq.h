@@ -27,7 +27,7 @@
  *   the int8 matrix cores           the static-input variants quantize A to 8 bits first; their product could run as
  *                                   oq_qlinear_matmul with an fp32 output.  That changes the arithmetic class (exact int32 sums
  *                                   instead of fp32 accumulation of dequantized activations) and is the natural follow-up.
- *   packed nibbles                  INT4 / UINT4 tensors arrive here unpacked, one value per byte.
+ *   packed nibbles                  INT4 / UINT4 tensors arrive here unpacked, one value per byte (as stored: oq_hip_qdq_packed4.h).
  *   group_size % 32 != 0            two groups would share one 32-deep matrix instruction (OQ_ERR_UNSUPPORTED, by name).
  *   K % group_size != 0             a [K, N] matrix has no padded group (OQ_ERR_UNSUPPORTED, by name).
  */

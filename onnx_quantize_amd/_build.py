@@ -42,9 +42,12 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # (tests/test_qdq_matmul_resources.py).
 # matmul_nbits_fzp.hip: tile_gemm once more, with a second scalar fma in the fold (the float zero point's correction): unpaired from its
 # first compile (tests/test_matmul_nbits_fzp_resources.py).
+# qdq_matmul_packed4.hip: tile_gemm on a [K, N / 2] matrix of packed nibbles, the same fold: unpaired from its first compile, and
+# compiled with the packed fp32 instructions switched off altogether, so that no other pass can pair it either.
 PER_FILE_FLAGS = {"hqq.hip": ("-fno-slp-vectorize",), "matmul_nbits.hip": ("-fno-slp-vectorize",),
                   "matmul_nbits_decode.hip": ("-fno-slp-vectorize",), "qdq_matmul.hip": ("-fno-slp-vectorize",),
-                  "matmul_nbits_fzp.hip": ("-fno-slp-vectorize",)}
+                  "matmul_nbits_fzp.hip": ("-fno-slp-vectorize",),
+                  "qdq_matmul_packed4.hip": ("-fno-slp-vectorize", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")}
 
 
 def flags_for(src: str) -> list[str]:
@@ -65,7 +68,7 @@ def sources() -> list[str]:
 def _deps_mtime() -> float:
     hdrs = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith((".hpp", ".h"))]
     hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h", "oq_hip_nbits_decode.h", "oq_hip_nbits_fzp.h", "oq_hip_qlinear.h",
-                                                           "oq_hip_qlinear_decode.h", "oq_hip_qlinear_function.h", "oq_hip_qdq.h", "oq_hip_qdq_function.h"))
+                                                           "oq_hip_qlinear_decode.h", "oq_hip_qlinear_function.h", "oq_hip_qdq.h", "oq_hip_qdq_function.h", "oq_hip_qdq_packed4.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -78,8 +81,10 @@ def _compile(src: str, force: bool, extra: tuple = ()) -> str:
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
-    if r.stderr.strip():
-        sys.stderr.write(r.stderr)
+    # the host pass of a file built with a device target feature says, once per use, that it does not know the feature
+    noise = "".join(line for line in r.stderr.splitlines(True) if "is not a recognized feature for this target (ignoring feature)" not in line)
+    if noise.strip():
+        sys.stderr.write(noise)
     return obj
 
 

@@ -71,7 +71,9 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     integers (`ops.qdq_matmul`: no fp32 copy of the weight is made per call).  The default stays the function body: the fused sum
     differs from torch's fp32 GEMM on the dequantized weight in its last bits.  ``qdq="fused+integer"`` also runs every call of a QDQ
     function with an input Q -> DQ (static or dynamic activations) as one library call on the int8 matrix cores (`ops.qdq_function`:
-    an exact int32 sum where the other routes accumulate the dequantized activations in fp32)."""
+    an exact int32 sum where the other routes accumulate the dequantized activations in fp32).  ``qdq="fused+packed4"`` is
+    ``"fused"`` with every 4-bit weight of such a function held as the file's packed nibbles (`ops.qdq_matmul_packed4`: half the
+    memory and half the weight read; the same bytes of output, so the same perplexity)."""
     import torch
 
     from .graph_runner import GraphRunner

@@ -136,10 +136,18 @@ class GraphRunner:
         # parameters, the static activation parameters and the bias triple are constants of the model on the GPU and X is a
         # non-empty fp32 tensor there.  Such calls are counted in `qdq_function_calls`: "integer", or "body" where a condition fails
         # and the body is walked node by node.  Every other QDQ function goes, and is counted, as under "fused".
-        if qdq not in ("torch", "fused", "fused+integer"):
-            raise ValueError(f"GraphRunner: qdq must be 'torch', 'fused' or 'fused+integer', got {qdq!r}")
+        # qdq = "fused+packed4": as "fused", and an INT4 / UINT4 initializer [K, N] with an even N that nothing reads but recognised QDQ
+        # functions, as their W, is uploaded as the file's packed bytes -- uint8 [K, N / 2], two values a byte -- and never held
+        # unpacked: half the HBM, the upload and the weight read.  Its calls run on `ops.qdq_matmul_packed4` and are counted under
+        # "packed4", a key only this mode adds; a call the kernel leaves out unpacks W on the device for that call, walks the body
+        # and is counted under "torch".  Not combined with "fused+integer", whose kernel refuses a 4-bit W.
+        if qdq not in ("torch", "fused", "fused+integer", "fused+packed4"):
+            raise ValueError(f"GraphRunner: qdq must be 'torch', 'fused', 'fused+integer' or 'fused+packed4', got {qdq!r}")
         self.qdq = qdq if self.device.type == "cuda" else "torch"
         self.qdq_calls = {"fused": 0, "torch": 0}        # calls of QDQ functions per route (counted like nbits_calls)
+        if self.qdq == "fused+packed4":
+            self.qdq_calls["packed4"] = 0
+        self._packed4: dict = {}                         # id(constant W held packed) -> (the constant, N, its nibbles are signed)
         self.qdq_function_calls = {"integer": 0, "body": 0}      # under "fused+integer": calls of the functions with an input Q -> DQ
         self._qdq_bias: dict = {}                        # id(constant B or b_zero_point) -> (the constant, its int32 copy)
         self._qdq_plans: dict = {}                       # id(function) -> (the function, _QdqPlan | None)
@@ -154,7 +162,15 @@ class GraphRunner:
             if i.name not in init_names and tt is not None and tt.elem_type in _NP_OF:
                 self.input_types[i.name] = np.dtype(_NP_OF[tt.elem_type])
         self.constants = {}
+        packable = self._packable_weights() if self.qdq == "fused+packed4" else ()
         for t in self.graph.initializer:
+            if t.name in packable:
+                raw = np.frombuffer(t.raw_data, dtype=np.uint8) if t.has("raw_data") else np.asarray(t.int32_data, dtype=np.int64).astype(np.uint8)
+                k, n = (int(d) for d in t.dims)
+                if raw.size == k * n // 2:                   # anything else is for tensor_to_numpy to name
+                    w = self.constants[t.name] = self._constant(raw.reshape(k, n // 2))
+                    self._packed4[id(w)] = (w, n, t.data_type == DataType.INT4)
+                    continue
             held = None if constants is None else constants.get(t.name)
             if (held is not None and held.device.type == self.device.type and tuple(held.shape) == tuple(int(d) for d in t.dims)
                     and _numpy_dtype(held) == np.dtype(_NP_OF.get(t.data_type, np.void))):
@@ -181,7 +197,7 @@ class GraphRunner:
         self.qlinear, self._qlinear_node, self.qlinear_calls = "torch", "torch", {"fused": 0, "torch": 0}
         self.qlinear_function_calls, self._qlinear_functions = {"function": 0, "body": 0}, {}
         self.qdq, self.qdq_calls, self._qdq_plans = "torch", {"fused": 0, "torch": 0}, {}
-        self.qdq_function_calls, self._qdq_bias = {"integer": 0, "body": 0}, {}
+        self.qdq_function_calls, self._qdq_bias, self._packed4 = {"integer": 0, "body": 0}, {}, {}
         return self
 
     def evaluate(self, node, arrays) -> list:
@@ -207,6 +223,23 @@ class GraphRunner:
         if t.dtype == torch.int64 and t.numel() <= 64:
             return t
         return t.to(self.device)
+
+    def _packable_weights(self) -> set:
+        """The names of the INT4 / UINT4 initializers "fused+packed4" holds packed: two axes, an even N, no external data, not a
+        wanted value, and every reader in the graph a call of a recognised QDQ function with the initializer as its W and nothing else."""
+        four_bit = {t.name for t in self.graph.initializer if t.data_type in (DataType.INT4, DataType.UINT4) and len(t.dims) == 2
+                    and int(t.dims[1]) % 2 == 0 and int(t.dims[0]) > 0 and int(t.dims[1]) > 0 and not t.data_location}
+        four_bit -= set(self.wanted) | {o.name for o in self.graph.output}
+        read = set()
+        for node in self.graph.node:
+            fn = self.functions.get((node.domain or "", node.op_type, node.overload or ""))
+            as_w = fn is not None and _QdqPlan.named(fn) and self._qdq_plan(fn) is not None and "W" in fn.input
+            inputs = list(node.input)
+            for name in self._reads(node):
+                if name in four_bit and not (as_w and inputs.count(name) == 1 and inputs.index(name) == list(fn.input).index("W")):
+                    four_bit.discard(name)
+                read.add(name)
+        return four_bit & read
 
     def _reads(self, node):
         names = [n for n in node.input if n]
@@ -393,11 +426,14 @@ class GraphRunner:
             if out is not None:
                 return (out,)
         elif _QdqPlan.named(fn):               # counted per call, whatever route it takes
-            plan = self._qdq_plan(fn) if self.qdq in ("fused", "fused+integer") else None
+            plan = self._qdq_plan(fn) if self.qdq in ("fused", "fused+integer", "fused+packed4") else None
+            packed = self._packed4.get(id(env.get("W")))
             outs = self._run_qdq_fused(fn, plan, dict(env)) if plan is not None else None
-            self.qdq_calls["torch" if outs is None else "fused"] += 1
+            self.qdq_calls["torch" if outs is None else "fused" if packed is None else "packed4"] += 1
             if outs is not None:
                 return outs
+            if packed is not None:             # what the kernel leaves out: the body reads W one value per byte, for this call only
+                env["W"] = self._unpacked4(*packed)
         if self.qlinear in ("function", "function+decode") and _qlinear_function_named(fn):      # counted per call, like the QDQ functions
             route, out = self._run_qlinear_function(fn, env)
             self.qlinear_function_calls[route] += 1
@@ -483,28 +519,43 @@ class GraphRunner:
             hit = self._qdq_bias[id(t)] = (t, t.to(torch.int32))
         return hit[1]
 
+    @staticmethod
+    def _unpacked4(w, n, signed):
+        """A weight held as packed nibbles [K, N / 2], one value per byte [K, N] in the 4-bit type's container, on the device."""
+        import torch
+        q = torch.stack((w & 0x0F, w >> 4), dim=-1).reshape(w.shape[0], n)
+        return ((q ^ 8).to(torch.int8) - 8) if signed else q
+
     def _run_qdq_fused(self, fn, plan, env):
-        """One call of a recognised QDQ function with its product on `ops.qdq_matmul`: the nodes of the body that dequantize W are
-        left out, the product node is replaced, every other node runs as it is.  Returns the function's outputs, or None --
-        nothing is kept -- where the kernel has no route for the call: the whole body then runs as under "torch"."""
+        """One call of a recognised QDQ function with its product on `ops.qdq_matmul` -- on `ops.qdq_matmul_packed4` where W is held
+        as packed nibbles ("fused+packed4"): the nodes of the body that dequantize W are left out, the product node is replaced,
+        every other node runs as it is.  Returns the function's outputs, or None -- nothing is kept -- where the kernel has no
+        route for the call: the whole body then runs as under "torch"."""
         import torch
         from .hip import ops
         w, scale, zp = env["W"], env["w_scale"], env["w_zero_point"]
+        packed = self._packed4.get(id(w))
         held = list(self.constants.values())
         if not all(isinstance(t, torch.Tensor) and t.is_cuda and any(t is c for c in held) for t in (w, scale) + (() if zp is None else (zp,))):
             return None
         if plan.group_size:
             shape = env.get("original_transposed_shape")
-            if not isinstance(shape, torch.Tensor) or shape.is_cuda or w.ndim != 2 or _ints(shape) != [w.shape[1], w.shape[0]]:
+            if not isinstance(shape, torch.Tensor) or shape.is_cuda or w.ndim != 2 or _ints(shape) != [w.shape[1] if packed is None else packed[1], w.shape[0]]:
                 return None
         nodes = list(fn.node)
         self._run([n for i, n in enumerate(nodes[:plan.product]) if i not in plan.weight_nodes], env)      # the input side, the bias
         x, bias = env[plan.x], env[plan.bias] if plan.bias else None
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.numel() > 0 and (bias is None or (isinstance(bias, torch.Tensor) and bias.is_cuda))):
             return None
-        if w.ndim != 2 or ops.qdq_matmul_unsupported(x, w, scale, zp, group_size=plan.group_size, bias=bias) is not None:
+        if packed is not None:
+            args = dict(n=packed[1], signed=packed[2], group_size=plan.group_size, bias=bias)
+            if ops.qdq_matmul_packed4_unsupported(x, w, scale, zp, **args) is not None:
+                return None
+            env[nodes[plan.product].output[0]] = ops.qdq_matmul_packed4(x, w, scale, zp, **args)
+        elif w.ndim != 2 or ops.qdq_matmul_unsupported(x, w, scale, zp, group_size=plan.group_size, bias=bias) is not None:
             return None
-        env[nodes[plan.product].output[0]] = ops.qdq_matmul(x, w, scale, zp, group_size=plan.group_size, bias=bias)
+        else:
+            env[nodes[plan.product].output[0]] = ops.qdq_matmul(x, w, scale, zp, group_size=plan.group_size, bias=bias)
         self._run(nodes[plan.product + 1:], env)                                                            # the output side
         return tuple(env[o] for o in fn.output)
 

@@ -53,6 +53,8 @@ OQ_QDQ_EXTENSION_VERSION = 1
 # include/oq_hip_qdq_function.h (its codes: oq_qdq_mode below, OQ_NBITS_* for X, OQ_UINT8 / OQ_INT8 and OQ_TENSOR / OQ_CHANNEL for W, OQ_QL_U8 / _I8)
 OQ_QDQ_NONE, OQ_QDQ_STATIC, OQ_QDQ_DYNAMIC = range(3)
 OQ_QDQ_FUNCTION_EXTENSION_VERSION = 1
+# include/oq_hip_qdq_packed4.h (the codes of oq_hip_qdq.h, with OQ_UINT4 / OQ_INT4 for W)
+OQ_QDQ_PACKED4_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -241,6 +243,14 @@ QDQ_FUNCTION_PROTOTYPES = {
                                _p, _i64, _p, _sz, _p]),
 }
 
+# the fused product from packed nibbles: mirrors include/oq_hip_qdq_packed4.h one to one (tests/test_qdq_matmul_packed4_abi.py checks
+# the set).  The argument list of oq_qdq_matmul: N counts values, ldw bytes.
+QDQ_PACKED4_PROTOTYPES = {
+    "oq_qdq_packed4_extension_version": (_i32, []),
+    "oq_qdq_matmul_packed4_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32]),
+    "oq_qdq_matmul_packed4": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i64, _p, _i32, _p, _p, _p, _i64, _p, _sz, _p]),
+}
+
 # what `load` binds and pins: (prototypes, the function that reports the version, the version this package expects, what the
 # message calls it)
 EXTENSIONS = [
@@ -254,6 +264,7 @@ EXTENSIONS = [
     (QLINEAR_FUNCTION_PROTOTYPES, "oq_qlinear_function_extension_version", OQ_QLINEAR_FUNCTION_EXTENSION_VERSION, "QLinear function extension"),
     (QDQ_PROTOTYPES, "oq_qdq_extension_version", OQ_QDQ_EXTENSION_VERSION, "QDQ matmul extension"),
     (QDQ_FUNCTION_PROTOTYPES, "oq_qdq_function_extension_version", OQ_QDQ_FUNCTION_EXTENSION_VERSION, "QDQ function extension"),
+    (QDQ_PACKED4_PROTOTYPES, "oq_qdq_packed4_extension_version", OQ_QDQ_PACKED4_EXTENSION_VERSION, "QDQ packed-nibble extension"),
 ]
 
 _lock = threading.Lock()

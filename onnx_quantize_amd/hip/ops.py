@@ -1279,7 +1279,12 @@ def qdq_matmul_unsupported(x, w, scale, zero_point=None, *, group_size: int = 0,
         return f"an input of {x.dtype} (fp32, fp16 and bf16 have a kernel)"
     if w.dtype not in _QDQ_WTYPE or w.ndim != 2:
         return f"a weight of {w.dtype} and {w.ndim} axes (a uint8 / int8 [K, N] matrix has a kernel)"
-    k, n, g = int(w.shape[0]), int(w.shape[1]), int(group_size)
+    return _qdq_parameters_unsupported(x, int(w.shape[0]), int(w.shape[1]), int(group_size), scale, zero_point, w.dtype, bias)
+
+
+def _qdq_parameters_unsupported(x, k: int, n: int, g: int, scale, zero_point, zp_dtype, bias) -> str | None:
+    """What `qdq_matmul_unsupported` and `qdq_matmul_packed4_unsupported` ask alike of a [K, N] weight's input, parameters and bias;
+    ``zp_dtype``: the container type of the weight's values."""
     if x.ndim < 1 or x.shape[-1] != k:
         return f"an input whose last axis is not K = {k}"
     if g < 0 or (g and g % 32):
@@ -1290,8 +1295,8 @@ def qdq_matmul_unsupported(x, w, scale, zero_point=None, *, group_size: int = 0,
         return f"scales of {scale.dtype} (float32 and the input's type have a kernel)"
     if _qdq_granularity(scale.numel(), k, n, g) is None:
         return f"{scale.numel()} scales for a [{k}, {n}] weight and group_size = {g} (1, N or N * K / group_size)"
-    if zero_point is not None and zero_point.dtype != w.dtype:
-        return f"a zero point of {zero_point.dtype} for a weight of {w.dtype}"
+    if zero_point is not None and zero_point.dtype != zp_dtype:
+        return f"a zero point of {zero_point.dtype} for a weight of {zp_dtype}"
     if zero_point is not None and zero_point.numel() != scale.numel():
         return f"{zero_point.numel()} zero points for {scale.numel()} scales"
     if bias is not None and (bias.dtype != x.dtype or bias.numel() != n):
@@ -1315,7 +1320,12 @@ def qdq_matmul(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, zero_point
     why = qdq_matmul_unsupported(x, w, scale, zero_point, group_size=group_size, bias=bias)
     if why is not None:
         raise NotImplementedError(f"qdq_matmul: {why}")
-    k, n = int(w.shape[0]), int(w.shape[1])
+    return _qdq_call("oq_qdq_matmul", x, w, _QDQ_WTYPE[w.dtype], int(w.shape[0]), int(w.shape[1]), scale, zero_point, group_size, bias)
+
+
+def _qdq_call(entry: str, x, w, wtype: int, k: int, n: int, scale, zero_point, group_size, bias) -> torch.Tensor:
+    """The call of `oq_qdq_matmul` / `oq_qdq_matmul_packed4` (one argument list) after its front has vouched for the operands:
+    ``w`` the byte matrix either of them reads, ``n`` the columns of the [K, N] weight it holds."""
     granularity, g = _qdq_granularity(scale.numel(), k, n, int(group_size))
     w, ldw = _row_major(w)
     scale = scale.contiguous()
@@ -1327,11 +1337,44 @@ def qdq_matmul(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, zero_point
     x2, m, lda, out = rows
     lib = L.load()
     atype = _NBITS_TYPE[x.dtype]
-    need = lib.oq_qdq_matmul_workspace_bytes(m, k, n, atype)
+    need = getattr(lib, entry + "_workspace_bytes")(m, k, n, atype)
     ws = _workspace(need, x.device) if need else None
-    L.check(lib.oq_qdq_matmul(_ptr(x2), atype, m, k, lda, _ptr(w), _QDQ_WTYPE[w.dtype], n, ldw, granularity, g, _ptr(scale), _NBITS_TYPE[scale.dtype],
-                              _ptr(zero_point), _ptr(bias), _ptr(out), n, _ptr(ws), need, _stream()))
+    L.check(getattr(lib, entry)(_ptr(x2), atype, m, k, lda, _ptr(w), wtype, n, ldw, granularity, g, _ptr(scale), _NBITS_TYPE[scale.dtype],
+                                _ptr(zero_point), _ptr(bias), _ptr(out), n, _ptr(ws), need, _stream()))
     return out.reshape(*x.shape[:-1], n)
+
+
+def qdq_matmul_packed4_unsupported(x, w_packed, scale, zero_point=None, *, n: int, signed: bool, group_size: int = 0, bias=None) -> str | None:
+    """Why `qdq_matmul_packed4` has no kernel for such a product (include/oq_hip_qdq_packed4.h), or None when it has one."""
+    if x.dtype not in _NBITS_TYPE:
+        return f"an input of {x.dtype} (fp32, fp16 and bf16 have a kernel)"
+    n = int(n)
+    if n <= 0 or n % 2:
+        return f"N = {n} (an even N has a kernel: the rows of a flat-packed odd N start on alternating nibbles)"
+    if w_packed.dtype != torch.uint8 or w_packed.ndim != 2 or w_packed.shape[1] < n // 2:
+        return f"a weight of {w_packed.dtype} and shape {tuple(w_packed.shape)} (a uint8 [K, >= N / 2 = {n // 2}] matrix of packed nibbles has a kernel)"
+    return _qdq_parameters_unsupported(x, int(w_packed.shape[0]), n, int(group_size), scale, zero_point, torch.int8 if signed else torch.uint8, bias)
+
+
+def qdq_matmul_packed4(x: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, zero_point: torch.Tensor | None = None, *, n: int, signed: bool,
+                       group_size: int = 0, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """`qdq_matmul` from a 4-bit weight as an ONNX INT4 / UINT4 initializer stores it (`oq_qdq_matmul_packed4`,
+    csrc/qdq_matmul_packed4.hip): ``w_packed`` uint8 [K, >= N / 2], byte [k, j] holding value [k, 2 j] in its low nibble and
+    [k, 2 j + 1] in its high one (rows may be strided); ``n`` the even number of values in a row; ``signed``: the nibbles are
+    two's-complement (INT4).  ``zero_point`` None (0) or one value per byte, int8 for a signed and uint8 for an unsigned weight.
+    Everything else, and the bytes of the result, as `qdq_matmul` on the unpacked weight.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out (`qdq_matmul_packed4_unsupported`)."""
+    for t, name in ((x, "x"), (w_packed, "w_packed"), (scale, "scale")) + (((zero_point, "zero_point"),) if zero_point is not None else ()) + \
+            (((bias, "bias"),) if bias is not None else ()):
+        _require_device(t, name)
+    why = qdq_matmul_packed4_unsupported(x, w_packed, scale, zero_point, n=n, signed=signed, group_size=group_size, bias=bias)
+    if why is not None:
+        raise NotImplementedError(f"qdq_matmul_packed4: {why}")
+    if w_packed.shape[1] > n // 2 and w_packed.stride(1) == 1:      # the columns that hold the N values; the row stride stays
+        w_packed = w_packed[:, :n // 2]
+    return _qdq_call("oq_qdq_matmul_packed4", x, w_packed, L.OQ_INT4 if signed else L.OQ_UINT4, int(w_packed.shape[0]), int(n), scale, zero_point,
+                     group_size, bias)
 
 
 DECODE_MAX_ROWS = 16      # include/oq_hip_nbits_decode.h: M of the decode route
