@@ -73,7 +73,9 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     function with an input Q -> DQ (static or dynamic activations) as one library call on the int8 matrix cores (`ops.qdq_function`:
     an exact int32 sum where the other routes accumulate the dequantized activations in fp32).  ``qdq="fused+packed4"`` is
     ``"fused"`` with every 4-bit weight of such a function held as the file's packed nibbles (`ops.qdq_matmul_packed4`: half the
-    memory and half the weight read; the same bytes of output, so the same perplexity)."""
+    memory and half the weight read; the same bytes of output, so the same perplexity).  ``qdq="fused+integer+packed4"`` is the
+    two together: the calls with an input Q -> DQ read the packed nibbles on the int8 matrix cores (`ops.qdq_function_packed4`: the
+    bytes of ``"fused+integer"``)."""
     import torch
 
     from .graph_runner import GraphRunner

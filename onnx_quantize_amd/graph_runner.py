@@ -140,15 +140,24 @@ class GraphRunner:
         # functions, as their W, is uploaded as the file's packed bytes -- uint8 [K, N / 2], two values a byte -- and never held
         # unpacked: half the HBM, the upload and the weight read.  Its calls run on `ops.qdq_matmul_packed4` and are counted under
         # "packed4", a key only this mode adds; a call the kernel leaves out unpacks W on the device for that call, walks the body
-        # and is counted under "torch".  Not combined with "fused+integer", whose kernel refuses a 4-bit W.
-        if qdq not in ("torch", "fused", "fused+integer", "fused+packed4"):
-            raise ValueError(f"GraphRunner: qdq must be 'torch', 'fused', 'fused+integer' or 'fused+packed4', got {qdq!r}")
+        # and is counted under "torch".  Under "fused+integer" a 4-bit W is held one value per byte, which `ops.qdq_function` reads.
+        # qdq = "fused+integer+packed4": the two combined.  The same initializers are held packed; a call of a function with an input
+        # Q -> DQ whose W is held packed runs as one call of `ops.qdq_function_packed4` and is counted in `qdq_function_calls` under
+        # "packed4", a key only this mode adds, with any other W as under "fused+integer"; a weight-only or output-only function with a
+        # packed W runs as under "fused+packed4".  A call of a function with an input Q -> DQ on a 4-bit W that the packed kernel
+        # leaves out -- or that is not held packed: an odd N -- walks the body ("body"), on W unpacked for that call where it is packed.
+        if qdq not in ("torch", "fused", "fused+integer", "fused+packed4", "fused+integer+packed4"):
+            raise ValueError("GraphRunner: qdq must be 'torch', 'fused', 'fused+integer', 'fused+packed4' or 'fused+integer+packed4', "
+                             f"got {qdq!r}")
         self.qdq = qdq if self.device.type == "cuda" else "torch"
         self.qdq_calls = {"fused": 0, "torch": 0}        # calls of QDQ functions per route (counted like nbits_calls)
-        if self.qdq == "fused+packed4":
+        if self.qdq in ("fused+packed4", "fused+integer+packed4"):
             self.qdq_calls["packed4"] = 0
         self._packed4: dict = {}                         # id(constant W held packed) -> (the constant, N, its nibbles are signed)
+        self._unpacked_four_bit: dict = {}               # "fused+integer+packed4": id(4-bit constant held one value per byte) -> the constant
         self.qdq_function_calls = {"integer": 0, "body": 0}      # under "fused+integer": calls of the functions with an input Q -> DQ
+        if self.qdq == "fused+integer+packed4":
+            self.qdq_function_calls["packed4"] = 0
         self._qdq_bias: dict = {}                        # id(constant B or b_zero_point) -> (the constant, its int32 copy)
         self._qdq_plans: dict = {}                       # id(function) -> (the function, _QdqPlan | None)
         self.functions = {(f.domain or "", f.name, f.overload or ""): f for f in model.functions}
@@ -162,7 +171,7 @@ class GraphRunner:
             if i.name not in init_names and tt is not None and tt.elem_type in _NP_OF:
                 self.input_types[i.name] = np.dtype(_NP_OF[tt.elem_type])
         self.constants = {}
-        packable = self._packable_weights() if self.qdq == "fused+packed4" else ()
+        packable = self._packable_weights() if self.qdq in ("fused+packed4", "fused+integer+packed4") else ()
         for t in self.graph.initializer:
             if t.name in packable:
                 raw = np.frombuffer(t.raw_data, dtype=np.uint8) if t.has("raw_data") else np.asarray(t.int32_data, dtype=np.int64).astype(np.uint8)
@@ -177,6 +186,8 @@ class GraphRunner:
                 self.constants[t.name] = held
             else:
                 self.constants[t.name] = self._constant(tensor_to_numpy(t), t.data_type)
+            if self.qdq == "fused+integer+packed4" and t.data_type in (DataType.INT4, DataType.UINT4):
+                self._unpacked_four_bit[id(self.constants[t.name])] = self.constants[t.name]
         self.nodes = self._needed_nodes(self.graph.node, self.wanted)
         # the last node that reads each value: it is dropped right after
         self.last_use: dict[str, int] = {}
@@ -197,7 +208,7 @@ class GraphRunner:
         self.qlinear, self._qlinear_node, self.qlinear_calls = "torch", "torch", {"fused": 0, "torch": 0}
         self.qlinear_function_calls, self._qlinear_functions = {"function": 0, "body": 0}, {}
         self.qdq, self.qdq_calls, self._qdq_plans = "torch", {"fused": 0, "torch": 0}, {}
-        self.qdq_function_calls, self._qdq_bias, self._packed4 = {"integer": 0, "body": 0}, {}, {}
+        self.qdq_function_calls, self._qdq_bias, self._packed4, self._unpacked_four_bit = {"integer": 0, "body": 0}, {}, {}, {}
         return self
 
     def evaluate(self, node, arrays) -> list:
@@ -420,13 +431,16 @@ class GraphRunner:
             env[name] = value
         for name in list(fn.input)[len(ins):]:
             env[name] = None
-        if self.qdq == "fused+integer" and _QdqPlan.input_mode(fn) is not None:      # counted per call, in a dict of their own
+        if self.qdq in ("fused+integer", "fused+integer+packed4") and _QdqPlan.input_mode(fn) is not None:      # counted per call, in a dict of their own
+            packed = self._packed4.get(id(env.get("W")))
             out = self._run_qdq_function(fn, env)
-            self.qdq_function_calls["body" if out is None else "integer"] += 1
+            self.qdq_function_calls["body" if out is None else "integer" if packed is None else "packed4"] += 1
             if out is not None:
                 return (out,)
+            if packed is not None:             # what the kernel leaves out: the body reads W one value per byte, for this call only
+                env["W"] = self._unpacked4(*packed)
         elif _QdqPlan.named(fn):               # counted per call, whatever route it takes
-            plan = self._qdq_plan(fn) if self.qdq in ("fused", "fused+integer", "fused+packed4") else None
+            plan = self._qdq_plan(fn) if self.qdq != "torch" else None
             packed = self._packed4.get(id(env.get("W")))
             outs = self._run_qdq_fused(fn, plan, dict(env)) if plan is not None else None
             self.qdq_calls["torch" if outs is None else "fused" if packed is None else "packed4"] += 1
@@ -479,8 +493,8 @@ class GraphRunner:
         return hit[1]
 
     def _run_qdq_function(self, fn, env):
-        """One call of a QDQ function with an input Q -> DQ as one library call (`ops.qdq_function`): the function's output, or None --
-        nothing was run -- where the body is not the one `onnx_functions.build_function` writes, W, a parameter or a member of the
+        """One call of a QDQ function with an input Q -> DQ as one library call (`ops.qdq_function`; `ops.qdq_function_packed4` where
+        W is held as packed nibbles, "fused+integer+packed4"): the function's output, or None -- nothing was run -- where the body is not the one `onnx_functions.build_function` writes, W, a parameter or a member of the
         bias triple is no constant of the model on the GPU, X is no fp32 tensor on the GPU with elements, or the kernel has no route
         for the call: the body then runs node by node."""
         import torch
@@ -504,9 +518,18 @@ class GraphRunner:
                     out_scale=env.get("out_scale") if out_mode == "static" else None,
                     out_zero_point=env.get("out_zero_point") if out_mode == "static" else None,
                     bias=(self._as_int32(env["B"]), env["b_scale"], self._as_int32(env["b_zero_point"])) if op == "Gemm" else None)
-        if ops.qdq_function_unsupported(x, env["W"], env["w_scale"], env["w_zero_point"], **args) is not None:
+        w = env["W"]
+        packed = self._packed4.get(id(w))
+        if packed is not None:
+            args.update(n=packed[1], signed=packed[2])
+            if ops.qdq_function_packed4_unsupported(x, w, env["w_scale"], env["w_zero_point"], **args) is not None:
+                return None
+            return ops.qdq_function_packed4(x, w, env["w_scale"], env["w_zero_point"], **args)
+        if self._unpacked_four_bit.get(id(w)) is w:      # a 4-bit W this mode could not hold packed: no unpacked copy feeds the 8-bit kernel
             return None
-        return ops.qdq_function(x, env["W"], env["w_scale"], env["w_zero_point"], **args)
+        if ops.qdq_function_unsupported(x, w, env["w_scale"], env["w_zero_point"], **args) is not None:
+            return None
+        return ops.qdq_function(x, w, env["w_scale"], env["w_zero_point"], **args)
 
     def _as_int32(self, t):
         """A constant of the bias triple as the library call takes it.  The writer stores B and its zero point in the weight's 8-bit

@@ -55,6 +55,8 @@ OQ_QDQ_NONE, OQ_QDQ_STATIC, OQ_QDQ_DYNAMIC = range(3)
 OQ_QDQ_FUNCTION_EXTENSION_VERSION = 1
 # include/oq_hip_qdq_packed4.h (the codes of oq_hip_qdq.h, with OQ_UINT4 / OQ_INT4 for W)
 OQ_QDQ_PACKED4_EXTENSION_VERSION = 1
+# include/oq_hip_qdq_function_packed4.h (the codes of oq_hip_qdq_function.h, with OQ_UINT4 / OQ_INT4 for W)
+OQ_QDQ_FUNCTION_PACKED4_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -251,6 +253,14 @@ QDQ_PACKED4_PROTOTYPES = {
     "oq_qdq_matmul_packed4": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i32, _i64, _i64, _i32, _i64, _p, _i32, _p, _p, _p, _i64, _p, _sz, _p]),
 }
 
+# a QDQ function with quantized activations from packed nibbles: mirrors include/oq_hip_qdq_function_packed4.h one to one
+# (tests/test_qdq_function_packed4_abi.py checks the set).  The argument list of oq_qdq_function: N counts values, ldw bytes.
+QDQ_FUNCTION_PACKED4_PROTOTYPES = {
+    "oq_qdq_function_packed4_extension_version": (_i32, []),
+    "oq_qdq_function_packed4_workspace_bytes": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function_workspace_bytes"],
+    "oq_qdq_function_packed4": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function"],
+}
+
 # what `load` binds and pins: (prototypes, the function that reports the version, the version this package expects, what the
 # message calls it)
 EXTENSIONS = [
@@ -265,6 +275,8 @@ EXTENSIONS = [
     (QDQ_PROTOTYPES, "oq_qdq_extension_version", OQ_QDQ_EXTENSION_VERSION, "QDQ matmul extension"),
     (QDQ_FUNCTION_PROTOTYPES, "oq_qdq_function_extension_version", OQ_QDQ_FUNCTION_EXTENSION_VERSION, "QDQ function extension"),
     (QDQ_PACKED4_PROTOTYPES, "oq_qdq_packed4_extension_version", OQ_QDQ_PACKED4_EXTENSION_VERSION, "QDQ packed-nibble extension"),
+    (QDQ_FUNCTION_PACKED4_PROTOTYPES, "oq_qdq_function_packed4_extension_version", OQ_QDQ_FUNCTION_PACKED4_EXTENSION_VERSION,
+     "QDQ function packed-nibble extension"),
 ]
 
 _lock = threading.Lock()

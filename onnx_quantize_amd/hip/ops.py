@@ -1818,29 +1818,30 @@ QDQ_FUNCTION_MAX_K = 33025      # include/oq_hip_qdq_function.h, `bounds`: 255 *
 _QDQ_MODE = {"static": L.OQ_QDQ_STATIC, "dynamic": L.OQ_QDQ_DYNAMIC, None: L.OQ_QDQ_NONE}
 
 
-def qdq_function_unsupported(x, w, w_scale, w_zero_point=None, *, x_mode, x_scale=None, x_zero_point=None, out_mode=None, out_scale=None,
-                             out_zero_point=None, bias=None) -> str | None:
-    """Why `qdq_function` has no kernel for such a call (include/oq_hip_qdq_function.h, "left out"), or None when it has one.
-    Element types, shapes and the refusals of the entry point; where the tensors live is the caller's question."""
+def _qdq_function_modes_unsupported(x, x_mode, out_mode) -> str | None:
+    """What `qdq_function_unsupported` and `qdq_function_packed4_unsupported` ask alike ahead of the weight: the modes and x's type."""
     if x_mode not in ("static", "dynamic"):
         return f"x_mode = {x_mode!r} ('static' and 'dynamic' have a kernel; a function without an input Q -> DQ keeps qdq_matmul)"
     if out_mode not in (None, "static", "dynamic"):
         return f"out_mode = {out_mode!r} (None, 'static' and 'dynamic' have a kernel)"
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
         return f"an x of {getattr(x, 'dtype', type(x).__name__)} (fp32 has a kernel)"
-    if w.dtype not in _QDQ_WTYPE or w.ndim != 2:
-        return f"a weight of {w.dtype} and {w.ndim} axes (a uint8 / int8 [K, N] matrix has a kernel)"
-    k, n = int(w.shape[0]), int(w.shape[1])
+    return None
+
+
+def _qdq_function_parameters_unsupported(x, k: int, n: int, max_k: int, products: str, w_dtype, w_scale, w_zero_point, x_mode, x_scale,
+                                         x_zero_point, out_mode, out_scale, out_zero_point, bias) -> str | None:
+    """... and behind it, of a [K, N] weight's input, parameters and bias; ``w_dtype``: the container type of the weight's values."""
     if x.ndim < 1 or x.shape[-1] != k:
         return f"an input whose last axis is not K = {k}"
-    if k > QDQ_FUNCTION_MAX_K:
-        return f"K = {k} (beyond {QDQ_FUNCTION_MAX_K} an int32 sum of 8-bit products could wrap)"
+    if k > max_k:
+        return f"K = {k} (beyond {max_k} an int32 sum of {products} products could wrap)"
     if w_scale is None:
         return "a missing w_scale"
     if w_scale.dtype != torch.float32 or w_scale.numel() not in (1, n):
         return f"a w_scale of {w_scale.numel()} x {w_scale.dtype} (1 or N fp32 values: a grouped W keeps qdq_matmul)"
-    if w_zero_point is not None and (w_zero_point.dtype != w.dtype or w_zero_point.numel() not in (1, n)):
-        return f"a w_zero_point of {w_zero_point.numel()} x {w_zero_point.dtype} for a weight of {w.dtype}"
+    if w_zero_point is not None and (w_zero_point.dtype != w_dtype or w_zero_point.numel() not in (1, n)):
+        return f"a w_zero_point of {w_zero_point.numel()} x {w_zero_point.dtype} for a weight of {w_dtype}"
     for mode, scale, zp, name in ((x_mode, x_scale, x_zero_point, "x"), (out_mode, out_scale, out_zero_point, "out")):
         if mode != "static":
             continue
@@ -1859,6 +1860,19 @@ def qdq_function_unsupported(x, w, w_scale, w_zero_point=None, *, x_mode, x_scal
     return None
 
 
+def qdq_function_unsupported(x, w, w_scale, w_zero_point=None, *, x_mode, x_scale=None, x_zero_point=None, out_mode=None, out_scale=None,
+                             out_zero_point=None, bias=None) -> str | None:
+    """Why `qdq_function` has no kernel for such a call (include/oq_hip_qdq_function.h, "left out"), or None when it has one.
+    Element types, shapes and the refusals of the entry point; where the tensors live is the caller's question."""
+    why = _qdq_function_modes_unsupported(x, x_mode, out_mode)
+    if why is not None:
+        return why
+    if w.dtype not in _QDQ_WTYPE or w.ndim != 2:
+        return f"a weight of {w.dtype} and {w.ndim} axes (a uint8 / int8 [K, N] matrix has a kernel)"
+    return _qdq_function_parameters_unsupported(x, int(w.shape[0]), int(w.shape[1]), QDQ_FUNCTION_MAX_K, "8-bit", w.dtype, w_scale, w_zero_point,
+                                                x_mode, x_scale, x_zero_point, out_mode, out_scale, out_zero_point, bias)
+
+
 def qdq_function(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, w_zero_point: torch.Tensor | None = None, *, x_mode: str,
                  x_scale: torch.Tensor | None = None, x_zero_point: torch.Tensor | None = None, out_mode: str | None = None,
                  out_scale: torch.Tensor | None = None, out_zero_point: torch.Tensor | None = None, bias=None) -> torch.Tensor:
@@ -1872,17 +1886,29 @@ def qdq_function(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, w_zero
     Deterministic; nothing synchronises with the host.
 
     NotImplementedError, naming the reason, for what the kernel leaves out (`qdq_function_unsupported`)."""
+    _qdq_function_on_device(x, w, w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, bias)
+    why = qdq_function_unsupported(x, w, w_scale, w_zero_point, x_mode=x_mode, x_scale=x_scale, x_zero_point=x_zero_point, out_mode=out_mode,
+                                   out_scale=out_scale, out_zero_point=out_zero_point, bias=bias)
+    if why is not None:
+        raise NotImplementedError(f"qdq_function: {why}")
+    return _qdq_function_call("oq_qdq_function", x, w, _QDQ_WTYPE[w.dtype], int(w.shape[0]), int(w.shape[1]), w_scale, w_zero_point, x_mode, x_scale,
+                              x_zero_point, out_mode, out_scale, out_zero_point, bias)
+
+
+def _qdq_function_on_device(x, w, w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, bias) -> None:
     b, b_scale, b_zp = bias if bias is not None else (None, None, None)
     named = dict(x=x, w=w, w_scale=w_scale, w_zero_point=w_zero_point, x_scale=x_scale, x_zero_point=x_zero_point, out_scale=out_scale,
                  out_zero_point=out_zero_point, B=b, b_scale=b_scale, b_zero_point=b_zp)
     for name, t in named.items():
         if t is not None:
             _require_device(t, name)
-    why = qdq_function_unsupported(x, w, w_scale, w_zero_point, x_mode=x_mode, x_scale=x_scale, x_zero_point=x_zero_point, out_mode=out_mode,
-                                   out_scale=out_scale, out_zero_point=out_zero_point, bias=bias)
-    if why is not None:
-        raise NotImplementedError(f"qdq_function: {why}")
-    k, n = int(w.shape[0]), int(w.shape[1])
+
+
+def _qdq_function_call(entry: str, x, w, wtype: int, k: int, n: int, w_scale, w_zero_point, x_mode, x_scale, x_zero_point, out_mode, out_scale,
+                       out_zero_point, bias) -> torch.Tensor:
+    """The call of `oq_qdq_function` / `oq_qdq_function_packed4` (one argument list) after its front has vouched for the operands:
+    ``w`` the byte matrix either of them reads, ``n`` the columns of the [K, N] weight it holds."""
+    b, b_scale, b_zp = bias if bias is not None else (None, None, None)
     rows = _rows_and_out(x.reshape(-1, k), n, torch.float32)
     if rows is None:
         return torch.zeros((*x.shape[:-1], n), dtype=torch.float32, device=x.device)
@@ -1897,13 +1923,56 @@ def qdq_function(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, w_zero
     x_code, out_code = _QDQ_MODE[x_mode], _QDQ_MODE[out_mode]
     type_of = lambda zp: _QL_TYPE[torch.uint8 if zp is None else zp.dtype]      # noqa: E731
     lib = L.load()
-    need = lib.oq_qdq_function_workspace_bytes(m, k, n, x_code, out_code)
+    need = getattr(lib, entry + "_workspace_bytes")(m, k, n, x_code, out_code)
     ws = _workspace(need, x.device)
-    L.check(lib.oq_qdq_function(_ptr(x2), L.OQ_NBITS_F32, m, k, lda, x_code, type_of(x_zero_point), _ptr(x_scale), _ptr(x_zero_point), _ptr(w),
-                                _QDQ_WTYPE[w.dtype], n, ldw, L.OQ_CHANNEL if per_column else L.OQ_TENSOR, 0, _ptr(w_scale), _ptr(w_zero_point),
+    L.check(getattr(lib, entry)(_ptr(x2), L.OQ_NBITS_F32, m, k, lda, x_code, type_of(x_zero_point), _ptr(x_scale), _ptr(x_zero_point), _ptr(w),
+                                wtype, n, ldw, L.OQ_CHANNEL if per_column else L.OQ_TENSOR, 0, _ptr(w_scale), _ptr(w_zero_point),
                                 _ptr(b), _ptr(b_scale), _ptr(b_zp), out_code, type_of(out_zero_point), _ptr(out_scale), _ptr(out_zero_point),
                                 _ptr(out), n, _ptr(ws), need, _stream()))
     return out.reshape(*x.shape[:-1], n)
+
+
+QDQ_FUNCTION_PACKED4_MAX_K = 561433      # include/oq_hip_qdq_function_packed4.h, `bounds`: 255 * 15 * K stays an int32
+
+
+def qdq_function_packed4_unsupported(x, w_packed, w_scale, w_zero_point=None, *, n: int, signed: bool, x_mode, x_scale=None, x_zero_point=None,
+                                     out_mode=None, out_scale=None, out_zero_point=None, bias=None) -> str | None:
+    """Why `qdq_function_packed4` has no kernel for such a call (include/oq_hip_qdq_function_packed4.h), or None when it has one."""
+    why = _qdq_function_modes_unsupported(x, x_mode, out_mode)
+    if why is not None:
+        return why
+    n = int(n)
+    if n <= 0 or n % 2:
+        return f"N = {n} (an even N has a kernel: the rows of a flat-packed odd N start on alternating nibbles)"
+    if w_packed.dtype != torch.uint8 or w_packed.ndim != 2 or w_packed.shape[1] < n // 2:
+        return (f"a weight of {w_packed.dtype} and shape {tuple(w_packed.shape)} (a uint8 [K, >= N / 2 = {n // 2}] matrix of packed nibbles has "
+                "a kernel; one value per byte keeps qdq_function)")
+    return _qdq_function_parameters_unsupported(x, int(w_packed.shape[0]), n, QDQ_FUNCTION_PACKED4_MAX_K, "8-bit by 4-bit",
+                                                torch.int8 if signed else torch.uint8, w_scale, w_zero_point, x_mode, x_scale, x_zero_point,
+                                                out_mode, out_scale, out_zero_point, bias)
+
+
+def qdq_function_packed4(x: torch.Tensor, w_packed: torch.Tensor, w_scale: torch.Tensor, w_zero_point: torch.Tensor | None = None, *, n: int,
+                         signed: bool, x_mode: str, x_scale: torch.Tensor | None = None, x_zero_point: torch.Tensor | None = None,
+                         out_mode: str | None = None, out_scale: torch.Tensor | None = None, out_zero_point: torch.Tensor | None = None,
+                         bias=None) -> torch.Tensor:
+    """`qdq_function` from a 4-bit weight as an ONNX INT4 / UINT4 initializer stores it (`oq_qdq_function_packed4`,
+    csrc/qdq_function_packed4.hip): ``w_packed`` uint8 [K, >= N / 2], byte [k, j] holding value [k, 2 j] in its low nibble and
+    [k, 2 j + 1] in its high one (rows may be strided); ``n`` the even number of values in a row; ``signed``: the nibbles are
+    two's-complement (INT4).  ``w_zero_point`` None (0) or one value per byte, int8 for a signed and uint8 for an unsigned weight.
+    K may reach `QDQ_FUNCTION_PACKED4_MAX_K`.  Everything else as `qdq_function`, and for a K it takes the bytes of the result are
+    those of `qdq_function` on the unpacked weight.
+
+    NotImplementedError, naming the reason, for what the kernel leaves out (`qdq_function_packed4_unsupported`)."""
+    _qdq_function_on_device(x, w_packed, w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, bias)
+    why = qdq_function_packed4_unsupported(x, w_packed, w_scale, w_zero_point, n=n, signed=signed, x_mode=x_mode, x_scale=x_scale,
+                                           x_zero_point=x_zero_point, out_mode=out_mode, out_scale=out_scale, out_zero_point=out_zero_point, bias=bias)
+    if why is not None:
+        raise NotImplementedError(f"qdq_function_packed4: {why}")
+    if w_packed.shape[1] > n // 2 and w_packed.stride(1) == 1:      # the columns that hold the N values; the row stride stays
+        w_packed = w_packed[:, :n // 2]
+    return _qdq_function_call("oq_qdq_function_packed4", x, w_packed, L.OQ_INT4 if signed else L.OQ_UINT4, int(w_packed.shape[0]), int(n), w_scale,
+                              w_zero_point, x_mode, x_scale, x_zero_point, out_mode, out_scale, out_zero_point, bias)
 
 
 # ----------------------------------------------------------------------------- G1 - G4
