@@ -20,6 +20,7 @@ from collections.abc import Mapping
 import numpy as np
 
 from .onnx_proto import _NP_OF, DataType, Message, attribute_value, tensor_to_numpy
+from .runner_routes import ById, Routes, _ints
 
 __all__ = ["GraphRunner", "UnsupportedOperator"]
 
@@ -47,12 +48,7 @@ def _numpy_dtype(t):
         return None
 
 
-def _ints(t) -> list[int]:
-    """A shape-like operand as Python ints (one sync when it lives on the device; shape arithmetic is kept on the host)."""
-    return [int(v) for v in (t.tolist() if t.ndim else [t.item()])]
-
-
-class GraphRunner:
+class GraphRunner(Routes):
     """``GraphRunner(model, outputs=[names], device="cuda")(feed)`` -> ``{name: tensor on the device}``.
 
     model: a parsed ModelProto (`onnx_proto.parse_model`); outputs: the value names wanted (default: the graph's own
@@ -64,7 +60,8 @@ class GraphRunner:
                  matmul_nbits: str = "torch", qlinear: str = "torch", qdq: str = "torch"):
         """`constants`: {initializer name: tensor on the device} for initializers the caller already holds in HBM (a second
         calibration walk over the weights the first one uploaded; a weight that was rescaled on the device and whose TensorProto
-        still has the old bytes): used as they are instead of the file's bytes when device, element type and shape fit."""
+        still has the old bytes): used as they are instead of the file's bytes when device, element type and shape fit.
+        `matmul`, `matmul_nbits`, `qlinear`, `qdq`: what runs on a library kernel instead of torch (runner_routes.py)."""
         import torch
 
         self.model, self.graph = model, model.graph
@@ -76,90 +73,9 @@ class GraphRunner:
         self.capture = bool(capture) and self.device.type == "cuda"
         self._graphs: dict = {}              # input signature -> (graph, static inputs, static outputs) | None (stays eager)
         self._seen: set = set()
-        self._moved: dict = {}               # id(host constant) -> (the constant, its copy on the device)
+        self._moved = ById()                 # host constant -> its copy on the device
         self._const_nodes: dict = {}         # id(Constant node) -> its value (one object per node, so `_moved` can key on it)
-        # matmul = "pieces": products of fp32 activations with a LARGE constant weight go through the library's fp16-piece GEMM
-        # (`ops.matmul_pieces`: the Hessian kernels' arithmetic, 22-bit operands, fp32 accumulate: ~3 x torch's fp32 GEMM at these
-        # sizes and closer to float64); the weight's pieces are made once.  Small products and everything else stay with torch.
-        if matmul not in ("torch", "pieces"):
-            raise ValueError(f"GraphRunner: matmul must be 'torch' or 'pieces', got {matmul!r}")
-        self.matmul = matmul if self.device.type == "cuda" else "torch"
-        self._weight_pieces: dict = {}       # id(constant weight) -> (the weight, its MatmulOperand)
-        # matmul_nbits = "fused": a MatMulNBits node the library has a kernel for (`ops.matmul_nbits`: integer zero points, a block
-        # size that is a multiple of 32, 4 / 8 bits, a constant B on the GPU) runs from the blob as stored -- no [N, K] weight is
-        # expanded.  Every other node, and every node under "torch", takes the expansion of `_op_MatMulNBits`.
-        # matmul_nbits = "fused+decode": a node whose flattened A has at most 16 rows and which the decode kernel takes
-        # (`ops.matmul_nbits_decode`: also float zero points -- HQQ files -- and block size 16) runs there; every other node goes as
-        # under "fused".  Only this mode counts a third route, "decode".
-        # matmul_nbits = "fused+float_zp" / "fused+float_zp+decode": as "fused" / "fused+decode", and a node with floating-point zero
-        # points (HQQ files) and a block size that is a multiple of 32, which the decode route has not taken, runs on
-        # `ops.matmul_nbits_float_zp` instead of the expansion.  Only these modes count the route "float_zp".
-        if matmul_nbits not in _NBITS_MODES:
-            raise ValueError("GraphRunner: matmul_nbits must be 'torch', 'fused', 'fused+decode', 'fused+float_zp' or 'fused+float_zp+decode', "
-                             f"got {matmul_nbits!r}")
-        self.matmul_nbits = matmul_nbits if self.device.type == "cuda" else "torch"
-        self.nbits_calls = {"fused": 0, "torch": 0}      # MatMulNBits nodes run per route (a replayed graph counts its recording only)
-        if "float_zp" in self.matmul_nbits:
-            self.nbits_calls["float_zp"] = 0
-        if self.matmul_nbits.endswith("decode"):
-            self.nbits_calls["decode"] = 0
-        # qlinear = "fused": a QLinearMatMul / QGemm node the library has a kernel for (`ops.qlinear_matmul`: 8-bit operands on the
-        # GPU, per-tensor activation parameters, fp32 scales, a constant 2-D B, alpha = 1, no transA) runs on the int8 matrix cores
-        # with an exact int32 sum -- no operand is dequantized.  Every other node, and every node under "torch", takes the expansion.
-        # qlinear = "fused+decode": such a node whose flattened A has at most 16 rows runs on the decode kernel
-        # (`ops.qlinear_matmul_decode`: B streamed once, the same accumulator and epilogue, so the same bytes); every other node goes
-        # as under "fused".  Only this mode counts a third route, "decode".
-        # qlinear = "function": a call of a `quant`-domain function QLinearMatMul / QLinearGemm (onnx_functions: what a
-        # `format="qlinear"` file holds) whose body is the one `build_function` writes -- QuantizeLinear, the integer product,
-        # DequantizeLinear -- runs as ONE library call (`ops.qlinear_function`: fp32 in, fp32 out, the bytes of the three nodes), when
-        # W and every parameter are constants of the model on the GPU.  Every other call walks its body, whose integer node then goes
-        # as under "fused".  qlinear = "function+decode": such a call with at most 16 flattened rows runs on
-        # `ops.qlinear_function_decode`; everything else as under "function", the body's integer node as under "fused+decode".
-        if qlinear not in ("torch", "fused", "fused+decode", "function", "function+decode"):
-            raise ValueError(f"GraphRunner: qlinear must be 'torch', 'fused', 'fused+decode', 'function' or 'function+decode', got {qlinear!r}")
-        self.qlinear = qlinear if self.device.type == "cuda" else "torch"
-        self._qlinear_node = _QLINEAR_NODE_MODE[self.qlinear]   # the route of a bare QLinearMatMul / QGemm node
-        self.qlinear_calls = {"fused": 0, "torch": 0}    # QLinearMatMul / QGemm nodes run per route (counted like nbits_calls)
-        if self._qlinear_node == "fused+decode":
-            self.qlinear_calls["decode"] = 0
-        self.qlinear_function_calls = {"function": 0, "body": 0}     # calls of the QLinear functions: one library call / the body walked
-        if self.qlinear == "function+decode":
-            self.qlinear_function_calls["decode"] = 0
-        self._qlinear_functions: dict = {}               # id(function) -> (the function, its body is the writer's)
-        # qdq = "fused": a call of a `quant`-domain QDQ function (onnx_functions: the default output format) whose body is the one
-        # `build_function` writes runs its product from the stored integers (`ops.qdq_matmul`: W [K, N] bytes, its scales and zero
-        # points as the file holds them; no fp32 weight is made).  The body's own operators around the product -- Q -> DQ of the
-        # input, of the output, DQ of the bias -- run as they are.  Every other call, and every call under "torch", walks the body.
-        # qdq = "fused+integer": as "fused", and a call of a QDQ function with an input Q -> DQ (static or dynamic; with or without an
-        # output Q -> DQ) whose body is the one `build_function` writes runs as ONE library call (`ops.qdq_function`: fp32 in, fp32
-        # out, the product of the 8-bit activations and the stored W as an exact int32 sum on the int8 matrix cores), when W, its
-        # parameters, the static activation parameters and the bias triple are constants of the model on the GPU and X is a
-        # non-empty fp32 tensor there.  Such calls are counted in `qdq_function_calls`: "integer", or "body" where a condition fails
-        # and the body is walked node by node.  Every other QDQ function goes, and is counted, as under "fused".
-        # qdq = "fused+packed4": as "fused", and an INT4 / UINT4 initializer [K, N] with an even N that nothing reads but recognised QDQ
-        # functions, as their W, is uploaded as the file's packed bytes -- uint8 [K, N / 2], two values a byte -- and never held
-        # unpacked: half the HBM, the upload and the weight read.  Its calls run on `ops.qdq_matmul_packed4` and are counted under
-        # "packed4", a key only this mode adds; a call the kernel leaves out unpacks W on the device for that call, walks the body
-        # and is counted under "torch".  Under "fused+integer" a 4-bit W is held one value per byte, which `ops.qdq_function` reads.
-        # qdq = "fused+integer+packed4": the two combined.  The same initializers are held packed; a call of a function with an input
-        # Q -> DQ whose W is held packed runs as one call of `ops.qdq_function_packed4` and is counted in `qdq_function_calls` under
-        # "packed4", a key only this mode adds, with any other W as under "fused+integer"; a weight-only or output-only function with a
-        # packed W runs as under "fused+packed4".  A call of a function with an input Q -> DQ on a 4-bit W that the packed kernel
-        # leaves out -- or that is not held packed: an odd N -- walks the body ("body"), on W unpacked for that call where it is packed.
-        if qdq not in ("torch", "fused", "fused+integer", "fused+packed4", "fused+integer+packed4"):
-            raise ValueError("GraphRunner: qdq must be 'torch', 'fused', 'fused+integer', 'fused+packed4' or 'fused+integer+packed4', "
-                             f"got {qdq!r}")
-        self.qdq = qdq if self.device.type == "cuda" else "torch"
-        self.qdq_calls = {"fused": 0, "torch": 0}        # calls of QDQ functions per route (counted like nbits_calls)
-        if self.qdq in ("fused+packed4", "fused+integer+packed4"):
-            self.qdq_calls["packed4"] = 0
-        self._packed4: dict = {}                         # id(constant W held packed) -> (the constant, N, its nibbles are signed)
-        self._unpacked_four_bit: dict = {}               # "fused+integer+packed4": id(4-bit constant held one value per byte) -> the constant
-        self.qdq_function_calls = {"integer": 0, "body": 0}      # under "fused+integer": calls of the functions with an input Q -> DQ
-        if self.qdq == "fused+integer+packed4":
-            self.qdq_function_calls["packed4"] = 0
-        self._qdq_bias: dict = {}                        # id(constant B or b_zero_point) -> (the constant, its int32 copy)
-        self._qdq_plans: dict = {}                       # id(function) -> (the function, _QdqPlan | None)
+        self._init_routes(matmul, matmul_nbits, qlinear, qdq)
         self.functions = {(f.domain or "", f.name, f.overload or ""): f for f in model.functions}
         self.opset = max([int(o.version or 1) for o in model.opset_import if not o.domain] or [1])
         self.wanted = list(outputs) if outputs is not None else [o.name for o in self.graph.output]
@@ -171,14 +87,15 @@ class GraphRunner:
             if i.name not in init_names and tt is not None and tt.elem_type in _NP_OF:
                 self.input_types[i.name] = np.dtype(_NP_OF[tt.elem_type])
         self.constants = {}
-        packable = self._packable_weights() if self.qdq in ("fused+packed4", "fused+integer+packed4") else ()
+        packing = "packed4" in self._qdq_routes
+        packable = self._packable_weights() if packing else ()
         for t in self.graph.initializer:
             if t.name in packable:
                 raw = np.frombuffer(t.raw_data, dtype=np.uint8) if t.has("raw_data") else np.asarray(t.int32_data, dtype=np.int64).astype(np.uint8)
                 k, n = (int(d) for d in t.dims)
                 if raw.size == k * n // 2:                   # anything else is for tensor_to_numpy to name
                     w = self.constants[t.name] = self._constant(raw.reshape(k, n // 2))
-                    self._packed4[id(w)] = (w, n, t.data_type == DataType.INT4)
+                    self._packed4.memo(w, lambda w: (n, t.data_type == DataType.INT4))
                     continue
             held = None if constants is None else constants.get(t.name)
             if (held is not None and held.device.type == self.device.type and tuple(held.shape) == tuple(int(d) for d in t.dims)
@@ -186,8 +103,10 @@ class GraphRunner:
                 self.constants[t.name] = held
             else:
                 self.constants[t.name] = self._constant(tensor_to_numpy(t), t.data_type)
-            if self.qdq == "fused+integer+packed4" and t.data_type in (DataType.INT4, DataType.UINT4):
-                self._unpacked_four_bit[id(self.constants[t.name])] = self.constants[t.name]
+            if packing and self._qdq_function_routes and t.data_type in (DataType.INT4, DataType.UINT4):
+                self._packed4.memo(self.constants[t.name], lambda w: ())
+        # `constants` is never rebound or written after this line, so what is a constant, by identity, is settled here (`_held`)
+        self._constant_ids = ById((id(c), (c, True)) for c in self.constants.values())
         self.nodes = self._needed_nodes(self.graph.node, self.wanted)
         # the last node that reads each value: it is dropped right after
         self.last_use: dict[str, int] = {}
@@ -197,19 +116,9 @@ class GraphRunner:
 
     @classmethod
     def evaluator(cls, opset: int):
-        """A runner without a model: `evaluate(node, arrays)` applies ONE operator on the host (what a constant folder needs)."""
-        import torch
-        self = cls.__new__(cls)
-        self.model = self.graph = None
-        self.device = torch.device("cpu")
-        self.functions, self.opset, self.wanted, self.input_names, self.constants, self.nodes, self.last_use = {}, opset, [], [], {}, [], {}
-        self.capture, self._graphs, self._seen, self._moved, self._const_nodes = False, {}, set(), {}, {}
-        self.matmul_nbits, self.nbits_calls = "torch", {"fused": 0, "torch": 0}
-        self.qlinear, self._qlinear_node, self.qlinear_calls = "torch", "torch", {"fused": 0, "torch": 0}
-        self.qlinear_function_calls, self._qlinear_functions = {"function": 0, "body": 0}, {}
-        self.qdq, self.qdq_calls, self._qdq_plans = "torch", {"fused": 0, "torch": 0}, {}
-        self.qdq_function_calls, self._qdq_bias, self._packed4, self._unpacked_four_bit = {"integer": 0, "body": 0}, {}, {}, {}
-        return self
+        """A runner on the host over a model with nothing in it: `evaluate(node, arrays)` applies ONE operator (what a constant
+        folder needs)."""
+        return cls(Message("ModelProto", graph=Message("GraphProto"), opset_import=[Message("OperatorSetIdProto", domain="", version=opset)]), device="cpu")
 
     def evaluate(self, node, arrays) -> list:
         """The outputs (NumPy) of `node` on the given input arrays (None for an absent optional input)."""
@@ -234,23 +143,6 @@ class GraphRunner:
         if t.dtype == torch.int64 and t.numel() <= 64:
             return t
         return t.to(self.device)
-
-    def _packable_weights(self) -> set:
-        """The names of the INT4 / UINT4 initializers "fused+packed4" holds packed: two axes, an even N, no external data, not a
-        wanted value, and every reader in the graph a call of a recognised QDQ function with the initializer as its W and nothing else."""
-        four_bit = {t.name for t in self.graph.initializer if t.data_type in (DataType.INT4, DataType.UINT4) and len(t.dims) == 2
-                    and int(t.dims[1]) % 2 == 0 and int(t.dims[0]) > 0 and int(t.dims[1]) > 0 and not t.data_location}
-        four_bit -= set(self.wanted) | {o.name for o in self.graph.output}
-        read = set()
-        for node in self.graph.node:
-            fn = self.functions.get((node.domain or "", node.op_type, node.overload or ""))
-            as_w = fn is not None and _QdqPlan.named(fn) and self._qdq_plan(fn) is not None and "W" in fn.input
-            inputs = list(node.input)
-            for name in self._reads(node):
-                if name in four_bit and not (as_w and inputs.count(name) == 1 and inputs.index(name) == list(fn.input).index("W")):
-                    four_bit.discard(name)
-                read.add(name)
-        return four_bit & read
 
     def _reads(self, node):
         names = [n for n in node.input if n]
@@ -413,12 +305,11 @@ class GraphRunner:
             return t
         if t.numel() == 1 and op_type in _SCALAR_FRIENDLY:
             return t.item()
-        hit = self._moved.get(id(t))
-        if hit is not None and hit[0] is t:
-            return hit[1]
-        moved = t.to(self.device)
-        if any(t is c for c in self.constants.values()) or any(t is c for c in self._const_nodes.values()):
-            self._moved[id(t)] = (t, moved)
+        moved = self._moved.value(t)
+        if moved is None:
+            moved = t.to(self.device)
+            if self._constant_ids.value(t) or any(t is c for c in self._const_nodes.values()):
+                self._moved.memo(t, lambda t: moved)
         return moved
 
     def _call_function(self, fn, node, ins):
@@ -431,155 +322,10 @@ class GraphRunner:
             env[name] = value
         for name in list(fn.input)[len(ins):]:
             env[name] = None
-        if self.qdq in ("fused+integer", "fused+integer+packed4") and _QdqPlan.input_mode(fn) is not None:      # counted per call, in a dict of their own
-            packed = self._packed4.get(id(env.get("W")))
-            out = self._run_qdq_function(fn, env)
-            self.qdq_function_calls["body" if out is None else "integer" if packed is None else "packed4"] += 1
-            if out is not None:
-                return (out,)
-            if packed is not None:             # what the kernel leaves out: the body reads W one value per byte, for this call only
-                env["W"] = self._unpacked4(*packed)
-        elif _QdqPlan.named(fn):               # counted per call, whatever route it takes
-            plan = self._qdq_plan(fn) if self.qdq != "torch" else None
-            packed = self._packed4.get(id(env.get("W")))
-            outs = self._run_qdq_fused(fn, plan, dict(env)) if plan is not None else None
-            self.qdq_calls["torch" if outs is None else "fused" if packed is None else "packed4"] += 1
-            if outs is not None:
-                return outs
-            if packed is not None:             # what the kernel leaves out: the body reads W one value per byte, for this call only
-                env["W"] = self._unpacked4(*packed)
-        if self.qlinear in ("function", "function+decode") and _qlinear_function_named(fn):      # counted per call, like the QDQ functions
-            route, out = self._run_qlinear_function(fn, env)
-            self.qlinear_function_calls[route] += 1
-            if out is not None:
-                return (out,)
+        outs = self._route_call(fn, env)
+        if outs is not None:
+            return outs
         self._run(list(fn.node), env)          # a function body sees its inputs only (ONNX functions are closed)
-        return tuple(env[o] for o in fn.output)
-
-    def _run_qlinear_function(self, fn, env):
-        """One call of a `quant`-domain QLinearMatMul / QLinearGemm function as one library call: (route, the function's output), or
-        ("body", None) -- nothing was run -- where the body is not the one `onnx_functions.build_function` writes (a file may carry
-        another function under a reference name), W or a parameter is no constant of the model on the GPU, X is no fp32 tensor on
-        the GPU with elements, or the kernel has no route for the call: the body then runs node by node."""
-        import torch
-        from .hip import ops
-        hit = self._qlinear_functions.get(id(fn))
-        if hit is None or hit[0] is not fn:
-            from .onnx_functions import build_function
-            hit = self._qlinear_functions[id(fn)] = (fn, _QdqPlan._shape(fn) == _QdqPlan._shape(build_function(fn.name)))
-        if not hit[1]:
-            return "body", None
-        x = env["X"]
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim >= 1 and x.numel() > 0):
-            return "body", None
-        names = ("W", "w_scale", "w_zero_point", "x_scale", "x_zero_point", "out_scale", "out_zero_point") + (("B",) if fn.name == "QLinearGemm" else ())
-        held = list(self.constants.values())
-        if not all(env[n] is None or (isinstance(env[n], torch.Tensor) and env[n].is_cuda and any(env[n] is c for c in held)) for n in names):
-            return "body", None
-        args = (x, env["x_scale"], env["x_zero_point"], env["W"], env["w_scale"], env["w_zero_point"], env["out_scale"], env["out_zero_point"])
-        bias = env.get("B") if fn.name == "QLinearGemm" else None
-        if self.qlinear == "function+decode" and ops.qlinear_function_decode_unsupported(*args, bias=bias) is None:
-            return "decode", ops.qlinear_function_decode(*args, bias=bias)
-        if ops.qlinear_function_unsupported(*args, bias=bias) is None:
-            return "function", ops.qlinear_function(*args, bias=bias)
-        return "body", None
-
-    def _qdq_plan(self, fn):
-        """The `_QdqPlan` of a `quant`-domain QDQ function whose body is the one `onnx_functions.build_function` writes under that
-        name; None for every other function -- a file may carry another function under a reference name."""
-        hit = self._qdq_plans.get(id(fn))
-        if hit is None or hit[0] is not fn:
-            hit = self._qdq_plans[id(fn)] = (fn, _QdqPlan.of(fn))
-        return hit[1]
-
-    def _run_qdq_function(self, fn, env):
-        """One call of a QDQ function with an input Q -> DQ as one library call (`ops.qdq_function`; `ops.qdq_function_packed4` where
-        W is held as packed nibbles, "fused+integer+packed4"): the function's output, or None -- nothing was run -- where the body is not the one `onnx_functions.build_function` writes, W, a parameter or a member of the
-        bias triple is no constant of the model on the GPU, X is no fp32 tensor on the GPU with elements, or the kernel has no route
-        for the call: the body then runs node by node."""
-        import torch
-        from .hip import ops
-        from .onnx_functions import _QDQ
-        if self._qdq_plan(fn) is None:
-            return None
-        x = env["X"]
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.ndim >= 1 and x.numel() > 0):
-            return None
-        op, (x_mode, out_mode) = _QDQ[fn.name]
-        names = ["W", "w_scale", "w_zero_point"] + (["B", "b_scale", "b_zero_point"] if op == "Gemm" else []) + \
-            (["x_scale", "x_zero_point"] if x_mode == "static" else []) + (["out_scale", "out_zero_point"] if out_mode == "static" else [])
-        held = list(self.constants.values())
-        if not all(env[n] is None or (isinstance(env[n], torch.Tensor) and env[n].is_cuda and any(env[n] is c for c in held)) for n in names):
-            return None
-        if env["W"] is None or env["w_scale"] is None or (op == "Gemm" and env["B"] is None):
-            return None
-        args = dict(x_mode=x_mode, x_scale=env.get("x_scale") if x_mode == "static" else None,
-                    x_zero_point=env.get("x_zero_point") if x_mode == "static" else None, out_mode=out_mode,
-                    out_scale=env.get("out_scale") if out_mode == "static" else None,
-                    out_zero_point=env.get("out_zero_point") if out_mode == "static" else None,
-                    bias=(self._as_int32(env["B"]), env["b_scale"], self._as_int32(env["b_zero_point"])) if op == "Gemm" else None)
-        w = env["W"]
-        packed = self._packed4.get(id(w))
-        if packed is not None:
-            args.update(n=packed[1], signed=packed[2])
-            if ops.qdq_function_packed4_unsupported(x, w, env["w_scale"], env["w_zero_point"], **args) is not None:
-                return None
-            return ops.qdq_function_packed4(x, w, env["w_scale"], env["w_zero_point"], **args)
-        if self._unpacked_four_bit.get(id(w)) is w:      # a 4-bit W this mode could not hold packed: no unpacked copy feeds the 8-bit kernel
-            return None
-        if ops.qdq_function_unsupported(x, w, env["w_scale"], env["w_zero_point"], **args) is not None:
-            return None
-        return ops.qdq_function(x, w, env["w_scale"], env["w_zero_point"], **args)
-
-    def _as_int32(self, t):
-        """A constant of the bias triple as the library call takes it.  The writer stores B and its zero point in the weight's 8-bit
-        type; the same integers as int32, made once per constant."""
-        import torch
-        if t is None or t.dtype == torch.int32 or t.dtype not in (torch.int8, torch.uint8):
-            return t
-        hit = self._qdq_bias.get(id(t))
-        if hit is None or hit[0] is not t:
-            hit = self._qdq_bias[id(t)] = (t, t.to(torch.int32))
-        return hit[1]
-
-    @staticmethod
-    def _unpacked4(w, n, signed):
-        """A weight held as packed nibbles [K, N / 2], one value per byte [K, N] in the 4-bit type's container, on the device."""
-        import torch
-        q = torch.stack((w & 0x0F, w >> 4), dim=-1).reshape(w.shape[0], n)
-        return ((q ^ 8).to(torch.int8) - 8) if signed else q
-
-    def _run_qdq_fused(self, fn, plan, env):
-        """One call of a recognised QDQ function with its product on `ops.qdq_matmul` -- on `ops.qdq_matmul_packed4` where W is held
-        as packed nibbles ("fused+packed4"): the nodes of the body that dequantize W are left out, the product node is replaced,
-        every other node runs as it is.  Returns the function's outputs, or None -- nothing is kept -- where the kernel has no
-        route for the call: the whole body then runs as under "torch"."""
-        import torch
-        from .hip import ops
-        w, scale, zp = env["W"], env["w_scale"], env["w_zero_point"]
-        packed = self._packed4.get(id(w))
-        held = list(self.constants.values())
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda and any(t is c for c in held) for t in (w, scale) + (() if zp is None else (zp,))):
-            return None
-        if plan.group_size:
-            shape = env.get("original_transposed_shape")
-            if not isinstance(shape, torch.Tensor) or shape.is_cuda or w.ndim != 2 or _ints(shape) != [w.shape[1] if packed is None else packed[1], w.shape[0]]:
-                return None
-        nodes = list(fn.node)
-        self._run([n for i, n in enumerate(nodes[:plan.product]) if i not in plan.weight_nodes], env)      # the input side, the bias
-        x, bias = env[plan.x], env[plan.bias] if plan.bias else None
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.numel() > 0 and (bias is None or (isinstance(bias, torch.Tensor) and bias.is_cuda))):
-            return None
-        if packed is not None:
-            args = dict(n=packed[1], signed=packed[2], group_size=plan.group_size, bias=bias)
-            if ops.qdq_matmul_packed4_unsupported(x, w, scale, zp, **args) is not None:
-                return None
-            env[nodes[plan.product].output[0]] = ops.qdq_matmul_packed4(x, w, scale, zp, **args)
-        elif w.ndim != 2 or ops.qdq_matmul_unsupported(x, w, scale, zp, group_size=plan.group_size, bias=bias) is not None:
-            return None
-        else:
-            env[nodes[plan.product].output[0]] = ops.qdq_matmul(x, w, scale, zp, group_size=plan.group_size, bias=bias)
-        self._run(nodes[plan.product + 1:], env)                                                            # the output side
         return tuple(env[o] for o in fn.output)
 
     # ------------------------------------------------------------------------------------------------- operators
@@ -841,20 +587,8 @@ class GraphRunner:
     # linear algebra
     def _op_MatMul(self, n, x, a, e):
         import torch
-        w = x[1]
-        if (self.matmul == "pieces" and w.ndim == 2 and w.dtype == torch.float32 and x[0].dtype == torch.float32 and x[0].is_cuda
-                and min(w.shape) >= _PIECES_MIN_WIDTH and x[0].numel() // max(1, w.shape[0]) >= _PIECES_MIN_ROWS and x[0].ndim >= 2):
-            hit = self._weight_pieces.get(id(w))
-            if hit is None and any(w is c for c in self.constants.values()):
-                from .hip import ops
-                # the pieces are a second copy of the weight (two fp16 halves): kept only while HBM has room for them and the
-                # activations of a pass; past that the product stays with torch's fp32 GEMM on the weight itself
-                free = torch.cuda.mem_get_info(w.device)[0] + torch.cuda.memory_reserved(w.device) - torch.cuda.memory_allocated(w.device)
-                hit = self._weight_pieces[id(w)] = (w, ops.matmul_prepare(w, False) if free > _PIECES_HEADROOM * w.numel() * 4 else None)
-            if hit is not None and hit[0] is w and hit[1] is not None:
-                from .hip import ops
-                return ops.matmul_pieces(x[0], hit[1])
-        return torch.matmul(x[0], w)
+        out = self._run_pieces(x[0], x[1], _PIECES_HEADROOM)
+        return torch.matmul(x[0], x[1]) if out is None else out
 
     def _op_FusedMatMul(self, n, x, a, e):                  # com.microsoft: alpha * op(A) @ op(B), the transposes on the last two axes
         import torch
@@ -1440,12 +1174,9 @@ class GraphRunner:
 
     def _op_QLinearMatMul(self, n, x, a, e):
         import torch
-        route = self._route(self._qlinear_node, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], None, False, 1.0, False,
-                                                                              decode))
-        self.qlinear_calls[route] += 1
-        if route != "torch":
-            from .hip import ops
-            return (ops.qlinear_matmul_decode if route == "decode" else ops.qlinear_matmul)(*x[:8])
+        out = self._run_qlinear(*x[:8])
+        if out is not None:
+            return out
         A = (x[0].to(torch.float32) - x[2].to(torch.float32)) * x[1]
         bz = self._per_axis(x[5].to(torch.float32), x[3], x[3].ndim - 1)
         B = (x[3].to(torch.float32) - bz) * self._per_axis(x[4], x[3], x[3].ndim - 1)
@@ -1458,13 +1189,9 @@ class GraphRunner:
         y_scale = x[7] if len(x) > 7 else None
         y_zp = x[8] if len(x) > 8 else None
         trans_b, alpha, trans_a = bool(a.get("transB", 0)), a.get("alpha", 1.0), bool(a.get("transA", 0))
-        route = self._route(self._qlinear_node, lambda decode: self._qlinear_fusable(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias, trans_b, alpha,
-                                                                              trans_a, decode))
-        self.qlinear_calls[route] += 1
-        if route != "torch":
-            from .hip import ops
-            fn = ops.qlinear_matmul_decode if route == "decode" else ops.qlinear_matmul
-            return fn(x[0], x[1], x[2], x[3], x[4], x[5], y_scale, y_zp, bias=bias, trans_b=trans_b)
+        out = self._run_qlinear(*x[:6], y_scale, y_zp, bias, trans_b, alpha, trans_a)
+        if out is not None:
+            return out
         A = (x[0].to(torch.float32) - x[2].to(torch.float32)) * x[1]
         if a.get("transA", 0):
             A = A.t()
@@ -1484,14 +1211,9 @@ class GraphRunner:
         import torch
         K, N, bits, g = a["K"], a["N"], a.get("bits", 4), a["block_size"]
         blocks = (K + g - 1) // g
-        route = self._route(_NBITS_MODES[self.matmul_nbits], lambda decode: self._nbits_fusable(x, bits, g, decode))
-        if route == "torch" and "float_zp" in self.matmul_nbits and self._nbits_fusable(x, bits, g, float_zp=True):
-            route = "float_zp"
-        self.nbits_calls[route] += 1
-        if route != "torch":
-            from .hip import ops
-            fn = {"decode": ops.matmul_nbits_decode, "fused": ops.matmul_nbits, "float_zp": ops.matmul_nbits_float_zp}[route]
-            return fn(x[0], x[1], x[2], x[3] if len(x) > 3 else None, K=K, N=N, bits=bits, block_size=g, bias=x[5] if len(x) > 5 else None)
+        out = self._run_nbits(x, K, N, bits, g)
+        if out is not None:
+            return out
         blob = x[1].reshape(N, blocks, -1).to(torch.uint8)
         if bits == 4:
             q = torch.stack([blob & 0x0F, blob >> 4], dim=-1).reshape(N, blocks, g)
@@ -1520,137 +1242,12 @@ class GraphRunner:
             out = out + x[5]
         return out
 
-    @staticmethod
-    def _route(mode, fusable) -> str:
-        """Which route takes a MatMulNBits / QLinearMatMul / QGemm node under ``mode``: "decode", "fused" or "torch", the keys of the
-        call counters.  ``fusable(decode)``: whether the decode / the tile kernel takes the node."""
-        if mode == "fused+decode" and fusable(True):
-            return "decode"
-        if mode in ("fused", "fused+decode") and fusable(False):
-            return "fused"
-        return "torch"
-
-    def _nbits_fusable(self, x, bits, g, decode: bool = False, float_zp: bool = False) -> bool:
-        """Whether `ops.matmul_nbits` (``decode``: `ops.matmul_nbits_decode`, which also wants at most 16 rows of A; ``float_zp``:
-        `ops.matmul_nbits_float_zp`, which wants floating-point zero points) takes this MatMulNBits node: what the kernel supports,
-        on the GPU, with B, scales and zero points constants of the model as the writer stores them."""
-        import torch
-        from .hip import ops
-        zp = x[3] if len(x) > 3 else None
-        g_idx = x[4] if len(x) > 4 else None
-        bias = x[5] if len(x) > 5 else None
-        if not (isinstance(x[0], torch.Tensor) and x[0].is_cuda and x[0].ndim >= 1 and x[0].numel() > 0):
-            return False
-        if decode:
-            rows = x[0].numel() // x[0].shape[-1] if x[0].shape[-1] else 0
-            if ops.matmul_nbits_decode_unsupported(x[0].dtype, bits, g, zp, g_idx, rows=rows) is not None:
-                return False
-        elif float_zp:
-            if ops.matmul_nbits_float_zp_unsupported(x[0].dtype, bits, g, zp, g_idx) is not None:
-                return False
-        elif ops.matmul_nbits_unsupported(x[0].dtype, bits, g, zp, g_idx) is not None:
-            return False
-        held = list(self.constants.values())
-        if not all(t is None or (t.is_cuda and any(t is c for c in held)) for t in (x[1], x[2], zp)):
-            return False
-        zp_types = (torch.uint8, torch.float32, x[0].dtype) if decode else (torch.float32, x[0].dtype) if float_zp else (torch.uint8,)
-        return (x[1].dtype == torch.uint8 and x[2].dtype in (torch.float32, x[0].dtype) and (zp is None or zp.dtype in zp_types)
-                and (bias is None or (bias.is_cuda and bias.dtype == x[0].dtype)))
-
-    def _qlinear_fusable(self, A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias, trans_b, alpha, trans_a, decode: bool = False) -> bool:
-        """Whether `ops.qlinear_matmul` (``decode``: `ops.qlinear_matmul_decode`, which also wants at most 16 rows of A) takes this
-        QLinearMatMul / QGemm node: A an 8-bit tensor on the GPU, every parameter a tensor on the GPU, B, its parameters and C
-        constants of the model, and nothing the kernel leaves out."""
-        import torch
-        from .hip import ops
-        if not (isinstance(A, torch.Tensor) and A.is_cuda and A.dtype in (torch.uint8, torch.int8) and A.ndim >= 1 and A.numel() > 0):
-            return False
-        every = (a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias)
-        if a_scale is None or B is None or b_scale is None or not all(t is None or (isinstance(t, torch.Tensor) and t.is_cuda) for t in every):
-            return False
-        held = list(self.constants.values())
-        if not all(t is None or any(t is c for c in held) for t in (B, b_scale, b_zp, bias)):
-            return False
-        unsupported = ops.qlinear_matmul_decode_unsupported if decode else ops.qlinear_matmul_unsupported
-        return unsupported(A, a_scale, a_zp, B, b_scale, b_zp, y_scale, y_zp, bias=bias, trans_b=trans_b, alpha=alpha, trans_a=trans_a) is None
-
-
-# `matmul_nbits` -> how `_route` reads it: the float-zp modes are "fused" / "fused+decode" plus a route of their own for what those leave
-_NBITS_MODES = {"torch": "torch", "fused": "fused", "fused+decode": "fused+decode", "fused+float_zp": "fused", "fused+float_zp+decode": "fused+decode"}
-
-# `qlinear` -> how a bare QLinearMatMul / QGemm node is routed (`_route`): the function modes leave it to "fused" / "fused+decode"
-_QLINEAR_NODE_MODE = {"torch": "torch", "fused": "fused", "fused+decode": "fused+decode", "function": "fused", "function+decode": "fused+decode"}
-
-
-def _qlinear_function_named(fn) -> bool:
-    """`fn` carries the name of a QLinear function of the `quant` domain (onnx_functions._qlinear_function)."""
-    from .onnx_functions import QUANT_DOMAIN
-    return (fn.domain or "") == QUANT_DOMAIN and fn.name in ("QLinearMatMul", "QLinearGemm")
-
 
 _CAPTURE_MAX_INPUT_ELEMENTS = 1 << 20     # recording pays when a pass is hundreds of small launches (one short sequence), not above
-_PIECES_MIN_WIDTH, _PIECES_MIN_ROWS = 512, 256
 _PIECES_HEADROOM = 8                      # free HBM, in sizes of the weight, below which its fp16 pieces are not kept
 _SCALAR_FRIENDLY = {"Add", "Sub", "Mul", "Div", "Pow"}
 _HOST_OPERANDS = {"GroupQueryAttention", "RotaryEmbedding", "CumSum", "Reshape", "Expand", "Slice", "Tile", "Unsqueeze", "Squeeze", "Split",
                   "ConstantOfShape", "Gather", "Trilu", "ReduceMean", "ReduceSum", "ReduceMax", "ReduceMin", "Range", "Clip", "Pad", "Resize", "TopK", "OneHot"}
-
-
-class _QdqPlan:
-    """How a `quant`-domain QDQ function (onnx_functions.py) is run with its product fused: which nodes of the body dequantize W
-    (left out), which one is the product (replaced), and what the product reads."""
-
-    def __init__(self, weight_nodes, product, x, bias, group_size):
-        self.weight_nodes, self.product, self.x, self.bias, self.group_size = weight_nodes, product, x, bias, group_size
-
-    @staticmethod
-    def _shape(fn):
-        """What is compared: inputs, outputs, and per node its operator, domain, wiring and attributes."""
-        return (list(fn.input), list(fn.output),
-                [(n.op_type, n.domain or "", list(n.input), list(n.output), sorted((a.name, repr(attribute_value(a))) for a in n.attribute))
-                 for n in fn.node])
-
-    @staticmethod
-    def named(fn) -> bool:
-        """`fn` carries the name of a QDQ function of the `quant` domain."""
-        from .onnx_functions import _QDQ, QUANT_DOMAIN
-        return (fn.domain or "") == QUANT_DOMAIN and (fn.name in _QDQ or fn.name in ("QMatMulWeightsOnlyGrouped", "QGemmWeightsOnlyGrouped"))
-
-    @classmethod
-    def input_mode(cls, fn):
-        """`fn` carries the name of a QDQ function with an input Q -> DQ: "static" / "dynamic", else None."""
-        from .onnx_functions import _QDQ, QUANT_DOMAIN
-        return _QDQ[fn.name][1][0] if (fn.domain or "") == QUANT_DOMAIN and fn.name in _QDQ else None
-
-    @classmethod
-    def of(cls, fn):
-        from .onnx_functions import _QDQ, build_function
-        if not cls.named(fn):
-            return None
-        nodes = list(fn.node)
-        if fn.name in _QDQ:
-            expected, group_size = build_function(fn.name), 0
-        elif fn.name in ("QMatMulWeightsOnlyGrouped", "QGemmWeightsOnlyGrouped"):
-            blocked = [n for n in nodes if n.op_type == "DequantizeLinear" and any(a.name == "block_size" for a in n.attribute)]
-            if len(blocked) != 1:
-                return None
-            group_size = int(attribute_value(next(a for a in blocked[0].attribute if a.name == "block_size")))
-            if group_size <= 0:
-                return None
-            expected = build_function(fn.name, group_size=group_size, four_bit=bool(nodes) and nodes[0].op_type == "Cast")
-        else:
-            return None
-        if cls._shape(fn) != cls._shape(expected):
-            return None
-        product = next(i for i, n in enumerate(nodes) if n.op_type in ("MatMul", "Gemm"))
-        node = nodes[product]
-        # the nodes between W and `dequantized_weights`: everything the product's second operand depends on
-        needed, weight_nodes = {node.input[1]}, set()
-        for i in range(product - 1, -1, -1):
-            if any(o in needed for o in nodes[i].output):
-                weight_nodes.add(i)
-                needed.update(name for name in nodes[i].input if name)
-        return cls(weight_nodes, product, node.input[0], node.input[2] if len(node.input) > 2 else None, group_size)
 
 
 class _Attrs:
