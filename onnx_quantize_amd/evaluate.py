@@ -75,7 +75,8 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     ``"fused"`` with every 4-bit weight of such a function held as the file's packed nibbles (`ops.qdq_matmul_packed4`: half the
     memory and half the weight read; the same bytes of output, so the same perplexity).  ``qdq="fused+integer+packed4"`` is the
     two together: the calls with an input Q -> DQ read the packed nibbles on the int8 matrix cores (`ops.qdq_function_packed4`: the
-    bytes of ``"fused+integer"``)."""
+    bytes of ``"fused+integer"``).  ``qdq="fused+integer+packed4+decode"`` sends those of them whose flattened input has at most 16
+    rows to `ops.qdq_function_packed4_decode` (the nibbles streamed once; the same bytes, so the same perplexity)."""
     import torch
 
     from .graph_runner import GraphRunner

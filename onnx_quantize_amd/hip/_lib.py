@@ -57,6 +57,8 @@ OQ_QDQ_FUNCTION_EXTENSION_VERSION = 1
 OQ_QDQ_PACKED4_EXTENSION_VERSION = 1
 # include/oq_hip_qdq_function_packed4.h (the codes of oq_hip_qdq_function.h, with OQ_UINT4 / OQ_INT4 for W)
 OQ_QDQ_FUNCTION_PACKED4_EXTENSION_VERSION = 1
+# include/oq_hip_qdq_function_packed4_decode.h (the codes of oq_hip_qdq_function_packed4.h)
+OQ_QDQ_FUNCTION_PACKED4_DECODE_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -261,6 +263,14 @@ QDQ_FUNCTION_PACKED4_PROTOTYPES = {
     "oq_qdq_function_packed4": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function"],
 }
 
+# ... its decode route (M <= 16): mirrors include/oq_hip_qdq_function_packed4_decode.h one to one
+# (tests/test_qdq_function_packed4_decode_abi.py checks the set).  The argument list of oq_qdq_function_packed4.
+QDQ_FUNCTION_PACKED4_DECODE_PROTOTYPES = {
+    "oq_qdq_function_packed4_decode_extension_version": (_i32, []),
+    "oq_qdq_function_packed4_decode_workspace_bytes": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function_workspace_bytes"],
+    "oq_qdq_function_packed4_decode": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function"],
+}
+
 # what `load` binds and pins: (prototypes, the function that reports the version, the version this package expects, what the
 # message calls it)
 EXTENSIONS = [
@@ -277,6 +287,8 @@ EXTENSIONS = [
     (QDQ_PACKED4_PROTOTYPES, "oq_qdq_packed4_extension_version", OQ_QDQ_PACKED4_EXTENSION_VERSION, "QDQ packed-nibble extension"),
     (QDQ_FUNCTION_PACKED4_PROTOTYPES, "oq_qdq_function_packed4_extension_version", OQ_QDQ_FUNCTION_PACKED4_EXTENSION_VERSION,
      "QDQ function packed-nibble extension"),
+    (QDQ_FUNCTION_PACKED4_DECODE_PROTOTYPES, "oq_qdq_function_packed4_decode_extension_version", OQ_QDQ_FUNCTION_PACKED4_DECODE_EXTENSION_VERSION,
+     "QDQ function packed-nibble decode extension"),
 ]
 
 _lock = threading.Lock()

@@ -1895,19 +1895,22 @@ def qdq_function(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, w_zero
                               x_zero_point, out_mode, out_scale, out_zero_point, bias)
 
 
-def _qdq_function_on_device(x, w, w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, bias) -> None:
+def _qdq_function_on_device(x, w, w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, bias, current: int | None = None) -> None:
+    """``current``: the current device where the caller has asked for it once (the decode route); `_require_device` then only words the refusal."""
     b, b_scale, b_zp = bias if bias is not None else (None, None, None)
     named = dict(x=x, w=w, w_scale=w_scale, w_zero_point=w_zero_point, x_scale=x_scale, x_zero_point=x_zero_point, out_scale=out_scale,
                  out_zero_point=out_zero_point, B=b, b_scale=b_scale, b_zero_point=b_zp)
     for name, t in named.items():
-        if t is not None:
+        if t is not None and not (current is not None and isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == current):
             _require_device(t, name)
 
 
 def _qdq_function_call(entry: str, x, w, wtype: int, k: int, n: int, w_scale, w_zero_point, x_mode, x_scale, x_zero_point, out_mode, out_scale,
-                       out_zero_point, bias) -> torch.Tensor:
-    """The call of `oq_qdq_function` / `oq_qdq_function_packed4` (one argument list) after its front has vouched for the operands:
-    ``w`` the byte matrix either of them reads, ``n`` the columns of the [K, N] weight it holds."""
+                       out_zero_point, bias, remembered: dict | None = None, current: int | None = None) -> torch.Tensor:
+    """The call of `oq_qdq_function` / `oq_qdq_function_packed4[_decode]` (one argument list) after its front has vouched for the
+    operands: ``w`` the byte matrix either of them reads, ``n`` the columns of the [K, N] weight it holds.  ``remembered``: a call made
+    per token -- the workspace size is kept there per request, the stream handle of device ``current`` taken raw, and no workspace is
+    made where none is needed (`_decode_route`)."""
     b, b_scale, b_zp = bias if bias is not None else (None, None, None)
     rows = _rows_and_out(x.reshape(-1, k), n, torch.float32)
     if rows is None:
@@ -1923,12 +1926,19 @@ def _qdq_function_call(entry: str, x, w, wtype: int, k: int, n: int, w_scale, w_
     x_code, out_code = _QDQ_MODE[x_mode], _QDQ_MODE[out_mode]
     type_of = lambda zp: _QL_TYPE[torch.uint8 if zp is None else zp.dtype]      # noqa: E731
     lib = L.load()
-    need = getattr(lib, entry + "_workspace_bytes")(m, k, n, x_code, out_code)
-    ws = _workspace(need, x.device)
+    if remembered is None:
+        need, stream = getattr(lib, entry + "_workspace_bytes")(m, k, n, x_code, out_code), _stream()
+        ws = _workspace(need, x.device)
+    else:
+        key = (m, k, n, x_code, out_code)
+        need = remembered.get(key)
+        if need is None:
+            need = remembered[key] = getattr(lib, entry + "_workspace_bytes")(*key)
+        stream, ws = C.c_void_p(_raw_stream(current)), _workspace(need, x.device) if need else None
     L.check(getattr(lib, entry)(_ptr(x2), L.OQ_NBITS_F32, m, k, lda, x_code, type_of(x_zero_point), _ptr(x_scale), _ptr(x_zero_point), _ptr(w),
                                 wtype, n, ldw, L.OQ_CHANNEL if per_column else L.OQ_TENSOR, 0, _ptr(w_scale), _ptr(w_zero_point),
                                 _ptr(b), _ptr(b_scale), _ptr(b_zp), out_code, type_of(out_zero_point), _ptr(out_scale), _ptr(out_zero_point),
-                                _ptr(out), n, _ptr(ws), need, _stream()))
+                                _ptr(out), n, _ptr(ws), need, stream))
     return out.reshape(*x.shape[:-1], n)
 
 
@@ -1973,6 +1983,49 @@ def qdq_function_packed4(x: torch.Tensor, w_packed: torch.Tensor, w_scale: torch
         w_packed = w_packed[:, :n // 2]
     return _qdq_function_call("oq_qdq_function_packed4", x, w_packed, L.OQ_INT4 if signed else L.OQ_UINT4, int(w_packed.shape[0]), int(n), w_scale,
                               w_zero_point, x_mode, x_scale, x_zero_point, out_mode, out_scale, out_zero_point, bias)
+
+
+QDQ_FUNCTION_PACKED4_DECODE_MAX_ROWS = 16      # include/oq_hip_qdq_function_packed4_decode.h: M of the decode route
+_QDQ_FUNCTION_PACKED4_DECODE_WORKSPACE: dict = {}      # (M, K, N, x_mode, out_mode) -> oq_qdq_function_packed4_decode_workspace_bytes
+
+
+def qdq_function_packed4_decode_unsupported(x, w_packed, w_scale, w_zero_point=None, *, n: int, signed: bool, x_mode, x_scale=None,
+                                            x_zero_point=None, out_mode=None, out_scale=None, out_zero_point=None, bias=None) -> str | None:
+    """Why `qdq_function_packed4_decode` has no kernel for such a call (include/oq_hip_qdq_function_packed4_decode.h), or None when it
+    has one: what `qdq_function_packed4_unsupported` names, and more than 16 rows of the flattened ``x``."""
+    why = qdq_function_packed4_unsupported(x, w_packed, w_scale, w_zero_point, n=n, signed=signed, x_mode=x_mode, x_scale=x_scale,
+                                           x_zero_point=x_zero_point, out_mode=out_mode, out_scale=out_scale, out_zero_point=out_zero_point, bias=bias)
+    if why is not None:
+        return why
+    rows = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    if rows > QDQ_FUNCTION_PACKED4_DECODE_MAX_ROWS:
+        return f"{rows} rows (the decode route takes 1 ... {QDQ_FUNCTION_PACKED4_DECODE_MAX_ROWS}; qdq_function_packed4 takes the rest)"
+    return None
+
+
+def qdq_function_packed4_decode(x: torch.Tensor, w_packed: torch.Tensor, w_scale: torch.Tensor, w_zero_point: torch.Tensor | None = None, *, n: int,
+                                signed: bool, x_mode: str, x_scale: torch.Tensor | None = None, x_zero_point: torch.Tensor | None = None,
+                                out_mode: str | None = None, out_scale: torch.Tensor | None = None, out_zero_point: torch.Tensor | None = None,
+                                bias=None) -> torch.Tensor:
+    """The decode route of `qdq_function_packed4` (`oq_qdq_function_packed4_decode`, csrc/qdq_function_packed4_decode.hip): the same
+    operands, for an ``x`` whose ``reshape(-1, K)`` has 1 ... 16 rows.  The packed nibbles are streamed once from global memory into
+    the registers of the int8 matrix instruction; each workgroup quantizes its slice of ``x`` on the way into LDS and the column
+    sums come from the same registers, so a static call is at most two launches.  The bytes of `qdq_function_packed4`.
+    Deterministic; nothing synchronises with the host.
+
+    NotImplementedError, naming the reason: more than 16 rows, and what `qdq_function_packed4` refuses."""
+    current = torch.cuda.current_device() if torch.cuda.is_available() else -1
+    _qdq_function_on_device(x, w_packed, w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, bias, current)
+    why = qdq_function_packed4_decode_unsupported(x, w_packed, w_scale, w_zero_point, n=n, signed=signed, x_mode=x_mode, x_scale=x_scale,
+                                                  x_zero_point=x_zero_point, out_mode=out_mode, out_scale=out_scale, out_zero_point=out_zero_point,
+                                                  bias=bias)
+    if why is not None:
+        raise NotImplementedError(f"qdq_function_packed4_decode: {why}")
+    if w_packed.shape[1] > n // 2 and w_packed.stride(1) == 1:      # the columns that hold the N values; the row stride stays
+        w_packed = w_packed[:, :n // 2]
+    return _qdq_function_call("oq_qdq_function_packed4_decode", x, w_packed, L.OQ_INT4 if signed else L.OQ_UINT4, int(w_packed.shape[0]), int(n),
+                              w_scale, w_zero_point, x_mode, x_scale, x_zero_point, out_mode, out_scale, out_zero_point, bias,
+                              remembered=_QDQ_FUNCTION_PACKED4_DECODE_WORKSPACE, current=current)
 
 
 # ----------------------------------------------------------------------------- G1 - G4
