@@ -75,6 +75,13 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // MatMulNBits blob does NOT: its 16-byte pieces meet their neighbours (other k-groups: other waves) in the L2, written through they
 // are a fabric write each (38.3-38.4 -> 38.5-38.7 us): the blob keeps plain stores.
 __device__ __forceinline__ void store_sc1(uint32_t w, uint32_t* p) { asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(w) : "memory"); }
+// 16 bytes of a whole 128-byte line of the pair build's blob (wave-uniform base + 32-bit byte offset), written through like the
+// [K,N] results above: eight neighbouring lanes complete a line, so nothing waits in the L2 for a neighbour.  Same box, alternating,
+// 4096 x 11008, four-wave build 39.71-40.01 us: whole lines with plain stores 39.85-40.42, written through 38.73-39.01
+// (docs/LAB_NOTES_r44.md).
+__device__ __forceinline__ void store_line_sc1(u32x4 v, uint8_t* base, uint32_t off) {
+    asm volatile("global_store_dwordx4 %0, %1, %2 sc1" : : "v"(off), "v"(v), "s"(base) : "memory");
+}
 
 // K1's fast path is proven row group by row group: kDecisionRows rows share ONE decision (a running v_maximum3_f32 of the
 // residuals against the narrowest band, then one ballot) instead of a compare and a scalar OR per element and a ballot + branch
@@ -635,15 +642,35 @@ __global__ __launch_bounds__(kMaxWaves* kWave) void rtn_group_fused(const RtnArg
 // butterflies: no LDS, no barrier, waves never wait for each other.  In the blob a lane's 16 rows
 // of a column are 8 (4-bit) / 16 (8-bit) consecutive bytes and the lane sets of a column are
 // adjacent, so one store instruction writes whole 64 / 128-byte chunks.  G = 128 for LPR = 8.
+//
+// PAIR (4-bit, G = 128, WPS > 0): a block is eight waves, TWO neighbouring k-groups x four strips -- wave w takes k-group
+// 2 * row_tile + (w >> 2) and strip w & 3.  In the blob the 64 bytes of a column's k-groups 2p and 2p + 1 are ONE 128-byte line: the
+// waves leave their finished nibbles (and the scales and zero points) in LDS, meet at one barrier, and every store instruction
+// then writes eight whole lines.  Loads, ranges, parameters and K1 are the code of the four-wave build.
+//   The barrier and the edge: no wave of a PAIR block returns before the barrier.  A block exists for every (row tile, column tile),
+//   so its first strip starts inside the matrix and both its k-groups exist (the host takes this build for an even K / g only).  A
+//   wave whose own strip starts at or past N reads the block's FIRST strip instead (all its lanes at the clamped last four columns,
+//   like any lane past the right edge), runs the same instructions on it and leaves bytes in its own LDS slots that nobody
+//   stores: every store after the barrier is guarded by its column < N.  So all eight waves arrive exactly once, whatever N is.
 // ---------------------------------------------------------------------------------------------
-template <int LPR, bool EMIT_Q, int WPS = 0>
-__global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void rtn_group_wave(const RtnArgs a_in) {
+// The body of both kernels (`rtn_group_wave`, `rtn_group_wave_pair` below it).
+template <int LPR, bool EMIT_Q, int WPS, bool PAIR>
+__device__ __forceinline__ void wave_body(const RtnArgs& a_in) {
+    static_assert(!PAIR || (LPR == 8 && WPS > 0 && EMIT_Q), "the pair build is the 4-bit, 128-row, five-waves-per-SIMD build");
     constexpr int RS = 64 / LPR;  // lane sets (row sub-ranges) per wave
     constexpr int G = 16 * RS;    // rows per group
+    constexpr int NW = PAIR ? 2 * kWaveStrips : kWaveStrips;   // waves per block
     // WPS > 0: built for WPS waves per SIMD (blocks of <= 4 waves).  The four scales of a lane are only needed again by
     // the rare exact-division fallback: they are parked in LDS (4 * LPR floats per wave, written and read by the same wave:
     // no barrier) instead of four registers, which is what separates 100 registers from the 96 that five waves allow.
-    __shared__ float s_scale[WPS ? 4 : 1][WPS ? 4 * LPR : 1];
+    // PAIR: the same slots are also where the block's parameter stores come from after the barrier, next to the zero points.
+    __shared__ float s_scale[WPS ? NW : 1][WPS ? 4 * LPR : 1];
+    __shared__ uint8_t s_zp[PAIR ? NW : 1][PAIR ? 4 * LPR : 1];
+    // PAIR: the block's 128 lines x 128 B.  Line C (column C of the tile) is eight 16-byte units, unit U = 4 * (k-group of the
+    // pair) + (h >> 1), kept at s_line[C * 8 + (U ^ ((C >> 2) & 7))].  Writing, eight neighbouring lanes (one h, cl = 0 .. 7)
+    // hold columns 4 apart -- (C >> 2) & 7 = cl -- and one U: eight different units of a 128-byte bank row.  Reading, eight
+    // neighbouring lanes hold one line and U = 0 .. 7: eight different units again.  Neither side has a bank conflict.
+    __shared__ u32x4 s_line[PAIR ? 128 * 8 : 1];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // provably wave-uniform: scalar address math below
     const int h = lane / LPR, cl = lane % LPR;
@@ -666,9 +693,13 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
 
     // block = one k-group x kWaveStrips strips of 4 * LPR columns; neighbouring strips on neighbouring waves
     // (the tile ids come out of a float division: readfirstlane keeps what follows from them in scalar registers)
-    const int64_t kg = __builtin_amdgcn_readfirstlane(row_tile);
-    const int64_t strip0 = (static_cast<int64_t>(__builtin_amdgcn_readfirstlane(col_tile)) * kWaveStrips + wave) * (4 * LPR);
-    if (kg >= a.kgroups || strip0 >= a.N) return;  // wave-uniform; nothing below synchronises
+    const int64_t kg = PAIR ? 2 * static_cast<int64_t>(__builtin_amdgcn_readfirstlane(row_tile)) + (wave >> 2) : __builtin_amdgcn_readfirstlane(row_tile);
+    const int64_t tile_col0 = static_cast<int64_t>(__builtin_amdgcn_readfirstlane(col_tile)) * kWaveStrips * (4 * LPR);
+    const int64_t strip0 = tile_col0 + (PAIR ? wave & 3 : wave) * (4 * LPR);
+    if constexpr (!PAIR) {
+        if (kg >= a.kgroups || strip0 >= a.N) return;  // wave-uniform; nothing below synchronises
+    }
+    const int64_t strip_ld = PAIR && strip0 >= a.N ? tile_col0 : strip0;   // PAIR: a wave past the edge reads the first strip (see above)
     // WPS > 0: 32-bit output indices (the host checks N * K/g * G/2 < 2^32): scalar base + 32-bit lane offset addressing
     // instead of 64-bit address pairs held across the kernel
     using idx_t = std::conditional_t<(WPS > 0), uint32_t, int64_t>;
@@ -680,8 +711,8 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
     {
         // scalar row base + one 32-bit lane offset for all 16 loads (host guarantees 112 * ldw * 4 + 4 * N < 2^32);
         // lanes past the right edge read a clamped address, never a predicated load
-        const char* base = reinterpret_cast<const char*>(a.W + kg * G * a.ldw + strip0);
-        const uint32_t loff = static_cast<uint32_t>(h * 16 * a.ldw + (col_ok ? cl * 4 : a.N - 4 - strip0)) * 4u;
+        const char* base = reinterpret_cast<const char*>(a.W + kg * G * a.ldw + strip_ld);
+        const uint32_t loff = static_cast<uint32_t>(h * 16 * a.ldw + (col_ok ? cl * 4 : a.N - 4 - strip_ld)) * 4u;
         const int64_t row_bytes = a.ldw * 4;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -734,7 +765,9 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
         const ColQ c = make_colq(qparam_from_minmax(mnj, mxj, a.grid), mnj, mxj, bias);
         own_scale = c.scale;
         if (h < 4) s_scale[wave][j * LPR + cl] = c.scale;      // for the fallback: slot i of strip column cl at [i * LPR + cl]
-        if (h < 4 && col_ok) {   // rtn.py:98-109 result layout (entry n * K/g + kg); lane set j stores column slot j
+        if constexpr (PAIR) {    // stored after the barrier, two k-groups at a time
+            if (h < 4) s_zp[wave][j * LPR + cl] = static_cast<uint8_t>(static_cast<int32_t>(c.zpb) - bias);
+        } else if (h < 4 && col_ok) {   // rtn.py:98-109 result layout (entry n * K/g + kg); lane set j stores column slot j
             const idx_t o = (c0 + j) * kgroups_i + kg_i;
             a.scale[o] = c.scale;
             a.zp[o] = static_cast<uint8_t>(static_cast<int32_t>(c.zpb) - bias);
@@ -835,13 +868,13 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[rg + r][i] = f[r][i];
         }
-        if (!col_ok) return;
+        if (!PAIR && !col_ok) return;
         // qrules/_common.py:72-87: out-channel n, k-group kg -> G * bits / 8 bytes, k ascending, even k in the low nibble.
         // v[r][i] holds M + level: the level is byte 0 of its bits (the other three bytes are those of M).
         auto low_bytes = [](uint32_t b0, uint32_t b1, uint32_t b2, uint32_t b3) {   // [b0.0, b1.0, b2.0, b3.0]
             return __builtin_amdgcn_perm(b1, b0, 0x0c0c0400u) | __builtin_amdgcn_perm(b3, b2, 0x04000c0cu);
         };
-        if (a.grid.bits == 4 && LPR == 8) {
+        if (PAIR || (a.grid.bits == 4 && LPR == 8)) {
             // 16-byte stores: the lane sets 2m and 2m + 1 of a 16-lane DPP row hold neighbouring 8-byte pieces of every
             // column slot.  The even set takes its partner's pieces of slots 0 and 1, the odd set its partner's pieces of
             // slots 2 and 3 (one row_ror:8 per dword), and every lane issues TWO 16-byte stores instead of four 8-byte ones.
@@ -866,9 +899,44 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
                 const uint32_t r0 = swap8(s0), r1 = swap8(s1);
                 const uint32_t m0 = odd ? wq[2 + t][0] : wq[t][0], m1 = odd ? wq[2 + t][1] : wq[t][1];
                 const u32x4 val = odd ? u32x4{r0, r1, m0, m1} : u32x4{m0, m1, r0, r1};
-                const idx_t col = c0 + (odd ? 2 + t : t);
-                u32x4* o = reinterpret_cast<u32x4*>(a.q + ((col * kgroups_i + kg_i) * (G / 2) + (h & ~1) * 8));
-                *o = val;
+                if constexpr (PAIR) {
+                    const int C = (wave & 3) * (4 * LPR) + cl * 4 + (odd ? 2 + t : t);
+                    s_line[C * 8 + (((wave >> 2) * 4 + (h >> 1)) ^ cl)] = val;
+                } else {
+                    const idx_t col = c0 + (odd ? 2 + t : t);
+                    u32x4* o = reinterpret_cast<u32x4*>(a.q + ((col * kgroups_i + kg_i) * (G / 2) + (h & ~1) * 8));
+                    *o = val;
+                }
+            }
+            if constexpr (PAIR) {
+                __syncthreads();   // reached by all eight waves, once (see the kernel's header)
+                const idx_t tile_c = static_cast<idx_t>(tile_col0), kg0 = kg_i & ~static_cast<idx_t>(1);
+#pragma unroll
+                for (int it = 0; it < 2; ++it) {   // a wave stores 16 of the 128 lines, eight per instruction, 16 B per lane
+                    const int C = wave * 16 + it * 8 + (lane >> 3), U = lane & 7;
+                    const u32x4 val = s_line[C * 8 + (U ^ ((C >> 2) & 7))];
+                    if (tile_c + C < static_cast<idx_t>(a.N)) store_line_sc1(val, a.q, ((tile_c + C) * kgroups_i + kg0) * (G / 2) + U * 16);
+                }
+                // the 128 columns' (scale, zero point) of both k-groups: entries o and o + 1 of the n-major arrays, o even
+                const int C = threadIdx.x;
+                if (C < 128 && tile_c + C < static_cast<idx_t>(a.N)) {
+                    const int strip = C >> 5, slot = (C & 3) * LPR + ((C >> 2) & 7);
+                    const idx_t o = (tile_c + C) * kgroups_i + kg0;
+                    const float s0 = s_scale[strip][slot], s1 = s_scale[4 + strip][slot];
+                    const uint32_t z0 = s_zp[strip][slot], z1 = s_zp[4 + strip][slot];
+                    if ((reinterpret_cast<uintptr_t>(a.scale) & 7u) == 0) {
+                        *reinterpret_cast<float2*>(a.scale + o) = make_float2(s0, s1);
+                    } else {
+                        a.scale[o] = s0;
+                        a.scale[o + 1] = s1;
+                    }
+                    if ((reinterpret_cast<uintptr_t>(a.zp) & 1u) == 0) {
+                        *reinterpret_cast<uint16_t*>(a.zp + o) = static_cast<uint16_t>(z0 | (z1 << 8));
+                    } else {
+                        a.zp[o] = static_cast<uint8_t>(z0);
+                        a.zp[o + 1] = static_cast<uint8_t>(z1);
+                    }
+                }
             }
         } else if (a.grid.bits == 4) {
             const uint32_t flip = bias ? 0x88888888u : 0u;
@@ -961,6 +1029,14 @@ __global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void r
         }
     }
 }
+
+template <int LPR, bool EMIT_Q, int WPS = 0>
+__global__ __launch_bounds__(WPS ? 256 : kMaxWaves* kWave, WPS ? WPS : 1) void rtn_group_wave(const RtnArgs a) {
+    wave_body<LPR, EMIT_Q, WPS, false>(a);
+}
+
+// the pair build: eight waves, compiled for the same five waves per SIMD
+__global__ __launch_bounds__(2 * kWaveStrips * kWave, 5) void rtn_group_wave_pair(const RtnArgs a) { wave_body<8, true, 5, true>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // Two-pass path (channel, tensor, groups too tall for registers).  Pass 1: per (row chunk, column)
@@ -1592,11 +1668,20 @@ static int32_t launch_wave(const RtnCall& c, const RtnShape& sh, hipStream_t s) 
     int tile_log2 = 6;                                                              // 64 * lpr bytes: four strips of 4 * lpr columns
     for (int l = lpr; l > 1; l >>= 1) ++tile_log2;
     a.xg_log2 = static_cast<uint32_t>(want_log2 > tile_log2 ? want_log2 - tile_log2 : 0);
-    set_block_order(a);
-    const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(c.batch)), block(kWaveStrips * kWave);
     // the 5-waves-per-SIMD build addresses its outputs with 32-bit offsets; g = 32 (two lane sets) does not fit its 96
     // registers.  Everything else runs the plain build.
     const bool small_idx = static_cast<uint64_t>(c.N) * static_cast<uint64_t>(c.K) * static_cast<uint64_t>(sh.grid.bits) / 8u < (1ull << 32);
+    // 4-bit groups of 128 rows, an even number of them: blocks of two neighbouring k-groups (eight waves) that store whole
+    // 128-byte lines of the blob.  A row tile is two k-groups; gk stays 4, eight k-groups a chunk (4096 x 11008, lines written
+    // through: gk = 2 38.94-39.90 us, gk = 4 38.73-39.01).  An odd K / g keeps the four-wave build.
+    const bool pair = small_idx && lpr == 8 && sh.grid.bits == 4 && sh.kgroups % 2 == 0;
+    if (pair) a.nrow_tiles = static_cast<uint32_t>(sh.kgroups / 2);
+    set_block_order(a);
+    const dim3 grid_dim(a.ncol_tiles * a.nrow_tiles, static_cast<uint32_t>(c.batch)), block((pair ? 2 : 1) * kWaveStrips * kWave);
+    if (pair) {
+        hipLaunchKernelGGL(rtn_group_wave_pair, grid_dim, block, 0, s, a);
+        return check_launch("rtn_group_wave_pair");
+    }
     if (small_idx && lpr <= 16) {
         if (lpr == 8) hipLaunchKernelGGL((rtn_group_wave<8, true, 5>), grid_dim, block, 0, s, a);
         else hipLaunchKernelGGL((rtn_group_wave<16, true, 5>), grid_dim, block, 0, s, a);
