@@ -5,7 +5,11 @@
 //        so the row sums, the products and the LDS footprint, are those of the byte route.
 //   DQ   the epilogue ends in Y = (fp32(q) - fp32(y_zp)) * y_scale as fp32 instead of the 8-bit q (finish_acc).
 // qlinear_decode.hip keeps its own text and does NOT include this file: wrapped around these bodies with the flags off, 18 of its 19
-// kernels compile to another order of instructions and other register numbers (docs/LAB_NOTES_r32.md, section 1), and
+// kernels compile to another order of instructions and other register numbers (docs/LAB_NOTES_r32.md, section 1), and the wrapped
+// ql_decode_kn_kernel of the 4- and 16-row tiers is slower: scripts/time_qlinear_decode.py, replayed, B [K, N], M = 4 at 4096 x 11008
+// and 11008 x 4096, M = 16 at 11008 x 4096 and 4096 x 4096, 1.5 - 3.4 % above the parent in two measurements out of two
+// (docs/LAB_NOTES_r45.md, section 4; the same registers and LDS, 6 - 12 % more code).  The flags are not the cause: the wrapper
+// compiles to the same code with a plain emit in the place of emit<DQ> (section 3 there).
 // scripts/compare_kernel_asm.py holds that file to its text.  So the argument struct, the bodies and the plan's workspace piece
 // below are a copy; the guarded loads, the quantizer, the epilogue (qlinear_epilogue.hpp), the plan (qlinear_decode_plan.hpp) and the
 // butterfly (lanes_reduce.hpp) are the one shared text.  The flags stay template arguments although this file's one user sets both:

@@ -7,8 +7,11 @@
 //                    per column, the output Q -> DQ, and for a dynamic output one (min, max) of the workgroup's valid elements.
 // qlinear_gemm.hip keeps its own text and does NOT include this file: wrapped around these bodies with the flag off, six of its seven
 // kernels -- the twenty lines of ql_sum_rows_kernel included -- compile to another order of instructions and other register numbers
-// (docs/LAB_NOTES_r32.md, section 1), and scripts/compare_kernel_asm.py holds that file to its text.  So the argument struct, the
-// bodies and the workspace layout below are a copy, as qdq_matmul.hip's kernel is one of matmul_nbits.hip's; the guarded loads, the
+// (docs/LAB_NOTES_r32.md, section 1), and the wrapped ql_gemm_kernel<4, KN> is slower: scripts/time_qlinear_matmul.py at M = 2048, B
+// [K, N], 4096 x 11008 / 11008 x 4096 / 4096 x 4096, 1.1 / 1.6 / 1.5 % above the parent in two measurements out of two
+// (docs/LAB_NOTES_r45.md, section 4; the same registers and LDS, 12 % more code).  The epilogue policy is not the cause: the wrapper
+// compiles to the same code with EP taken out of the body (section 3 there).  scripts/compare_kernel_asm.py holds that file to its
+// text.  So the argument struct, the bodies and the workspace layout below are a copy, as qdq_matmul.hip's kernel is one of matmul_nbits.hip's; the guarded loads, the
 // correction terms and the epilogue (qlinear_epilogue.hpp) and the plan (tile_plan.hpp) are the one shared text.  The policy marks
 // the only places where the copy departs from the original.
 // What the tile is and how it is staged: qlinear_gemm.hip.
