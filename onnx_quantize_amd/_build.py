@@ -47,6 +47,7 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # qdq_function_packed4.hip: integer products, fp32 only in the epilogue and the Q -> DQ passes; the packed fp32 instructions are
 # switched off for it as well, from its first compile.
 # qdq_function_packed4_decode.hip: the same epilogue and Q -> DQ passes, held to the same bytes: the same flags.
+# qdq_function_decode.hip is held to the bytes of qdq_function.hip, which has no flags of its own: none here either.
 PER_FILE_FLAGS = {"hqq.hip": ("-fno-slp-vectorize",), "matmul_nbits.hip": ("-fno-slp-vectorize",),
                   "matmul_nbits_decode.hip": ("-fno-slp-vectorize",), "qdq_matmul.hip": ("-fno-slp-vectorize",),
                   "matmul_nbits_fzp.hip": ("-fno-slp-vectorize",),
@@ -74,7 +75,8 @@ def _deps_mtime() -> float:
     hdrs = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith((".hpp", ".h"))]
     hdrs.extend(os.path.join(ROOT, "include", h) for h in ("oq_hip.h", "oq_hip_half.h", "oq_hip_nbits.h", "oq_hip_nbits_decode.h", "oq_hip_nbits_fzp.h", "oq_hip_qlinear.h",
                                                            "oq_hip_qlinear_decode.h", "oq_hip_qlinear_function.h", "oq_hip_qdq.h", "oq_hip_qdq_function.h", "oq_hip_qdq_packed4.h",
-                                                           "oq_hip_qdq_function_packed4.h", "oq_hip_qdq_function_packed4_decode.h"))
+                                                           "oq_hip_qdq_function_packed4.h", "oq_hip_qdq_function_packed4_decode.h",
+                                                           "oq_hip_qdq_function_decode.h"))
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -76,7 +76,10 @@ def perplexity(model, input_ids, *, max_length: int = 2048, stride: int = 512, e
     memory and half the weight read; the same bytes of output, so the same perplexity).  ``qdq="fused+integer+packed4"`` is the
     two together: the calls with an input Q -> DQ read the packed nibbles on the int8 matrix cores (`ops.qdq_function_packed4`: the
     bytes of ``"fused+integer"``).  ``qdq="fused+integer+packed4+decode"`` sends those of them whose flattened input has at most 16
-    rows to `ops.qdq_function_packed4_decode` (the nibbles streamed once; the same bytes, so the same perplexity)."""
+    rows to `ops.qdq_function_packed4_decode` (the nibbles streamed once; the same bytes, so the same perplexity).
+    ``qdq="fused+integer+decode"`` does the same for the 8-bit weights of ``"fused+integer"``: calls of at most 16 rows run on
+    `ops.qdq_function_decode` (the [K, N] bytes streamed once; the same bytes), and ``"fused+integer+decode+packed4"`` has both
+    decode routes."""
     import torch
 
     from .graph_runner import GraphRunner

@@ -59,6 +59,8 @@ OQ_QDQ_PACKED4_EXTENSION_VERSION = 1
 OQ_QDQ_FUNCTION_PACKED4_EXTENSION_VERSION = 1
 # include/oq_hip_qdq_function_packed4_decode.h (the codes of oq_hip_qdq_function_packed4.h)
 OQ_QDQ_FUNCTION_PACKED4_DECODE_EXTENSION_VERSION = 1
+# include/oq_hip_qdq_function_decode.h (the codes of oq_hip_qdq_function.h)
+OQ_QDQ_FUNCTION_DECODE_EXTENSION_VERSION = 1
 
 
 class OqHipError(RuntimeError):
@@ -271,6 +273,14 @@ QDQ_FUNCTION_PACKED4_DECODE_PROTOTYPES = {
     "oq_qdq_function_packed4_decode": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function"],
 }
 
+# the decode route (M <= 16) of the 8-bit QDQ function: mirrors include/oq_hip_qdq_function_decode.h one to one
+# (tests/test_qdq_function_decode_abi.py checks the set).  The argument list of oq_qdq_function.
+QDQ_FUNCTION_DECODE_PROTOTYPES = {
+    "oq_qdq_function_decode_extension_version": (_i32, []),
+    "oq_qdq_function_decode_workspace_bytes": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function_workspace_bytes"],
+    "oq_qdq_function_decode": QDQ_FUNCTION_PROTOTYPES["oq_qdq_function"],
+}
+
 # what `load` binds and pins: (prototypes, the function that reports the version, the version this package expects, what the
 # message calls it)
 EXTENSIONS = [
@@ -289,6 +299,8 @@ EXTENSIONS = [
      "QDQ function packed-nibble extension"),
     (QDQ_FUNCTION_PACKED4_DECODE_PROTOTYPES, "oq_qdq_function_packed4_decode_extension_version", OQ_QDQ_FUNCTION_PACKED4_DECODE_EXTENSION_VERSION,
      "QDQ function packed-nibble decode extension"),
+    (QDQ_FUNCTION_DECODE_PROTOTYPES, "oq_qdq_function_decode_extension_version", OQ_QDQ_FUNCTION_DECODE_EXTENSION_VERSION,
+     "QDQ function decode extension"),
 ]
 
 _lock = threading.Lock()

@@ -1942,6 +1942,46 @@ def _qdq_function_call(entry: str, x, w, wtype: int, k: int, n: int, w_scale, w_
     return out.reshape(*x.shape[:-1], n)
 
 
+QDQ_FUNCTION_DECODE_MAX_ROWS = 16      # include/oq_hip_qdq_function_decode.h: M of the decode route
+_QDQ_FUNCTION_DECODE_WORKSPACE: dict = {}      # (M, K, N, x_mode, out_mode) -> oq_qdq_function_decode_workspace_bytes
+
+
+def qdq_function_decode_unsupported(x, w, w_scale, w_zero_point=None, *, x_mode, x_scale=None, x_zero_point=None, out_mode=None, out_scale=None,
+                                    out_zero_point=None, bias=None, rows: int | None = None) -> str | None:
+    """Why `qdq_function_decode` has no kernel for such a call (include/oq_hip_qdq_function_decode.h), or None when it has one: what
+    `qdq_function_unsupported` names, and more than 16 ``rows`` (None: those of the flattened ``x``)."""
+    why = qdq_function_unsupported(x, w, w_scale, w_zero_point, x_mode=x_mode, x_scale=x_scale, x_zero_point=x_zero_point, out_mode=out_mode,
+                                   out_scale=out_scale, out_zero_point=out_zero_point, bias=bias)
+    if why is not None:
+        return why
+    if rows is None:
+        rows = x.numel() // x.shape[-1] if x.shape[-1] else 0
+    if rows > QDQ_FUNCTION_DECODE_MAX_ROWS:
+        return f"{rows} rows (the decode route takes 1 ... {QDQ_FUNCTION_DECODE_MAX_ROWS}; qdq_function takes the rest)"
+    return None
+
+
+def qdq_function_decode(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, w_zero_point: torch.Tensor | None = None, *, x_mode: str,
+                        x_scale: torch.Tensor | None = None, x_zero_point: torch.Tensor | None = None, out_mode: str | None = None,
+                        out_scale: torch.Tensor | None = None, out_zero_point: torch.Tensor | None = None, bias=None) -> torch.Tensor:
+    """The decode route of `qdq_function` (`oq_qdq_function_decode`, csrc/qdq_function_decode.hip): the same operands, for an ``x``
+    whose ``reshape(-1, K)`` has 1 ... 16 rows.  The [K, N] bytes of ``w`` are streamed once from global memory into the registers
+    of the int8 matrix instruction; each workgroup quantizes its slice of ``x`` on the way into LDS, and the row and column sums of
+    the zero-point correction come from the same registers, so a static call is at most two launches.  The bytes of `qdq_function`.
+    Deterministic; nothing synchronises with the host.
+
+    NotImplementedError, naming the reason: more than 16 rows, and what `qdq_function` refuses."""
+    current = torch.cuda.current_device() if torch.cuda.is_available() else -1
+    _qdq_function_on_device(x, w, w_scale, w_zero_point, x_scale, x_zero_point, out_scale, out_zero_point, bias, current)
+    why = qdq_function_decode_unsupported(x, w, w_scale, w_zero_point, x_mode=x_mode, x_scale=x_scale, x_zero_point=x_zero_point, out_mode=out_mode,
+                                          out_scale=out_scale, out_zero_point=out_zero_point, bias=bias)
+    if why is not None:
+        raise NotImplementedError(f"qdq_function_decode: {why}")
+    return _qdq_function_call("oq_qdq_function_decode", x, w, _QDQ_WTYPE[w.dtype], int(w.shape[0]), int(w.shape[1]), w_scale, w_zero_point, x_mode,
+                              x_scale, x_zero_point, out_mode, out_scale, out_zero_point, bias, remembered=_QDQ_FUNCTION_DECODE_WORKSPACE,
+                              current=current)
+
+
 QDQ_FUNCTION_PACKED4_MAX_K = 561433      # include/oq_hip_qdq_function_packed4.h, `bounds`: 255 * 15 * K stays an int32
 
 

@@ -47,6 +47,11 @@ routes are asked about, in `qdq_function_calls`.  Which kernel takes a call foll
     "fused+integer+packed4+decode": as "fused+integer+packed4", and a call that would run on `ops.qdq_function_packed4` and whose
         flattened X has at most 16 rows runs on `ops.qdq_function_packed4_decode` instead (the nibbles streamed once, the same
         bytes), counted as "decode".
+    "fused+integer+decode": as "fused+integer", and a call that would run on `ops.qdq_function` and whose flattened X has at most 16
+        rows runs on `ops.qdq_function_decode` instead (the [K, N] bytes streamed once, the same bytes), counted as
+        "integer_decode".
+    "fused+integer+decode+packed4": "fused+integer+packed4+decode" and "fused+integer+decode" combined: a W held packed goes as
+        under the first, every other W as under the second.
 """
 from __future__ import annotations
 
@@ -64,7 +69,9 @@ QLINEAR_MODES = {"torch": ((), ()), "fused": (("fused",), ()), "fused+decode": (
 # ... -> (the routes of a QDQ function's product, the routes of a whole call of one with an input Q -> DQ)
 QDQ_MODES = {"torch": ((), ()), "fused": (("fused",), ()), "fused+integer": (("fused",), ("integer",)), "fused+packed4": (("fused", "packed4"), ()),
              "fused+integer+packed4": (("fused", "packed4"), ("integer", "packed4")),
-             "fused+integer+packed4+decode": (("fused", "packed4"), ("integer", "packed4", "decode"))}
+             "fused+integer+packed4+decode": (("fused", "packed4"), ("integer", "packed4", "decode")),
+             "fused+integer+decode": (("fused",), ("integer", "integer_decode")),
+             "fused+integer+decode+packed4": (("fused", "packed4"), ("integer", "integer_decode", "packed4", "decode"))}
 MATMUL_MODES = {"torch": False, "pieces": True}
 
 # route -> the `ops` function that runs it; `<that name>_unsupported` says what the kernel leaves out
@@ -72,7 +79,8 @@ _KERNELS = {"nbits": {"decode": "matmul_nbits_decode", "fused": "matmul_nbits", 
             "qlinear": {"decode": "qlinear_matmul_decode", "fused": "qlinear_matmul"},
             "qlinear_function": {"decode": "qlinear_function_decode", "function": "qlinear_function"},
             "qdq": {"packed4": "qdq_matmul_packed4", "fused": "qdq_matmul"},
-            "qdq_function": {"decode": "qdq_function_packed4_decode", "packed4": "qdq_function_packed4", "integer": "qdq_function"}}
+            "qdq_function": {"decode": "qdq_function_packed4_decode", "packed4": "qdq_function_packed4", "integer_decode": "qdq_function_decode",
+                             "integer": "qdq_function"}}
 
 _PIECES_MIN_WIDTH, _PIECES_MIN_ROWS = 512, 256
 
@@ -287,8 +295,8 @@ class Routes:
 
     def _run_qdq_function(self, fn, env):
         """One call of a QDQ function with an input Q -> DQ as one library call (`ops.qdq_function`; `ops.qdq_function_packed4` where
-        W is held as packed nibbles, or `ops.qdq_function_packed4_decode` where the mode has it and it takes the call): (route, the
-        function's outputs), or ("body", None) -- nothing was run -- where `_one_call`
+        W is held as packed nibbles; `ops.qdq_function_decode` / `ops.qdq_function_packed4_decode` in their places where the mode
+        has them and they take the call): (route, the function's outputs), or ("body", None) -- nothing was run -- where `_one_call`
         refuses, W, its scale or B is absent, or the kernel has no route for the call."""
         op, (x_mode, out_mode) = _QDQ[fn.name]
         names = ["W", "w_scale", "w_zero_point"] + (["B", "b_scale", "b_zero_point"] if op == "Gemm" else []) + \
@@ -302,8 +310,8 @@ class Routes:
         w, held = env["W"], self._packed4.value(env["W"])
         if held == ():                         # a 4-bit W this mode could not hold packed: no unpacked copy feeds the 8-bit kernel
             return "body", None
-        routes = ("integer",)
-        if held:                               # the decode kernel first where the mode has it: it refuses more than 16 rows by itself
+        routes = tuple(r for r in ("integer_decode", "integer") if r in self._qdq_function_routes)
+        if held:                               # the decode kernels first where the mode has them: they refuse more than 16 rows by themselves
             routes, (args["n"], args["signed"]) = tuple(r for r in ("decode", "packed4") if r in self._qdq_function_routes), held
         operands = (env["X"], w, env["w_scale"], env["w_zero_point"])
         route = first_route(routes, lambda r: _kernel("qdq_function", r)[1](*operands, **args) is None, "body")
